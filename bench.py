@@ -3,16 +3,22 @@
    passages/sec encode (bert-base, 128 tok -> 768-d) + queries/sec exact top-1000 over 8.8M x 768.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+  python bench.py ... --full                             (+ every leg and sub-object beyond the headline encode leg)
+  python bench.py ... --dump-outputs DIR                 (+ the last timed step's embeddings as DIR/p_reps.npy)
+
+A plain run times the headline encode leg and nothing else; `--full` adds the GEMM roofline pass, the search leg, the parity
+legs, the other formats, the packed / few-row / long-passage / training legs and the CPU baseline (the `--no-*` switches
+below drop single legs of a `--full` run).
 
 A *step* = one pass of the encoder hot path over one batch of synthetic MS-MARCO-shaped token
 ids already resident in HBM: ids -> embeddings+LN -> 12 x (QKV GEMM, fused attention, out-proj
 GEMM + residual, LN, FFN GEMMs + GELU, LN) -> CLS pooling -> 768-d embedding.  float16 MFMA with f32
 accumulation -- the reference's own 16-bit format (`--fp16` = torch.cuda.amp float16, retriever/dense_retriever.py:76,151;
 docs/dr-msmarco-passage.md:74) and the 16-bit mode whose dot products stay within `north_star`'s 1e-4 of the fp32 chain;
-`--precision bf16` runs the two-plane bfloat16 path (reported as the `bf16` sub-object of the default line).
+`--precision bf16` runs the two-plane bfloat16 path (reported as the `bf16` sub-object of the default `--full` line).
 Random-init bert-base weights.
 `value` = passages/s over all ranks (weak scaling: each rank encodes its own batches).
-The search leg (same process, after the encode leg) serves Q queries against an 8 841 823 x 768
+The search leg (`--full`; same process, after the encode leg) serves Q queries against an 8 841 823 x 768
 index sharded over the ranks: all-gather of query vectors -> per-shard filtered MFMA scan +
 top-1000 -> candidates exchanged by query range (all-to-all) and merged per slice (ids identical to the exact f32 scan).
 """
@@ -56,7 +62,14 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the f32 and training sub-objects")
     ap.add_argument("--precision", default="f16", choices=["bf16", "f16", "f32"],
                     help="compute format of the headline encode leg (default float16: the reference's --fp16 format)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline pass, search, parity, other formats, packed / few-row / long / training legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's passage embeddings (float32) to DIR/p_reps.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def synth_ids(batch, L, device, seed):
@@ -96,6 +109,21 @@ def max_over_ranks(x, world, device):
     t = torch.tensor([x], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(out_dir, reps, rank, world):
+    """What the timed path hands its caller in the last timed step -- DRModelForInference's `p_reps` -- as float32
+    DIR/p_reps.npy (rank r > 0 of a multi-rank run: DIR/p_reps_rank<r>.npy).  Beyond the byte budget a fixed seeded
+    sample of rows is kept, in row order."""
+    x = reps.detach().float().cpu().numpy()
+    cap = DUMP_BYTES // world // (x.shape[1] * 4)
+    if x.shape[0] > cap:
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], cap, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "p_reps.npy" if rank == 0 else "p_reps_rank%d.npy" % rank), x)
 
 
 def cpu_baseline(no_search, sample_batches):
@@ -533,48 +561,52 @@ def main():
     barrier_sync(world)
     t0 = time.perf_counter()
     for i in range(a.steps):
-        step(i)
+        reps = step(i)
     barrier_sync(world)
     t_enc = max_over_ranks(time.perf_counter() - t0, world, device)
     passages_per_s = world * a.batch * a.steps / t_enc
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, reps, rank, world)
+    peak = PEAK_BF16_TFLOPS if half else 157.3
 
     # second pass of the same K steps with every GEMM launch bracketed by HIP events
-    lib.om_kernel_timing_enable(1)
-    for i in range(a.steps):
-        step(i)
-    torch.cuda.synchronize()
-    ms, n_launch, flops = C.c_double(), C.c_int64(), C.c_double()
-    cls = 0 if half else 1
-    N.check(lib.om_kernel_timing_read(cls, C.byref(ms), C.byref(n_launch), C.byref(flops)))
-    lib.om_kernel_timing_enable(0)
-    gemm_tflops = flops.value / (ms.value * 1e-3) / 1e12 if ms.value > 0 else 0.0
-    peak = PEAK_BF16_TFLOPS if half else 157.3
-    traffic, tsrc = None, None   # HBM bytes per launch of the dominant kernel: the round's committed rocprofv3 --pmc passes of this command
-    tfile = os.path.join(REPO, "profiles", TRAFFIC_FILES.get(a.precision, ""))
-    if half and a.batch == 1024 and os.path.isfile(tfile):      # named per precision and round: a stale file is never picked up by sort order
-        try:
-            tj = json.load(open(tfile))
-            traffic, tsrc = tj["hbm_bytes_per_launch"], "profiles/" + os.path.basename(tfile) + ": " + tj.get("note", "")
-        except Exception:
-            traffic = None
-    roofline = {
-        "kernel": ("gemm_nt_kernel7c16 / gemm_nt_kernel7r16<%s>" % a.precision) if half else "gemm_nt_kernel6<f32>",
-        "kernel_note": (("persistent 256x256 tiles on a continuous five-unit LDS ring, 128-byte K steps, 16x16x32 MFMAs; the encoder's QKV / "
-                         "out-proj / FFN contractions with plain / GELU / LayerNorm-residual epilogues%s"
-                         % ("; bf16: the two-plane residual epilogue runs on gemm_nt_kernel7" if a.precision == "bf16" else ""))
-                        if half else "exact-f32 MFMA (32x32x2), k-ordered fmaf chain"),
-        "bound": "mfma", "achieved": round(gemm_tflops, 1), "peak": peak, "unit": "TFLOP/s",
-        "frac": round(gemm_tflops / peak, 4), "traffic": traffic,
-        "traffic_source": tsrc,
-        "launches": int(n_launch.value), "avg_launch_us": round(ms.value * 1e3 / max(n_launch.value, 1), 2),
-        "flops_per_launch": flops.value / max(n_launch.value, 1),
-        "measured": "hipEvents around every launch of the kernel on its stream, second pass of the same K steps",
-        "end_to_end_frac_of_peak": round(passages_per_s / world * GFLOP_PER_PASSAGE / 1e3 / peak, 4),
-    }
+    roofline = None
+    if a.full:
+        lib.om_kernel_timing_enable(1)
+        for i in range(a.steps):
+            step(i)
+        torch.cuda.synchronize()
+        ms, n_launch, flops = C.c_double(), C.c_int64(), C.c_double()
+        cls = 0 if half else 1
+        N.check(lib.om_kernel_timing_read(cls, C.byref(ms), C.byref(n_launch), C.byref(flops)))
+        lib.om_kernel_timing_enable(0)
+        gemm_tflops = flops.value / (ms.value * 1e-3) / 1e12 if ms.value > 0 else 0.0
+        traffic, tsrc = None, None   # HBM bytes per launch of the dominant kernel: the round's committed rocprofv3 --pmc passes of this command
+        tfile = os.path.join(REPO, "profiles", TRAFFIC_FILES.get(a.precision, ""))
+        if half and a.batch == 1024 and os.path.isfile(tfile):      # named per precision and round: a stale file is never picked up by sort order
+            try:
+                tj = json.load(open(tfile))
+                traffic, tsrc = tj["hbm_bytes_per_launch"], "profiles/" + os.path.basename(tfile) + ": " + tj.get("note", "")
+            except Exception:
+                traffic = None
+        roofline = {
+            "kernel": ("gemm_nt_kernel7c16 / gemm_nt_kernel7r16<%s>" % a.precision) if half else "gemm_nt_kernel6<f32>",
+            "kernel_note": (("persistent 256x256 tiles on a continuous five-unit LDS ring, 128-byte K steps, 16x16x32 MFMAs; the encoder's QKV / "
+                             "out-proj / FFN contractions with plain / GELU / LayerNorm-residual epilogues%s"
+                             % ("; bf16: the two-plane residual epilogue runs on gemm_nt_kernel7" if a.precision == "bf16" else ""))
+                            if half else "exact-f32 MFMA (32x32x2), k-ordered fmaf chain"),
+            "bound": "mfma", "achieved": round(gemm_tflops, 1), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(gemm_tflops / peak, 4), "traffic": traffic,
+            "traffic_source": tsrc,
+            "launches": int(n_launch.value), "avg_launch_us": round(ms.value * 1e3 / max(n_launch.value, 1), 2),
+            "flops_per_launch": flops.value / max(n_launch.value, 1),
+            "measured": "hipEvents around every launch of the kernel on its stream, second pass of the same K steps",
+            "end_to_end_frac_of_peak": round(passages_per_s / world * GFLOP_PER_PASSAGE / 1e3 / peak, 4),
+        }
 
     # ---------------- search leg -----------------------------------------------------------
     search, parity = None, None
-    if not a.no_search:
+    if a.full and not a.no_search:
         rows, offset = shard_range(a.index_rows, world, rank)
         index = FlatIPIndex(768, device=device, precision="f16_rescore" if half else "f32")
         g = torch.Generator(device=device).manual_seed(77 + rank)
@@ -649,13 +681,13 @@ def main():
             parity = parity_leg(model, lm, batches, device, index, q_local, a.topk, headline=a.precision)
         del index
         torch.cuda.empty_cache()
-    if parity is None and rank == 0 and not dist_on and not a.no_parity and half:
+    if a.full and parity is None and rank == 0 and not dist_on and not a.no_parity and half:
         parity = parity_leg(model, lm, batches, device, headline=a.precision)
 
     # ---------------- exact-f32 mode and the training step (sub-objects; N = 1 only) ----------
     f32_mode, train, f16_mode, packed_mode, few_rows, long_passages = None, None, None, None, None, None
     other16 = "bf16" if a.precision == "f16" else "f16"
-    if rank == 0 and not dist_on and not a.no_extra and half:
+    if a.full and rank == 0 and not dist_on and not a.no_extra and half:
         # the OTHER 16-bit format on the SAME timed batches (same kernels and MFMA rate): bfloat16 carries its pre-LayerNorm
         # residual stream in two planes to stay inside the reference's 16-bit envelope, float16 needs one
         m16 = DRModelForInference(lm_q=lm, lm_p=lm, pooling="first",
@@ -695,7 +727,7 @@ def main():
         train = train_leg(device)
 
     cpu = None
-    if rank == 0 and not dist_on and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not dist_on and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.no_search, batches)
 
     if rank == 0:
@@ -718,7 +750,7 @@ def main():
             # all-gathered, candidates exchanged by query range with one all-to-all + per-slice merge)
             "ranks": {"world": world, "rccl_ranks": rccl_ranks,
                       "encode": {"scaling": "weak", "passages_per_step": [a.batch] * world},
-                      "search": (None if a.no_search else
+                      "search": (None if a.no_search or not a.full else
                                  {"scaling": "strong" if world > 1 else "single shard",
                                   "index_rows": [shard_range(a.index_rows, world, r)[0] for r in range(world)],
                                   "query_slices": [shard_range(a.queries, world, r)[0] for r in range(world)]})},

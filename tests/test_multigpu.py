@@ -41,7 +41,7 @@ def test_bench_multi_rank_branches_on_two_gpus():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(repo, "bench.py"),
                         "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--index-rows", "40001",
-                        "--queries", "37", "--topk", "100", "--no-cpu-baseline"],
+                        "--queries", "37", "--topk", "100", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=repo)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -74,7 +74,7 @@ def test_bench_multi_rank_branches_on_a_one_rank_group():
         env["MASTER_PORT"] = str(s.getsockname()[1])
     repo = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--index-rows", "40001", "--queries", "37", "--topk", "100", "--no-cpu-baseline"],
+                        "--index-rows", "40001", "--queries", "37", "--topk", "100", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=repo)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

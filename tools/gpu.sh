@@ -31,7 +31,7 @@ validate)
   ;;
 prof)
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity "$@" > $O/prof.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-parity "$@" > $O/prof.log 2>&1
   cd $R; f=$(find $O/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && { cp "$f" $O/kernel_stats.csv; head -14 "$f" | cut -c1-170; }
   ;;
 pmc)
@@ -46,14 +46,14 @@ pmc)
   cd /tmp; i=0
   for c in "${passes[@]}"; do
     i=$((i+1))      # counters in their own run, kernel trace only (never with --sys-trace / hip / hsa / memory-copy domains)
-    timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc$i -- python $R/bench.py --steps 3 --warmup 1 $QUIET "$@" > $O/pmc$i.log 2>&1 || echo "pass $i failed"
+    timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc$i -- python $R/bench.py --steps 3 --warmup 1 --full $QUIET "$@" > $O/pmc$i.log 2>&1 || echo "pass $i failed"
   done
   cd $R; python tools/summarize_pmc.py $O > $O/pmc_summary.txt 2>&1; grep -A6 "gemm_nt_kernel7\|sim_filter_kernel7\|attention_fwd16" $O/pmc_summary.txt | head -80
   ;;
 ab)
   V=$1; shift
   for round in 1 2; do for val in "$@"; do
-    env $V=$val timeout 300 python bench.py --steps 10 --warmup 3 --no-search $QUIET > $O/bench_${val}_$round.json 2>$O/bench_${val}_$round.err
+    env $V=$val timeout 300 python bench.py --steps 10 --warmup 3 --full --no-search $QUIET > $O/bench_${val}_$round.json 2>$O/bench_${val}_$round.err
     echo "$V=$val $(grep -o '"value": [0-9.]*' $O/bench_${val}_$round.json | head -1) $(grep -o '"achieved": [0-9.]*' $O/bench_${val}_$round.json | head -1)"
   done; done
   ;;
