@@ -78,6 +78,19 @@ void om_debug_gemm_trace(unsigned long long* buf);
 /* Debug hook for A/B measurements inside one process: 0 = default tile-generation selection; 6 = never the persistent
  * generation 7 (gemm_wide7.h); 70 = generation 7 with one tile per workgroup (no cross-tile prefetch). */
 void om_debug_gemm_gen(int gen);
+/* Test hook: the kernel family of the last GEMM launcher the calling thread reached.  Each launcher stores its code; omk_gemm
+ * (under every om_gemm_nt call) stores 0 on entry, before any argument check, so an om_gemm_nt call that launches nothing --
+ * an error, an empty problem -- reads 0.  Internal callers that reach a launcher without omk_gemm only store their family.
+ * Lets a test assert that a case reached the family it names. */
+#define OM_GEMM_FAMILY_V1 1          /* gemm_nt_kernel: 128 x 128 tiles, any M, N                                  */
+#define OM_GEMM_FAMILY_V2 2          /* gemm_nt_kernel2: 256 x 128 tiles                                           */
+#define OM_GEMM_FAMILY_V6 6          /* gemm_nt_kernel6: 256 x 256 tiles (gemm_wide6_*.hip)                          */
+#define OM_GEMM_FAMILY_G7 7          /* gemm_nt_kernel7: persistent 256 x 256, the K ring restarts per tile         */
+#define OM_GEMM_FAMILY_G7_ONE_TILE 70 /* gemm_nt_kernel7 with one tile per workgroup (om_debug_gemm_gen(70))       */
+#define OM_GEMM_FAMILY_G7C16 71      /* gemm_nt_kernel7c16: continuous ring, no residual                            */
+#define OM_GEMM_FAMILY_G7R16 72      /* gemm_nt_kernel7r16: continuous ring, residual                               */
+#define OM_GEMM_FAMILY_SKINNY 9      /* gemm_skinny.hip: few rows, weight streaming                                 */
+int om_debug_gemm_last(void);
 /* Run-time switches for A/B measurements and tests (initialised from the environment variable of the same
  * name on first use): OM_OPT_ENCODER_FUSED_LN 1 = LayerNorm / RMSNorm fused across the encoder GEMMs where the
  * shapes allow (default), 0 = one normalisation kernel per site; OM_OPT_ENCODER_DEBUG 1 = log the path taken. */
@@ -144,6 +157,8 @@ void om_debug_gemm_gen(int gen);
                                       normalises its operand rows itself, the one that adds it re-derives the element (gemm_skinny.hip; same bits) */
 #define OM_OPT_COUNT 22
 int om_debug_option(int opt, int value);
+/* the current value of a run-time switch (OM_OPT_*), so a test can restore exactly what it changed; -1 for an unknown option */
+int om_debug_option_value(int opt);
 /* the attention kernel alone (bf16 qkv [B*L, 3H] -> ctx [B*L, H]; mask [B, L] int64), for timing: csrc/kernels.h omk_attention */
 int om_debug_attention(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, void* stream);
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly

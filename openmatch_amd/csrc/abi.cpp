@@ -134,6 +134,10 @@ extern "C" int om_debug_option(int opt, int value) {
   g_opt[opt].store(value);
   return 0;
 }
+extern "C" int om_debug_option_value(int opt) {
+  if (opt < 0 || opt >= OM_OPT_COUNT) { om_set_error("om_debug_option_value: unknown option"); return -1; }
+  return om_option(opt);
+}
 
 // T5 relative-position bucket table of a sequence length, resident on the device: built and uploaded ONCE per
 // (device, L, buckets, max distance) -- no pageable copy and no stream synchronisation on later forwards.

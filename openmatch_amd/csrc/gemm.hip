@@ -94,8 +94,12 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_nt_kernel2(
   if (tr && threadIdx.x == 0) { tr[28] = clock64(); tr[29] = blockIdx.x; }
 }
 
-OM_DEFINE_LAUNCHER(launch_gemm, gemm_nt_kernel, GEMM_THREADS, GEMM_LDS_BYTES, GEMM_BM, GEMM_BN)
-OM_DEFINE_LAUNCHER(launch_gemm2, gemm_nt_kernel2, G2_THREADS, G2_LDS_BYTES, G2_BM, G2_BN)
+static thread_local int g_gemm_last = 0;
+void omk_gemm_note(int family) { g_gemm_last = family; }
+extern "C" int om_debug_gemm_last(void) { return g_gemm_last; }
+
+OM_DEFINE_LAUNCHER(launch_gemm, gemm_nt_kernel, GEMM_THREADS, GEMM_LDS_BYTES, GEMM_BM, GEMM_BN, OM_GEMM_FAMILY_V1)
+OM_DEFINE_LAUNCHER(launch_gemm2, gemm_nt_kernel2, G2_THREADS, G2_LDS_BYTES, G2_BM, G2_BN, OM_GEMM_FAMILY_V2)
 
 static int gemm_variant() {     // OM_OPT_GEMM_VARIANT = 1|2|6 pins a kernel generation (A/B measurements; 0: automatic)
   return om_option(OM_OPT_GEMM_VARIANT);
@@ -144,6 +148,7 @@ int omk_gemm(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ld
              hipStream_t s) {
   GemmEpilogue ep = ep_in;
   ep.trace = g_trace;
+  g_gemm_last = 0;
   if (M <= 0 || N <= 0) return 0;
   if (K <= 0) OM_FAIL("K must be positive");
   const int64_t es = in_dtype == OM_F32 ? 4 : 2;

@@ -28,7 +28,7 @@ template <int ACT, bool FAST>
 __device__ __forceinline__ float act_apply(float x) {
   if (ACT == OM_ACT_GELU_ERF)
     return FAST ? gelu_erf_fast(x) : 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-  if (ACT == OM_ACT_RELU) return fmaxf(x, 0.0f);
+  if (ACT == OM_ACT_RELU) return x < 0.0f ? 0.0f : x;      // NaN stays NaN, as torch.relu (fmaxf gave 0: test_non_finite_values_propagate)
   if (ACT == OM_ACT_GELU_TANH) {
     // HF NewGELUActivation: 0.5x(1+tanh(sqrt(2/pi)(x+0.044715x^3)))
     const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
@@ -239,7 +239,7 @@ __device__ __forceinline__ void store_direct(const f32x16_t a00, const f32x16_t 
 }
 
 // ---- launchers -------------------------------------------------------------------------------------
-#define OM_DEFINE_LAUNCHER(NAME, KERNEL, THREADS, LDS, BMV, BNV)                                        \
+#define OM_DEFINE_LAUNCHER(NAME, KERNEL, THREADS, LDS, BMV, BNV, FAMILY)                                        \
   template <typename T, typename OutT>                                                                  \
   static int NAME(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,         \
                   int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {             \
@@ -253,6 +253,7 @@ __device__ __forceinline__ void store_direct(const f32x16_t a00, const f32x16_t 
     const int tclass = sizeof(T) == 2 ? OM_TIMING_GEMM_BF16 : OM_TIMING_GEMM_F32; /* f16 counts as 16-bit */ \
     const bool timing = om_timing_on();                                                                 \
     if (timing) om_timing_begin(tclass, s);                                                             \
+    omk_gemm_note(FAMILY);                                                                              \
     /* sweep order: 8 row tiles stay resident while the column tiles are walked (L2 reuse per XCD) */    \
     hipLaunchKernelGGL((KERNEL<T, OutT>), dim3((unsigned)nwg), dim3(THREADS), LDS, s, (const T*)A, lda,  \
                        (const T*)B, ldb, (OutT*)C, ldc, M, N, K, ep, 8);                                \

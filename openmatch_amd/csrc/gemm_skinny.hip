@@ -241,6 +241,7 @@ int launch_skinny_cfg(const void* A, int64_t lda, const void* W, int64_t ldw, vo
       attr_set = true;
     }
   }
+  omk_gemm_note(OM_GEMM_FAMILY_SKINNY);
   hipLaunchKernelGGL((gemm_nt_skinny_kernel<T, MT, NT, NW, LNA>), dim3((unsigned)(N / (16 * NT)), (unsigned)((M + 16 * MT - 1) / (16 * MT))),
                      dim3(64 * NW), lds, s, (const T*)A, lda, (const T*)W, ldw, (T*)C, ldc, (int)M, (int)N, (int)K, ep.bias,
                      (const T*)ep.resid, ep.ldr, act, mul, ep.resid32, ep.out32, ln);

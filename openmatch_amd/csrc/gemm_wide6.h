@@ -126,6 +126,7 @@ static int launch6(const void* A, int64_t lda, const void* B, int64_t ldb, void*
   const int tclass = sizeof(T) == 2 ? OM_TIMING_GEMM_BF16 : OM_TIMING_GEMM_F32;
   const bool timing = om_timing_on();
   if (timing) om_timing_begin(tclass, s);
+  omk_gemm_note(OM_GEMM_FAMILY_V6);
   // sweep order: 8 row tiles stay resident while the column tiles are walked (L2 reuse per XCD)
   hipLaunchKernelGGL((gemm_nt_kernel6<T, OutT, ACT, TRAIN, RESID, LNF>), dim3((unsigned)nwg), dim3(G6_THREADS), lds_bytes, s,
                      (const T*)A, lda, (const T*)B, ldb, (OutT*)C, ldc, M, N, K, ep, g6_group_m());

@@ -1443,6 +1443,7 @@ static int launch7c(const void* A, int64_t lda, const void* B, int64_t ldb, void
   const bool timing = om_timing_on();
   if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
   const int gm_arg = (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0) | g7_stagger_bits();
+  omk_gemm_note(OM_GEMM_FAMILY_G7C16);
   hipLaunchKernelGGL((gemm_nt_kernel7c16<T, ACT, LNF, TRAIN>), dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s,
                      (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, gm_arg);
   if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
@@ -1468,6 +1469,7 @@ static int launch7r(const void* A, int64_t lda, const void* B, int64_t ldb, void
   const bool timing = om_timing_on();
   if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
   const int gm_arg = (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0) | g7_stagger_bits();
+  omk_gemm_note(OM_GEMM_FAMILY_G7R16);
   hipLaunchKernelGGL((gemm_nt_kernel7r16<T, ACT, LNF>), dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s,
                      (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, gm_arg);
   if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
@@ -1508,6 +1510,7 @@ static int launch7(const void* A, int64_t lda, const void* B, int64_t ldb, void*
   }
   const bool timing = om_timing_on();
   if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
+  omk_gemm_note(OM_GEMM_FAMILY_G7);
   hipLaunchKernelGGL((gemm_nt_kernel7<T, ACT, RESID, LNF, true>), dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s,
                      (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0));
   if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);

@@ -35,6 +35,7 @@ int omk_gemm_wide7(bool persist, const void* A, int64_t lda, const void* B, int6
                                  hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));                          \
       attr_set = true;                                                                                                \
     }                                                                                                                 \
+    omk_gemm_note(OM_GEMM_FAMILY_G7_ONE_TILE);                                                                      \
     hipLaunchKernelGGL((gemm_nt_kernel7<bf16_t, A_, false, 0, false>), dim3((unsigned)ntiles), dim3(G6_THREADS), G7_LDS_BYTES, s, \
                        (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (bf16_t*)C, ldc, M, N, K, ep, 8);                \
     OM_LAUNCH_CHECK();                                                                                                \

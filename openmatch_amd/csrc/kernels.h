@@ -118,6 +118,8 @@ int omk_gemm_wide6_f32(int in_dtype, const void* A, int64_t lda, const void* B, 
 int omk_gemm(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype,
              void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep,
              hipStream_t s);
+// the kernel family (OM_GEMM_FAMILY_*) the calling thread's last omk_gemm launched: one host store per launch (om_debug_gemm_last)
+void omk_gemm_note(int family);
 
 // C (f32, pre-zeroed) += A · B^T with K sliced across workgroups (weight gradients)
 int omk_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C,

@@ -18,6 +18,9 @@ ARCH_BERT, ARCH_T5 = 0, 1
 POOL_NONE, POOL_FIRST, POOL_MEAN = 0, 1, 2
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
 OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
+OPT_GEMM_GROUP_M, OPT_GEMM_VARIANT, OPT_GEMM_SKINNY_M = 6, 12, 19
+# om_debug_gemm_last codes (include/openmatch_hip.h: OM_GEMM_FAMILY_*)
+GEMM_FAMILY = {"v1": 1, "v2": 2, "v6": 6, "g7": 7, "g7_one_tile": 70, "7c16": 71, "7r16": 72, "skinny": 9}
 SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
 ABI_VERSION = 5
 
@@ -99,6 +102,8 @@ _SIGNATURES = {
     "om_debug_gemm_trace": (None, [c_void_p]),
     "om_debug_gemm_gen": (None, [c_int]),
     "om_debug_option": (c_int, [c_int, c_int]),
+    "om_debug_option_value": (c_int, [c_int]),
+    "om_debug_gemm_last": (c_int, []),
     "om_debug_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "om_encoder_fold_bytes": (c_size_t, [C.POINTER(OmEncoderConfig)]),

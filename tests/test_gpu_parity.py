@@ -2596,14 +2596,14 @@ def test_pending_layernorms_of_a_handful_of_rows_give_the_bits_of_the_layernorm_
 @pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
 def test_few_row_contractions_on_the_weight_streaming_kernel(dtype):
     """gemm_skinny.hip (om_gemm_nt with M <= OM_OPT_GEMM_SKINNY_M rows, 16-bit): every epilogue the small forwards use -- bias,
-    erf-GELU / ReLU / tanh-GELU, residual added or multiplied (in place too) -- against torch in f32 on the same 16-bit operands;
+    erf-GELU / ReLU / tanh-GELU, residual added or multiplied (in place too) -- every element within the float64 bound of
+    tests/test_gemm_kernels.py on the same 16-bit operands;
     a row's bits do not depend on how many rows ride along; switched off, the tile kernels give the same numbers."""
     from openmatch_amd import native as N_
     td = getattr(torch, dtype)
     code = N_.OM_BF16 if dtype == "bfloat16" else N_.OM_F16
     lib = N_.lib()
     gen = torch.Generator().manual_seed(17)
-    tol = 2e-2 if dtype == "bfloat16" else 3e-3
 
     def run(A, W, bias, resid, act, M=None, inplace=False):
         M = A.shape[0] if M is None else M
@@ -2615,35 +2615,39 @@ def test_few_row_contractions_on_the_weight_streaming_kernel(dtype):
                                     N_.stream_ptr(torch.device(DEV))))
         return C
 
-    acts = {N_.ACT_NONE: lambda v: v, N_.ACT_GELU_ERF: torch.nn.functional.gelu, N_.ACT_RELU: torch.relu,
-            N_.ACT_GELU_TANH: lambda v: torch.nn.functional.gelu(v, approximate="tanh")}
+    from tests.test_gemm_kernels import error_bound, gemm_reference, violations
+
+    def within_bound(got, act, mode, bias, resid, K):
+        """every element within the float64 bound of tests/test_gemm_kernels.py (rounding, accumulation, activation fit)"""
+        r = None if mode == "plain" else resid
+        ref, acc, mag, y = gemm_reference(A, W, bias, r, act, mode == "mul")
+        bound = error_bound(acc, mag, y, r, act, mode == "mul", K, code)
+        bad = violations(got, ref, bound, code)
+        return int(bad.sum())
+
     for (M, Nn, K) in [(1, 768, 768), (5, 2304, 768), (32, 3072, 768), (33, 768, 3072), (64, 256, 256), (100, 768, 1024), (256, 3072, 768)]:
         A = (torch.randn(M, K, generator=gen) * 0.5).to(DEV, td)
         W = (torch.randn(Nn, K, generator=gen) * 0.05).to(DEV, td)
         bias = torch.randn(Nn, generator=gen).to(DEV)
         resid = torch.randn(M, Nn, generator=gen).to(DEV, td)
-        base = A.float() @ W.float().t()
-        for act, fn in acts.items():
+        for act in (N_.ACT_NONE, N_.ACT_GELU_ERF, N_.ACT_RELU, N_.ACT_GELU_TANH):
             for mode in ("plain", "add", "mul", "inplace"):
                 if mode == "mul" and act != N_.ACT_GELU_TANH:
                     continue
-                want = fn(base + bias)
-                if mode in ("add", "inplace"):
-                    want = want + resid.float()
-                elif mode == "mul":
-                    want = want * resid.float()
                 got = run(A, W, bias, None if mode == "plain" else resid, act | (N_.ACT_MUL_RESID if mode == "mul" else 0), inplace=mode == "inplace")
-                err = (got.float() - want).abs().max().item() / max(1.0, want.abs().max().item())
-                assert err < tol, (M, Nn, K, act, mode, err)
+                assert lib.om_debug_gemm_last() == N_.GEMM_FAMILY["skinny"], (M, Nn, K, act, mode)
+                assert within_bound(got, act, mode, bias, resid, K) == 0, (M, Nn, K, act, mode)
         full = run(A, W, bias, resid, N_.ACT_GELU_ERF)
         one = run(A, W, bias, resid, N_.ACT_GELU_ERF, M=1)
         assert torch.equal(one[:1], full[:1])                      # row 0 alone == row 0 of the batch, bit for bit
-        N_.check(lib.om_debug_option(19, 0))                        # OM_OPT_GEMM_SKINNY_M = 0: the tile kernels
+        before = lib.om_debug_option_value(N_.OPT_GEMM_SKINNY_M)
+        N_.check(lib.om_debug_option(N_.OPT_GEMM_SKINNY_M, 0))     # the tile kernels
         try:
             tiles = run(A, W, bias, resid, N_.ACT_GELU_ERF)
+            assert lib.om_debug_gemm_last() != N_.GEMM_FAMILY["skinny"]
         finally:
-            N_.check(lib.om_debug_option(19, 1024))
-        assert (tiles.float() - full.float()).abs().max().item() <= 2 * tol * max(1.0, full.float().abs().max().item())
+            N_.check(lib.om_debug_option(N_.OPT_GEMM_SKINNY_M, before))
+        assert within_bound(tiles, N_.ACT_GELU_ERF, "add", bias, resid, K) == 0, (M, Nn, K, "tiles")
 
 
 def test_fused_adamw_does_not_count_the_steps_the_loss_scaler_skipped():
