@@ -235,7 +235,7 @@ typedef struct OmEncoderConfig {
   int hidden;        /* H                                                         */
   int n_layers;
   int n_heads;
-  int head_dim;      /* 64                                                        */
+  int head_dim;      /* 64; BERT family: 32 or 64 (n_heads * head_dim == hidden)   */
   int ffn;           /* F                                                         */
   int vocab;
   int max_pos;       /* BERT position table rows                                  */

@@ -893,6 +893,8 @@ int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
                   const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
                   float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu) {
   if (B <= 0) return 0;
+  if (H == heads * 32) return omk_attention_d32(dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (cu && !(dtype == OM_F16 || (dtype == OM_BF16 && om_option(OM_OPT_ATTENTION_FAST))))
     OM_FAIL("packed rows: the 16-bit attention kernels");      // (with dropout too: the packed training forward, round 5; beyond 256 tokens: round 6)
   if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");

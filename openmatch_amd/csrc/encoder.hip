@@ -217,8 +217,11 @@ static int check_cfg(const OmEncoderConfig* c) {
   if (c->dtype == OM_F16 && c->arch == OM_ARCH_T5 && c->act != OM_ACT_RELU && c->act != OM_ACT_GELU_TANH)
     OM_FAIL("float16 mode: T5 feed-forwards with ReLU or tanh-GELU only");
   if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) OM_FAIL("unknown arch");
-  if (c->head_dim != 64 || c->n_heads * 64 != c->hidden)
-    OM_FAIL("only head_dim 64 with n_heads*64 == hidden is supported");
+  // BERT family: 32-wide heads (MiniLM-shaped encoders, attention_d32.hip) or 64-wide; T5 (and the monoT5 decoder): d_kv 64
+  if (c->arch == OM_ARCH_T5 && (c->head_dim != 64 || c->n_heads * 64 != c->hidden))
+    OM_FAIL("T5 encoders: only d_kv 64 with n_heads*64 == d_model is supported");
+  if ((c->head_dim != 32 && c->head_dim != 64) || c->n_heads * c->head_dim != c->hidden)
+    OM_FAIL("head_dim must be 32 or 64 with n_heads*head_dim == hidden");
   const int es = c->dtype == OM_F32 ? 4 : 2;
   if ((c->hidden * es) % 128 || (c->ffn * es) % 128) OM_FAIL("hidden/ffn rows must be multiples of 128 bytes");
   if (c->head_in > 0 && ((c->head_in * 4) % 128 || c->head_in != c->hidden)) OM_FAIL("head_in must equal hidden");

@@ -26,12 +26,15 @@ int omk_l2norm(const float* x, float* y, int64_t M, int D, hipStream_t s);
 int omk_t5_bias(const float* table, const int* lut, float* out, int L, int heads, hipStream_t s);
 
 // softmax(scale * Q K^T + mask [+ pos_bias]) V for every (batch, head); qkv is the fused
-// projection output [B*L, 3H] (q | k | v), ctx is [B*L, H].  L <= 256, head_dim == 64.
+// projection output [B*L, 3H] (q | k | v), ctx is [B*L, H].  L <= 1024, head_dim 32 or 64.
 int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
                   const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
                   float drop_p, uint64_t seed, hipStream_t s, int reverse = 0 /* batch rows last to first */,
                   const int* kmax = nullptr /* omk_mask_extent: per batch row, 1 + its last unmasked key (16-bit kernels skip the key tiles past it) */,
                   const int* cu = nullptr /* packed rows: sequence b occupies rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (L stays the mask's row pitch) */);
+// the same for 32-wide heads (H == heads * 32, attention_d32.hip): L <= 1024, no position bias; omk_attention sends such calls here
+int omk_attention_d32(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
+                      int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu);
 // packed rows (om_encoder_forward_packed): cu[0..B] = offsets of the sequences (kmax[b] rows each) clamped to `rows`, cu[B + 1] = the
 // unclamped token count; cls_rows[b] = min(cu[b], rows - 1); row_map[t] = b * L + position of packed row t, -1 for the pad rows
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);

@@ -186,9 +186,12 @@ int check_train_cfg(const OmEncoderConfig* c, int64_t L) {
   // since round 6 (ReLU / gated tanh-GELU feed-forwards; as under the reference's autocast nothing clamps -- a checkpoint whose feed-forward
   // activations leave the float16 range overflows there and here alike, the loss scaler skips such steps)
   if (c->dtype == OM_F16 && c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) OM_FAIL("float16 training: BERT-family and T5 encoders");
-  if (c->head_dim != 64 || c->n_heads * 64 != c->hidden) OM_FAIL("head_dim must be 64");
+  if (c->arch == OM_ARCH_T5 && (c->head_dim != 64 || c->n_heads * 64 != c->hidden)) OM_FAIL("T5 training: only d_kv 64 with n_heads*64 == d_model");
+  if ((c->head_dim != 32 && c->head_dim != 64) || c->n_heads * c->head_dim != c->hidden) OM_FAIL("head_dim must be 32 or 64 with n_heads*head_dim == hidden");
   if (L < 1 || L > 512) OM_FAIL("training supports sequence lengths up to 512");      // (257 .. 512: round 6, the tile-at-a-time attention kernels)
-  if (c->dtype == OM_F32 && L > 192) OM_FAIL("float32 training supports sequence lengths up to 192 (16-bit formats: 512)");
+  // 32-wide heads (attention_d32.hip): one backward kernel with a whole score row in registers, every format
+  if (c->head_dim == 32 && L > 256) OM_FAIL("training with head_dim 32 supports sequence lengths up to 256");
+  if (c->dtype == OM_F32 && L > 192 && c->head_dim != 32) OM_FAIL("float32 training supports sequence lengths up to 192 (16-bit formats: 512)");
   if (c->arch == OM_ARCH_BERT && c->act != OM_ACT_GELU_ERF) OM_FAIL("BERT training supports the erf-GELU FFN");
   if (c->arch == OM_ARCH_T5 && (c->act & 0xff) != OM_ACT_RELU && (c->act & 0xff) != OM_ACT_GELU_TANH)
     OM_FAIL("T5 training supports relu and gated gelu_new feed-forward layers");
@@ -463,7 +466,7 @@ extern "C" int om_encoder_train_packed_supported(const OmEncoderConfig* c, int64
   if (!c || B <= 0 || L <= 0 || packed_rows <= 0) return 0;
   if ((c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) || (c->dtype != OM_BF16 && c->dtype != OM_F16) || c->n_layers <= 0) return 0;      // (T5: round 6)
   if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255 || packed_rows >= B * L) return 0;
-  if (c->hidden % 256 || c->ffn % 256 || c->n_heads * 64 != c->hidden) return 0;
+  if (c->hidden % 256 || c->ffn % 256 || (c->n_heads * 64 != c->hidden && c->n_heads * 32 != c->hidden)) return 0;
   if (c->pooling != OM_POOL_FIRST && c->pooling != OM_POOL_MEAN) return 0;
   if (!om_option(OM_OPT_ATTENTION_FAST) || L > 256) return 0;
   if (c->arch == OM_ARCH_BERT && (size_t)c->ffn < (size_t)2 * c->hidden) return 0;      // (the f32 pooled tail borrows the [M, F] scratch)

@@ -1247,6 +1247,11 @@ int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const vo
                            int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
                            const float* pos_bias, float* drel, float* stats, hipStream_t s) {
   if (B <= 0) return 0;
+  if (H == heads * 32) {      // 32-wide heads: one kernel up to 256 tokens (it recomputes the statistics; ctx and stats are not needed)
+    if (pos_bias || drel) OM_FAIL("T5 position bias: head_dim 64 only");
+    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, nullptr);
+  }
+  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (L < 1 || L > 512) OM_FAIL("attention backward (tile-at-a-time form): up to 512 tokens");      // (taken from 257 on; below that only when a test forces it)
   if (H != heads * 64) OM_FAIL("head_dim must be 64");
   if (!ctx || !stats) OM_FAIL("attention backward beyond 256 tokens needs the forward's output and a statistics buffer (omk_attention_bwd_long_stats_bytes)");
@@ -1258,6 +1263,8 @@ int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const vo
 int omk_attention_bwd(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
                       int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
                       hipStream_t s, const int* cu) {
+  if (H == heads * 32) return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
+  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (cu) {           // packed rows (16-bit formats): the transposing-read kernel up to 128 tokens, the generic one up to 256
     if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("packed rows: attention backward for 16-bit formats");
     if (B <= 0) return 0;
@@ -1283,6 +1290,11 @@ int omk_attention_bwd_bias(int dtype, const void* qkv, const void* dctx, void* d
                            int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
                            const float* pos_bias, float* drel, hipStream_t s, const int* cu) {
   if (B <= 0) return 0;
+  if (H == heads * 32) {
+    if (pos_bias || drel) OM_FAIL("T5 position bias: head_dim 64 only");
+    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
+  }
+  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (cu && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("packed rows: attention backward for 16-bit formats");
   if (omk_attention_bwd16_ok(dtype, L, H, heads) && (pos_bias != nullptr) == (drel != nullptr))      // (with the T5 bias too since round 6)
     return omk_attention_bwd16(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
