@@ -29,7 +29,8 @@
 extern "C" {
 #endif
 
-#define OM_ABI_VERSION 5   /* 5 (round 5): om_grad_sqnorm, om_adamw_step, om_loss_scale_update, om_encoder_packed_supported; OM_F16 training */
+#define OM_ABI_VERSION 6   /* 6: OM_ARCH_MODERNBERT; rope / sliding-window fields appended to OmEncoderConfig, final_ln_b to OmEncoderWeights
+                    * 5 (round 5): om_grad_sqnorm, om_adamw_step, om_loss_scale_update, om_encoder_packed_supported; OM_F16 training */
 
 /* element types */
 #define OM_F32 0
@@ -48,6 +49,11 @@ extern "C" {
 /* encoder architecture */
 #define OM_ARCH_BERT 0 /* HF:models/bert/modeling_bert.py  BertModel       */
 #define OM_ARCH_T5 1   /* HF:models/t5/modeling_t5.py      T5EncoderModel  */
+#define OM_ARCH_MODERNBERT 2 /* HF:models/modernbert/modeling_modernbert.py  ModernBertModel (inference only):
+                              * word embedding + LayerNorm; per layer x += Wo(attn(rope(Wqkv(LN1(x))))) (layer 0: no LN1,
+                              * ln1_g == NULL), x += W2(gelu_erf(W1 LN2(x)) * Wg LN2(x)); final LayerNorm.  LayerNorm biases
+                              * optional (norm_bias), no linear biases.  Attention at 1/sqrt(64) with rotary Q/K (rope_theta_global /
+                              * rope_theta_local); layers flagged in sliding_layers see keys |q - k| <= half_window only. */
 
 /* pooling — modeling/dense_retrieval_model.py:145-150 */
 #define OM_POOL_NONE 0
@@ -216,11 +222,11 @@ typedef struct OmLayerWeights {
   const float* qkv_b;  /* [3H] or NULL (T5)                                       */
   const void* o_w;     /* [H,H]                                                   */
   const float* o_b;    /* [H] or NULL                                             */
-  const float* ln1_g;  /* BERT: attention.output.LayerNorm ; T5: layer[0].layer_norm */
+  const float* ln1_g;  /* BERT: attention.output.LayerNorm ; T5: layer[0].layer_norm ; ModernBERT: attn_norm (NULL in layer 0) */
   const float* ln1_b;  /* NULL for T5 (RMSNorm)                                   */
   const void* ffn1_w;  /* [F,H]   BERT intermediate.dense / T5 wi (wi_0 if gated) */
   const float* ffn1_b; /* [F] or NULL                                             */
-  const void* ffn1g_w; /* [F,H]   T5 v1.1 wi_1 (linear gate) or NULL              */
+  const void* ffn1g_w; /* [F,H]   T5 v1.1 wi_1 (linear gate) or NULL ; ModernBERT: Wi rows F..2F-1 (ffn1_w: rows 0..F-1) */
   const void* ffn2_w;  /* [H,F]                                                   */
   const float* ffn2_b; /* [H] or NULL                                             */
   const float* ln2_g;  /* BERT: output.LayerNorm ; T5: layer[1].layer_norm        */
@@ -248,19 +254,25 @@ typedef struct OmEncoderConfig {
   int head_in;       /* LinearHead input dim  (0 = no head)                       */
   int head_out;      /* LinearHead output dim                                     */
   int normalize;     /* F.normalize(reps, dim=1)                                  */
+  /* ---- ABI v6, OM_ARCH_MODERNBERT only (zero for BERT / T5) ---- */
+  float rope_theta_global; /* rope_parameters["full_attention"]["rope_theta"] (160 000)     */
+  float rope_theta_local;  /* rope_parameters["sliding_attention"]["rope_theta"] (10 000)   */
+  int half_window;         /* local_attention // 2: key k visible from query q iff |q - k| <= half_window (sliding layers) */
+  uint64_t sliding_layers; /* bit l set: layer l is a sliding-window layer (config.layer_types[l] == "sliding_attention") */
 } OmEncoderConfig;
 
 typedef struct OmEncoderWeights {
   const float* word_emb;  /* [vocab,H] f32                                        */
   const float* pos_emb;   /* [max_pos,H] f32 (BERT)                               */
   const float* type_emb;  /* [type_vocab,H] f32 (BERT)                            */
-  const float* emb_ln_g;  /* BERT embeddings.LayerNorm                            */
+  const float* emb_ln_g;  /* BERT embeddings.LayerNorm ; ModernBERT embeddings.norm */
   const float* emb_ln_b;
   const OmLayerWeights* layers_host; /* HOST array [n_layers] of device pointers  */
-  const float* final_ln_g; /* T5 final_layer_norm.weight                          */
+  const float* final_ln_g; /* T5 final_layer_norm.weight ; ModernBERT final_norm.weight */
   const float* rel_bias;   /* T5 block[0] relative_attention_bias [buckets,heads] f32 */
   const float* head_w;     /* LinearHead weight [head_out,head_in] f32, or NULL   */
   const void* folded;      /* LayerNorm-folded weights made by om_encoder_fold_weights (ABI v4), or NULL: folded per forward */
+  const float* final_ln_b; /* ModernBERT final_norm.bias, or NULL (norm_bias = False) (ABI v6)                          */
 } OmEncoderWeights;
 
 /* LayerNorm / RMSNorm folded into the weights that consume the normalised tensor (the 16-bit fused path): size of the

@@ -225,10 +225,15 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void embed_kernel(
       if (j < nvec && c < H) {
         float w[4], ty[4], p[4];
         Vec4<float>::load(word + id * H + c, w);
-        Vec4<float>::load(type + tt * H + c, ty);
-        Vec4<float>::load(pos + (int64_t)t * H + c, p);
+        if (type) {
+          Vec4<float>::load(type + tt * H + c, ty);
+          Vec4<float>::load(pos + (int64_t)t * H + c, p);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[j][e] = (w[e] + ty[e]) + p[e];
+          for (int e = 0; e < 4; ++e) v[j][e] = (w[e] + ty[e]) + p[e];
+        } else {                   // ModernBERT: LayerNorm of the word embedding alone (no position or token-type table)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[j][e] = w[e];
+        }
       }
     }
     norm_and_store<TOut, MAX_VEC>(v, nvec, lane, H, g, b, eps, 0, out + orow * H, out32 ? out32 + orow * H : nullptr);

@@ -1,4 +1,4 @@
-// om_encoder_forward: the whole eval-mode encoder (BERT post-LN or T5 pre-RMSNorm stack)
+// om_encoder_forward: the whole eval-mode encoder (BERT post-LN, T5 pre-RMSNorm or ModernBERT pre-LN stack)
 // + pooling + LinearHead + normalise, as a fixed sequence of launches on ONE stream.
 // Stands in for DRModel.encode (modeling/dense_retrieval_model.py:133-155) and the HF model
 // it calls (HF:models/bert/modeling_bert.py:623-684 / HF:models/t5/modeling_t5.py T5Stack).
@@ -8,7 +8,7 @@
 //   y   [M,H]   pre-LayerNorm sum (BERT) / normed input (T5)
 //   x1  [M,H]   post-attention hidden (BERT)
 //   qkv [M,3H]  fused projection      ctx [M,H] attention output
-//   ff  [M,F]   FFN inner activation  ff2 [M,F] gate (T5 v1.1 only)
+//   ff  [M,F]   FFN inner activation  ff2 [M,F] gate (T5 v1.1, ModernBERT)
 #include <math.h>
 
 #include <stdlib.h>
@@ -42,8 +42,8 @@ FoldLayout fold_layout(const OmEncoderConfig* c) {
   L.total = off * (size_t)c->n_layers;
   return L;
 }
-bool fold_applies(const OmEncoderConfig* c) {
-  return (c->dtype == OM_BF16 || c->dtype == OM_F16) && c->n_layers > 0 && c->hidden % 256 == 0 && c->ffn % 256 == 0;
+bool fold_applies(const OmEncoderConfig* c) {      // (ModernBERT runs no fused normalisation: nothing to fold)
+  return c->arch != OM_ARCH_MODERNBERT && (c->dtype == OM_BF16 || c->dtype == OM_F16) && c->n_layers > 0 && c->hidden % 256 == 0 && c->ffn % 256 == 0;
 }
 }  // namespace
 
@@ -131,7 +131,7 @@ static EncWs carve(const OmEncoderConfig* c, int64_t B, int64_t L, char* base, i
   w.qkv = take(M * 3 * H * es);
   w.ctx = take(M * H * es);
   w.ff = take(M * F * es);
-  w.ff2 = take(c->arch == OM_ARCH_T5 ? M * F * es : 0);
+  w.ff2 = take(c->arch == OM_ARCH_T5 || c->arch == OM_ARCH_MODERNBERT ? M * F * es : 0);
   w.pooled = (float*)take((size_t)B * H * 4);
   w.headout = (float*)take((size_t)B * (c->head_out > 0 ? c->head_out : 1) * 4);
   w.posbias = (float*)take(c->arch == OM_ARCH_T5 ? (size_t)c->n_heads * L * L * 4 : 0);
@@ -141,7 +141,7 @@ static EncWs carve(const OmEncoderConfig* c, int64_t B, int64_t L, char* base, i
   w.cls_rows = (int*)take(packed_rows > 0 ? (size_t)B * 4 : 0);
   w.row_map = (int*)take(packed_rows > 0 ? (size_t)packed_rows * 4 : 0);
   w.final32 = (float*)take(half && c->pooling != OM_POOL_NONE ? (c->pooling == OM_POOL_FIRST ? (size_t)B : Mreal) * H * 4 : 0);
-  const bool fuse = half;                             // fused-norm path (BERT LayerNorm / T5 RMSNorm)
+  const bool fuse = half && c->arch != OM_ARCH_MODERNBERT;   // fused-norm path (BERT LayerNorm / T5 RMSNorm; ModernBERT has none)
   const size_t wide = std::max((size_t)3 * H, F);
   w.wfold = take(fuse ? wide * H * es : 0);
   w.colsum = (float*)take(fuse ? wide * 4 : 0);
@@ -216,7 +216,15 @@ static int check_cfg(const OmEncoderConfig* c) {
   if (c->dtype == OM_F16 && c->arch == OM_ARCH_BERT && c->act != OM_ACT_GELU_ERF) OM_FAIL("float16 mode: erf-GELU BERT-family encoders only");
   if (c->dtype == OM_F16 && c->arch == OM_ARCH_T5 && c->act != OM_ACT_RELU && c->act != OM_ACT_GELU_TANH)
     OM_FAIL("float16 mode: T5 feed-forwards with ReLU or tanh-GELU only");
-  if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) OM_FAIL("unknown arch");
+  if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5 && c->arch != OM_ARCH_MODERNBERT) OM_FAIL("unknown arch");
+  // ModernBERT (inference): 64-wide heads, the gated erf-GELU feed-forward (float16 included), at most 64 layers (sliding_layers bits)
+  if (c->arch == OM_ARCH_MODERNBERT) {
+    if (c->head_dim != 64 || c->n_heads * 64 != c->hidden) OM_FAIL("ModernBERT: only head_dim 64 with n_heads*64 == hidden is supported");
+    if (c->act != OM_ACT_GELU_ERF) OM_FAIL("ModernBERT: hidden_activation must be \"gelu\" (erf)");
+    if (c->n_layers > 64) OM_FAIL("ModernBERT: at most 64 layers");
+    if (!(c->rope_theta_global > 0.f) || !(c->rope_theta_local > 0.f) || c->half_window < 0)
+      OM_FAIL("ModernBERT: positive rope thetas and a non-negative half window");
+  }
   // BERT family: 32-wide heads (MiniLM-shaped encoders, attention_d32.hip) or 64-wide; T5 (and the monoT5 decoder): d_kv 64
   if (c->arch == OM_ARCH_T5 && (c->head_dim != 64 || c->n_heads * 64 != c->hidden))
     OM_FAIL("T5 encoders: only d_kv 64 with n_heads*64 == d_model is supported");
@@ -497,6 +505,57 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
       }
     }
     if (c->n_layers == 0) final_hidden = ws.x;
+  } else if (c->arch == OM_ARCH_MODERNBERT) {
+    // ModernBERT (HF:models/modernbert/modeling_modernbert.py ModernBertModel.forward): the unfused pre-norm loop of T5 below with
+    // LayerNorms (optional biases), no norm before layer 0's attention, rotary Q / K, a sliding window on the layers flagged in
+    // sliding_layers, and the GeGLU feed-forward gelu_erf(Wi[:F] x) * Wi[F:] x as two contractions over the one packed Wi.
+    if (packed) OM_FAIL("packed rows: not for ModernBERT (om_encoder_packed_supported is 0)");
+    if (!w->emb_ln_g || !w->final_ln_g) OM_FAIL("ModernBERT needs emb_ln_g and final_ln_g");
+    RUN(omk_embed(dt, input_ids, nullptr, w->word_emb, nullptr, nullptr, w->emb_ln_g, w->emb_ln_b, ws.x, M, (int)L, H, c->vocab, 1,
+                  c->ln_eps, 1, s));
+    const float scale = 1.0f / sqrtf((float)c->head_dim);
+    for (int l = 0; l < c->n_layers; ++l) {
+      const OmLayerWeights& lw = Ls[l];
+      if (!lw.ffn1g_w) OM_FAIL("ModernBERT layers need the gate half of Wi (ffn1g_w)");
+      const void* a_in = ws.x;
+      if (lw.ln1_g) {                                                        // attn_norm (nn.Identity in layer 0)
+        RUN(omk_layernorm(dt, ws.x, H, ws.y, H, lw.ln1_g, lw.ln1_b, M, H, c->ln_eps, 0, s));
+        a_in = ws.y;
+      }
+      GEMM(a_in, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, lw.qkv_b, nullptr, 0, OM_ACT_NONE);
+      const bool sliding = ((c->sliding_layers >> l) & 1) != 0;
+      RUN(omk_rope(dt, ws.qkv, M, (int)L, H, sliding ? c->rope_theta_local : c->rope_theta_global, s));
+      if (sliding)
+        RUN(omk_attention_band(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, H, nh, scale, c->half_window, ws.kmax, s));
+      else
+        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
+      GEMM(ws.ctx, H, lw.o_w, H, ws.x, H, H, H, lw.o_b, ws.x, H, OM_ACT_NONE);        // x += Wo(ctx)
+      RUN(omk_layernorm(dt, ws.x, H, ws.y, H, lw.ln2_g, lw.ln2_b, M, H, c->ln_eps, 0, s));
+      GEMM(ws.y, H, lw.ffn1g_w, H, ws.ff2, F, F, H, nullptr, nullptr, 0, OM_ACT_NONE);
+      GEMM(ws.y, H, lw.ffn1_w, H, ws.ff, F, F, H, lw.ffn1_b, ws.ff2, F, c->act | OM_ACT_MUL_RESID);
+      GEMM(ws.ff, F, lw.ffn2_w, F, ws.x, H, H, F, lw.ffn2_b, ws.x, H, OM_ACT_NONE);    // x += Wo(mlp)
+    }
+    // final_norm: in f32 for the pooled rows of a 16-bit run (as the other stacks)
+    const float* fg = w->final_ln_g;
+    const float* fb = w->final_ln_b;
+    if (dt != OM_F32 && !out_hidden && c->pooling == OM_POOL_FIRST) {
+      RUN(omk_layernorm_f32out(dt, ws.x, L * H, ws.final32, H, fg, fb, B, H, c->ln_eps, 0, s));
+      final32_rows = B;
+    } else if (dt != OM_F32 && !out_hidden && c->pooling != OM_POOL_NONE) {
+      RUN(omk_layernorm_f32out(dt, ws.x, H, ws.final32, H, fg, fb, M, H, c->ln_eps, 0, s));
+      final32_rows = M;
+    } else {
+      void* dst = out_hidden ? out_hidden : (void*)ws.y;
+      RUN(omk_layernorm(dt, ws.x, H, dst, H, fg, fb, M, H, c->ln_eps, 0, s));
+      final_hidden = (char*)dst;
+      if (dt != OM_F32 && c->pooling == OM_POOL_FIRST) {
+        RUN(omk_layernorm_f32out(dt, ws.x, L * H, ws.final32, H, fg, fb, B, H, c->ln_eps, 0, s));
+        final32_rows = B;
+      } else if (dt != OM_F32 && c->pooling != OM_POOL_NONE) {
+        RUN(omk_layernorm_f32out(dt, ws.x, H, ws.final32, H, fg, fb, M, H, c->ln_eps, 0, s));
+        final32_rows = M;
+      }
+    }
   } else {
     // relative-position bias, shared by all layers (table lives in block 0)
     if (!w->rel_bias || !w->final_ln_g) OM_FAIL("T5 needs rel_bias and final_ln_g");

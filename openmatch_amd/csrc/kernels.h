@@ -35,6 +35,12 @@ int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
 // the same for 32-wide heads (H == heads * 32, attention_d32.hip): L <= 1024, no position bias; omk_attention sends such calls here
 int omk_attention_d32(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
                       int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu);
+// ModernBERT (attention_band.hip, head_dim 64, inference): rotary positions on the Q and K columns of qkv in place (position = row % L,
+// one device cos / sin table per theta), and attention where key k is visible from query q only if |q - k| <= w and k is unmasked
+// (w <= 0 or w >= L - 1: omk_attention).  Key chunks outside a query block's band are not visited.
+int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s);
+int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
+                       int w, const int* kmax, hipStream_t s);
 // packed rows (om_encoder_forward_packed): cu[0..B] = offsets of the sequences (kmax[b] rows each) clamped to `rows`, cu[B + 1] = the
 // unclamped token count; cls_rows[b] = min(cu[b], rows - 1); row_map[t] = b * L + position of packed row t, -1 for the pad rows
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);

@@ -1,4 +1,4 @@
-"""Host side of the HIP encoder: turns a HF `BertModel` / `T5EncoderModel` (the parameter
+"""Host side of the HIP encoder: turns a HF `BertModel` / `T5EncoderModel` / `ModernBertModel` (the parameter
 container the reference keeps in `DRModel.lm_q / lm_p`) into the packed device weights that
 `om_encoder_forward` consumes, and launches it.
 
@@ -44,6 +44,8 @@ def inference_code(model, code, seq_len):
     if code != N.OM_F16:
         return code
     cfg = getattr(model, "config", None)
+    if _arch_of(model) == "modernbert":          # the GeGLU feed-forward with erf-GELU: float16 as for erf-GELU BERT
+        return code if getattr(cfg, "hidden_activation", None) == "gelu" else N.OM_BF16
     if _arch_of(model) == "t5":
         ok = _ACT.get(getattr(cfg, "dense_act_fn", None)) in (N.ACT_RELU, N.ACT_GELU_TANH) and os.environ.get("OM_T5_F16", "1") != "0"
         return code if ok else N.OM_BF16
@@ -120,12 +122,14 @@ def _arch_of(model):
     name = type(model).__name__
     if "T5" in name:
         return "t5"
+    if name.startswith("ModernBert"):    # ModernBertModel: pre-LayerNorm stack with rotary positions and sliding-window layers
+        return "modernbert"
     if name.startswith("Bert") or "Bert" in name and "Roberta" not in name:
         return "bert"
     if "Roberta" in name:          # RobertaModel, XLMRobertaModel: the BERT stack behind offset position ids
         return "bert"
     raise NotImplementedError(
-        f"openmatch_amd has HIP encoders for BERT / RoBERTa and T5-encoder backbones; got {name}")
+        f"openmatch_amd has HIP encoders for BERT / RoBERTa, T5-encoder and ModernBERT backbones; got {name}")
 
 
 def position_offset(model):
@@ -243,6 +247,72 @@ def _pack_t5(model, code, device):
     return pk
 
 
+def modernbert_config_fields(cfg):
+    """The ModernBERT-only OmEncoderConfig fields of a `ModernBertConfig`: the two rope thetas, the half window and the per-layer
+    sliding flags (bit l: config.layer_types[l] == "sliding_attention"), after refusing what the HIP encoder does not serve."""
+    if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
+        raise NotImplementedError("ModernBERT with attention_bias / mlp_bias = True is not supported by the HIP encoder")
+    if cfg.hidden_size % cfg.num_attention_heads or cfg.hidden_size // cfg.num_attention_heads != 64:
+        raise NotImplementedError(f"ModernBERT: only head_dim 64 is supported (got {cfg.hidden_size} / {cfg.num_attention_heads} heads)")
+    if cfg.hidden_activation != "gelu":
+        raise NotImplementedError(f"ModernBERT: hidden_activation must be 'gelu' (erf); got {cfg.hidden_activation!r}")
+    types = list(cfg.layer_types)
+    if len(types) != cfg.num_hidden_layers or any(t not in ("full_attention", "sliding_attention") for t in types):
+        raise NotImplementedError(f"ModernBERT layer_types must name full_attention / sliding_attention per layer; got {types}")
+    if len(types) > 64:
+        raise NotImplementedError("ModernBERT: at most 64 layers")
+    rp = cfg.rope_parameters
+    for kind in ("full_attention", "sliding_attention"):
+        if rp[kind].get("rope_type", "default") != "default":
+            raise NotImplementedError(f"ModernBERT: only default rope is supported (got {rp[kind]['rope_type']!r} for {kind})")
+    mask = 0
+    for i, t in enumerate(types):
+        if t == "sliding_attention":
+            mask |= 1 << i
+    return dict(rope_theta_global=float(rp["full_attention"]["rope_theta"]),
+                rope_theta_local=float(rp["sliding_attention"]["rope_theta"]),
+                half_window=int(cfg.local_attention) // 2, sliding_layers=mask)
+
+
+def _pack_modernbert(model, code, device):
+    cfg = model.config
+    extra = modernbert_config_fields(cfg)
+    wd = torch_dtype_of(code)
+    f32 = torch.float32
+    pk = _Packed()
+    w = pk.weights
+    opt = lambda t: pk.dev(t, f32, device) if t is not None else None       # noqa: E731  (norm_bias = False: no bias)
+    w.word_emb = pk.dev(model.embeddings.tok_embeddings.weight, f32, device)
+    w.emb_ln_g = pk.dev(model.embeddings.norm.weight, f32, device)
+    w.emb_ln_b = opt(model.embeddings.norm.bias)
+    w.final_ln_g = pk.dev(model.final_norm.weight, f32, device)
+    w.final_ln_b = opt(model.final_norm.bias)
+    F = cfg.intermediate_size
+    layers = (N.OmLayerWeights * cfg.num_hidden_layers)()
+    for i, layer in enumerate(model.layers):
+        lw = layers[i]
+        lw.qkv_w = pk.dev(layer.attn.Wqkv.weight, wd, device)               # rows q | k | v already
+        lw.o_w = pk.dev(layer.attn.Wo.weight, wd, device)
+        if isinstance(layer.attn_norm, torch.nn.LayerNorm):                   # (nn.Identity in layer 0)
+            lw.ln1_g = pk.dev(layer.attn_norm.weight, f32, device)
+            lw.ln1_b = opt(layer.attn_norm.bias)
+        lw.ln2_g = pk.dev(layer.mlp_norm.weight, f32, device)
+        lw.ln2_b = opt(layer.mlp_norm.bias)
+        wi = pk.dev(layer.mlp.Wi.weight, wd, device)                          # [2F, H]: input rows 0..F-1, gate rows F..2F-1
+        lw.ffn1_w = wi
+        lw.ffn1g_w = wi + F * cfg.hidden_size * torch.finfo(wd).bits // 8
+        lw.ffn2_w = pk.dev(layer.mlp.Wo.weight, wd, device)
+    pk.layers = layers
+    w.layers_host = C.cast(layers, C.POINTER(N.OmLayerWeights))
+    pk.cfg = dict(arch=N.ARCH_MODERNBERT, dtype=code, hidden=cfg.hidden_size, n_layers=cfg.num_hidden_layers,
+                  n_heads=cfg.num_attention_heads, head_dim=64, ffn=F, vocab=cfg.vocab_size, max_pos=0, type_vocab=0,
+                  act=N.ACT_GELU_ERF, ln_eps=float(cfg.norm_eps), rel_buckets=0, rel_max_dist=0, **extra)
+    return pk
+
+
+_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert}
+
+
 def _pack_t5_decoder(model, code, device):
     """Decoder-side weights of a T5Model / T5ForConditionalGeneration for om_t5_decoder_step (one decoder position:
     self-attention needs only v, o; cross-attention k | v fused to [2H, H])."""
@@ -310,7 +380,7 @@ def packed_weights(model, head, code, device):
         return hit[1]
     if hit is not None:
         hit[1].retired = True                   # its buffers are no longer anyone's weights: optimizers stop refreshing them
-    pk = _pack_bert(model, code, device) if _arch_of(model) == "bert" else _pack_t5(model, code, device)
+    pk = _PACKERS[_arch_of(model)](model, code, device)
     pk.owner_cache, pk.owner_key = cache, key
     if head is not None:
         lin = head.linear

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libopenmatch_hip.so")
 OM_F32, OM_BF16, OM_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_GELU_TANH = 0, 1, 2, 3
 ACT_MUL_RESID = 0x100
-ARCH_BERT, ARCH_T5 = 0, 1
+ARCH_BERT, ARCH_T5, ARCH_MODERNBERT = 0, 1, 2
 POOL_NONE, POOL_FIRST, POOL_MEAN = 0, 1, 2
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
 OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
@@ -22,7 +22,7 @@ OPT_GEMM_GROUP_M, OPT_GEMM_VARIANT, OPT_GEMM_SKINNY_M = 6, 12, 19
 # om_debug_gemm_last codes (include/openmatch_hip.h: OM_GEMM_FAMILY_*)
 GEMM_FAMILY = {"v1": 1, "v2": 2, "v6": 6, "g7": 7, "g7_one_tile": 70, "7c16": 71, "7r16": 72, "skinny": 9}
 SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 c_void_p, c_int, c_int64, c_float, c_size_t = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -38,14 +38,17 @@ class OmEncoderConfig(C.Structure):
                 ("n_heads", c_int), ("head_dim", c_int), ("ffn", c_int), ("vocab", c_int),
                 ("max_pos", c_int), ("type_vocab", c_int), ("act", c_int), ("ln_eps", c_float),
                 ("rel_buckets", c_int), ("rel_max_dist", c_int), ("pooling", c_int),
-                ("head_in", c_int), ("head_out", c_int), ("normalize", c_int)]
+                ("head_in", c_int), ("head_out", c_int), ("normalize", c_int),
+                # ABI v6 (ModernBERT; zero for BERT / T5)
+                ("rope_theta_global", c_float), ("rope_theta_local", c_float), ("half_window", c_int),
+                ("sliding_layers", C.c_uint64)]
 
 
 class OmEncoderWeights(C.Structure):
     _fields_ = [("word_emb", c_void_p), ("pos_emb", c_void_p), ("type_emb", c_void_p),
                 ("emb_ln_g", c_void_p), ("emb_ln_b", c_void_p),
                 ("layers_host", C.POINTER(OmLayerWeights)), ("final_ln_g", c_void_p),
-                ("rel_bias", c_void_p), ("head_w", c_void_p), ("folded", c_void_p)]
+                ("rel_bias", c_void_p), ("head_w", c_void_p), ("folded", c_void_p), ("final_ln_b", c_void_p)]
 
 
 class OmTnProblem(C.Structure):

@@ -221,6 +221,9 @@ def encode_train(model, head, items, pooling, normalize, code, training, packed_
     packed_rows: a bound on the batch's token count known on the HOST (encoder.packed_rows_bound of the collator's lengths) --
     the step then runs over that many rows instead of B x L where the packed pair takes the configuration (OM_TRAIN_PACKED=0: never)."""
     global LAST_TRAIN_CODE
+    if _arch_of(model) == "modernbert":
+        raise NotImplementedError("ModernBERT training is not supported by the HIP encoder (inference only: encode in eval "
+                                  "mode under torch.no_grad())")
     code = LAST_TRAIN_CODE = training_code(code, model)
     ids = items["input_ids"].to(torch.int64).contiguous()
     mask = items["attention_mask"].to(device=ids.device, dtype=torch.int64).contiguous()
