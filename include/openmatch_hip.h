@@ -47,7 +47,9 @@ extern "C" {
                                 * v -- the backward's dgrad then multiplies by it (OM_ACT_MUL_RESID) instead of evaluating gelu' */
 
 /* encoder architecture */
-#define OM_ARCH_BERT 0 /* HF:models/bert/modeling_bert.py  BertModel       */
+#define OM_ARCH_BERT 0 /* HF:models/bert/modeling_bert.py  BertModel -- the post-LayerNorm stack; also RoBERTa, and with two optional
+                          parts: no token-type table (type_emb == NULL: DistilBERT, MPNet) and a relative-position bias added to the
+                          scaled scores of every layer (rel_bias != NULL with rel_buckets > 0: MPNet) */
 #define OM_ARCH_T5 1   /* HF:models/t5/modeling_t5.py      T5EncoderModel  */
 #define OM_ARCH_MODERNBERT 2 /* HF:models/modernbert/modeling_modernbert.py  ModernBertModel (inference only):
                               * word embedding + LayerNorm; per layer x += Wo(attn(rope(Wqkv(LN1(x))))) (layer 0: no LN1,
@@ -245,11 +247,11 @@ typedef struct OmEncoderConfig {
   int ffn;           /* F                                                         */
   int vocab;
   int max_pos;       /* BERT position table rows                                  */
-  int type_vocab;    /* BERT token-type table rows                                */
+  int type_vocab;    /* BERT token-type table rows; 0 with type_emb == NULL: word + position only (DistilBERT, MPNet) */
   int act;           /* OM_ACT_*                                                  */
   float ln_eps;      /* 1e-12 BERT, 1e-6 T5                                       */
-  int rel_buckets;   /* T5 relative_attention_num_buckets (32)                    */
-  int rel_max_dist;  /* T5 relative_attention_max_distance (128)                  */
+  int rel_buckets;   /* T5 / MPNet relative_attention_num_buckets (32); OM_ARCH_BERT: 0 = no relative bias */
+  int rel_max_dist;  /* T5 relative_attention_max_distance (128); MPNet: 128, fixed in its modelling code */
   int pooling;       /* OM_POOL_*                                                 */
   int head_in;       /* LinearHead input dim  (0 = no head)                       */
   int head_out;      /* LinearHead output dim                                     */
@@ -264,12 +266,13 @@ typedef struct OmEncoderConfig {
 typedef struct OmEncoderWeights {
   const float* word_emb;  /* [vocab,H] f32                                        */
   const float* pos_emb;   /* [max_pos,H] f32 (BERT)                               */
-  const float* type_emb;  /* [type_vocab,H] f32 (BERT)                            */
+  const float* type_emb;  /* [type_vocab,H] f32 (BERT); NULL: no token types (DistilBERT, MPNet) */
   const float* emb_ln_g;  /* BERT embeddings.LayerNorm ; ModernBERT embeddings.norm */
   const float* emb_ln_b;
   const OmLayerWeights* layers_host; /* HOST array [n_layers] of device pointers  */
   const float* final_ln_g; /* T5 final_layer_norm.weight ; ModernBERT final_norm.weight */
-  const float* rel_bias;   /* T5 block[0] relative_attention_bias [buckets,heads] f32 */
+  const float* rel_bias;   /* relative_attention_bias [buckets,heads] f32, one table for all layers: T5 block[0]; OM_ARCH_BERT: MPNet's
+                              encoder.relative_attention_bias (bias[h][q][k] = table[bucket(k - q)][h], T5's bidirectional rule), else NULL */
   const float* head_w;     /* LinearHead weight [head_out,head_in] f32, or NULL   */
   const void* folded;      /* LayerNorm-folded weights made by om_encoder_fold_weights (ABI v4), or NULL: folded per forward */
   const float* final_ln_b; /* ModernBERT final_norm.bias, or NULL (norm_bias = False) (ABI v6)                          */
@@ -408,7 +411,7 @@ typedef struct OmEncoderGrads {
   const OmLayerGrads* layers_host;  /* HOST array [n_layers] of device pointers */
   float* head_w;                    /* [head_out, head_in] or NULL              */
   float* final_ln_g;                /* T5: final RMSNorm weight [hidden] (ABI v2)     */
-  float* rel_bias;                  /* T5: relative_attention_bias [buckets, heads]   */
+  float* rel_bias;                  /* T5, MPNet: relative_attention_bias [buckets, heads] (summed over layers) */
 } OmEncoderGrads;
 
 size_t om_encoder_tape_bytes(const OmEncoderConfig* cfg, int64_t B, int64_t L);

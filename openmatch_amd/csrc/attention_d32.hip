@@ -80,10 +80,11 @@ __device__ inline void store_row32(T* p, const f32x16_t& o, float mul, int half)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Forward.  Grid (heads * B, ceil(Lm / (32 W))), W = blockDim.x / 64 waves.  KT: 32-key tiles per chunk.
-template <typename T, int KT, bool DROP>
+// BIAS: pos_bias[h][q][k] (pitch Lm, the padded length, also for packed rows) is added to the SCALED score (MPNet's relative position bias).
+template <typename T, int KT, bool DROP, bool BIAS>
 __global__ __launch_bounds__(512) void attention_d32_fwd_kernel(
-    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lm, int H, int heads, float scale,
-    float drop_p, uint64_t seed, int rev, const int* __restrict__ kmax, const int* __restrict__ cu) {
+    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, const float* __restrict__ pos_bias, int Lm, int H,
+    int heads, float scale, float drop_p, uint64_t seed, int rev, const int* __restrict__ kmax, const int* __restrict__ cu) {
   typedef D32<T> G;
   typedef typename MmaOps<T>::frag_t frag_t;
   constexpr int KC = KT * 32, LP = KC + 4;
@@ -160,9 +161,16 @@ __global__ __launch_bounds__(512) void attention_d32_fwd_kernel(
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4_t mb = *(const f32x4_t*)(sM + t * 32 + 8 * g + 4 * half);
+        f32x4_t pb = {0.f, 0.f, 0.f, 0.f};
+        if (BIAS) {              // four consecutive keys of this query's bias row (keys past the padded length: clamped, they are masked)
+          const float* pr = pos_bias + ((int64_t)h * Lm + qrow) * Lm;
+          const int k0 = kc + t * 32 + 8 * g + 4 * half;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pb[e] = pr[(k0 + e) < Lm ? (k0 + e) : (Lm - 1)];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = s[t][4 * g + e] * scale + mb[e];
+          const float v = BIAS ? (s[t][4 * g + e] * scale + pb[e]) + mb[e] : s[t][4 * g + e] * scale + mb[e];
           s[t][4 * g + e] = v;
           mx = fmaxf(mx, v);
         }
@@ -211,38 +219,40 @@ __global__ __launch_bounds__(512) void attention_d32_fwd_kernel(
   store_row32<T>(ctx + (row0 + q0 + l31) * (int64_t)H + h * 32, o, inv, half);
 }
 
-template <typename T, int KT, bool DROP>
-int launch_fwd(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale, float drop_p,
+template <typename T, int KT, bool DROP, bool BIAS>
+int launch_fwd(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H, int heads, float scale, float drop_p,
                uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
   constexpr int KC = KT * 32;
   const int lds = KC * D32<T>::ROWB + 32 * (KC + 4) * (int)sizeof(T) + KC * 4;
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_d32_fwd_kernel<T, KT, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    OM_HIP(hipFuncSetAttribute((const void*)attention_d32_fwd_kernel<T, KT, DROP, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     attr_set = true;
   }
   const int waves = L < 256 ? (L + 31) / 32 : 8;
-  hipLaunchKernelGGL((attention_d32_fwd_kernel<T, KT, DROP>), dim3((unsigned)(heads * B), (unsigned)((L + 32 * waves - 1) / (32 * waves))),
-                     dim3(64 * waves), lds, s, (const T*)qkv, (T*)ctx, mask, L, H, heads, scale, drop_p, seed, rev, kmax, cu);
+  hipLaunchKernelGGL((attention_d32_fwd_kernel<T, KT, DROP, BIAS>), dim3((unsigned)(heads * B), (unsigned)((L + 32 * waves - 1) / (32 * waves))),
+                     dim3(64 * waves), lds, s, (const T*)qkv, (T*)ctx, mask, pos_bias, L, H, heads, scale, drop_p, seed, rev, kmax, cu);
   OM_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename T, bool DROP>
-int dispatch_fwd(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale, float drop_p,
+template <typename T, bool DROP, bool BIAS>
+int dispatch_fwd(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H, int heads, float scale, float drop_p,
                  uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
-  if (L <= 32) return launch_fwd<T, 1, DROP>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (L <= 64) return launch_fwd<T, 2, DROP>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (L <= 128) return launch_fwd<T, 4, DROP>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (L <= 192) return launch_fwd<T, 6, DROP>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  return launch_fwd<T, 8, DROP>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);      // beyond 256: 256-key chunks
+  if (L <= 32) return launch_fwd<T, 1, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
+  if (L <= 64) return launch_fwd<T, 2, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
+  if (L <= 128) return launch_fwd<T, 4, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
+  if (L <= 192) return launch_fwd<T, 6, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
+  return launch_fwd<T, 8, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);      // beyond 256: 256-key chunks
 }
 
 template <typename T>
-int dispatch_fwd_t(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale, float drop_p,
-                   uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
-  if (drop_p > 0.f) return dispatch_fwd<T, true>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  return dispatch_fwd<T, false>(qkv, ctx, mask, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
+int dispatch_fwd_t(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
+                   float drop_p, uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
+  if (pos_bias && drop_p > 0.f) return dispatch_fwd<T, true, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
+  if (pos_bias) return dispatch_fwd<T, false, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
+  if (drop_p > 0.f) return dispatch_fwd<T, true, false>(qkv, ctx, mask, nullptr, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
+  return dispatch_fwd<T, false, false>(qkv, ctx, mask, nullptr, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -250,10 +260,13 @@ int dispatch_fwd_t(const void* qkv, void* ctx, const int64_t* mask, int64_t B, i
 //   P = softmax(scale QK^T + mask), Pd = dropout(P)   (recomputed)
 //   dPd = dO V^T ; dP = dropout'(dPd) ; dS = P o (dP - rowsum(P o dP)) * scale
 //   dQ = dS K ; dK = dS^T Q ; dV = Pd^T dO
-template <typename T, int KT>
+// BIAS: pos_bias [heads][Lm][Lm] is added to the scaled scores; drel [heads][2 Lm - 1] accumulates the gradient of the bias per
+// offset key - query, summed over the batch (omk_t5_bias_bwd folds it into the bucket table) -- as attention_bwd_kernel does at D = 64.
+template <typename T, int KT, bool BIAS>
 __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
     const T* __restrict__ qkv, const T* __restrict__ dctx, T* __restrict__ dqkv, const int64_t* __restrict__ mask, int Lm, int H,
-    int heads, float scale, float drop_p, uint64_t seed, const int* __restrict__ cu) {
+    int heads, float scale, float drop_p, uint64_t seed, const int* __restrict__ cu, const float* __restrict__ pos_bias,
+    float* __restrict__ drel) {
   typedef D32<T> G;
   typedef typename MmaOps<T>::frag_t frag_t;
   constexpr int LP = KT * 32 + 4;
@@ -265,6 +278,7 @@ __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
   float* sMax = sM + KT * 32;                  // per query: row max, 1 / row sum, delta
   float* sInv = sMax + KT * 32;
   float* sDelta = sInv + KT * 32;
+  float* sRel = sDelta + KT * 32;              // BIAS: this workgroup's share of drel [2 Lm - 1]
 
   const int h = blockIdx.x % heads;
   const int64_t b = blockIdx.x / heads;
@@ -272,6 +286,8 @@ __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
   int L = Lm;
   if (cu) { row0 = cu[b]; L = cu[b + 1] - cu[b]; if (L <= 0) return; }
   const int tid = threadIdx.x, nthr = blockDim.x;
+  if (BIAS)
+    for (int k = tid; k < 2 * Lm - 1; k += nthr) sRel[k] = 0.f;
   const int64_t ld = 3 * (int64_t)H;
   const T* base = qkv + row0 * ld + h * 32;
   const T* dob = dctx + row0 * H + h * 32;
@@ -326,8 +342,15 @@ __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4_t mb = *(const f32x4_t*)(sM + t * 32 + 8 * g + 4 * half);
+        if (BIAS) {
+          const float* pr = pos_bias + ((int64_t)h * Lm + myrow) * Lm;
+          const int k0 = t * 32 + 8 * g + 4 * half;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[4 * g + e] = (v[4 * g + e] * scale + pr[(k0 + e) < Lm ? (k0 + e) : (Lm - 1)]) + mb[e];
+        } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[4 * g + e] = v[4 * g + e] * scale + mb[e];
+        }
       }
     };
     // dropout'(dPd)^T of key tile t: dPd^T[key][query] = V dO^T, the forward's mask and 1 / (1 - p)
@@ -390,12 +413,21 @@ __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
       s_tile(t, v);
       dp_tile(t, d);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = AttnGeom<T>::exp_(v[r] - mx) * inv * (d[r] - delta) * scale;      // dS
+      for (int r = 0; r < 16; ++r) {
+        const float dlogit = AttnGeom<T>::exp_(v[r] - mx) * inv * (d[r] - delta);      // d loss / d (scaled score + bias)
+        if (BIAS) {
+          const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, q = blk0 + l31;
+          if (q < L && key < L) atomicAdd(&sRel[key - q + (Lm - 1)], dlogit);
+        }
+        v[r] = dlogit * scale;                                                          // dS
+      }
       ContractT<T>::run(v, sKt + l31 * LP + t * 32 + 4 * half, LP, o);   // dQ^T += K^T dS^T
     }
     if (blk0 + l31 < L) store_row32<T>(dbase + (int64_t)(blk0 + l31) * ld, o, 1.f, half);
   }
   __syncthreads();
+  if (BIAS)
+    for (int k = tid; k < 2 * Lm - 1; k += nthr) atomicAdd(drel + (int64_t)h * (2 * Lm - 1) + k, sRel[k]);
 
   // ------------------------------------------------------------------ phase B: lane <-> key
   for (int blk0 = wave * 32; blk0 < L; blk0 += nw * 32) {      // first key of the block
@@ -436,6 +468,8 @@ __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
         const int q = q4 + e;
         float p = 0.f, pd = 0.f, dpp = 0.f;
         if (q < L && kvalid) {
+          if (BIAS) p = AttnGeom<T>::exp_((sb[4 * g + e] * scale + pos_bias[((int64_t)h * Lm + q) * Lm + blk0 + l31]) + mbk - m4[e]) * i4[e];
+          else
           p = AttnGeom<T>::exp_(sb[4 * g + e] * scale + mbk - m4[e]) * i4[e];
           pd = p; dpp = dpb[4 * g + e];
           if (thresh) {
@@ -458,30 +492,30 @@ __global__ __launch_bounds__(256) void attention_d32_bwd_kernel(
   }
 }
 
-template <typename T, int KT>
+template <typename T, int KT, bool BIAS>
 int launch_bwd(const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
-               float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
+               float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias, float* drel) {
   constexpr int LP = KT * 32 + 4;
-  const int lds = 3 * 32 * LP * (int)sizeof(T) + 4 * KT * 32 * 4;
+  const int lds = 3 * 32 * LP * (int)sizeof(T) + 4 * KT * 32 * 4 + (BIAS ? 2 * KT * 32 * 4 : 0);      // (by the tile count, like every other term: the attribute below is set once)
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_d32_bwd_kernel<T, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    OM_HIP(hipFuncSetAttribute((const void*)attention_d32_bwd_kernel<T, KT, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     attr_set = true;
   }
-  hipLaunchKernelGGL((attention_d32_bwd_kernel<T, KT>), dim3((unsigned)(heads * B)), dim3(64 * (L < 128 ? (L + 31) / 32 : 4)), lds, s, (const T*)qkv,
-                     (const T*)dctx, (T*)dqkv, mask, L, H, heads, scale, drop_p, seed, cu);
+  hipLaunchKernelGGL((attention_d32_bwd_kernel<T, KT, BIAS>), dim3((unsigned)(heads * B)), dim3(64 * (L < 128 ? (L + 31) / 32 : 4)), lds, s, (const T*)qkv,
+                     (const T*)dctx, (T*)dqkv, mask, L, H, heads, scale, drop_p, seed, cu, pos_bias, drel);
   OM_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename T>
+template <typename T, bool BIAS>
 int dispatch_bwd(const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
-                 float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
-  if (L <= 32) return launch_bwd<T, 1>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-  if (L <= 64) return launch_bwd<T, 2>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-  if (L <= 128) return launch_bwd<T, 4>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-  if (L <= 192) return launch_bwd<T, 6>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-  return launch_bwd<T, 8>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
+                 float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias, float* drel) {
+  if (L <= 32) return launch_bwd<T, 1, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+  if (L <= 64) return launch_bwd<T, 2, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+  if (L <= 128) return launch_bwd<T, 4, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+  if (L <= 192) return launch_bwd<T, 6, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+  return launch_bwd<T, 8, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
 }
 
 }  // namespace
@@ -490,26 +524,32 @@ int omk_attention_d32(int dtype, const void* qkv, void* ctx, const int64_t* mask
                       int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu) {
   if (B <= 0) return 0;
   if (H != heads * 32) OM_FAIL("head_dim 32: H must be heads * 32");
-  if (pos_bias) OM_FAIL("T5 position bias: head_dim 64 only");
   if (cu && dtype != OM_F16 && dtype != OM_BF16) OM_FAIL("packed rows: the 16-bit attention kernels");
   if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
   if (L > 256 && drop_p > 0.f && (L > 512 || dtype == OM_F32)) OM_FAIL("attention with dropout: up to 512 tokens in the 16-bit formats (float32: 256)");
   if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
-  if (dtype == OM_F16) return dispatch_fwd_t<f16_t>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  if (dtype == OM_BF16) return dispatch_fwd_t<bf16_t>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  if (dtype == OM_F32) return dispatch_fwd_t<float>(qkv, ctx, mask, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+  if (dtype == OM_F16) return dispatch_fwd_t<f16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+  if (dtype == OM_BF16) return dispatch_fwd_t<bf16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+  if (dtype == OM_F32) return dispatch_fwd_t<float>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
   OM_FAIL("attention: dtype must be OM_F32, OM_BF16 or OM_F16");
 }
 
 int omk_attention_bwd_d32(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
-                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
+                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias,
+                          float* drel) {
   if (B <= 0) return 0;
   if (H != heads * 32) OM_FAIL("head_dim 32: H must be heads * 32");
   if (L < 1 || L > 256) OM_FAIL("training with head_dim 32 supports sequence lengths up to 256");
   if (cu && dtype != OM_F16 && dtype != OM_BF16) OM_FAIL("packed rows: attention backward for 16-bit formats");
   if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
-  if (dtype == OM_F16) return dispatch_bwd<f16_t>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-  if (dtype == OM_BF16) return dispatch_bwd<bf16_t>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-  if (dtype == OM_F32) return dispatch_bwd<float>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
+  if ((pos_bias != nullptr) != (drel != nullptr)) OM_FAIL("attention backward: a position bias needs its gradient buffer (and the reverse)");
+  if (pos_bias) {
+    if (dtype == OM_F16) return dispatch_bwd<f16_t, true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+    if (dtype == OM_BF16) return dispatch_bwd<bf16_t, true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+    if (dtype == OM_F32) return dispatch_bwd<float, true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+  }
+  if (dtype == OM_F16) return dispatch_bwd<f16_t, false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
+  if (dtype == OM_BF16) return dispatch_bwd<bf16_t, false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
+  if (dtype == OM_F32) return dispatch_bwd<float, false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
   OM_FAIL("attention backward: dtype must be OM_F32, OM_BF16 or OM_F16");
 }

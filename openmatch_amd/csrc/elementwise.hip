@@ -230,6 +230,10 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void embed_kernel(
           Vec4<float>::load(pos + (int64_t)t * H + c, p);
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[j][e] = (w[e] + ty[e]) + p[e];
+        } else if (pos) {          // DistilBERT, MPNet: word + position, no token-type table
+          Vec4<float>::load(pos + (int64_t)t * H + c, p);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[j][e] = w[e] + p[e];
         } else {                   // ModernBERT: LayerNorm of the word embedding alone (no position or token-type table)
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[j][e] = w[e];

@@ -134,8 +134,10 @@ static EncWs carve(const OmEncoderConfig* c, int64_t B, int64_t L, char* base, i
   w.ff2 = take(c->arch == OM_ARCH_T5 || c->arch == OM_ARCH_MODERNBERT ? M * F * es : 0);
   w.pooled = (float*)take((size_t)B * H * 4);
   w.headout = (float*)take((size_t)B * (c->head_out > 0 ? c->head_out : 1) * 4);
-  w.posbias = (float*)take(c->arch == OM_ARCH_T5 ? (size_t)c->n_heads * L * L * 4 : 0);
-  w.lut = (int*)take(c->arch == OM_ARCH_T5 ? (size_t)(2 * L) * 4 : 0);
+  // relative-position bias [heads, L, L]: T5, and a BERT-family stack configured with a bucket table (MPNet: rel_buckets > 0)
+  const bool rel = c->arch == OM_ARCH_T5 || (c->arch == OM_ARCH_BERT && c->rel_buckets > 0);
+  w.posbias = (float*)take(rel ? (size_t)c->n_heads * L * L * 4 : 0);
+  w.lut = (int*)take(rel ? (size_t)(2 * L) * 4 : 0);
   w.kmax = (int*)take((size_t)B * 4);
   w.cu = (int*)take(packed_rows > 0 ? (size_t)(B + 2) * 4 : 0);
   w.cls_rows = (int*)take(packed_rows > 0 ? (size_t)B * 4 : 0);
@@ -230,6 +232,8 @@ static int check_cfg(const OmEncoderConfig* c) {
     OM_FAIL("T5 encoders: only d_kv 64 with n_heads*64 == d_model is supported");
   if ((c->head_dim != 32 && c->head_dim != 64) || c->n_heads * c->head_dim != c->hidden)
     OM_FAIL("head_dim must be 32 or 64 with n_heads*head_dim == hidden");
+  if (c->arch == OM_ARCH_BERT && c->rel_buckets != 0 && (c->rel_buckets < 4 || c->rel_buckets % 2 || c->rel_max_dist <= c->rel_buckets / 4))
+    OM_FAIL("relative position bias: an even number of buckets >= 4 and a maximum distance beyond the exact buckets");
   const int es = c->dtype == OM_F32 ? 4 : 2;
   if ((c->hidden * es) % 128 || (c->ffn * es) % 128) OM_FAIL("hidden/ffn rows must be multiples of 128 bytes");
   if (c->head_in > 0 && ((c->head_in * 4) % 128 || c->head_in != c->hidden)) OM_FAIL("head_in must equal hidden");
@@ -302,6 +306,18 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   const float* f32_rows = ws.final32;       // where those rows are (the few-rows path leaves them in its f32 residual buffer)
   if (bert) {
     if (L > c->max_pos) OM_FAIL("sequence longer than the position table");
+    // Optional relative-position bias (MPNet): one bucket table for all layers, expanded once per forward to [heads, L, L] exactly as
+    // the T5 branch does, and handed to EVERY attention launch below next to the BERT scale (the kernels scale q.k only).  The two
+    // fields must agree: a table without a bucket count (or the reverse) is an error, never a forward without the bias.
+    if ((w->rel_bias != nullptr) != (c->rel_buckets > 0)) OM_FAIL("relative position bias: rel_bias and rel_buckets must be set together");
+    if (w->type_emb && c->type_vocab <= 0) OM_FAIL("token types: a type_emb table needs type_vocab > 0");      // (type_emb == NULL: word + position only)
+    const float* posbias = nullptr;
+    if (w->rel_bias) {
+      const int* lut = nullptr;                  // device-resident, cached per (L, buckets, max distance)
+      RUN(om_t5_lut_device((int)L, c->rel_buckets, c->rel_max_dist, &lut));
+      RUN(omk_t5_bias(w->rel_bias, lut, ws.posbias, (int)L, nh, s));
+      posbias = ws.posbias;
+    }
     // few rows, 16-bit (round 6): the residual stream in f32 -- the embedding leaves its LayerNorm output in both forms
     const bool few32 = few_rows && ws.y32 && c->n_layers > 0 && (om_option(OM_OPT_ENCODER_TWO_PLANE) & (dt == OM_BF16 ? 1 : 2)) != 0;
     RUN(omk_embed(dt, input_ids, token_type_ids, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g,
@@ -317,7 +333,11 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
     const bool fuse = !no_fuse && !few_rows && c->act == OM_ACT_GELU_ERF && c->n_layers > 0 && H % 8 == 0 &&
                       omk_gemm_ln_fusable(dt, Mg, H, H) && omk_gemm_ln_fusable(dt, Mg, F, H) &&
                       omk_gemm_ln_fusable(dt, Mg, 3 * H, H) && omk_gemm_ln_fusable(dt, Mg, H, F);
-    if (om_option(OM_OPT_ENCODER_DEBUG)) fprintf(stderr, "om_encoder_forward: M=%ld fused_ln=%d packed=%d\n", (long)M, (int)fuse, (int)packed);
+    const bool pending_ln = !fuse && few32 && M <= (int64_t)om_option(OM_OPT_FEW_ROWS_LN_FUSE) && pending_ln_ok(dt, Mg, H, F, c->act);
+    // (attention under every path: head_dim 32 -> attention_d32.hip; L > 256 -> the key-chunked / online-softmax kernels)
+    if (om_option(OM_OPT_ENCODER_DEBUG))
+      fprintf(stderr, "om_encoder_forward: M=%ld fused_ln=%d packed=%d few_rows=%d pending_ln=%d L=%ld head_dim=%d rel_bias=%d\n", (long)M, (int)fuse,
+              (int)packed, (int)few_rows, (int)pending_ln, (long)L, c->head_dim, (int)(posbias != nullptr));
     if (packed && !fuse) OM_FAIL("packed rows need the fused 16-bit path (hidden, ffn multiples of 256; erf-GELU)");
     if (fuse) {
       const float inv_h = 1.0f / (float)H;
@@ -354,7 +374,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
           e.bias = bfp; e.ln_stats = st2p; e.ln_colsum = cs; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.reverse = OM_WALK();
           RUN(omk_gemm(dt, ws.x1, H, wf, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
         }
-        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, OM_WALK(), ws.kmax, cu));
+        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, posbias, B, (int)L, H, nh, scale, 0.f, 0, s, OM_WALK(), ws.kmax, cu));
         // ---- attention output + residual -> y1, statistics of LN1
         e = GemmEpilogue{};
         e.bias = lw.o_b; e.ldr = H; e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
@@ -411,7 +431,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
           final32_rows = M;
         }
       }
-    } else if (few32 && M <= (int64_t)om_option(OM_OPT_FEW_ROWS_LN_FUSE) && pending_ln_ok(dt, Mg, H, F, c->act)) {
+    } else if (pending_ln) {
       // A handful of rows (<= 64: a served query), 16-bit (round 6): the f32 residual stream of the branch below with its LayerNorms PENDING --
       // no normalisation launches between the embedding and the last layer (86 -> 63 dependent launches for bert-base; a launch costs
       // 5.3 us here whatever it does, profiles/r06_few_rows_graph_probe.json).  y_a / y_b hold the pre-LayerNorm sums in f32; the
@@ -428,7 +448,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
         e.bias = lw.qkv_b; e.ln_eps = c->ln_eps;
         if (l) { e.a_ln32 = y_b; e.a_ln_g = Ls[l - 1].ln2_g; e.a_ln_b = Ls[l - 1].ln2_b; e.a_ln_stats_out = st2p; }
         RUN(omk_gemm(dt, ws.x, H, lw.qkv_w, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
-        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
+        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, posbias, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
         e = GemmEpilogue{};
         e.bias = lw.o_b; e.ldr = H; e.out32 = y_a; e.ln_eps = c->ln_eps;
         if (l) { e.rln32 = y_b; e.rln32_stats = st2p; e.rln_g = Ls[l - 1].ln2_g; e.rln_b = Ls[l - 1].ln2_b; }
@@ -458,7 +478,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
         const OmLayerWeights& lw = Ls[l];
         const bool last = l == c->n_layers - 1;
         GEMM(ws.x, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, lw.qkv_b, nullptr, 0, OM_ACT_NONE);
-        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
+        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, posbias, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
         GemmEpilogue e = {};
         e.bias = lw.o_b; e.resid32 = ws.r32a; e.ldr = H; e.out32 = ws.y32;
         RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.y, H, Mg, H, H, e, s));                  // y32 = ctx Wo^T + b + x (f32)
@@ -479,7 +499,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
     for (int l = 0; l < c->n_layers; ++l) {
       const OmLayerWeights& lw = Ls[l];
       GEMM(ws.x, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, lw.qkv_b, nullptr, 0, OM_ACT_NONE);
-      RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
+      RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, posbias, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
       GEMM(ws.ctx, H, lw.o_w, H, ws.y, H, H, H, lw.o_b, ws.x, H, OM_ACT_NONE);
       RUN(omk_layernorm(dt, ws.y, H, ws.x1, H, lw.ln1_g, lw.ln1_b, M, H, c->ln_eps, 0, s));
       GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F, F, H, lw.ffn1_b, nullptr, 0, c->act);

@@ -20,6 +20,7 @@
 namespace {
 struct Dims {
   int64_t M, Mp, B, L; int H, F, nl, nh, D; size_t es; bool t5, gated;
+  bool rel;          // a BERT-family stack with a relative-position bias table (MPNet: OmEncoderConfig::rel_buckets > 0)
   bool packed;       // packed rows (round 5): M = the caller's row bound; sequence b lives in rows cu[b] .. cu[b + 1] - 1 of every [M, .] tensor
   // what a 16-bit BERT tape holds (fixed by the FORWARD, remembered per tape: tape_flags below):
   bool bert16;       // 16-bit BERT: the configurations the two flags below apply to
@@ -36,6 +37,7 @@ Dims dims_of(const OmEncoderConfig* c, int64_t B, int64_t L, int64_t packed_rows
   d.D = c->head_in > 0 ? c->head_out : c->hidden;
   d.es = (c->dtype == OM_BF16 || c->dtype == OM_F16) ? 2 : 4;
   d.t5 = c->arch == OM_ARCH_T5;
+  d.rel = c->arch == OM_ARCH_BERT && c->rel_buckets > 0;
   d.gated = d.t5 && (c->act & 0xff) == OM_ACT_GELU_TANH;      // T5 v1.1: gated gelu_new (wi_0, wi_1)
   d.bert16 = !d.t5 && d.es == 2 && (size_t)d.F * d.es >= (size_t)d.H * 4;
   d.res32 = d.bert16 && om_option(OM_OPT_TRAIN_RES32) != 0;
@@ -126,9 +128,9 @@ Ws carve_ws(const Dims& d, char* base) {
   w.x32b = (float*)take(d.bert16 ? (size_t)d.M * d.H * 4 : 0);      //  under the other setting must find the same workspace)
   w.nbuf = take(d.t5 ? mh : 0);
   w.df2 = take(d.gated ? mf : 0);
-  w.posbias = (float*)take(d.t5 ? (size_t)d.nh * d.L * d.L * 4 : 0);
-  w.drel = (float*)take(d.t5 ? (size_t)d.nh * (2 * d.L) * 4 : 0);
-  w.lut = (int*)take(d.t5 ? (size_t)(2 * d.L) * 4 : 0);
+  w.posbias = (float*)take(d.t5 || d.rel ? (size_t)d.nh * d.L * d.L * 4 : 0);
+  w.drel = (float*)take(d.t5 || d.rel ? (size_t)d.nh * (2 * d.L) * 4 : 0);
+  w.lut = (int*)take(d.t5 || d.rel ? (size_t)(2 * d.L) * 4 : 0);
   w.skeep = keep_ok(d) ? align_up(5 * mh + mf, 256) : 0;
   w.keep = take(w.skeep * d.nl);
   w.slnpart = d.t5 ? 0 : (size_t)OM_LNB_MAX_BLOCKS * 2 * d.H;
@@ -207,8 +209,15 @@ inline uint64_t site_seed(uint64_t seed, int layer, int site) {
 #define RUN(expr) do { if (expr) return 1; } while (0)
 
 // relative-position bias [nh, L, L] from the bucket table (and the LUT the backward needs again)
+int rel_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Dims& d, Ws& ws, hipStream_t s);
 int t5_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Dims& d, Ws& ws, hipStream_t s) {
   if (!w->rel_bias || !w->final_ln_g) OM_FAIL("T5 needs rel_bias and final_ln_g");
+  return rel_bias_setup(c, w, d, ws, s);
+}
+// (the BERT-family stack with a bucket table -- MPNet -- shares it: same bucket rule, same [nh, L, L] expansion)
+int rel_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Dims& d, Ws& ws, hipStream_t s) {
+  if (!w->rel_bias || c->rel_buckets < 4 || c->rel_buckets % 2 || c->rel_max_dist <= c->rel_buckets / 4)
+    OM_FAIL("relative position bias: rel_bias with an even number of buckets >= 4 and a maximum distance beyond the exact buckets");
   const int L = (int)d.L;
   const int* lut = nullptr;                      // device-resident, cached per (L, buckets, max distance)
   if (om_t5_lut_device(L, c->rel_buckets, c->rel_max_dist, &lut)) return 1;
@@ -532,6 +541,10 @@ static int train_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* 
     return 0;
   }
   if (L > c->max_pos) OM_FAIL("sequence longer than the position table");
+  if ((w->rel_bias != nullptr) != d.rel) OM_FAIL("relative position bias: rel_bias and rel_buckets must be set together");
+  if (w->type_emb && c->type_vocab <= 0) OM_FAIL("token types: a type_emb table needs type_vocab > 0");
+  if (d.rel) RUN(rel_bias_setup(c, w, d, ws, s));      // [nh, L, L], added to the scaled scores of every layer's attention
+  const float* const posbias = d.rel ? ws.posbias : nullptr;
 
   tape_flags_set(tape_mem, flags_of(d));
   if ((om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 2) && d.es == 2 && d.nl > 0) {
@@ -587,7 +600,7 @@ static int train_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* 
     GemmEpilogue ep = {};
     ep.bias = lw.qkv_b;
     RUN(omk_gemm(dt, x, H, lw.qkv_w, H, dt, qkv, 3 * H, M, 3 * H, H, ep, s));
-    RUN(omk_attention(dt, qkv, ctx, attention_mask, nullptr, B, (int)L, H, d.nh, scale, attn_dropout,
+    RUN(omk_attention(dt, qkv, ctx, attention_mask, posbias, B, (int)L, H, d.nh, scale, attn_dropout,
                       site_seed(seed, l, 2), s, 0, packed ? ws.kmax : nullptr, cu));
     if (packed) RUN(omk_zero_rows_from(ctx, (int64_t)H * d.es, ws.cu + B, M, s));      // the rows no sequence owns
     ep = GemmEpilogue{};
@@ -751,6 +764,14 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
     return t5_train_backward(c, w, input_ids, attention_mask, d, t, ws, hidden_dropout, attn_dropout, seed, dx,
                              dx_prev, g, s);
 
+  // relative-position bias (MPNet): the table is shared by all layers, so every layer's attention backward adds its score gradient,
+  // summed over the batch, into ONE per-offset buffer drel [nh, 2L - 1]; omk_t5_bias_bwd folds it into the bucket table at the end
+  if ((w->rel_bias != nullptr) != d.rel) OM_FAIL("relative position bias: rel_bias and rel_buckets must be set together");
+  if (d.rel) {
+    if (!g->rel_bias) OM_FAIL("relative position bias: the gradients need a rel_bias buffer");
+    RUN(rel_bias_setup(c, w, d, ws, s));
+    OM_HIP(hipMemsetAsync(ws.drel, 0, (size_t)d.nh * (2 * d.L) * 4, s));
+  }
   // weight gradients on the second stream when every one of them takes the direct kernel (16-bit, widths of 128)
   WgradLane* lane = nullptr;
   if (om_option(OM_OPT_TRAIN_WGRAD_STREAM) && omk_gemm_tn_ok(dt, M, H, F, H, F) && omk_gemm_tn_ok(dt, M, F, H, F, H) &&
@@ -863,7 +884,10 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
     // (round 6) beyond 256 tokens -- and from 193 on (see t5_train_backward) --
     if (L > 256 || (!d.packed && dt != OM_F32 && ((om_option(OM_OPT_ATTENTION_FAST) & 2) || ((om_option(OM_OPT_ATTENTION_FAST) & 1) && L > 192))))      // one score tile in registers at a time, delta from the tape's attention output
       RUN(omk_attention_bwd_long(dt, qkv, ctx, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale,
-                                 attn_dropout, site_seed(seed, l, 2), nullptr, nullptr, ws.astats, s));
+                                 attn_dropout, site_seed(seed, l, 2), d.rel ? ws.posbias : nullptr, d.rel ? ws.drel : nullptr, ws.astats, s));
+    else if (d.rel)
+      RUN(omk_attention_bwd_bias(dt, qkv, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale,
+                                 attn_dropout, site_seed(seed, l, 2), ws.posbias, ws.drel, s, cu));
     else
     RUN(omk_attention_bwd(dt, qkv, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale,
                           attn_dropout, site_seed(seed, l, 2), s, cu));
@@ -913,6 +937,7 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
   RUN(omk_embed_bwd(dt, de, input_ids, token_type_ids, w->word_emb, w->pos_emb, w->type_emb,
                     w->emb_ln_g, g->word_emb, g->pos_emb, g->type_emb, g->emb_ln_g, g->emb_ln_b, B * L,
                     (int)L, H, c->vocab, c->type_vocab, c->ln_eps, s, cu));
+  if (d.rel) RUN(omk_t5_bias_bwd(ws.drel, ws.lut, g->rel_bias, (int)d.L, d.nh, s));
 #undef WGRAD
 #undef WGRAD_DONE
   RUN(record_layer_event(d.nl, s));

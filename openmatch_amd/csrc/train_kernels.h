@@ -53,7 +53,8 @@ int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const vo
 size_t omk_attention_bwd_long_stats_bytes(int64_t B, int heads);
 // 32-wide heads (H == heads * 32, attention_d32.hip), L <= 256, every format, packed rows in 16 bits; omk_attention_bwd* send such calls here
 int omk_attention_bwd_d32(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
-                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu);
+                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias = nullptr,
+                          float* drel = nullptr);      // pos_bias [heads, L, L] added to the scaled scores, drel [heads, 2L - 1] its per-offset gradient
 // bf16, L <= 128, no position bias: the transposing-read kernel of attention_bwd16.hip
 bool omk_attention_bwd16_ok(int dtype, int L, int H, int heads);
 int omk_attention_bwd16(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,

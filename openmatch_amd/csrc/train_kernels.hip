@@ -275,6 +275,7 @@ __global__ __launch_bounds__((NV == 8 || MODE == 1) ? 256 : 512, (NV == 8 || MOD
     if (MODE == 1) {
       id = ids[row]; id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
       tt = type_ids ? type_ids[row] : 0; tt = tt < 0 ? 0 : (tt >= type_vocab ? type_vocab - 1 : tt);
+      if (!type) tt = 0;                     // no token-type table (DistilBERT, MPNet): word + position only
       t = (int)(row % L);
     }
     float s1 = 0.f;
@@ -303,7 +304,7 @@ __global__ __launch_bounds__((NV == 8 || MODE == 1) ? 256 : 512, (NV == 8 || MOD
           if (x32) load4<float>(x32 + row * H + c, xv[j]); else load4<T>(x + row * H + c, xv[j]);
         } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) xv[j][e] = (word[id * H + c + e] + type[tt * H + c + e]) + pos[(int64_t)t * H + c + e];
+          for (int e = 0; e < 4; ++e) xv[j][e] = (type ? word[id * H + c + e] + type[tt * H + c + e] : word[id * H + c + e]) + pos[(int64_t)t * H + c + e];
         }
         if (MODE == 0 && dy32) load4<float>(dy32 + row * H + c, dv[j]); else load4<T>(dy + drow * H + c, dv[j]);
 #pragma unroll
@@ -428,8 +429,8 @@ __global__ __launch_bounds__((NV == 8 || MODE == 1) ? 256 : 512, (NV == 8 || MOD
       float s0 = 0.f, s1 = 0.f;
 #pragma unroll
       for (int k = 0; k < LNB_WAVES; ++k) { s0 += red[k * H + c]; s1 += red[(LNB_WAVES + k) * H + c]; }
-      atomicAdd(dtype_ + c, s0);
-      if (type_vocab > 1) atomicAdd(dtype_ + H + c, s1);
+      if (dtype_) atomicAdd(dtype_ + c, s0);                       // (NULL: no token-type table, no gradient to scatter)
+      if (dtype_ && type_vocab > 1) atomicAdd(dtype_ + H + c, s1);
     }
     __syncthreads();                   // the block's position row
 #pragma unroll
@@ -1248,8 +1249,7 @@ int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const vo
                            const float* pos_bias, float* drel, float* stats, hipStream_t s) {
   if (B <= 0) return 0;
   if (H == heads * 32) {      // 32-wide heads: one kernel up to 256 tokens (it recomputes the statistics; ctx and stats are not needed)
-    if (pos_bias || drel) OM_FAIL("T5 position bias: head_dim 64 only");
-    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, nullptr);
+    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, nullptr, pos_bias, drel);
   }
   if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (L < 1 || L > 512) OM_FAIL("attention backward (tile-at-a-time form): up to 512 tokens");      // (taken from 257 on; below that only when a test forces it)
@@ -1263,7 +1263,7 @@ int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const vo
 int omk_attention_bwd(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
                       int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
                       hipStream_t s, const int* cu) {
-  if (H == heads * 32) return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
+  if (H == heads * 32) return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
   if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (cu) {           // packed rows (16-bit formats): the transposing-read kernel up to 128 tokens, the generic one up to 256
     if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("packed rows: attention backward for 16-bit formats");
@@ -1291,8 +1291,7 @@ int omk_attention_bwd_bias(int dtype, const void* qkv, const void* dctx, void* d
                            const float* pos_bias, float* drel, hipStream_t s, const int* cu) {
   if (B <= 0) return 0;
   if (H == heads * 32) {
-    if (pos_bias || drel) OM_FAIL("T5 position bias: head_dim 64 only");
-    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
+    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
   }
   if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
   if (cu && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("packed rows: attention backward for 16-bit formats");

@@ -1,4 +1,5 @@
-"""Host side of the HIP encoder: turns a HF `BertModel` / `T5EncoderModel` / `ModernBertModel` (the parameter
+"""Host side of the HIP encoder: turns a HF `BertModel` / `RobertaModel` / `DistilBertModel` / `MPNetModel` / `T5EncoderModel` /
+`ModernBertModel` (the parameter
 container the reference keeps in `DRModel.lm_q / lm_p`) into the packed device weights that
 `om_encoder_forward` consumes, and launches it.
 
@@ -12,6 +13,7 @@ import os
 import torch
 
 from . import native as N
+from .flavours import bert_parts, flavour_of
 
 _ACT = {"gelu": N.ACT_GELU_ERF, "relu": N.ACT_RELU, "gelu_new": N.ACT_GELU_TANH,
         "gelu_pytorch_tanh": N.ACT_GELU_TANH}
@@ -49,7 +51,8 @@ def inference_code(model, code, seq_len):
     if _arch_of(model) == "t5":
         ok = _ACT.get(getattr(cfg, "dense_act_fn", None)) in (N.ACT_RELU, N.ACT_GELU_TANH) and os.environ.get("OM_T5_F16", "1") != "0"
         return code if ok else N.OM_BF16
-    if _ACT.get(getattr(cfg, "hidden_act", None)) != N.ACT_GELU_ERF:
+    act = getattr(cfg, "activation", None) if flavour_of(model) == "distilbert" else getattr(cfg, "hidden_act", None)
+    if _ACT.get(act) != N.ACT_GELU_ERF:
         return N.OM_BF16
     return code
 
@@ -124,12 +127,13 @@ def _arch_of(model):
         return "t5"
     if name.startswith("ModernBert"):    # ModernBertModel: pre-LayerNorm stack with rotary positions and sliding-window layers
         return "modernbert"
-    if name.startswith("Bert") or "Bert" in name and "Roberta" not in name:
-        return "bert"
-    if "Roberta" in name:          # RobertaModel, XLMRobertaModel: the BERT stack behind offset position ids
+    # BertModel; RobertaModel / XLMRobertaModel (the BERT stack behind offset position ids); DistilBertModel (no token types);
+    # MPNetModel (no token types, RoBERTa position numbering, one relative-position bias table for all layers) -- by an explicit
+    # rule (flavours.FLAVOURS): AlbertModel, MobileBertModel, SqueezeBertModel, ... carry "Bert" in their names and another layout
+    if flavour_of(model) is not None:
         return "bert"
     raise NotImplementedError(
-        f"openmatch_amd has HIP encoders for BERT / RoBERTa, T5-encoder and ModernBERT backbones; got {name}")
+        f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder and ModernBERT backbones; got {name}")
 
 
 def position_offset(model):
@@ -137,23 +141,27 @@ def position_offset(model):
     create_position_ids_from_input_ids: cumsum over non-pad tokens + padding_idx): token t of a right-padded sequence
     reads row t + padding_idx + 1 of the position table.  The kernels index positions from 0, so the table (and its
     gradient) is handed over starting at that row.  Padded positions read other rows than HF's (row padding_idx) -- they
-    are masked out of attention and pooling, so no output depends on them.  0 for BERT."""
-    if "Roberta" in type(model).__name__:
-        pad = getattr(model.config, "pad_token_id", None)
-        return (1 if pad is None else int(pad)) + 1
+    are masked out of attention and pooling, so no output depends on them.  MPNet numbers positions the same way
+    (HF:models/mpnet/modeling_mpnet.py create_position_ids_from_input_ids).  0 for BERT and DistilBERT."""
+    if flavour_of(model) in ("roberta", "mpnet"):
+        return _position_pad_id(model) + 1
     return 0
 
 
+def _position_pad_id(model):
+    pad = getattr(model.config, "pad_token_id", None)
+    return 1 if pad is None else int(pad)
+
+
 def check_position_layout(model, ids, mask):
-    """RoBERTa-family models only: the kernels read position row t (+ position_offset) for token t, HF reads
+    """RoBERTa-family and MPNet models only: the kernels read position row t (+ position_offset) for token t, HF reads
     cumsum(input_ids != pad)[t] + padding_idx (modeling_roberta.py create_position_ids_from_input_ids).  The two agree on
     every attended token exactly when no pad id precedes an attended token (right-padded text without pad ids inside
     it).  Anything else -- left padding, pad ids inside the text -- would silently read other rows than the reference:
     rejected here (one small device reduction + host read per call, RoBERTa only)."""
     if position_offset(model) == 0:
         return
-    pad = getattr(model.config, "pad_token_id", None)
-    pad = 1 if pad is None else int(pad)
+    pad = _position_pad_id(model)
     L = ids.shape[1]
     pos = torch.arange(L, device=ids.device)
     first_pad = torch.where(ids == pad, pos, L).amin(dim=1)
@@ -163,48 +171,54 @@ def check_position_layout(model, ids, mask):
                          "inside the text); the HIP encoder numbers positions for right-padded inputs only")
 
 
+def bert_config_fields(model):
+    """The OmEncoderConfig fields of a BERT-family module that do not depend on the compute format (flavours.bert_parts)."""
+    bp = bert_parts(model)
+    if bp.act not in _ACT:
+        raise NotImplementedError(f"activation {bp.act!r} has no HIP epilogue")
+    off = position_offset(model)
+    return dict(arch=N.ARCH_BERT, hidden=bp.hidden, n_layers=bp.hidden_layers, n_heads=bp.heads, head_dim=bp.hidden // bp.heads,
+                ffn=bp.ffn, vocab=bp.vocab, max_pos=bp.max_pos - off, type_vocab=bp.type_vocab if bp.type is not None else 0,
+                act=_ACT[bp.act], ln_eps=bp.eps, rel_buckets=bp.rel_buckets if bp.rel_bias is not None else 0,
+                rel_max_dist=bp.rel_max_dist if bp.rel_bias is not None else 0)
+
+
 def _pack_bert(model, code, device):
-    cfg = model.config
-    if getattr(cfg, "position_embedding_type", "absolute") != "absolute":
-        raise NotImplementedError("only absolute position embeddings are supported")
+    bp = bert_parts(model)
+    fields = bert_config_fields(model)
     wd = torch_dtype_of(code)
     f32 = torch.float32
     pk = _Packed()
-    emb = model.embeddings
     w = pk.weights
-    w.word_emb = pk.dev(emb.word_embeddings.weight, f32, device)
+    w.word_emb = pk.dev(bp.word.weight, f32, device)
     off = position_offset(model)
-    w.pos_emb = pk.dev(emb.position_embeddings.weight, f32, device) + off * cfg.hidden_size * 4
-    w.type_emb = pk.dev(emb.token_type_embeddings.weight, f32, device)
-    w.emb_ln_g = pk.dev(emb.LayerNorm.weight, f32, device)
-    w.emb_ln_b = pk.dev(emb.LayerNorm.bias, f32, device)
-    layers = (N.OmLayerWeights * cfg.num_hidden_layers)()
-    for i, layer in enumerate(model.encoder.layer):
-        at, lw = layer.attention, layers[i]
-        qkv_w = torch.cat([at.self.query.weight, at.self.key.weight, at.self.value.weight], 0)
-        qkv_b = torch.cat([at.self.query.bias, at.self.key.bias, at.self.value.bias], 0)
-        lw.qkv_w = pk.dev(qkv_w, wd, device, [at.self.query.weight, at.self.key.weight, at.self.value.weight])
-        lw.qkv_b = pk.dev(qkv_b, f32, device, [at.self.query.bias, at.self.key.bias, at.self.value.bias])
-        lw.o_w = pk.dev(at.output.dense.weight, wd, device)
-        lw.o_b = pk.dev(at.output.dense.bias, f32, device)
-        lw.ln1_g = pk.dev(at.output.LayerNorm.weight, f32, device)
-        lw.ln1_b = pk.dev(at.output.LayerNorm.bias, f32, device)
-        lw.ffn1_w = pk.dev(layer.intermediate.dense.weight, wd, device)
-        lw.ffn1_b = pk.dev(layer.intermediate.dense.bias, f32, device)
-        lw.ffn2_w = pk.dev(layer.output.dense.weight, wd, device)
-        lw.ffn2_b = pk.dev(layer.output.dense.bias, f32, device)
-        lw.ln2_g = pk.dev(layer.output.LayerNorm.weight, f32, device)
-        lw.ln2_b = pk.dev(layer.output.LayerNorm.bias, f32, device)
+    w.pos_emb = pk.dev(bp.pos.weight, f32, device) + off * bp.hidden * 4
+    if bp.type is not None:                  # (DistilBERT, MPNet: no token types -- type_emb stays NULL, type_vocab 0)
+        w.type_emb = pk.dev(bp.type.weight, f32, device)
+    w.emb_ln_g = pk.dev(bp.emb_ln.weight, f32, device)
+    w.emb_ln_b = pk.dev(bp.emb_ln.bias, f32, device)
+    if bp.rel_bias is not None:              # (MPNet: one [buckets, heads] table for all layers)
+        w.rel_bias = pk.dev(bp.rel_bias.weight, f32, device)
+    layers = (N.OmLayerWeights * len(bp.layers))()
+    for i, lp in enumerate(bp.layers):
+        lw = layers[i]
+        qkv_w = torch.cat([lp.q.weight, lp.k.weight, lp.v.weight], 0)
+        qkv_b = torch.cat([lp.q.bias, lp.k.bias, lp.v.bias], 0)
+        lw.qkv_w = pk.dev(qkv_w, wd, device, [lp.q.weight, lp.k.weight, lp.v.weight])
+        lw.qkv_b = pk.dev(qkv_b, f32, device, [lp.q.bias, lp.k.bias, lp.v.bias])
+        lw.o_w = pk.dev(lp.o.weight, wd, device)
+        lw.o_b = pk.dev(lp.o.bias, f32, device)
+        lw.ln1_g = pk.dev(lp.ln1.weight, f32, device)
+        lw.ln1_b = pk.dev(lp.ln1.bias, f32, device)
+        lw.ffn1_w = pk.dev(lp.ffn1.weight, wd, device)
+        lw.ffn1_b = pk.dev(lp.ffn1.bias, f32, device)
+        lw.ffn2_w = pk.dev(lp.ffn2.weight, wd, device)
+        lw.ffn2_b = pk.dev(lp.ffn2.bias, f32, device)
+        lw.ln2_g = pk.dev(lp.ln2.weight, f32, device)
+        lw.ln2_b = pk.dev(lp.ln2.bias, f32, device)
     pk.layers = layers
     w.layers_host = C.cast(layers, C.POINTER(N.OmLayerWeights))
-    act = cfg.hidden_act if isinstance(cfg.hidden_act, str) else "gelu"
-    if act not in _ACT:
-        raise NotImplementedError(f"activation {act!r} has no HIP epilogue")
-    pk.cfg = dict(arch=N.ARCH_BERT, dtype=code, hidden=cfg.hidden_size, n_layers=cfg.num_hidden_layers,
-                  n_heads=cfg.num_attention_heads, head_dim=cfg.hidden_size // cfg.num_attention_heads,
-                  ffn=cfg.intermediate_size, vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings - off,
-                  type_vocab=cfg.type_vocab_size, act=_ACT[act], ln_eps=float(cfg.layer_norm_eps),
-                  rel_buckets=0, rel_max_dist=0)
+    pk.cfg = dict(dtype=code, **fields)
     return pk
 
 
@@ -444,6 +458,24 @@ def invalidate_packed(root):
                 cache.clear()
 
 
+_TTI_WARNED = set()
+
+
+def token_types_of(model, items):
+    """The batch's token_type_ids, or None.  DistilBERT and MPNet have no token-type table: a batch that carries the ids all the
+    same (a BERT tokenizer's habit, and what the reranker's collator emits) has them DROPPED, with one warning per backbone class
+    (observable differences)."""
+    tti = items.get("token_type_ids") if hasattr(items, "get") else None
+    if tti is not None and flavour_of(model) in ("distilbert", "mpnet"):
+        name = type(model).__name__
+        if name not in _TTI_WARNED:
+            _TTI_WARNED.add(name)
+            import warnings
+            warnings.warn(f"{name} has no token-type embeddings: token_type_ids in the batch are ignored")
+        return None
+    return tti
+
+
 _POOL = {None: N.POOL_NONE, "first": N.POOL_FIRST, "mean": N.POOL_MEAN}
 
 
@@ -517,7 +549,7 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
         raise ValueError("Unknown pooling type: {}".format(pooling))
     ids = items["input_ids"]
     mask = items["attention_mask"]
-    tti = items.get("token_type_ids") if hasattr(items, "get") else None
+    tti = token_types_of(model, items)
     if ids.dim() != 2:
         raise ValueError("input_ids must be [batch, length]")
     ids = ids.to(torch.int64).contiguous()

@@ -26,6 +26,7 @@ from ..arguments import DataArguments, ModelArguments
 from ..arguments import DRTrainingArguments as TrainingArguments
 from ..encoder import compute_dtype_code, hip_encode
 from ..feed import is_packed, token_rows_bound, unpack_token_batch
+from ..flavours import dropout_probs, flavour_of
 from ..encoder import TOKEN_ROWS_KEY, rows_bound_of
 from ..ops import contrastive_loss, encode_with_grad
 from .linear import LinearHead
@@ -128,9 +129,10 @@ class DRModel(nn.Module):
         code = compute_dtype_code(self.model_args)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())
         cfg = getattr(model, "config", None)
-        has_dropout = self.training and (getattr(cfg, "hidden_dropout_prob", 0.0) > 0
-                                         or getattr(cfg, "attention_probs_dropout_prob", 0.0) > 0
-                                         or getattr(cfg, "dropout_rate", 0.0) > 0)       # T5
+        if flavour_of(model) is not None:           # BERT family: the backbone's own names for the two rates (flavours.dropout_probs)
+            has_dropout = self.training and max(dropout_probs(model)) > 0
+        else:
+            has_dropout = self.training and getattr(cfg, "dropout_rate", 0.0) > 0       # T5
         # train-mode forward: with autograd on, with dropout, and for ANY forward of a model in training mode -- the gradient-cache
         # trainer's first, tape-less pass must produce the representations its second pass differentiates (the inference kernels'
         # differ from the training forward's in the last 16-bit digits, which a contrastive loss over near-equal scores amplifies)

@@ -10,22 +10,24 @@ import torch
 
 from . import native as N
 from .encoder import (_POOL, _arch_of, check_position_layout, packed_decoder_weights, packed_weights, position_offset,
-                      torch_dtype_of, training_code)
+                      token_types_of, torch_dtype_of, training_code)
+from .flavours import bert_parts, dropout_probs
 
 
 def _bert_params(model, head):
-    """Parameters in the order the backward returns their gradients."""
-    emb = model.embeddings
-    ps = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
-          emb.LayerNorm.weight, emb.LayerNorm.bias]
-    for layer in model.encoder.layer:
-        at = layer.attention
-        ps += [at.self.query.weight, at.self.key.weight, at.self.value.weight,
-               at.self.query.bias, at.self.key.bias, at.self.value.bias,
-               at.output.dense.weight, at.output.dense.bias, at.output.LayerNorm.weight, at.output.LayerNorm.bias,
-               layer.intermediate.dense.weight, layer.intermediate.dense.bias,
-               layer.output.dense.weight, layer.output.dense.bias,
-               layer.output.LayerNorm.weight, layer.output.LayerNorm.bias]
+    """Parameters in the order the backward returns their gradients (through flavours.bert_parts: BERT / RoBERTa, DistilBERT,
+    MPNet).  The token-type table and the relative-position table appear only where the backbone has them."""
+    bp = bert_parts(model)
+    ps = [bp.word.weight, bp.pos.weight]
+    if bp.type is not None:
+        ps.append(bp.type.weight)
+    ps += [bp.emb_ln.weight, bp.emb_ln.bias]
+    if bp.rel_bias is not None:
+        ps.append(bp.rel_bias.weight)
+    for lp in bp.layers:
+        ps += [lp.q.weight, lp.k.weight, lp.v.weight, lp.q.bias, lp.k.bias, lp.v.bias,
+               lp.o.weight, lp.o.bias, lp.ln1.weight, lp.ln1.bias,
+               lp.ffn1.weight, lp.ffn1.bias, lp.ffn2.weight, lp.ffn2.bias, lp.ln2.weight, lp.ln2.bias]
     if head is not None:
         ps.append(head.linear.weight)
     return ps
@@ -60,11 +62,13 @@ def _encoder_grad_arena(model, head, cfg, device, extra=0):
         n_emb = model.encoder.embed_tokens.weight.numel() + H + cfg.rel_buckets * cfg.n_heads
         n_layer = 3 * H * H + H * H + 2 * H + (2 if gated else 1) * F * H + H * F
     else:
-        emb = model.embeddings
-        n_emb = sum(t.numel() for t in (emb.word_embeddings.weight, emb.position_embeddings.weight,
-                                        emb.token_type_embeddings.weight)) + 2 * H
+        bp = bert_parts(model)
+        n_emb = (bp.word.weight.numel() + bp.pos.weight.numel() + (bp.type.weight.numel() if bp.type is not None else 0) + 2 * H
+                 + (bp.rel_bias.weight.numel() if bp.rel_bias is not None else 0))
         n_layer = 3 * H * H + 3 * H + H * H + H + 2 * H + F * H + F + H * F + H + 2 * H
-    arena = torch.zeros(n_emb + nl * n_layer + n_head + 64 * (8 + 13 * nl) + extra, device=device, dtype=torch.float32)
+    # (+ 64 floats of alignment slack per buffer: 13 per layer and 9 for the encoder-level ones -- one more than before MPNet, whose
+    #  rel_bias table is one more buffer on the BERT side; the other backbones simply leave that slot unused)
+    arena = torch.zeros(n_emb + nl * n_layer + n_head + 64 * (9 + 13 * nl) + extra, device=device, dtype=torch.float32)
     cursor = [0]
     g = N.OmEncoderGrads()
 
@@ -93,12 +97,13 @@ def _encoder_grad_arena(model, head, cfg, device, extra=0):
             per_layer.append(d)
             layer_bounds.append((lo_, cursor[0]))
     else:
-        gw = buf(g, "word_emb", *emb.word_embeddings.weight.shape)
-        gp = buf(g, "pos_emb", *emb.position_embeddings.weight.shape)
-        g.pos_emb = gp[position_offset(model):].data_ptr()        # RoBERTa: positions start at padding_idx + 1
-        gt = buf(g, "type_emb", *emb.token_type_embeddings.weight.shape)
+        gw = buf(g, "word_emb", *bp.word.weight.shape)
+        gp = buf(g, "pos_emb", *bp.pos.weight.shape)
+        g.pos_emb = gp[position_offset(model):].data_ptr()        # RoBERTa, MPNet: positions start at padding_idx + 1 (the rows below stay zero)
+        gt = buf(g, "type_emb", *bp.type.weight.shape) if bp.type is not None else None      # (no table: the backward takes NULL)
         gg = buf(g, "emb_ln_g", H)
         gb = buf(g, "emb_ln_b", H)
+        grel = buf(g, "rel_bias", *bp.rel_bias.weight.shape) if bp.rel_bias is not None else None   # MPNet: summed over the layers
         for l in range(nl):
             lg = layers[l]
             lo_ = cursor[0]
@@ -119,7 +124,7 @@ def _encoder_grad_arena(model, head, cfg, device, extra=0):
                 grads.append(d["ffn1g_w"])
             grads += [d["ffn2_w"], d["ln2_g"]]
     else:
-        grads = [gw, gp, gt, gg, gb]
+        grads = [gw, gp] + ([gt] if gt is not None else []) + [gg, gb] + ([grel] if grel is not None else [])
         for d in per_layer:
             q, k, v = d["qkv_w"].split(H, dim=0)
             qb, kb, vb = d["qkv_b"].split(H, dim=0)
@@ -227,7 +232,7 @@ def encode_train(model, head, items, pooling, normalize, code, training, packed_
     code = LAST_TRAIN_CODE = training_code(code, model)
     ids = items["input_ids"].to(torch.int64).contiguous()
     mask = items["attention_mask"].to(device=ids.device, dtype=torch.int64).contiguous()
-    tti = items.get("token_type_ids") if hasattr(items, "get") else None
+    tti = token_types_of(model, items)
     if tti is not None:
         tti = tti.to(device=ids.device, dtype=torch.int64).contiguous()
     N.require_device(ids, mask, tti)
@@ -235,8 +240,7 @@ def encode_train(model, head, items, pooling, normalize, code, training, packed_
     cfg = model.config
     bert = _arch_of(model) == "bert"
     if bert:
-        p_hidden = float(cfg.hidden_dropout_prob) if training else 0.0
-        p_attn = float(cfg.attention_probs_dropout_prob) if training else 0.0
+        p_hidden, p_attn = dropout_probs(model) if training else (0.0, 0.0)
     else:                                   # T5: one dropout_rate for every site
         p_hidden = p_attn = float(cfg.dropout_rate) if training else 0.0
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (p_hidden > 0 or p_attn > 0) else 0
