@@ -169,6 +169,36 @@ int om_debug_option(int opt, int value);
 int om_debug_option_value(int opt);
 /* the attention kernel alone (bf16 qkv [B*L, 3H] -> ctx [B*L, H]; mask [B, L] int64), for timing: csrc/kernels.h omk_attention */
 int om_debug_attention(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, void* stream);
+/* Test hooks for the attention forward (tests/test_attention_kernels.py).  om_debug_attention_ex forwards every argument of the
+ * internal launcher: qkv [rows, 3H] (q | k | v) and ctx [rows, H] of `dtype`, mask [B, L] int64, pos_bias [heads, L, L] f32 or NULL,
+ * kmax [B] (om_debug_mask_extent) or NULL, cu [B + 2] (om_debug_pack_rows: packed rows, L stays the pitch of mask and pos_bias) or
+ * NULL; w > 0 is the half window of banded attention (key k visible from q iff |q - k| <= w; no bias, dropout, cu or reverse there,
+ * w >= L - 1 is full attention).  om_debug_attention is this with bf16, scale 0.125 and everything else off. */
+int om_debug_attention_ex(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
+                          int heads, float scale, float drop_p, uint64_t seed, void* stream, int reverse, const int* kmax,
+                          const int* cu, int w);
+/* rotary positions in place on the Q and K columns of qkv [M, 3H], position = row % L (M need not be a multiple of L) */
+int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, void* stream);
+/* kmax[b] = 1 + the last unmasked key of mask row b (L when it has none) */
+int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
+/* cu [B + 2], cls_rows [B], row_map [rows] of the packed layout (csrc/kernels.h omk_pack_rows) */
+int om_debug_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, void* stream);
+/* The kernel family of the last attention forward launcher the calling thread reached, family | key tiles << 8 (key tiles: 32-key
+ * tiles a workgroup holds at once: the template's KT, 4 for the kernels that walk 128-key chunks).  Each launcher stores its code;
+ * the attention entry points store 0 on entry, before any argument check, so a call that launches nothing reads 0.  One host store
+ * per launch, nothing on the device. */
+#define OM_ATTN_FAMILY_GENERIC 1      /* attention_kernel: f32, and bf16 with OM_OPT_ATTENTION_FAST = 0, up to 256 tokens   */
+#define OM_ATTN_FAMILY_FWD16 2        /* attention_fwd16_kernel: 16-bit, up to 256 tokens                                     */
+#define OM_ATTN_FAMILY_FWD16_KMAX4 3  /* its KT = 4 body without bias / dropout under kmax or cu: trailing key tiles skipped   */
+#define OM_ATTN_FAMILY_FWD16C 4       /* attention_fwd16c_kernel: 16-bit, 128-key chunks, online softmax                      */
+#define OM_ATTN_FAMILY_LONG 5         /* attention_long_kernel: the first online-softmax kernel (f32 beyond 256 tokens; bf16 there
+                                         with OM_OPT_ATTENTION_FAST = 0; both 16-bit formats under bit 2)                       */
+#define OM_ATTN_FAMILY_D32 6          /* attention_d32_fwd_kernel: 32-wide heads                                              */
+#define OM_ATTN_FAMILY_BAND16 7       /* attention_band16_kernel                                                              */
+#define OM_ATTN_FAMILY_BAND32 8       /* attention_band32_kernel                                                              */
+int om_debug_attention_last(void);
+/* host only: 1 if attention-probability dropout keeps (b, h, q, key) at rate p under `seed`; Lm is the mask's row pitch */
+int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, int q, int key, float p);
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly
  * (out_shuffle[g]) and by its DPP / permlane form (out_dpp[g]); the two must agree bit for bit (tests/test_gpu_parity.py) */
 int om_debug_wave_sum_check(const float* in, float* out_shuffle, float* out_dpp, int64_t groups, void* stream);

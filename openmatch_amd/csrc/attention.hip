@@ -12,6 +12,10 @@
 
 #include "attn_common.h"
 
+static thread_local int g_attn_last = 0;
+void omk_attn_note(int family, int kt) { g_attn_last = family | (kt << 8); }
+extern "C" int om_debug_attention_last(void) { return g_attn_last; }
+
 template <typename T, int KT>
 __global__ __launch_bounds__(64 * KT) void attention_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask,
@@ -386,6 +390,7 @@ template <typename T, int KT, bool BIAS, bool DROP>
 static int launch_attn16_(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu = nullptr) {
   const int lds = 2 * KT * 32 * 128 + KT * 32 * 4;
+  omk_attn_note((KT == 4 && !BIAS && !DROP && (kmax || cu)) ? OM_ATTN_FAMILY_FWD16_KMAX4 : OM_ATTN_FAMILY_FWD16, KT);
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     OM_HIP(hipFuncSetAttribute((const void*)attention_fwd16_kernel<T, KT, BIAS, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -613,6 +618,7 @@ template <typename T, bool BIAS, bool DROP>
 static int launch_attn16c_(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
                            int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
   const int lds = 2 * 128 * 128 + 128 * 4;
+  omk_attn_note(OM_ATTN_FAMILY_FWD16C, 4);
   hipLaunchKernelGGL((attention_fwd16c_kernel<T, BIAS, DROP>), dim3((unsigned)(heads * B), (unsigned)((L + 127) / 128)), dim3(256), lds, s,
                      (const T*)qkv, (T*)ctx, mask, pos_bias, L, H, heads, scale, drop_p, seed, cu);
   OM_LAUNCH_CHECK();
@@ -788,6 +794,7 @@ template <typename T>
 static int launch_attn_long(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
                             int heads, float scale, hipStream_t s, float drop_p = 0.f, uint64_t seed = 0, const int* cu = nullptr) {
   const int lds = 128 * AttnGeom<T>::ROWB + 64 * 132 * (int)sizeof(T) + 128 * 4 + 128 * 4;
+  omk_attn_note(OM_ATTN_FAMILY_LONG, 4);
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     OM_HIP(hipFuncSetAttribute((const void*)attention_long_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -805,6 +812,7 @@ static int launch_attn(const void* qkv, void* ctx, const int64_t* mask, const fl
                        hipStream_t s) {
   constexpr int LP = KT * 32 + 4;
   const int lds = KT * 32 * AttnGeom<T>::ROWB + 64 * LP * (int)sizeof(T) + KT * 32 * 4;
+  omk_attn_note(OM_ATTN_FAMILY_GENERIC, KT);
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     OM_HIP(hipFuncSetAttribute((const void*)attention_kernel<T, KT>,
@@ -892,6 +900,7 @@ int omk_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, hipStream_
 int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
                   const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
                   float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu) {
+  omk_attn_note(0, 0);
   if (B <= 0) return 0;
   if (H == heads * 32) return omk_attention_d32(dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
   if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
@@ -931,7 +940,37 @@ int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
   return dispatch_attn<float>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
 }
 
-extern "C" int om_debug_attention(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, void* stream) {
+extern "C" int om_debug_attention_ex(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
+                                     int heads, float scale, float drop_p, uint64_t seed, void* stream, int reverse, const int* kmax,
+                                     const int* cu, int w) {
+  omk_attn_note(0, 0);
   if (!qkv || !ctx || !mask) OM_FAIL("null argument");
-  return omk_attention(OM_BF16, qkv, ctx, mask, nullptr, B, L, H, heads, 0.125f, 0.f, 0, (hipStream_t)stream);
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("attention: dtype must be OM_F32, OM_BF16 or OM_F16");
+  if (w > 0) {
+    if (pos_bias || drop_p > 0.f || cu || reverse) OM_FAIL("banded attention: no position bias, dropout, packed rows or reverse walk");
+    return omk_attention_band(dtype, qkv, ctx, mask, B, L, H, heads, scale, w, kmax, (hipStream_t)stream);
+  }
+  return omk_attention(dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, (hipStream_t)stream, reverse, kmax, cu);
+}
+extern "C" int om_debug_attention(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, void* stream) {
+  return om_debug_attention_ex(OM_BF16, qkv, ctx, mask, nullptr, B, L, H, heads, 0.125f, 0.f, 0, stream, 0, nullptr, nullptr, 0);
+}
+extern "C" int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, void* stream) {
+  if (!qkv) OM_FAIL("null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
+  return omk_rope(dtype, qkv, M, L, H, theta, (hipStream_t)stream);
+}
+extern "C" int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream) {
+  if (!mask || !kmax) OM_FAIL("null argument");
+  if (L < 1) OM_FAIL("mask extent: L must be at least 1");
+  return omk_mask_extent(mask, B, L, kmax, (hipStream_t)stream);
+}
+extern "C" int om_debug_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, void* stream) {
+  if (!kmax || !cu || !cls_rows || !row_map) OM_FAIL("null argument");
+  if (rows < 1) OM_FAIL("packed rows: rows must be at least 1");
+  return omk_pack_rows(kmax, B, L, rows, cu, cls_rows, row_map, (hipStream_t)stream);
+}
+// host only: the dropout decision of probability (b, h, q, key) exactly as the kernels take it (attn_common.h)
+extern "C" int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, int q, int key, float p) {
+  return attn_drop_keep1(seed, b, h, heads, Lm, q, key, AttnDrop(p).thresh) ? 1 : 0;
 }

@@ -423,6 +423,7 @@ int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStre
 
 int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
                        int w, const int* kmax, hipStream_t s) {
+  omk_attn_note(0, 0);
   if (B <= 0) return 0;
   if (w <= 0 || w >= L - 1)                                 // every key within reach: full attention
     return omk_attention(dtype, qkv, ctx, mask, nullptr, B, L, H, heads, scale, 0.f, 0, s, 0, kmax);
@@ -430,6 +431,7 @@ int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mas
   if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
   if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
   const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
+  omk_attn_note(dtype == OM_F32 ? OM_ATTN_FAMILY_BAND32 : OM_ATTN_FAMILY_BAND16, 4);
   if (dtype == OM_F32) {
     const int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
     static std::atomic<bool> attr_set{false};

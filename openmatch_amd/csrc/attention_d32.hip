@@ -224,6 +224,7 @@ int launch_fwd(const void* qkv, void* ctx, const int64_t* mask, const float* pos
                uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
   constexpr int KC = KT * 32;
   const int lds = KC * D32<T>::ROWB + 32 * (KC + 4) * (int)sizeof(T) + KC * 4;
+  omk_attn_note(OM_ATTN_FAMILY_D32, KT);
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     OM_HIP(hipFuncSetAttribute((const void*)attention_d32_fwd_kernel<T, KT, DROP, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));

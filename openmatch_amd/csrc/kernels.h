@@ -46,6 +46,9 @@ int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mas
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);
 int omk_pack_overflow_poison(const int* cu, int64_t B, int64_t rows, float* out, int64_t n, hipStream_t s);
 int omk_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, hipStream_t s);
+// the kernel family (OM_ATTN_FAMILY_*) and key-tile count of the calling thread's last attention forward launch: one host store per
+// launch (om_debug_attention_last)
+void omk_attn_note(int family, int kt);
 
 // ---- extended GEMM epilogue (training) ---------------------------------------------------
 // order: v = acc + bias ; [pre_act <- v] ; v = act(v) ; v = dropout(v) ; v = v (+|*) resid

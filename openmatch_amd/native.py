@@ -21,6 +21,9 @@ OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
 OPT_GEMM_GROUP_M, OPT_GEMM_VARIANT, OPT_GEMM_SKINNY_M = 6, 12, 19
 # om_debug_gemm_last codes (include/openmatch_hip.h: OM_GEMM_FAMILY_*)
 GEMM_FAMILY = {"v1": 1, "v2": 2, "v6": 6, "g7": 7, "g7_one_tile": 70, "7c16": 71, "7r16": 72, "skinny": 9}
+# om_debug_attention_last codes (include/openmatch_hip.h: OM_ATTN_FAMILY_*); the call returns family | key tiles << 8
+ATTN_FAMILY = {"generic": 1, "fwd16": 2, "fwd16_kmax4": 3, "fwd16c": 4, "long": 5, "d32": 6, "band16": 7, "band32": 8}
+OPT_ATTENTION_FAST = 2
 SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
 ABI_VERSION = 6
 
@@ -108,6 +111,13 @@ _SIGNATURES = {
     "om_debug_option_value": (c_int, [c_int]),
     "om_debug_gemm_last": (c_int, []),
     "om_debug_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "om_debug_attention_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float,
+                                      C.c_uint64, c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "om_debug_rope": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "om_debug_mask_extent": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "om_debug_attention_last": (c_int, []),
+    "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "om_encoder_fold_bytes": (c_size_t, [C.POINTER(OmEncoderConfig)]),
     "om_encoder_fold_weights": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p, c_size_t, c_void_p]),
