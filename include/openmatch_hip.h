@@ -99,6 +99,11 @@ void om_debug_gemm_gen(int gen);
 #define OM_GEMM_FAMILY_G7R16 72      /* gemm_nt_kernel7r16: continuous ring, residual                               */
 #define OM_GEMM_FAMILY_SKINNY 9      /* gemm_skinny.hip: few rows, weight streaming                                 */
 int om_debug_gemm_last(void);
+/* Test hook: the family (OM_GEMM_FAMILY_*) an om_gemm_nt call with these arguments would launch at the current switches, 0 for an empty
+ * problem, -1 for a call om_gemm_nt refuses.  Launches nothing and touches no GPU: the pointers are read as addresses only (alignment,
+ * null), so the whole decision table can be walked with made-up addresses on a machine without a GPU. */
+int om_debug_gemm_plan(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,
+                       int64_t M, int64_t N, int64_t K, const float* bias, const void* resid, int64_t ldr, int act);
 /* Run-time switches for A/B measurements and tests (initialised from the environment variable of the same
  * name on first use): OM_OPT_ENCODER_FUSED_LN 1 = LayerNorm / RMSNorm fused across the encoder GEMMs where the
  * shapes allow (default), 0 = one normalisation kernel per site; OM_OPT_ENCODER_DEBUG 1 = log the path taken. */

@@ -242,7 +242,7 @@ static int check_cfg(const OmEncoderConfig* c) {
 
 // packed_rows > 0: the token axis holds only the rows up to each sequence's last unmasked token, back to back
 // (om_encoder_forward_packed); every per-token kernel and contraction then runs over packed_rows rows instead of B * L.
-bool omk_gemm_skinny_ok(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep);      // gemm_skinny.hip
+bool omk_gemm_skinny_ok(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep, int max_m);      // gemm_skinny.hip
 // whether the four contractions of a BERT layer take their pending-LayerNorm forms on the few-rows kernel at this shape
 static bool pending_ln_ok(int dt, int64_t M, int H, int F, int act) {
   static const float one = 1.f;
@@ -251,8 +251,9 @@ static bool pending_ln_ok(int dt, int64_t M, int H, int F, int act) {
   r.rln32 = &one; r.rln32_stats = &one; r.rln_g = &one; r.rln_b = &one; r.out32 = const_cast<float*>(&one);
   GemmEpilogue f = a;
   f.act = act;
-  return omk_gemm_skinny_ok(dt, dt, M, 3 * (int64_t)H, H, a) && omk_gemm_skinny_ok(dt, dt, M, F, H, f) &&
-         omk_gemm_skinny_ok(dt, dt, M, H, H, r) && omk_gemm_skinny_ok(dt, dt, M, H, F, r);
+  const int max_m = om_option(OM_OPT_GEMM_SKINNY_M);
+  return omk_gemm_skinny_ok(dt, dt, M, 3 * (int64_t)H, H, a, max_m) && omk_gemm_skinny_ok(dt, dt, M, F, H, f, max_m) &&
+         omk_gemm_skinny_ok(dt, dt, M, H, H, r, max_m) && omk_gemm_skinny_ok(dt, dt, M, H, F, r, max_m);
 }
 
 static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* w,

@@ -273,8 +273,8 @@ int launch_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void* 
 }  // namespace
 
 // shapes and epilogues the kernel takes (omk_gemm asks before it picks a tile generation)
-bool omk_gemm_skinny_ok(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep) {
-  const int max_m = om_option(OM_OPT_GEMM_SKINNY_M);
+// (max_m: OM_OPT_GEMM_SKINNY_M)
+bool omk_gemm_skinny_ok(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep, int max_m) {
   if (max_m <= 0 || M > max_m || M < 1) return false;
   if (in_dtype != out_dtype || (in_dtype != OM_BF16 && in_dtype != OM_F16)) return false;
   if (N % 16 || K % 128 || N > (int64_t)65535 * 16 || M > (int64_t)65535 * 16) return false;

@@ -1424,97 +1424,65 @@ static int g7_num_cus() {
   return n;
 }
 
-template <typename T, int ACT, int LNF, bool TRAIN = false>
-static int launch7c(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                    int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {
+// The one launcher of the generation-7 kernels.  The persistent families run one workgroup per CU, fewer under OM_OPT_GEMM_MAX_GRID or where
+// the tiles run out; OM_GEMM_FAMILY_G7_ONE_TILE runs one workgroup per tile with the plain group of 8.  The restart-per-tile kernel
+// (OM_GEMM_FAMILY_G7) gets no stagger bits, deliberately: the OM_GEMM_STAGGER probe lives in the continuous kernels only (g7_stagger).
+template <auto KERN, typename T>
+static int g7_launch(int family, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
+                     int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {
   const int64_t ntiles = (M / 256) * (N / 256);
-  if (ntiles >= 0x7fff0000LL) OM_FAIL("gemm: more than 2^31 output tiles");
-  if (TRAIN && (!ep.pre_act || ep.ldp != ldc || ep.drop_p > 0.f || !(ep.act & OM_ACT_PRE_GRAD) || ((uintptr_t)ep.pre_act & 15)))
-    OM_FAIL("two-output GELU epilogue: pre_act with ldp == ldc, OM_ACT_PRE_GRAD, no dropout");
-  int grid = g7_num_cus();
-  const int cap = om_option(OM_OPT_GEMM_MAX_GRID);
-  if (cap > 0 && cap < grid) grid = cap;
-  if (ntiles < grid) grid = (int)ntiles;
+  if (ntiles >= 0x7fff0000LL) OM_FAIL("gemm: more than 2^31 output tiles");      // g7_tile works in 32 bits
+  int grid = (int)ntiles, gm_arg = 8;
+  if (family != OM_GEMM_FAMILY_G7_ONE_TILE) {
+    const int cap = om_option(OM_OPT_GEMM_MAX_GRID);       // > 0: at most this many workgroups (multiples of 8 keep the XCD-aware walk)
+    grid = std::min(grid, cap > 0 ? std::min(cap, g7_num_cus()) : g7_num_cus());
+    gm_arg = (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0) | (family == OM_GEMM_FAMILY_G7 ? 0 : g7_stagger_bits());
+  }
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)gemm_nt_kernel7c16<T, ACT, LNF, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
+    OM_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
     attr_set = true;
   }
   const bool timing = om_timing_on();
   if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
-  const int gm_arg = (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0) | g7_stagger_bits();
-  omk_gemm_note(OM_GEMM_FAMILY_G7C16);
-  hipLaunchKernelGGL((gemm_nt_kernel7c16<T, ACT, LNF, TRAIN>), dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s,
-                     (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, gm_arg);
+  omk_gemm_note(family);
+  hipLaunchKernelGGL(KERN, dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s, (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, gm_arg);
   if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
   OM_LAUNCH_CHECK();
   return 0;
+}
+
+// Preconditions of every generation-7 kernel: the planner admits nothing else, these protect the kernels from another caller.
+static int g7_check(const GemmPlan& p, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep) {
+  if (!gemm_whole_tiles(M, N, K)) OM_FAIL("generation 7 takes whole 256 x 256 tiles and 128-byte K steps");
+  if (p.lnf >= 2 && !ep.stats_out) OM_FAIL("the output-side LayerNorm variant writes row statistics: stats_out is null");
+  if ((ep.out_lo || ep.resid_lo) && p.lnf < 3) OM_FAIL("two-plane residual stream: only with the output-side LayerNorm epilogue");
+  if (ep.ln_stats && (ep.rln_stats || ep.stats_out)) OM_FAIL("fused LayerNorm: either the A side or the output side");
+  return 0;
+}
+
+template <typename T, int ACT, int LNF, bool TRAIN = false>
+static int launch7c(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
+                    int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {
+  if (TRAIN && (!ep.pre_act || ep.ldp != ldc || ep.drop_p > 0.f || !(ep.act & OM_ACT_PRE_GRAD) || ((uintptr_t)ep.pre_act & 15)))
+    OM_FAIL("two-output GELU epilogue: pre_act with ldp == ldc, OM_ACT_PRE_GRAD, no dropout");
+  return g7_launch<gemm_nt_kernel7c16<T, ACT, LNF, TRAIN>, T>(OM_GEMM_FAMILY_G7C16, A, lda, B, ldb, C, ldc, M, N, K, ep, s);
 }
 
 template <typename T, int ACT, int LNF>
 static int launch7r(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
                     int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {
-  const int64_t ntiles = (M / 256) * (N / 256);
-  if (ntiles >= 0x7fff0000LL) OM_FAIL("gemm: more than 2^31 output tiles");
   if (LNF >= 3 && (!ep.out_lo || ((uintptr_t)ep.out_lo & 15) || ((uintptr_t)ep.resid_lo & 15))) OM_FAIL("two-plane residual epilogue: out_lo (and resid_lo) 16-byte aligned planes");
-  int grid = g7_num_cus();
-  const int cap = om_option(OM_OPT_GEMM_MAX_GRID);
-  if (cap > 0 && cap < grid) grid = cap;
-  if (ntiles < grid) grid = (int)ntiles;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)gemm_nt_kernel7r16<T, ACT, LNF>, hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
-    attr_set = true;
-  }
-  const bool timing = om_timing_on();
-  if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
-  const int gm_arg = (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0) | g7_stagger_bits();
-  omk_gemm_note(OM_GEMM_FAMILY_G7R16);
-  hipLaunchKernelGGL((gemm_nt_kernel7r16<T, ACT, LNF>), dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s,
-                     (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, gm_arg);
-  if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
-  OM_LAUNCH_CHECK();
-  return 0;
+  return g7_launch<gemm_nt_kernel7r16<T, ACT, LNF>, T>(OM_GEMM_FAMILY_G7R16, A, lda, B, ldb, C, ldc, M, N, K, ep, s);
 }
 
+// family: which of the kernels this epilogue is instantiated for the planner chose (g7_kernel of gemm_plan.h) -- 7c16 exists without
+// a residual (LNF <= 1), 7r16 with one (every LNF but 1), the restart-per-tile kernel 7 everywhere but for the eight-bit plane (LNF 4)
 template <typename T, int ACT, bool RESID, int LNF>
-static int launch7(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
+static int launch7(int family, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
                    int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {
-  if constexpr (!RESID && LNF <= 1) {      // the continuous ring: needs three K steps (its prefetch reaches at most one tile ahead)
-    if (K * 2 >= 3 * G7_ROW_BYTES && (om_option(OM_OPT_GEMM_CONT) & 1) != 0) return launch7c<T, ACT, LNF>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
-  }
-  if constexpr (RESID && (LNF == 0 || LNF == 2)) {      // one-plane residual variants on the continuous ring (bit 1 of the option)
-    if (K * 2 >= 3 * G7_ROW_BYTES && (om_option(OM_OPT_GEMM_CONT) & 2) != 0) return launch7r<T, ACT, LNF>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
-  }
-  if constexpr (LNF == 4) {                              // float16 with the eight-bit second plane: the continuous kernel only
-    if (K * 2 < 3 * G7_ROW_BYTES) OM_FAIL("two-plane residual epilogue with the eight-bit plane: K >= 192");
-    return launch7r<T, ACT, LNF>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
-  } else {
-  if constexpr (RESID && LNF == 3) {                     // two-plane residual variant on the continuous ring (round 6): bit 8 float16, bit 9 bfloat16
-    // (bfloat16 stays on the restart-per-tile kernel by default: the continuous kernel is 1.3 % faster end to end, but its 16 x 16 x 32 summation
-    // order moves the config-1 fixture's tie-broken MRR@10 from 0.0025 to 0.0037 against the reference's own 0.0035 -- one swapped pair)
-    constexpr int bit = sizeof(T) == 2 && std::is_same<T, bf16_t>::value ? 512 : 256;
-    if (K * 2 >= 3 * G7_ROW_BYTES && (om_option(OM_OPT_GEMM_CONT) & bit) != 0) return launch7r<T, ACT, LNF>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
-  }
-  const int64_t ntiles = (M / 256) * (N / 256);
-  if (ntiles >= 0x7fff0000LL) OM_FAIL("gemm: more than 2^31 output tiles");      // g7_tile works in 32 bits
-  int grid = g7_num_cus();
-  const int cap = om_option(OM_OPT_GEMM_MAX_GRID);       // > 0: at most this many workgroups (multiples of 8 keep the XCD-aware walk)
-  if (cap > 0 && cap < grid) grid = cap;
-  if (ntiles < grid) grid = (int)ntiles;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)gemm_nt_kernel7<T, ACT, RESID, LNF, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
-    attr_set = true;
-  }
-  const bool timing = om_timing_on();
-  if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
-  omk_gemm_note(OM_GEMM_FAMILY_G7);
-  hipLaunchKernelGGL((gemm_nt_kernel7<T, ACT, RESID, LNF, true>), dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s,
-                     (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, (std::max(1, om_option(OM_OPT_GEMM_GROUP_M)) & 0xffff) | (ep.reverse ? 1 << 16 : 0));
-  if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
-  OM_LAUNCH_CHECK();
-  return 0;
-  }
+  if constexpr (!RESID && LNF <= 1) if (family == OM_GEMM_FAMILY_G7C16 && K * 2 >= 3 * G7_ROW_BYTES) return launch7c<T, ACT, LNF>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
+  if constexpr (RESID && LNF != 1) if (family == OM_GEMM_FAMILY_G7R16 && K * 2 >= 3 * G7_ROW_BYTES) return launch7r<T, ACT, LNF>(A, lda, B, ldb, C, ldc, M, N, K, ep, s);
+  if constexpr (LNF != 4) if (family == OM_GEMM_FAMILY_G7) return g7_launch<gemm_nt_kernel7<T, ACT, RESID, LNF, true>, T>(family, A, lda, B, ldb, C, ldc, M, N, K, ep, s);
+  OM_FAIL("generation 7: this epilogue has no kernel of the planned family (or fewer than three K steps for the continuous ring)");
 }

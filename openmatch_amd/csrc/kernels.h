@@ -110,6 +110,17 @@ __host__ __device__ inline size_t omk_lo8_offset(int64_t m, int64_t n, int64_t N
 }
 // (sum, sum of squares) per row from the slot partials a GEMM with stats_out left: out[m] = sum over slots, in slot order
 int omk_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, hipStream_t s);
+// What omk_gemm's planner (gemm_plan.h) decided: the kernel family (OM_GEMM_FAMILY_*; 0: launch nothing -- an empty problem, or a
+// refusal with its reason in `error`) and the kernel coordinates the launchers switch on.  Generation 7's launchers take it as it is.
+struct GemmPlan { int family; const char* error; int act /* ep.act & 0xff */; bool resid, train /* ep.pre_act or dropout */; int lnf /* gemm_lnf */; };
+// The LayerNorm-fusion code (template argument LNF of generation 7) of an epilogue: 0 none, 1 the A operand is a raw pre-norm tensor,
+// 2 normalised residual + row statistics of the output, 3 the same on a two-plane residual stream, 4 with the eight-bit second plane.
+// lo8 is a float16 field: bfloat16 has no eight-bit kernel and takes out_lo as a 16-bit plane whatever lo8 says.
+inline int gemm_lnf(const GemmEpilogue& ep, bool f16) {
+  return ep.ln_stats ? 1 : ((ep.rln_stats || ep.stats_out) ? (ep.out_lo ? (ep.lo8 && f16 ? 4 : 3) : 2) : 0);
+}
+// whole 256 x 256 tiles and 128-byte K steps of a 16-bit operand: what generation 7 takes (the encoder pads its token rows)
+inline bool gemm_whole_tiles(int64_t M, int64_t N, int64_t K) { return M % 256 == 0 && N % 256 == 0 && (K * 2) % 128 == 0; }
 // true when omk_gemm will run [M,N] x K (16-bit) on the kernel that implements the ln_* / rln_* / stats_out fields
 bool omk_gemm_ln_fusable(int dtype, int64_t M, int64_t N, int64_t K);
 unsigned long long* omk_debug_trace();

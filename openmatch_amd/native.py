@@ -110,6 +110,8 @@ _SIGNATURES = {
     "om_debug_option": (c_int, [c_int, c_int]),
     "om_debug_option_value": (c_int, [c_int]),
     "om_debug_gemm_last": (c_int, []),
+    "om_debug_gemm_plan": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                   c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int]),
     "om_debug_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "om_debug_attention_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float,
                                       C.c_uint64, c_void_p, c_int, c_void_p, c_void_p, c_int]),

@@ -247,13 +247,18 @@ def _bits(t):
     return t.view(BITS_DT[{torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}[t.dtype]])
 
 
+def _start(ld, pre, off):
+    """Element offset of a Buf's window inside its flat buffer."""
+    return pre * ld + off
+
+
 class Buf:
     """A strided matrix inside a flat buffer filled with a sentinel: rows * ld elements, `pre` guard rows before and
     `post` after, `off` extra elements of misalignment.  `window` is the [rows, cols] view the kernel may touch."""
 
     def __init__(self, dtype_code, rows, cols, ld, pre=1, post=2, off=0, fill=None):
         self.code, self.rows, self.cols, self.ld = dtype_code, rows, cols, ld
-        self.start = pre * ld + off
+        self.start = _start(ld, pre, off)
         total = (pre + rows + post) * ld + off + 8
         self.flat = torch.empty(total, dtype=TORCH_DT[dtype_code], device=DEV)
         _bits(self.flat).fill_(SENTINEL[dtype_code] - (1 << 32 if dtype_code == F32 and SENTINEL[dtype_code] >= 1 << 31 else 0))
@@ -427,15 +432,25 @@ def test_family_dtype_epilogue(fam, in_dt, out_dt, epi):
             check_case(case, family, f"{fam} {NAME[in_dt]}->{NAME[out_dt]} {epi} M={M} N={Nn} K={K}")
 
 
+FEW_K_STEPS = ((1, "erf"), (2, "bias"), (1, "relu"))      # (K steps, epilogue)
+
+
+def _few_k_opts(dt):
+    return dict(skinny_m=0) if dt == BF16 else dict(skinny_m=0, cont=495 & ~128)
+
+
+def _few_k_size(dt):
+    return 4096 if dt == BF16 else 512
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dt", [BF16, F16], ids=["bf16", "f16"])
 def test_restart_per_tile_kernel_at_one_and_two_k_steps(dt):
     """Fewer than three K steps: whole-tile 16-bit shapes the cost model sends to generation 7 take its restart-per-tile
     kernel (the continuous ring needs three).  bf16 at default options (256 tiles), f16 with bit 7 cleared."""
-    opts = dict(skinny_m=0) if dt == BF16 else dict(skinny_m=0, cont=495 & ~128)
-    with gemm_options(**opts):
-        for ks, epi in ((1, "erf"), (2, "bias"), (1, "relu")):
-            M = Nn = 4096 if dt == BF16 else 512
+    with gemm_options(**_few_k_opts(dt)):
+        for ks, epi in FEW_K_STEPS:
+            M = Nn = _few_k_size(dt)
             case = make_case(dt, dt, M, Nn, steps(dt, ks), epi, seed=ks)
             check_case(case, "g7", f"g7 {NAME[dt]} K steps={ks} {epi}")
 
@@ -598,6 +613,80 @@ ALIGN_CASES = [
 def test_alignment_fallbacks(name, opts, dt, epi, M, Nn, ks, kw, fam):
     with gemm_options(**opts):
         check_case(make_case(dt, dt, M, Nn, steps(dt, ks), epi, seed=M + Nn, **kw), fam, name)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# D'. the decision table without a GPU: om_debug_gemm_plan on the addresses the GPU cases above would pass
+# ---------------------------------------------------------------------------------------------------------------
+_ES = {F32: 4, BF16: 2, F16: 2}
+
+
+def planned_family(in_dt, out_dt, M, Nn, K, epi, lda=None, ldb=None, ldc=None, ldr=None, a_slice=False,
+                   bias_off=0, c_off=0, r_off=0):
+    """om_debug_gemm_plan for the call make_case(the same arguments) + launch would make.  Every buffer make_case allocates
+    gets a made-up base address of its own, 512-byte aligned as the device allocator's are, plus the byte offset of its
+    window (Buf: guard rows, misalignment; the bias slice); the leading dimensions are make_case's."""
+    act, has_bias, rmode = EPI[epi]
+    lda, ldb, ldc = (3 * K if a_slice else lda or K), ldb or K, ldc or Nn
+    bases = iter(range(1 << 30, 1 << 40, 1 << 30))
+    a = next(bases) + (K if a_slice else 0) * _ES[in_dt]
+    b = next(bases)
+    bias = next(bases) + 4 * bias_off if has_bias else None
+    r = None
+    if rmode in ("add", "mul"):
+        ldr = ldr or Nn
+        r = next(bases) + _start(ldr, 0, r_off) * _ES[out_dt]
+    c = next(bases) + _start(ldc, 1, c_off) * _ES[out_dt]
+    if rmode == "inplace":
+        r, ldr = c, ldc
+    return N.lib().om_debug_gemm_plan(in_dt, a, lda, b, ldb, out_dt, c, ldc, M, Nn, K, bias, r, ldr if r else 0,
+                                      act | (N.ACT_MUL_RESID if rmode == "mul" else 0))
+
+
+def _decision_table():
+    """(label, options, in, out, M, N, K, epilogue, make_case kwargs, family) of every case of the GPU tables above, with the
+    family the GPU test asserts through om_debug_gemm_last."""
+    for fam, (opts, pairs, epis, shapes) in FAMILIES.items():
+        for i, o in pairs:
+            for e in epis:
+                for M, Nn, ks in shapes:
+                    yield f"A {fam}", opts, i, o, M, Nn, steps(i, ks), e, {}, _family_code(fam)
+    for i, o, M, Nn, K, e, fam in SELFTEST_QUICK:
+        yield "quick", {}, i, o, M, Nn, K, e, {}, fam
+    for c in GEN7_CASES:
+        gen, M, Nn, K, e, fam = c.values
+        yield "gen7 list", dict(gen=gen, cont=495 | 16, skinny_m=0), BF16, BF16, M, Nn, K, e, {}, fam
+    for name, opts, dt, e, M, Nn, ks, kw, fam in ALIGN_CASES:
+        yield name, opts, dt, dt, M, Nn, steps(dt, ks), e, kw, fam
+    for dt in (BF16, F16):
+        for ks, e in FEW_K_STEPS:
+            yield "few K steps", _few_k_opts(dt), dt, dt, _few_k_size(dt), _few_k_size(dt), steps(dt, ks), e, {}, "g7"
+
+
+def test_decision_table_without_a_gpu():
+    """The planner alone (no launch, no GPU) names, for every case of FAMILIES, the quick list, the gen7 list, ALIGN_CASES and
+    the one- and two-K-step cases, the family the GPU test of that case asserts."""
+    wrong, n = [], 0
+    for label, opts, i, o, M, Nn, K, e, kw, fam in _decision_table():
+        gen, opts = _opts(opts)
+        with gemm_options(gen=gen, **opts):
+            got = planned_family(i, o, M, Nn, K, e, **kw)
+        n += 1
+        if got != FAM[fam]:
+            wrong.append((label, opts, gen, NAME[i], NAME[o], M, Nn, K, e, kw, fam, got))
+    assert n == (sum(len(p) * len(e) * len(sh) for _, p, e, sh in FAMILIES.values()) + len(SELFTEST_QUICK) + len(GEN7_CASES) +
+                 len(ALIGN_CASES) + 2 * len(FEW_K_STEPS)), n
+    assert not wrong, f"{len(wrong)} of {n} cases planned another family, e.g. {wrong[:5]}"
+    # refusals and empty problems: what om_gemm_nt answers with an error is negative, what it skips is 0
+    assert N.lib().om_debug_gemm_plan(F32, 16, 33, 16, 33, F32, 16, 8, 4, 8, 33, None, None, 0, 0) < 0
+    assert N.lib().om_debug_gemm_plan(BF16, 1 << 30, 64, 2 << 30, 64, BF16, 3 << 30, 8, 0, 8, 64, None, None, 0, 0) == 0
+
+
+def test_plan_hook_leaves_the_last_family_alone():
+    lib = N.lib()
+    assert lib.om_gemm_nt(F32, 16, 33, 16, 33, F32, 16, 8, 4, 8, 33, None, None, 0, 0, None) != 0      # refused: last = 0
+    assert planned_family(BF16, BF16, 4096, 768, 768, "erf") in FAM.values()
+    assert lib.om_debug_gemm_last() == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------
