@@ -109,9 +109,12 @@ int om_debug_gemm_plan(int in_dtype, const void* A, int64_t lda, const void* B, 
  * shapes allow (default), 0 = one normalisation kernel per site; OM_OPT_ENCODER_DEBUG 1 = log the path taken. */
 #define OM_OPT_ENCODER_FUSED_LN 0
 #define OM_OPT_ENCODER_DEBUG 1
-#define OM_OPT_ATTENTION_FAST 2   /* 1 (default): bf16 inference attention on the low-instruction-count kernel; 0: the generic kernel; bit 1 (tests): the
-                                     tile-at-a-time kernels that serve more than 256 tokens (forward with dropout, backward) at every length; bit 2 (A/B):
-                                     beyond 256 tokens the first online-softmax kernel instead of the chunked fast one (round 6) */
+#define OM_OPT_ATTENTION_FAST 2   /* bit mask (default 1), read once per call by the attention planners (csrc/attn_plan.h; DESIGN.md 4c lists the rules).
+                                     bit 0: bfloat16 on the 16-bit kernels -- forward the low-instruction-count and chunked ones, backward the
+                                     transposing-read one up to 128 tokens and the tile-at-a-time one from 193 (cleared: the generic kernels; float16
+                                     has no others in the forward); bit 1 (tests): the kernels that serve more than 256 tokens -- online-softmax
+                                     forward, tile-at-a-time backward -- at every length in the 16-bit formats; bit 2 (A/B): the first online-softmax
+                                     forward kernel instead of the chunked 16-bit one */
 #define OM_OPT_SCAN_GEN7 3        /* 1 (default): f16 index scan of wide query batches on the persistent generation-7 kernel; 0: generation 6 */
 #define OM_OPT_SCAN_GROWTH 4      /* fast schedule of the index scan: rows scanned per round grow by this many percent of the rows already
                                     * scanned (default 60; smaller = more rounds, tighter thresholds, fewer appends per tile) */
@@ -188,9 +191,9 @@ int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, vo
 int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
 /* cu [B + 2], cls_rows [B], row_map [rows] of the packed layout (csrc/kernels.h omk_pack_rows) */
 int om_debug_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, void* stream);
-/* The kernel family of the last attention forward launcher the calling thread reached, family | key tiles << 8 (key tiles: 32-key
- * tiles a workgroup holds at once: the template's KT, 4 for the kernels that walk 128-key chunks).  Each launcher stores its code;
- * the attention entry points store 0 on entry, before any argument check, so a call that launches nothing reads 0.  One host store
+/* The kernel family of the calling thread's last attention forward launch, family | key tiles << 8 (key tiles: 32-key tiles a
+ * workgroup holds at once: the template's KT, 4 for the kernels that walk 128-key chunks).  The one forward entry (csrc/kernels.h
+ * omk_attention) stores 0 on entry and its plan's code before it launches, so a call that launches nothing reads 0.  One host store
  * per launch, nothing on the device. */
 #define OM_ATTN_FAMILY_GENERIC 1      /* attention_kernel: f32, and bf16 with OM_OPT_ATTENTION_FAST = 0, up to 256 tokens   */
 #define OM_ATTN_FAMILY_FWD16 2        /* attention_fwd16_kernel: 16-bit, up to 256 tokens                                     */
@@ -202,6 +205,19 @@ int om_debug_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu,
 #define OM_ATTN_FAMILY_BAND16 7       /* attention_band16_kernel                                                              */
 #define OM_ATTN_FAMILY_BAND32 8       /* attention_band32_kernel                                                              */
 int om_debug_attention_last(void);
+/* host only (no GPU needed): what the forward entry would launch for these arguments at the current switches (csrc/attn_plan.h
+ * attn_plan_fwd; has_*: whether the optional pointer is given; w: the half window) -- family | key tiles << 8, 0 when nothing would
+ * launch (an empty batch), -1 for a refusal with its reason in om_last_error.  Leaves the last-launch words alone. */
+int om_debug_attention_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, float drop_p, int has_kmax, int has_cu, int w);
+/* The same pair for the attention backward of a training step (csrc/train_kernels.h omk_attention_bwd, attn_plan_bwd; packed: the
+ * step runs over packed rows).  The last-launch word is the PROCESS's, not the thread's: torch's autograd engine runs a backward on
+ * a thread of its own. */
+#define OM_ATTN_BWD_FAMILY_BWD16 1    /* attention_bwd16_kernel: transposing LDS reads, 16-bit, up to 128 tokens                 */
+#define OM_ATTN_BWD_FAMILY_GENERIC 2  /* attention_bwd_kernel: a whole score row in registers, up to 256 tokens (float32: 192)    */
+#define OM_ATTN_BWD_FAMILY_LONG 3     /* attention_bwd_long_a / _b_kernel: two passes, one score tile at a time, 16-bit, up to 512 */
+#define OM_ATTN_BWD_FAMILY_D32 4      /* attention_d32_bwd_kernel: 32-wide heads, up to 256 tokens                               */
+int om_debug_attention_bwd_last(void);
+int om_debug_attention_bwd_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, int has_drel, int has_cu, int packed);
 /* host only: 1 if attention-probability dropout keeps (b, h, q, key) at rate p under `seed`; Lm is the mask's row pitch */
 int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, int q, int key, float p);
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly

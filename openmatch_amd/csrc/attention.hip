@@ -1,7 +1,12 @@
-// Fused self-attention for short sequences (L <= 256, head_dim 64), gfx950.
+// Fused self-attention, head_dim 64, gfx950, and omk_attention, the one forward entry of every attention kernel.
 // Replaces BertSelfAttention / T5Attention score+softmax+context
-// (HF:models/bert/modeling_bert.py:111-136, HF:models/t5/modeling_t5.py:176-370, eval mode).
+// (HF:models/bert/modeling_bert.py:111-136, HF:models/t5/modeling_t5.py:176-370; with dropout for training).
 //
+// omk_attention (at the end of this file) is: plan (attn_plan.h: argument checks, kernel family, key tiles, template flags), switch on
+// the family, launch -- the kernels of this file (generic, 16-bit up to 256 tokens, 16-bit chunked, first online-softmax kernel) or the
+// launchers of attention_d32.hip (32-wide heads) and attention_band.hip (a window).  No launcher here checks an argument or reads a switch.
+//
+// The generic kernel (attention_kernel, L <= 256):
 // One workgroup per (batch, head); one wavefront per 32 query rows.  K is staged in LDS
 // row-major (XOR-swizzled 16-byte slots), V is staged TRANSPOSED ([d][key], +4 pad) so both
 // MFMA B-operands are contiguous LDS reads.  Scores are computed swapped (S^T = K Q^T): with
@@ -11,9 +16,9 @@
 #include <type_traits>
 
 #include "attn_common.h"
+#include "attn_plan.h"
 
-static thread_local int g_attn_last = 0;
-void omk_attn_note(int family, int kt) { g_attn_last = family | (kt << 8); }
+static thread_local int g_attn_last = 0;      // family | key tiles << 8 of this thread's last forward launch: omk_attention writes it from its plan
 extern "C" int om_debug_attention_last(void) { return g_attn_last; }
 
 template <typename T, int KT>
@@ -387,15 +392,10 @@ __global__ __launch_bounds__(64 * KT, KT <= 4 ? ((BIAS || DROP) ? 3 : 4) : 2) vo
 }
 
 template <typename T, int KT, bool BIAS, bool DROP>
-static int launch_attn16_(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
-                         int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu = nullptr) {
+static int launch_attn16(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
+                         int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
   const int lds = 2 * KT * 32 * 128 + KT * 32 * 4;
-  omk_attn_note((KT == 4 && !BIAS && !DROP && (kmax || cu)) ? OM_ATTN_FAMILY_FWD16_KMAX4 : OM_ATTN_FAMILY_FWD16, KT);
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_fwd16_kernel<T, KT, BIAS, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_fwd16_kernel<T, KT, BIAS, DROP>>(lds)) return 1;
   // The timing variants (parts of the kernel compiled out: their results are WRONG) exist in probe builds only
   // (-DOM_PROBE_KERNELS: python -m openmatch_amd._build --probe); the product library ignores OM_OPT_ATTENTION_DEBUG.
 #ifdef OM_PROBE_KERNELS
@@ -421,23 +421,6 @@ static int launch_attn16_(const void* qkv, void* ctx, const int64_t* mask, const
   OM_LAUNCH_CHECK();
   return 0;
 }
-template <typename T, int KT>
-static int launch_attn16(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
-                         int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu = nullptr) {
-  if (std::is_same<T, f16_t>::value) {            // float16: BERT-family encoders; dropout for float16 training, T5's bias table for inference (round 5)
-    if (pos_bias && drop_p > 0.f) return launch_attn16_<f16_t, KT, true, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);   // float16 T5 training (round 6)
-    if (pos_bias) return launch_attn16_<f16_t, KT, true, false>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
-    if (drop_p > 0.f) return launch_attn16_<f16_t, KT, false, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-    return launch_attn16_<T, KT, false, false>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
-  }
-  if (drop_p > 0.f) {
-    if (pos_bias) return launch_attn16_<bf16_t, KT, true, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-    return launch_attn16_<bf16_t, KT, false, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  }
-  if (pos_bias) return launch_attn16_<bf16_t, KT, true, false>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
-  return launch_attn16_<bf16_t, KT, false, false>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Beyond 256 tokens in the 16-bit formats (round 6): the body of the kernel above inside a loop over 128-key chunks with the online
 // softmax.  A workgroup owns 128 queries of one (sequence, head) -- four waves of 32 -- and per chunk: K and V rows by LDS-DMA
@@ -615,24 +598,14 @@ __global__ __launch_bounds__(256, 2) void attention_fwd16c_kernel(
 }
 
 template <typename T, bool BIAS, bool DROP>
-static int launch_attn16c_(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
+static int launch_attn16c(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
                            int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
   const int lds = 2 * 128 * 128 + 128 * 4;
-  omk_attn_note(OM_ATTN_FAMILY_FWD16C, 4);
   hipLaunchKernelGGL((attention_fwd16c_kernel<T, BIAS, DROP>), dim3((unsigned)(heads * B), (unsigned)((L + 127) / 128)), dim3(256), lds, s,
                      (const T*)qkv, (T*)ctx, mask, pos_bias, L, H, heads, scale, drop_p, seed, cu);
   OM_LAUNCH_CHECK();
   return 0;
 }
-template <typename T>
-static int launch_attn16c(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
-                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
-  if (pos_bias && drop_p > 0.f) return launch_attn16c_<T, true, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, cu);
-  if (pos_bias) return launch_attn16c_<T, true, false>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, cu);
-  if (drop_p > 0.f) return launch_attn16c_<T, false, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, cu);
-  return launch_attn16c_<T, false, false>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, cu);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Long sequences (256 < L <= 1024, inference): the kernels above keep a whole score row per lane (L / 2 registers) and
 // all of K, V in LDS, which stops at 256 keys.  Document corpora are encoded at 512 tokens (the reference accepts anything
@@ -792,14 +765,9 @@ __global__ __launch_bounds__(256) void attention_long_kernel(
 
 template <typename T>
 static int launch_attn_long(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
-                            int heads, float scale, hipStream_t s, float drop_p = 0.f, uint64_t seed = 0, const int* cu = nullptr) {
+                            int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu) {
   const int lds = 128 * AttnGeom<T>::ROWB + 64 * 132 * (int)sizeof(T) + 128 * 4 + 128 * 4;
-  omk_attn_note(OM_ATTN_FAMILY_LONG, 4);
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_long_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_long_kernel<T>>(lds)) return 1;
   hipLaunchKernelGGL((attention_long_kernel<T>), dim3((unsigned)(heads * B), (unsigned)((L + 127) / 128)), dim3(256), lds, s,
                      (const T*)qkv, (T*)ctx, mask, pos_bias, L, H, heads, scale, drop_p, seed, cu);
   OM_LAUNCH_CHECK();
@@ -812,30 +780,13 @@ static int launch_attn(const void* qkv, void* ctx, const int64_t* mask, const fl
                        hipStream_t s) {
   constexpr int LP = KT * 32 + 4;
   const int lds = KT * 32 * AttnGeom<T>::ROWB + 64 * LP * (int)sizeof(T) + KT * 32 * 4;
-  omk_attn_note(OM_ATTN_FAMILY_GENERIC, KT);
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_kernel<T, KT>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_kernel<T, KT>>(lds)) return 1;
   const int waves = (L + 31) / 32;
   hipLaunchKernelGGL((attention_kernel<T, KT>), dim3((unsigned)(heads * B)),
                      dim3(64 * waves), lds, s, (const T*)qkv, (T*)ctx, mask, pos_bias, L, H, heads,
                      scale, drop_p, seed);
   OM_LAUNCH_CHECK();
   return 0;
-}
-
-template <typename T>
-static int dispatch_attn(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias,
-                         int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                         hipStream_t s) {
-  if (L <= 32) return launch_attn<T, 1>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
-  if (L <= 64) return launch_attn<T, 2>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
-  if (L <= 128) return launch_attn<T, 4>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
-  if (L <= 192) return launch_attn<T, 6>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
-  return launch_attn<T, 8>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
 }
 
 // kmax[b] = 1 + the last unmasked key of batch row b (L when the row has none): once per forward, read by every layer's
@@ -897,60 +848,56 @@ int omk_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, hipStream_
   return 0;
 }
 
-int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
-                  const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
-                  float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu) {
-  omk_attn_note(0, 0);
-  if (B <= 0) return 0;
-  if (H == heads * 32) return omk_attention_d32(dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
-  if (cu && !(dtype == OM_F16 || (dtype == OM_BF16 && om_option(OM_OPT_ATTENTION_FAST))))
-    OM_FAIL("packed rows: the 16-bit attention kernels");      // (with dropout too: the packed training forward, round 5; beyond 256 tokens: round 6)
-  if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
-  if (L > 256 && drop_p > 0.f && (L > 512 || dtype == OM_F32)) OM_FAIL("attention with dropout: up to 512 tokens in the 16-bit formats (float32: 256)");
-  if (H != heads * 64) OM_FAIL("head_dim must be 64");
-  if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
-  // OM_OPT_ATTENTION_FAST bit 1 (tests): the tile-at-a-time kernels of L > 256 at every length (their masks and results must agree with the others')
-  const bool force_long = (om_option(OM_OPT_ATTENTION_FAST) & 2) != 0 && dtype != OM_F32;
-  if (dtype == OM_F16) {                                      // float16 inference mode: the fast kernel only
-    if (L > 256 || force_long) {
-      if (!(om_option(OM_OPT_ATTENTION_FAST) & 4)) return launch_attn16c<f16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, cu);
-      return launch_attn_long<f16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, s, drop_p, seed, cu);      // (bit 2, A/B: the first online-softmax kernel)
-    }
-    if (L <= 32) return launch_attn16<f16_t, 1>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    if (L <= 64) return launch_attn16<f16_t, 2>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    if (L <= 128) return launch_attn16<f16_t, 4>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    if (L <= 192) return launch_attn16<f16_t, 6>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    return launch_attn16<f16_t, 8>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+// plan (attn_plan.h), switch on the family, launch
+int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H, int heads,
+                  float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu, int w) {
+  g_attn_last = 0;
+  const AttnPlan p = attn_plan_fwd(dtype, B, L, H, heads, pos_bias != nullptr, drop_p, kmax != nullptr, cu != nullptr, w, attn_switches());
+  if (p.error) OM_FAIL(p.error);
+  g_attn_last = p.family | (p.kt << 8);
+  switch (p.family) {
+    case 0: return 0;                                   // an empty batch
+    case OM_ATTN_FAMILY_D32: return omk_attention_d32(p, dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+    case OM_ATTN_FAMILY_BAND16: case OM_ATTN_FAMILY_BAND32: return omk_attention_band(dtype, qkv, ctx, mask, B, L, H, heads, scale, w, kmax, s);
+    case OM_ATTN_FAMILY_FWD16: case OM_ATTN_FAMILY_FWD16_KMAX4:
+      return attn_with_type16(dtype, [&](auto t) {
+        return attn_with_kt<1, 2, 4, 6, 8>(p.kt, [&](auto kt) {
+          return attn_with_flags(p.bias, p.drop, [&](auto bias, auto drop) {
+            return launch_attn16<decltype(t), kt(), bias(), drop()>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+          });
+        });
+      });
+    case OM_ATTN_FAMILY_FWD16C:
+      return attn_with_type16(dtype, [&](auto t) {
+        return attn_with_flags(p.bias, p.drop, [&](auto bias, auto drop) {
+          return launch_attn16c<decltype(t), bias(), drop()>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, cu);
+        });
+      });
+    case OM_ATTN_FAMILY_LONG:
+      return attn_with_type(dtype, [&](auto t) { return launch_attn_long<decltype(t)>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, cu); });
+    default:                                            // OM_ATTN_FAMILY_GENERIC: float32 and bfloat16
+      if (dtype == OM_BF16)
+        return attn_with_kt<1, 2, 4, 6, 8>(p.kt, [&](auto kt) { return launch_attn<bf16_t, kt()>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s); });
+      return attn_with_kt<1, 2, 4, 6, 8>(p.kt, [&](auto kt) { return launch_attn<float, kt()>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s); });
   }
-  if (L > 256 || force_long) {                                // online-softmax kernel, any dtype
-    if (dtype == OM_BF16 && om_option(OM_OPT_ATTENTION_FAST) && !(om_option(OM_OPT_ATTENTION_FAST) & 4))
-      return launch_attn16c<bf16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, cu);
-    if (dtype == OM_BF16) return launch_attn_long<bf16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, s, drop_p, seed, cu);
-    return launch_attn_long<float>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, s);
-  }
-  if (dtype == OM_BF16 && om_option(OM_OPT_ATTENTION_FAST)) {        // the low-instruction-count kernel (inference, and training with dropout)
-    if (L <= 32) return launch_attn16<bf16_t, 1>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    if (L <= 64) return launch_attn16<bf16_t, 2>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    if (L <= 128) return launch_attn16<bf16_t, 4>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    if (L <= 192) return launch_attn16<bf16_t, 6>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-    return launch_attn16<bf16_t, 8>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  }
-  if (dtype == OM_BF16) return dispatch_attn<bf16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
-  return dispatch_attn<float>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s);
+}
+
+// host only: what omk_attention would launch for these arguments at the current switches -- family | key tiles << 8, 0 when nothing
+// would launch, -1 for a refusal (its reason in om_last_error); the last-launch word is not touched
+extern "C" int om_debug_attention_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, float drop_p, int has_kmax, int has_cu, int w) {
+  const AttnPlan p = attn_plan_fwd(dtype, B, L, H, heads, has_bias != 0, drop_p, has_kmax != 0, has_cu != 0, w, attn_switches());
+  if (p.error) { om_set_error(std::string(__func__) + ": " + p.error); return -1; }
+  return p.family | (p.kt << 8);
 }
 
 extern "C" int om_debug_attention_ex(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
                                      int heads, float scale, float drop_p, uint64_t seed, void* stream, int reverse, const int* kmax,
                                      const int* cu, int w) {
-  omk_attn_note(0, 0);
+  g_attn_last = 0;
   if (!qkv || !ctx || !mask) OM_FAIL("null argument");
   if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("attention: dtype must be OM_F32, OM_BF16 or OM_F16");
-  if (w > 0) {
-    if (pos_bias || drop_p > 0.f || cu || reverse) OM_FAIL("banded attention: no position bias, dropout, packed rows or reverse walk");
-    return omk_attention_band(dtype, qkv, ctx, mask, B, L, H, heads, scale, w, kmax, (hipStream_t)stream);
-  }
-  return omk_attention(dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, (hipStream_t)stream, reverse, kmax, cu);
+  if (w > 0 && (pos_bias || drop_p > 0.f || cu || reverse)) OM_FAIL("banded attention: no position bias, dropout, packed rows or reverse walk");
+  return omk_attention(dtype, qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, (hipStream_t)stream, reverse, kmax, cu, w);
 }
 extern "C" int om_debug_attention(const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, void* stream) {
   return om_debug_attention_ex(OM_BF16, qkv, ctx, mask, nullptr, B, L, H, heads, 0.125f, 0.f, 0, stream, 0, nullptr, nullptr, 0);

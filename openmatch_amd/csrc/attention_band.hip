@@ -18,7 +18,8 @@
 //     unmasked key averages the values it visited instead of producing NaN, and keys past L stay -inf.
 //     16-bit: the key-chunked kernel of attention.hip (attention_fwd16c_kernel: LDS-DMA, transposing V reads, exp2);
 //     float32: the generic online-softmax kernel (attention_long_kernel's layout, queries in registers).
-//     w <= 0 or w >= L - 1 is full attention: omk_attention as it stands.
+//     Launch only: omk_attention (attention.hip) sends a call here when its planner (attn_plan.h) finds 0 < w < L - 1; a window
+//     that reaches every key is full attention and never arrives.
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -421,24 +422,13 @@ int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStre
   return 0;
 }
 
+// launch only: attn_plan_fwd (attn_plan.h) has checked the arguments and found 0 < w < L - 1
 int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
                        int w, const int* kmax, hipStream_t s) {
-  omk_attn_note(0, 0);
-  if (B <= 0) return 0;
-  if (w <= 0 || w >= L - 1)                                 // every key within reach: full attention
-    return omk_attention(dtype, qkv, ctx, mask, nullptr, B, L, H, heads, scale, 0.f, 0, s, 0, kmax);
-  if (H != heads * 64) OM_FAIL("banded attention: head_dim must be 64");
-  if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
-  if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
   const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
-  omk_attn_note(dtype == OM_F32 ? OM_ATTN_FAMILY_BAND32 : OM_ATTN_FAMILY_BAND16, 4);
   if (dtype == OM_F32) {
     const int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-      OM_HIP(hipFuncSetAttribute((const void*)attention_band32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr_set = true;
-    }
+    if (attn_lds_once<attention_band32_kernel>(lds)) return 1;
     hipLaunchKernelGGL(attention_band32_kernel, grid, dim3(256), lds, s, (const float*)qkv, (float*)ctx, mask, L, H, heads, scale, w, kmax);
   } else {
     const int lds = 2 * 128 * 128 + 128 * 4;

@@ -7,7 +7,8 @@
 //   dPd = dO V^T ; dP = dropout'(dPd) ; delta = rowsum(P o dP) ; dS = P o (dP - delta) * scale
 //   dQ = dS K ; dK = dS^T Q ; dV = Pd^T dO
 //
-// The generic kernel (train_kernels.hip, still used for f32, T5 biases and L > 128) recomputes the scores in a second,
+// The generic kernel (train_kernels.hip, still used for f32, for L > 128 and with OM_OPT_ATTENTION_FAST = 0; attn_plan.h decides, this
+// file only launches) recomputes the scores in a second,
 // lane-per-key orientation for dK / dV -- exponentials and dropout hashes twice -- and builds three transposed LDS
 // images with 2-byte stores: 153 us per layer at 72 x 12 heads x 128 tokens for ~15 MFLOP per head
 // (profiles/r02_train_kernel_stats_v3.csv).  Here:
@@ -26,6 +27,7 @@
 #include <atomic>
 
 #include "attn_common.h"
+#include "attn_plan.h"
 #include "train_kernels.h"
 
 namespace {
@@ -305,11 +307,7 @@ int launch_bwd16(const void* qkv, const void* dctx, void* dqkv, const int64_t* m
                  float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias, float* drel) {
   constexpr int LT = KT * 32;
   const int lds = 2 * LT * PITCH + 2 * LT * (LT * 2 + 8) + LT * 4 + (BIAS ? 2 * LT * 4 : 0);
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_bwd16_kernel<T, KT, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_bwd16_kernel<T, KT, BIAS>>(lds)) return 1;
   hipLaunchKernelGGL((attention_bwd16_kernel<T, KT, BIAS>), dim3((unsigned)(heads * B)), dim3(64 * KT), lds, s, (const bf16_t*)qkv,
                      (const bf16_t*)dctx, (bf16_t*)dqkv, mask, L, H, heads, scale, drop_p, seed, cu, pos_bias, drel);
   OM_LAUNCH_CHECK();
@@ -317,23 +315,14 @@ int launch_bwd16(const void* qkv, const void* dctx, void* dqkv, const int64_t* m
 }
 }  // namespace
 
-bool omk_attention_bwd16_ok(int dtype, int L, int H, int heads) {
-  return (dtype == OM_BF16 || dtype == OM_F16) && L >= 1 && L <= 128 && H == heads * 64 && om_option(OM_OPT_ATTENTION_FAST);
-}
-
-int omk_attention_bwd16(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
-                        int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias, float* drel) {
-  if (B <= 0) return 0;
-  if ((pos_bias != nullptr) != (drel != nullptr)) OM_FAIL("attention backward: the position bias and its gradient buffer go together");
-#define BWD16_(TT, BB)                                                                                                            \
-  do {                                                                                                                            \
-    if (L <= 32) return launch_bwd16<TT, 1, BB>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);   \
-    if (L <= 64) return launch_bwd16<TT, 2, BB>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);   \
-    return launch_bwd16<TT, 4, BB>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);                \
-  } while (0)
-#define BWD16(TT) do { if (pos_bias) BWD16_(TT, true); else BWD16_(TT, false); } while (0)
-  if (dtype == OM_F16) BWD16(f16_t);
-  BWD16(bf16_t);
-#undef BWD16
-#undef BWD16_
+// launch only: attn_plan_bwd (attn_plan.h) admits 16-bit calls of up to 128 tokens, a position bias together with its gradient buffer
+int omk_attention_bwd16(const AttnPlan& p, int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L,
+                        int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias,
+                        float* drel) {
+  return attn_with_type16(dtype, [&](auto t) {
+    return attn_with_kt<1, 2, 4>(p.kt, [&](auto kt) {
+      if (p.bias) return launch_bwd16<decltype(t), kt(), true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+      return launch_bwd16<decltype(t), kt(), false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+    });
+  });
 }

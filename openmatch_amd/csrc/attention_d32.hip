@@ -1,6 +1,7 @@
 // Self-attention for 32-wide heads (MiniLM-L6, e5-small, bge-small, gte-small: hidden 384, 12 heads), gfx950.
 // Forward up to 1 024 tokens in every format, backward up to 256 tokens.  The head-dim-64 kernels (attention.hip,
-// attention_bwd16.hip, train_kernels.hip) are not touched: omk_attention / omk_attention_bwd* send H == heads * 32 here.
+// attention_bwd16.hip, train_kernels.hip) are not touched.  Launch only: the planners (attn_plan.h) check the arguments and choose the tile
+// count; omk_attention / omk_attention_bwd send their D32 family here.
 //
 // Forward (attention_d32_fwd_kernel): one workgroup per (sequence, head, 32 W queries), one wave per 32 queries.  The keys
 // are walked in chunks of KT * 32 (one chunk for L <= 256) with the online softmax; per chunk K sits in LDS row-major
@@ -17,6 +18,7 @@
 // over every fourth 32-row block, with the three transposed images K^T, Q^T, dO^T ([32][L + 4]) in LDS: 100 KiB at 256 tokens
 // in float32, so float32 trains to 256 tokens as well.  No instantiation spills to scratch.
 #include "attn_common.h"
+#include "attn_plan.h"
 #include "train_kernels.h"
 
 namespace {
@@ -224,36 +226,12 @@ int launch_fwd(const void* qkv, void* ctx, const int64_t* mask, const float* pos
                uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
   constexpr int KC = KT * 32;
   const int lds = KC * D32<T>::ROWB + 32 * (KC + 4) * (int)sizeof(T) + KC * 4;
-  omk_attn_note(OM_ATTN_FAMILY_D32, KT);
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_d32_fwd_kernel<T, KT, DROP, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_d32_fwd_kernel<T, KT, DROP, BIAS>>(lds)) return 1;
   const int waves = L < 256 ? (L + 31) / 32 : 8;
   hipLaunchKernelGGL((attention_d32_fwd_kernel<T, KT, DROP, BIAS>), dim3((unsigned)(heads * B), (unsigned)((L + 32 * waves - 1) / (32 * waves))),
                      dim3(64 * waves), lds, s, (const T*)qkv, (T*)ctx, mask, pos_bias, L, H, heads, scale, drop_p, seed, rev, kmax, cu);
   OM_LAUNCH_CHECK();
   return 0;
-}
-
-template <typename T, bool DROP, bool BIAS>
-int dispatch_fwd(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H, int heads, float scale, float drop_p,
-                 uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
-  if (L <= 32) return launch_fwd<T, 1, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (L <= 64) return launch_fwd<T, 2, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (L <= 128) return launch_fwd<T, 4, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (L <= 192) return launch_fwd<T, 6, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  return launch_fwd<T, 8, DROP, BIAS>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);      // beyond 256: 256-key chunks
-}
-
-template <typename T>
-int dispatch_fwd_t(const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
-                   float drop_p, uint64_t seed, hipStream_t s, int rev, const int* kmax, const int* cu) {
-  if (pos_bias && drop_p > 0.f) return dispatch_fwd<T, true, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  if (pos_bias) return dispatch_fwd<T, false, true>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
-  if (drop_p > 0.f) return dispatch_fwd<T, true, false>(qkv, ctx, mask, nullptr, B, L, H, heads, scale, drop_p, seed, s, rev, kmax, cu);
-  return dispatch_fwd<T, false, false>(qkv, ctx, mask, nullptr, B, L, H, heads, scale, 0.f, 0, s, rev, kmax, cu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -498,59 +476,35 @@ int launch_bwd(const void* qkv, const void* dctx, void* dqkv, const int64_t* mas
                float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias, float* drel) {
   constexpr int LP = KT * 32 + 4;
   const int lds = 3 * 32 * LP * (int)sizeof(T) + 4 * KT * 32 * 4 + (BIAS ? 2 * KT * 32 * 4 : 0);      // (by the tile count, like every other term: the attribute below is set once)
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_d32_bwd_kernel<T, KT, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_d32_bwd_kernel<T, KT, BIAS>>(lds)) return 1;
   hipLaunchKernelGGL((attention_d32_bwd_kernel<T, KT, BIAS>), dim3((unsigned)(heads * B)), dim3(64 * (L < 128 ? (L + 31) / 32 : 4)), lds, s, (const T*)qkv,
                      (const T*)dctx, (T*)dqkv, mask, L, H, heads, scale, drop_p, seed, cu, pos_bias, drel);
   OM_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename T, bool BIAS>
-int dispatch_bwd(const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
-                 float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias, float* drel) {
-  if (L <= 32) return launch_bwd<T, 1, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  if (L <= 64) return launch_bwd<T, 2, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  if (L <= 128) return launch_bwd<T, 4, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  if (L <= 192) return launch_bwd<T, 6, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  return launch_bwd<T, 8, BIAS>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-}
-
 }  // namespace
 
-int omk_attention_d32(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
-                      int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu) {
-  if (B <= 0) return 0;
-  if (H != heads * 32) OM_FAIL("head_dim 32: H must be heads * 32");
-  if (cu && dtype != OM_F16 && dtype != OM_BF16) OM_FAIL("packed rows: the 16-bit attention kernels");
-  if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
-  if (L > 256 && drop_p > 0.f && (L > 512 || dtype == OM_F32)) OM_FAIL("attention with dropout: up to 512 tokens in the 16-bit formats (float32: 256)");
-  if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
-  if (dtype == OM_F16) return dispatch_fwd_t<f16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  if (dtype == OM_BF16) return dispatch_fwd_t<bf16_t>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  if (dtype == OM_F32) return dispatch_fwd_t<float>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
-  OM_FAIL("attention: dtype must be OM_F32, OM_BF16 or OM_F16");
+// launch only: attn_plan_fwd (attn_plan.h) has checked the arguments and chosen the tile count and the flags
+int omk_attention_d32(const AttnPlan& p, int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L,
+                      int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu) {
+  return attn_with_type(dtype, [&](auto t) {
+    return attn_with_kt<1, 2, 4, 6, 8>(p.kt, [&](auto kt) {      // (8: beyond 256 tokens too, in 256-key chunks)
+      return attn_with_flags(p.bias, p.drop, [&](auto bias, auto drop) {
+        return launch_fwd<decltype(t), kt(), drop(), bias()>(qkv, ctx, mask, pos_bias, B, L, H, heads, scale, drop_p, seed, s, reverse, kmax, cu);
+      });
+    });
+  });
 }
 
-int omk_attention_bwd_d32(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
-                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias,
+// launch only: attn_plan_bwd
+int omk_attention_bwd_d32(const AttnPlan& p, int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L,
+                          int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias,
                           float* drel) {
-  if (B <= 0) return 0;
-  if (H != heads * 32) OM_FAIL("head_dim 32: H must be heads * 32");
-  if (L < 1 || L > 256) OM_FAIL("training with head_dim 32 supports sequence lengths up to 256");
-  if (cu && dtype != OM_F16 && dtype != OM_BF16) OM_FAIL("packed rows: attention backward for 16-bit formats");
-  if (B * heads > 0x7fffffffLL) OM_FAIL("batch too large for one launch");
-  if ((pos_bias != nullptr) != (drel != nullptr)) OM_FAIL("attention backward: a position bias needs its gradient buffer (and the reverse)");
-  if (pos_bias) {
-    if (dtype == OM_F16) return dispatch_bwd<f16_t, true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-    if (dtype == OM_BF16) return dispatch_bwd<bf16_t, true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-    if (dtype == OM_F32) return dispatch_bwd<float, true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  }
-  if (dtype == OM_F16) return dispatch_bwd<f16_t, false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
-  if (dtype == OM_BF16) return dispatch_bwd<bf16_t, false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
-  if (dtype == OM_F32) return dispatch_bwd<float, false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
-  OM_FAIL("attention backward: dtype must be OM_F32, OM_BF16 or OM_F16");
+  return attn_with_type(dtype, [&](auto t) {
+    return attn_with_kt<1, 2, 4, 6, 8>(p.kt, [&](auto kt) {
+      if (p.bias) return launch_bwd<decltype(t), kt(), true>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+      return launch_bwd<decltype(t), kt(), false>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
+    });
+  });
 }

@@ -1,7 +1,43 @@
 // Shared pieces of the attention forward / backward kernels (gfx950).
 #pragma once
+#include <type_traits>
+
 #include "gemm_core.h"
 #include "kernels.h"
+
+// ---- host side: from a plan (attn_plan.h) to a template instantiation ----
+// A run-time key-tile count as a compile-time one: f(std::integral_constant<int, KT>{}) for the KT among KTS... that equals kt.  Each
+// call site names the tile counts it instantiates.
+template <int... KTS, typename F>
+static int attn_with_kt(int kt, F&& f) {
+  int rc = 1;
+  if (!((kt == KTS && ((rc = f(std::integral_constant<int, KTS>{})), true)) || ...)) OM_FAIL("attention: no kernel of this key-tile count");
+  return rc;
+}
+// the storage type of a planned call: f(T{}) with T = f16_t, bf16_t or float (every other dtype code counts as float32) ...
+template <typename F>
+static int attn_with_type(int dtype, F&& f) { return dtype == OM_F16 ? f(f16_t{}) : dtype == OM_BF16 ? f(bf16_t{}) : f(float{}); }
+// ... and of a family that exists in the 16-bit formats only
+template <typename F>
+static int attn_with_type16(int dtype, F&& f) { return dtype == OM_F16 ? f(f16_t{}) : f(bf16_t{}); }
+// the twin of attn_with_kt for the (BIAS, DROP) pair: f(std::bool_constant<BIAS>{}, std::bool_constant<DROP>{})
+template <typename F>
+static int attn_with_flags(bool bias, bool drop, F&& f) {
+  const std::true_type yes;
+  const std::false_type no;
+  return bias ? (drop ? f(yes, yes) : f(yes, no)) : (drop ? f(no, yes) : f(no, no));
+}
+// Raise the dynamic LDS limit of Kernel to `lds` bytes, once per process (a kernel is always launched with the same figure: it follows
+// from the template arguments).
+template <auto Kernel>
+static int attn_lds_once(int lds) {
+  static std::atomic<bool> done{false};
+  if (!done) {
+    OM_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    done = true;
+  }
+  return 0;
+}
 
 template <typename T> struct AttnGeom;
 template <> struct AttnGeom<bf16_t> {

@@ -182,7 +182,7 @@ extern "C" int om_encoder_packed_supported(const OmEncoderConfig* c, int gated_f
   if (B * L <= (int64_t)om_option(OM_OPT_GEMM_SKINNY_M)) return 0;
   const int dt = c->dtype;
   if (dt != OM_BF16 && dt != OM_F16) return 0;
-  if (dt == OM_BF16 && !om_option(OM_OPT_ATTENTION_FAST)) return 0;
+  if (dt == OM_BF16 && !om_option(OM_OPT_ATTENTION_FAST)) return 0;      // (restates attn_plan.h: packed rows need the 16-bit attention kernels)
   if (om_option(OM_OPT_ENCODER_FUSED_LN) == 0 || c->n_layers <= 0 || c->hidden % 8) return 0;
   const int H = c->hidden, F = c->ffn;
   if (c->arch == OM_ARCH_BERT) { if (c->act != OM_ACT_GELU_ERF) return 0; }
@@ -546,10 +546,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
       GEMM(a_in, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, lw.qkv_b, nullptr, 0, OM_ACT_NONE);
       const bool sliding = ((c->sliding_layers >> l) & 1) != 0;
       RUN(omk_rope(dt, ws.qkv, M, (int)L, H, sliding ? c->rope_theta_local : c->rope_theta_global, s));
-      if (sliding)
-        RUN(omk_attention_band(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, H, nh, scale, c->half_window, ws.kmax, s));
-      else
-        RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
+      RUN(omk_attention(dt, ws.qkv, ws.ctx, attention_mask, nullptr, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax, nullptr, sliding ? c->half_window : 0));
       GEMM(ws.ctx, H, lw.o_w, H, ws.x, H, H, H, lw.o_b, ws.x, H, OM_ACT_NONE);        // x += Wo(ctx)
       RUN(omk_layernorm(dt, ws.x, H, ws.y, H, lw.ln2_g, lw.ln2_b, M, H, c->ln_eps, 0, s));
       GEMM(ws.y, H, lw.ffn1g_w, H, ws.ff2, F, F, H, nullptr, nullptr, 0, OM_ACT_NONE);

@@ -26,18 +26,21 @@ int omk_l2norm(const float* x, float* y, int64_t M, int D, hipStream_t s);
 int omk_t5_bias(const float* table, const int* lut, float* out, int L, int heads, hipStream_t s);
 
 // softmax(scale * Q K^T + mask [+ pos_bias]) V for every (batch, head); qkv is the fused
-// projection output [B*L, 3H] (q | k | v), ctx is [B*L, H].  L <= 1024, head_dim 32 or 64.
+// projection output [B*L, 3H] (q | k | v), ctx is [B*L, H].  L <= 1024, head_dim 32 or 64.  The one forward entry: it plans
+// (attn_plan.h: arguments, kernel family, key tiles), launches, and notes family | key tiles << 8 for om_debug_attention_last.
 int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
                   const float* pos_bias, int64_t B, int L, int H, int heads, float scale,
                   float drop_p, uint64_t seed, hipStream_t s, int reverse = 0 /* batch rows last to first */,
                   const int* kmax = nullptr /* omk_mask_extent: per batch row, 1 + its last unmasked key (16-bit kernels skip the key tiles past it) */,
-                  const int* cu = nullptr /* packed rows: sequence b occupies rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (L stays the mask's row pitch) */);
-// the same for 32-wide heads (H == heads * 32, attention_d32.hip): L <= 1024, no position bias; omk_attention sends such calls here
-int omk_attention_d32(int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L, int H,
-                      int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu);
+                  const int* cu = nullptr /* packed rows: sequence b occupies rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (L stays the mask's row pitch) */,
+                  int w = 0 /* > 0: banded attention, key k visible from query q only if |q - k| <= w (head_dim 64, no bias, dropout or cu) */);
+// its launchers for 32-wide heads (attention_d32.hip) and for a band (attention_band.hip, 0 < w < L - 1): no argument checks of their own
+struct AttnPlan;
+int omk_attention_d32(const AttnPlan& p, int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L,
+                      int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu);
 // ModernBERT (attention_band.hip, head_dim 64, inference): rotary positions on the Q and K columns of qkv in place (position = row % L,
-// one device cos / sin table per theta), and attention where key k is visible from query q only if |q - k| <= w and k is unmasked
-// (w <= 0 or w >= L - 1: omk_attention).  Key chunks outside a query block's band are not visited.
+// one device cos / sin table per theta), and attention where key k is visible from query q only if |q - k| <= w and k is unmasked.
+// Key chunks outside a query block's band are not visited.
 int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s);
 int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
                        int w, const int* kmax, hipStream_t s);
@@ -46,9 +49,6 @@ int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mas
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);
 int omk_pack_overflow_poison(const int* cu, int64_t B, int64_t rows, float* out, int64_t n, hipStream_t s);
 int omk_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, hipStream_t s);
-// the kernel family (OM_ATTN_FAMILY_*) and key-tile count of the calling thread's last attention forward launch: one host store per
-// launch (om_debug_attention_last)
-void omk_attn_note(int family, int kt);
 
 // ---- extended GEMM epilogue (training) ---------------------------------------------------
 // order: v = acc + bias ; [pre_act <- v] ; v = act(v) ; v = dropout(v) ; v = v (+|*) resid

@@ -431,14 +431,8 @@ int t5_train_backward(const OmEncoderConfig* c, const OmEncoderWeights* w, const
     WGRAD(dA, H, ctx, H, lg.o_w);
     e = GemmEpilogue{};
     RUN(omk_gemm(dt, dA, H, wt.o, H, dt, ws.dctx, H, M, H, H, e, s));         // dctx = dA Wo
-    // (round 6) beyond 256 tokens -- and from 193 on: the generic kernel keeps a whole score row in registers, which is fine up to six key tiles
-    // (it wins by 4-7 % of a step at 144 ... 192 tokens) and 20 % of a step slower with eight (profiles/r06_train_long_sequences.txt) --
-    if (d.L > 256 || (!d.packed && dt != OM_F32 && ((om_option(OM_OPT_ATTENTION_FAST) & 2) || ((om_option(OM_OPT_ATTENTION_FAST) & 1) && d.L > 192))))      // one score tile in registers at a time, delta from the tape's attention output
-      RUN(omk_attention_bwd_long(dt, qkv, ctx, ws.dctx, ws.dqkv, attention_mask, d.B, (int)d.L, H, d.nh, 1.0f, ad,
-                                 site_seed(seed, l, 2), ws.posbias, ws.drel, ws.astats, s));
-    else
-    RUN(omk_attention_bwd_bias(dt, qkv, ws.dctx, ws.dqkv, attention_mask, d.B, (int)d.L, H, d.nh, 1.0f, ad,
-                               site_seed(seed, l, 2), ws.posbias, ws.drel, s, cu));
+    RUN(omk_attention_bwd(dt, qkv, ctx, ws.dctx, ws.dqkv, attention_mask, d.B, (int)d.L, H, d.nh, 1.0f, ad, site_seed(seed, l, 2), ws.posbias, ws.drel,
+                          ws.astats, s, cu, d.packed));
     if (d.packed) RUN(omk_zero_rows_from(ws.dqkv, (int64_t)3 * H * d.es, ws.cu + d.B, M, s));      // rows the kernel does not own: zero, not stale
     RUN(omk_layernorm(dt, x, H, ws.nbuf, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));    // n1 again
     WGRAD(ws.dqkv, 3 * H, ws.nbuf, H, lg.qkv_w);
@@ -477,7 +471,7 @@ extern "C" int om_encoder_train_packed_supported(const OmEncoderConfig* c, int64
   if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255 || packed_rows >= B * L) return 0;
   if (c->hidden % 256 || c->ffn % 256 || (c->n_heads * 64 != c->hidden && c->n_heads * 32 != c->hidden)) return 0;
   if (c->pooling != OM_POOL_FIRST && c->pooling != OM_POOL_MEAN) return 0;
-  if (!om_option(OM_OPT_ATTENTION_FAST) || L > 256) return 0;
+  if (!om_option(OM_OPT_ATTENTION_FAST) || L > 256) return 0;      // (deliberately stricter than attn_plan.h: float16 packs with the switch on only, and no packed rows beyond 256 tokens)
   if (c->arch == OM_ARCH_BERT && (size_t)c->ffn < (size_t)2 * c->hidden) return 0;      // (the f32 pooled tail borrows the [M, F] scratch)
   return 1;
 }
@@ -881,16 +875,8 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
       RUN(omk_gemm(dt, dA, H, wt.o, H, dt, ws.dctx, H, M, H, H, e3, s));    // dctx = dA Wo
     }
     WGRAD_DONE(l + 1, 3);                                           // ws.dqkv: last read by dWqkv of the layer above
-    // (round 6) beyond 256 tokens -- and from 193 on (see t5_train_backward) --
-    if (L > 256 || (!d.packed && dt != OM_F32 && ((om_option(OM_OPT_ATTENTION_FAST) & 2) || ((om_option(OM_OPT_ATTENTION_FAST) & 1) && L > 192))))      // one score tile in registers at a time, delta from the tape's attention output
-      RUN(omk_attention_bwd_long(dt, qkv, ctx, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale,
-                                 attn_dropout, site_seed(seed, l, 2), d.rel ? ws.posbias : nullptr, d.rel ? ws.drel : nullptr, ws.astats, s));
-    else if (d.rel)
-      RUN(omk_attention_bwd_bias(dt, qkv, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale,
-                                 attn_dropout, site_seed(seed, l, 2), ws.posbias, ws.drel, s, cu));
-    else
-    RUN(omk_attention_bwd(dt, qkv, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale,
-                          attn_dropout, site_seed(seed, l, 2), s, cu));
+    RUN(omk_attention_bwd(dt, qkv, ctx, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale, attn_dropout, site_seed(seed, l, 2),
+                          d.rel ? ws.posbias : nullptr, d.rel ? ws.drel : nullptr, ws.astats, s, cu, d.packed));
     if (d.packed) RUN(omk_zero_rows_from(dqkvl, (int64_t)3 * H * d.es, ws.cu + B, M, s));      // rows the kernel does not own: zero, not stale
     WGRAD(3, dqkvl, 3 * H, x, H, lg.qkv_w, lg.qkv_b);               // dWqkv [3H,H], dbqkv
     {

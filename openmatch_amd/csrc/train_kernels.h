@@ -40,26 +40,26 @@ int omk_zero_rows_from(void* p, int64_t row_bytes, const int* first, int64_t M, 
 int omk_l2norm_bwd(const float* x, const float* dy, float* dx, int64_t M, int D, hipStream_t s);
 int omk_small_nn(const float* A, const float* Bm, float* C, int I, int J, int Cc, hipStream_t s);
 int omk_small_tn(const float* A, const float* Bm, float* C, int I, int J, int Cc, hipStream_t s);
-int omk_attention_bwd(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
-                      int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                      hipStream_t s, const int* cu = nullptr /* packed rows (16-bit, L <= 256): sequence b is rows cu[b] .. cu[b + 1] - 1 */);
-int omk_attention_bwd_bias(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
-                           int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                           const float* pos_bias, float* drel, hipStream_t s, const int* cu = nullptr /* packed rows, as above (the bias table keeps the pitch L) */);
-// 256 < L <= 512, 16-bit formats (round 6): two kernels with one key / query tile in registers at a time; ctx = the forward's output (delta = dO . O)
-int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const int64_t* mask,
-                           int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                           const float* pos_bias, float* drel, float* stats /* omk_attention_bwd_long_stats_bytes(B, heads) of scratch */, hipStream_t s);
+// The one attention backward entry: it plans (attn_plan.h: arguments, kernel family, key tiles), launches, and notes
+// family | key tiles << 8 for om_debug_attention_bwd_last.  Families: the transposing-read kernel (attention_bwd16.hip: 16 bits, up to
+// 128 tokens), the generic kernel (up to 256 tokens, float32 192), the two-pass tile-at-a-time kernels (16 bits, up to 512 tokens,
+// no packed rows; they need ctx and stats) and the kernel for 32-wide heads (attention_d32.hip, up to 256 tokens).
+int omk_attention_bwd(int dtype, const void* qkv, const void* ctx /* the forward's output (the tape's); NULL: no tile-at-a-time kernel */,
+                      const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H, int heads, float scale, float drop_p,
+                      uint64_t seed, const float* pos_bias /* [heads][L][L] added to the scaled scores, or NULL */,
+                      float* drel /* [heads][2L - 1]: its gradient per relative position, or NULL */,
+                      float* stats /* omk_attention_bwd_long_stats_bytes(B, heads) of scratch, or NULL */, hipStream_t s,
+                      const int* cu /* packed rows (16-bit, L <= 256): sequence b is rows cu[b] .. cu[b + 1] - 1; the bias table keeps the pitch L */,
+                      bool packed /* the step runs over packed rows */);
 size_t omk_attention_bwd_long_stats_bytes(int64_t B, int heads);
-// 32-wide heads (H == heads * 32, attention_d32.hip), L <= 256, every format, packed rows in 16 bits; omk_attention_bwd* send such calls here
-int omk_attention_bwd_d32(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
-                          int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias = nullptr,
-                          float* drel = nullptr);      // pos_bias [heads, L, L] added to the scaled scores, drel [heads, 2L - 1] its per-offset gradient
-// bf16, L <= 128, no position bias: the transposing-read kernel of attention_bwd16.hip
-bool omk_attention_bwd16_ok(int dtype, int L, int H, int heads);
-int omk_attention_bwd16(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
-                        int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu = nullptr,
-                        const float* pos_bias = nullptr, float* drel = nullptr /* T5 (round 6): the bias table [heads][L][L] and its gradient per relative position */);
+// its launchers in other translation units: no argument checks of their own
+struct AttnPlan;
+int omk_attention_bwd_d32(const AttnPlan& p, int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L,
+                          int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias,
+                          float* drel);
+int omk_attention_bwd16(const AttnPlan& p, int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L,
+                        int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, const int* cu, const float* pos_bias,
+                        float* drel);
 // T5 feed-forward activation (kind 0 relu, 1 gated gelu_new) forward / backward, embedding and bias backward
 int omk_t5_act_fwd(int dtype, const void* f, const void* f2, void* g, int64_t n, int kind, hipStream_t s);
 int omk_t5_act_bwd(int dtype, const void* dg, const void* f, const void* f2, void* df, void* df2, int64_t n, int kind, hipStream_t s);

@@ -3,6 +3,7 @@
 // LayerNorm / embedding / pooling / normalise backward, and the fused attention backward.
 // The dense contractions themselves (dgrad, wgrad) run on the MFMA GEMM of gemm.hip.
 #include "attn_common.h"
+#include "attn_plan.h"
 #include "train_kernels.h"
 
 // ---------------------------------------------------------------------------------------
@@ -931,15 +932,10 @@ __global__ __launch_bounds__(64 * KT) void attention_bwd_kernel(
 template <typename T, int KT>
 static int launch_attn_bwd(const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
                            int64_t B, int L, int H, int heads, float scale, float drop_p,
-                           uint64_t seed, const float* pos_bias, float* drel, hipStream_t s, const int* cu = nullptr) {
+                           uint64_t seed, const float* pos_bias, float* drel, hipStream_t s, const int* cu) {
   constexpr int LP = KT * 32 + 4;
   const int lds = 3 * 64 * LP * (int)sizeof(T) + 6 * KT * 32 * 4;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_bwd_kernel<T, KT>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_bwd_kernel<T, KT>>(lds)) return 1;
   const int waves = (L + 31) / 32;
   hipLaunchKernelGGL((attention_bwd_kernel<T, KT>), dim3((unsigned)(heads * B)), dim3(64 * waves), lds, s,
                      (const T*)qkv, (const T*)dctx, (T*)dqkv, mask, L, H, heads, scale, drop_p, seed, pos_bias, drel, cu);
@@ -1226,12 +1222,7 @@ static int launch_attn_bwd_long(const void* qkv, const void* ctx, const void* dc
                                 uint64_t seed, const float* pos_bias, float* drel, float* stats, hipStream_t s) {
   const int lds_a = 64 * OM_ABL_LP * (int)sizeof(T) + 3 * OM_ABL_LMAX * 4;
   const int lds_b = 2 * 64 * OM_ABL_LP * (int)sizeof(T) + 3 * OM_ABL_LMAX * 4;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    OM_HIP(hipFuncSetAttribute((const void*)attention_bwd_long_a_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_a));
-    OM_HIP(hipFuncSetAttribute((const void*)attention_bwd_long_b_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b));
-    attr_set = true;
-  }
+  if (attn_lds_once<attention_bwd_long_a_kernel<T>>(lds_a) || attn_lds_once<attention_bwd_long_b_kernel<T>>(lds_b)) return 1;
   const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
   hipLaunchKernelGGL((attention_bwd_long_a_kernel<T>), grid, dim3(256), lds_a, s,
                      (const T*)qkv, (const T*)ctx, (const T*)dctx, (T*)dqkv, mask, L, H, heads, scale, drop_p, seed, pos_bias, drel, stats);
@@ -1242,79 +1233,47 @@ static int launch_attn_bwd_long(const void* qkv, const void* ctx, const void* dc
   return 0;
 }
 
-// 256 < L <= 512, 16-bit formats: needs the forward's output (the tape's ctx)
 size_t omk_attention_bwd_long_stats_bytes(int64_t B, int heads) { return (size_t)B * heads * 3 * OM_ABL_LMAX * 4; }
-int omk_attention_bwd_long(int dtype, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const int64_t* mask,
-                           int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                           const float* pos_bias, float* drel, float* stats, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (H == heads * 32) {      // 32-wide heads: one kernel up to 256 tokens (it recomputes the statistics; ctx and stats are not needed)
-    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, nullptr, pos_bias, drel);
+
+// family | key tiles << 8 of the process's last backward launch.  Not per thread as the forward's word is: torch's autograd engine runs
+// a backward on a thread of its own, and the test that reads the word runs on another.
+static std::atomic<int> g_attn_bwd_last{0};
+extern "C" int om_debug_attention_bwd_last(void) { return g_attn_bwd_last; }
+
+// the one backward entry: plan (attn_plan.h), switch on the family, launch
+int omk_attention_bwd(int dtype, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const int64_t* mask, int64_t B, int L, int H,
+                      int heads, float scale, float drop_p, uint64_t seed, const float* pos_bias, float* drel, float* stats, hipStream_t s,
+                      const int* cu, bool packed) {
+  g_attn_bwd_last = 0;
+  const AttnPlan p = attn_plan_bwd(dtype, B, L, H, heads, pos_bias != nullptr, drel != nullptr, cu != nullptr, packed, attn_switches());
+  if (p.error) OM_FAIL(p.error);
+  if (p.family == OM_ATTN_BWD_FAMILY_LONG && (!ctx || !stats))
+    OM_FAIL("attention backward beyond 256 tokens needs the forward's output and a statistics buffer (omk_attention_bwd_long_stats_bytes)");
+  g_attn_bwd_last = p.family | (p.kt << 8);
+  switch (p.family) {
+    case 0: return 0;                                   // an empty batch
+    case OM_ATTN_BWD_FAMILY_D32: return omk_attention_bwd_d32(p, dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+    case OM_ATTN_BWD_FAMILY_BWD16: return omk_attention_bwd16(p, dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
+    case OM_ATTN_BWD_FAMILY_LONG:
+      return attn_with_type16(dtype, [&](auto t) {
+        return launch_attn_bwd_long<decltype(t)>(qkv, ctx, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, stats, s);
+      });
+    default:                                            // OM_ATTN_BWD_FAMILY_GENERIC
+      return attn_with_type(dtype, [&](auto t) {
+        return attn_with_kt<1, 2, 4, 6, 8>(p.kt, [&](auto kt) {
+          return launch_attn_bwd<decltype(t), kt()>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, s, cu);
+        });
+      });
   }
-  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
-  if (L < 1 || L > 512) OM_FAIL("attention backward (tile-at-a-time form): up to 512 tokens");      // (taken from 257 on; below that only when a test forces it)
-  if (H != heads * 64) OM_FAIL("head_dim must be 64");
-  if (!ctx || !stats) OM_FAIL("attention backward beyond 256 tokens needs the forward's output and a statistics buffer (omk_attention_bwd_long_stats_bytes)");
-  if (dtype == OM_BF16) return launch_attn_bwd_long<bf16_t>(qkv, ctx, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, stats, s);
-  if (dtype == OM_F16) return launch_attn_bwd_long<f16_t>(qkv, ctx, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, stats, s);
-  OM_FAIL("attention backward beyond 256 tokens: 16-bit formats");
 }
 
-int omk_attention_bwd(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
-                      int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                      hipStream_t s, const int* cu) {
-  if (H == heads * 32) return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, nullptr, nullptr);
-  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
-  if (cu) {           // packed rows (16-bit formats): the transposing-read kernel up to 128 tokens, the generic one up to 256
-    if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("packed rows: attention backward for 16-bit formats");
-    if (B <= 0) return 0;
-    if (omk_attention_bwd16_ok(dtype, L, H, heads))
-      return omk_attention_bwd16(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu);
-    if (L < 1 || L > 256 || H != heads * 64) OM_FAIL("packed rows: attention backward up to 256 tokens, head_dim 64");
-#define ABP(TT)                                                                                      \
-  do {                                                                                               \
-    if (L <= 32) return launch_attn_bwd<TT, 1>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, nullptr, nullptr, s, cu); \
-    if (L <= 64) return launch_attn_bwd<TT, 2>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, nullptr, nullptr, s, cu); \
-    if (L <= 128) return launch_attn_bwd<TT, 4>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, nullptr, nullptr, s, cu); \
-    if (L <= 192) return launch_attn_bwd<TT, 6>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, nullptr, nullptr, s, cu); \
-    return launch_attn_bwd<TT, 8>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, nullptr, nullptr, s, cu);    \
-  } while (0)
-    if (dtype == OM_BF16) ABP(bf16_t);
-    ABP(f16_t);
-#undef ABP
-  }
-  return omk_attention_bwd_bias(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, nullptr, nullptr, s, nullptr);
+// host only: what omk_attention_bwd would launch at the current switches -- family | key tiles << 8, 0 when nothing would launch, -1 for
+// a refusal (its reason in om_last_error); the last-launch words are not touched
+extern "C" int om_debug_attention_bwd_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, int has_drel, int has_cu, int packed) {
+  const AttnPlan p = attn_plan_bwd(dtype, B, L, H, heads, has_bias != 0, has_drel != 0, has_cu != 0, packed != 0, attn_switches());
+  if (p.error) { om_set_error(std::string(__func__) + ": " + p.error); return -1; }
+  return p.family | (p.kt << 8);
 }
-
-int omk_attention_bwd_bias(int dtype, const void* qkv, const void* dctx, void* dqkv, const int64_t* mask,
-                           int64_t B, int L, int H, int heads, float scale, float drop_p, uint64_t seed,
-                           const float* pos_bias, float* drel, hipStream_t s, const int* cu) {
-  if (B <= 0) return 0;
-  if (H == heads * 32) {
-    return omk_attention_bwd_d32(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  }
-  if (H != heads * 64) OM_FAIL("head_dim must be 32 or 64");
-  if (cu && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("packed rows: attention backward for 16-bit formats");
-  if (omk_attention_bwd16_ok(dtype, L, H, heads) && (pos_bias != nullptr) == (drel != nullptr))      // (with the T5 bias too since round 6)
-    return omk_attention_bwd16(dtype, qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, s, cu, pos_bias, drel);
-  if (L < 1 || L > 256) OM_FAIL("training supports sequence lengths up to 256");
-  // the three transposed [64][L + 4] images of the backward kernel must fit the 160 KiB of LDS: 256 keys in 16 bits, 192 in f32
-  if (dtype == OM_F32 && L > 192) OM_FAIL("float32 training supports sequence lengths up to 192 (16-bit formats: 256)");
-  if (H != heads * 64) OM_FAIL("head_dim must be 64");
-#define AB(TT)                                                                                       \
-  do {                                                                                               \
-    if (L <= 32) return launch_attn_bwd<TT, 1>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, s, cu); \
-    if (L <= 64) return launch_attn_bwd<TT, 2>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, s, cu); \
-    if (L <= 128) return launch_attn_bwd<TT, 4>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, s, cu); \
-    if (L <= 192) return launch_attn_bwd<TT, 6>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, s, cu); \
-    return launch_attn_bwd<TT, 8>(qkv, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, s, cu);    \
-  } while (0)
-  if (dtype == OM_BF16) AB(bf16_t);
-  if (dtype == OM_F16) AB(f16_t);
-  AB(float);
-#undef AB
-}
-
 
 // ---------------------------------------------------------------------------------------
 // T5 feed-forward activations (HF:models/t5/modeling_t5.py T5DenseActDense / T5DenseGatedActDense)

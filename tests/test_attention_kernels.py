@@ -37,7 +37,13 @@ family -> GPU cases (test_lengths ids are [route-dtype-L]; routes: OM_OPT_ATTENT
   BAND16       test_band[bf16|f16-*]
   BAND32       test_band[f32-*]
 
-The attention backward kernels are not covered here.
+Every expectation above comes from a table or a small function of this file (ROUTES, masks_expect, BD / bd_expect, REVERSE, PACKED,
+SWITCHES, BAND, REFUSALS) that the CPU tests walk as well: test_forward_plan_names_what_the_gpu_cases_assert asks the planner
+(csrc/attn_plan.h, through om_debug_attention_plan, no GPU) for every case and expects the family, tile count or refusal the GPU case
+asserts, so the two cannot drift.  kt_of is this file's own statement of the tile rule.
+
+The attention backward kernels are not run here; their planner is walked against BWD_TABLE (test_backward_plan_matches_the_table), and
+the training tests of tests/test_gpu_parity.py assert through om_debug_attention_bwd_last() which of them each arm reached.
 """
 import contextlib
 import math
@@ -363,7 +369,8 @@ def test_python_dropout_mask_equals_the_c_one():
 def test_hooks_are_bound():
     lib = N.lib()
     for name in ("om_debug_attention_ex", "om_debug_rope", "om_debug_mask_extent", "om_debug_pack_rows", "om_debug_attention_last",
-                 "om_debug_attn_drop_keep", "om_debug_attention"):
+                 "om_debug_attn_drop_keep", "om_debug_attention", "om_debug_attention_plan", "om_debug_attention_bwd_plan",
+                 "om_debug_attention_bwd_last"):
         assert name in N.exported_symbols() and hasattr(lib, name)
     assert lib.om_debug_attention_ex(BF16, None, None, None, None, 1, 8, 64, 1, 0.125, 0.0, 0, None, 0, None, None, 0) != 0
     assert b"null" in lib.om_last_error()
@@ -386,7 +393,7 @@ def test_visibility_rules():
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# GPU
+# CPU: the planners (csrc/attn_plan.h) through their host-only hooks, on the tables the GPU cases below take their expectations from
 # ---------------------------------------------------------------------------------------------------------------
 @contextlib.contextmanager
 def option(opt, value):
@@ -400,6 +407,150 @@ def option(opt, value):
         assert lib.om_debug_option_value(opt) == old
 
 
+FAM_NAME = {v: k for k, v in FAM.items()}
+BWD_FAM_NAME = {v: k for k, v in N.ATTN_BWD_FAMILY.items()}
+
+
+def planned(dtype, B, L, heads, D, bias=False, p=0.0, kmax=False, cu=False, w=0):
+    """What the forward entry would launch: (family name, kt), None for an empty batch, the error text for a refusal."""
+    rc = N.lib().om_debug_attention_plan(dtype, B, L, heads * D, heads, int(bias), p, int(kmax), int(cu), w)
+    return N.lib().om_last_error() if rc < 0 else None if rc == 0 else (FAM_NAME[rc & 0xFF], rc >> 8)
+
+
+def test_forward_plan_names_what_the_gpu_cases_assert():
+    n = 0
+    for route, dtype in ROUTE_CASES:                                         # test_lengths, test_masks_switched
+        fast, _, fam = ROUTES[route]
+        with option(N.OPT_ATTENTION_FAST, fast):
+            for L in LENGTHS:
+                B, heads = shape_for(L)
+                assert planned(dtype, B, L, heads, 64) == fam(dtype, L), (route, NAME[dtype], L)
+                n += 1
+            if (route, dtype) in ROUTE_CASES[3:]:
+                for use_kmax in (False, True):
+                    assert planned(dtype, 12, 128, 5, 64, kmax=use_kmax) == fam(dtype, 128), (route, NAME[dtype], use_kmax)
+                    n += 1
+    for dtype in DTYPES:
+        for L in LENGTHS:                                                    # test_lengths_d32
+            B, heads = shape_for(L)
+            assert planned(dtype, B, L, heads, 32, kmax=L % 2 == 0) == ("d32", kt_of(L)), (NAME[dtype], L)
+            n += 1
+        for D in (64, 32):                                                   # test_masks
+            for use_kmax in (False, True):
+                assert planned(dtype, 12, 128, 5, D, kmax=use_kmax) == masks_expect(dtype, D, use_kmax), (NAME[dtype], D, use_kmax)
+                n += 1
+        for L, w in BAND:                                                    # test_band, and the window that reaches every key
+            for use_kmax in (False, True):
+                B, heads = shape_for(L)
+                assert planned(dtype, B, L, heads, 64, kmax=use_kmax, w=w) == band_expect(dtype), (NAME[dtype], L, w)
+                n += 1
+        assert planned(dtype, 3, 300, 5, 64, kmax=True, w=299) == widest_window_expect(dtype)
+        n += 1
+    for family, dtype, L, D in BD:                                           # test_bias_dropout
+        for bias in (False, True):
+            for drop in (False, True):
+                _, p, fast, kt, refused = bd_expect(family, dtype, L, D, drop)
+                with option(N.OPT_ATTENTION_FAST, 1 if refused else fast):
+                    got = planned(dtype, 3, L, 5, D, bias=bias, p=p)
+                assert (DROP_REFUSAL in got) if refused else got == (family, kt), (family, NAME[dtype], L, bias, drop, got)
+                n += 1
+    for dtype, L, D in DROP_REFUSALS:                                        # test_dropout_refusals
+        assert DROP_REFUSAL in planned(dtype, 1, L, 2, D, p=0.1), (NAME[dtype], L, D)
+        n += 1
+    for dtype, D, L, bias, p, family, kt in REVERSE:                         # test_reverse_is_bit_identical
+        assert planned(dtype, 3, L, 5, D, bias=bias, p=p, kmax=True) == (family, kt), (NAME[dtype], D, L)
+        n += 1
+    for dtype, D, L, family, p, fast in PACKED:                              # test_packed_rows: the padded call, then the packed one
+        with option(N.OPT_ATTENTION_FAST, fast):
+            for cu in (False, True):
+                assert planned(dtype, 6, L, 5, D, p=p, kmax=True, cu=cu) == (family, packed_kt(family, L)), (NAME[dtype], D, L, family, cu)
+                n += 1
+    assert PACKED_REFUSAL in planned(F32, 1, 8, 1, 64, cu=True)              # test_packed_rows_refused_in_f32
+    for fast, L, family, kt in SWITCHES:                                     # test_switches
+        with option(N.OPT_ATTENTION_FAST, fast):
+            assert planned(BF16, 3, L, 5, 64) == (family, kt), (fast, L)
+            n += 1
+    for dtype, D, L, fast, family, kt in NONFINITE:
+        with option(N.OPT_ATTENTION_FAST, fast):
+            assert planned(dtype, 3, L, 5, D) == (family, kt), (NAME[dtype], D, L, fast)
+            n += 1
+    assert n == 392, n                                                       # every table case above was walked
+    # refusals and the empty batch, by rule 1 of the planner
+    assert planned(BF16, 0, 128, 5, 64) is None and planned(F32, -1, 5000, 5, 48) is None
+    assert b"dtype must be OM_F32, OM_BF16 or OM_F16" in planned(7, 1, 128, 5, 64)
+    assert b"head_dim must be 32 or 64" in planned(BF16, 1, 128, 5, 48)
+    assert b"banded attention: head_dim must be 64" in planned(BF16, 1, 128, 5, 32, w=5)
+    assert b"banded attention: no position bias, dropout, packed rows" in planned(BF16, 1, 128, 5, 64, bias=True, w=5)
+    assert b"sequence length must be in [1,1024]" in planned(F16, 1, 1025, 5, 64) and b"sequence length must be in [1,1024]" in planned(F16, 1, 0, 5, 32)
+    assert b"batch too large for one launch" in planned(F16, 2 ** 31, 8, 1, 64)
+    with option(N.OPT_ATTENTION_FAST, 0):
+        assert PACKED_REFUSAL in planned(BF16, 1, 8, 1, 64, cu=True)         # 64-wide bfloat16 without bit 0 has no 16-bit kernel
+        assert planned(BF16, 1, 8, 1, 32, cu=True) == ("d32", 1) and planned(F16, 1, 8, 1, 64, cu=True) == ("fwd16", 1)
+
+
+# The backward planner's outcome at every length of LENGTHS, one letter each:
+#   b transposing-read kernel (bwd16)   g generic kernel   l tile-at-a-time pair (long)   d the 32-wide-heads kernel
+#   X 32-wide heads stop at 256 tokens  P packed rows are 16-bit only  F float32 stops at 192 tokens  S beyond 256 tokens 16 bits only
+#   T the tile-at-a-time pair stops at 512 tokens  C ... and does not read cu (the one refusal that used to be a silently dropped argument)
+# keyed by (head width, 16-bit format?, packed rows?) and then by OM_OPT_ATTENTION_FAST; a position bias (with its gradient buffer)
+# changes none of them.  LENGTHS:  1 31 32 33 64 65 128 | 129 192 | 193 256 | 257 384 511 512 | 1000 1024
+BWD_TABLE = {
+    (32, True, False): {f: "ddddddddddd" "XXXXXX" for f in range(4)},
+    (32, True, True): {f: "ddddddddddd" "XXXXXX" for f in range(4)},
+    (32, False, False): {f: "ddddddddddd" "XXXXXX" for f in range(4)},
+    (32, False, True): {f: "PPPPPPPPPPP" "XXXXXX" for f in range(4)},
+    (64, False, False): {f: "ggggggg" "gg" "FF" "SSSS" "TT" for f in range(4)},
+    (64, False, True): {f: "PPPPPPP" "PP" "PP" "SSSS" "TT" for f in range(4)},
+    (64, True, False): {0: "ggggggg" "gg" "gg" "llll" "TT", 1: "bbbbbbb" "gg" "ll" "llll" "TT",
+                        2: "lllllll" "ll" "ll" "llll" "TT", 3: "lllllll" "ll" "ll" "llll" "TT"},
+    (64, True, True): {0: "ggggggg" "gg" "gg" "CCCC" "TT", 1: "bbbbbbb" "gg" "gg" "CCCC" "TT",
+                       2: "bbbbbbb" "gg" "gg" "CCCC" "TT", 3: "bbbbbbb" "gg" "gg" "CCCC" "TT"},
+}
+BWD_LETTER = {"b": "bwd16", "g": "generic", "l": "long", "d": "d32",
+              "X": b"training with head_dim 32 supports sequence lengths up to 256", "P": b"packed rows: attention backward for 16-bit formats",
+              "F": b"float32 training supports sequence lengths up to 192 (16-bit formats: 256)", "S": b"attention backward beyond 256 tokens: 16-bit formats",
+              "T": b"attention backward (tile-at-a-time form): up to 512 tokens", "C": b"attention backward (tile-at-a-time form): no packed rows"}
+
+
+def planned_bwd(dtype, B, L, heads, D, bias=False, drel=None, packed=False):
+    rc = N.lib().om_debug_attention_bwd_plan(dtype, B, L, heads * D, heads, int(bias), int(bias if drel is None else drel), int(packed), int(packed))
+    return N.lib().om_last_error() if rc < 0 else None if rc == 0 else (BWD_FAM_NAME[rc & 0xFF], rc >> 8)
+
+
+def test_backward_plan_matches_the_table():
+    n = 0
+    for fast in range(4):
+        with option(N.OPT_ATTENTION_FAST, fast):
+            for dtype in DTYPES:
+                for D in (32, 64):
+                    for packed in (False, True):
+                        row = BWD_TABLE[(D, dtype != F32, packed)][fast]
+                        assert len(row) == len(LENGTHS)
+                        for L, letter in zip(LENGTHS, row):
+                            for bias in (False, True):
+                                got, want = planned_bwd(dtype, 4, L, 3, D, bias=bias, packed=packed), BWD_LETTER[letter]
+                                ok = (want in got) if isinstance(want, bytes) else got == (want, 4 if want == "long" else kt_of(L))
+                                assert isinstance(got, type(want) if isinstance(want, bytes) else tuple) and ok, (fast, NAME[dtype], D, packed, L, bias, got)
+                                n += 1
+    assert n == 4 * 3 * 2 * 2 * len(LENGTHS) * 2
+    assert planned_bwd(BF16, 0, 128, 3, 64) is None
+    assert b"head_dim must be 32 or 64" in planned_bwd(BF16, 1, 128, 3, 48)
+    assert b"a position bias needs its gradient buffer" in planned_bwd(BF16, 1, 128, 3, 32, bias=True, drel=False)
+    assert planned_bwd(BF16, 1, 128, 3, 64, bias=True, drel=False) == ("generic", 4)       # 64-wide: the generic kernel adds the bias and skips its gradient
+
+
+def test_plan_hooks_leave_the_last_launch_words_alone():
+    lib = N.lib()
+    assert lib.om_debug_attention_ex(BF16, None, None, None, None, 1, 8, 64, 1, 0.125, 0.0, 0, None, 0, None, None, 0) != 0      # refused: last = 0
+    before = (lib.om_debug_attention_last(), lib.om_debug_attention_bwd_last())
+    assert planned(BF16, 3, 128, 5, 64) == ("fwd16", 4) and planned_bwd(BF16, 3, 128, 5, 64) == ("bwd16", 4)
+    assert b"sequence length" in planned(BF16, 3, 2000, 5, 64)
+    assert (lib.om_debug_attention_last(), lib.om_debug_attention_bwd_last()) == before and before[0] == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------------------------------
 def bits(t, dtype):
     return t.view(BITS_DT[dtype])
 
@@ -517,19 +668,22 @@ def test_lengths_d32(dtype, L):
     run_case(dtype, B, L, heads, 32, SCALES[(LENGTHS.index(L) + 1) % 3], mixed_mask(B, L), "d32", kt_of(L), use_kmax=L % 2 == 0)
 
 
+def masks_expect(dtype, D, use_kmax):
+    """(family, kt) of a test_masks case: 128 tokens at the shipped switch."""
+    if D == 32:
+        return "d32", 4
+    if dtype == F32:
+        return "generic", 4
+    return ("fwd16_kmax4" if use_kmax else "fwd16"), 4
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("use_kmax", [False, True], ids=["nokmax", "kmax"])
 @pytest.mark.parametrize("D", [64, 32])
 @pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: NAME[d])
 def test_masks(dtype, D, use_kmax):
     """The eleven mask patterns (and a sequence without any key: uniform over all L), with kmax and without."""
-    if D == 32:
-        family = "d32"
-    elif dtype == F32:
-        family = "generic"
-    else:
-        family = "fwd16_kmax4" if use_kmax else "fwd16"
-    run_case(dtype, 12, 128, 5, D, 0.125 if D == 64 else SCALES[1], masks_eleven(), family, 4, use_kmax=use_kmax)
+    run_case(dtype, 12, 128, 5, D, 0.125 if D == 64 else SCALES[1], masks_eleven(), *masks_expect(dtype, D, use_kmax), use_kmax=use_kmax)
 
 
 @pytest.mark.gpu
@@ -568,22 +722,32 @@ BD = [("fwd16", BF16, 100, 64), ("fwd16", F16, 100, 64), ("fwd16", F16, 200, 64)
       ("long", F32, 300, 64), ("long", BF16, 300, 64), ("long", F16, 300, 64)]
 
 
+DROP_REFUSAL = b"attention with dropout: up to 512 tokens in the 16-bit formats (float32: 256)"
+PACKED_REFUSAL = b"packed rows: the 16-bit attention kernels"
+
+
+def bd_expect(family, dtype, L, D, drop):
+    """(index in BD, dropout rate, OM_OPT_ATTENTION_FAST, kt, refused) of a test_bias_dropout case."""
+    i = BD.index((family, dtype, L, D))
+    p = (0.1, 0.5, DROP_ODD)[i % 3] if drop else 0.0
+    fast = 0 if (family == "generic" and dtype == BF16) else 4 if (family == "long" and dtype != F32) else 1
+    kt = kt_of(L) if family in ("fwd16", "generic", "d32") else 4
+    return i, p, fast, kt, family == "long" and dtype == F32 and drop
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "drop"])
 @pytest.mark.parametrize("bias", [False, True], ids=["nobias", "bias"])
 @pytest.mark.parametrize("family,dtype,L,D", BD, ids=[f"{f}-{NAME[d]}-{L}" for f, d, L, _ in BD])
 def test_bias_dropout(family, dtype, L, D, bias, drop):
     B, heads = 3, 5
-    i = BD.index((family, dtype, L, D))
-    p = (0.1, 0.5, DROP_ODD)[i % 3] if drop else 0.0
-    fast = 0 if (family == "generic" and dtype == BF16) else 4 if (family == "long" and dtype != F32) else 1
-    kt = kt_of(L) if family in ("fwd16", "generic", "d32") else 4
+    i, p, fast, kt, refused = bd_expect(family, dtype, L, D, drop)
     mask = mixed_mask(B, L).to(DEV)
-    if family == "long" and dtype == F32 and drop:          # refused: float32 dropout stops at 256 tokens
+    if refused:                                             # float32 dropout stops at 256 tokens
         qkv, pb = make_inputs(dtype, B, L, heads, D, 0.125, seed=1, bias=bias, device=DEV)
         ctx = new_ctx(B * L, heads * D, dtype)
         assert launch(dtype, qkv, ctx, mask, pb, B, L, heads * D, heads, 0.125, p, 5) != 0
-        assert b"attention with dropout: up to 512 tokens in the 16-bit formats (float32: 256)" in N.lib().om_last_error()
+        assert DROP_REFUSAL in N.lib().om_last_error()
         assert N.lib().om_debug_attention_last() == 0
         assert untouched(ctx, dtype)
         return
@@ -591,15 +755,18 @@ def test_bias_dropout(family, dtype, L, D, bias, drop):
         run_case(dtype, B, L, heads, D, SCALES[i % 3], mask, family, kt, bias=bias, p=p, seed=0xC0FFEE + i, tag=i)
 
 
+DROP_REFUSALS = [(BF16, 600, 64), (F16, 513, 64), (F32, 257, 32), (BF16, 1024, 32)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype,L,D", [(BF16, 600, 64), (F16, 513, 64), (F32, 257, 32), (BF16, 1024, 32)])
+@pytest.mark.parametrize("dtype,L,D", DROP_REFUSALS)
 def test_dropout_refusals(dtype, L, D):
     B, heads = 1, 2
     qkv, _ = make_inputs(dtype, B, L, heads, D, 0.125, seed=2, device=DEV)
     mask = torch.ones(B, L, dtype=torch.long, device=DEV)
     ctx = new_ctx(B * L, heads * D, dtype)
     assert launch(dtype, qkv, ctx, mask, None, B, L, heads * D, heads, 0.125, 0.1, 5) != 0
-    assert b"attention with dropout: up to 512 tokens in the 16-bit formats (float32: 256)" in N.lib().om_last_error()
+    assert DROP_REFUSAL in N.lib().om_last_error()
     assert N.lib().om_debug_attention_last() == 0
     assert untouched(ctx, dtype)
 
@@ -643,6 +810,10 @@ def test_packed_rows(dtype, D, L, family, p, fast):
         _packed_rows(dtype, D, L, family, p)
 
 
+def packed_kt(family, L):
+    return 4 if family in ("fwd16c", "long") else kt_of(L)
+
+
 def _packed_rows(dtype, D, L, family, p):
     """cu: the rows that exist carry the bits of the padded call (which itself meets the bound), at 256 tokens or fewer and
     beyond, with dropout too (the hash is keyed on the mask's pitch, not on the sequence's own length).  Rows of the packed ctx
@@ -653,7 +824,7 @@ def _packed_rows(dtype, D, L, family, p):
     for b, n in enumerate((L, 1, L // 2 + 1, 33, 0, 97)):
         mask[b, :n] = 1
     mask[4, 0] = 1; mask[4, 5] = 1                         # holes inside a packed sequence: rows 0 .. 5 exist
-    kt = 4 if family in ("fwd16c", "long") else kt_of(L)
+    kt = packed_kt(family, L)
     padded = run_case(dtype, B, L, heads, D, 0.125, mask, family, kt, use_kmax=True, tag=77, p=p, seed=4242)
     qkv, _ = make_inputs(dtype, B, L, heads, D, 0.125, seed=1000 + 13 * L + D + 77, device=DEV)
     mask = mask.to(DEV)
@@ -678,12 +849,15 @@ def test_packed_rows_refused_in_f32():
     mask = torch.ones(1, 8, dtype=torch.long, device=DEV)
     cu = torch.tensor([0, 8, 8], dtype=torch.int32, device=DEV)
     assert launch(F32, qkv, new_ctx(8, 64, F32), mask, None, 1, 8, 64, 1, 0.125, cu=cu) != 0
-    assert b"packed rows: the 16-bit attention kernels" in N.lib().om_last_error()
+    assert PACKED_REFUSAL in N.lib().om_last_error()
+
+
+SWITCHES = [(0, 100, "generic", 4), (1, 100, "fwd16", 4), (2, 100, "fwd16c", 4), (4, 300, "long", 4),
+            (6, 100, "long", 4), (0, 300, "long", 4), (1, 300, "fwd16c", 4), (0, 256, "generic", 8)]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("fast,L,family,kt", [(0, 100, "generic", 4), (1, 100, "fwd16", 4), (2, 100, "fwd16c", 4), (4, 300, "long", 4),
-                                              (6, 100, "long", 4), (0, 300, "long", 4), (1, 300, "fwd16c", 4), (0, 256, "generic", 8)])
+@pytest.mark.parametrize("fast,L,family,kt", SWITCHES)
 def test_switches(fast, L, family, kt):
     """OM_OPT_ATTENTION_FAST 0 / 1 / bit 1 / bit 2 in bf16 reach the family the header names; the old value comes back."""
     before = N.lib().om_debug_option_value(N.OPT_ATTENTION_FAST)
@@ -695,6 +869,15 @@ def test_switches(fast, L, family, kt):
 BAND = [(300, 1), (300, 63), (300, 64), (300, 65), (300, 127), (300, 128), (300, 298), (129, 64), (257, 127), (1000, 64), (1024, 128), (385, 2)]
 
 
+def band_expect(dtype):
+    return ("band32" if dtype == F32 else "band16"), 4
+
+
+def widest_window_expect(dtype):
+    """w = L - 1 at 300 tokens reaches every key: full attention at the shipped switch"""
+    return ("long" if dtype == F32 else "fwd16c"), 4
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("use_kmax", [False, True], ids=["nokmax", "kmax"])
 @pytest.mark.parametrize("L,w", BAND)
@@ -704,14 +887,14 @@ def test_band(dtype, L, w, use_kmax):
     B, heads = (3, 5) if L <= 512 else (2, 3)
     mask = mixed_mask(B, L)
     mask[1, :] = 0; mask[1, :max(1, (7 * L) // 10)] = 1        # a prefix: kmax clips inside the band of the last query blocks
-    run_case(dtype, B, L, heads, 64, 0.125 if w != 65 else SCALES[2], mask, "band32" if dtype == F32 else "band16", 4, use_kmax=use_kmax, w=w)
+    run_case(dtype, B, L, heads, 64, 0.125 if w != 65 else SCALES[2], mask, *band_expect(dtype), use_kmax=use_kmax, w=w)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: NAME[d])
 def test_band_widest_window_is_full_attention(dtype):
     L = 300
-    run_case(dtype, 3, L, 5, 64, 0.125, mixed_mask(3, L), "long" if dtype == F32 else "fwd16c", 4, w=L - 1, use_kmax=True)
+    run_case(dtype, 3, L, 5, 64, 0.125, mixed_mask(3, L), *widest_window_expect(dtype), w=L - 1, use_kmax=True)
 
 
 def rope_table(theta, L):

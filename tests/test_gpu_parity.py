@@ -14,6 +14,13 @@ from oracle import encoder_ref, flatip, retrieval_ref
 from tests.helpers import NS, items_from_golden, model_from_golden, synth_tokens
 
 pytestmark = pytest.mark.gpu
+
+
+def attention_bwd_last():
+    """(family name, key tiles) of the process's last attention backward launch (om_debug_attention_bwd_last)."""
+    from openmatch_amd import native
+    last = native.lib().om_debug_attention_bwd_last()
+    return {v: k for k, v in native.ATTN_BWD_FAMILY.items()}.get(last & 0xFF), last >> 8
 DEV = "cuda:0"
 CASES = [("bert_tiny_first", "bert", False), ("bert_tiny_mean_head_norm", "bert", False),
          ("t5_tiny_gtr", "t5", False), ("t5_tiny_gated", "t5", True)]
@@ -1388,6 +1395,8 @@ def test_bf16_attention_backward_kernels_agree(L, p_drop):
             out.loss.backward()
         finally:
             N_.check(N_.lib().om_debug_option(2, 1))
+        # the two arms ran two different kernels
+        assert attention_bwd_last() == ("bwd16" if fast else "generic", 1 if L <= 32 else 2 if L <= 64 else 4), (fast, attention_bwd_last())
         grads.append((out.loss.item(), {n: t.grad.detach().float().cpu().clone() for n, t in lm.named_parameters() if t.grad is not None}))
     (l1, g1), (l2, g2) = grads
     assert abs(l1 - l2) < 1e-3 * max(1.0, abs(l2))           # (without dropout the switch also changes the forward attention kernel)
@@ -1439,6 +1448,9 @@ def test_tile_at_a_time_attention_kernels_agree_with_the_others_under_dropout(dt
                 out.loss.backward()
             finally:
                 N_.check(N_.lib().om_debug_option(2, 1))
+            # forced (bit 1): the tile-at-a-time backward; unforced: the transposing-read kernel at 96 tokens -- and at 200 the tile-at-a-time one
+            # as well (it serves 16-bit training from 193 tokens on: there the two arms differ in the forward kernel only)
+            assert attention_bwd_last() == (("bwd16", 4) if opt == 1 and L == 96 else ("long", 4)), (opt, L, attention_bwd_last())
             grads.append((out.loss.item(), {n: t.grad.detach().float().cpu().clone() for n, t in lm.named_parameters() if t.grad is not None}))
         (l1, g1), (l2, g2) = grads
         assert abs(l1 - l2) < 2e-3 * max(1.0, abs(l1)), (L, p_drop, l1, l2)
@@ -1495,6 +1507,7 @@ def test_training_step_beyond_256_tokens_matches_torch_autograd(L, arch, monkeyp
         out = model(query={"input_ids": tens(q_ids), "attention_mask": tens(q_mask)}, passage={"input_ids": tens(p_ids), "attention_mask": tens(p_mask)})
         lscale = 4096.0 if dtype == "float16" else 1.0       # float16 trains under a loss scale (the reference's GradScaler; DRTrainer's device-side one): a mean over
         (out.loss * lscale).backward()                        # 512 tokens puts unscaled score gradients below float16's smallest normal
+        assert attention_bwd_last() == ("long", 4), attention_bwd_last()
         for t in lm.parameters():
             if t.grad is not None:
                 t.grad /= lscale
@@ -2106,7 +2119,7 @@ def test_packed_rows_training_step_matches_the_padded_step(dtype, pooling, L):
                      max_position_embeddings=256, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     lm = BertModel(cfg).to(DEV).train()
     rng = np.random.default_rng(6)
-    B = 24                       # (L = 200: the attention backward's generic kernel; 128: the transposing-read one)
+    B = 24                       # (L = 200: the attention backward's generic kernel over packed rows; 128: the transposing-read one)
     ids, mask = _ragged_train_batch(rng, B, L)
     tokens = int(token_rows_of(mask).sum())
     rows = rows_bound_of(token_rows_of(mask))
@@ -2120,6 +2133,10 @@ def test_packed_rows_training_step_matches_the_padded_step(dtype, pooling, L):
         lm.zero_grad(set_to_none=True)
         reps = T.encode_train(lm, None, items, pooling, False, code, True, packed_rows=packed_rows)[1]
         (reps * wgt).sum().backward()
+        # 128 tokens: the transposing-read kernel, packed or not; 200: the generic kernel over packed rows, the tile-at-a-time one (16-bit
+        # training from 193 tokens on, which does not read cu) over padded ones
+        want = ("bwd16", 4) if L == 128 else ("generic", 8) if packed_rows else ("long", 4)
+        assert attention_bwd_last() == want, (L, packed_rows, attention_bwd_last())
         return reps.detach().clone(), {n: p.grad.detach().clone() for n, p in lm.named_parameters() if p.grad is not None}
 
     reps0, g0 = step(None)
@@ -2207,6 +2224,8 @@ def test_packed_rows_t5_training_step_matches_the_padded_step(dtype, ff, L, monk
             lm.zero_grad(set_to_none=True)
             reps = T.encode_train(lm, None, items, pooling, False, code, True, packed_rows=packed_rows)[1]
             (reps * wgt).sum().backward()
+            want = ("bwd16", 4) if L == 96 else ("generic", 8) if packed_rows else ("long", 4)      # (as in the BERT test above, with the bias and its gradient)
+            assert attention_bwd_last() == want, (L, packed_rows, attention_bwd_last())
             return reps.detach().clone(), {n: p.grad.detach().clone() for n, p in lm.named_parameters() if p.grad is not None}
 
         def compare(drop):
