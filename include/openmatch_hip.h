@@ -42,6 +42,8 @@ extern "C" {
 #define OM_ACT_GELU_ERF 1  /* HF "gelu"      (HF:activations.py GELUActivation)   */
 #define OM_ACT_RELU 2      /* HF "relu"      (T5 DenseReluDense)                  */
 #define OM_ACT_GELU_TANH 3 /* HF "gelu_new"  (T5 v1.1 gated act)                  */
+#define OM_ACT_SILU 5      /* HF "silu": OmCausalConfig.base.act only -- om_causal_encoder_forward applies it in an elementwise kernel of its
+                              own (silu(gate) * up); NOT a GEMM epilogue: om_gemm_nt does not take it (4 is internal to the training epilogues) */
 #define OM_ACT_MUL_RESID 0x100 /* flag: multiply by `resid` instead of adding it (gated FFN) */
 #define OM_ACT_PRE_GRAD 0x200  /* flag (erf-GELU training epilogue, 16-bit output): `pre_act` receives gelu'(v) instead of the pre-activation
                                 * v -- the backward's dgrad then multiplies by it (OM_ACT_MUL_RESID) instead of evaluating gelu' */
@@ -57,10 +59,14 @@ extern "C" {
                               * optional (norm_bias), no linear biases.  Attention at 1/sqrt(64) with rotary Q/K (rope_theta_global /
                               * rope_theta_local); layers flagged in sliding_layers see keys |q - k| <= half_window only. */
 
+#define OM_ARCH_CAUSAL 3 /* HF:models/llama/modeling_llama.py LlamaModel, HF:models/qwen2/modeling_qwen2.py Qwen2Model (inference only):
+                          * OmCausalConfig.base.arch, served by om_causal_encoder_forward alone (om_encoder_forward refuses it as unknown) */
+
 /* pooling — modeling/dense_retrieval_model.py:145-150 */
 #define OM_POOL_NONE 0
 #define OM_POOL_FIRST 1
 #define OM_POOL_MEAN 2 /* utils.py:233-235 mean_pooling */
+#define OM_POOL_LAST 3 /* the hidden state of each row's last unmasked token (right or left padding); om_causal_encoder_forward only */
 
 /* search precision */
 #define OM_SEARCH_F32 0           /* exact f32 MFMA scan                                   */
@@ -187,6 +193,14 @@ int om_debug_attention_ex(int dtype, const void* qkv, void* ctx, const int64_t* 
                           const int* cu, int w);
 /* rotary positions in place on the Q and K columns of qkv [M, 3H], position = row % L (M need not be a multiple of L) */
 int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, void* stream);
+/* Test hooks of the decoder-only stack (csrc/attention_causal.hip).  qkv is the grouped projection [rows, (n_heads + 2 n_kv_heads) * 64]
+ * (q heads | k heads | v heads), ctx [rows, n_heads * 64]; query head h reads K / V head h / (n_heads / n_kv_heads).
+ * om_debug_attention_causal: key k visible from query q iff k <= q and mask[b][k] != 0; it computes the key extents (one more small
+ * launch) into a grow-only device buffer it keeps per device, so its first call on a device allocates.  om_debug_rope_gqa: rotary positions in place on the
+ * q and k heads, position = row % L; inv_freq is a HOST array of 32 frequencies, cos / sin are multiplied by `scaling`. */
+int om_debug_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads, int n_kv_heads,
+                              float scale, void* stream);
+int om_debug_rope_gqa(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling, void* stream);
 /* kmax[b] = 1 + the last unmasked key of mask row b (L when it has none) */
 int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
 /* cu [B + 2], cls_rows [B], row_map [rows] of the packed layout (csrc/kernels.h omk_pack_rows) */
@@ -372,6 +386,32 @@ int om_encoder_forward_packed(const OmEncoderConfig* cfg, const OmEncoderWeights
                               const int64_t* input_ids, const int64_t* attention_mask,
                               const int64_t* token_type_ids, int64_t B, int64_t L, int64_t packed_rows,
                               float* out_reps, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Decoder-only backbones as encoders (inference): HF LlamaModel / Qwen2Model.forward in eval mode without a KV cache
+ * (HF:models/llama/modeling_llama.py, HF:models/qwen2/modeling_qwen2.py) + pooling + head + normalise, what
+ * modeling/dense_retrieval_model.py:133-155 computes when AutoModel returns one of them.  A grouped-query backbone needs a K / V head
+ * count that OmEncoderConfig has no field for, so these entries take a config struct of their own that EMBEDS the encoder's (its
+ * layout and OM_ABI_VERSION are unchanged).  base: arch = OM_ARCH_CAUSAL, head_dim = 64 with n_heads * 64 == hidden (<= 2048), hidden
+ * and ffn multiples of 64, act = OM_ACT_SILU, ln_eps = rms_norm_eps, pooling OM_POOL_NONE / FIRST / MEAN / LAST; the position, type,
+ * relative-bias, rope-theta and window fields are ignored.
+ * Weights: OmLayerWeights / OmEncoderWeights as they are --
+ *   qkv_w  [(n_heads + 2 n_kv_heads) * 64, H] rows q_proj | k_proj | v_proj, qkv_b alongside or NULL (Qwen2: biases; Llama attention_bias)
+ *   o_w    [H, H] o_proj, o_b or NULL;  ln1_g input_layernorm, ln2_g post_attention_layernorm (RMSNorm: no biases)
+ *   ffn1_w [F, H] gate_proj, ffn1g_w [F, H] up_proj, ffn2_w [H, F] down_proj (no biases);  word_emb embed_tokens, final_ln_g norm.
+ * Key k is visible from query q iff k <= q and attention_mask[b][k] != 0; positions are 0 .. L - 1 whatever the padding (HF's
+ * arange).  L <= 1024.  out_hidden [B, L, H] in base.dtype or NULL; out_reps f32 [B, D].  No packed rows, no training entry.
+ * ------------------------------------------------------------------------ */
+typedef struct OmCausalConfig {
+  OmEncoderConfig base;
+  int n_kv_heads;               /* config.num_key_value_heads: divides n_heads (n_heads: MHA, 1: MQA)                          */
+  float rope_attention_scaling; /* rotary_emb.attention_scaling: cos and sin are multiplied by it (1 for default / linear / llama3) */
+  float inv_freq[32];           /* rotary_emb.inv_freq, read on the host: serves the rope types whose frequencies do not depend on L */
+} OmCausalConfig;
+size_t om_causal_encoder_workspace_bytes(const OmCausalConfig* cfg, int64_t B, int64_t L);
+int om_causal_encoder_forward(const OmCausalConfig* cfg, const OmEncoderWeights* w, const int64_t* input_ids,
+                              const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * One decoder position of a T5 encoder-decoder over the encoder's output (inference):

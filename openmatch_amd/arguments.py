@@ -21,7 +21,7 @@ class ModelArguments:
     # bi-encoder structure
     untie_encoder: bool = _f(False, "separate query and passage encoders")
     feature: str = _f("last_hidden_state", "which encoder output feeds the pooling")
-    pooling: str = _f("first", "'first' (CLS) or 'mean' (mask-weighted)")
+    pooling: str = _f("first", "'first' (CLS), 'mean' (mask-weighted) or 'last' (last unmasked token; Llama / Qwen2 backbones)")
     # projection head
     add_linear_head: bool = _f(False)
     projection_in_dim: int = _f(768)

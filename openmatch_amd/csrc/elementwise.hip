@@ -363,6 +363,16 @@ int omk_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, h
   return 0;
 }
 
+// x in f32 (a residual stream kept in f32 under a 16-bit compute format: encoder_causal.hip) -> y in the compute format
+int omk_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
+                           float eps, int rms, hipStream_t s) {
+  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
+  if (M <= 0) return 0;
+  if (dtype == OM_BF16) return launch_ln<float, bf16_t>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
+  if (dtype == OM_F16) return launch_ln<float, f16_t>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
+  return launch_ln<float, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
+}
+
 // x in the compute format (optionally two planes, bf16) -> y in f32
 int omk_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b,
                          int64_t M, int H, float eps, int rms, hipStream_t s, const void* x_lo, const int* rows, int lo8) {

@@ -15,6 +15,8 @@ int omk_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_
                          int64_t M, int H, float eps, int rms, hipStream_t s, const void* x_lo = nullptr,
                          const int* rows = nullptr /* gather: output row r normalises input row rows[r] */,
                          int lo8 = 0 /* 1: x_lo is the eight-bit plane of omk_lo8_offset; ldx = H or a multiple of it (the CLS-row gather) */);
+int omk_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
+                           float eps, int rms, hipStream_t s);      // f32 rows -> the compute format (a residual stream kept in f32)
 int omk_embed(int dtype, const int64_t* ids, const int64_t* type_ids, const float* word,
               const float* pos, const float* type, const float* g, const float* b, void* out,
               int64_t M, int L, int H, int vocab, int type_vocab, float eps, int bert,

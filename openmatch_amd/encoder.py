@@ -1,7 +1,7 @@
 """Host side of the HIP encoder: turns a HF `BertModel` / `RobertaModel` / `DistilBertModel` / `MPNetModel` / `T5EncoderModel` /
-`ModernBertModel` (the parameter
+`ModernBertModel` / `LlamaModel` / `Qwen2Model` (the parameter
 container the reference keeps in `DRModel.lm_q / lm_p`) into the packed device weights that
-`om_encoder_forward` consumes, and launches it.
+`om_encoder_forward` (`om_causal_encoder_forward` for the decoder-only backbones) consumes, and launches it.
 
 The HF module's own `forward` is never called on this path; it stays the owner of the
 parameters so `state_dict()` / `save_pretrained()` keep the reference's checkpoint layout
@@ -46,6 +46,8 @@ def inference_code(model, code, seq_len):
     if code != N.OM_F16:
         return code
     cfg = getattr(model, "config", None)
+    if _arch_of(model) == "causal":              # Llama / Qwen2: float16 and bfloat16 as asked (nothing clamps, as under the reference's autocast)
+        return code
     if _arch_of(model) == "modernbert":          # the GeGLU feed-forward with erf-GELU: float16 as for erf-GELU BERT
         return code if getattr(cfg, "hidden_activation", None) == "gelu" else N.OM_BF16
     if _arch_of(model) == "t5":
@@ -121,19 +123,27 @@ def shadows_of(param):
     return out
 
 
+# what AutoModel returns for RepLLaMA-style / Qwen2-based / SmolLM / TinyLlama embedders; MistralModel (head_dim 128 checkpoints, a
+# sliding window) and every *ForCausalLM wrapper stay refused by name
+_CAUSAL_CLASSES = ("LlamaModel", "Qwen2Model")
+
+
 def _arch_of(model):
     name = type(model).__name__
     if "T5" in name:
         return "t5"
     if name.startswith("ModernBert"):    # ModernBertModel: pre-LayerNorm stack with rotary positions and sliding-window layers
         return "modernbert"
+    if name in _CAUSAL_CLASSES:          # decoder-only backbones as encoders: pre-RMSNorm, rotary grouped-query CAUSAL attention, SwiGLU
+        return "causal"
     # BertModel; RobertaModel / XLMRobertaModel (the BERT stack behind offset position ids); DistilBertModel (no token types);
     # MPNetModel (no token types, RoBERTa position numbering, one relative-position bias table for all layers) -- by an explicit
     # rule (flavours.FLAVOURS): AlbertModel, MobileBertModel, SqueezeBertModel, ... carry "Bert" in their names and another layout
     if flavour_of(model) is not None:
         return "bert"
     raise NotImplementedError(
-        f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder and ModernBERT backbones; got {name}")
+        f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder, ModernBERT and Llama / Qwen2 "
+        f"(head_dim 64, inference) backbones; got {name}")
 
 
 def position_offset(model):
@@ -324,7 +334,90 @@ def _pack_modernbert(model, code, device):
     return pk
 
 
-_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert}
+def causal_config_fields(cfg, model):
+    """The OmCausalConfig fields of a `LlamaModel` / `Qwen2Model` that do not depend on the compute format, after refusing (by name and
+    limit, before anything touches the device) what the HIP stack does not serve.  The rotary frequencies and the cos / sin scaling
+    are the module's OWN (`rotary_emb.inv_freq`, `rotary_emb.attention_scaling`): `default`, `linear` and `llama3` rope without
+    restating HF's rules; the types whose frequencies depend on the sequence length are refused."""
+    name = type(model).__name__ if model is not None else "Llama / Qwen2"
+    heads, hidden = int(cfg.num_attention_heads), int(cfg.hidden_size)
+    head_dim = getattr(cfg, "head_dim", None) or hidden // heads
+    if head_dim != 64 or heads * 64 != hidden:
+        raise NotImplementedError(f"{name}: only head_dim 64 with num_attention_heads * 64 == hidden_size is supported "
+                                  f"(got head_dim {head_dim}, {heads} heads, hidden_size {hidden}); head_dim 128 has no attention kernel")
+    n_kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
+    if n_kv < 1 or heads % n_kv:
+        raise NotImplementedError(f"{name}: num_key_value_heads ({n_kv}) must divide num_attention_heads ({heads})")
+    if hidden % 64 or cfg.intermediate_size % 64 or hidden > 2048:
+        raise NotImplementedError(f"{name}: hidden_size and intermediate_size must be multiples of 64, hidden_size at most 2048 "
+                                  f"(got {hidden}, {cfg.intermediate_size})")
+    if getattr(cfg, "mlp_bias", False):
+        raise NotImplementedError(f"{name} with mlp_bias = True is not supported by the HIP encoder")
+    if getattr(cfg, "use_sliding_window", False):
+        raise NotImplementedError(f"{name} with use_sliding_window = True is not supported by the HIP encoder (causal attention over the whole prefix only)")
+    if any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
+        raise NotImplementedError(f"{name}: every layer must be full_attention; got layer_types {list(cfg.layer_types)}")
+    if cfg.hidden_act != "silu":
+        raise NotImplementedError(f"{name}: hidden_act must be 'silu'; got {cfg.hidden_act!r}")
+    rp = getattr(cfg, "rope_parameters", None) or {}
+    rope_type = rp.get("rope_type", "default")
+    if rope_type not in ("default", "linear", "llama3"):
+        raise NotImplementedError(f"{name}: rope type {rope_type!r} is not supported by the HIP encoder (its frequencies depend on the "
+                                  "sequence length); default, linear and llama3 are")
+    rot = model.rotary_emb
+    inv = rot.inv_freq.detach().to("cpu", torch.float32).reshape(-1)
+    if inv.numel() != 32:
+        raise NotImplementedError(f"{name}: expected 32 rotary frequencies (head_dim 64, full rotation); got {inv.numel()}")
+    return dict(arch=N.ARCH_CAUSAL, hidden=hidden, n_layers=int(cfg.num_hidden_layers), n_heads=heads, head_dim=64,
+                ffn=int(cfg.intermediate_size), vocab=int(cfg.vocab_size), max_pos=0, type_vocab=0, act=N.ACT_SILU,
+                ln_eps=float(cfg.rms_norm_eps), rel_buckets=0, rel_max_dist=0,
+                n_kv_heads=n_kv, rope_attention_scaling=float(rot.attention_scaling), inv_freq=[float(v) for v in inv])
+
+
+def _pack_causal(model, code, device):
+    """LlamaModel / Qwen2Model: the embedding table and the RMSNorm weights in f32, the matrices in the compute dtype; q / k / v
+    fused to rows q | k | v of [(heads + 2 kv) * 64, H] (a missing bias of a projection that has siblings with one counts as zero)."""
+    cfg = model.config
+    fields = causal_config_fields(cfg, model)
+    wd = torch_dtype_of(code)
+    f32 = torch.float32
+    pk = _Packed()
+    w = pk.weights
+    w.word_emb = pk.dev(model.embed_tokens.weight, f32, device)
+    w.final_ln_g = pk.dev(model.norm.weight, f32, device)
+    layers = (N.OmLayerWeights * cfg.num_hidden_layers)()
+    for i, layer in enumerate(model.layers):
+        sa, mlp, lw = layer.self_attn, layer.mlp, layers[i]
+        projs = [sa.q_proj, sa.k_proj, sa.v_proj]
+        lw.qkv_w = pk.dev(torch.cat([p.weight for p in projs], 0), wd, device, [p.weight for p in projs])
+        if any(p.bias is not None for p in projs):
+            if all(p.bias is not None for p in projs):
+                lw.qkv_b = pk.dev(torch.cat([p.bias for p in projs], 0), f32, device, [p.bias for p in projs])
+            else:
+                lw.qkv_b = pk.dev(torch.cat([p.bias if p.bias is not None else p.weight.new_zeros(p.out_features) for p in projs], 0), f32, device)
+        lw.o_w = pk.dev(sa.o_proj.weight, wd, device)
+        if sa.o_proj.bias is not None:
+            lw.o_b = pk.dev(sa.o_proj.bias, f32, device)
+        lw.ln1_g = pk.dev(layer.input_layernorm.weight, f32, device)
+        lw.ln2_g = pk.dev(layer.post_attention_layernorm.weight, f32, device)
+        lw.ffn1_w = pk.dev(mlp.gate_proj.weight, wd, device)
+        lw.ffn1g_w = pk.dev(mlp.up_proj.weight, wd, device)
+        lw.ffn2_w = pk.dev(mlp.down_proj.weight, wd, device)
+    pk.layers = layers
+    w.layers_host = C.cast(layers, C.POINTER(N.OmLayerWeights))
+    pk.cfg = dict(dtype=code, **fields)
+    return pk
+
+
+def causal_config(pk_cfg, pooling, normalize):
+    """The OmCausalConfig of a packed Llama / Qwen2 (`_pack_causal`'s cfg dict + the head fields) for one call."""
+    own = ("n_kv_heads", "rope_attention_scaling", "inv_freq")
+    base = N.OmEncoderConfig(pooling=pooling, normalize=int(bool(normalize)), **{k: v for k, v in pk_cfg.items() if k not in own})
+    return N.OmCausalConfig(base=base, n_kv_heads=pk_cfg["n_kv_heads"], rope_attention_scaling=pk_cfg["rope_attention_scaling"],
+                            inv_freq=(C.c_float * 32)(*pk_cfg["inv_freq"]))
+
+
+_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert, "causal": _pack_causal}
 
 
 def _pack_t5_decoder(model, code, device):
@@ -413,6 +506,8 @@ def _ensure_folded(pk, device):
     if getattr(pk, "fold_done", False):
         return
     pk.fold_done = True
+    if pk.cfg.get("arch") == N.ARCH_CAUSAL:      # (no fused-norm path: nothing to fold)
+        return
     lib = N.lib()
     cfg = N.OmEncoderConfig(pooling=N.POOL_NONE, normalize=0, **pk.cfg)
     nfold = lib.om_encoder_fold_bytes(C.byref(cfg))
@@ -476,7 +571,16 @@ def token_types_of(model, items):
     return tti
 
 
-_POOL = {None: N.POOL_NONE, "first": N.POOL_FIRST, "mean": N.POOL_MEAN}
+_POOL = {None: N.POOL_NONE, "first": N.POOL_FIRST, "mean": N.POOL_MEAN, "last": N.POOL_LAST}
+
+
+def check_pooling(model, pooling):
+    """Unknown values: the reference's ValueError.  "last" (the hidden state of each row's last unmasked token, the usual
+    last_token_pool of decoder-only embedders) exists for the causal backbones only."""
+    if pooling not in _POOL:
+        raise ValueError("Unknown pooling type: {}".format(pooling))
+    if pooling == "last" and _arch_of(model) != "causal":
+        raise NotImplementedError(f"pooling='last' is served for Llama / Qwen2 backbones only; {type(model).__name__} pools with 'first' or 'mean'")
 
 
 def packed_rows_bound(mask):
@@ -545,8 +649,7 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     input_ids / attention_mask / optional token_type_ids as int64 device tensors.
     packed_rows (with want_hidden=False): run om_encoder_forward_packed over that many rows (packed_rows_bound of the
     mask, computed where the mask still lives on the host) instead of B * L padded ones."""
-    if pooling not in _POOL:
-        raise ValueError("Unknown pooling type: {}".format(pooling))
+    check_pooling(model, pooling)
     ids = items["input_ids"]
     mask = items["attention_mask"]
     tti = token_types_of(model, items)
@@ -561,6 +664,8 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     device = ids.device
     code = inference_code(model, code, ids.shape[1])
     pk = packed_weights(model, head, code, device)
+    if _arch_of(model) == "causal":
+        return _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden)
     _ensure_folded(pk, device)
     cfg = N.OmEncoderConfig(pooling=_POOL[pooling], normalize=int(bool(normalize)), **pk.cfg)
     B, L = ids.shape
@@ -590,6 +695,25 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
         N.check(lib.om_encoder_forward(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask),
                                        N.ptr(tti), B, L, N.ptr(hidden), N.ptr(reps),
                                        C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+    return hidden, reps
+
+
+def _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden):
+    """hip_encode for a packed Llama / Qwen2 through om_causal_encoder_forward (padded rows only: no packed-rows entry)."""
+    device = ids.device
+    cfg = causal_config(pk.cfg, _POOL[pooling], normalize)
+    B, L = ids.shape
+    H = cfg.base.hidden
+    D = cfg.base.head_out if cfg.base.head_in > 0 else H
+    lib = N.lib()
+    LAST_CALL.update(rows=B * L, packed=False)
+    with torch.cuda.device(device):
+        nbytes = lib.om_causal_encoder_workspace_bytes(C.byref(cfg), B, L)
+        ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
+        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
+        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
+        N.check(lib.om_causal_encoder_forward(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
+                                              C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
     return hidden, reps
 
 

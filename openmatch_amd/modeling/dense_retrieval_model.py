@@ -124,7 +124,7 @@ class DRModel(nn.Module):
             # (modeling/dense_retrieval_model.py:143-149), which fails on HF's 2-D pooler_output
             raise NotImplementedError("only feature='last_hidden_state' is produced by the HIP encoder (the reference's own "
                                       "encode() fails on 2-D features such as pooler_output)")
-        if self.pooling not in ("first", "mean"):
+        if self.pooling not in ("first", "mean", "last"):      # ("last": Llama / Qwen2 backbones only -- encoder.check_pooling)
             raise ValueError("Unknown pooling type: {}".format(self.pooling))
         code = compute_dtype_code(self.model_args)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())

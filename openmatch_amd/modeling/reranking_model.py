@@ -70,7 +70,7 @@ class RRModel(nn.Module):
         items = BatchEncoding(items)
         if "T5" in type(self.lm).__name__ and not self.model_args.encoder_only:
             return self._encode_mono_t5(items)
-        if self.pooling not in ("first", "mean"):
+        if self.pooling not in ("first", "mean", "last"):      # ("last": Llama / Qwen2 backbones only -- encoder.check_pooling)
             raise ValueError("Unknown pooling type: {}".format(self.pooling))
         code = compute_dtype_code(self.model_args)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.lm.parameters()):

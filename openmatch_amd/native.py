@@ -13,9 +13,10 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libopenmatch_hip.so")
 
 OM_F32, OM_BF16, OM_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_GELU_TANH = 0, 1, 2, 3
+ACT_SILU = 5
 ACT_MUL_RESID = 0x100
-ARCH_BERT, ARCH_T5, ARCH_MODERNBERT = 0, 1, 2
-POOL_NONE, POOL_FIRST, POOL_MEAN = 0, 1, 2
+ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL = 0, 1, 2, 3
+POOL_NONE, POOL_FIRST, POOL_MEAN, POOL_LAST = 0, 1, 2, 3
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
 OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
 OPT_GEMM_GROUP_M, OPT_GEMM_VARIANT, OPT_GEMM_SKINNY_M = 6, 12, 19
@@ -47,6 +48,11 @@ class OmEncoderConfig(C.Structure):
                 # ABI v6 (ModernBERT; zero for BERT / T5)
                 ("rope_theta_global", c_float), ("rope_theta_local", c_float), ("half_window", c_int),
                 ("sliding_layers", C.c_uint64)]
+
+
+class OmCausalConfig(C.Structure):
+    """Llama / Qwen2 (om_causal_encoder_forward): the encoder's config, untouched, followed by what a grouped-query rotary stack adds."""
+    _fields_ = [("base", OmEncoderConfig), ("n_kv_heads", c_int), ("rope_attention_scaling", c_float), ("inv_freq", c_float * 32)]
 
 
 class OmEncoderWeights(C.Structure):
@@ -118,6 +124,8 @@ _SIGNATURES = {
     "om_debug_attention_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float,
                                       C.c_uint64, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "om_debug_rope": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "om_debug_attention_causal": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
+    "om_debug_rope_gqa": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, C.POINTER(c_float), c_float, c_void_p]),
     "om_debug_mask_extent": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_debug_attention_last": (c_int, []),
@@ -143,6 +151,9 @@ _SIGNATURES = {
     "om_encoder_forward": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p,
                                    c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    "om_causal_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmCausalConfig), c_int64, c_int64]),
+    "om_causal_encoder_forward": (c_int, [C.POINTER(OmCausalConfig), C.POINTER(OmEncoderWeights), c_void_p, c_void_p, c_int64, c_int64,
+                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_encoder_packed_supported": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int64, c_int64, c_int64]),
     "om_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64, c_int64]),
     "om_encoder_forward_packed": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p,

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import native as N
-from .encoder import (_POOL, _arch_of, check_position_layout, packed_decoder_weights, packed_weights, position_offset,
+from .encoder import (_POOL, _arch_of, check_pooling, check_position_layout, packed_decoder_weights, packed_weights, position_offset,
                       token_types_of, torch_dtype_of, training_code)
 from .flavours import bert_parts, dropout_probs
 
@@ -229,6 +229,10 @@ def encode_train(model, head, items, pooling, normalize, code, training, packed_
     if _arch_of(model) == "modernbert":
         raise NotImplementedError("ModernBERT training is not supported by the HIP encoder (inference only: encode in eval "
                                   "mode under torch.no_grad())")
+    if _arch_of(model) == "causal":
+        raise NotImplementedError("Llama / Qwen2 training is not supported by the HIP encoder (inference only: encode in eval "
+                                  "mode under torch.no_grad())")
+    check_pooling(model, pooling)
     code = LAST_TRAIN_CODE = training_code(code, model)
     ids = items["input_ids"].to(torch.int64).contiguous()
     mask = items["attention_mask"].to(device=ids.device, dtype=torch.int64).contiguous()
