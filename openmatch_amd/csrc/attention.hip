@@ -15,7 +15,7 @@
 // and the probabilities already sit in the A-operand layout of the P·V MFMA.
 #include <type_traits>
 
-#include "attn_common.h"
+#include "attn_chunked.h"
 #include "attn_plan.h"
 
 static thread_local int g_attn_last = 0;      // family | key tiles << 8 of this thread's last forward launch: omk_attention writes it from its plan
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(64 * KT) void attention_kernel(
   }
   // additive key mask: padded keys get finfo.min (HF extended mask); keys past L do not exist
   for (int k = tid; k < KT * 32; k += nthr)
-    sM[k] = k < L ? (mask[b * L + k] != 0 ? 0.f : -3.4028235e38f) : -INFINITY;
+    sM[k] = k < L ? (mask[b * L + k] != 0 ? 0.f : kFinfoMin) : -INFINITY;
   __syncthreads();
 
   const int wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
@@ -175,15 +175,6 @@ __global__ __launch_bounds__(64 * KT) void attention_kernel(
 //     wave's own K rows and written out as whole 128-byte lines;
 //   * softmax in the log2 domain: v = fma(s, scale log2e, mask), exp2(v - max) -- five instructions per score.
 // Masked keys carry -1e30 (finite: a fully masked row stays uniform, as with HF's finfo.min), keys past L -inf.
-#include "gemm_core7.h"
-
-typedef short v4s_a_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4s_a_t vtrd(const char* p) {           // ds_read_b64_tr_b16
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_a_t __attribute__((address_space(3)))*)(p));
-}
-template <typename F>
-__device__ __forceinline__ F vfrag_of(v4s_a_t a, v4s_a_t b) { return __builtin_bit_cast(F, (bf16x8_t){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}); }
-
 // DBG (timing experiments, OM_OPT_ATTENTION_DEBUG): bit 0 no K / V fetch, bit 1 no arithmetic, bit 2 no stores
 // T: bf16_t or f16_t (the float16 inference mode) -- same instruction stream, the other MFMA / conversion opcodes
 // KTV: the key tiles this (batch, head) walks -- KT, or fewer when its trailing tiles hold no unmasked key (round 4).  Every key
@@ -422,21 +413,14 @@ static int launch_attn16(const void* qkv, void* ctx, const int64_t* mask, const 
   return 0;
 }
 // ---------------------------------------------------------------------------------------------------------------
-// Beyond 256 tokens in the 16-bit formats (round 6): the body of the kernel above inside a loop over 128-key chunks with the online
-// softmax.  A workgroup owns 128 queries of one (sequence, head) -- four waves of 32 -- and per chunk: K and V rows by LDS-DMA
-// (row-major, swizzled on the source address), S^T = K Q^T, exp2 softmax against the running maximum, V^T fragments by transposing
-// LDS reads.  O^T keeps a query per LANE, so the rescaling by exp2(m_old - m_new) is one multiply per accumulator register with the
-// lane's own factor (the f32 kernel below keeps queries in registers and sends the factors through an LDS table).  Dropout, the T5
-// bias table and packed rows as in the kernel above.  Measured at 16 x 512 tokens, 12 heads: profiles/r06_train_long_sequences.txt.
+// Beyond 256 tokens in the 16-bit formats: attn_chunked16 (attn_chunked.h) over every key -- the body of the kernel above inside a loop
+// over 128-key chunks with the online softmax.  Dropout, the T5 bias table and packed rows as in the kernel above: cu != NULL makes
+// sequence b rows cu[b] .. cu[b + 1] - 1 of qkv / ctx and L its own row count, while the mask, the bias table and the dropout hash keep
+// the padded pitch Lm.  No clipping to kmax.
 template <typename T, bool BIAS, bool DROP>
 __global__ __launch_bounds__(256, 2) void attention_fwd16c_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask,
     const float* __restrict__ pos_bias, int Lm, int H, int heads, float scale, float drop_p, uint64_t seed, const int* __restrict__ cu) {
-  typedef typename MmaOps<T>::frag_t frag_t;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const sK = smem;
-  char* const sV = smem + 128 * 128;
-  float* const sM = (float*)(smem + 2 * 128 * 128);
   const int h = blockIdx.x % heads;
   const int64_t b = blockIdx.x / heads;
   int64_t row0 = b * Lm;
@@ -447,154 +431,7 @@ __global__ __launch_bounds__(256, 2) void attention_fwd16c_kernel(
   }
   const int qb = blockIdx.y * 128;
   if (qb >= L) return;                                      // (whole workgroup)
-  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t ld2 = 6 * (int64_t)H;                       // row pitch of qkv in bytes
-  const char* const base = (const char*)(qkv + row0 * 3 * (int64_t)H + h * 64);
-  const float LOG2E = 1.4426950408889634f;
-  const int q0 = qb + wave * 32;
-  const bool active = q0 < L;                               // (wave-uniform; an inactive wave still fetches its share of every chunk)
-  const int qrow = (q0 + l31) < L ? (q0 + l31) : (L - 1);
-  frag_t qf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) qf[kk] = *(const frag_t*)(base + (int64_t)qrow * ld2 + (kk * 2 + half) * 16);
-  const float c2 = scale * LOG2E;
-  const AttnDrop dr(drop_p);
-  const int key = (l31 >> 1) & 7;
-  const int i16 = lane & 15;
-  const char* const vt0 = sV + (4 * half + (i16 >> 2)) * 128 + 32 * ((lane >> 4) & 1) + 8 * (i16 & 3);
-  const int vsw = (i16 >> 3) & 1;
-  float m_run = -INFINITY, l_run = 0.f;
-  f32x16_t o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-
-  for (int kc = 0; kc < L; kc += 128) {
-    __syncthreads();                                         // the previous chunk has been consumed by every wave
-    // K and V rows kc .. kc + 127: instruction i of wave w moves rows (i * 4 + w) * 8 .. + 7, lane -> row (lane >> 3), physical
-    // 16-byte chunk (lane & 7) <- source chunk (lane & 7) ^ ((row >> 1) & 7) for K, ^ 4 ((row >> 1) & 1) for V (the kernel above)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = (i * 4 + wave) * 8 + (lane >> 3);
-      const int rr = (kc + r) < L ? (kc + r) : (L - 1);
-      const uint32_t off = (uint32_t)(rr * ld2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
-      const uint32_t offv = (uint32_t)(rr * ld2) + (((lane & 7) ^ (((r >> 1) & 1) << 2)) << 4);
-      const uint32_t dst = (uint32_t)((i * 4 + wave) * 1024);
-      g7_dma(base + 2 * H, off, g7_lds_addr(sK) + dst);
-      g7_dma(base + 4 * H, offv, g7_lds_addr(sV) + dst);
-    }
-    if (tid < 128) sM[tid] = (kc + tid) < L ? (mask[b * Lm + kc + tid] != 0 ? 0.f : -1e30f) : -INFINITY;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the DMA above is not in hipcc's bookkeeping
-    __syncthreads();
-    if (!active) continue;
-
-    f32x16_t s[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
-      const char* krow = sK + (t * 32 + l31) * 128;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const frag_t a = *(const frag_t*)(krow + (((kk * 2 + half) ^ key) << 4));
-        MmaOps<T>::mma(a, qf[kk], s[t]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    float mx = m_run;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int k0 = t * 32 + 8 * g + 4 * half;
-        const f32x4_t mb = *(const f32x4_t*)(sM + k0);
-        f32x4_t pb = {0.f, 0.f, 0.f, 0.f};
-        if (BIAS) {
-          const float* pr = pos_bias + ((int64_t)h * Lm + qrow) * Lm;      // (the table's pitch: the padded length, also for packed rows)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) pb[e] = pr[(kc + k0 + e) < Lm ? (kc + k0 + e) : (Lm - 1)] * LOG2E;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = fmaf(s[t][4 * g + e], c2, mb[e]) + pb[e];
-          s[t][4 * g + e] = v;
-          mx = fmaxf(mx, v);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // the first chunk always holds key 0 (unmasked, or -1e30: finite): mx is finite from here on
-    const float alpha = __builtin_amdgcn_exp2f(m_run - mx);   // exp2(-inf) = 0 on the first chunk
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(s[t][r] - mx);
-        s[t][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 32, 64);
-    l_run = l_run * alpha + sum;
-    m_run = mx;
-    if (DROP) {       // (keyed with the mask's row pitch Lm: the backward kernels and a packed step regenerate the same mask)
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const uint64_t bits = attn_drop_bits(seed, b, h, heads, Lm, q0 + l31, (kc + t * 32 + 8 * g + 4 * half) >> 2);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s[t][4 * g + e] = attn_drop_keep(bits, e, dr.thresh) ? s[t][4 * g + e] : 0.f;
-          __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;        // O^T: this lane's query in every register
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint4 pa[2];      // probabilities of this key tile as two k slabs (k slot e of half h <-> register 8u + e)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        pa[u] = make_uint4(Half16<T>::pack2(s[t][8 * u + 0], s[t][8 * u + 1]), Half16<T>::pack2(s[t][8 * u + 2], s[t][8 * u + 3]),
-                           Half16<T>::pack2(s[t][8 * u + 4], s[t][8 * u + 5]), Half16<T>::pack2(s[t][8 * u + 6], s[t][8 * u + 7]));
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const char* p = vt0 + (t * 32 + 16 * u) * 128 + ((dt ^ vsw) << 6);
-          const frag_t vf = vfrag_of<frag_t>(vtrd(p), vtrd(p + 8 * 128));
-          MmaOps<T>::mma(vf, __builtin_bit_cast(frag_t, pa[u]), o[dt]);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // O / l (x the keep scale): through the wave's own K rows, out as whole 128-byte rows (the kernel above)
-  __syncthreads();
-  if (!active) return;
-  const float inv = (DROP ? dr.keep_scale : 1.0f) / l_run;
-  char* const so = sK + (wave * 32) * 128;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int gp = 0; gp < 2; ++gp) {
-      uint32_t a0 = Half16<T>::pack2(o[dt][8 * gp + 0] * inv, o[dt][8 * gp + 1] * inv), a1 = Half16<T>::pack2(o[dt][8 * gp + 2] * inv, o[dt][8 * gp + 3] * inv);
-      uint32_t b0 = Half16<T>::pack2(o[dt][8 * gp + 4] * inv, o[dt][8 * gp + 5] * inv), b1 = Half16<T>::pack2(o[dt][8 * gp + 6] * inv, o[dt][8 * gp + 7] * inv);
-      auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-      auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-      *(uint4*)(so + l31 * 128 + (((4 * dt + 2 * gp + half) ^ (l31 & 7)) << 4)) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-    }
-  char* const out = (char*)(ctx + (row0 + q0) * (int64_t)H + h * 64);
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = it * 8 + (lane >> 3), c = lane & 7;
-    const uint4 v = *(const uint4*)(so + row * 128 + ((c ^ (row & 7)) << 4));
-    if (q0 + row < L) *(uint4*)(out + (int64_t)row * H * 2 + c * 16) = v;
-  }
+  attn_chunked16<T, AttnFull, BIAS, DROP>(attn_rows_fused(qkv, ctx, row0, H, h), AttnFull{}, mask + b * Lm, L, L, qb, scale, AttnFullArgs{pos_bias, drop_p, seed, b, h, heads, Lm});
 }
 
 template <typename T, bool BIAS, bool DROP>
@@ -607,160 +444,21 @@ static int launch_attn16c(const void* qkv, void* ctx, const int64_t* mask, const
   return 0;
 }
 // ---------------------------------------------------------------------------------------------------------------
-// Long sequences (256 < L <= 1024, inference): the kernels above keep a whole score row per lane (L / 2 registers) and
-// all of K, V in LDS, which stops at 256 keys.  Document corpora are encoded at 512 tokens (the reference accepts anything
-// up to max_position_embeddings).  Here a workgroup owns 128 QUERIES of one (batch, head) -- four waves of 32 -- and walks
-// the keys in chunks of 128 with the online softmax: running maximum m and sum l per query, O rescaled by
-// exp(m_old - m_new) per chunk.  K chunk row-major (swizzled), V chunk transposed, as in attention_kernel<T, 4>; the
-// accumulators O[query][d] keep queries in REGISTERS and d in lanes (SlabMma), so the per-query factors travel through a
-// 32-float LDS table per wave.  Constant registers and LDS for any L; K / V are re-read once per 128 queries (L2).
+// Long sequences (256 < L <= 1024) in any format: the kernels above keep a whole score row per lane (L / 2 registers) and all of
+// K, V in LDS, which stops at 256 keys.  Document corpora are encoded at 512 tokens (the reference accepts anything up to
+// max_position_embeddings).  attn_chunked_qreg (attn_chunked.h) over every key; bias, dropout and packed rows (cu) as in the kernel above.
 template <typename T>
 __global__ __launch_bounds__(256) void attention_long_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask,
     const float* __restrict__ pos_bias, int Lm, int H, int heads, float scale, float drop_p, uint64_t seed, const int* __restrict__ cu) {
-  // cu != NULL (packed rows beyond 256 tokens, round 6): sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv / ctx, L its own row count; the mask,
-  // the bias table and the dropout hash keep the padded pitch Lm.
-  // drop_p > 0 (round 6: training beyond 256 tokens): the probabilities that meet V are masked with the (sequence, head, query, key)
-  // hash the backward regenerates (attn_common.h); the normaliser is the sum of the unmasked ones, as in the other kernels
-  typedef AttnGeom<T> G;
-  typedef typename MmaOps<T>::frag_t frag_t;
-  constexpr int LP = 128 + 4;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* sK = smem;
-  T* sVt = (T*)(smem + 128 * G::ROWB);
-  float* sM = (float*)(smem + 128 * G::ROWB + 64 * LP * (int)sizeof(T));
-  float* sF = sM + 128;                                     // [4 waves][32] per-query factors
-
   const int h = blockIdx.x % heads;
   const int64_t b = blockIdx.x / heads;
   const int qb = blockIdx.y * 128;
-  const int tid = threadIdx.x;
-  const int64_t ld = 3 * (int64_t)H;
   int64_t row0 = b * Lm;
   int L = Lm;
   if (cu) { row0 = cu[b]; L = cu[b + 1] - cu[b]; }
   if (qb >= L) return;                                       // (whole workgroup: a sequence shorter than this query block)
-  const T* base = qkv + row0 * ld + h * 64;
-  const int wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-  const int q0 = qb + wave * 32;
-  const int qrow = (q0 + l31) < L ? (q0 + l31) : (L - 1);
-  frag_t qf[G::NKK];
-#pragma unroll
-  for (int kk = 0; kk < G::NKK; ++kk) qf[kk] = *(const frag_t*)(base + (int64_t)qrow * ld + (kk * 2 + half) * G::EPC);
-
-  const AttnDrop dr_(drop_p);
-  const uint32_t thresh = dr_.thresh;
-  const float keep_scale = dr_.keep_scale;
-  float m_run = -INFINITY, l_run = 0.f;
-  f32x16_t o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-
-  for (int kc = 0; kc < L; kc += 128) {
-    __syncthreads();                                         // the previous chunk has been consumed by every wave
-    for (int idx = tid; idx < 128 * G::CPR; idx += 256) {
-      const int row = idx / G::CPR, c = idx % G::CPR;
-      uint4 kv = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
-      if (kc + row < L) {
-        kv = *(const uint4*)(base + (int64_t)(kc + row) * ld + H + c * G::EPC);
-        vv = *(const uint4*)(base + (int64_t)(kc + row) * ld + 2 * H + c * G::EPC);
-      }
-      *(uint4*)(sK + row * G::ROWB + ((c ^ G::key(row)) << 4)) = kv;
-      const T* ve = (const T*)&vv;
-#pragma unroll
-      for (int e = 0; e < G::EPC; ++e) sVt[(c * G::EPC + e) * LP + row] = ve[e];
-    }
-    if (tid < 128) sM[tid] = (kc + tid) < L ? (mask[b * Lm + kc + tid] != 0 ? 0.f : -3.4028235e38f) : -INFINITY;
-    __syncthreads();
-
-    f32x16_t s[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
-      const int row = t * 32 + l31;
-      const char* krow = sK + row * G::ROWB;
-      const int key = G::key(row);
-#pragma unroll
-      for (int kk = 0; kk < G::NKK; ++kk) {
-        const frag_t a = *(const frag_t*)(krow + (((kk * 2 + half) ^ key) << 4));
-        MmaOps<T>::mma(a, qf[kk], s[t]);
-      }
-    }
-    float mx = m_run;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int k0 = t * 32 + 8 * g + 4 * half;
-        const f32x4_t mb = *(const f32x4_t*)(sM + k0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float v = s[t][4 * g + e] * scale;
-          if (pos_bias) {
-            const int kcol = (kc + k0 + e) < L ? (kc + k0 + e) : (L - 1);
-            v += pos_bias[((int64_t)h * Lm + qrow) * Lm + kcol];
-          }
-          v += mb[e];
-          s[t][4 * g + e] = v;
-          mx = fmaxf(mx, v);
-        }
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // the first chunk always holds key 0 (unmasked [CLS] or finfo.min, finite): mx is finite from here on
-    const float alpha = G::exp_(m_run - mx);                 // exp(-inf) = 0 on the first chunk
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = G::exp_(s[t][r] - mx);
-        sum += e;
-        s[t][r] = (thresh && !attn_drop_keep1(seed, b, h, heads, Lm, q0 + l31, kc + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, thresh)) ? 0.f : (thresh ? e * keep_scale : e);
-      }
-    sum += __shfl_xor(sum, 32, 64);
-    l_run = l_run * alpha + sum;
-    m_run = mx;
-    // rescale O: the factor of query q lives in lane q; O holds queries in registers -> through the wave's table
-    if (half == 0) sF[wave * 32 + l31] = alpha;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (same wave: LDS operations execute in order)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4_t a4 = *(const f32x4_t*)(sF + wave * 32 + 8 * g + 4 * half);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { o[0][4 * g + e] *= a4[e]; o[1][4 * g + e] *= a4[e]; }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) SlabMma<T>::run(s[t], sVt + l31 * LP + t * 32 + 4 * half, LP, o);
-  }
-  // O / l, parked in the wave's own K rows, stored as whole 16-byte vectors
-  __syncthreads();
-  if (half == 0) sF[wave * 32 + l31] = 1.0f / l_run;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  T* so = (T*)(sK + (size_t)(wave * 32) * G::ROWB);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const f32x4_t i4 = *(const f32x4_t*)(sF + wave * 32 + 8 * g + 4 * half);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int q = 8 * g + 4 * half + e;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) ElemOps<T>::store(so + q * 64 + dt * 32 + l31, o[dt][4 * g + e] * i4[e]);
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (q0 < L) {
-    T* out = ctx + (row0 + q0) * H + h * 64;
-    constexpr int VPR = G::ROWB / 16;
-#pragma unroll
-    for (int it = 0; it < 32 * VPR / 64; ++it) {
-      const int idx = it * 64 + lane, row = idx / VPR, c = idx % VPR;
-      const uint4 v = *(const uint4*)((const char*)so + row * G::ROWB + c * 16);
-      if (q0 + row < L) *(uint4*)((char*)(out + (int64_t)row * H) + c * 16) = v;
-    }
-  }
+  attn_chunked_qreg<T, AttnFull>(attn_rows_fused(qkv, ctx, row0, H, h), AttnFull{}, mask + b * Lm, L, L, qb, scale, AttnFullArgs{pos_bias, drop_p, seed, b, h, heads, Lm});
 }
 
 template <typename T>

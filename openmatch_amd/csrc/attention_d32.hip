@@ -23,8 +23,6 @@
 
 namespace {
 
-constexpr float kFinfoMin = -3.4028235e38f;
-
 template <typename T> struct D32 {             // one head's slice of a row: 64 bytes (16-bit) / 128 bytes (f32)
   static constexpr int EPC = AttnGeom<T>::EPC;          // elements per 16-byte chunk
   static constexpr int CPR = 32 / EPC;                  // chunks per row

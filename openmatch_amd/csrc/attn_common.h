@@ -56,6 +56,18 @@ template <> struct AttnGeom<float> {
   __device__ static inline float exp_(float x) { return expf(x); }
 };
 
+// HF's masked score in the natural-exp kernels: torch.finfo(float32).min
+constexpr float kFinfoMin = -3.4028235e38f;
+
+// ds_read_b64_tr_b16: a transposing LDS read of a row-major 16-bit image; two of them hand a lane eight k slots of one column, an
+// MFMA operand as read (attention_fwd16_body in attention.hip, attn_chunked16 in attn_chunked.h)
+typedef short v4s_a_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ v4s_a_t vtrd(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_a_t __attribute__((address_space(3)))*)(p));
+}
+template <typename F>
+__device__ __forceinline__ F vfrag_of(v4s_a_t a, v4s_a_t b) { return __builtin_bit_cast(F, (bf16x8_t){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}); }
+
 // One 32-wide slab of a contraction whose left operand sits in a 32x32 accumulator layout:
 //   o[dt][i][j] += sum_c a[i][c] * Bt[dt*32 + j][c]      (i = lane&31 of the A operand)
 // `a` holds, for lane (i, half), the 16 values c = (r&3) + 8(r>>2) + 4*half, r in [0,16);

@@ -28,10 +28,6 @@
 
 #include "kernels.h"
 
-int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s);
-int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                         const int* kmax, hipStream_t s);
-
 namespace {
 
 template <typename T> struct Io8;          // eight consecutive elements <-> floats

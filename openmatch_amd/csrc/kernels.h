@@ -40,12 +40,19 @@ int omk_attention(int dtype, const void* qkv, void* ctx, const int64_t* mask,
 struct AttnPlan;
 int omk_attention_d32(const AttnPlan& p, int dtype, const void* qkv, void* ctx, const int64_t* mask, const float* pos_bias, int64_t B, int L,
                       int H, int heads, float scale, float drop_p, uint64_t seed, hipStream_t s, int reverse, const int* kmax, const int* cu);
-// ModernBERT (attention_band.hip, head_dim 64, inference): rotary positions on the Q and K columns of qkv in place (position = row % L,
-// one device cos / sin table per theta), and attention where key k is visible from query q only if |q - k| <= w and k is unmasked.
-// Key chunks outside a query block's band are not visited.
+// ModernBERT (head_dim 64, inference): rotary positions on the Q and K columns of qkv in place (attention_causal.hip; position = row % L,
+// frequencies 1 / theta ** (2i / 64)), and attention where key k is visible from query q only if |q - k| <= w and k is unmasked
+// (attention_band.hip).  Key chunks outside a query block's band are not visited.
 int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s);
 int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
                        int w, const int* kmax, hipStream_t s);
+// Decoder-only backbones (attention_causal.hip, head_dim 64, inference): qkv is the grouped projection [M, (heads + 2 kv_heads) * 64]
+// (q heads | k heads | v heads), ctx [M, heads * 64].  Rotary positions on its q and k heads in place from the host's 32 frequencies
+// (cos, sin times `scaling`), and attention where key k is visible from query q iff k <= q and k is unmasked; query head h reads K / V
+// head h / (heads / kv_heads).  Its own launch: the planner of the bidirectional kernels (attn_plan.h) knows nothing of it.
+int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s);
+int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                         const int* kmax, hipStream_t s);
 // packed rows (om_encoder_forward_packed): cu[0..B] = offsets of the sequences (kmax[b] rows each) clamped to `rows`, cu[B + 1] = the
 // unclamped token count; cls_rows[b] = min(cu[b], rows - 1); row_map[t] = b * L + position of packed row t, -1 for the pad rows
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);

@@ -898,7 +898,7 @@ def test_band_widest_window_is_full_attention(dtype):
 
 
 def rope_table(theta, L):
-    """The f32 table recipe of csrc/attention_band.hip, written out again: inv_freq_i = 1 / f32(theta ** (2 i / 64)),
+    """The f32 table recipe of csrc/attention_causal.hip (omk_rope), written out again: inv_freq_i = 1 / f32(theta ** (2 i / 64)),
     angle = f32(inv_freq_i * pos), cos / sin of that f32 angle rounded to f32."""
     i = np.arange(32)
     e = (2 * i).astype(np.float32) / np.float32(64.0)

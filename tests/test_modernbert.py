@@ -1,5 +1,5 @@
 """ModernBERT (ModernBertModel) encoded through the HIP path: pre-LayerNorm stack, rotary positions, sliding-window layers and the
-GeGLU feed-forward (csrc/encoder.hip, csrc/attention_band.hip), against the HF module built at test time (random init, perturbed
+GeGLU feed-forward (csrc/encoder.hip, csrc/attention_causal.hip, csrc/attention_band.hip), against the HF module built at test time (random init, perturbed
 norms and embeddings, eager attention so its sliding-window mask is the explicit one), in fp32 on the CPU."""
 import ctypes as C
 
