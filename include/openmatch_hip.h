@@ -197,10 +197,17 @@ int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, vo
  * (q heads | k heads | v heads), ctx [rows, n_heads * 64]; query head h reads K / V head h / (n_heads / n_kv_heads).
  * om_debug_attention_causal: key k visible from query q iff k <= q and mask[b][k] != 0; it computes the key extents (one more small
  * launch) into a grow-only device buffer it keeps per device, so its first call on a device allocates.  om_debug_rope_gqa: rotary positions in place on the
- * q and k heads, position = row % L; inv_freq is a HOST array of 32 frequencies, cos / sin are multiplied by `scaling`. */
+ * q and k heads, position = row % L; inv_freq is a HOST array of 32 frequencies, cos / sin are multiplied by `scaling`.
+ * The _packed / _rows forms are the kernels of om_causal_encoder_forward_packed alone, over the layout om_debug_mask_extent +
+ * om_debug_pack_rows describe: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (L stays the pitch of mask; rows outside are
+ * neither read nor written), and the position of row t is row_map[t] % L (rows with row_map[t] < 0 are left as they are). */
 int om_debug_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads, int n_kv_heads,
                               float scale, void* stream);
 int om_debug_rope_gqa(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling, void* stream);
+int om_debug_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L, int n_heads,
+                                     int n_kv_heads, float scale, void* stream);
+int om_debug_rope_gqa_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling,
+                           const int* row_map, void* stream);
 /* kmax[b] = 1 + the last unmasked key of mask row b (L when it has none) */
 int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
 /* cu [B + 2], cls_rows [B], row_map [rows] of the packed layout (csrc/kernels.h omk_pack_rows) */
@@ -400,7 +407,17 @@ int om_encoder_forward_packed(const OmEncoderConfig* cfg, const OmEncoderWeights
  *   o_w    [H, H] o_proj, o_b or NULL;  ln1_g input_layernorm, ln2_g post_attention_layernorm (RMSNorm: no biases)
  *   ffn1_w [F, H] gate_proj, ffn1g_w [F, H] up_proj, ffn2_w [H, F] down_proj (no biases);  word_emb embed_tokens, final_ln_g norm.
  * Key k is visible from query q iff k <= q and attention_mask[b][k] != 0; positions are 0 .. L - 1 whatever the padding (HF's
- * arange).  L <= 1024.  out_hidden [B, L, H] in base.dtype or NULL; out_reps f32 [B, D].  No packed rows, no training entry.
+ * arange).  L <= 1024.  out_hidden [B, L, H] in base.dtype or NULL; out_reps f32 [B, D].  No training entry.
+ *
+ * om_causal_encoder_forward_packed: the same representations from PACKED rows, under the contract of om_encoder_forward_packed --
+ * each sequence's rows up to its last unmasked token, back to back; ids and mask keep their [B, L] layout; packed_rows is the caller's
+ * bound on the token count, a multiple of 256 in [512, B * L + 255]; a batch that holds more tokens returns NaN in every
+ * representation (checked on the device, nothing is read or written out of range).  The same launch sequence over packed_rows rows
+ * instead of B * L, in f32, f16 and bf16; a position is the token's COLUMN (HF's arange), so rotary phases survive packing; a
+ * sequence with leading pad tokens keeps them inside its extent, masked.  Representations only: a pooling, no out_hidden.
+ * om_causal_encoder_packed_supported: 1 when the packed entry takes (cfg, B, L, packed_rows), else 0 -- the host layer asks and falls
+ * back to om_causal_encoder_forward (0 also where B * L is at or below OM_OPT_GEMM_SKINNY_M: the padded entry's contractions take the
+ * few-rows kernels there).  Workspace: om_causal_encoder_workspace_bytes_packed.
  * ------------------------------------------------------------------------ */
 typedef struct OmCausalConfig {
   OmEncoderConfig base;
@@ -412,6 +429,11 @@ size_t om_causal_encoder_workspace_bytes(const OmCausalConfig* cfg, int64_t B, i
 int om_causal_encoder_forward(const OmCausalConfig* cfg, const OmEncoderWeights* w, const int64_t* input_ids,
                               const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps,
                               void* workspace, size_t workspace_bytes, void* stream);
+int om_causal_encoder_packed_supported(const OmCausalConfig* cfg, int64_t B, int64_t L, int64_t packed_rows);
+size_t om_causal_encoder_workspace_bytes_packed(const OmCausalConfig* cfg, int64_t B, int64_t L, int64_t packed_rows);
+int om_causal_encoder_forward_packed(const OmCausalConfig* cfg, const OmEncoderWeights* w, const int64_t* input_ids,
+                                     const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows, float* out_reps,
+                                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * One decoder position of a T5 encoder-decoder over the encoder's output (inference):

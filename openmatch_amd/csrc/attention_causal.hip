@@ -23,6 +23,10 @@
 //     float32: attention_causal32_kernel = attn_chunked_qreg with it.  Every query head fetches its group's K / V chunks itself
 //     (one workgroup per (sequence, query head, query block)); a form that serves a whole K / V group from one fetch has not been
 //     built or measured.
+//
+//   * Packed rows (om_causal_encoder_forward_packed): omk_attention_causal_packed runs the same two bodies with an AttnRows filled
+//     from cu -- sequence b is rows cu[b] .. cu[b + 1] - 1, the body's L is that row count, the mask keeps its [B, L] pitch -- and
+//     omk_rope_gqa with a row_map takes a row's position from row_map[t] % L (the column omk_pack_rows recorded) instead of row % L.
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -78,22 +82,12 @@ template <> struct RopeIO<f16_t> : RopeIO16<f16_t> {};
 
 // one thread: four consecutive pairs (i .. i + 3, i + 32 .. i + 35) of one q or k head of one row; the v heads are never touched.
 // q' = q cos + rotate_half(q) sin in f32 (HF: q.float() * cos + rotate_half(q.float()) * sin), rounded once; products and sum kept apart
-// (no fused multiply-add) as torch evaluates them.
+// (no fused multiply-add) as torch evaluates them.  p: this thread's first element; t: its position's first (cos, sin).
 template <typename T>
-__global__ __launch_bounds__(256) void rope_gqa_kernel(T* __restrict__ qkv, const float2* __restrict__ tab, int64_t M, int L, int rot_heads,
-                                                       int pitch) {
-  const int per_row = rot_heads * 8;                       // 8 threads per rotated head
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= M * per_row) return;
-  const int64_t row = idx / per_row;
-  const int j = (int)(idx % per_row);
-  const int seg = j / 8, i0 = (j % 8) * 4;                 // seg: head (q heads, then k heads); i0: first of four pairs
-  const int pos = (int)(row % L);
-  T* p = qkv + row * (int64_t)pitch + (int64_t)seg * 64 + i0;
+__device__ __forceinline__ void rope_rotate4(T* p, const float2* t) {
   float a[4], b[4];
   RopeIO<T>::load4(p, a);
   RopeIO<T>::load4(p + 32, b);
-  const float2* t = tab + (size_t)pos * 32 + i0;
   float ra[4], rb[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -105,15 +99,44 @@ __global__ __launch_bounds__(256) void rope_gqa_kernel(T* __restrict__ qkv, cons
   RopeIO<T>::store4(p + 32, rb);
 }
 
-// rows of the grouped projection [M, (heads + 2 kv_heads) * 64] (q heads | k heads | v heads) and of ctx [M, heads * 64] for sequence
-// b, query head h: it reads K / V head h / (heads / kv_heads) (HF repeat_kv)
 template <typename T>
-__device__ __forceinline__ AttnRows<T> causal_rows(const T* qkv, T* ctx, int64_t b, int L, int heads, int kv_heads, int h) {
+__global__ __launch_bounds__(256) void rope_gqa_kernel(T* __restrict__ qkv, const float2* __restrict__ tab, int64_t M, int L, int rot_heads,
+                                                       int pitch) {
+  const int per_row = rot_heads * 8;                       // 8 threads per rotated head
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * per_row) return;
+  const int64_t row = idx / per_row;
+  const int j = (int)(idx % per_row);
+  const int seg = j / 8, i0 = (j % 8) * 4;                 // seg: head (q heads, then k heads); i0: first of four pairs
+  const int pos = (int)(row % L);
+  rope_rotate4(qkv + row * (int64_t)pitch + (int64_t)seg * 64 + i0, tab + (size_t)pos * 32 + i0);
+}
+
+// packed rows: row t holds token row_map[t] = b * L + column, so its position is row_map[t] % L; row_map[t] < 0 is a tail row, left
+// as it is
+template <typename T>
+__global__ __launch_bounds__(256) void rope_gqa_rows_kernel(T* __restrict__ qkv, const float2* __restrict__ tab, int64_t M, int L, int rot_heads,
+                                                            int pitch, const int* __restrict__ row_map) {
+  const int per_row = rot_heads * 8;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * per_row) return;
+  const int64_t row = idx / per_row;
+  const int j = (int)(idx % per_row);
+  const int seg = j / 8, i0 = (j % 8) * 4;
+  const int tok = row_map[row];
+  if (tok < 0) return;
+  rope_rotate4(qkv + row * (int64_t)pitch + (int64_t)seg * 64 + i0, tab + (size_t)(tok % L) * 32 + i0);
+}
+
+// rows of the grouped projection [M, (heads + 2 kv_heads) * 64] (q heads | k heads | v heads) and of ctx [M, heads * 64] for the
+// sequence whose first row is row0 (b * L padded, cu[b] packed), query head h: it reads K / V head h / (heads / kv_heads) (HF repeat_kv)
+template <typename T>
+__device__ __forceinline__ AttnRows<T> causal_rows(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
   const int kvh = h / (heads / kv_heads);
   const int pitch = (heads + 2 * kv_heads) * 64;
-  const T* const row = qkv + b * L * pitch;
+  const T* const row = qkv + row0 * pitch;
   const T* const k = row + (heads + kvh) * 64;
-  return {row + h * 64, k, k + kv_heads * 64, pitch, ctx + b * L * (int64_t)(heads * 64) + h * 64, heads * 64};
+  return {row + h * 64, k, k + kv_heads * 64, pitch, ctx + row0 * (int64_t)(heads * 64) + h * 64, heads * 64};
 }
 
 template <typename T>
@@ -123,7 +146,7 @@ __global__ __launch_bounds__(256, 2) void attention_causal16_kernel(
   const int h = blockIdx.x % heads;
   const int64_t b = blockIdx.x / heads;
   const int kend = kmax ? __builtin_amdgcn_readfirstlane(kmax[b]) : L;
-  attn_chunked16<T, AttnCausal, false, false>(causal_rows(qkv, ctx, b, L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kend, blockIdx.y * 128, scale,
+  attn_chunked16<T, AttnCausal, false, false>(causal_rows(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kend, blockIdx.y * 128, scale,
                                               AttnFullArgs{});
 }
 
@@ -132,8 +155,39 @@ __global__ __launch_bounds__(256) void attention_causal32_kernel(
     const int* __restrict__ kmax) {
   const int h = blockIdx.x % heads;
   const int64_t b = blockIdx.x / heads;
-  attn_chunked_qreg<float, AttnCausal>(causal_rows(qkv, ctx, b, L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128,
+  attn_chunked_qreg<float, AttnCausal>(causal_rows(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128,
                                        scale, AttnFullArgs{});
+}
+
+// Packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 (omk_pack_rows), which is the body's L and its key extent; the mask row keeps
+// the padded pitch Lp, so leading pad tokens inside the extent stay masked.  The grid is the padded launch's, (heads * B,
+// ceil(Lp / 128)): a query block at or past the sequence's end -- every block of a sequence the row bound clamped to no rows -- leaves
+// before it touches LDS or memory, so no row outside [cu[b], cu[b + 1]) is read or written.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void attention_causal16_packed_kernel(
+    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
+    const int* __restrict__ cu) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int row0 = __builtin_amdgcn_readfirstlane(cu[b]);
+  const int Lb = __builtin_amdgcn_readfirstlane(cu[b + 1]) - row0;
+  const int qb = blockIdx.y * 128;
+  if (qb >= Lb) return;
+  attn_chunked16<T, AttnCausal, false, false>(causal_rows(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale,
+                                              AttnFullArgs{});
+}
+
+__global__ __launch_bounds__(256) void attention_causal32_packed_kernel(
+    const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
+    const int* __restrict__ cu) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int row0 = cu[b];
+  const int Lb = cu[b + 1] - row0;
+  const int qb = blockIdx.y * 128;
+  if (qb >= Lb) return;
+  attn_chunked_qreg<float, AttnCausal>(causal_rows(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale,
+                                       AttnFullArgs{});
 }
 
 }  // namespace
@@ -144,14 +198,20 @@ static int check_gqa(int heads, int kv_heads) {
 }
 
 // rot_heads rotated heads at the start of each row of `pitch` elements
-static int rope_launch(int dtype, void* qkv, int64_t M, int L, int rot_heads, int pitch, const float* inv_freq_host, float scaling, hipStream_t s) {
+template <typename T>
+static void rope_launch_as(T* qkv, const float2* tab, int64_t M, int L, int rot_heads, int pitch, const int* row_map, hipStream_t s) {
+  const unsigned grid = (unsigned)((M * rot_heads * 8 + 255) / 256);
+  if (row_map) hipLaunchKernelGGL(rope_gqa_rows_kernel<T>, dim3(grid), dim3(256), 0, s, qkv, tab, M, L, rot_heads, pitch, row_map);
+  else hipLaunchKernelGGL(rope_gqa_kernel<T>, dim3(grid), dim3(256), 0, s, qkv, tab, M, L, rot_heads, pitch);
+}
+
+static int rope_launch(int dtype, void* qkv, int64_t M, int L, int rot_heads, int pitch, const float* inv_freq_host, float scaling, hipStream_t s,
+                       const int* row_map = nullptr) {
   const float2* tab = nullptr;
   if (rope_table_device(inv_freq_host, scaling, &tab)) return 1;
-  const int64_t n = M * rot_heads * 8;
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  if (dtype == OM_BF16) hipLaunchKernelGGL(rope_gqa_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)qkv, tab, M, L, rot_heads, pitch);
-  else if (dtype == OM_F16) hipLaunchKernelGGL(rope_gqa_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qkv, tab, M, L, rot_heads, pitch);
-  else hipLaunchKernelGGL(rope_gqa_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qkv, tab, M, L, rot_heads, pitch);
+  if (dtype == OM_BF16) rope_launch_as((bf16_t*)qkv, tab, M, L, rot_heads, pitch, row_map, s);
+  else if (dtype == OM_F16) rope_launch_as((f16_t*)qkv, tab, M, L, rot_heads, pitch, row_map, s);
+  else rope_launch_as((float*)qkv, tab, M, L, rot_heads, pitch, row_map, s);
   OM_LAUNCH_CHECK();
   return 0;
 }
@@ -169,12 +229,13 @@ int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStre
   return rope_launch(dtype, qkv, M, L, 2 * H / 64, 3 * H, inv_freq, 1.0f, s);
 }
 
-int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s) {
+int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s,
+                 const int* row_map) {
   if (M <= 0) return 0;
   if (L < 1 || L > kRopeMaxPos) OM_FAIL("rotary positions: sequence length must be in [1,1024]");
   if (check_gqa(heads, kv_heads)) return 1;
   if (!inv_freq_host) OM_FAIL("rotary positions: a frequency table of 32 values");
-  return rope_launch(dtype, qkv, M, L, heads + kv_heads, (heads + 2 * kv_heads) * 64, inv_freq_host, scaling, s);
+  return rope_launch(dtype, qkv, M, L, heads + kv_heads, (heads + 2 * kv_heads) * 64, inv_freq_host, scaling, s, row_map);
 }
 
 // its own launch: the planner of the bidirectional kernels (attn_plan.h) and omk_attention know nothing of it
@@ -195,6 +256,31 @@ int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* m
       hipLaunchKernelGGL(attention_causal16_kernel<f16_t>, grid, dim3(256), lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
     else
       hipLaunchKernelGGL(attention_causal16_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
+  }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// the same two bodies over packed rows: cu [B + 1] from omk_pack_rows (its offsets are clamped to the row bound, so a bound that is too
+// small shortens or empties the last sequences and nothing leaves the buffers); L is the pitch of the mask
+int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                                const int* cu, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
+  if (check_gqa(heads, kv_heads)) return 1;
+  if (!cu) OM_FAIL("causal attention over packed rows: the sequence offsets cu");
+  if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
+  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
+  if (dtype == OM_F32) {
+    const int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
+    if (attn_lds_once<attention_causal32_packed_kernel>(lds)) return 1;
+    hipLaunchKernelGGL(attention_causal32_packed_kernel, grid, dim3(256), lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, cu);
+  } else {
+    const int lds = 2 * 128 * 128 + 128 * 4;
+    if (dtype == OM_F16)
+      hipLaunchKernelGGL(attention_causal16_packed_kernel<f16_t>, grid, dim3(256), lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
+    else
+      hipLaunchKernelGGL(attention_causal16_packed_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
   }
   OM_LAUNCH_CHECK();
   return 0;
@@ -238,4 +324,19 @@ extern "C" int om_debug_rope_gqa(int dtype, void* qkv, int64_t M, int L, int n_h
   if (!qkv || !inv_freq) OM_FAIL("null argument");
   if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
   return omk_rope_gqa(dtype, qkv, M, L, n_heads, n_kv_heads, inv_freq, scaling, (hipStream_t)stream);
+}
+
+// the packed kernels alone: cu [B + 2] and row_map [rows] as om_debug_pack_rows wrote them
+extern "C" int om_debug_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                                int n_heads, int n_kv_heads, float scale, void* stream) {
+  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("causal attention: dtype must be OM_F32, OM_BF16 or OM_F16");
+  return omk_attention_causal_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, cu, (hipStream_t)stream);
+}
+
+extern "C" int om_debug_rope_gqa_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling,
+                                      const int* row_map, void* stream) {
+  if (!qkv || !inv_freq || !row_map) OM_FAIL("null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
+  return omk_rope_gqa(dtype, qkv, rows, L, n_heads, n_kv_heads, inv_freq, scaling, (hipStream_t)stream, row_map);
 }

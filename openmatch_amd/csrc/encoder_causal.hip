@@ -21,6 +21,12 @@
 //
 // Activation buffers ([M = B*L tokens] x width): x [M, H] f32 residual stream; in the compute dtype y normed input,
 // qkv [M, (heads + 2 kv) * 64], ctx [M, H], ff / ff2 [M, F].
+//
+// om_causal_encoder_forward_packed is the SAME launch sequence (causal_forward_impl below, one layer loop for both entries) with
+// M = packed_rows: each sequence's rows up to its last unmasked token, back to back (omk_pack_rows).  The embedding gathers through
+// row_map, the rotary pass reads its position from it, attention walks cu, pooling reads cu / cls_rows / the last-token rows.  Rows
+// past the token count are embedded as zeros and stay finite (a zero row normalises to zero; its ctx rows are cleared once, since no
+// attention workgroup writes them); nothing pools from them.
 #include <math.h>
 
 #include <algorithm>
@@ -84,19 +90,27 @@ __global__ void last_rows_kernel(const int* __restrict__ kmax, int64_t B, int L,
   if (b < B) rows[b] = (int)(b * L + kmax[b] - 1);
 }
 
+// packed rows: the row of sequence b's last unmasked token is cu[b] + kmax[b] - 1, clamped into the buffer as cls_rows is (a bound that
+// was too small: the representations are poisoned afterwards)
+__global__ void last_rows_packed_kernel(const int* __restrict__ kmax, const int* __restrict__ cu, int64_t B, int rows_cap, int* __restrict__ rows) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) rows[b] = min(cu[b] + kmax[b] - 1, rows_cap - 1);
+}
+
 struct CausalWs {
   char *x, *y, *qkv, *ctx, *ff, *ff2;
   float *pooled, *headout, *final32;
   int *kmax, *last_rows;
+  int *cu, *cls_rows, *row_map;   // packed rows: sequence offsets [B + 2], first row of each sequence [B], token of each row [packed_rows]
   int64_t Mp;       // row count the contractions run on: M rounded up to whole 256-row tiles for large 16-bit batches (as encoder.hip)
   size_t total;
 };
 
-CausalWs carve(const OmCausalConfig* cc, int64_t B, int64_t L, char* base) {
+CausalWs carve(const OmCausalConfig* cc, int64_t B, int64_t L, char* base, int64_t packed_rows = 0) {
   const OmEncoderConfig* c = &cc->base;
   const bool half = c->dtype == OM_BF16 || c->dtype == OM_F16;
   const size_t es = half ? 2 : 4;
-  const size_t Mreal = (size_t)B * L, H = c->hidden, F = c->ffn, P = (size_t)(c->n_heads + 2 * cc->n_kv_heads) * 64;
+  const size_t Mreal = packed_rows > 0 ? (size_t)packed_rows : (size_t)B * L, H = c->hidden, F = c->ffn, P = (size_t)(c->n_heads + 2 * cc->n_kv_heads) * 64;
   const size_t M = (half && Mreal >= 512) ? (Mreal + 255) / 256 * 256 : Mreal;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
@@ -112,6 +126,9 @@ CausalWs carve(const OmCausalConfig* cc, int64_t B, int64_t L, char* base) {
   w.kmax = (int*)take((size_t)B * 4);
   w.last_rows = (int*)take((size_t)B * 4);
   w.final32 = (float*)take(c->pooling == OM_POOL_MEAN ? Mreal * H * 4 : 0);      // mean pooling reads every row of the f32 final norm
+  w.cu = (int*)take(packed_rows > 0 ? (size_t)(B + 2) * 4 : 0);
+  w.cls_rows = (int*)take(packed_rows > 0 ? (size_t)B * 4 : 0);
+  w.row_map = (int*)take(packed_rows > 0 ? (size_t)packed_rows * 4 : 0);
   w.Mp = (int64_t)M;
   w.total = off;
   return w;
@@ -142,16 +159,39 @@ extern "C" size_t om_causal_encoder_workspace_bytes(const OmCausalConfig* cfg, i
   return carve(cfg, B, L, nullptr).total;
 }
 
-extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids,
-                                         const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
+// Whether om_causal_encoder_forward_packed takes (cfg, B, L, packed_rows): the stack is unfused, so every compute format and none of
+// the fused-LayerNorm switches enter.  No region is excluded on grounds of speed: the packed entry's throughput has not been measured
+// yet (DESIGN.md section 8 says what is to be done when it is).
+extern "C" int om_causal_encoder_packed_supported(const OmCausalConfig* cc, int64_t B, int64_t L, int64_t packed_rows) {
+  if (!cc || B <= 0 || L <= 0 || L > 1024 || packed_rows <= 0) return 0;
+  if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) return 0;
+  // few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so a batch
+  // whose PADDED form is that small is sent back (as om_encoder_packed_supported)
+  if (B * L <= (int64_t)om_option(OM_OPT_GEMM_SKINNY_M)) return 0;
+  return check_cfg(cc) ? 0 : 1;
+}
+
+extern "C" size_t om_causal_encoder_workspace_bytes_packed(const OmCausalConfig* cfg, int64_t B, int64_t L, int64_t packed_rows) {
+  if (!cfg || B <= 0 || L <= 0 || packed_rows <= 0 || cfg->n_kv_heads < 1 || cfg->base.n_heads < 1) return 0;
+  return carve(cfg, B, L, nullptr, packed_rows).total;
+}
+
+// both entries: packed_rows == 0 is the padded layout [B * L rows], > 0 the packed one
+static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids, const int64_t* attention_mask,
+                               int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace, size_t workspace_bytes, void* stream,
+                               int64_t packed_rows) {
   if (!cc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
   if (check_cfg(cc)) return 1;
   const OmEncoderConfig* c = &cc->base;
   if (B <= 0) return 0;
   if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
+  const bool packed = packed_rows > 0;
+  if (packed) {
+    if (c->pooling == OM_POOL_NONE || out_hidden) OM_FAIL("packed rows: representations only (a pooling, no out_hidden)");
+    if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) OM_FAIL("packed_rows: a multiple of 256 in [512, B * L + 255]");
+  }
   if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  CausalWs ws = carve(cc, B, L, (char*)workspace);
+  CausalWs ws = carve(cc, B, L, (char*)workspace, packed_rows);
   if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
   if (c->pooling != OM_POOL_NONE && !out_reps) OM_FAIL("out_reps required when pooling is set");
   const OmLayerWeights* Ls = w->layers_host;
@@ -160,7 +200,8 @@ extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncod
   hipStream_t s = (hipStream_t)stream;
   const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nkv = cc->n_kv_heads;
   const int P = (nh + 2 * nkv) * 64;
-  const int64_t M = B * L, Mg = ws.Mp;
+  const int64_t M = packed ? packed_rows : B * L, Mg = ws.Mp;
+  const int* const row_map = packed ? ws.row_map : nullptr;
 
 #define GEMM(A_, lda_, W_, ldw_, C_, ldc_, N_, K_, bias_, res_, ldr_)                                      \
   do {                                                                                                     \
@@ -176,7 +217,11 @@ extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncod
 #define RUN(expr) do { if (expr) return 1; } while (0)
 
   RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-  RUN(omk_embed(OM_F32, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s));
+  if (packed) {
+    RUN(omk_pack_rows(ws.kmax, B, (int)L, packed_rows, ws.cu, ws.cls_rows, ws.row_map, s));
+    OM_HIP(hipMemsetAsync(ws.ctx, 0, (size_t)M * H * (dt == OM_F32 ? 4 : 2), s));      // the tail rows: no attention workgroup writes them
+  }
+  RUN(omk_embed(OM_F32, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
   const float scale = 1.0f / sqrtf((float)c->head_dim);
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
@@ -184,8 +229,9 @@ extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncod
       OM_FAIL("Llama / Qwen2 layers need qkv_w, o_w, ln1_g, ln2_g, ffn1_w (gate_proj), ffn1g_w (up_proj) and ffn2_w (down_proj)");
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));   // input_layernorm
     GEMM(ws.y, H, lw.qkv_w, H, ws.qkv, P, P, H, lw.qkv_b, nullptr, 0);
-    RUN(omk_rope_gqa(dt, ws.qkv, M, (int)L, nh, nkv, cc->inv_freq, cc->rope_attention_scaling, s));
-    RUN(omk_attention_causal(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
+    RUN(omk_rope_gqa(dt, ws.qkv, M, (int)L, nh, nkv, cc->inv_freq, cc->rope_attention_scaling, s, row_map));
+    if (packed) RUN(omk_attention_causal_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
+    else RUN(omk_attention_causal(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
     GEMM_ACC(ws.ctx, H, lw.o_w, H, H, H, lw.o_b);                                                          // x += o_proj(ctx)
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // post_attention_layernorm
     GEMM(ws.y, H, lw.ffn1_w, H, ws.ff2, F, F, H, nullptr, nullptr, 0);                                     // gate_proj
@@ -202,14 +248,17 @@ extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncod
     const bool head = c->head_in > 0 && w->head_w;
     float* pooled = head ? ws.pooled : out_reps;
     if (c->pooling == OM_POOL_FIRST) {
-      RUN(omk_layernorm_f32out(OM_F32, xf, L * H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s));
+      if (packed) RUN(omk_layernorm_f32out(OM_F32, xf, H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s, nullptr, ws.cls_rows));
+      else RUN(omk_layernorm_f32out(OM_F32, xf, L * H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s));
     } else if (c->pooling == OM_POOL_LAST) {
-      hipLaunchKernelGGL(last_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, ws.kmax, B, (int)L, ws.last_rows);
+      const dim3 grid((unsigned)((B + 255) / 256));
+      if (packed) hipLaunchKernelGGL(last_rows_packed_kernel, grid, dim3(256), 0, s, ws.kmax, ws.cu, B, (int)packed_rows, ws.last_rows);
+      else hipLaunchKernelGGL(last_rows_kernel, grid, dim3(256), 0, s, ws.kmax, B, (int)L, ws.last_rows);
       OM_LAUNCH_CHECK();
       RUN(omk_layernorm_f32out(OM_F32, xf, H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s, nullptr, ws.last_rows));
     } else {
       RUN(omk_layernorm_f32out(OM_F32, xf, H, ws.final32, H, fg, nullptr, M, H, c->ln_eps, 1, s));
-      RUN(omk_pool(OM_F32, ws.final32, attention_mask, pooled, B, (int)L, H, OM_POOL_MEAN, s));
+      RUN(omk_pool(OM_F32, ws.final32, attention_mask, pooled, B, (int)L, H, OM_POOL_MEAN, s, packed ? ws.cu : nullptr));
     }
     int D = H;
     if (head) {
@@ -218,9 +267,23 @@ extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncod
         return 1;
     }
     if (c->normalize) RUN(omk_l2norm(out_reps, out_reps, B, D, s));
+    if (packed) RUN(omk_pack_overflow_poison(ws.cu, B, packed_rows, out_reps, B * (int64_t)D, s));      // a bound below the token count: NaN, never a truncated batch
   }
 #undef GEMM_ACC
 #undef GEMM
 #undef RUN
   return 0;
+}
+
+extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids,
+                                         const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return causal_forward_impl(cc, w, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace, workspace_bytes, stream, 0);
+}
+
+extern "C" int om_causal_encoder_forward_packed(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids,
+                                                const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows, float* out_reps,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (packed_rows <= 0) OM_FAIL("packed_rows must be positive");
+  return causal_forward_impl(cc, w, input_ids, attention_mask, B, L, nullptr, out_reps, workspace, workspace_bytes, stream, packed_rows);
 }

@@ -50,9 +50,13 @@ int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mas
 // (q heads | k heads | v heads), ctx [M, heads * 64].  Rotary positions on its q and k heads in place from the host's 32 frequencies
 // (cos, sin times `scaling`), and attention where key k is visible from query q iff k <= q and k is unmasked; query head h reads K / V
 // head h / (heads / kv_heads).  Its own launch: the planner of the bidirectional kernels (attn_plan.h) knows nothing of it.
-int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s);
+int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s,
+                 const int* row_map = nullptr /* packed rows: the position of row t is row_map[t] % L, rows with row_map[t] < 0 are skipped */);
 int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
                          const int* kmax, hipStream_t s);
+// packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (omk_pack_rows), L stays the pitch of the mask
+int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                                const int* cu, hipStream_t s);
 // packed rows (om_encoder_forward_packed): cu[0..B] = offsets of the sequences (kmax[b] rows each) clamped to `rows`, cu[B + 1] = the
 // unclamped token count; cls_rows[b] = min(cu[b], rows - 1); row_map[t] = b * L + position of packed row t, -1 for the pad rows
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);

@@ -647,8 +647,8 @@ def packed_rows_apply(cfg, B, L, rows, want_hidden, pooling, gated=False):
 def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, packed_rows=None):
     """(hidden [B,L,H], reps [B,D] f32) through om_encoder_forward.  `items` holds
     input_ids / attention_mask / optional token_type_ids as int64 device tensors.
-    packed_rows (with want_hidden=False): run om_encoder_forward_packed over that many rows (packed_rows_bound of the
-    mask, computed where the mask still lives on the host) instead of B * L padded ones."""
+    packed_rows (with want_hidden=False): run om_encoder_forward_packed (Llama / Qwen2: om_causal_encoder_forward_packed) over
+    that many rows (packed_rows_bound of the mask, computed where the mask still lives on the host) instead of B * L padded ones."""
     check_pooling(model, pooling)
     ids = items["input_ids"]
     mask = items["attention_mask"]
@@ -665,7 +665,7 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     code = inference_code(model, code, ids.shape[1])
     pk = packed_weights(model, head, code, device)
     if _arch_of(model) == "causal":
-        return _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden)
+        return _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
     _ensure_folded(pk, device)
     cfg = N.OmEncoderConfig(pooling=_POOL[pooling], normalize=int(bool(normalize)), **pk.cfg)
     B, L = ids.shape
@@ -698,20 +698,40 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     return hidden, reps
 
 
-def _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden):
-    """hip_encode for a packed Llama / Qwen2 through om_causal_encoder_forward (padded rows only: no packed-rows entry)."""
+def causal_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
+    """Whether om_causal_encoder_forward_packed takes this call (cfg: an OmCausalConfig) and pays: representations only, at least one
+    256-row tile saved -- a left-padded batch's bound is B * L, so it stays on the padded entry -- and the library's own view
+    (include/openmatch_hip.h om_causal_encoder_packed_supported).  OM_ENCODER_PACKED=0 keeps every batch on the padded entry."""
+    if os.environ.get("OM_ENCODER_PACKED", "1") == "0" or want_hidden or pooling is None:
+        return False
+    if not (rows % 256 == 0 and 512 <= rows <= (B * L) // 256 * 256 - 256):
+        return False
+    return bool(N.lib().om_causal_encoder_packed_supported(C.byref(cfg), B, L, rows))
+
+
+def _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
+    """hip_encode for a packed Llama / Qwen2: om_causal_encoder_forward_packed over `packed_rows` rows where causal_packed_rows_apply
+    admits the call, om_causal_encoder_forward over the B * L padded rows otherwise."""
     device = ids.device
     cfg = causal_config(pk.cfg, _POOL[pooling], normalize)
     B, L = ids.shape
     H = cfg.base.hidden
     D = cfg.base.head_out if cfg.base.head_in > 0 else H
     lib = N.lib()
-    LAST_CALL.update(rows=B * L, packed=False)
+    if packed_rows and not causal_packed_rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
+        packed_rows = None
+    LAST_CALL.update(rows=int(packed_rows) if packed_rows else B * L, packed=bool(packed_rows))
     with torch.cuda.device(device):
+        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
+        if packed_rows:
+            nbytes = lib.om_causal_encoder_workspace_bytes_packed(C.byref(cfg), B, L, int(packed_rows))
+            ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
+            N.check(lib.om_causal_encoder_forward_packed(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask), B, L, int(packed_rows),
+                                                         N.ptr(reps), C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+            return None, reps
         nbytes = lib.om_causal_encoder_workspace_bytes(C.byref(cfg), B, L)
         ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
         hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
-        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
         N.check(lib.om_causal_encoder_forward(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
                                               C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
     return hidden, reps

@@ -126,6 +126,8 @@ _SIGNATURES = {
     "om_debug_rope": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
     "om_debug_attention_causal": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
     "om_debug_rope_gqa": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, C.POINTER(c_float), c_float, c_void_p]),
+    "om_debug_attention_causal_packed": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
+    "om_debug_rope_gqa_rows": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, C.POINTER(c_float), c_float, c_void_p, c_void_p]),
     "om_debug_mask_extent": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_debug_attention_last": (c_int, []),
@@ -154,6 +156,10 @@ _SIGNATURES = {
     "om_causal_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmCausalConfig), c_int64, c_int64]),
     "om_causal_encoder_forward": (c_int, [C.POINTER(OmCausalConfig), C.POINTER(OmEncoderWeights), c_void_p, c_void_p, c_int64, c_int64,
                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_causal_encoder_packed_supported": (c_int, [C.POINTER(OmCausalConfig), c_int64, c_int64, c_int64]),
+    "om_causal_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmCausalConfig), c_int64, c_int64, c_int64]),
+    "om_causal_encoder_forward_packed": (c_int, [C.POINTER(OmCausalConfig), C.POINTER(OmEncoderWeights), c_void_p, c_void_p, c_int64, c_int64,
+                                                 c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_encoder_packed_supported": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int64, c_int64, c_int64]),
     "om_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64, c_int64]),
     "om_encoder_forward_packed": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p,

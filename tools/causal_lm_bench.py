@@ -12,6 +12,11 @@ the per-layer time of the kernels the stack adds; prints one JSON line:
       rope        om_debug_rope_gqa, in place
 
     python tools/causal_lm_bench.py [--tokens 65536] [--iters 20] [--kernels-only] [--encode-only]
+
+--ragged: the encode batches hold ragged right-padded rows instead of full-length ones (lengths ~ U{L/8 .. L}, as tools/train_bench.py
+draws them) and each step is timed on its own; the result carries the median, fastest and slowest of --iters steps, the rows the
+contractions ran on and B * L.  --packed (with --ragged): the batch also carries the host-side token counts, so the encoder takes
+om_causal_encoder_forward_packed; without it the same batch runs the padded entry.  --dtype, --shapes and --lengths narrow a run.
 """
 import argparse, ctypes as C, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -46,7 +51,19 @@ def _events_us(fn, iters):
     return a.elapsed_time(b) * 1e3 / iters
 
 
-def _model(s):
+def _steps_ms(fn, iters):
+    for _ in range(3):
+        fn()
+    out = []
+    for _ in range(iters):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return sorted(out)
+
+
+def _model(s, dtype="bfloat16"):
     from transformers import LlamaConfig, LlamaModel, Qwen2Config, Qwen2Model
     from openmatch.modeling import DRModelForInference
     torch.manual_seed(0)
@@ -56,12 +73,23 @@ def _model(s):
     with torch.device(DEV):              # (initialised on the device: 1.2 G parameters take a while on the host)
         lm = mcls(cfg).eval()
     return DRModelForInference(lm_q=lm, lm_p=lm, pooling="last", normalize=True,
-                               model_args=NS(encoder_only=False, dtype="bfloat16")).to(DEV).eval()
+                               model_args=NS(encoder_only=False, dtype=dtype)).to(DEV).eval()
 
 
 def _batch(B, L, vocab):
     ids = torch.randint(3, vocab, (B, L), generator=torch.Generator().manual_seed(1)).to(DEV)
     return {"input_ids": ids, "attention_mask": torch.ones_like(ids)}
+
+
+def _ragged_batch(B, L, vocab, packed):
+    from openmatch_amd.encoder import TOKEN_ROWS_KEY, token_rows_of
+    ids = torch.randint(3, vocab, (B, L), generator=torch.Generator().manual_seed(1))
+    lens = torch.randint(max(2, L // 8), L + 1, (B,), generator=torch.Generator().manual_seed(3))
+    mask = (torch.arange(L)[None, :] < lens[:, None]).long()
+    x = {"input_ids": ids.to(DEV), "attention_mask": mask.to(DEV)}
+    if packed:                           # the token counts a caller notes while the collator's batch is still on the host
+        x[TOKEN_ROWS_KEY] = token_rows_of(mask)
+    return x, int(lens.sum())
 
 
 def _kernels(s, B, L, iters):
@@ -95,18 +123,37 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--encode-only", action="store_true")
+    ap.add_argument("--ragged", action="store_true", help="ragged right-padded encode batches, each step timed on its own")
+    ap.add_argument("--packed", action="store_true", help="with --ragged: hand the host-side token counts over (the packed-rows entry)")
+    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16", "float32"])
+    ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated subset of " + ", ".join(SHAPES))
+    ap.add_argument("--lengths", default="128,512", help="comma-separated encode lengths")
     a = ap.parse_args()
-    out = {"dtype": "bfloat16", "tokens_per_batch": a.tokens}
+    if a.packed and not a.ragged:
+        ap.error("--packed goes with --ragged")
+    out = {"dtype": a.dtype, "tokens_per_batch": a.tokens}
+    if a.ragged:
+        out.update(ragged=True, packed=bool(a.packed))
     with torch.no_grad():
-        for name, s in SHAPES.items():
+        for name in a.shapes.split(","):
+            s = SHAPES[name]
             r = {}
-            if not a.encode_only:
+            if not a.encode_only and not a.ragged:
                 for L in (128, 512, 1024):
                     r[f"kernel_us_per_layer_{L}"] = _kernels(s, a.tokens // L, L, a.iters)
             if not a.kernels_only:
-                m = _model(s)
-                for L in (128, 512):
+                from openmatch_amd import encoder as E
+                m = _model(s, a.dtype)
+                for L in (int(v) for v in a.lengths.split(",")):
                     B = a.tokens // L
+                    if a.ragged:
+                        x, tokens = _ragged_batch(B, L, s["vocab"], a.packed)
+                        ms = _steps_ms(lambda: m(passage=x), a.iters)
+                        med = ms[len(ms) // 2] if len(ms) % 2 else (ms[len(ms) // 2 - 1] + ms[len(ms) // 2]) / 2
+                        r[f"encode_{L}"] = {"batch": B, "tokens": tokens, "padded_rows": B * L, "rows": E.LAST_CALL["rows"],
+                                            "packed_entry": E.LAST_CALL["packed"], "steps": len(ms), "ms_median": round(med, 2),
+                                            "ms_min": round(ms[0], 2), "ms_max": round(ms[-1], 2), "passages_per_s": round(B / med * 1e3, 1)}
+                        continue
                     x = _batch(B, L, s["vocab"])
                     t = _timed(lambda: m(passage=x), max(2, a.iters // 4))
                     r[f"encode_{L}"] = {"batch": B, "ms": round(t * 1e3, 2), "passages_per_s": round(B / t, 1)}
