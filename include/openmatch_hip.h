@@ -239,6 +239,21 @@ int om_debug_attention_plan(int dtype, int64_t B, int L, int H, int heads, int h
 #define OM_ATTN_BWD_FAMILY_D32 4      /* attention_d32_bwd_kernel: 32-wide heads, up to 256 tokens                               */
 int om_debug_attention_bwd_last(void);
 int om_debug_attention_bwd_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, int has_drel, int has_cu, int packed);
+/* host only (no GPU needed): which layer loop om_encoder_forward (packed_rows == 0) or om_encoder_forward_packed would run for this
+ * call at the current switches (csrc/encoder_plan.h encoder_plan; DESIGN.md 4d lists the rules).  gated_ffn, has_rel_bias: what the
+ * forward reads from the weights (layers_host[0].ffn1g_w, rel_bias); a type_emb table is assumed where type_vocab > 0.  Returns
+ * path | few_rows << 8 | two << 9 | lo8 << 10 (few_rows: the contractions run on the few-rows kernel; two / lo8: the fused BERT path's
+ * second residual plane, and that plane in eight bits), 0 for an empty batch, -1 for a refusal with its reason in om_last_error. */
+#define OM_ENC_PATH_BERT_FUSED 1       /* LayerNorm fused across the contractions (16-bit, >= 512 rows, widths of 256)          */
+#define OM_ENC_PATH_BERT_PENDING_LN 2  /* few rows (<= OM_OPT_FEW_ROWS_LN_FUSE), f32 residual stream, LayerNorms inside the contractions */
+#define OM_ENC_PATH_BERT_FEW32 3       /* few rows (<= OM_OPT_GEMM_SKINNY_M), f32 residual stream, LayerNorms as kernels          */
+#define OM_ENC_PATH_BERT_PLAIN 4       /* one normalisation kernel per site: float32, and every other 16-bit shape                 */
+#define OM_ENC_PATH_MODERNBERT 5
+#define OM_ENC_PATH_T5_FUSED 6         /* RMSNorm fused across the contractions                                                    */
+#define OM_ENC_PATH_T5_PLAIN 7         /* one normalisation kernel per site (float32, few rows, gated feed-forwards)               */
+struct OmEncoderConfig;
+int om_debug_encoder_plan(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
+                          int want_hidden);
 /* host only: 1 if attention-probability dropout keeps (b, h, q, key) at rate p under `seed`; Lm is the mask's row pitch */
 int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, int q, int key, float p);
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly

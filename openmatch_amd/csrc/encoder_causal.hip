@@ -245,8 +245,7 @@ static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights*
   const float* xf = (const float*)ws.x;
   if (out_hidden) RUN(omk_layernorm_from_f32(dt, xf, H, out_hidden, H, fg, nullptr, M, H, c->ln_eps, 1, s));
   if (c->pooling != OM_POOL_NONE) {
-    const bool head = c->head_in > 0 && w->head_w;
-    float* pooled = head ? ws.pooled : out_reps;
+    float* pooled = c->head_in > 0 && w->head_w ? ws.pooled : out_reps;
     if (c->pooling == OM_POOL_FIRST) {
       if (packed) RUN(omk_layernorm_f32out(OM_F32, xf, H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s, nullptr, ws.cls_rows));
       else RUN(omk_layernorm_f32out(OM_F32, xf, L * H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s));
@@ -260,14 +259,7 @@ static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights*
       RUN(omk_layernorm_f32out(OM_F32, xf, H, ws.final32, H, fg, nullptr, M, H, c->ln_eps, 1, s));
       RUN(omk_pool(OM_F32, ws.final32, attention_mask, pooled, B, (int)L, H, OM_POOL_MEAN, s, packed ? ws.cu : nullptr));
     }
-    int D = H;
-    if (head) {
-      D = c->head_out;
-      if (om_gemm_nt(OM_F32, pooled, H, w->head_w, c->head_in, OM_F32, out_reps, D, B, D, c->head_in, nullptr, nullptr, 0, OM_ACT_NONE, s))
-        return 1;
-    }
-    if (c->normalize) RUN(omk_l2norm(out_reps, out_reps, B, D, s));
-    if (packed) RUN(omk_pack_overflow_poison(ws.cu, B, packed_rows, out_reps, B * (int64_t)D, s));      // a bound below the token count: NaN, never a truncated batch
+    RUN(omk_pooled_tail(c, w, pooled, out_reps, B, packed ? ws.cu : nullptr, packed_rows, s));
   }
 #undef GEMM_ACC
 #undef GEMM

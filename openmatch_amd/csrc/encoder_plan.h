@@ -1,0 +1,179 @@
+// Which layer loop an encoder forward runs: encoder_plan() maps (configuration, batch shape, what the caller wants back, which optional
+// weights are present, switches) to an EncPlan and does nothing else -- no launch, no HIP call, no global written, no pointer
+// dereferenced but the configuration's.  encoder_forward_impl (encoder.hip) carves its workspace by the plan and runs the loop it names;
+// om_encoder_packed_supported asks it; om_debug_encoder_plan returns it alone, so the table is testable on a machine without a GPU.
+// DESIGN.md 4d lists the rules in the order they are tested here.
+#pragma once
+#include <algorithm>
+
+#include "kernels.h"
+
+bool omk_gemm_skinny_ok(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep, int max_m);      // gemm_skinny.hip
+
+struct EncSwitches {
+  int fused_ln;       // OM_OPT_ENCODER_FUSED_LN: 0 = one normalisation kernel per site (A/B)
+  int two_plane;      // OM_OPT_ENCODER_TWO_PLANE: bit 0 bfloat16, bit 1 float16: the second plane of the residual stream; bit 2: float16's in eight bits
+  int pingpong;       // OM_OPT_ENCODER_PINGPONG: the fused path's kernels alternate their walk over the token rows
+  int skinny_m;       // OM_OPT_GEMM_SKINNY_M: most rows of the few-rows paths
+  int few_ln_fuse;    // OM_OPT_FEW_ROWS_LN_FUSE: most rows of the pending-LayerNorm path
+  int attention_fast; // OM_OPT_ATTENTION_FAST: read by om_encoder_packed_supported only (attn_plan.h decides the attention kernel itself)
+};
+
+// every switch the planner reads, read once per call (omk_gemm_ln_fusable reads OM_OPT_GEMM_VARIANT and om_debug_gemm_gen itself)
+static EncSwitches encoder_switches() {
+  return EncSwitches{om_option(OM_OPT_ENCODER_FUSED_LN), om_option(OM_OPT_ENCODER_TWO_PLANE), om_option(OM_OPT_ENCODER_PINGPONG),
+                     om_option(OM_OPT_GEMM_SKINNY_M), om_option(OM_OPT_FEW_ROWS_LN_FUSE), om_option(OM_OPT_ATTENTION_FAST)};
+}
+
+struct EncPlanIn {
+  const OmEncoderConfig* c;
+  int64_t B, L, packed_rows;      // packed_rows > 0: om_encoder_forward_packed
+  bool want_hidden;               // out_hidden is given
+  bool gated_ffn, has_rel_bias, has_type_emb;      // layers_host[0].ffn1g_w, rel_bias, type_emb are given
+};
+
+// What the planner decided.  path: OM_ENC_PATH_*; 0: run nothing -- an empty batch, or a refusal with its reason in `error` (the one
+// refusal that knows its path, "packed rows need the fused 16-bit path", keeps it for the OM_OPT_ENCODER_DEBUG line).
+struct EncPlan {
+  int path;
+  const char* error;
+  int64_t M;          // token rows: packed_rows, or B * L
+  int64_t Mp;         // M in whole 256-row tiles for 16-bit batches of >= 512 rows (the buffers are that tall)
+  int64_t Mg;         // rows of the contractions: M on the few-rows kernels, else Mp
+  bool few_rows;      // the contractions run on the weight-streaming kernel (gemm_skinny.hip)
+  bool two;           // fused BERT path: the residual stream has its second plane
+  int lo8;            //   ... in eight bits (float16)
+  bool pingpong;      // fused BERT path: alternate walk directions
+  bool rel_bias;      // a relative-position bias is expanded and handed to every attention launch
+  bool alloc_few32;   // carve's condition for r32a / r32b / y32: WIDER than path == BERT_FEW32 | BERT_PENDING_LN (follow-up)
+};
+
+// rule 1: the configuration alone (the texts of the former check_cfg)
+static const char* encoder_cfg_error(const OmEncoderConfig* c) {
+  if (c->dtype != OM_F32 && c->dtype != OM_BF16 && c->dtype != OM_F16) return "dtype must be OM_F32, OM_BF16 or OM_F16";
+  // float16 (the reference's --fp16 = torch.cuda.amp float16, retriever/dense_retriever.py:76): BERT-family erf-GELU encoders, and
+  // (round 5) T5 encoder stacks with ReLU / tanh-GELU feed-forwards.  As under the reference's autocast, nothing clamps: a checkpoint
+  // whose feed-forward activations leave the float16 range overflows here as it does there (the caller picks OM_BF16 for those).
+  if (c->dtype == OM_F16 && c->arch == OM_ARCH_BERT && c->act != OM_ACT_GELU_ERF) return "float16 mode: erf-GELU BERT-family encoders only";
+  if (c->dtype == OM_F16 && c->arch == OM_ARCH_T5 && c->act != OM_ACT_RELU && c->act != OM_ACT_GELU_TANH)
+    return "float16 mode: T5 feed-forwards with ReLU or tanh-GELU only";
+  if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5 && c->arch != OM_ARCH_MODERNBERT) return "unknown arch";
+  // ModernBERT (inference): 64-wide heads, the gated erf-GELU feed-forward (float16 included), at most 64 layers (sliding_layers bits)
+  if (c->arch == OM_ARCH_MODERNBERT) {
+    if (c->head_dim != 64 || c->n_heads * 64 != c->hidden) return "ModernBERT: only head_dim 64 with n_heads*64 == hidden is supported";
+    if (c->act != OM_ACT_GELU_ERF) return "ModernBERT: hidden_activation must be \"gelu\" (erf)";
+    if (c->n_layers > 64) return "ModernBERT: at most 64 layers";
+    if (!(c->rope_theta_global > 0.f) || !(c->rope_theta_local > 0.f) || c->half_window < 0)
+      return "ModernBERT: positive rope thetas and a non-negative half window";
+  }
+  // BERT family: 32-wide heads (MiniLM-shaped encoders, attention_d32.hip) or 64-wide; T5 (and the monoT5 decoder): d_kv 64
+  if (c->arch == OM_ARCH_T5 && (c->head_dim != 64 || c->n_heads * 64 != c->hidden))
+    return "T5 encoders: only d_kv 64 with n_heads*64 == d_model is supported";
+  if ((c->head_dim != 32 && c->head_dim != 64) || c->n_heads * c->head_dim != c->hidden)
+    return "head_dim must be 32 or 64 with n_heads*head_dim == hidden";
+  if (c->arch == OM_ARCH_BERT && c->rel_buckets != 0 && (c->rel_buckets < 4 || c->rel_buckets % 2 || c->rel_max_dist <= c->rel_buckets / 4))
+    return "relative position bias: an even number of buckets >= 4 and a maximum distance beyond the exact buckets";
+  const int es = c->dtype == OM_F32 ? 4 : 2;
+  if ((c->hidden * es) % 128 || (c->ffn * es) % 128) return "hidden/ffn rows must be multiples of 128 bytes";
+  if (c->head_in > 0 && ((c->head_in * 4) % 128 || c->head_in != c->hidden)) return "head_in must equal hidden";
+  return nullptr;
+}
+
+// whether the four contractions of a layer run [rows, *] on the kernel that implements the fused-norm epilogues
+static bool enc_ln_fusable(int dt, int64_t rows, int H, int F) {
+  return omk_gemm_ln_fusable(dt, rows, H, H) && omk_gemm_ln_fusable(dt, rows, F, H) && omk_gemm_ln_fusable(dt, rows, 3 * H, H) &&
+         omk_gemm_ln_fusable(dt, rows, H, F);
+}
+
+// whether the four contractions of a BERT layer take their pending-LayerNorm forms on the few-rows kernel at this shape (the
+// epilogues' addresses are tested for null only)
+static bool enc_pending_ln_ok(int dt, int64_t M, int H, int F, int act, int max_m) {
+  static const float one = 1.f;
+  GemmEpilogue a = {}, r = {};
+  a.a_ln32 = &one; a.a_ln_g = &one; a.a_ln_b = &one;
+  r.rln32 = &one; r.rln32_stats = &one; r.rln_g = &one; r.rln_b = &one; r.out32 = const_cast<float*>(&one);
+  GemmEpilogue f = a;
+  f.act = act;
+  return omk_gemm_skinny_ok(dt, dt, M, 3 * (int64_t)H, H, a, max_m) && omk_gemm_skinny_ok(dt, dt, M, F, H, f, max_m) &&
+         omk_gemm_skinny_ok(dt, dt, M, H, H, r, max_m) && omk_gemm_skinny_ok(dt, dt, M, H, F, r, max_m);
+}
+
+// rules 2 ... 7, for a configuration that passed rule 1 -- or whose caller leaves that rule to the forward (om_encoder_packed_supported)
+static EncPlan encoder_plan_checked(const EncPlanIn& in, const EncSwitches sw) {
+  const OmEncoderConfig* c = in.c;
+  EncPlan p = {};
+  auto run = [&](int path) { p.path = path; return p; };
+  auto refuse = [&](const char* why) { p.error = why; return p; };
+  const int dt = c->dtype, H = c->hidden, F = c->ffn;
+  const bool half = dt == OM_BF16 || dt == OM_F16, packed = in.packed_rows > 0, bert = c->arch == OM_ARCH_BERT;
+  // 2. rows -- filled whatever is refused below: the workspace size of a call does not depend on whether the call would be taken.
+  // 16-bit batches of >= 512 tokens are padded to whole 256-row tiles: the persistent GEMM generation (gemm_wide7.h) takes whole
+  // tiles only.  Rows are independent in every contraction, so whatever the pad rows hold stays in the pad rows; every other kernel
+  // (embedding, attention, normalisation, pooling) sees M rows.
+  p.M = packed ? in.packed_rows : in.B * in.L;
+  p.Mp = half && p.M >= 512 ? (p.M + 255) / 256 * 256 : p.M;
+  // (what carve has always tested for the f32-stream buffers: rule 4 without its bfloat16 exception, rule 7b without its two-plane bit)
+  p.alloc_few32 = half && bert && !packed && p.M <= (int64_t)std::max(0, sw.skinny_m);
+  // 3. arguments
+  if (in.B <= 0) return p;
+  if (in.L < 1 || in.L > 1024) return refuse("sequence length must be in [1,1024]");
+  if (packed) {
+    if (dt == OM_F32 || in.want_hidden || c->pooling == OM_POOL_NONE || c->n_layers < 1)
+      return refuse("packed rows: 16-bit inference that returns representations only");
+    if (in.packed_rows % 256 || in.packed_rows < 512 || in.packed_rows > in.B * in.L + 255)
+      return refuse("packed_rows: a multiple of 256 in [512, B * L + 255]");
+  }
+  // 4. few rows (a served query, a handful of sequences; round 5): up to OM_OPT_GEMM_SKINNY_M rows the contractions run on the
+  // weight-streaming kernel (gemm_skinny.hip) with the normalisations as kernels -- the persistent 256 x 256 tiles of the fused path
+  // put 6 ... 24 workgroups on 256 CUs there and take ~150 us per layer whatever the batch (profiles/r05_small_forward_*.txt).
+  // (bfloat16 BERT from 512 rows on stays on the fused path: its two-plane residual stream is what holds bfloat16 inside the
+  // reference's own autocast deviation, and the unfused path keeps one plane)
+  p.few_rows = !packed && half && p.M <= (int64_t)sw.skinny_m && !(dt == OM_BF16 && bert && p.M >= 512 && (sw.two_plane & 1) != 0);
+  p.Mg = p.few_rows ? p.M : p.Mp;
+  const bool fusable = sw.fused_ln != 0 && !p.few_rows && c->n_layers > 0 && H % 8 == 0 && enc_ln_fusable(dt, p.Mg, H, F);
+  // 5. ModernBERT: one loop, norms as kernels
+  if (c->arch == OM_ARCH_MODERNBERT) {
+    if (packed) return refuse("packed rows: not for ModernBERT (om_encoder_packed_supported is 0)");
+    return run(OM_ENC_PATH_MODERNBERT);
+  }
+  // 6. T5: RMSNorm fused across the contractions (16-bit, >= 512 rows, widths of 256), else per site
+  // (gated feed-forward layers keep the kernels: two folded GEMMs per norm measured 1 % slower, tools/gtr_bench.py)
+  if (!bert) {
+    if (!in.has_rel_bias) return refuse("T5 needs rel_bias and final_ln_g");
+    p.rel_bias = true;
+    p.path = fusable && !in.gated_ffn ? OM_ENC_PATH_T5_FUSED : OM_ENC_PATH_T5_PLAIN;
+    if (packed && p.path != OM_ENC_PATH_T5_FUSED) return refuse("packed rows need the fused 16-bit path (T5: widths of 256, no gated feed-forward)");
+    return p;
+  }
+  // 7. BERT family
+  if (in.L > c->max_pos) return refuse("sequence longer than the position table");
+  // (a table without a bucket count, or the reverse, is an error, never a forward without the bias)
+  if (in.has_rel_bias != (c->rel_buckets > 0)) return refuse("relative position bias: rel_bias and rel_buckets must be set together");
+  if (in.has_type_emb && c->type_vocab <= 0) return refuse("token types: a type_emb table needs type_vocab > 0");      // (type_emb == NULL: word + position only)
+  p.rel_bias = in.has_rel_bias;
+  const bool plane = (sw.two_plane & (dt == OM_BF16 ? 1 : 2)) != 0;      // this format's bit of the two-plane switch
+  // 7a. LayerNorm fused across the contractions (16-bit, >= 512 rows, widths of 256, erf-GELU)
+  if (fusable && c->act == OM_ACT_GELU_ERF) {
+    p.two = plane;
+    p.lo8 = plane && dt == OM_F16 && (sw.two_plane & 4) ? 1 : 0;
+    p.pingpong = sw.pingpong != 0;
+    return run(OM_ENC_PATH_BERT_FUSED);
+  }
+  // 7b. few rows with the residual stream in f32 (round 6; needs the format's two-plane bit), its LayerNorms pending up to
+  // OM_OPT_FEW_ROWS_LN_FUSE rows where the few-rows kernel has the four epilogues; 7c. one normalisation kernel per site
+  const bool few32 = p.few_rows && c->n_layers > 0 && plane;
+  p.path = !few32 ? OM_ENC_PATH_BERT_PLAIN
+           : p.M <= (int64_t)sw.few_ln_fuse && enc_pending_ln_ok(dt, p.Mg, H, F, c->act, sw.skinny_m) ? OM_ENC_PATH_BERT_PENDING_LN
+                                                                                                       : OM_ENC_PATH_BERT_FEW32;
+  if (packed) return refuse("packed rows need the fused 16-bit path (hidden, ffn multiples of 256; erf-GELU)");
+  return p;
+}
+
+static EncPlan encoder_plan(const EncPlanIn& in, const EncSwitches sw) {
+  if (const char* why = encoder_cfg_error(in.c)) {
+    EncPlan p = {};
+    p.error = why;
+    return p;
+  }
+  return encoder_plan_checked(in, sw);
+}

@@ -62,6 +62,11 @@ int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);
 int omk_pack_overflow_poison(const int* cu, int64_t B, int64_t rows, float* out, int64_t n, hipStream_t s);
 int omk_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, hipStream_t s);
+// The end of every encoder forward (encoder.hip; the causal stacks too): pooled rows [B, hidden] f32 -> out_reps through the optional
+// head contraction (then `pooled` is workspace; else it IS out_reps), l2norm where configured, and for packed rows (cu != NULL) the
+// overflow poison -- a bound below the token count gives NaN, never a truncated batch
+int omk_pooled_tail(const OmEncoderConfig* c, const OmEncoderWeights* w, const float* pooled, float* out_reps, int64_t B, const int* cu,
+                    int64_t packed_rows, hipStream_t s);
 
 // ---- extended GEMM epilogue (training) ---------------------------------------------------
 // order: v = acc + bias ; [pre_act <- v] ; v = act(v) ; v = dropout(v) ; v = v (+|*) resid

@@ -26,6 +26,8 @@ GEMM_FAMILY = {"v1": 1, "v2": 2, "v6": 6, "g7": 7, "g7_one_tile": 70, "7c16": 71
 ATTN_FAMILY = {"generic": 1, "fwd16": 2, "fwd16_kmax4": 3, "fwd16c": 4, "long": 5, "d32": 6, "band16": 7, "band32": 8}
 # om_debug_attention_bwd_last codes (OM_ATTN_BWD_FAMILY_*), packed the same way
 ATTN_BWD_FAMILY = {"bwd16": 1, "generic": 2, "long": 3, "d32": 4}
+# om_debug_encoder_plan codes (OM_ENC_PATH_*); the call returns path | few_rows << 8 | two << 9 | lo8 << 10
+ENC_PATH = {"bert_fused": 1, "bert_pending_ln": 2, "bert_few32": 3, "bert_plain": 4, "modernbert": 5, "t5_fused": 6, "t5_plain": 7}
 OPT_ATTENTION_FAST = 2
 SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
 ABI_VERSION = 6
@@ -134,6 +136,7 @@ _SIGNATURES = {
     "om_debug_attention_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int]),
     "om_debug_attention_bwd_last": (c_int, []),
     "om_debug_attention_bwd_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "om_encoder_fold_bytes": (c_size_t, [C.POINTER(OmEncoderConfig)]),

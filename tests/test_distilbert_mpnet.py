@@ -357,6 +357,15 @@ def _debug_lines(text):
     return out
 
 
+def _planned(cfg, rows, B, L, packed, gated=False):
+    """What om_debug_encoder_plan (csrc/encoder_plan.h, no GPU) says of the call that wrote a debug line, in the line's own fields."""
+    word = N.lib().om_debug_encoder_plan(C.byref(cfg), int(gated), int(cfg.arch == N.ARCH_T5 or cfg.rel_buckets > 0), B, L, rows if packed else 0, 0)
+    assert word > 0, (word, N.lib().om_last_error())
+    path = word & 0xff
+    return dict(path=path, fused_ln=int(path == N.ENC_PATH["bert_fused"]), pending_ln=int(path == N.ENC_PATH["bert_pending_ln"]),
+                fused_norm=int(path == N.ENC_PATH["t5_fused"]), few_rows=(word >> 8) & 1, packed=int(packed), M=rows)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", list(BIAS_PATHS))
 def test_bias_is_used_on_every_path(path, capfd):
@@ -390,6 +399,14 @@ def test_bias_is_used_on_every_path(path, capfd):
     took = lines[0]
     assert took["rel_bias"] == 1 and took["L"] == L, took
     assert {k: took[k] for k in expect} == expect, (path, took)
+    # the line is printed from the call's plan: the plan asked on its own, for this configuration and these rows, says the same
+    from openmatch_amd import encoder as E
+    cfg = N.OmEncoderConfig(arch=N.ARCH_BERT, dtype={"float32": N.OM_F32, "bfloat16": N.OM_BF16, "float16": N.OM_F16}[dtype],
+                            hidden=shape["hidden"], n_heads=shape["heads"], head_dim=shape["hidden"] // shape["heads"], ffn=shape["ffn"],
+                            n_layers=2, vocab=600, max_pos=516, act=N.ACT_GELU_ERF, ln_eps=1e-5, rel_buckets=32, rel_max_dist=128,
+                            pooling=N.POOL_MEAN)
+    planned = _planned(cfg, E.LAST_CALL["rows"], B, L, packed)
+    assert {k: took[k] for k in ("M", "fused_ln", "packed", "few_rows", "pending_ln")} == {k: planned[k] for k in ("M", "fused_ln", "packed", "few_rows", "pending_ln")}, (took, planned)
     if dtype == "float32":
         err = _rel(got, want)
         print(f"\n[MPNet bias, {path}] {took}; table zeroed moves HF by {moved:.2f}; HIP f32 max rel err {err:.2e}")
@@ -398,6 +415,41 @@ def test_bias_is_used_on_every_path(path, capfd):
         gap, gap0 = _cos_gap(got, want), _cos_gap(got, without)
         print(f"\n[MPNet bias, {path}, {dtype}] {took}; table zeroed moves HF by {moved:.2f}; HIP 1 - min cos {gap:.2e} (vs the zeroed run {gap0:.2e})")
         assert gap < COS_BAR[dtype], gap
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["fused", "per_site"])
+def test_t5_debug_line_names_the_planned_path(case, capfd):
+    """The T5 stack's OM_OPT_ENCODER_DEBUG line against om_debug_encoder_plan, on both of its loops: RMSNorm fused across the
+    contractions (bfloat16, 1 536 rows, widths of 256) and one normalisation kernel per site (float32)."""
+    from transformers import T5Config, T5EncoderModel
+    from openmatch.modeling import DRModelForInference
+    from openmatch_amd import encoder as E
+    dtype, code, fused = ("bfloat16", N.OM_BF16, 1) if case == "fused" else ("float32", N.OM_F32, 0)
+    B, L = (12, 128) if fused else (6, 128)
+    torch.manual_seed(8)
+    lm = T5EncoderModel(T5Config(d_model=256, d_ff=1024, num_layers=2, num_heads=4, d_kv=64, vocab_size=600, feed_forward_proj="relu")).eval()
+    model = DRModelForInference(lm_q=lm, lm_p=lm, pooling="mean", model_args=NS(encoder_only=True, dtype=dtype)).to(DEV).eval()
+    ids, mask = _ragged(np.random.default_rng(13), B, L, L // 2)
+    items = {"input_ids": torch.from_numpy(ids).to(DEV), "attention_mask": torch.from_numpy(mask).to(DEV)}
+    lib = N.lib()
+    before = lib.om_debug_option_value(1)                   # OM_OPT_ENCODER_DEBUG
+    capfd.readouterr()
+    N.check(lib.om_debug_option(1, 1))
+    try:
+        with torch.no_grad():
+            reps = E.hip_encode(model.lm_p, items, "mean", None, False, E.compute_dtype_code(model.model_args), want_hidden=False)[1]
+        torch.cuda.synchronize()
+    finally:
+        N.check(lib.om_debug_option(1, before))
+    lines = [dict((f.split("=")[0], int(f.split("=")[1])) for f in ln.split(":", 1)[1].split())
+             for ln in capfd.readouterr().err.splitlines() if ln.startswith("om_encoder_forward (t5):")]
+    assert len(lines) == 1 and torch.isfinite(reps).all(), lines
+    cfg = N.OmEncoderConfig(arch=N.ARCH_T5, dtype=code, hidden=256, n_heads=4, head_dim=64, ffn=1024, n_layers=2, vocab=600, act=N.ACT_RELU,
+                            ln_eps=1e-6, rel_buckets=32, rel_max_dist=128, pooling=N.POOL_MEAN)
+    planned = _planned(cfg, B * L, B, L, False)
+    assert planned["path"] == N.ENC_PATH["t5_fused" if fused else "t5_plain"] and planned["few_rows"] == 0, planned
+    assert lines[0] == {"M": B * L, "fused_norm": fused, "packed": 0} == {k: planned[k] for k in ("M", "fused_norm", "packed")}, (lines, planned)
 
 
 @pytest.mark.gpu
