@@ -208,6 +208,18 @@ int om_debug_attention_causal_packed(int dtype, const void* qkv, void* ctx, cons
                                      int n_kv_heads, float scale, void* stream);
 int om_debug_rope_gqa_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling,
                            const int* row_map, void* stream);
+/* The same hooks with a head width (csrc/attention_causal128.hip): head_dim 64 runs the kernels above, head_dim 128 the 128-wide ones
+ * over qkv [rows, (n_heads + 2 n_kv_heads) * 128] and ctx [rows, n_heads * 128].  om_debug_qknorm_rope: the per-head RMSNorm of the q
+ * and k heads (x * rsqrt(mean(x^2) + eps) * g; q_norm_g / k_norm_g device arrays [head_dim] f32, NULL: no norm on that side) and the
+ * rotary positions in one pass, in place; inv_freq is a HOST array of head_dim / 2 frequencies.  _packed / _rows as above. */
+int om_debug_attention_causal_hd(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads, int n_kv_heads,
+                                 int head_dim, float scale, void* stream);
+int om_debug_attention_causal_hd_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                        int n_heads, int n_kv_heads, int head_dim, float scale, void* stream);
+int om_debug_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
+                         const float* k_norm_g, float eps, const float* inv_freq, float scaling, void* stream);
+int om_debug_qknorm_rope_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
+                              const float* k_norm_g, float eps, const float* inv_freq, float scaling, const int* row_map, void* stream);
 /* kmax[b] = 1 + the last unmasked key of mask row b (L when it has none) */
 int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
 /* cu [B + 2], cls_rows [B], row_map [rows] of the packed layout (csrc/kernels.h omk_pack_rows) */
@@ -449,6 +461,40 @@ size_t om_causal_encoder_workspace_bytes_packed(const OmCausalConfig* cfg, int64
 int om_causal_encoder_forward_packed(const OmCausalConfig* cfg, const OmEncoderWeights* w, const int64_t* input_ids,
                                      const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows, float* out_reps,
                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Qwen3 embedders (HF Qwen3Model, HF:models/qwen3/modeling_qwen3.py; Qwen3-Embedding): the stack above with three things more --
+ * heads of 128 columns, an attention width A = n_heads * head_dim that need not equal `hidden`, and an RMSNorm over each q and k head
+ * before the rotation (q_norm, k_norm).  The entries are the five above with a config that EMBEDS OmCausalConfig (no layout above
+ * changes, OM_ABI_VERSION stays) and one more argument, a HOST array of n_layers OmCausalQkNorm (may be NULL when qk_norm is 0).
+ * Rules: base.base.head_dim is 64 or 128; A a multiple of 64; hidden and ffn multiples of 64, hidden <= 2048 (the row-norm, embedding
+ * and pooling kernels hold a row in 8 vectors per lane); n_kv_heads divides n_heads; act = OM_ACT_SILU; L <= 1024; pooling NONE /
+ * FIRST / MEAN / LAST.  The rotary frequencies are inv_freq[64] below when head_dim is 128 and base.inv_freq[32] when it is 64; the
+ * norm's eps is base.base.ln_eps (rms_norm_eps).
+ * Weights as above with the attention width in place of H where a head count sets it:
+ *   qkv_w [(n_heads + 2 n_kv_heads) * head_dim, H], qkv_b alongside or NULL;  o_w [H, A].
+ * Packed rows: the rule of om_causal_encoder_packed_supported (a multiple of 256 rows in [512, B * L + 255], a padded form above
+ * OM_OPT_GEMM_SKINNY_M).
+ * ------------------------------------------------------------------------ */
+typedef struct OmCausalConfig2 {
+  OmCausalConfig base;          /* at offset 0: arch, widths, n_kv_heads, rope_attention_scaling, the 32 frequencies of head_dim 64 */
+  int qk_norm;                  /* 1: RMSNorm over each q and k head before the rotation, weights in OmCausalQkNorm                   */
+  int reserved;                 /* 0                                                                                                    */
+  float inv_freq[64];           /* rotary_emb.inv_freq when head_dim is 128                                                             */
+} OmCausalConfig2;
+typedef struct OmCausalQkNorm {
+  const float* q_norm_g;        /* self_attn.q_norm.weight [head_dim] f32, device */
+  const float* k_norm_g;        /* self_attn.k_norm.weight [head_dim] f32, device */
+} OmCausalQkNorm;
+size_t om_causal2_encoder_workspace_bytes(const OmCausalConfig2* cfg, int64_t B, int64_t L);
+int om_causal2_encoder_forward(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
+                               const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden,
+                               float* out_reps, void* workspace, size_t workspace_bytes, void* stream);
+int om_causal2_encoder_packed_supported(const OmCausalConfig2* cfg, int64_t B, int64_t L, int64_t packed_rows);
+size_t om_causal2_encoder_workspace_bytes_packed(const OmCausalConfig2* cfg, int64_t B, int64_t L, int64_t packed_rows);
+int om_causal2_encoder_forward_packed(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
+                                      const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows,
+                                      float* out_reps, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * One decoder position of a T5 encoder-decoder over the encoder's output (inference):

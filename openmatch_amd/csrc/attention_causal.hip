@@ -38,23 +38,25 @@ namespace {
 
 constexpr int kRopeMaxPos = 1024;
 
-// [kRopeMaxPos][32] (cos, sin) * scaling for one frequency vector, resident on the device: built and uploaded ONCE per
-// (device, frequencies, scaling)
-int rope_table_device(const float* inv_freq, float scaling, const float2** out) {
+}  // namespace
+
+// [kRopeMaxPos][n] (cos, sin) * scaling for one frequency vector of n values (32: head_dim 64, 64: head_dim 128), resident on the
+// device: built and uploaded ONCE per (device, frequencies, scaling) -- the vector's length is part of the key
+int omk_rope_table(const float* inv_freq, int n, float scaling, const float2** out) {
   static std::mutex mu;
   static std::map<std::tuple<int, std::vector<float>, float>, float2*> cache;
   int dev = 0;
   OM_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(mu);
-  auto key = std::make_tuple(dev, std::vector<float>(inv_freq, inv_freq + 32), scaling);
+  auto key = std::make_tuple(dev, std::vector<float>(inv_freq, inv_freq + n), scaling);
   auto it = cache.find(key);
   if (it == cache.end()) {
-    std::vector<float2> tab((size_t)kRopeMaxPos * 32);
-    for (int i = 0; i < 32; ++i)
+    std::vector<float2> tab((size_t)kRopeMaxPos * n);
+    for (int i = 0; i < n; ++i)
       for (int pos = 0; pos < kRopeMaxPos; ++pos) {
         const float f = inv_freq[i] * (float)pos;                            // inv_freq @ position_ids, f32
         const float c = (float)cos((double)f), sn = (float)sin((double)f);  // emb.cos(), emb.sin(), f32
-        tab[(size_t)pos * 32 + i] = make_float2(c * scaling, sn * scaling);  // * attention_scaling, f32
+        tab[(size_t)pos * n + i] = make_float2(c * scaling, sn * scaling);   // * attention_scaling, f32
       }
     float2* d = nullptr;
     OM_HIP(hipMalloc(&d, tab.size() * sizeof(float2)));
@@ -64,6 +66,8 @@ int rope_table_device(const float* inv_freq, float scaling, const float2** out) 
   *out = it->second;
   return 0;
 }
+
+namespace {
 
 template <typename T> struct RopeIO;
 template <> struct RopeIO<float> {
@@ -208,7 +212,7 @@ static void rope_launch_as(T* qkv, const float2* tab, int64_t M, int L, int rot_
 static int rope_launch(int dtype, void* qkv, int64_t M, int L, int rot_heads, int pitch, const float* inv_freq_host, float scaling, hipStream_t s,
                        const int* row_map = nullptr) {
   const float2* tab = nullptr;
-  if (rope_table_device(inv_freq_host, scaling, &tab)) return 1;
+  if (omk_rope_table(inv_freq_host, 32, scaling, &tab)) return 1;
   if (dtype == OM_BF16) rope_launch_as((bf16_t*)qkv, tab, M, L, rot_heads, pitch, row_map, s);
   else if (dtype == OM_F16) rope_launch_as((f16_t*)qkv, tab, M, L, rot_heads, pitch, row_map, s);
   else rope_launch_as((float*)qkv, tab, M, L, rot_heads, pitch, row_map, s);
@@ -286,10 +290,10 @@ int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int
   return 0;
 }
 
-// Test hooks (tests/test_attention_causal.py, tools/causal_lm_bench.py).  The key extents go into a grow-only device buffer the hook
+// Test hooks (tests/test_attention_causal.py, tools/causal_lm_bench.py; attention_causal128.hip's share the buffer).  The key extents go into a grow-only device buffer the hook
 // keeps per device (a forward has them in its workspace): like rope_gqa_table_device it allocates on first use only, and launches
 // after that are stream-ordered with no synchronisation -- calls on one device are expected from one stream at a time.
-static int causal_debug_kmax(int64_t B, int** out) {
+int omk_causal_debug_kmax(int64_t B, int** out) {
   static std::mutex mu;
   static std::map<int, std::pair<int*, int64_t>> bufs;
   int dev = 0;
@@ -314,7 +318,7 @@ extern "C" int om_debug_attention_causal(int dtype, const void* qkv, void* ctx, 
   if (check_gqa(n_heads, n_kv_heads)) return 1;
   hipStream_t s = (hipStream_t)stream;
   int* kmax = nullptr;
-  if (causal_debug_kmax(B, &kmax)) return 1;
+  if (omk_causal_debug_kmax(B, &kmax)) return 1;
   if (omk_mask_extent(mask, B, L, kmax, s)) return 1;
   return omk_attention_causal(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, kmax, s);
 }

@@ -1,0 +1,277 @@
+// What a Qwen3 embedder (HF:models/qwen3/modeling_qwen3.py) adds to the decoder-only stack of attention_causal.hip (gfx950, inference):
+//
+//   * omk_attention_causal_d128 / _packed: causal grouped-query attention over heads of 128 columns.  The projection rows are
+//     [M, (heads + 2 kv_heads) * 128] (q heads | k heads | v heads), ctx rows [M, heads * 128].  Grid, policy (AttnCausal), key
+//     extents and the packed form are those of omk_attention_causal: one workgroup of 256 threads per (sequence, query head,
+//     128-query block) walking 128-key chunks up to the diagonal chunk, clipped to kmax[b] or the packed extent.  The bodies are
+//     attn_chunked128.h.
+//
+//   * omk_qknorm_rope: the per-head RMSNorm of q and k (Qwen3Attention.forward: q_norm(q_proj(x).view(.., head_dim)), k_norm alike)
+//     and the rotary positions in ONE pass over the q and k columns, for head_dim 64 or 128, norm or no norm (a NULL weight vector:
+//     that side is rotated only).  The v heads are never touched.  D / 8 lanes own one head of one row: lane j holds the four pairs
+//     (4j .. 4j + 3, D/2 + 4j .. D/2 + 4j + 3), so each rotation stays inside a lane and the sum of squares is a shuffle reduction
+//     inside the group (16 lanes at D = 128).  In f32: ss = sum x^2; r = 1 / sqrt(ss / D + eps); n = x * r; y = n * g; then
+//     y' = y cos + rotate_half(y) sin with products and sum kept apart as rope_rotate4 does, rounded once on store.
+//     Rounding points of HF in the 16-bit formats (the reference's autocast: q_proj's output is 16-bit, the norm weight and the
+//     cos / sin tables are f32): Qwen3RMSNorm casts x * rsqrt(..) back to the input dtype BEFORE the weight multiply -- reproduced
+//     by one convert of n to the storage format and back; the weight multiply and the rotation then run in f32 as they do there (an
+//     f32 weight times a 16-bit tensor promotes), and the stored value is rounded once, where HF rounds when the attention
+//     contraction casts its operands.  Not reproduced: a model held in 16-bit outright (weights cast by .to(dtype)), where the weight
+//     multiply and each product of the rotation round to 16 bits as well.
+//     cos / sin come from omk_rope_table's device table of D / 2 columns per position.
+#include "attn_chunked128.h"
+
+namespace {
+
+// attention_causal.hip's causal_rows with 128 columns per head
+template <typename T>
+__device__ __forceinline__ AttnRows<T> causal_rows_d128(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
+  const int kvh = h / (heads / kv_heads);
+  const int pitch = (heads + 2 * kv_heads) * 128;
+  const T* const row = qkv + row0 * pitch;
+  const T* const k = row + (heads + kvh) * 128;
+  return {row + h * 128, k, k + kv_heads * 128, pitch, ctx + row0 * (int64_t)(heads * 128) + h * 128, heads * 128};
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, 2) void attention_causal16_d128_kernel(
+    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale,
+    const int* __restrict__ kmax) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int kend = kmax ? __builtin_amdgcn_readfirstlane(kmax[b]) : L;
+  attn_chunked16_d128<T, AttnCausal>(causal_rows_d128(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kend, blockIdx.y * 128, scale);
+}
+
+__global__ __launch_bounds__(256) void attention_causal32_d128_kernel(
+    const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale,
+    const int* __restrict__ kmax) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  attn_chunked32_d128<AttnCausal>(causal_rows_d128(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128,
+                                  scale);
+}
+
+// packed rows, as attention_causal16_packed_kernel: sequence b is rows cu[b] .. cu[b + 1] - 1, the mask row keeps the padded pitch Lp;
+// a query block at or past the sequence's end leaves before it touches LDS or memory
+template <typename T>
+__global__ __launch_bounds__(256, 2) void attention_causal16_d128_packed_kernel(
+    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
+    const int* __restrict__ cu) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int row0 = __builtin_amdgcn_readfirstlane(cu[b]);
+  const int Lb = __builtin_amdgcn_readfirstlane(cu[b + 1]) - row0;
+  const int qb = blockIdx.y * 128;
+  if (qb >= Lb) return;
+  attn_chunked16_d128<T, AttnCausal>(causal_rows_d128(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale);
+}
+
+__global__ __launch_bounds__(256) void attention_causal32_d128_packed_kernel(
+    const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
+    const int* __restrict__ cu) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int row0 = cu[b];
+  const int Lb = cu[b + 1] - row0;
+  const int qb = blockIdx.y * 128;
+  if (qb >= Lb) return;
+  attn_chunked32_d128<AttnCausal>(causal_rows_d128(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale);
+}
+
+// ---- q / k RMSNorm + rotary positions ---------------------------------------------------------------------------------------
+template <typename T> struct QkIO;      // four consecutive elements <-> floats; one value rounded to the storage format and back
+template <> struct QkIO<float> {
+  __device__ static inline void load4(const float* p, float (&v)[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+  __device__ static inline void store4(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
+  __device__ static inline float round(float v) { return v; }
+};
+template <typename T> struct QkIO16 {
+  __device__ static inline void load4(const T* p, float (&v)[4]) {
+    const uint2 t = *(const uint2*)p;
+    v[0] = Half16<T>::lo(t.x); v[1] = Half16<T>::hi(t.x); v[2] = Half16<T>::lo(t.y); v[3] = Half16<T>::hi(t.y);
+  }
+  __device__ static inline void store4(T* p, const float (&v)[4]) { *(uint2*)p = make_uint2(Half16<T>::pack2(v[0], v[1]), Half16<T>::pack2(v[2], v[3])); }
+  __device__ static inline float round(float v) { return Half16<T>::value(Half16<T>::bits(v)); }
+};
+template <> struct QkIO<bf16_t> : QkIO16<bf16_t> {};
+template <> struct QkIO<f16_t> : QkIO16<f16_t> {};
+
+// one thread: the pairs (i0 .. i0 + 3, D/2 + i0 .. D/2 + i0 + 3) of one q or k head of one row; D / 8 consecutive lanes: the head.
+// row_map != NULL (packed rows): the position of row t is row_map[t] % L, rows with row_map[t] < 0 are left as they are.  A group is
+// wholly inside or wholly outside the launch and the row test is the same for all of its lanes, so the shuffles below meet live lanes.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ qkv, const float2* __restrict__ tab, int64_t M, int L, int heads,
+                                                          int rot_heads, int pitch, const float* __restrict__ qg, const float* __restrict__ kg,
+                                                          float eps, const int* __restrict__ row_map) {
+  constexpr int G = D / 8;                                  // lanes per head
+  const int per_row = rot_heads * G;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * per_row) return;
+  const int64_t row = idx / per_row;
+  const int j = (int)(idx % per_row);
+  const int seg = j / G, i0 = (j % G) * 4;                  // seg: head (q heads, then k heads); i0: first of four pairs
+  int pos = (int)(row % L);
+  if (row_map) {
+    const int tok = row_map[row];
+    if (tok < 0) return;
+    pos = tok % L;
+  }
+  T* const p = qkv + row * (int64_t)pitch + (int64_t)seg * D + i0;
+  float a[4], b[4];
+  QkIO<T>::load4(p, a);
+  QkIO<T>::load4(p + D / 2, b);
+  const float* const g = seg < heads ? qg : kg;
+  if (g) {
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ss += a[e] * a[e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ss += b[e] * b[e];
+#pragma unroll
+    for (int m = G / 2; m > 0; m >>= 1) ss += __shfl_xor(ss, m, G);
+    const float r = 1.0f / sqrtf(ss * (1.0f / D) + eps);    // rsqrt(mean + eps)
+    const float4 ga = *(const float4*)(g + i0), gb = *(const float4*)(g + D / 2 + i0);
+    const float wa[4] = {ga.x, ga.y, ga.z, ga.w}, wb[4] = {gb.x, gb.y, gb.z, gb.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(a[e], r)), wa[e]);
+      b[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(b[e], r)), wb[e]);
+    }
+  }
+  const float2* const t = tab + (size_t)pos * (D / 2) + i0;
+  float ra[4], rb[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float2 cs = t[e];
+    ra[e] = __fadd_rn(__fmul_rn(a[e], cs.x), __fmul_rn(-b[e], cs.y));
+    rb[e] = __fadd_rn(__fmul_rn(b[e], cs.x), __fmul_rn(a[e], cs.y));
+  }
+  QkIO<T>::store4(p, ra);
+  QkIO<T>::store4(p + D / 2, rb);
+}
+
+template <typename T>
+void qknorm_rope_launch_as(T* qkv, const float2* tab, int64_t M, int L, int heads, int kv_heads, int D, const float* qg, const float* kg, float eps,
+                           const int* row_map, hipStream_t s) {
+  const int rot = heads + kv_heads, pitch = (heads + 2 * kv_heads) * D;
+  const unsigned grid = (unsigned)((M * rot * (D / 8) + 255) / 256);
+  if (D == 128) hipLaunchKernelGGL((qknorm_rope_kernel<T, 128>), dim3(grid), dim3(256), 0, s, qkv, tab, M, L, heads, rot, pitch, qg, kg, eps, row_map);
+  else hipLaunchKernelGGL((qknorm_rope_kernel<T, 64>), dim3(grid), dim3(256), 0, s, qkv, tab, M, L, heads, rot, pitch, qg, kg, eps, row_map);
+}
+
+int check_gqa_d(int heads, int kv_heads, int head_dim) {
+  if (heads < 1 || kv_heads < 1 || heads % kv_heads) OM_FAIL("grouped heads: n_kv_heads must be at least 1 and divide n_heads");
+  if (head_dim != 64 && head_dim != 128) OM_FAIL("grouped heads: head_dim must be 64 or 128");
+  return 0;
+}
+
+}  // namespace
+
+int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, int head_dim, const float* q_norm_g, const float* k_norm_g,
+                    float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map) {
+  if (M <= 0) return 0;
+  if (L < 1 || L > 1024) OM_FAIL("rotary positions: sequence length must be in [1,1024]");
+  if (check_gqa_d(heads, kv_heads, head_dim)) return 1;
+  if (!inv_freq_host) OM_FAIL("rotary positions: a frequency table of head_dim / 2 values");
+  if (M * (heads + kv_heads) * (head_dim / 8) > 0x7fffffffLL * 256) OM_FAIL("q / k norm and rotary positions: too many rows for one launch");
+  const float2* tab = nullptr;
+  if (omk_rope_table(inv_freq_host, head_dim / 2, scaling, &tab)) return 1;
+  if (dtype == OM_BF16) qknorm_rope_launch_as((bf16_t*)qkv, tab, M, L, heads, kv_heads, head_dim, q_norm_g, k_norm_g, eps, row_map, s);
+  else if (dtype == OM_F16) qknorm_rope_launch_as((f16_t*)qkv, tab, M, L, heads, kv_heads, head_dim, q_norm_g, k_norm_g, eps, row_map, s);
+  else qknorm_rope_launch_as((float*)qkv, tab, M, L, heads, kv_heads, head_dim, q_norm_g, k_norm_g, eps, row_map, s);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// kmax [B] (padded rows, cu NULL) or cu [B + 1] (packed rows): one launch function for both forms
+static int attention_causal_d128_launch(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads,
+                                        float scale, const int* kmax, const int* cu, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
+  if (check_gqa_d(heads, kv_heads, 128)) return 1;
+  if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
+  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
+  if (dtype == OM_F32) {
+    if (cu) {
+      if (attn_lds_once<attention_causal32_d128_packed_kernel>(kAttn32D128Lds)) return 1;
+      hipLaunchKernelGGL(attention_causal32_d128_packed_kernel, grid, dim3(256), kAttn32D128Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, cu);
+    } else {
+      if (attn_lds_once<attention_causal32_d128_kernel>(kAttn32D128Lds)) return 1;
+      hipLaunchKernelGGL(attention_causal32_d128_kernel, grid, dim3(256), kAttn32D128Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, kmax);
+    }
+  } else if (dtype == OM_F16) {
+    if (cu) {
+      if (attn_lds_once<attention_causal16_d128_packed_kernel<f16_t>>(kAttn16D128Lds)) return 1;
+      hipLaunchKernelGGL(attention_causal16_d128_packed_kernel<f16_t>, grid, dim3(256), kAttn16D128Lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
+    } else {
+      if (attn_lds_once<attention_causal16_d128_kernel<f16_t>>(kAttn16D128Lds)) return 1;
+      hipLaunchKernelGGL(attention_causal16_d128_kernel<f16_t>, grid, dim3(256), kAttn16D128Lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
+    }
+  } else {
+    if (cu) {
+      if (attn_lds_once<attention_causal16_d128_packed_kernel<bf16_t>>(kAttn16D128Lds)) return 1;
+      hipLaunchKernelGGL(attention_causal16_d128_packed_kernel<bf16_t>, grid, dim3(256), kAttn16D128Lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
+    } else {
+      if (attn_lds_once<attention_causal16_d128_kernel<bf16_t>>(kAttn16D128Lds)) return 1;
+      hipLaunchKernelGGL(attention_causal16_d128_kernel<bf16_t>, grid, dim3(256), kAttn16D128Lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
+    }
+  }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int omk_attention_causal_d128(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                              const int* kmax, hipStream_t s) {
+  return attention_causal_d128_launch(dtype, qkv, ctx, mask, B, L, heads, kv_heads, scale, kmax, nullptr, s);
+}
+
+int omk_attention_causal_d128_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                                     const int* cu, hipStream_t s) {
+  if (B > 0 && !cu) OM_FAIL("causal attention over packed rows: the sequence offsets cu");
+  return attention_causal_d128_launch(dtype, qkv, ctx, mask, B, L, heads, kv_heads, scale, nullptr, cu, s);
+}
+
+// Test hooks (tests/test_qwen3_kernels.py, tools/causal_lm_bench.py): the kernels of either head width alone.
+static int debug_dtype(int dtype) {
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
+  return 0;
+}
+
+extern "C" int om_debug_attention_causal_hd(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads,
+                                            int n_kv_heads, int head_dim, float scale, void* stream) {
+  if (!qkv || !ctx || !mask) OM_FAIL("null argument");
+  if (debug_dtype(dtype)) return 1;
+  if (B <= 0) return 0;
+  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
+  if (check_gqa_d(n_heads, n_kv_heads, head_dim)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int* kmax = nullptr;
+  if (omk_causal_debug_kmax(B, &kmax)) return 1;
+  if (omk_mask_extent(mask, B, L, kmax, s)) return 1;
+  if (head_dim == 64) return omk_attention_causal(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, kmax, s);
+  return omk_attention_causal_d128(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, kmax, s);
+}
+
+extern "C" int om_debug_attention_causal_hd_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                                   int n_heads, int n_kv_heads, int head_dim, float scale, void* stream) {
+  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
+  if (debug_dtype(dtype)) return 1;
+  if (check_gqa_d(n_heads, n_kv_heads, head_dim)) return 1;
+  if (head_dim == 64) return omk_attention_causal_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, cu, (hipStream_t)stream);
+  return omk_attention_causal_d128_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, cu, (hipStream_t)stream);
+}
+
+extern "C" int om_debug_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
+                                    const float* k_norm_g, float eps, const float* inv_freq, float scaling, void* stream) {
+  if (!qkv || !inv_freq) OM_FAIL("null argument");
+  if (debug_dtype(dtype)) return 1;
+  return omk_qknorm_rope(dtype, qkv, M, L, n_heads, n_kv_heads, head_dim, q_norm_g, k_norm_g, eps, inv_freq, scaling, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int om_debug_qknorm_rope_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
+                                         const float* k_norm_g, float eps, const float* inv_freq, float scaling, const int* row_map, void* stream) {
+  if (!qkv || !inv_freq || !row_map) OM_FAIL("null argument");
+  if (debug_dtype(dtype)) return 1;
+  return omk_qknorm_rope(dtype, qkv, rows, L, n_heads, n_kv_heads, head_dim, q_norm_g, k_norm_g, eps, inv_freq, scaling, (hipStream_t)stream, row_map);
+}

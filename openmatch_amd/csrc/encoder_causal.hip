@@ -20,7 +20,11 @@
 // at 1.77e-3.
 //
 // Activation buffers ([M = B*L tokens] x width): x [M, H] f32 residual stream; in the compute dtype y normed input,
-// qkv [M, (heads + 2 kv) * 64], ctx [M, H], ff / ff2 [M, F].
+// qkv [M, (heads + 2 kv) * head_dim], ctx [M, A = heads * head_dim], ff / ff2 [M, F].
+//
+// om_causal2_encoder_forward / _packed (Qwen3Model, HF:models/qwen3/modeling_qwen3.py) are the same loop with three things read from
+// their config instead of assumed: head_dim 64 or 128, an attention width A that need not equal H (o_proj contracts over A), and the
+// RMSNorm of each q and k head, applied with the rotation in one pass (omk_qknorm_rope) where the older entries call omk_rope_gqa.
 //
 // om_causal_encoder_forward_packed is the SAME launch sequence (causal_forward_impl below, one layer loop for both entries) with
 // M = packed_rows: each sequence's rows up to its last unmasked token, back to back (omk_pack_rows).  The embedding gathers through
@@ -106,11 +110,14 @@ struct CausalWs {
   size_t total;
 };
 
-CausalWs carve(const OmCausalConfig* cc, int64_t B, int64_t L, char* base, int64_t packed_rows = 0) {
+// head_dim: 64 for the Llama / Qwen2 entries; the config's own for the om_causal2_* entries, whose attention width A = n_heads * head_dim
+// need not equal the hidden size
+CausalWs carve(const OmCausalConfig* cc, int head_dim, int64_t B, int64_t L, char* base, int64_t packed_rows = 0) {
   const OmEncoderConfig* c = &cc->base;
   const bool half = c->dtype == OM_BF16 || c->dtype == OM_F16;
   const size_t es = half ? 2 : 4;
-  const size_t Mreal = packed_rows > 0 ? (size_t)packed_rows : (size_t)B * L, H = c->hidden, F = c->ffn, P = (size_t)(c->n_heads + 2 * cc->n_kv_heads) * 64;
+  const size_t Mreal = packed_rows > 0 ? (size_t)packed_rows : (size_t)B * L, H = c->hidden, F = c->ffn;
+  const size_t A = (size_t)c->n_heads * head_dim, P = (size_t)(c->n_heads + 2 * cc->n_kv_heads) * head_dim;
   const size_t M = (half && Mreal >= 512) ? (Mreal + 255) / 256 * 256 : Mreal;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
@@ -118,7 +125,7 @@ CausalWs carve(const OmCausalConfig* cc, int64_t B, int64_t L, char* base, int64
   w.x = take(M * H * 4);
   w.y = take(M * H * es);
   w.qkv = take(M * P * es);
-  w.ctx = take(M * H * es);
+  w.ctx = take(M * A * es);
   w.ff = take(M * F * es);
   w.ff2 = take(M * F * es);
   w.pooled = (float*)take((size_t)B * H * 4);
@@ -152,36 +159,70 @@ int check_cfg(const OmCausalConfig* cc) {
   return 0;
 }
 
+// the om_causal2_* entries (Qwen3): head_dim 64 or 128, an attention width of its own, optional q / k norm
+int check_cfg2(const OmCausalConfig2* c2) {
+  const OmCausalConfig* cc = &c2->base;
+  const OmEncoderConfig* c = &cc->base;
+  if (c->dtype != OM_F32 && c->dtype != OM_BF16 && c->dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
+  if (c->arch != OM_ARCH_CAUSAL) OM_FAIL("base.arch must be OM_ARCH_CAUSAL");
+  if ((c->head_dim != 64 && c->head_dim != 128) || c->n_heads < 1) OM_FAIL("Qwen3: head_dim must be 64 or 128, with at least one head");
+  if (cc->n_kv_heads < 1 || c->n_heads % cc->n_kv_heads) OM_FAIL("Qwen3: n_kv_heads must be at least 1 and divide n_heads");
+  if (c->act != OM_ACT_SILU) OM_FAIL("Qwen3: hidden_act must be \"silu\" (OM_ACT_SILU)");
+  if (c->hidden < 64 || c->hidden % 64 || c->ffn < 64 || c->ffn % 64 || c->hidden > 2048)
+    OM_FAIL("Qwen3: hidden and ffn widths are multiples of 64, hidden at most 2048");
+  if (c->n_layers < 0 || c->vocab < 1) OM_FAIL("Qwen3: n_layers >= 0 and a vocabulary");
+  if (c->pooling != OM_POOL_NONE && c->pooling != OM_POOL_FIRST && c->pooling != OM_POOL_MEAN && c->pooling != OM_POOL_LAST)
+    OM_FAIL("pooling must be OM_POOL_NONE, OM_POOL_FIRST, OM_POOL_MEAN or OM_POOL_LAST");
+  if (c->head_in > 0 && c->head_in != c->hidden) OM_FAIL("head_in must equal hidden");
+  if (!(cc->rope_attention_scaling > 0.f)) OM_FAIL("Qwen3: a positive rope_attention_scaling");
+  if (c2->qk_norm != 0 && c2->qk_norm != 1) OM_FAIL("Qwen3: qk_norm is 0 or 1");
+  const float* f = c->head_dim == 128 ? c2->inv_freq : cc->inv_freq;
+  for (int i = 0; i < c->head_dim / 2; ++i)
+    if (!(f[i] >= 0.f) || !std::isfinite(f[i])) OM_FAIL("Qwen3: inv_freq holds head_dim / 2 finite, non-negative frequencies");
+  return 0;
+}
+
+bool packed_rows_rule(int64_t B, int64_t L, int64_t packed_rows) {
+  if (B <= 0 || L <= 0 || L > 1024 || packed_rows <= 0) return false;
+  if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) return false;
+  // few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so a batch
+  // whose PADDED form is that small is sent back (as om_encoder_packed_supported)
+  return B * L > (int64_t)om_option(OM_OPT_GEMM_SKINNY_M);
+}
+
+// What the one layer loop reads beyond OmCausalConfig: the Llama / Qwen2 entries fill it with head_dim 64, their 32 frequencies and no
+// norm; `v2` selects the names in messages and the q / k norm + rotation pass (the older entries keep omk_rope_gqa)
+struct CausalExtra {
+  bool v2;
+  int head_dim;
+  const float* inv_freq;
+  const OmCausalQkNorm* qk_norm;      // [n_layers] on the host, or NULL: no q / k norm
+};
+
 }  // namespace
 
 extern "C" size_t om_causal_encoder_workspace_bytes(const OmCausalConfig* cfg, int64_t B, int64_t L) {
   if (!cfg || B <= 0 || L <= 0 || cfg->n_kv_heads < 1 || cfg->base.n_heads < 1) return 0;
-  return carve(cfg, B, L, nullptr).total;
+  return carve(cfg, 64, B, L, nullptr).total;
 }
 
 // Whether om_causal_encoder_forward_packed takes (cfg, B, L, packed_rows): the stack is unfused, so every compute format and none of
 // the fused-LayerNorm switches enter.  No region is excluded on grounds of speed: the packed entry's throughput has not been measured
 // yet (DESIGN.md section 8 says what is to be done when it is).
 extern "C" int om_causal_encoder_packed_supported(const OmCausalConfig* cc, int64_t B, int64_t L, int64_t packed_rows) {
-  if (!cc || B <= 0 || L <= 0 || L > 1024 || packed_rows <= 0) return 0;
-  if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) return 0;
-  // few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so a batch
-  // whose PADDED form is that small is sent back (as om_encoder_packed_supported)
-  if (B * L <= (int64_t)om_option(OM_OPT_GEMM_SKINNY_M)) return 0;
+  if (!cc || !packed_rows_rule(B, L, packed_rows)) return 0;
   return check_cfg(cc) ? 0 : 1;
 }
 
 extern "C" size_t om_causal_encoder_workspace_bytes_packed(const OmCausalConfig* cfg, int64_t B, int64_t L, int64_t packed_rows) {
   if (!cfg || B <= 0 || L <= 0 || packed_rows <= 0 || cfg->n_kv_heads < 1 || cfg->base.n_heads < 1) return 0;
-  return carve(cfg, B, L, nullptr, packed_rows).total;
+  return carve(cfg, 64, B, L, nullptr, packed_rows).total;
 }
 
-// both entries: packed_rows == 0 is the padded layout [B * L rows], > 0 the packed one
-static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids, const int64_t* attention_mask,
-                               int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace, size_t workspace_bytes, void* stream,
-                               int64_t packed_rows) {
-  if (!cc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
-  if (check_cfg(cc)) return 1;
+// all four forward entries (the config is checked by the caller): packed_rows == 0 is the padded layout [B * L rows], > 0 the packed one
+static int causal_forward_impl(const OmCausalConfig* cc, const CausalExtra& ex, const OmEncoderWeights* w, const int64_t* input_ids,
+                               const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace,
+                               size_t workspace_bytes, void* stream, int64_t packed_rows) {
   const OmEncoderConfig* c = &cc->base;
   if (B <= 0) return 0;
   if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
@@ -191,15 +232,15 @@ static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights*
     if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) OM_FAIL("packed_rows: a multiple of 256 in [512, B * L + 255]");
   }
   if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  CausalWs ws = carve(cc, B, L, (char*)workspace, packed_rows);
+  CausalWs ws = carve(cc, ex.head_dim, B, L, (char*)workspace, packed_rows);
   if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
   if (c->pooling != OM_POOL_NONE && !out_reps) OM_FAIL("out_reps required when pooling is set");
   const OmLayerWeights* Ls = w->layers_host;
   if (c->n_layers > 0 && !Ls) OM_FAIL("layers_host is null");
-  if (!w->word_emb || !w->final_ln_g) OM_FAIL("Llama / Qwen2 need word_emb and final_ln_g (norm.weight)");
+  if (!w->word_emb || !w->final_ln_g) OM_FAIL(ex.v2 ? "Qwen3 needs word_emb and final_ln_g (norm.weight)" : "Llama / Qwen2 need word_emb and final_ln_g (norm.weight)");
   hipStream_t s = (hipStream_t)stream;
   const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nkv = cc->n_kv_heads;
-  const int P = (nh + 2 * nkv) * 64;
+  const int hd = ex.head_dim, A = nh * hd, P = (nh + 2 * nkv) * hd;      // A: the attention width (ctx rows, o_proj's contraction)
   const int64_t M = packed ? packed_rows : B * L, Mg = ws.Mp;
   const int* const row_map = packed ? ws.row_map : nullptr;
 
@@ -219,20 +260,33 @@ static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights*
   RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
   if (packed) {
     RUN(omk_pack_rows(ws.kmax, B, (int)L, packed_rows, ws.cu, ws.cls_rows, ws.row_map, s));
-    OM_HIP(hipMemsetAsync(ws.ctx, 0, (size_t)M * H * (dt == OM_F32 ? 4 : 2), s));      // the tail rows: no attention workgroup writes them
+    OM_HIP(hipMemsetAsync(ws.ctx, 0, (size_t)M * A * (dt == OM_F32 ? 4 : 2), s));      // the tail rows: no attention workgroup writes them
   }
   RUN(omk_embed(OM_F32, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
   const float scale = 1.0f / sqrtf((float)c->head_dim);
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
     if (!lw.qkv_w || !lw.o_w || !lw.ln1_g || !lw.ln2_g || !lw.ffn1_w || !lw.ffn1g_w || !lw.ffn2_w)
-      OM_FAIL("Llama / Qwen2 layers need qkv_w, o_w, ln1_g, ln2_g, ffn1_w (gate_proj), ffn1g_w (up_proj) and ffn2_w (down_proj)");
+      OM_FAIL(ex.v2 ? "Qwen3 layers need qkv_w, o_w, ln1_g, ln2_g, ffn1_w (gate_proj), ffn1g_w (up_proj) and ffn2_w (down_proj)"
+                    : "Llama / Qwen2 layers need qkv_w, o_w, ln1_g, ln2_g, ffn1_w (gate_proj), ffn1g_w (up_proj) and ffn2_w (down_proj)");
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));   // input_layernorm
     GEMM(ws.y, H, lw.qkv_w, H, ws.qkv, P, P, H, lw.qkv_b, nullptr, 0);
-    RUN(omk_rope_gqa(dt, ws.qkv, M, (int)L, nh, nkv, cc->inv_freq, cc->rope_attention_scaling, s, row_map));
-    if (packed) RUN(omk_attention_causal_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
-    else RUN(omk_attention_causal(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
-    GEMM_ACC(ws.ctx, H, lw.o_w, H, H, H, lw.o_b);                                                          // x += o_proj(ctx)
+    if (ex.v2) {                                                                                           // q_norm, k_norm, rotary positions
+      const OmCausalQkNorm* qn = ex.qk_norm ? &ex.qk_norm[l] : nullptr;
+      if (qn && (!qn->q_norm_g || !qn->k_norm_g)) OM_FAIL("Qwen3 layers with qk_norm need q_norm_g and k_norm_g");
+      RUN(omk_qknorm_rope(dt, ws.qkv, M, (int)L, nh, nkv, hd, qn ? qn->q_norm_g : nullptr, qn ? qn->k_norm_g : nullptr, c->ln_eps, ex.inv_freq,
+                          cc->rope_attention_scaling, s, row_map));
+    } else {
+      RUN(omk_rope_gqa(dt, ws.qkv, M, (int)L, nh, nkv, cc->inv_freq, cc->rope_attention_scaling, s, row_map));
+    }
+    if (hd == 128) {
+      if (packed) RUN(omk_attention_causal_d128_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
+      else RUN(omk_attention_causal_d128(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
+    } else {
+      if (packed) RUN(omk_attention_causal_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
+      else RUN(omk_attention_causal(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
+    }
+    GEMM_ACC(ws.ctx, A, lw.o_w, A, H, A, lw.o_b);                                                          // x += o_proj(ctx)
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // post_attention_layernorm
     GEMM(ws.y, H, lw.ffn1_w, H, ws.ff2, F, F, H, nullptr, nullptr, 0);                                     // gate_proj
     GEMM(ws.y, H, lw.ffn1g_w, H, ws.ff, F, F, H, nullptr, nullptr, 0);                                     // up_proj
@@ -270,12 +324,60 @@ static int causal_forward_impl(const OmCausalConfig* cc, const OmEncoderWeights*
 extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids,
                                          const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-  return causal_forward_impl(cc, w, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace, workspace_bytes, stream, 0);
+  if (!cc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
+  if (check_cfg(cc)) return 1;
+  return causal_forward_impl(cc, CausalExtra{false, 64, cc->inv_freq, nullptr}, w, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace,
+                             workspace_bytes, stream, 0);
 }
 
 extern "C" int om_causal_encoder_forward_packed(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids,
                                                 const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows, float* out_reps,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
   if (packed_rows <= 0) OM_FAIL("packed_rows must be positive");
-  return causal_forward_impl(cc, w, input_ids, attention_mask, B, L, nullptr, out_reps, workspace, workspace_bytes, stream, packed_rows);
+  if (!cc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
+  if (check_cfg(cc)) return 1;
+  return causal_forward_impl(cc, CausalExtra{false, 64, cc->inv_freq, nullptr}, w, input_ids, attention_mask, B, L, nullptr, out_reps, workspace,
+                             workspace_bytes, stream, packed_rows);
+}
+
+// ---- Qwen3: the same loop behind a config that adds the head width, the q / k norm and 64 frequencies ----
+static CausalExtra extra_of(const OmCausalConfig2* c2, const OmCausalQkNorm* qk_norm_host) {
+  const int hd = c2->base.base.head_dim;
+  return CausalExtra{true, hd, hd == 128 ? c2->inv_freq : c2->base.inv_freq, c2->qk_norm ? qk_norm_host : nullptr};
+}
+
+extern "C" size_t om_causal2_encoder_workspace_bytes(const OmCausalConfig2* cfg, int64_t B, int64_t L) {
+  if (!cfg || B <= 0 || L <= 0 || check_cfg2(cfg)) return 0;
+  return carve(&cfg->base, cfg->base.base.head_dim, B, L, nullptr).total;
+}
+
+extern "C" int om_causal2_encoder_packed_supported(const OmCausalConfig2* cfg, int64_t B, int64_t L, int64_t packed_rows) {
+  if (!cfg || !packed_rows_rule(B, L, packed_rows)) return 0;
+  return check_cfg2(cfg) ? 0 : 1;
+}
+
+extern "C" size_t om_causal2_encoder_workspace_bytes_packed(const OmCausalConfig2* cfg, int64_t B, int64_t L, int64_t packed_rows) {
+  if (!cfg || B <= 0 || L <= 0 || packed_rows <= 0 || check_cfg2(cfg)) return 0;
+  return carve(&cfg->base, cfg->base.base.head_dim, B, L, nullptr, packed_rows).total;
+}
+
+extern "C" int om_causal2_encoder_forward(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
+                                          const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden,
+                                          float* out_reps, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!cfg || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
+  if (check_cfg2(cfg)) return 1;
+  if (cfg->qk_norm && cfg->base.base.n_layers > 0 && !qk_norm_host) OM_FAIL("Qwen3: qk_norm is set but the q / k norm weights are null");
+  return causal_forward_impl(&cfg->base, extra_of(cfg, qk_norm_host), w, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace,
+                             workspace_bytes, stream, 0);
+}
+
+extern "C" int om_causal2_encoder_forward_packed(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
+                                                 const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L,
+                                                 int64_t packed_rows, float* out_reps, void* workspace, size_t workspace_bytes, void* stream) {
+  if (packed_rows <= 0) OM_FAIL("packed_rows must be positive");
+  if (!cfg || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
+  if (check_cfg2(cfg)) return 1;
+  if (cfg->qk_norm && cfg->base.base.n_layers > 0 && !qk_norm_host) OM_FAIL("Qwen3: qk_norm is set but the q / k norm weights are null");
+  return causal_forward_impl(&cfg->base, extra_of(cfg, qk_norm_host), w, input_ids, attention_mask, B, L, nullptr, out_reps, workspace,
+                             workspace_bytes, stream, packed_rows);
 }

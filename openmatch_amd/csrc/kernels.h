@@ -57,6 +57,19 @@ int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* m
 // packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (omk_pack_rows), L stays the pitch of the mask
 int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
                                 const int* cu, hipStream_t s);
+// Qwen3 (attention_causal128.hip): heads of 128 columns -- qkv [M, (heads + 2 kv_heads) * 128], ctx [M, heads * 128], otherwise the
+// two launches above -- and ONE pass for the per-head RMSNorm of q and k (weights [head_dim] f32, NULL: no norm on that side) and the
+// rotary positions, head_dim 64 or 128, from the host's head_dim / 2 frequencies.
+int omk_attention_causal_d128(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                              const int* kmax, hipStream_t s);
+int omk_attention_causal_d128_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads,
+                                     float scale, const int* cu, hipStream_t s);
+int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, int head_dim, const float* q_norm_g, const float* k_norm_g,
+                    float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map = nullptr);
+// attention_causal.hip: the device table [1024 positions][n] of (cos, sin) * scaling for n host frequencies, cached per (device,
+// frequencies, scaling); the grow-only device buffer of key extents the causal test hooks share
+int omk_rope_table(const float* inv_freq, int n, float scaling, const float2** out);
+int omk_causal_debug_kmax(int64_t B, int** out);
 // packed rows (om_encoder_forward_packed): cu[0..B] = offsets of the sequences (kmax[b] rows each) clamped to `rows`, cu[B + 1] = the
 // unclamped token count; cls_rows[b] = min(cu[b], rows - 1); row_map[t] = b * L + position of packed row t, -1 for the pad rows
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);

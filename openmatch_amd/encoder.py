@@ -124,8 +124,9 @@ def shadows_of(param):
 
 
 # what AutoModel returns for RepLLaMA-style / Qwen2-based / SmolLM / TinyLlama embedders; MistralModel (head_dim 128 checkpoints, a
-# sliding window) and every *ForCausalLM wrapper stay refused by name
-_CAUSAL_CLASSES = ("LlamaModel", "Qwen2Model")
+# sliding window) and every *ForCausalLM wrapper stay refused by name.  Qwen3Model (the Qwen3-Embedding models): heads of 64 or 128
+# columns, an attention width of its own and q / k norms, through the om_causal2_* entries
+_CAUSAL_CLASSES = ("LlamaModel", "Qwen2Model", "Qwen3Model")
 
 
 def _arch_of(model):
@@ -143,7 +144,7 @@ def _arch_of(model):
         return "bert"
     raise NotImplementedError(
         f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder, ModernBERT and Llama / Qwen2 "
-        f"(head_dim 64, inference) backbones; got {name}")
+        f"(head_dim 64, inference) / Qwen3 (head_dim 64 or 128, inference) backbones; got {name}")
 
 
 def position_offset(model):
@@ -374,11 +375,55 @@ def causal_config_fields(cfg, model):
                 n_kv_heads=n_kv, rope_attention_scaling=float(rot.attention_scaling), inv_freq=[float(v) for v in inv])
 
 
+def is_qwen3(model):
+    return type(model).__name__ == "Qwen3Model"
+
+
+def qwen3_config_fields(cfg, model):
+    """The OmCausalConfig2 fields of a `Qwen3Model` that do not depend on the compute format, after refusing (naming Qwen3Model and the
+    limit, before anything touches the device) what the HIP stack does not serve.  head_dim is the config's own (64 or 128) and the
+    attention width num_attention_heads * head_dim need not equal hidden_size; the D / 2 rotary frequencies and the cos / sin scaling
+    are the module's own, under Llama's rope-type rule; eps is rms_norm_eps, for the block norms and the q / k norms alike."""
+    name = "Qwen3Model"
+    heads, hidden = int(cfg.num_attention_heads), int(cfg.hidden_size)
+    head_dim = int(getattr(cfg, "head_dim", None) or hidden // heads)
+    if head_dim not in (64, 128):
+        raise NotImplementedError(f"{name}: head_dim {head_dim} is not supported by the HIP encoder (attention kernels exist for head_dim 64 and 128)")
+    n_kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
+    if n_kv < 1 or heads % n_kv:
+        raise NotImplementedError(f"{name}: num_key_value_heads ({n_kv}) must divide num_attention_heads ({heads})")
+    if hidden % 64 or cfg.intermediate_size % 64 or hidden > 2048:
+        raise NotImplementedError(f"{name}: hidden_size and intermediate_size must be multiples of 64, hidden_size at most 2048 "
+                                  f"(got {hidden}, {cfg.intermediate_size}): the row kernels hold a row of at most 2048 columns")
+    if getattr(cfg, "use_sliding_window", False):
+        raise NotImplementedError(f"{name} with use_sliding_window = True is not supported by the HIP encoder (causal attention over the whole prefix only)")
+    if any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
+        raise NotImplementedError(f"{name}: every layer must be full_attention; got layer_types {list(cfg.layer_types)}")
+    if cfg.hidden_act != "silu":
+        raise NotImplementedError(f"{name}: hidden_act must be 'silu'; got {cfg.hidden_act!r}")
+    rp = getattr(cfg, "rope_parameters", None) or {}
+    rope_type = rp.get("rope_type", "default")
+    if rope_type not in ("default", "linear", "llama3"):
+        raise NotImplementedError(f"{name}: rope type {rope_type!r} is not supported by the HIP encoder (its frequencies depend on the "
+                                  "sequence length); default, linear and llama3 are")
+    rot = model.rotary_emb
+    inv = rot.inv_freq.detach().to("cpu", torch.float32).reshape(-1)
+    if inv.numel() != head_dim // 2:
+        raise NotImplementedError(f"{name}: expected {head_dim // 2} rotary frequencies (head_dim {head_dim}, full rotation); got {inv.numel()}")
+    return dict(arch=N.ARCH_CAUSAL, hidden=hidden, n_layers=int(cfg.num_hidden_layers), n_heads=heads, head_dim=head_dim,
+                ffn=int(cfg.intermediate_size), vocab=int(cfg.vocab_size), max_pos=0, type_vocab=0, act=N.ACT_SILU,
+                ln_eps=float(cfg.rms_norm_eps), rel_buckets=0, rel_max_dist=0,
+                n_kv_heads=n_kv, rope_attention_scaling=float(rot.attention_scaling), inv_freq=[float(v) for v in inv], qk_norm=1)
+
+
 def _pack_causal(model, code, device):
-    """LlamaModel / Qwen2Model: the embedding table and the RMSNorm weights in f32, the matrices in the compute dtype; q / k / v
-    fused to rows q | k | v of [(heads + 2 kv) * 64, H] (a missing bias of a projection that has siblings with one counts as zero)."""
+    """LlamaModel / Qwen2Model / Qwen3Model: the embedding table and the RMSNorm weights in f32, the matrices in the compute dtype;
+    q / k / v fused to rows q | k | v of [(heads + 2 kv) * head_dim, H] (a missing bias of a projection that has siblings with one
+    counts as zero).  Qwen3Model: the per-layer q_norm / k_norm weights [head_dim] in f32 as well (pk.qk_norm, an OmCausalQkNorm
+    array), and a cfg dict that carries qk_norm -- the key that routes its calls to the om_causal2_* entries."""
     cfg = model.config
-    fields = causal_config_fields(cfg, model)
+    fields = qwen3_config_fields(cfg, model) if is_qwen3(model) else causal_config_fields(cfg, model)
+    qk_norm = (N.OmCausalQkNorm * cfg.num_hidden_layers)() if is_qwen3(model) else None
     wd = torch_dtype_of(code)
     f32 = torch.float32
     pk = _Packed()
@@ -403,10 +448,26 @@ def _pack_causal(model, code, device):
         lw.ffn1_w = pk.dev(mlp.gate_proj.weight, wd, device)
         lw.ffn1g_w = pk.dev(mlp.up_proj.weight, wd, device)
         lw.ffn2_w = pk.dev(mlp.down_proj.weight, wd, device)
+        if qk_norm is not None:
+            qk_norm[i].q_norm_g = pk.dev(sa.q_norm.weight, f32, device)
+            qk_norm[i].k_norm_g = pk.dev(sa.k_norm.weight, f32, device)
     pk.layers = layers
+    pk.qk_norm = qk_norm
     w.layers_host = C.cast(layers, C.POINTER(N.OmLayerWeights))
     pk.cfg = dict(dtype=code, **fields)
     return pk
+
+
+def causal2_config(pk_cfg, pooling, normalize):
+    """The OmCausalConfig2 of a packed Qwen3 (`_pack_causal`'s cfg dict + the head fields) for one call: the frequencies go into the
+    embedded 32 when head_dim is 64, into the struct's own 64 when it is 128."""
+    own = ("n_kv_heads", "rope_attention_scaling", "inv_freq", "qk_norm")
+    base = N.OmEncoderConfig(pooling=pooling, normalize=int(bool(normalize)), **{k: v for k, v in pk_cfg.items() if k not in own})
+    freq = list(pk_cfg["inv_freq"])
+    wide = pk_cfg["head_dim"] == 128
+    inner = N.OmCausalConfig(base=base, n_kv_heads=pk_cfg["n_kv_heads"], rope_attention_scaling=pk_cfg["rope_attention_scaling"],
+                             inv_freq=(C.c_float * 32)(*([0.0] * 32 if wide else freq)))
+    return N.OmCausalConfig2(base=inner, qk_norm=int(pk_cfg["qk_norm"]), reserved=0, inv_freq=(C.c_float * 64)(*(freq if wide else [0.0] * 64)))
 
 
 def causal_config(pk_cfg, pooling, normalize):
@@ -580,7 +641,7 @@ def check_pooling(model, pooling):
     if pooling not in _POOL:
         raise ValueError("Unknown pooling type: {}".format(pooling))
     if pooling == "last" and _arch_of(model) != "causal":
-        raise NotImplementedError(f"pooling='last' is served for Llama / Qwen2 backbones only; {type(model).__name__} pools with 'first' or 'mean'")
+        raise NotImplementedError(f"pooling='last' is served for Llama / Qwen2 / Qwen3 backbones only; {type(model).__name__} pools with 'first' or 'mean'")
 
 
 def packed_rows_bound(mask):
@@ -699,13 +760,15 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
 
 
 def causal_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
-    """Whether om_causal_encoder_forward_packed takes this call (cfg: an OmCausalConfig) and pays: representations only, at least one
+    """Whether om_causal_encoder_forward_packed takes this call (cfg: an OmCausalConfig; an OmCausalConfig2: the om_causal2_* entry) and pays: representations only, at least one
     256-row tile saved -- a left-padded batch's bound is B * L, so it stays on the padded entry -- and the library's own view
     (include/openmatch_hip.h om_causal_encoder_packed_supported).  OM_ENCODER_PACKED=0 keeps every batch on the padded entry."""
     if os.environ.get("OM_ENCODER_PACKED", "1") == "0" or want_hidden or pooling is None:
         return False
     if not (rows % 256 == 0 and 512 <= rows <= (B * L) // 256 * 256 - 256):
         return False
+    if isinstance(cfg, N.OmCausalConfig2):
+        return bool(N.lib().om_causal2_encoder_packed_supported(C.byref(cfg), B, L, rows))
     return bool(N.lib().om_causal_encoder_packed_supported(C.byref(cfg), B, L, rows))
 
 
@@ -713,6 +776,8 @@ def _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, pac
     """hip_encode for a packed Llama / Qwen2: om_causal_encoder_forward_packed over `packed_rows` rows where causal_packed_rows_apply
     admits the call, om_causal_encoder_forward over the B * L padded rows otherwise."""
     device = ids.device
+    if "qk_norm" in pk.cfg:
+        return _hip_encode_causal2(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
     cfg = causal_config(pk.cfg, _POOL[pooling], normalize)
     B, L = ids.shape
     H = cfg.base.hidden
@@ -734,6 +799,35 @@ def _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, pac
         hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
         N.check(lib.om_causal_encoder_forward(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
                                               C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+    return hidden, reps
+
+
+def _hip_encode_causal2(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
+    """_hip_encode_causal for a packed Qwen3: the om_causal2_* entries, padded and packed, under the same causal_packed_rows_apply rule."""
+    device = ids.device
+    cfg = causal2_config(pk.cfg, _POOL[pooling], normalize)
+    B, L = ids.shape
+    base = cfg.base.base
+    H = base.hidden
+    D = base.head_out if base.head_in > 0 else H
+    lib = N.lib()
+    qkn = C.cast(pk.qk_norm, C.POINTER(N.OmCausalQkNorm)) if pk.qk_norm is not None and len(pk.qk_norm) else None
+    if packed_rows and not causal_packed_rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
+        packed_rows = None
+    LAST_CALL.update(rows=int(packed_rows) if packed_rows else B * L, packed=bool(packed_rows))
+    with torch.cuda.device(device):
+        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
+        if packed_rows:
+            nbytes = lib.om_causal2_encoder_workspace_bytes_packed(C.byref(cfg), B, L, int(packed_rows))
+            ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
+            N.check(lib.om_causal2_encoder_forward_packed(C.byref(cfg), C.byref(pk.weights), qkn, N.ptr(ids), N.ptr(mask), B, L, int(packed_rows),
+                                                          N.ptr(reps), C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+            return None, reps
+        nbytes = lib.om_causal2_encoder_workspace_bytes(C.byref(cfg), B, L)
+        ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
+        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
+        N.check(lib.om_causal2_encoder_forward(C.byref(cfg), C.byref(pk.weights), qkn, N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
+                                               C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
     return hidden, reps
 
 

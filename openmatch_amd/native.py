@@ -57,6 +57,16 @@ class OmCausalConfig(C.Structure):
     _fields_ = [("base", OmEncoderConfig), ("n_kv_heads", c_int), ("rope_attention_scaling", c_float), ("inv_freq", c_float * 32)]
 
 
+class OmCausalConfig2(C.Structure):
+    """Qwen3 (om_causal2_encoder_forward): OmCausalConfig, untouched, followed by the q / k norm flag and the 64 frequencies of head_dim 128."""
+    _fields_ = [("base", OmCausalConfig), ("qk_norm", c_int), ("reserved", c_int), ("inv_freq", c_float * 64)]
+
+
+class OmCausalQkNorm(C.Structure):
+    """One layer's q_norm.weight / k_norm.weight: device pointers to [head_dim] f32."""
+    _fields_ = [("q_norm_g", c_void_p), ("k_norm_g", c_void_p)]
+
+
 class OmEncoderWeights(C.Structure):
     _fields_ = [("word_emb", c_void_p), ("pos_emb", c_void_p), ("type_emb", c_void_p),
                 ("emb_ln_g", c_void_p), ("emb_ln_b", c_void_p),
@@ -130,6 +140,13 @@ _SIGNATURES = {
     "om_debug_rope_gqa": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, C.POINTER(c_float), c_float, c_void_p]),
     "om_debug_attention_causal_packed": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
     "om_debug_rope_gqa_rows": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, C.POINTER(c_float), c_float, c_void_p, c_void_p]),
+    "om_debug_attention_causal_hd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "om_debug_attention_causal_hd_packed": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float,
+                                                    c_void_p]),
+    "om_debug_qknorm_rope": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(c_float),
+                                     c_float, c_void_p]),
+    "om_debug_qknorm_rope_rows": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(c_float),
+                                          c_float, c_void_p, c_void_p]),
     "om_debug_mask_extent": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_debug_attention_last": (c_int, []),
@@ -163,6 +180,13 @@ _SIGNATURES = {
     "om_causal_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmCausalConfig), c_int64, c_int64, c_int64]),
     "om_causal_encoder_forward_packed": (c_int, [C.POINTER(OmCausalConfig), C.POINTER(OmEncoderWeights), c_void_p, c_void_p, c_int64, c_int64,
                                                  c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_causal2_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmCausalConfig2), c_int64, c_int64]),
+    "om_causal2_encoder_forward": (c_int, [C.POINTER(OmCausalConfig2), C.POINTER(OmEncoderWeights), C.POINTER(OmCausalQkNorm), c_void_p, c_void_p,
+                                           c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_causal2_encoder_packed_supported": (c_int, [C.POINTER(OmCausalConfig2), c_int64, c_int64, c_int64]),
+    "om_causal2_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmCausalConfig2), c_int64, c_int64, c_int64]),
+    "om_causal2_encoder_forward_packed": (c_int, [C.POINTER(OmCausalConfig2), C.POINTER(OmEncoderWeights), C.POINTER(OmCausalQkNorm), c_void_p,
+                                                  c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_encoder_packed_supported": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int64, c_int64, c_int64]),
     "om_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64, c_int64]),
     "om_encoder_forward_packed": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p,

@@ -25,7 +25,8 @@ from types import SimpleNamespace as NS
 
 DEV = "cuda:0"
 SHAPES = {"qwen2-0.5b": dict(kind="qwen2", layers=24, hidden=896, heads=14, kv=2, ffn=4864, vocab=151936),
-          "llama-3.2-1b": dict(kind="llama", layers=16, hidden=2048, heads=32, kv=8, ffn=8192, vocab=128256)}
+          "llama-3.2-1b": dict(kind="llama", layers=16, hidden=2048, heads=32, kv=8, ffn=8192, vocab=128256),
+          "qwen3-embedding-0.6b": dict(kind="qwen3", layers=28, hidden=1024, heads=16, kv=8, head_dim=128, ffn=3072, vocab=151669)}
 
 
 def _timed(fn, iters):
@@ -64,12 +65,13 @@ def _steps_ms(fn, iters):
 
 
 def _model(s, dtype="bfloat16"):
-    from transformers import LlamaConfig, LlamaModel, Qwen2Config, Qwen2Model
+    from transformers import LlamaConfig, LlamaModel, Qwen2Config, Qwen2Model, Qwen3Config, Qwen3Model
     from openmatch.modeling import DRModelForInference
     torch.manual_seed(0)
-    ccls, mcls = (LlamaConfig, LlamaModel) if s["kind"] == "llama" else (Qwen2Config, Qwen2Model)
+    ccls, mcls = {"llama": (LlamaConfig, LlamaModel), "qwen2": (Qwen2Config, Qwen2Model), "qwen3": (Qwen3Config, Qwen3Model)}[s["kind"]]
+    extra = {"head_dim": s["head_dim"]} if "head_dim" in s else {}
     cfg = ccls(hidden_size=s["hidden"], num_hidden_layers=s["layers"], num_attention_heads=s["heads"], num_key_value_heads=s["kv"],
-               intermediate_size=s["ffn"], vocab_size=s["vocab"], max_position_embeddings=8192, pad_token_id=0)
+               intermediate_size=s["ffn"], vocab_size=s["vocab"], max_position_embeddings=8192, pad_token_id=0, **extra)
     with torch.device(DEV):              # (initialised on the device: 1.2 G parameters take a while on the host)
         lm = mcls(cfg).eval()
     return DRModelForInference(lm_q=lm, lm_p=lm, pooling="last", normalize=True,
@@ -92,7 +94,33 @@ def _ragged_batch(B, L, vocab, packed):
     return x, int(lens.sum())
 
 
+def _kernels_d128(s, B, L, iters):
+    """The 128-wide causal kernel and the q / k norm + rotation pass alone, beside the 64-wide causal kernel on a case of equal FLOPs
+    and bytes: twice the heads (and K / V heads) of half the width."""
+    from openmatch_amd import native as N
+    lib, st = N.lib(), N.stream_ptr()
+    heads, kv, D = s["heads"], s["kv"], 128
+    x = torch.randn(B * L, (heads + 2 * kv) * D, generator=torch.Generator().manual_seed(2)).to(torch.bfloat16).to(DEV)
+    mask = torch.ones(B, L, dtype=torch.int64, device=DEV)
+    ctx = torch.empty(B * L, heads * D, dtype=torch.bfloat16, device=DEV)
+    kmax = torch.empty(B, dtype=torch.int32, device=DEV)
+    g = torch.ones(D, device=DEV)
+    inv = (C.c_float * 64)(*[float(t) for t in 1.0 / (1000000.0 ** (torch.arange(0, D, 2).float() / D))])
+    run = lambda rc: N.check(rc)                                                                            # noqa: E731
+    out = {}
+    out["extent"] = _events_us(lambda: run(lib.om_debug_mask_extent(N.ptr(mask), B, L, N.ptr(kmax), st)), iters)
+    out["causal_d128"] = _events_us(lambda: run(lib.om_debug_attention_causal_hd(N.OM_BF16, N.ptr(x), N.ptr(ctx), N.ptr(mask), B, L, heads, kv, 128,
+                                                                                 128 ** -0.5, st)), iters) - out["extent"]
+    out["causal_d64_equal_flops"] = _events_us(lambda: run(lib.om_debug_attention_causal_hd(N.OM_BF16, N.ptr(x), N.ptr(ctx), N.ptr(mask), B, L, 2 * heads,
+                                                                                            2 * kv, 64, 0.125, st)), iters) - out["extent"]
+    out["qknorm_rope"] = _events_us(lambda: run(lib.om_debug_qknorm_rope(N.OM_BF16, N.ptr(x), B * L, L, heads, kv, 128, N.ptr(g), N.ptr(g), 1e-6, inv,
+                                                                         1.0, st)), iters)
+    return {k: round(t, 1) for k, t in out.items()}
+
+
 def _kernels(s, B, L, iters):
+    if s.get("head_dim") == 128:
+        return _kernels_d128(s, B, L, iters)
     from openmatch_amd import native as N
     lib, st = N.lib(), N.stream_ptr()
     heads, kv, D = s["heads"], s["kv"], 64
