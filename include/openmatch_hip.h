@@ -42,8 +42,8 @@ extern "C" {
 #define OM_ACT_GELU_ERF 1  /* HF "gelu"      (HF:activations.py GELUActivation)   */
 #define OM_ACT_RELU 2      /* HF "relu"      (T5 DenseReluDense)                  */
 #define OM_ACT_GELU_TANH 3 /* HF "gelu_new"  (T5 v1.1 gated act)                  */
-#define OM_ACT_SILU 5      /* HF "silu": OmCausalConfig.base.act only -- om_causal_encoder_forward applies it in an elementwise kernel of its
-                              own (silu(gate) * up); NOT a GEMM epilogue: om_gemm_nt does not take it (4 is internal to the training epilogues) */
+#define OM_ACT_SILU 5      /* HF "silu": OmCausalConfig.base.act and OM_ARCH_NOMICBERT only -- those forwards apply it in an elementwise kernel of
+                              their own (silu(gate) * up); NOT a GEMM epilogue: om_gemm_nt does not take it (4 is internal to the training epilogues) */
 #define OM_ACT_MUL_RESID 0x100 /* flag: multiply by `resid` instead of adding it (gated FFN) */
 #define OM_ACT_PRE_GRAD 0x200  /* flag (erf-GELU training epilogue, 16-bit output): `pre_act` receives gelu'(v) instead of the pre-activation
                                 * v -- the backward's dgrad then multiplies by it (OM_ACT_MUL_RESID) instead of evaluating gelu' */
@@ -61,6 +61,14 @@ extern "C" {
 
 #define OM_ARCH_CAUSAL 3 /* HF:models/llama/modeling_llama.py LlamaModel, HF:models/qwen2/modeling_qwen2.py Qwen2Model (inference only):
                           * OmCausalConfig.base.arch, served by om_causal_encoder_forward alone (om_encoder_forward refuses it as unknown) */
+
+#define OM_ARCH_NOMICBERT 4 /* HF:models/nomic_bert/modeling_nomic_bert.py NomicBertModel (nomic-embed-text-v1 / v1.5; inference only): the
+                            * post-LayerNorm stack of OM_ARCH_BERT on its four layer loops with three differences -- no linear layer has a bias
+                            * (every *_b is NULL), Q and K are rotated before attention (rotate_half pairs of 64-wide heads, theta in
+                            * rope_theta_global, position = the token's column), and the feed-forward is SwiGLU: ffn1_w is [2F, H] rows
+                            * gate_proj | up_proj (ONE contraction), down(silu(gate) * up) with ffn2_w [H, F].  The embedding is
+                            * LayerNorm(word + token type): pos_emb is NULL, max_pos bounds L only.  act = OM_ACT_SILU; head_dim 64; hidden and
+                            * ffn multiples of 64; rel_buckets and the other rotary / window fields are 0.  float16 as for OM_ARCH_BERT: nothing clamps. */
 
 /* pooling — modeling/dense_retrieval_model.py:145-150 */
 #define OM_POOL_NONE 0
@@ -193,6 +201,16 @@ int om_debug_attention_ex(int dtype, const void* qkv, void* ctx, const int64_t* 
                           const int* cu, int w);
 /* rotary positions in place on the Q and K columns of qkv [M, 3H], position = row % L (M need not be a multiple of L) */
 int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, void* stream);
+/* the same pass over packed rows (OM_ARCH_NOMICBERT under om_encoder_forward_packed): the position of row t is row_map[t] % L, rows with
+ * row_map[t] < 0 are left as they are (row_map [rows] as om_debug_pack_rows writes it) */
+int om_debug_rope_rows(int dtype, void* qkv, int64_t rows, int L, int H, float theta, const int* row_map, void* stream);
+/* SwiGLU of OM_ARCH_NOMICBERT: out[m, j] = silu(in[m, j]) * in[m, F + j] for M rows of in [M, 2F] (gate | up) into out [M, F], both of
+ * `dtype`; f32 arithmetic, silu(g) = g / (1 + exp(-g)), rounded once.  F a multiple of 64. */
+int om_debug_swiglu_rows(int dtype, const void* in, void* out, int64_t M, int F, void* stream);
+/* the embedding launch alone: LayerNorm(word[id] + type[tt] (+ pos[row % L])) into out [M, H] of `dtype`; type_ids, pos and type may be
+ * NULL (pos == NULL with a type table: OM_ARCH_NOMICBERT) */
+int om_debug_embed(int dtype, const int64_t* ids, const int64_t* type_ids, const float* word, const float* pos, const float* type,
+                   const float* g, const float* b, void* out, int64_t M, int L, int H, int vocab, int type_vocab, float eps, void* stream);
 /* Test hooks of the decoder-only stack (csrc/attention_causal.hip).  qkv is the grouped projection [rows, (n_heads + 2 n_kv_heads) * 64]
  * (q heads | k heads | v heads), ctx [rows, n_heads * 64]; query head h reads K / V head h / (n_heads / n_kv_heads).
  * om_debug_attention_causal: key k visible from query q iff k <= q and mask[b][k] != 0; it computes the key extents (one more small
@@ -256,6 +274,7 @@ int om_debug_attention_bwd_plan(int dtype, int64_t B, int L, int H, int heads, i
  * forward reads from the weights (layers_host[0].ffn1g_w, rel_bias); a type_emb table is assumed where type_vocab > 0.  Returns
  * path | few_rows << 8 | two << 9 | lo8 << 10 (few_rows: the contractions run on the few-rows kernel; two / lo8: the fused BERT path's
  * second residual plane, and that plane in eight bits), 0 for an empty batch, -1 for a refusal with its reason in om_last_error. */
+/* (OM_ARCH_NOMICBERT runs the four BERT loops under their codes) */
 #define OM_ENC_PATH_BERT_FUSED 1       /* LayerNorm fused across the contractions (16-bit, >= 512 rows, widths of 256)          */
 #define OM_ENC_PATH_BERT_PENDING_LN 2  /* few rows (<= OM_OPT_FEW_ROWS_LN_FUSE), f32 residual stream, LayerNorms inside the contractions */
 #define OM_ENC_PATH_BERT_FEW32 3       /* few rows (<= OM_OPT_GEMM_SKINNY_M), f32 residual stream, LayerNorms as kernels          */
@@ -314,8 +333,9 @@ int om_gemm_tn_acc_batch(int in_dtype, const OmTnProblem* problems, int n, int64
  * Encoder forward:  ids -> hidden [B,L,H] -> pooled/head/normalised reps [B,D]
  * Replaces  lm(**items) + pooling + head + F.normalize  in
  * modeling/dense_retrieval_model.py:133-155 (DRModel.encode), i.e. the whole
- * HF BertModel.forward (HF:models/bert/modeling_bert.py:623-684) or
- * T5Stack.forward (HF:models/t5/modeling_t5.py) in eval mode.
+ * HF BertModel.forward (HF:models/bert/modeling_bert.py:623-684),
+ * T5Stack.forward (HF:models/t5/modeling_t5.py), ModernBertModel.forward or
+ * NomicBertModel.forward (OM_ARCH_*) in eval mode.
  * ------------------------------------------------------------------------ */
 typedef struct OmLayerWeights {
   /* matrices: compute dtype (OM_F32 / OM_BF16 / OM_F16), [out,in] row-major */
@@ -323,9 +343,10 @@ typedef struct OmLayerWeights {
   const float* qkv_b;  /* [3H] or NULL (T5)                                       */
   const void* o_w;     /* [H,H]                                                   */
   const float* o_b;    /* [H] or NULL                                             */
-  const float* ln1_g;  /* BERT: attention.output.LayerNorm ; T5: layer[0].layer_norm ; ModernBERT: attn_norm (NULL in layer 0) */
+  const float* ln1_g;  /* BERT: attention.output.LayerNorm ; T5: layer[0].layer_norm ; ModernBERT: attn_norm (NULL in layer 0) ;
+                          NomicBERT: post_attention_layernorm (ln2: post_mlp_layernorm) */
   const float* ln1_b;  /* NULL for T5 (RMSNorm)                                   */
-  const void* ffn1_w;  /* [F,H]   BERT intermediate.dense / T5 wi (wi_0 if gated) */
+  const void* ffn1_w;  /* [F,H]   BERT intermediate.dense / T5 wi (wi_0 if gated) ; NomicBERT: [2F,H] rows gate_proj | up_proj */
   const float* ffn1_b; /* [F] or NULL                                             */
   const void* ffn1g_w; /* [F,H]   T5 v1.1 wi_1 (linear gate) or NULL ; ModernBERT: Wi rows F..2F-1 (ffn1_w: rows 0..F-1) */
   const void* ffn2_w;  /* [H,F]                                                   */
@@ -345,7 +366,7 @@ typedef struct OmEncoderConfig {
   int head_dim;      /* 64; BERT family: 32 or 64 (n_heads * head_dim == hidden)   */
   int ffn;           /* F                                                         */
   int vocab;
-  int max_pos;       /* BERT position table rows                                  */
+  int max_pos;       /* BERT position table rows ; NomicBERT: max_position_embeddings (bounds L; no table) */
   int type_vocab;    /* BERT token-type table rows; 0 with type_emb == NULL: word + position only (DistilBERT, MPNet) */
   int act;           /* OM_ACT_*                                                  */
   float ln_eps;      /* 1e-12 BERT, 1e-6 T5                                       */
@@ -355,8 +376,8 @@ typedef struct OmEncoderConfig {
   int head_in;       /* LinearHead input dim  (0 = no head)                       */
   int head_out;      /* LinearHead output dim                                     */
   int normalize;     /* F.normalize(reps, dim=1)                                  */
-  /* ---- ABI v6, OM_ARCH_MODERNBERT only (zero for BERT / T5) ---- */
-  float rope_theta_global; /* rope_parameters["full_attention"]["rope_theta"] (160 000)     */
+  /* ---- ABI v6, OM_ARCH_MODERNBERT (OM_ARCH_NOMICBERT: rope_theta_global alone, the rest zero; zero for BERT / T5) ---- */
+  float rope_theta_global; /* rope_parameters["full_attention"]["rope_theta"] (160 000) ; OM_ARCH_NOMICBERT: rope_parameters["rope_theta"] (1 000) */
   float rope_theta_local;  /* rope_parameters["sliding_attention"]["rope_theta"] (10 000)   */
   int half_window;         /* local_attention // 2: key k visible from query q iff |q - k| <= half_window (sliding layers) */
   uint64_t sliding_layers; /* bit l set: layer l is a sliding-window layer (config.layer_types[l] == "sliding_attention") */
@@ -364,7 +385,7 @@ typedef struct OmEncoderConfig {
 
 typedef struct OmEncoderWeights {
   const float* word_emb;  /* [vocab,H] f32                                        */
-  const float* pos_emb;   /* [max_pos,H] f32 (BERT)                               */
+  const float* pos_emb;   /* [max_pos,H] f32 (BERT); NULL: NomicBERT (rotary positions)       */
   const float* type_emb;  /* [type_vocab,H] f32 (BERT); NULL: no token types (DistilBERT, MPNet) */
   const float* emb_ln_g;  /* BERT embeddings.LayerNorm ; ModernBERT embeddings.norm */
   const float* emb_ln_b;
@@ -407,7 +428,7 @@ int om_encoder_forward(const OmEncoderConfig* cfg, const OmEncoderWeights* w,
  * the embedding, all contractions and the normalisations over `packed_rows` rows instead of B * L, attention per
  * sequence over its own rows, and pools from them: the representations om_encoder_forward returns, for
  * sum(lengths) / (B * L) of the work.  16-bit configurations with the fused path (hidden, ffn multiples of 256;
- * BERT-family: erf-GELU, float16 or bfloat16; T5 encoders: no gated feed-forward), L <= 1024 (round 6; was 256), pooling set (no out_hidden).
+ * BERT-family: erf-GELU, float16 or bfloat16; NomicBERT (a row's rotary position stays its token's column); T5 encoders: no gated feed-forward), L <= 1024 (round 6; was 256), pooling set (no out_hidden).
  * packed_rows: the caller's bound on the token count -- sum over sequences of (1 + index of the last unmasked token) --
  * rounded up to a multiple of 256, >= 512.  The bound is checked on the device: a batch that holds more tokens returns
  * NaN in every representation (no host synchronisation, never a truncated batch).

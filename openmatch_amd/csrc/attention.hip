@@ -605,6 +605,11 @@ extern "C" int om_debug_rope(int dtype, void* qkv, int64_t M, int L, int H, floa
   if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
   return omk_rope(dtype, qkv, M, L, H, theta, (hipStream_t)stream);
 }
+extern "C" int om_debug_rope_rows(int dtype, void* qkv, int64_t rows, int L, int H, float theta, const int* row_map, void* stream) {
+  if (!qkv || !row_map) OM_FAIL("null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
+  return omk_rope(dtype, qkv, rows, L, H, theta, (hipStream_t)stream, row_map);
+}
 extern "C" int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream) {
   if (!mask || !kmax) OM_FAIL("null argument");
   if (L < 1) OM_FAIL("mask extent: L must be at least 1");

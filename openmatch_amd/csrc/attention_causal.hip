@@ -1,7 +1,7 @@
 // Causal grouped-query attention of the decoder-only backbones (HF:models/llama/modeling_llama.py, HF:models/qwen2/modeling_qwen2.py),
 // and the rotary positions of every backbone that has them (gfx950), head_dim 64, inference.  Here: the two causal kernels -- wrappers of
 // the shared chunked bodies (attn_chunked.h) -- their launch and test hooks, and the ONE rotary kernel with its table cache and both of
-// its entries, omk_rope (ModernBERT, fused [M, 3H]) and omk_rope_gqa (grouped projection).
+// its entries, omk_rope (ModernBERT and NomicBERT, fused [M, 3H]) and omk_rope_gqa (grouped projection).
 //
 //   * Rotary positions applied IN PLACE to the q and k heads of a projection whose rows hold (q heads | k heads | v heads) of 64
 //     columns (apply_rotary_pos_emb with rotate_half: pairs (i, i + 32) of each head, position = row % L as HF's arange(L) whatever
@@ -27,6 +27,7 @@
 //   * Packed rows (om_causal_encoder_forward_packed): omk_attention_causal_packed runs the same two bodies with an AttnRows filled
 //     from cu -- sequence b is rows cu[b] .. cu[b + 1] - 1, the body's L is that row count, the mask keeps its [B, L] pitch -- and
 //     omk_rope_gqa with a row_map takes a row's position from row_map[t] % L (the column omk_pack_rows recorded) instead of row % L.
+//     omk_rope takes the same row_map (NomicBERT under om_encoder_forward_packed).
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -220,7 +221,7 @@ static int rope_launch(int dtype, void* qkv, int64_t M, int L, int rot_heads, in
   return 0;
 }
 
-int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s) {
+int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s, const int* row_map) {
   if (M <= 0) return 0;
   if (L < 1 || L > kRopeMaxPos) OM_FAIL("rotary positions: sequence length must be in [1,1024]");
   if (H % 64 || !(theta > 0.f)) OM_FAIL("rotary positions: head_dim 64 and a positive theta");
@@ -230,7 +231,7 @@ int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStre
     const float p = (float)pow((double)theta, (double)e);                   // theta ** e, rounded to f32
     inv_freq[i] = 1.0f / p;                                                  // 1.0 / (...), f32
   }
-  return rope_launch(dtype, qkv, M, L, 2 * H / 64, 3 * H, inv_freq, 1.0f, s);
+  return rope_launch(dtype, qkv, M, L, 2 * H / 64, 3 * H, inv_freq, 1.0f, s, row_map);
 }
 
 int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s,

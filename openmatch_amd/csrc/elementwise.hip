@@ -192,7 +192,7 @@ int omk_ln_fold(int dtype, const void* W, const float* gamma, const float* beta,
   return 0;
 }
 
-// BERT: LN(word[id] + type[tt] + pos[t])  (HF:models/bert/modeling_bert.py:68-108).
+// BERT: LN(word[id] + type[tt] + pos[t])  (HF:models/bert/modeling_bert.py:68-108); any of the two tables may be missing.
 // T5  : word[id]                          (shared embedding, no norm).
 template <typename TOut, int MAX_VEC>
 __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void embed_kernel(
@@ -225,11 +225,15 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void embed_kernel(
       if (j < nvec && c < H) {
         float w[4], ty[4], p[4];
         Vec4<float>::load(word + id * H + c, w);
-        if (type) {
+        if (type && pos) {
           Vec4<float>::load(type + tt * H + c, ty);
           Vec4<float>::load(pos + (int64_t)t * H + c, p);
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[j][e] = (w[e] + ty[e]) + p[e];
+        } else if (type) {         // NomicBERT: word + token type, no position table (the positions are rotary)
+          Vec4<float>::load(type + tt * H + c, ty);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[j][e] = w[e] + ty[e];
         } else if (pos) {          // DistilBERT, MPNet: word + position, no token-type table
           Vec4<float>::load(pos + (int64_t)t * H + c, p);
 #pragma unroll
@@ -499,6 +503,60 @@ int omk_l2norm(const float* x, float* y, int64_t M, int D, hipStream_t s) {
   hipLaunchKernelGGL(l2norm_kernel, dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, x, y, M, D);
   OM_LAUNCH_CHECK();
   return 0;
+}
+
+// NomicBERT's SwiGLU (HF:models/nomic_bert/modeling_nomic_bert.py NomicBertMLP): the one FFN1 contraction leaves [M, 2F] rows of
+// (gate | up); out[m, j] = silu(in[m, j]) * in[m, F + j] in f32, rounded once, silu(g) = g / (1 + exp(-g)) (torch.nn.functional.silu).
+// One thread per 16-byte vector of the output; the input row is read, never written.
+template <typename T>
+__global__ __launch_bounds__(256) void swiglu_rows_kernel(const T* __restrict__ in, T* __restrict__ out, int64_t M, int F) {
+  constexpr int N = 16 / (int)sizeof(T);                 // elements per 16-byte vector
+  const int per_row = F / N;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M * per_row) return;
+  const int64_t m = i / per_row;
+  const int j = (int)(i % per_row) * N;
+  const T* gp = in + m * 2 * (int64_t)F + j;
+  const uint4 gq = *(const uint4*)gp, uq = *(const uint4*)(gp + F);
+  const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w}, uw[4] = {uq.x, uq.y, uq.z, uq.w};
+  uint32_t o[4];
+  auto act = [](float g, float u) { return g / (1.0f + expf(-g)) * u; };
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (sizeof(T) == 4) o[e] = __float_as_uint(act(__uint_as_float(gw[e]), __uint_as_float(uw[e])));
+    else o[e] = Half16<T>::pack2(act(Half16<T>::lo(gw[e]), Half16<T>::lo(uw[e])), act(Half16<T>::hi(gw[e]), Half16<T>::hi(uw[e])));
+  }
+  *(uint4*)(out + m * (int64_t)F + j) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+int omk_swiglu_rows(int dtype, const void* in, void* out, int64_t M, int F, hipStream_t s) {
+  if (F < 64 || F % 64) OM_FAIL("SwiGLU rows: the inner width must be a positive multiple of 64");
+  if (((uintptr_t)in | (uintptr_t)out) & 15) OM_FAIL("SwiGLU rows: 16-byte aligned buffers");
+  if (M <= 0) return 0;
+  const int64_t nvec = M * (F / (dtype == OM_F32 ? 4 : 8));
+  if ((nvec + 255) / 256 > 0x7fffffffLL) OM_FAIL("SwiGLU rows: too many rows for one launch");
+  const unsigned grid = (unsigned)((nvec + 255) / 256);
+  if (dtype == OM_BF16) hipLaunchKernelGGL(swiglu_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, M, F);
+  else if (dtype == OM_F16) hipLaunchKernelGGL(swiglu_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const f16_t*)in, (f16_t*)out, M, F);
+  else hipLaunchKernelGGL(swiglu_rows_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)in, (float*)out, M, F);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int om_debug_swiglu_rows(int dtype, const void* in, void* out, int64_t M, int F, void* stream) {
+  if (!in || !out) OM_FAIL("om_debug_swiglu_rows: null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("SwiGLU rows: dtype must be OM_F32, OM_BF16 or OM_F16");
+  if (M < 0) OM_FAIL("SwiGLU rows: a negative row count");
+  return omk_swiglu_rows(dtype, in, out, M, F, (hipStream_t)stream);
+}
+
+extern "C" int om_debug_embed(int dtype, const int64_t* ids, const int64_t* type_ids, const float* word, const float* pos, const float* type,
+                              const float* g, const float* b, void* out, int64_t M, int L, int H, int vocab, int type_vocab, float eps,
+                              void* stream) {
+  if (!ids || !word || !g || !b || !out) OM_FAIL("om_debug_embed: null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("embedding: dtype must be OM_F32, OM_BF16 or OM_F16");
+  if (L < 1 || vocab < 1 || (type && type_vocab < 1)) OM_FAIL("embedding: L, vocab and the type table's rows must be at least 1");
+  return omk_embed(dtype, ids, type_ids, word, pos, type, g, b, out, M, L, H, vocab, type_vocab, eps, 1, (hipStream_t)stream);
 }
 
 int omk_t5_bias(const float* table, const int* lut, float* out, int L, int heads, hipStream_t s) {

@@ -1,4 +1,4 @@
-// om_encoder_forward: the whole eval-mode encoder (BERT post-LN, T5 pre-RMSNorm or ModernBERT pre-LN stack)
+// om_encoder_forward: the whole eval-mode encoder (BERT post-LN -- NomicBERT on the same loops --, T5 pre-RMSNorm or ModernBERT pre-LN stack)
 // + pooling + LinearHead + normalise, as a fixed sequence of launches on ONE stream.
 // Stands in for DRModel.encode (modeling/dense_retrieval_model.py:133-155) and the HF model
 // it calls (HF:models/bert/modeling_bert.py:623-684 / HF:models/t5/modeling_t5.py T5Stack).
@@ -9,6 +9,7 @@
 //   x1  [M,H]   post-attention hidden (BERT)
 //   qkv [M,3H]  fused projection      ctx [M,H] attention output
 //   ff  [M,F]   FFN inner activation  ff2 [M,F] gate (T5 v1.1, ModernBERT)
+//   NomicBERT: ff [M,2F] holds (gate | up) of the one FFN1 contraction, ff2 [M,F] silu(gate) * up (omk_swiglu_rows), FFN2's operand
 #include <math.h>
 
 #include <stdlib.h>
@@ -28,11 +29,12 @@
 //                           [ffn1: W' (F x H)         | column sums (F f32)  | folded bias (F f32)], every part 256-byte aligned.
 // BERT: qkv of layer l is folded with LN2 of layer l-1 (layer 0's slot is unused), ffn1 with LN1 of layer l.
 // T5 (not gated): qkv with the layer's first RMSNorm weight (l >= 1), ffn1 with its second.
+// NomicBERT: as BERT, the ffn1 slot 2F rows tall ([gate; up] is one weight, one fold); no biases, so the folded bias is the beta term alone.
 namespace {
 struct FoldSlot { size_t w, cs, bf; };
 struct FoldLayout { size_t per_layer, total; FoldSlot qkv, ffn1; };
 FoldLayout fold_layout(const OmEncoderConfig* c) {
-  const size_t H = c->hidden, F = c->ffn;
+  const size_t H = c->hidden, F = enc_ffn1_cols(c);
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
   FoldLayout L;
@@ -60,8 +62,8 @@ extern "C" int om_encoder_fold_weights(const OmEncoderConfig* c, const OmEncoder
   const OmLayerWeights* Ls = w->layers_host;
   if (!Ls) OM_FAIL("layers_host is null");
   hipStream_t s = (hipStream_t)stream;
-  const int H = c->hidden, F = c->ffn;
-  const bool bert = c->arch == OM_ARCH_BERT;
+  const int H = c->hidden, F = enc_ffn1_cols(c);
+  const bool bert = enc_bert_family(c);
   for (int l = 0; l < c->n_layers; ++l) {
     char* base = (char*)blob + (size_t)l * L.per_layer;
     const OmLayerWeights& lw = Ls[l];
@@ -117,7 +119,8 @@ struct EncWs {
 static EncWs carve(const OmEncoderConfig* c, const EncPlan& p, int64_t B, int64_t L, int64_t packed_rows, char* base) {
   const bool half = c->dtype == OM_BF16 || c->dtype == OM_F16;
   const size_t es = half ? 2 : 4;
-  const size_t Mreal = (size_t)p.M, M = (size_t)p.Mp, H = c->hidden, F = c->ffn;
+  const size_t Mreal = (size_t)p.M, M = (size_t)p.Mp, H = c->hidden, F = c->ffn, F1 = enc_ffn1_cols(c);
+  const bool bertf = enc_bert_family(c);
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
   EncWs w;
@@ -126,8 +129,8 @@ static EncWs carve(const OmEncoderConfig* c, const EncPlan& p, int64_t B, int64_
   w.x1 = take(M * H * es);
   w.qkv = take(M * 3 * H * es);
   w.ctx = take(M * H * es);
-  w.ff = take(M * F * es);
-  w.ff2 = take(c->arch == OM_ARCH_T5 || c->arch == OM_ARCH_MODERNBERT ? M * F * es : 0);
+  w.ff = take(M * F1 * es);
+  w.ff2 = take(c->arch == OM_ARCH_T5 || c->arch == OM_ARCH_MODERNBERT || c->arch == OM_ARCH_NOMICBERT ? M * F * es : 0);
   w.pooled = (float*)take((size_t)B * H * 4);
   w.headout = (float*)take((size_t)B * (c->head_out > 0 ? c->head_out : 1) * 4);
   // relative-position bias [heads, L, L]: T5, and a BERT-family stack configured with a bucket table (MPNet: rel_buckets > 0)
@@ -140,7 +143,7 @@ static EncWs carve(const OmEncoderConfig* c, const EncPlan& p, int64_t B, int64_
   w.row_map = (int*)take(packed_rows > 0 ? (size_t)packed_rows * 4 : 0);
   w.final32 = (float*)take(half && c->pooling != OM_POOL_NONE ? (c->pooling == OM_POOL_FIRST ? (size_t)B : Mreal) * H * 4 : 0);
   const bool fuse = half && c->arch != OM_ARCH_MODERNBERT;   // fused-norm path (BERT LayerNorm / T5 RMSNorm; ModernBERT has none)
-  const size_t wide = std::max((size_t)3 * H, F);
+  const size_t wide = std::max((size_t)3 * H, F1);
   w.wfold = take(fuse ? wide * H * es : 0);
   w.colsum = (float*)take(fuse ? wide * 4 : 0);
   w.bfold = (float*)take(fuse ? wide * 4 : 0);
@@ -148,7 +151,7 @@ static EncWs carve(const OmEncoderConfig* c, const EncPlan& p, int64_t B, int64_
   w.stats1 = (float*)take(fuse ? (size_t)2 * c->n_layers * M * 8 : 0);
   w.stats2 = w.stats1 ? w.stats1 + (size_t)c->n_layers * M * 2 : nullptr;
   w.slots = (float*)take(fuse ? (size_t)2 * ((H + 255) / 256) * M * 8 : 0);
-  const bool two = fuse && c->arch == OM_ARCH_BERT;      // both 16-bit formats (round 6): the planes exist whether or not the switch uses them
+  const bool two = fuse && bertf;      // both 16-bit formats (round 6): the planes exist whether or not the switch uses them
   w.y_lo = take(two ? M * H * es : 0);
   w.x1_lo = take(two ? M * H * es : 0);
   w.r32a = (float*)take(p.alloc_few32 ? Mreal * H * 4 : 0);
@@ -182,7 +185,7 @@ extern "C" size_t om_encoder_workspace_bytes_packed(const OmEncoderConfig* cfg, 
 // (encoder.py packed_rows_apply).  Three clauses are STRICTER than the plan: (a), (b), (c).
 extern "C" int om_encoder_packed_supported(const OmEncoderConfig* c, int gated_ffn, int64_t B, int64_t L, int64_t packed_rows) {
   if (!c || B <= 0 || packed_rows <= 0) return 0;
-  if ((c->dtype != OM_BF16 && c->dtype != OM_F16) || (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5)) return 0;      // (what it keeps of rule 1)
+  if ((c->dtype != OM_BF16 && c->dtype != OM_F16) || (!enc_bert_family(c) && c->arch != OM_ARCH_T5)) return 0;      // (what it keeps of rule 1)
   const EncSwitches sw = encoder_switches();
   // (a) few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so only a
   // batch whose PADDED form is that small is sent back (B = 64, L = 128 with 1 024 real tokens would otherwise run the tile kernels
@@ -247,6 +250,7 @@ struct EncCall {
   const EncWs& ws;
   const float* posbias;   // the expanded relative-position bias (plan.rel_bias), else NULL
   const int* cu;          // packed rows: ws.cu, else NULL
+  const int* row_map;     // packed rows: ws.row_map (the token of each row: NomicBERT's rotary positions), else NULL
   void* out_hidden;
   hipStream_t s;
 };
@@ -274,6 +278,15 @@ struct EncStream {
   const OmEncoderConfig* c = k.c; const EncWs& ws = k.ws; const OmLayerWeights* Ls = k.w->layers_host; hipStream_t s = k.s;     \
   const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads;                                              \
   const int64_t B = k.B, L = k.L, M = k.p.M, Mg = k.p.Mg
+// NomicBERT on the four BERT loops: Q / K rotated in place after the QKV contraction; FFN1 is ONE contraction over (gate | up) -- F1 = 2F
+// columns, no activation -- and omk_swiglu_rows turns them into FFN2's operand ffa (all Mg rows: FFN2 contracts over every row it is
+// given); no biases (the weights' *_b are NULL).  BERT: F1 = F, act1 = the activation, ffa = ws.ff, and neither launch.
+#define NOMIC_LOCALS                                                                                                 \
+  const bool nomic = c->arch == OM_ARCH_NOMICBERT;                                                                   \
+  const int F1 = enc_ffn1_cols(c), act1 = nomic ? OM_ACT_NONE : c->act;                                             \
+  const void* const ffa = nomic ? ws.ff2 : ws.ff
+#define NOMIC_ROPE() do { if (nomic) RUN(omk_rope(dt, ws.qkv, M, (int)L, H, c->rope_theta_global, s, k.row_map)); } while (0)
+#define NOMIC_SWIGLU() do { if (nomic) RUN(omk_swiglu_rows(dt, ws.ff, ws.ff2, Mg, F, s)); } while (0)
 
 // LayerNorm fused across the GEMMs (16-bit, large batches): the LayerNorm outputs are never
 // written.  The GEMM that produces a pre-LayerNorm sum y also accumulates its row statistics; the
@@ -284,6 +297,7 @@ struct EncStream {
 // (attention under every path: head_dim 32 -> attention_d32.hip; L > 256 -> the key-chunked / online-softmax kernels)
 static int bert_fused(const EncCall& k, EncStream* out) {
   ENC_LOCALS;
+  NOMIC_LOCALS;
   const float scale = 1.0f / sqrtf((float)c->head_dim);
   const float inv_h = 1.0f / (float)H;
   // Two-plane residual stream (bfloat16): y1 = ws.y + ws.y_lo, y2 = ws.x1 + ws.x1_lo; the GEMMs that consume LN(y)
@@ -319,6 +333,7 @@ static int bert_fused(const EncCall& k, EncStream* out) {
       e.bias = bfp; e.ln_stats = st2p; e.ln_colsum = cs; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.reverse = OM_WALK();
       RUN(omk_gemm(dt, ws.x1, H, wf, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
     }
+    NOMIC_ROPE();
     RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, OM_WALK(), ws.kmax, k.cu));
     // ---- attention output + residual -> y1, statistics of LN1
     e = GemmEpilogue{};
@@ -336,18 +351,19 @@ static int bert_fused(const EncCall& k, EncStream* out) {
     RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st1, s));
     // ---- FFN1 on LN1(y1), folded
     const void* wf1; const float *cs1, *bf1;
-    RUN(folded_weights(c, k.w, l, true, lw.ffn1_w, lw.ln1_g, lw.ln1_b, lw.ffn1_b, F, H, ws.wfold, ws.colsum, ws.bfold, s, &wf1, &cs1, &bf1));
+    RUN(folded_weights(c, k.w, l, true, lw.ffn1_w, lw.ln1_g, lw.ln1_b, lw.ffn1_b, F1, H, ws.wfold, ws.colsum, ws.bfold, s, &wf1, &cs1, &bf1));
     e = GemmEpilogue{};
-    e.bias = bf1; e.act = c->act; e.ln_stats = st1; e.ln_colsum = cs1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
+    e.bias = bf1; e.act = act1; e.ln_stats = st1; e.ln_colsum = cs1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
     e.reverse = OM_WALK();
-    RUN(omk_gemm(dt, ws.y, H, wf1, H, dt, ws.ff, F, Mg, F, H, e, s));
+    RUN(omk_gemm(dt, ws.y, H, wf1, H, dt, ws.ff, F1, Mg, F1, H, e, s));
+    NOMIC_SWIGLU();
     // ---- FFN2 + LN1(y1) as the residual -> y2, statistics of LN2
     e = GemmEpilogue{};
     e.bias = lw.ffn2_b; e.resid = ws.y; e.ldr = H; e.rln_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
     e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
     if (two) { e.resid_lo = ws.y_lo; e.out_lo = ws.x1_lo; e.lo8 = lo8; }
     e.reverse = OM_WALK();
-    RUN(omk_gemm(dt, ws.ff, F, lw.ffn2_w, F, dt, ws.x1, H, Mg, H, F, e, s));
+    RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, ws.x1, H, Mg, H, F, e, s));
     RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
   }
 #undef OM_WALK
@@ -364,6 +380,7 @@ static int bert_fused(const EncCall& k, EncStream* out) {
 // the bits are those of bert_few32 -- test_few_rows_forward_*).
 static int bert_pending_ln(const EncCall& k, EncStream* out) {
   ENC_LOCALS;
+  NOMIC_LOCALS;
   const float scale = 1.0f / sqrtf((float)c->head_dim);
   float* const y_a = ws.y32;      // attention block's sum: ctx Wo^T + b + x
   float* const y_b = ws.r32b;     // feed-forward block's sum: ff W2^T + b + x1
@@ -375,6 +392,7 @@ static int bert_pending_ln(const EncCall& k, EncStream* out) {
     e.bias = lw.qkv_b; e.ln_eps = c->ln_eps;
     if (l) { e.a_ln32 = y_b; e.a_ln_g = Ls[l - 1].ln2_g; e.a_ln_b = Ls[l - 1].ln2_b; e.a_ln_stats_out = st2p; }
     RUN(omk_gemm(dt, ws.x, H, lw.qkv_w, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
+    NOMIC_ROPE();
     RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
     e = GemmEpilogue{};
     e.bias = lw.o_b; e.ldr = H; e.out32 = y_a; e.ln_eps = c->ln_eps;
@@ -382,13 +400,14 @@ static int bert_pending_ln(const EncCall& k, EncStream* out) {
     else e.resid32 = ws.r32a;
     RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.y, H, Mg, H, H, e, s));
     e = GemmEpilogue{};
-    e.bias = lw.ffn1_b; e.act = c->act; e.ln_eps = c->ln_eps;
+    e.bias = lw.ffn1_b; e.act = act1; e.ln_eps = c->ln_eps;
     e.a_ln32 = y_a; e.a_ln_g = lw.ln1_g; e.a_ln_b = lw.ln1_b; e.a_ln_stats_out = st1;
-    RUN(omk_gemm(dt, ws.x1, H, lw.ffn1_w, H, dt, ws.ff, F, Mg, F, H, e, s));
+    RUN(omk_gemm(dt, ws.x1, H, lw.ffn1_w, H, dt, ws.ff, F1, Mg, F1, H, e, s));
+    NOMIC_SWIGLU();
     e = GemmEpilogue{};
     e.bias = lw.ffn2_b; e.ldr = H; e.out32 = y_b; e.ln_eps = c->ln_eps;
     e.rln32 = y_a; e.rln32_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
-    RUN(omk_gemm(dt, ws.ff, F, lw.ffn2_w, F, dt, ws.y, H, Mg, H, F, e, s));
+    RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, ws.y, H, Mg, H, F, e, s));
   }
   const OmLayerWeights& last = Ls[c->n_layers - 1];
   void* dst = k.out_hidden ? k.out_hidden : (void*)ws.x;
@@ -405,20 +424,23 @@ static int bert_pending_ln(const EncCall& k, EncStream* out) {
 // the f32 copy and leave their sum in f32 (gemm_skinny.hip: resid32 / out32).  Rounds 4-5 kept one 16-bit plane here.
 static int bert_few32(const EncCall& k, EncStream* out) {
   ENC_LOCALS;
+  NOMIC_LOCALS;
   const float scale = 1.0f / sqrtf((float)c->head_dim);
   void* dst = ws.x;
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
     GEMM(ws.x, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, lw.qkv_b, nullptr, 0, OM_ACT_NONE);
+    NOMIC_ROPE();
     RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
     GemmEpilogue e = {};
     e.bias = lw.o_b; e.resid32 = ws.r32a; e.ldr = H; e.out32 = ws.y32;
     RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.y, H, Mg, H, H, e, s));                  // y32 = ctx Wo^T + b + x (f32)
     RUN(omk_layernorm_dual(dt, ws.y32, H, ws.x1, ws.r32b, H, lw.ln1_g, lw.ln1_b, M, H, c->ln_eps, s));
-    GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F, F, H, lw.ffn1_b, nullptr, 0, c->act);
+    GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F1, F1, H, lw.ffn1_b, nullptr, 0, act1);
+    NOMIC_SWIGLU();
     e = GemmEpilogue{};
     e.bias = lw.ffn2_b; e.resid32 = ws.r32b; e.ldr = H; e.out32 = ws.y32;
-    RUN(omk_gemm(dt, ws.ff, F, lw.ffn2_w, F, dt, ws.y, H, Mg, H, F, e, s));                // y32 = ff W2^T + b + x1 (f32)
+    RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, ws.y, H, Mg, H, F, e, s));                   // y32 = ff W2^T + b + x1 (f32)
     if (l == c->n_layers - 1 && k.out_hidden) dst = k.out_hidden;
     RUN(omk_layernorm_dual(dt, ws.y32, H, dst, ws.r32a, H, lw.ln2_g, lw.ln2_b, M, H, c->ln_eps, s));
   }
@@ -432,16 +454,19 @@ static int bert_few32(const EncCall& k, EncStream* out) {
 // final_norm's; a stack of no layers leaves the embedding output as it is.
 static int bert_plain(const EncCall& k, EncStream* out) {
   ENC_LOCALS;
+  NOMIC_LOCALS;
   const float scale = 1.0f / sqrtf((float)c->head_dim);
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
     if (l) RUN(omk_layernorm(dt, ws.y, H, ws.x, H, Ls[l - 1].ln2_g, Ls[l - 1].ln2_b, M, H, c->ln_eps, 0, s));
     GEMM(ws.x, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, lw.qkv_b, nullptr, 0, OM_ACT_NONE);
+    NOMIC_ROPE();
     RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, 0, ws.kmax));
     GEMM(ws.ctx, H, lw.o_w, H, ws.y, H, H, H, lw.o_b, ws.x, H, OM_ACT_NONE);
     RUN(omk_layernorm(dt, ws.y, H, ws.x1, H, lw.ln1_g, lw.ln1_b, M, H, c->ln_eps, 0, s));
-    GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F, F, H, lw.ffn1_b, nullptr, 0, c->act);
-    GEMM(ws.ff, F, lw.ffn2_w, F, ws.y, H, H, F, lw.ffn2_b, ws.x1, H, OM_ACT_NONE);
+    GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F1, F1, H, lw.ffn1_b, nullptr, 0, act1);
+    NOMIC_SWIGLU();
+    GEMM(ffa, F, lw.ffn2_w, F, ws.y, H, H, F, lw.ffn2_b, ws.x1, H, OM_ACT_NONE);
   }
   *out = EncStream{};
   if (c->n_layers > 0) *out = EncStream{ws.y, nullptr, 0, Ls[c->n_layers - 1].ln2_g, Ls[c->n_layers - 1].ln2_b, 0, ws.x};
@@ -600,7 +625,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   if (!Ls) OM_FAIL("layers_host is null");
   const EncPlan plan = encoder_plan_checked(EncPlanIn{c, B, L, packed_rows, out_hidden != nullptr, c->n_layers > 0 && Ls[0].ffn1g_w != nullptr,
                                                       w->rel_bias != nullptr, w->type_emb != nullptr}, encoder_switches());
-  const bool packed = packed_rows > 0, bert = c->arch == OM_ARCH_BERT;
+  const bool packed = packed_rows > 0, bert = enc_bert_family(c);
   if (om_option(OM_OPT_ENCODER_DEBUG) && plan.path && bert)
     fprintf(stderr, "om_encoder_forward: M=%ld fused_ln=%d packed=%d few_rows=%d pending_ln=%d L=%ld head_dim=%d rel_bias=%d\n", (long)plan.M,
             (int)(plan.path == OM_ENC_PATH_BERT_FUSED), (int)packed, (int)plan.few_rows, (int)(plan.path == OM_ENC_PATH_BERT_PENDING_LN), (long)L,
@@ -610,6 +635,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   if (plan.error) OM_FAIL(plan.error);
   if (c->arch == OM_ARCH_T5 && !w->final_ln_g) OM_FAIL("T5 needs rel_bias and final_ln_g");
   if (c->arch == OM_ARCH_MODERNBERT && (!w->emb_ln_g || !w->final_ln_g)) OM_FAIL("ModernBERT needs emb_ln_g and final_ln_g");
+  if (c->arch == OM_ARCH_NOMICBERT && (!w->type_emb || w->pos_emb || w->rel_bias)) OM_FAIL("NomicBERT needs type_emb and takes no pos_emb or rel_bias");
   if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
   const EncWs ws = carve(c, plan, B, L, packed_rows, (char*)workspace);
   if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
@@ -638,7 +664,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   else
     RUN(omk_embed(dt, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
 
-  const EncCall k = {c, w, attention_mask, B, L, plan, ws, plan.rel_bias ? ws.posbias : nullptr, packed ? ws.cu : nullptr, out_hidden, s};
+  const EncCall k = {c, w, attention_mask, B, L, plan, ws, plan.rel_bias ? ws.posbias : nullptr, packed ? ws.cu : nullptr, row_map, out_hidden, s};
   EncStream stream_out;
   switch (plan.path) {
     case OM_ENC_PATH_BERT_FUSED: RUN(bert_fused(k, &stream_out)); break;
@@ -667,6 +693,9 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   }
   return 0;
 }
+#undef NOMIC_SWIGLU
+#undef NOMIC_ROPE
+#undef NOMIC_LOCALS
 #undef ENC_LOCALS
 #undef GEMM
 #undef RUN

@@ -57,7 +57,16 @@ static const char* encoder_cfg_error(const OmEncoderConfig* c) {
   if (c->dtype == OM_F16 && c->arch == OM_ARCH_BERT && c->act != OM_ACT_GELU_ERF) return "float16 mode: erf-GELU BERT-family encoders only";
   if (c->dtype == OM_F16 && c->arch == OM_ARCH_T5 && c->act != OM_ACT_RELU && c->act != OM_ACT_GELU_TANH)
     return "float16 mode: T5 feed-forwards with ReLU or tanh-GELU only";
-  if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5 && c->arch != OM_ARCH_MODERNBERT) return "unknown arch";
+  if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5 && c->arch != OM_ARCH_MODERNBERT && c->arch != OM_ARCH_NOMICBERT) return "unknown arch";
+  // NomicBERT (inference): 64-wide rotated heads, SwiGLU over one [gate; up] contraction (omk_swiglu_rows: whole 64-column groups), no
+  // relative bias; all three formats -- float16 as for BERT: nothing clamps
+  if (c->arch == OM_ARCH_NOMICBERT) {
+    if (c->head_dim != 64 || c->n_heads * 64 != c->hidden) return "NomicBERT: only head_dim 64 with n_heads*64 == hidden is supported";
+    if (c->act != OM_ACT_SILU) return "NomicBERT: hidden_act must be \"silu\"";
+    if (!(c->rope_theta_global > 0.f)) return "NomicBERT: a positive rope theta";
+    if (c->rel_buckets != 0) return "NomicBERT: no relative position bias (rel_buckets must be 0)";
+    if (c->hidden % 64 || c->ffn % 64 || c->ffn < 64) return "NomicBERT: hidden and ffn must be multiples of 64";
+  }
   // ModernBERT (inference): 64-wide heads, the gated erf-GELU feed-forward (float16 included), at most 64 layers (sliding_layers bits)
   if (c->arch == OM_ARCH_MODERNBERT) {
     if (c->head_dim != 64 || c->n_heads * 64 != c->hidden) return "ModernBERT: only head_dim 64 with n_heads*64 == hidden is supported";
@@ -79,22 +88,27 @@ static const char* encoder_cfg_error(const OmEncoderConfig* c) {
   return nullptr;
 }
 
-// whether the four contractions of a layer run [rows, *] on the kernel that implements the fused-norm epilogues
-static bool enc_ln_fusable(int dt, int64_t rows, int H, int F) {
-  return omk_gemm_ln_fusable(dt, rows, H, H) && omk_gemm_ln_fusable(dt, rows, F, H) && omk_gemm_ln_fusable(dt, rows, 3 * H, H) &&
+// the BERT-family post-LayerNorm stacks: the four BERT loops serve both
+static inline bool enc_bert_family(const OmEncoderConfig* c) { return c->arch == OM_ARCH_BERT || c->arch == OM_ARCH_NOMICBERT; }
+// columns FFN1 writes: F, or NomicBERT's [gate; up] pair (2F; omk_swiglu_rows then leaves the F columns FFN2 contracts over)
+static inline int enc_ffn1_cols(const OmEncoderConfig* c) { return c->arch == OM_ARCH_NOMICBERT ? 2 * c->ffn : c->ffn; }
+
+// whether the four contractions of a layer run [rows, *] on the kernel that implements the fused-norm epilogues (F1: enc_ffn1_cols)
+static bool enc_ln_fusable(int dt, int64_t rows, int H, int F, int F1) {
+  return omk_gemm_ln_fusable(dt, rows, H, H) && omk_gemm_ln_fusable(dt, rows, F1, H) && omk_gemm_ln_fusable(dt, rows, 3 * H, H) &&
          omk_gemm_ln_fusable(dt, rows, H, F);
 }
 
 // whether the four contractions of a BERT layer take their pending-LayerNorm forms on the few-rows kernel at this shape (the
 // epilogues' addresses are tested for null only)
-static bool enc_pending_ln_ok(int dt, int64_t M, int H, int F, int act, int max_m) {
+static bool enc_pending_ln_ok(int dt, int64_t M, int H, int F, int F1, int act, int max_m) {
   static const float one = 1.f;
   GemmEpilogue a = {}, r = {};
   a.a_ln32 = &one; a.a_ln_g = &one; a.a_ln_b = &one;
   r.rln32 = &one; r.rln32_stats = &one; r.rln_g = &one; r.rln_b = &one; r.out32 = const_cast<float*>(&one);
   GemmEpilogue f = a;
   f.act = act;
-  return omk_gemm_skinny_ok(dt, dt, M, 3 * (int64_t)H, H, a, max_m) && omk_gemm_skinny_ok(dt, dt, M, F, H, f, max_m) &&
+  return omk_gemm_skinny_ok(dt, dt, M, 3 * (int64_t)H, H, a, max_m) && omk_gemm_skinny_ok(dt, dt, M, F1, H, f, max_m) &&
          omk_gemm_skinny_ok(dt, dt, M, H, H, r, max_m) && omk_gemm_skinny_ok(dt, dt, M, H, F, r, max_m);
 }
 
@@ -104,8 +118,8 @@ static EncPlan encoder_plan_checked(const EncPlanIn& in, const EncSwitches sw) {
   EncPlan p = {};
   auto run = [&](int path) { p.path = path; return p; };
   auto refuse = [&](const char* why) { p.error = why; return p; };
-  const int dt = c->dtype, H = c->hidden, F = c->ffn;
-  const bool half = dt == OM_BF16 || dt == OM_F16, packed = in.packed_rows > 0, bert = c->arch == OM_ARCH_BERT;
+  const int dt = c->dtype, H = c->hidden, F = c->ffn, F1 = enc_ffn1_cols(c);
+  const bool half = dt == OM_BF16 || dt == OM_F16, packed = in.packed_rows > 0, bert = enc_bert_family(c), nomic = c->arch == OM_ARCH_NOMICBERT;
   // 2. rows -- filled whatever is refused below: the workspace size of a call does not depend on whether the call would be taken.
   // 16-bit batches of >= 512 tokens are padded to whole 256-row tiles: the persistent GEMM generation (gemm_wide7.h) takes whole
   // tiles only.  Rows are independent in every contraction, so whatever the pad rows hold stays in the pad rows; every other kernel
@@ -130,7 +144,7 @@ static EncPlan encoder_plan_checked(const EncPlanIn& in, const EncSwitches sw) {
   // reference's own autocast deviation, and the unfused path keeps one plane)
   p.few_rows = !packed && half && p.M <= (int64_t)sw.skinny_m && !(dt == OM_BF16 && bert && p.M >= 512 && (sw.two_plane & 1) != 0);
   p.Mg = p.few_rows ? p.M : p.Mp;
-  const bool fusable = sw.fused_ln != 0 && !p.few_rows && c->n_layers > 0 && H % 8 == 0 && enc_ln_fusable(dt, p.Mg, H, F);
+  const bool fusable = sw.fused_ln != 0 && !p.few_rows && c->n_layers > 0 && H % 8 == 0 && enc_ln_fusable(dt, p.Mg, H, F, F1);
   // 5. ModernBERT: one loop, norms as kernels
   if (c->arch == OM_ARCH_MODERNBERT) {
     if (packed) return refuse("packed rows: not for ModernBERT (om_encoder_packed_supported is 0)");
@@ -146,14 +160,15 @@ static EncPlan encoder_plan_checked(const EncPlanIn& in, const EncSwitches sw) {
     return p;
   }
   // 7. BERT family
-  if (in.L > c->max_pos) return refuse("sequence longer than the position table");
+  if (in.L > c->max_pos) return refuse(nomic ? "NomicBERT: sequence longer than max_pos (max_position_embeddings)" : "sequence longer than the position table");
   // (a table without a bucket count, or the reverse, is an error, never a forward without the bias)
   if (in.has_rel_bias != (c->rel_buckets > 0)) return refuse("relative position bias: rel_bias and rel_buckets must be set together");
   if (in.has_type_emb && c->type_vocab <= 0) return refuse("token types: a type_emb table needs type_vocab > 0");      // (type_emb == NULL: word + position only)
   p.rel_bias = in.has_rel_bias;
   const bool plane = (sw.two_plane & (dt == OM_BF16 ? 1 : 2)) != 0;      // this format's bit of the two-plane switch
-  // 7a. LayerNorm fused across the contractions (16-bit, >= 512 rows, widths of 256, erf-GELU)
-  if (fusable && c->act == OM_ACT_GELU_ERF) {
+  // 7a. LayerNorm fused across the contractions (16-bit, >= 512 rows, widths of 256, erf-GELU; NomicBERT: its SiLU is no epilogue --
+  // FFN1 runs with OM_ACT_NONE over the 2F columns, which is the shape tested)
+  if (fusable && (c->act == OM_ACT_GELU_ERF || nomic)) {
     p.two = plane;
     p.lo8 = plane && dt == OM_F16 && (sw.two_plane & 4) ? 1 : 0;
     p.pingpong = sw.pingpong != 0;
@@ -163,7 +178,7 @@ static EncPlan encoder_plan_checked(const EncPlanIn& in, const EncSwitches sw) {
   // OM_OPT_FEW_ROWS_LN_FUSE rows where the few-rows kernel has the four epilogues; 7c. one normalisation kernel per site
   const bool few32 = p.few_rows && c->n_layers > 0 && plane;
   p.path = !few32 ? OM_ENC_PATH_BERT_PLAIN
-           : p.M <= (int64_t)sw.few_ln_fuse && enc_pending_ln_ok(dt, p.Mg, H, F, c->act, sw.skinny_m) ? OM_ENC_PATH_BERT_PENDING_LN
+           : p.M <= (int64_t)sw.few_ln_fuse && enc_pending_ln_ok(dt, p.Mg, H, F, F1, nomic ? OM_ACT_NONE : c->act, sw.skinny_m) ? OM_ENC_PATH_BERT_PENDING_LN
                                                                                                        : OM_ENC_PATH_BERT_FEW32;
   if (packed) return refuse("packed rows need the fused 16-bit path (hidden, ffn multiples of 256; erf-GELU)");
   return p;

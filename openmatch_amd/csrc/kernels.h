@@ -25,6 +25,8 @@ int omk_embed(int dtype, const int64_t* ids, const int64_t* type_ids, const floa
 int omk_pool(int dtype, const void* x, const int64_t* mask, float* out, int64_t B, int L, int H,
              int mode, hipStream_t s, const int* cu = nullptr /* packed rows: sequence b is rows cu[b] .. of x */);
 int omk_l2norm(const float* x, float* y, int64_t M, int D, hipStream_t s);
+// NomicBERT's SwiGLU (elementwise.hip): out[m, j] = silu(in[m, j]) * in[m, F + j], in [M, 2F] (gate | up) -> out [M, F]; F % 64 == 0
+int omk_swiglu_rows(int dtype, const void* in, void* out, int64_t M, int F, hipStream_t s);
 int omk_t5_bias(const float* table, const int* lut, float* out, int L, int heads, hipStream_t s);
 
 // softmax(scale * Q K^T + mask [+ pos_bias]) V for every (batch, head); qkv is the fused
@@ -43,7 +45,8 @@ int omk_attention_d32(const AttnPlan& p, int dtype, const void* qkv, void* ctx, 
 // ModernBERT (head_dim 64, inference): rotary positions on the Q and K columns of qkv in place (attention_causal.hip; position = row % L,
 // frequencies 1 / theta ** (2i / 64)), and attention where key k is visible from query q only if |q - k| <= w and k is unmasked
 // (attention_band.hip).  Key chunks outside a query block's band are not visited.
-int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s);
+int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStream_t s,
+             const int* row_map = nullptr /* packed rows (NomicBERT): the position of row t is row_map[t] % L, rows with row_map[t] < 0 are skipped */);
 int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
                        int w, const int* kmax, hipStream_t s);
 // Decoder-only backbones (attention_causal.hip, head_dim 64, inference): qkv is the grouped projection [M, (heads + 2 kv_heads) * 64]

@@ -1,5 +1,5 @@
 """Host side of the HIP encoder: turns a HF `BertModel` / `RobertaModel` / `DistilBertModel` / `MPNetModel` / `T5EncoderModel` /
-`ModernBertModel` / `LlamaModel` / `Qwen2Model` (the parameter
+`ModernBertModel` / `NomicBertModel` / `LlamaModel` / `Qwen2Model` (the parameter
 container the reference keeps in `DRModel.lm_q / lm_p`) into the packed device weights that
 `om_encoder_forward` (`om_causal_encoder_forward` for the decoder-only backbones) consumes, and launches it.
 
@@ -47,6 +47,8 @@ def inference_code(model, code, seq_len):
         return code
     cfg = getattr(model, "config", None)
     if _arch_of(model) == "causal":              # Llama / Qwen2: float16 and bfloat16 as asked (nothing clamps, as under the reference's autocast)
+        return code
+    if _arch_of(model) == "nomicbert":           # float16 under BERT's no-clamp statement: as asked
         return code
     if _arch_of(model) == "modernbert":          # the GeGLU feed-forward with erf-GELU: float16 as for erf-GELU BERT
         return code if getattr(cfg, "hidden_activation", None) == "gelu" else N.OM_BF16
@@ -135,6 +137,8 @@ def _arch_of(model):
         return "t5"
     if name.startswith("ModernBert"):    # ModernBertModel: pre-LayerNorm stack with rotary positions and sliding-window layers
         return "modernbert"
+    if name == "NomicBertModel":         # nomic-embed-text-v1 / v1.5: the post-LayerNorm BERT stack without biases, rotary Q / K, SwiGLU
+        return "nomicbert"
     if name in _CAUSAL_CLASSES:          # decoder-only backbones as encoders: pre-RMSNorm, rotary grouped-query CAUSAL attention, SwiGLU
         return "causal"
     # BertModel; RobertaModel / XLMRobertaModel (the BERT stack behind offset position ids); DistilBertModel (no token types);
@@ -143,8 +147,8 @@ def _arch_of(model):
     if flavour_of(model) is not None:
         return "bert"
     raise NotImplementedError(
-        f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder, ModernBERT and Llama / Qwen2 "
-        f"(head_dim 64, inference) / Qwen3 (head_dim 64 or 128, inference) backbones; got {name}")
+        f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder, ModernBERT, NomicBERT (NomicBertModel, "
+        f"inference) and Llama / Qwen2 (head_dim 64, inference) / Qwen3 (head_dim 64 or 128, inference) backbones; got {name}")
 
 
 def position_offset(model):
@@ -335,6 +339,72 @@ def _pack_modernbert(model, code, device):
     return pk
 
 
+def nomicbert_config_fields(cfg, model=None):
+    """The OmEncoderConfig fields of a `NomicBertModel` that do not depend on the compute format, after refusing (by name and limit,
+    before anything touches the device) what the HIP stack does not serve.  The theta is `rope_parameters["rope_theta"]`: the device
+    derives the default rope's frequencies 1 / theta ** (2i / 64) from it as NomicBertRotaryEmbedding does in f32, with cos / sin
+    unscaled -- so any other rope type, or a scaling other than 1, is refused.  max_pos bounds the sequence length only (there is no
+    position table)."""
+    name = "NomicBertModel"
+    heads, hidden, ffn = int(cfg.num_attention_heads), int(cfg.hidden_size), int(cfg.intermediate_size)
+    rp = getattr(cfg, "rope_parameters", None) or {}
+    rope_type = rp.get("rope_type", "default")
+    if rope_type != "default":
+        raise NotImplementedError(f"{name}: rope type {rope_type!r} is not supported by the HIP encoder; only default rope is")
+    scaling = float(getattr(getattr(model, "rotary_emb", None), "attention_scaling", 1.0))
+    if scaling != 1.0:
+        raise NotImplementedError(f"{name}: rotary attention_scaling must be 1; got {scaling}")
+    head_dim = getattr(cfg, "head_dim", None) or hidden // heads
+    if head_dim != 64 or heads * 64 != hidden:
+        raise NotImplementedError(f"{name}: only head_dim 64 with num_attention_heads * 64 == hidden_size is supported "
+                                  f"(got head_dim {head_dim}, {heads} heads, hidden_size {hidden})")
+    if cfg.hidden_act != "silu":
+        raise NotImplementedError(f"{name}: hidden_act must be 'silu'; got {cfg.hidden_act!r}")
+    if hidden % 64 or ffn % 64 or hidden > 2048:
+        raise NotImplementedError(f"{name}: hidden_size and intermediate_size must be multiples of 64, hidden_size at most 2048 "
+                                  f"(got {hidden}, {ffn}): the row kernels hold a row of at most 2048 columns")
+    theta = float(rp.get("rope_theta", getattr(cfg, "default_theta", 1000.0)))
+    if not theta > 0:
+        raise NotImplementedError(f"{name}: rope_theta must be positive; got {theta}")
+    return dict(arch=N.ARCH_NOMICBERT, hidden=hidden, n_layers=int(cfg.num_hidden_layers), n_heads=heads, head_dim=64, ffn=ffn,
+                vocab=int(cfg.vocab_size), max_pos=int(cfg.max_position_embeddings), type_vocab=int(cfg.type_vocab_size),
+                act=N.ACT_SILU, ln_eps=float(cfg.layer_norm_eps), rel_buckets=0, rel_max_dist=0, rope_theta_global=theta)
+
+
+def _pack_nomicbert(model, code, device):
+    """NomicBertModel: word and token-type tables and every LayerNorm in f32, the matrices in the compute dtype, no biases anywhere;
+    qkv_w = [q; k; v] and ffn1_w = [gate_proj; up_proj] ([2F, H]: ONE FFN1 contraction, split again by the SwiGLU pass), ffn2_w =
+    down_proj; ln1 = post_attention_layernorm, ln2 = post_mlp_layernorm."""
+    cfg = model.config
+    fields = nomicbert_config_fields(cfg, model)
+    wd = torch_dtype_of(code)
+    f32 = torch.float32
+    pk = _Packed()
+    w = pk.weights
+    emb = model.embeddings
+    w.word_emb = pk.dev(emb.word_embeddings.weight, f32, device)
+    w.type_emb = pk.dev(emb.token_type_embeddings.weight, f32, device)
+    w.emb_ln_g = pk.dev(emb.LayerNorm.weight, f32, device)
+    w.emb_ln_b = pk.dev(emb.LayerNorm.bias, f32, device)
+    layers = (N.OmLayerWeights * cfg.num_hidden_layers)()
+    for i, layer in enumerate(model.layers):
+        sa, mlp, lw = layer.self_attn, layer.mlp, layers[i]
+        projs = [sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight]
+        lw.qkv_w = pk.dev(torch.cat(projs, 0), wd, device, projs)
+        lw.o_w = pk.dev(sa.o_proj.weight, wd, device)
+        lw.ln1_g = pk.dev(layer.post_attention_layernorm.weight, f32, device)
+        lw.ln1_b = pk.dev(layer.post_attention_layernorm.bias, f32, device)
+        gate_up = [mlp.gate_proj.weight, mlp.up_proj.weight]
+        lw.ffn1_w = pk.dev(torch.cat(gate_up, 0), wd, device, gate_up)
+        lw.ffn2_w = pk.dev(mlp.down_proj.weight, wd, device)
+        lw.ln2_g = pk.dev(layer.post_mlp_layernorm.weight, f32, device)
+        lw.ln2_b = pk.dev(layer.post_mlp_layernorm.bias, f32, device)
+    pk.layers = layers
+    w.layers_host = C.cast(layers, C.POINTER(N.OmLayerWeights))
+    pk.cfg = dict(dtype=code, **fields)
+    return pk
+
+
 def causal_config_fields(cfg, model):
     """The OmCausalConfig fields of a `LlamaModel` / `Qwen2Model` that do not depend on the compute format, after refusing (by name and
     limit, before anything touches the device) what the HIP stack does not serve.  The rotary frequencies and the cos / sin scaling
@@ -478,7 +548,7 @@ def causal_config(pk_cfg, pooling, normalize):
                             inv_freq=(C.c_float * 32)(*pk_cfg["inv_freq"]))
 
 
-_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert, "causal": _pack_causal}
+_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert, "causal": _pack_causal, "nomicbert": _pack_nomicbert}
 
 
 def _pack_t5_decoder(model, code, device):
@@ -685,7 +755,7 @@ LAST_CALL = {}       # what the most recent hip_encode ran on: {"rows": token ro
 
 def packed_rows_apply(cfg, B, L, rows, want_hidden, pooling, gated=False):
     """Whether om_encoder_forward_packed takes this call (include/openmatch_hip.h states the same conditions) and pays:
-    a 16-bit encoder on its fused path (BERT-family erf-GELU; T5 without a gated feed-forward), representations only, and
+    a 16-bit encoder on its fused path (BERT-family erf-GELU; NomicBERT; T5 without a gated feed-forward), representations only, and
     at least one 256-row tile saved.
     OM_ENCODER_PACKED=0 keeps every batch on the padded entry."""
     if os.environ.get("OM_ENCODER_PACKED", "1") == "0" or want_hidden or pooling is None:

@@ -15,7 +15,7 @@ OM_F32, OM_BF16, OM_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_GELU_TANH = 0, 1, 2, 3
 ACT_SILU = 5
 ACT_MUL_RESID = 0x100
-ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL = 0, 1, 2, 3
+ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL, ARCH_NOMICBERT = 0, 1, 2, 3, 4
 POOL_NONE, POOL_FIRST, POOL_MEAN, POOL_LAST = 0, 1, 2, 3
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
 OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
@@ -47,7 +47,7 @@ class OmEncoderConfig(C.Structure):
                 ("max_pos", c_int), ("type_vocab", c_int), ("act", c_int), ("ln_eps", c_float),
                 ("rel_buckets", c_int), ("rel_max_dist", c_int), ("pooling", c_int),
                 ("head_in", c_int), ("head_out", c_int), ("normalize", c_int),
-                # ABI v6 (ModernBERT; zero for BERT / T5)
+                # ABI v6 (ModernBERT; NomicBERT: rope_theta_global; zero for BERT / T5)
                 ("rope_theta_global", c_float), ("rope_theta_local", c_float), ("half_window", c_int),
                 ("sliding_layers", C.c_uint64)]
 
@@ -136,6 +136,10 @@ _SIGNATURES = {
     "om_debug_attention_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float,
                                       C.c_uint64, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "om_debug_rope": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "om_debug_rope_rows": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "om_debug_swiglu_rows": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "om_debug_embed": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                               c_int, c_int, c_float, c_void_p]),
     "om_debug_attention_causal": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
     "om_debug_rope_gqa": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, C.POINTER(c_float), c_float, c_void_p]),
     "om_debug_attention_causal_packed": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),

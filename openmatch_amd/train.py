@@ -229,6 +229,9 @@ def encode_train(model, head, items, pooling, normalize, code, training, packed_
     if _arch_of(model) == "modernbert":
         raise NotImplementedError("ModernBERT training is not supported by the HIP encoder (inference only: encode in eval "
                                   "mode under torch.no_grad())")
+    if _arch_of(model) == "nomicbert":
+        raise NotImplementedError("NomicBERT training is not supported by the HIP encoder (inference only: encode in eval "
+                                  "mode under torch.no_grad())")
     if type(model).__name__ == "Qwen3Model":
         raise NotImplementedError("Qwen3 training is not supported by the HIP encoder (inference only: encode in eval "
                                   "mode under torch.no_grad())")
