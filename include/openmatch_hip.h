@@ -269,6 +269,18 @@ int om_debug_attention_plan(int dtype, int64_t B, int L, int H, int heads, int h
 #define OM_ATTN_BWD_FAMILY_D32 4      /* attention_d32_bwd_kernel: 32-wide heads, up to 256 tokens                               */
 int om_debug_attention_bwd_last(void);
 int om_debug_attention_bwd_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, int has_drel, int has_cu, int packed);
+/* Test hook for the attention backward (tests/test_attention_bwd_kernels.py): every argument of the one backward entry, forwarded as
+ * given (the hook chooses no kernel; a refused call leaves the last-launch word 0).  qkv [rows, 3H] and dqkv [rows, 3H] (dq | dk | dv),
+ * dctx [rows, H] and ctx [rows, H] (the forward's output) of `dtype`; mask [B, L] int64; pos_bias [heads, L, L] f32 or NULL; drel
+ * [heads, 2L - 1] f32 or NULL: the gradient of the bias per relative position key - query + (L - 1), ACCUMULATED into what the buffer
+ * holds; ctx and stats (om_debug_attention_bwd_stats_bytes(B, heads) bytes of scratch) are read and written by the LONG family only and
+ * may be NULL for every other; cu [B + 2] (om_debug_pack_rows) or NULL, with packed != 0 for a step over packed rows: sequence b is rows
+ * cu[b] .. cu[b + 1] - 1, L stays the pitch of mask, pos_bias and drel, and rows of dqkv from cu[B] on are not written.  The dK / dV rows
+ * of a padded key are zero whenever its sequence has an unmasked key. */
+int om_debug_attention_bwd_ex(int dtype, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const int64_t* mask,
+                              const float* pos_bias, float* drel, float* stats, int64_t B, int L, int H, int heads, float scale,
+                              float drop_p, uint64_t seed, const int* cu, int packed, void* stream);
+size_t om_debug_attention_bwd_stats_bytes(int64_t B, int heads);
 /* host only (no GPU needed): which layer loop om_encoder_forward (packed_rows == 0) or om_encoder_forward_packed would run for this
  * call at the current switches (csrc/encoder_plan.h encoder_plan; DESIGN.md 4d lists the rules).  gated_ffn, has_rel_bias: what the
  * forward reads from the weights (layers_host[0].ffn1g_w, rel_bias); a type_emb table is assumed where type_vocab > 0.  Returns

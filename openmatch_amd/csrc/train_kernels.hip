@@ -1267,6 +1267,18 @@ int omk_attention_bwd(int dtype, const void* qkv, const void* ctx, const void* d
   }
 }
 
+// the backward entry alone (tests/test_attention_bwd_kernels.py): null checks, then every argument to omk_attention_bwd as given -- no
+// kernel choice here, attn_plan_bwd stays the one place a family is chosen
+extern "C" int om_debug_attention_bwd_ex(int dtype, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const int64_t* mask,
+                                         const float* pos_bias, float* drel, float* stats, int64_t B, int L, int H, int heads, float scale,
+                                         float drop_p, uint64_t seed, const int* cu, int packed, void* stream) {
+  g_attn_bwd_last = 0;
+  if (!qkv || !dctx || !dqkv || !mask) OM_FAIL("null argument");
+  return omk_attention_bwd(dtype, qkv, ctx, dctx, dqkv, mask, B, L, H, heads, scale, drop_p, seed, pos_bias, drel, stats, (hipStream_t)stream, cu,
+                           packed != 0);
+}
+extern "C" size_t om_debug_attention_bwd_stats_bytes(int64_t B, int heads) { return omk_attention_bwd_long_stats_bytes(B, heads); }
+
 // host only: what omk_attention_bwd would launch at the current switches -- family | key tiles << 8, 0 when nothing would launch, -1 for
 // a refusal (its reason in om_last_error); the last-launch words are not touched
 extern "C" int om_debug_attention_bwd_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, int has_drel, int has_cu, int packed) {

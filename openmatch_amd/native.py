@@ -157,6 +157,9 @@ _SIGNATURES = {
     "om_debug_attention_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int]),
     "om_debug_attention_bwd_last": (c_int, []),
     "om_debug_attention_bwd_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "om_debug_attention_bwd_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                          c_int, c_int, c_float, c_float, C.c_uint64, c_void_p, c_int, c_void_p]),
+    "om_debug_attention_bwd_stats_bytes": (c_size_t, [c_int64, c_int]),
     "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -42,7 +42,8 @@ SWITCHES, BAND, REFUSALS) that the CPU tests walk as well: test_forward_plan_nam
 (csrc/attn_plan.h, through om_debug_attention_plan, no GPU) for every case and expects the family, tile count or refusal the GPU case
 asserts, so the two cannot drift.  kt_of is this file's own statement of the tile rule.
 
-The attention backward kernels are not run here; their planner is walked against BWD_TABLE (test_backward_plan_matches_the_table), and
+The attention backward kernels are run, family by family against a float64 reference, in tests/test_attention_bwd_kernels.py, which
+imports this file's shared pieces; their planner is walked here against BWD_TABLE (test_backward_plan_matches_the_table), and
 the training tests of tests/test_gpu_parity.py assert through om_debug_attention_bwd_last() which of them each arm reached.
 """
 import contextlib
