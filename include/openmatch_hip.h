@@ -302,6 +302,51 @@ int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, 
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly
  * (out_shuffle[g]) and by its DPP / permlane form (out_dpp[g]); the two must agree bit for bit (tests/test_gpu_parity.py) */
 int om_debug_wave_sum_check(const float* in, float* out_shuffle, float* out_dpp, int64_t groups, void* stream);
+/* Test hooks for the row kernels (tests/test_row_kernels.py): normalisation forward and backward, pooling, L2 normalisation, dropout,
+ * the bias-gradient column sum, the LayerNorm fold and the two deterministic reductions.  Each checks its own pointers for NULL and
+ * its dtype (OM_F32 | OM_BF16 | OM_F16; om_debug_ln_fold and om_debug_layernorm_dual: the two 16-bit ones), then forwards EVERY
+ * argument to the internal launcher of the same name (csrc/kernels.h, csrc/train_kernels.h) and adds nothing of its own.
+ * Optional pointers (NULL allowed): b, x_lo, rows, add, dx_drop, db, dy32 / x32 (then dy / x may be NULL), partial (then dg may be
+ * NULL), partial_blocks, drop_rows, type_ids, type with dtype_, cu, beta, the fold's b.
+ * om_debug_row_kernel_last(): which kernel the calling thread's last normalisation launch ran -- one host store per launch, 0 after
+ * a hook call that launched nothing (a refusal, an empty problem):
+ *   forward : OM_ROW_FWD_GENERIC | OM_ROW_FWD_X8, NV (x8: 1..4) or MAX_VEC (generic: 4 | 8) << 4, input dtype << 8,
+ *             output dtype << 12, second plane read << 16, and that plane in eight bits << 17
+ *   backward: OM_ROW_LN_BWD, NV (3 | 4 | 8) << 4, MODE << 8, waves per block << 12, prefetch << 16, per-block partial sums << 17 */
+#define OM_ROW_FWD_GENERIC 1
+#define OM_ROW_FWD_X8 2
+#define OM_ROW_LN_BWD 3
+int om_debug_row_kernel_last(void);
+int om_debug_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
+                       float eps, int rms, const void* x_lo, int lo8, void* stream);
+int om_debug_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b, int64_t M,
+                              int H, float eps, int rms, const void* x_lo, const int* rows, int lo8, void* stream);
+int om_debug_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M,
+                                int H, float eps, int rms, void* stream);
+int om_debug_layernorm_dual(int dtype, const float* x, int64_t ldx, void* y, float* y32, int64_t ldy, const float* g, const float* b,
+                            int64_t M, int H, float eps, void* stream);
+int om_debug_norm_bwd(int dtype, const void* dy, const void* x, const float* g, void* dx, float* dg, float* db, int64_t M, int H,
+                      float eps, int rms, const void* add, void* stream);
+int om_debug_ln_bwd_drop(int dtype, const void* dy, const void* x, const float* g, void* dx, void* dx_drop, float drop_p,
+                         uint64_t drop_seed, float* dg, float* db, int64_t M, int H, float eps, const float* dy32, const float* x32,
+                         float* partial, int* partial_blocks /* host */, const int* drop_rows, void* stream);
+/* one LayerNorm site of om_debug_ln_param_reduce: dg[c] += sum over b < blocks of partial[b][0][c], db (may be NULL) likewise [1] */
+typedef struct OmLnSite { const float* partial; float* dg; float* db; int blocks; } OmLnSite;
+int om_debug_ln_param_reduce(const OmLnSite* sites /* host */, int n, int H, void* stream);
+int om_debug_embed_bwd(int dtype, const void* dy, const int64_t* ids, const int64_t* type_ids, const float* word, const float* pos,
+                       const float* type, const float* g, float* dword, float* dpos, float* dtype_, float* dg, float* db, int64_t M,
+                       int L, int H, int vocab, int type_vocab, float eps, const int* cu, void* stream);
+int om_debug_pool(int dtype, const void* x, const int64_t* mask, float* out, int64_t B, int L, int H, int mode, const int* cu,
+                  void* stream);
+int om_debug_pool_bwd(int dtype, const float* dp, const int64_t* mask, void* dh, int64_t B, int L, int H, int mode, const int* cu,
+                      void* stream);
+int om_debug_l2norm(const float* x, float* y, int64_t M, int D, void* stream);
+int om_debug_l2norm_bwd(const float* x, const float* dy, float* dx, int64_t M, int D, void* stream);
+int om_debug_colsum(int dtype, const void* x, int64_t ld, int64_t M, int N, float* out, void* stream);
+int om_debug_dropout(int dtype, const void* x, void* y, int64_t n, float p, uint64_t seed, const int* rows, int H, void* stream);
+int om_debug_ln_fold(int dtype, const void* W, const float* gamma, const float* beta, const float* b, void* Wf, float* colsum,
+                     float* bf, int N, int K, void* stream);
+int om_debug_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, void* stream);
 int om_kernel_timing_enable(int enable);
 int om_kernel_timing_read(int kernel_class, double* total_ms, int64_t* launches, double* flops);
 

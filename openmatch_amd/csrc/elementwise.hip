@@ -4,6 +4,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "ln_row.h"
+#include <type_traits>
 
 #define ROWS_PER_BLOCK 4
 #define MAX_VEC_LIMIT 8  // 4-element vectors per lane -> H <= 2048 (NV = 4 covers H <= 1024)
@@ -337,10 +338,19 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void index_to_f16_kernel(
 }
 
 // ---- host launchers ---------------------------------------------------------
+static thread_local int g_row_last = 0;      // the OM_ROW_* word of this thread's last normalisation launch (include/openmatch_hip.h)
+void omk_row_note(int word) { g_row_last = word; }
+extern "C" int om_debug_row_kernel_last(void) { return g_row_last; }
+template <typename T> constexpr int row_dt() { return sizeof(T) == 4 ? OM_F32 : (std::is_same<T, bf16_t>::value ? OM_BF16 : OM_F16); }
+static inline int row_fwd_word(int body, int nv, int tin, int tout, bool plane, bool lo8) {
+  return body | nv << 4 | tin << 8 | tout << 12 | (plane ? 1 << 16 : 0) | (plane && lo8 ? 1 << 17 : 0);
+}
+
 template <typename TIn, typename TOut>
 static int launch_ln(const void* x, int64_t ldx, void* y, int64_t ldy, const float* g,
                      const float* b, int64_t M, int H, float eps, int rms, hipStream_t s, const int* rows = nullptr) {
   const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+  omk_row_note(row_fwd_word(OM_ROW_FWD_GENERIC, H <= 1024 ? 4 : 8, row_dt<TIn>(), row_dt<TOut>(), false, false));
   if (H <= 1024)
     hipLaunchKernelGGL((layernorm_kernel<TIn, TOut, 4>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s,
                        (const TIn*)x, ldx, (TOut*)y, ldy, g, b, M, H, eps, rms, rows);
@@ -390,6 +400,7 @@ int omk_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_
 #define LN8F_(NV, TI) hipLaunchKernelGGL((layernorm_bf16x8_kernel<NV, float, TI>), dim3(grid), dim3(256), 0, s, (const TI*)x, ldx, \
                                     y, ldy, g, b, M, H, eps, rms, (const TI*)x_lo, rows, lo8)
 #define LN8F(NV) do { if (dtype == OM_BF16) LN8F_(NV, bf16_t); else LN8F_(NV, f16_t); } while (0)
+    omk_row_note(row_fwd_word(OM_ROW_FWD_X8, nv <= 1 ? 1 : nv, dtype, OM_F32, x_lo != nullptr, lo8 != 0));
     if (nv <= 1) LN8F(1); else if (nv == 2) LN8F(2); else if (nv == 3) LN8F(3); else LN8F(4);
 #undef LN8F
 #undef LN8F_
@@ -423,9 +434,10 @@ int omk_layernorm_dual(int dtype, const float* x, int64_t ldx, void* y, float* y
   const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
 #define LND(TO, MV) hipLaunchKernelGGL((layernorm_kernel<float, TO, MV>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, x, ldx, (TO*)y, ldy, g, b, M, \
                                        H, eps, 0, (const int*)nullptr, y32)
+  if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("a 16-bit output format");
+  omk_row_note(row_fwd_word(OM_ROW_FWD_GENERIC, H <= 1024 ? 4 : 8, OM_F32, dtype, false, false));
   if (dtype == OM_BF16) { if (H <= 1024) LND(bf16_t, 4); else LND(bf16_t, 8); }
-  else if (dtype == OM_F16) { if (H <= 1024) LND(f16_t, 4); else LND(f16_t, 8); }
-  else OM_FAIL("a 16-bit output format");
+  else { if (H <= 1024) LND(f16_t, 4); else LND(f16_t, 8); }
 #undef LND
   OM_LAUNCH_CHECK();
   return 0;
@@ -446,6 +458,7 @@ int omk_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, c
 #define LN8_(NV, TI) hipLaunchKernelGGL((layernorm_bf16x8_kernel<NV, TI, TI>), dim3(grid), dim3(256), 0, s, (const TI*)x, ldx, \
                                    (TI*)y, ldy, g, b, M, H, eps, rms, (const TI*)x_lo, (const int*)nullptr, lo8)
 #define LN8(NV) do { if (dtype == OM_BF16) LN8_(NV, bf16_t); else LN8_(NV, f16_t); } while (0)
+    omk_row_note(row_fwd_word(OM_ROW_FWD_X8, nv <= 1 ? 1 : nv, dtype, dtype, x_lo != nullptr, lo8 != 0));
     if (nv <= 1) LN8(1); else if (nv == 2) LN8(2); else if (nv == 3) LN8(3); else LN8(4);
 #undef LN8
 #undef LN8_
@@ -548,6 +561,58 @@ extern "C" int om_debug_swiglu_rows(int dtype, const void* in, void* out, int64_
   if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("SwiGLU rows: dtype must be OM_F32, OM_BF16 or OM_F16");
   if (M < 0) OM_FAIL("SwiGLU rows: a negative row count");
   return omk_swiglu_rows(dtype, in, out, M, F, (hipStream_t)stream);
+}
+
+// ---- test hooks of the row kernels (include/openmatch_hip.h): argument checks, then the launcher as it is ----
+#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+#define OM_DBG_DTYPE16(what) if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_BF16 or OM_F16")
+extern "C" int om_debug_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
+                                  float eps, int rms, const void* x_lo, int lo8, void* stream) {
+  omk_row_note(0);
+  if (!x || !y || !g) OM_FAIL("om_debug_layernorm: null argument");
+  OM_DBG_DTYPE("om_debug_layernorm");
+  return omk_layernorm(dtype, x, ldx, y, ldy, g, b, M, H, eps, rms, (hipStream_t)stream, x_lo, lo8);
+}
+extern "C" int om_debug_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b, int64_t M,
+                                         int H, float eps, int rms, const void* x_lo, const int* rows, int lo8, void* stream) {
+  omk_row_note(0);
+  if (!x || !y || !g) OM_FAIL("om_debug_layernorm_f32out: null argument");
+  OM_DBG_DTYPE("om_debug_layernorm_f32out");
+  return omk_layernorm_f32out(dtype, x, ldx, y, ldy, g, b, M, H, eps, rms, (hipStream_t)stream, x_lo, rows, lo8);
+}
+extern "C" int om_debug_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b,
+                                           int64_t M, int H, float eps, int rms, void* stream) {
+  omk_row_note(0);
+  if (!x || !y || !g) OM_FAIL("om_debug_layernorm_from_f32: null argument");
+  OM_DBG_DTYPE("om_debug_layernorm_from_f32");
+  return omk_layernorm_from_f32(dtype, x, ldx, y, ldy, g, b, M, H, eps, rms, (hipStream_t)stream);
+}
+extern "C" int om_debug_layernorm_dual(int dtype, const float* x, int64_t ldx, void* y, float* y32, int64_t ldy, const float* g, const float* b,
+                                       int64_t M, int H, float eps, void* stream) {
+  omk_row_note(0);
+  if (!x || !y || !y32 || !g) OM_FAIL("om_debug_layernorm_dual: null argument");
+  OM_DBG_DTYPE16("om_debug_layernorm_dual");
+  return omk_layernorm_dual(dtype, x, ldx, y, y32, ldy, g, b, M, H, eps, (hipStream_t)stream);
+}
+extern "C" int om_debug_pool(int dtype, const void* x, const int64_t* mask, float* out, int64_t B, int L, int H, int mode, const int* cu,
+                             void* stream) {
+  if (!x || !mask || !out) OM_FAIL("om_debug_pool: null argument");
+  OM_DBG_DTYPE("om_debug_pool");
+  return omk_pool(dtype, x, mask, out, B, L, H, mode, (hipStream_t)stream, cu);
+}
+extern "C" int om_debug_l2norm(const float* x, float* y, int64_t M, int D, void* stream) {
+  if (!x || !y) OM_FAIL("om_debug_l2norm: null argument");
+  return omk_l2norm(x, y, M, D, (hipStream_t)stream);
+}
+extern "C" int om_debug_ln_fold(int dtype, const void* W, const float* gamma, const float* beta, const float* b, void* Wf, float* colsum,
+                                float* bf, int N, int K, void* stream) {
+  if (!W || !gamma || !Wf || !colsum || !bf) OM_FAIL("om_debug_ln_fold: null argument");
+  OM_DBG_DTYPE16("om_debug_ln_fold");
+  return omk_ln_fold(dtype, W, gamma, beta, b, Wf, colsum, bf, N, K, (hipStream_t)stream);
+}
+extern "C" int om_debug_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, void* stream) {
+  if (!slots || !out) OM_FAIL("om_debug_ln_stats_reduce: null argument");
+  return omk_ln_stats_reduce(slots, nslots, M, out, (hipStream_t)stream);
 }
 
 extern "C" int om_debug_embed(int dtype, const int64_t* ids, const int64_t* type_ids, const float* word, const float* pos, const float* type,

@@ -27,6 +27,9 @@ int omk_pool(int dtype, const void* x, const int64_t* mask, float* out, int64_t 
 int omk_l2norm(const float* x, float* y, int64_t M, int D, hipStream_t s);
 // NomicBERT's SwiGLU (elementwise.hip): out[m, j] = silu(in[m, j]) * in[m, F + j], in [M, 2F] (gate | up) -> out [M, F]; F % 64 == 0
 int omk_swiglu_rows(int dtype, const void* in, void* out, int64_t M, int F, hipStream_t s);
+// which normalisation kernel the calling thread last launched (om_debug_row_kernel_last: the OM_ROW_* word of include/openmatch_hip.h):
+// one host store per launch
+void omk_row_note(int word);
 int omk_t5_bias(const float* table, const int* lut, float* out, int L, int heads, hipStream_t s);
 
 // softmax(scale * Q K^T + mask [+ pos_bias]) V for every (batch, head); qkv is the fused

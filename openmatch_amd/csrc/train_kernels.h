@@ -23,7 +23,7 @@ int omk_ln_bwd_drop(int dtype, const void* dy, const void* x, const float* g, vo
 // the second half of that: dg[c] += sum_b partial[b][0][c], db likewise, for n sites in one launch, in a fixed order
 #define OM_LNB_MAX_BLOCKS 512
 #define OM_LN_SITES_MAX 32
-struct OmLnSite { const float* partial; float* dg; float* db; int blocks; };
+// (OmLnSite: include/openmatch_hip.h, beside om_debug_ln_param_reduce)
 int omk_ln_param_reduce(const OmLnSite* sites, int n, int H, hipStream_t s);
 // LayerNorm (rms = 0) or T5 RMSNorm (rms = 1) backward; `add` (optional, same shape) is added to dx
 int omk_norm_bwd(int dtype, const void* dy, const void* x, const float* g, void* dx, float* dg,

@@ -472,12 +472,15 @@ static int launch_ln_bwd(const void* dy, const void* x, const float* g, void* dx
     grid = (unsigned)(L * parts);
   }
   const size_t lds = (size_t)2 * waves * H * sizeof(float);       // <= 64 KiB for both shapes
+  constexpr bool can_pf = MODE == 0 && sizeof(T) == 2;
+  // the prefetching body: bit 3 of the switch (A/B) takes it out; wider rows spill with it
+  const bool pf = can_pf && x32 && !dy32 && H <= 768 && (om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 8) == 0;
+  const int nv = (H <= 768 && MODE == 0) ? 3 : (H <= 1024 ? 4 : 8);
+  omk_row_note(OM_ROW_LN_BWD | nv << 4 | MODE << 8 | waves << 12 | (pf ? 1 << 16 : 0) | ((MODE == 0 && partial) ? 1 << 17 : 0));
 #define LNB_(NV, PF_) hipLaunchKernelGGL((ln_bwd_kernel<T, NV, MODE, PF_>), dim3(grid), dim3(64 * waves), lds, s, (const T*)dy, (const T*)x, g, (T*)dx, dg, db, M, H, eps, ids, tt, word, pos, type, dword, dpos, dtype_, L, vocab, type_vocab, rms, (const T*)add, (T*)dx_drop, drop_p, drop_seed, dy32, x32, partial, cu)
 #define LNB(NV) LNB_(NV, false)
-  constexpr bool can_pf = MODE == 0 && sizeof(T) == 2;
-  if (can_pf && x32 && !dy32 && H <= 768 && (om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 8) == 0) {        // (bit 3, A/B: no prefetch;
-    LNB_(3, can_pf);                                                                                   //  wider rows: the prefetch spills)
-  } else if (H <= 768 && MODE == 0) LNB(3);
+  if (pf) LNB_(3, can_pf);
+  else if (H <= 768 && MODE == 0) LNB(3);
   else if (H <= 1024) LNB(4);
   else LNB(8);
 #undef LNB
@@ -655,6 +658,59 @@ int omk_l2norm_bwd(const float* x, const float* dy, float* dx, int64_t M, int D,
   OM_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- test hooks of the row kernels (include/openmatch_hip.h): argument checks, then the launcher as it is ----
+#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+extern "C" int om_debug_norm_bwd(int dtype, const void* dy, const void* x, const float* g, void* dx, float* dg, float* db, int64_t M, int H,
+                                 float eps, int rms, const void* add, void* stream) {
+  omk_row_note(0);
+  if (!dy || !x || !g || !dx || !dg) OM_FAIL("om_debug_norm_bwd: null argument");
+  OM_DBG_DTYPE("om_debug_norm_bwd");
+  return omk_norm_bwd(dtype, dy, x, g, dx, dg, db, M, H, eps, rms, add, (hipStream_t)stream);
+}
+extern "C" int om_debug_ln_bwd_drop(int dtype, const void* dy, const void* x, const float* g, void* dx, void* dx_drop, float drop_p,
+                                    uint64_t drop_seed, float* dg, float* db, int64_t M, int H, float eps, const float* dy32, const float* x32,
+                                    float* partial, int* partial_blocks, const int* drop_rows, void* stream) {
+  omk_row_note(0);
+  if ((!dy && !dy32) || (!x && !x32) || !g || !dx || (!dg && !partial)) OM_FAIL("om_debug_ln_bwd_drop: null argument");
+  OM_DBG_DTYPE("om_debug_ln_bwd_drop");
+  return omk_ln_bwd_drop(dtype, dy, x, g, dx, dx_drop, drop_p, drop_seed, dg, db, M, H, eps, (hipStream_t)stream, dy32, x32, partial,
+                         partial_blocks, drop_rows);
+}
+extern "C" int om_debug_ln_param_reduce(const OmLnSite* sites, int n, int H, void* stream) {
+  if (!sites) OM_FAIL("om_debug_ln_param_reduce: null argument");
+  return omk_ln_param_reduce(sites, n, H, (hipStream_t)stream);
+}
+extern "C" int om_debug_embed_bwd(int dtype, const void* dy, const int64_t* ids, const int64_t* type_ids, const float* word, const float* pos,
+                                  const float* type, const float* g, float* dword, float* dpos, float* dtype_, float* dg, float* db, int64_t M,
+                                  int L, int H, int vocab, int type_vocab, float eps, const int* cu, void* stream) {
+  omk_row_note(0);
+  if (!dy || !ids || !word || !pos || !g || !dword || !dpos || !dg || (type && !dtype_)) OM_FAIL("om_debug_embed_bwd: null argument");
+  OM_DBG_DTYPE("om_debug_embed_bwd");
+  return omk_embed_bwd(dtype, dy, ids, type_ids, word, pos, type, g, dword, dpos, dtype_, dg, db, M, L, H, vocab, type_vocab, eps,
+                       (hipStream_t)stream, cu);
+}
+extern "C" int om_debug_pool_bwd(int dtype, const float* dp, const int64_t* mask, void* dh, int64_t B, int L, int H, int mode, const int* cu,
+                                 void* stream) {
+  if (!dp || !mask || !dh) OM_FAIL("om_debug_pool_bwd: null argument");
+  OM_DBG_DTYPE("om_debug_pool_bwd");
+  return omk_pool_bwd(dtype, dp, mask, dh, B, L, H, mode, (hipStream_t)stream, cu);
+}
+extern "C" int om_debug_l2norm_bwd(const float* x, const float* dy, float* dx, int64_t M, int D, void* stream) {
+  if (!x || !dy || !dx) OM_FAIL("om_debug_l2norm_bwd: null argument");
+  return omk_l2norm_bwd(x, dy, dx, M, D, (hipStream_t)stream);
+}
+extern "C" int om_debug_colsum(int dtype, const void* x, int64_t ld, int64_t M, int N, float* out, void* stream) {
+  if (!x || !out) OM_FAIL("om_debug_colsum: null argument");
+  OM_DBG_DTYPE("om_debug_colsum");
+  return omk_colsum(dtype, x, ld, M, N, out, (hipStream_t)stream);
+}
+extern "C" int om_debug_dropout(int dtype, const void* x, void* y, int64_t n, float p, uint64_t seed, const int* rows, int H, void* stream) {
+  if (!x || !y) OM_FAIL("om_debug_dropout: null argument");
+  OM_DBG_DTYPE("om_debug_dropout");
+  return omk_dropout(dtype, x, y, n, p, seed, (hipStream_t)stream, rows, H);
+}
+#undef OM_DBG_DTYPE
 
 // small f32 contractions (LinearHead backward, [B,768]-sized):
 //   nn: C[i,c] = sum_j A[i,j] * Bm[j,c]      tn: C[j,c] = sum_i A[i,j] * Bm[i,c]

@@ -105,6 +105,14 @@ class OmAdamTensor(C.Structure):
                 ("n", c_int64), ("weight_decay", c_float), ("shadow0_dtype", c_int), ("shadow1_dtype", c_int), ("reserved", c_int)]
 
 
+class OmLnSite(C.Structure):
+    """One LayerNorm site of om_debug_ln_param_reduce (include/openmatch_hip.h)."""
+    _fields_ = [("partial", c_void_p), ("dg", c_void_p), ("db", c_void_p), ("blocks", c_int)]
+
+
+# om_debug_row_kernel_last (include/openmatch_hip.h: OM_ROW_*)
+ROW_KERNEL = {"fwd_generic": 1, "fwd_x8": 2, "ln_bwd": 3}
+OPT_TRAIN_WGRAD_STREAM = 8
 ADAM_CHUNK = 16384
 
 
@@ -163,6 +171,30 @@ _SIGNATURES = {
     "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "om_debug_row_kernel_last": (c_int, []),
+    "om_debug_layernorm": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p,
+                                   c_int, c_void_p]),
+    "om_debug_layernorm_f32out": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int,
+                                          c_void_p, c_void_p, c_int, c_void_p]),
+    "om_debug_layernorm_from_f32": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int,
+                                            c_void_p]),
+    "om_debug_layernorm_dual": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float,
+                                        c_void_p]),
+    "om_debug_norm_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p,
+                                  c_void_p]),
+    "om_debug_ln_bwd_drop": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, C.c_uint64, c_void_p, c_void_p, c_int64,
+                                     c_int, c_float, c_void_p, c_void_p, c_void_p, C.POINTER(c_int), c_void_p, c_void_p]),
+    "om_debug_ln_param_reduce": (c_int, [C.POINTER(OmLnSite), c_int, c_int, c_void_p]),
+    "om_debug_embed_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "om_debug_pool": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "om_debug_pool_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "om_debug_l2norm": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "om_debug_l2norm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "om_debug_colsum": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "om_debug_dropout": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_float, C.c_uint64, c_void_p, c_int, c_void_p]),
+    "om_debug_ln_fold": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "om_debug_ln_stats_reduce": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "om_encoder_fold_bytes": (c_size_t, [C.POINTER(OmEncoderConfig)]),
     "om_encoder_fold_weights": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p, c_size_t, c_void_p]),
     "om_kernel_timing_enable": (c_int, [c_int]),
