@@ -118,6 +118,30 @@ int om_debug_gemm_last(void);
  * null), so the whole decision table can be walked with made-up addresses on a machine without a GPU. */
 int om_debug_gemm_plan(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,
                        int64_t M, int64_t N, int64_t K, const float* bias, const void* resid, int64_t ldr, int act);
+/* Test hooks for the epilogues om_gemm_nt cannot express (tests/test_gemm_epilogues.py): the fused-LayerNorm and two-plane epilogues of
+ * generation 7, the training epilogues (pre-activation tape, dropout; act may also be 4 = (acc + bias) * gelu'(resid), the backward
+ * through erf-GELU), the f32-stream and pending-LayerNorm extras of the few-rows kernel.  OmDebugGemmEpilogue mirrors the internal
+ * GemmEpilogue (csrc/kernels.h, which documents every field) except its trace pointer; zero-initialise it and set what the case needs.
+ * om_debug_gemm_ex copies the struct field by field and calls the internal omk_gemm with every argument unchanged -- it checks nothing
+ * but a NULL ep, so the planner's and the launchers' own refusals are what a test sees; om_debug_gemm_last() names the family.
+ * om_debug_gemm_plan_ex is om_debug_gemm_plan for such a call: the family, 0 for an empty problem, -1 for a refusal; launches nothing,
+ * reads every pointer as an address only.  om_debug_gemm_splitk forwards to the K-sliced weight-gradient contraction
+ * C (f32) += A[M, K] B[N, K]^T (f32 atomics; K * sizeof(in) % 128 == 0). */
+typedef struct OmDebugGemmEpilogue {
+  const float* bias; const void* resid; int64_t ldr; int act;
+  void* pre_act; int64_t ldp; float drop_p; uint64_t seed; const int* drop_rows;
+  const float* ln_stats; const float* ln_colsum; const float* rln_stats; const float* rln_g; const float* rln_b; float* stats_out;
+  const void* resid_lo; void* out_lo;
+  const float* resid32; float* out32;
+  const float* a_ln32; const float* a_ln_g; const float* a_ln_b; float* a_ln_stats_out; const float* rln32; const float* rln32_stats;
+  int lo8; float ln_inv_h, ln_eps; int ln_rms; int reverse;
+} OmDebugGemmEpilogue;
+int om_debug_gemm_ex(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,
+                     int64_t M, int64_t N, int64_t K, const OmDebugGemmEpilogue* ep, void* stream);
+int om_debug_gemm_plan_ex(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,
+                          int64_t M, int64_t N, int64_t K, const OmDebugGemmEpilogue* ep);
+int om_debug_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
+                         int64_t N, int64_t K, void* stream);
 /* Run-time switches for A/B measurements and tests (initialised from the environment variable of the same
  * name on first use): OM_OPT_ENCODER_FUSED_LN 1 = LayerNorm / RMSNorm fused across the encoder GEMMs where the
  * shapes allow (default), 0 = one normalisation kernel per site; OM_OPT_ENCODER_DEBUG 1 = log the path taken. */

@@ -156,6 +156,33 @@ extern "C" int om_debug_gemm_plan(int in_dtype, const void* A, int64_t lda, cons
   return p.error ? -1 : p.family;
 }
 
+// test hooks (openmatch_hip.h): the whole GemmEpilogue from C, field by field (everything but the trace pointer, which omk_gemm sets)
+static GemmEpilogue debug_epilogue(const OmDebugGemmEpilogue& d) {
+  GemmEpilogue ep = {};
+  ep.bias = d.bias; ep.resid = d.resid; ep.ldr = d.ldr; ep.act = d.act;
+  ep.pre_act = d.pre_act; ep.ldp = d.ldp; ep.drop_p = d.drop_p; ep.seed = d.seed; ep.drop_rows = d.drop_rows;
+  ep.ln_stats = d.ln_stats; ep.ln_colsum = d.ln_colsum; ep.rln_stats = d.rln_stats; ep.rln_g = d.rln_g; ep.rln_b = d.rln_b;
+  ep.stats_out = d.stats_out;
+  ep.resid_lo = d.resid_lo; ep.out_lo = d.out_lo;
+  ep.resid32 = d.resid32; ep.out32 = d.out32;
+  ep.a_ln32 = d.a_ln32; ep.a_ln_g = d.a_ln_g; ep.a_ln_b = d.a_ln_b; ep.a_ln_stats_out = d.a_ln_stats_out;
+  ep.rln32 = d.rln32; ep.rln32_stats = d.rln32_stats;
+  ep.lo8 = d.lo8; ep.ln_inv_h = d.ln_inv_h; ep.ln_eps = d.ln_eps; ep.ln_rms = d.ln_rms; ep.reverse = d.reverse;
+  return ep;
+}
+extern "C" int om_debug_gemm_ex(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,
+                                int64_t M, int64_t N, int64_t K, const OmDebugGemmEpilogue* ep, void* stream) {
+  if (!ep) OM_FAIL("om_debug_gemm_ex: null epilogue");
+  return omk_gemm(in_dtype, A, lda, B, ldb, out_dtype, C, ldc, M, N, K, debug_epilogue(*ep), (hipStream_t)stream);
+}
+extern "C" int om_debug_gemm_plan_ex(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C,
+                                     int64_t ldc, int64_t M, int64_t N, int64_t K, const OmDebugGemmEpilogue* ep) {
+  if (!ep) return -1;
+  const GemmPlan p = gemm_plan(in_dtype, (uintptr_t)A, lda, (uintptr_t)B, ldb, out_dtype, (uintptr_t)C, ldc, M, N, K, debug_epilogue(*ep),
+                               gemm_switches(g_debug_gen));
+  return p.error ? -1 : p.family;
+}
+
 int omk_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
                     int64_t ldc, int64_t M, int64_t N, int64_t K, hipStream_t s) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
@@ -190,6 +217,10 @@ int omk_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B, int
   if (timing) om_timing_end(tclass, s, 2.0 * (double)M * (double)N * (double)K);
   OM_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int om_debug_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
+                                    int64_t N, int64_t K, void* stream) {
+  return omk_gemm_splitk(in_dtype, A, lda, B, ldb, C, ldc, M, N, K, (hipStream_t)stream);
 }
 
 extern "C" int om_gemm_nt(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb,

@@ -43,8 +43,8 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 }
 // The same for 16-bit outputs, ~20 instructions instead of ~90 (libm erff + expf made the epilogue of the GELU-backward
 // contraction longer than its K = 768 main loop: 138 us per launch, profiles/r02_train_kernel_stats_v2.csv):
-// Phi(x) = 0.5 + xc Q(xc^2) with the degree-8 fit of gemm_epilogue6.h's forward (|error| <= 7.4e-6, xc = clamp(x, +-4.2)),
-// phi by the hardware exp2 (1 ulp).  |error| < 1e-5 against an output rounded to 2^-9.
+// Phi(x) = 0.5 + xc Q(xc^2) with the degree-8 fit of gemm_epilogue6.h's forward (|error| <= 1.33e-5, xc = clamp(x, +-4.2)),
+// phi by the hardware exp2 (1 ulp).  |error| <= 1.34e-5 against an output rounded to 2^-9.
 __device__ __forceinline__ float gelu_erf_grad_fast(float x) {
   const float xc = __builtin_amdgcn_fmed3f(x, -4.2f, 4.2f);
   const float t = xc * xc;

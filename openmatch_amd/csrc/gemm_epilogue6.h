@@ -23,7 +23,7 @@
 
 // erf-GELU for 16-bit outputs without transcendentals, two elements per instruction
 // (v_pk_mul_f32 / v_pk_fma_f32):  gelu(x) = x * (0.5 + h(xc)),  h(x) = 0.5 erf(x / sqrt 2) ~ x Q(x^2)
-// evaluated at xc = clamp(x, +-4.2), Q the degree-8 minimax fit (|h error| <= 7.4e-6) scaled so that
+// evaluated at xc = clamp(x, +-4.2), Q the degree-8 fit (|h error| <= 1.33e-5, largest at |x| = 2.23) scaled so that
 // h(4.2) = 0.5 (1 + 2e-7): beyond the clamp the factor is 1.0000001 / -1e-7, i.e. the tails are x and 0
 // to 1e-7 |x|.  |gelu error| <= 6e-5 for |x| <= 8 -- far inside a bf16 ulp.  13 instructions per two
 // elements.  The f32 output path keeps erff.

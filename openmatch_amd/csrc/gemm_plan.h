@@ -78,6 +78,8 @@ static GemmPlan gemm_plan(int in_dtype, uintptr_t A, int64_t lda, uintptr_t B, i
   if (sw.variant == 0 && sw.debug_gen == 0 && omk_gemm_skinny_ok(in_dtype, out_dtype, M, N, K, ep, sw.skinny_m)) return run(OM_GEMM_FAMILY_SKINNY);
   // 3. the f32-stream and pending-LayerNorm epilogues exist there only
   if (ep.resid32 || ep.out32 || ep.a_ln32 || ep.rln32) return refuse("f32 residual / f32 sum / pending-LayerNorm epilogue: the few-rows kernel only (gemm_skinny.hip)");
+  // a second plane exists in generation 7's output-side LayerNorm kernels only: every other family would drop it without a word
+  if ((ep.out_lo || ep.resid_lo) && p.lnf < 3) return refuse("two-plane residual stream: only with the output-side LayerNorm epilogue");
   // 4. the 256-row kernels write whole 16-byte output segments; small or ragged problems use v1
   const int64_t vec = out_dtype == OM_F32 ? 4 : 8;
   const bool wide = sw.variant != 1 && M >= 512 && N % vec == 0 && ldc % vec == 0 && (C & 15) == 0 &&

@@ -15,6 +15,7 @@ OM_F32, OM_BF16, OM_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_GELU_TANH = 0, 1, 2, 3
 ACT_SILU = 5
 ACT_MUL_RESID = 0x100
+ACT_GELU_ERF_GRAD, ACT_PRE_GRAD = 4, 0x200      # training epilogues (csrc/kernels.h; include/openmatch_hip.h), om_debug_gemm_ex only
 ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL, ARCH_NOMICBERT = 0, 1, 2, 3, 4
 POOL_NONE, POOL_FIRST, POOL_MEAN, POOL_LAST = 0, 1, 2, 3
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
@@ -105,6 +106,17 @@ class OmAdamTensor(C.Structure):
                 ("n", c_int64), ("weight_decay", c_float), ("shadow0_dtype", c_int), ("shadow1_dtype", c_int), ("reserved", c_int)]
 
 
+class OmDebugGemmEpilogue(C.Structure):
+    """Every field of the internal GemmEpilogue but its trace pointer (om_debug_gemm_ex / om_debug_gemm_plan_ex)."""
+    _fields_ = [("bias", c_void_p), ("resid", c_void_p), ("ldr", c_int64), ("act", c_int),
+                ("pre_act", c_void_p), ("ldp", c_int64), ("drop_p", c_float), ("seed", C.c_uint64), ("drop_rows", c_void_p),
+                ("ln_stats", c_void_p), ("ln_colsum", c_void_p), ("rln_stats", c_void_p), ("rln_g", c_void_p), ("rln_b", c_void_p),
+                ("stats_out", c_void_p), ("resid_lo", c_void_p), ("out_lo", c_void_p), ("resid32", c_void_p), ("out32", c_void_p),
+                ("a_ln32", c_void_p), ("a_ln_g", c_void_p), ("a_ln_b", c_void_p), ("a_ln_stats_out", c_void_p), ("rln32", c_void_p),
+                ("rln32_stats", c_void_p), ("lo8", c_int), ("ln_inv_h", c_float), ("ln_eps", c_float), ("ln_rms", c_int),
+                ("reverse", c_int)]
+
+
 class OmLnSite(C.Structure):
     """One LayerNorm site of om_debug_ln_param_reduce (include/openmatch_hip.h)."""
     _fields_ = [("partial", c_void_p), ("dg", c_void_p), ("db", c_void_p), ("blocks", c_int)]
@@ -140,6 +152,11 @@ _SIGNATURES = {
     "om_debug_gemm_last": (c_int, []),
     "om_debug_gemm_plan": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
                                    c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int]),
+    "om_debug_gemm_ex": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                 c_int64, c_int64, c_int64, C.POINTER(OmDebugGemmEpilogue), c_void_p]),
+    "om_debug_gemm_plan_ex": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                      c_int64, c_int64, c_int64, C.POINTER(OmDebugGemmEpilogue)]),
+    "om_debug_gemm_splitk": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "om_debug_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "om_debug_attention_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float,
                                       C.c_uint64, c_void_p, c_int, c_void_p, c_void_p, c_int]),

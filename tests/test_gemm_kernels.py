@@ -37,13 +37,14 @@ EPI = {
     "tanh": (N.ACT_GELU_TANH, True, None),
     "add": (N.ACT_NONE, True, "add"),
     "mul": (N.ACT_GELU_TANH, True, "mul"),
+    "none_mul": (N.ACT_NONE, True, "mul"),                    # the backward through GELU with a gelu' tape: (A B^T + bias) x resid
     "inplace": (N.ACT_NONE, True, "inplace"),
     # combinations of the ported self-test lists
     "erf_add": (N.ACT_GELU_ERF, True, "add"),
     "relu_add": (N.ACT_RELU, True, "add"),
     "mul_nobias": (N.ACT_GELU_TANH, False, "mul"),
 }
-MAIN_EPI = ["none", "bias", "erf", "relu", "tanh", "add", "mul", "inplace"]
+MAIN_EPI = ["none", "bias", "erf", "relu", "tanh", "add", "mul", "none_mul", "inplace"]
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -391,7 +392,7 @@ FAMILIES = {
     # generation 7 with the ring restarting per tile: bf16 sent there by bit 4 of OM_OPT_GEMM_CONT (bits 0 / 1 clear),
     # float16 by clearing bit 7 (every whole-tile f16 shape on the persistent kernel)
     "g7": (dict(cont=16, skinny_m=0), [(BF16, BF16)], ALL_EPI, [(512, 256, 3), (768, 512, 4), (512, 768, 48)]),
-    "g7-f16": (dict(cont=0, skinny_m=0), [(F16, F16)], ["none", "bias", "erf", "relu", "add", "inplace"],
+    "g7-f16": (dict(cont=0, skinny_m=0), [(F16, F16)], ["none", "bias", "erf", "relu", "add", "none_mul", "inplace"],
                [(512, 256, 1), (768, 512, 3), (512, 768, 48)]),
     "g7_one_tile": (dict(cont=511, skinny_m=0, gen=70), [(BF16, BF16)], ["none", "bias", "erf"],
                     [(512, 256, 3), (768, 512, 48)]),
@@ -399,9 +400,9 @@ FAMILIES = {
              [(512, 256, 3), (768, 512, 4), (512, 768, 48), (1024, 1024, 3)]),
     "7c16-f16": (dict(cont=495 & ~128, skinny_m=0), [(F16, F16)], ["none", "bias", "erf", "relu"],
                  [(512, 256, 3), (768, 512, 4), (512, 768, 48), (1024, 1024, 3)]),
-    "7r16": (dict(cont=511, skinny_m=0), [(BF16, BF16)], ["add", "mul", "inplace"],
+    "7r16": (dict(cont=511, skinny_m=0), [(BF16, BF16)], ["add", "mul", "none_mul", "inplace"],
              [(512, 256, 3), (768, 512, 4), (512, 768, 48), (1024, 1024, 3)]),
-    "7r16-f16": (dict(cont=495 & ~128, skinny_m=0), [(F16, F16)], ["add", "inplace"],
+    "7r16-f16": (dict(cont=495 & ~128, skinny_m=0), [(F16, F16)], ["add", "none_mul", "inplace"],
                  [(512, 256, 3), (768, 512, 4), (512, 768, 48), (1024, 1024, 3)]),
 }
 
