@@ -135,6 +135,7 @@ typedef struct OmDebugGemmEpilogue {
   const float* resid32; float* out32;
   const float* a_ln32; const float* a_ln_g; const float* a_ln_b; float* a_ln_stats_out; const float* rln32; const float* rln32_stats;
   int lo8; float ln_inv_h, ln_eps; int ln_rms; int reverse;
+  const int* rows_dev;   /* a row count in device memory: generation 7 skips the rows from roundup256(clamp(count, 0, M)) on; others ignore it */
 } OmDebugGemmEpilogue;
 int om_debug_gemm_ex(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,
                      int64_t M, int64_t N, int64_t K, const OmDebugGemmEpilogue* ep, void* stream);
@@ -209,7 +210,11 @@ int om_debug_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B
 #define OM_OPT_FEW_ROWS_LN_FUSE 21 /* round 6: 16-bit BERT forwards of at most this many token rows (default 64; env OM_FEW_ROWS_LN_FUSE; 0: off) launch no
                                       LayerNorm kernels between the embedding and the last layer: the contraction that consumes a LayerNorm's output
                                       normalises its operand rows itself, the one that adds it re-derives the element (gemm_skinny.hip; same bits) */
-#define OM_OPT_COUNT 22
+#define OM_OPT_ENCODER_SKIP_PAD 22  /* 1 (default; env OM_ENCODER_SKIP_PAD): om_encoder_forward skips a padded 16-bit batch's pad rows ON THE DEVICE where
+                                      om_debug_encoder_skip_pad says so -- the rows up to each sequence's last unmasked token are packed back to back by
+                                      a launch, and the persistent contractions read the token count from device memory (no copy to the host, no
+                                      synchronisation); the representations keep their bits.  0 (A/B, tests): every contraction runs over all B * L rows */
+#define OM_OPT_COUNT 23
 int om_debug_option(int opt, int value);
 /* the current value of a run-time switch (OM_OPT_*), so a test can restore exactly what it changed; -1 for an unknown option */
 int om_debug_option_value(int opt);
@@ -321,6 +326,11 @@ size_t om_debug_attention_bwd_stats_bytes(int64_t B, int heads);
 struct OmEncoderConfig;
 int om_debug_encoder_plan(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
                           int want_hidden);
+/* host only: 1 if om_encoder_forward (packed_rows == 0) would skip this call's pad rows on the device at the current switches
+ * (csrc/encoder_plan.h encoder_skip_pad): OM_OPT_ENCODER_SKIP_PAD is set, no hidden states are wanted, a pooling is set,
+ * the call plans OM_ENC_PATH_BERT_FUSED or OM_ENC_PATH_T5_FUSED, and om_encoder_packed_supported takes the bound roundup256(B * L).
+ * 0 otherwise (a call the forward refuses included), -1 for a NULL cfg.  The plan word above does not change with it. */
+int om_debug_encoder_skip_pad(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int want_hidden);
 /* host only: 1 if attention-probability dropout keeps (b, h, q, key) at rate p under `seed`; Lm is the mask's row pitch */
 int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, int q, int key, float p);
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly
@@ -495,7 +505,18 @@ int om_t5_relative_bucket(int relative_position, int num_buckets, int max_distan
  * collators produce them (dataset/data_collator.py:27-38,78-83); token_type_ids
  * may be NULL (treated as 0; always ignored for T5).
  * out_hidden: [B,L,H] in cfg->dtype, or NULL.  out_reps: f32 [B,D]
- * (D = head_out if head else H), or NULL when pooling == OM_POOL_NONE. */
+ * (D = head_out if head else H), or NULL when pooling == OM_POOL_NONE.
+ * Pad rows: a 16-bit call that returns representations only and plans a fused path (om_debug_encoder_skip_pad == 1) does not compute
+ * the rows past each sequence's last unmasked token.  It packs the remaining rows on the device as om_encoder_forward_packed does,
+ * with the bound roundup256(B * L), and its contractions read the token count from device memory: no copy to the host and no
+ * synchronisation, the same bits, the workspace of om_encoder_workspace_bytes.  The packing arrays (4 * (roundup256(B * L) + 2 B + 2)
+ * bytes) live in a buffer the library keeps per (device, stream); it is allocated by the first such call on a stream and grows only,
+ * and a call that would have to allocate it while its stream is capturing runs over all B * L rows instead.  What follows from that:
+ * the first call on a stream, and every call that grows the buffer, allocates and synchronises the device -- make it outside any
+ * stream capture of the process (it would invalidate a capture another thread has open in global mode); a graph captured with the
+ * skip keeps the buffer's address, shares the buffer with later eager calls on that stream, and must be replayed on the stream it
+ * was captured on; buffers are kept per stream handle for the life of the process (about 0.5 MB for the 1024 x 128 batch).
+ * OM_OPT_ENCODER_SKIP_PAD = 0 turns this off. */
 int om_encoder_forward(const OmEncoderConfig* cfg, const OmEncoderWeights* w,
                        const int64_t* input_ids, const int64_t* attention_mask,
                        const int64_t* token_type_ids, int64_t B, int64_t L,

@@ -116,6 +116,8 @@ void opt_init() {
   g_opt[OM_OPT_GEMM_SKINNY_M] = e ? atoi(e) : 1024;
   e = getenv("OM_FEW_ROWS_LN_FUSE");
   g_opt[OM_OPT_FEW_ROWS_LN_FUSE] = e ? atoi(e) : 64;
+  e = getenv("OM_ENCODER_SKIP_PAD");
+  g_opt[OM_OPT_ENCODER_SKIP_PAD] = e ? atoi(e) : 1;
   g_opt_init.store(true);
 }
 }  // namespace

@@ -15,6 +15,9 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 #include "encoder_plan.h"
@@ -182,27 +185,9 @@ extern "C" size_t om_encoder_workspace_bytes_packed(const OmEncoderConfig* cfg, 
 // OM_ENCODER_FUSED_LN = 0, OM_ATTENTION_FAST = 0, om_debug_gemm_gen) degrades a compact batch to the padded entry instead of failing
 // the call.  It asks with widths, format, activation and rows (no head counts, no pooling, no position table): rule 1 of
 // the plan is left to the forward but for format and arch, and the caller states its pooling and hidden-state wishes itself
-// (encoder.py packed_rows_apply).  Three clauses are STRICTER than the plan: (a), (b), (c).
+// (encoder.py packed_rows_apply).  The clauses, three of them STRICTER than the plan: encoder_plan.h encoder_packed_ok.
 extern "C" int om_encoder_packed_supported(const OmEncoderConfig* c, int gated_ffn, int64_t B, int64_t L, int64_t packed_rows) {
-  if (!c || B <= 0 || packed_rows <= 0) return 0;
-  if ((c->dtype != OM_BF16 && c->dtype != OM_F16) || (!enc_bert_family(c) && c->arch != OM_ARCH_T5)) return 0;      // (what it keeps of rule 1)
-  const EncSwitches sw = encoder_switches();
-  // (a) few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so only a
-  // batch whose PADDED form is that small is sent back (B = 64, L = 128 with 1 024 real tokens would otherwise run the tile kernels
-  // over all 8 192 padded rows: ADVICE r5)
-  if (B * L <= (int64_t)sw.skinny_m) return 0;
-  // (b) 64-wide bfloat16 heads without the 16-bit attention kernels: the forward would fail in its first attention launch
-  // (restates attn_plan.h; kept as it was written, 32-wide heads included, which attn_plan_fwd would take)
-  if (c->dtype == OM_BF16 && !sw.attention_fast) return 0;
-  // (c) float16 T5: ReLU only (the forward takes tanh-GELU as well)
-  if (c->arch == OM_ARCH_T5 && c->dtype == OM_F16 && c->act != OM_ACT_RELU) return 0;
-  // the call it plans: the fields the host may leave unset (it asks with widths, format and rows) are set so that they refuse nothing
-  OmEncoderConfig q = *c;
-  q.pooling = OM_POOL_FIRST;
-  q.max_pos = 1024;
-  const bool rel = c->arch == OM_ARCH_T5 || c->rel_buckets > 0;
-  const EncPlan p = encoder_plan_checked(EncPlanIn{&q, B, L, packed_rows, false, gated_ffn != 0, rel, false}, sw);
-  return p.path && !p.error ? 1 : 0;
+  return encoder_packed_ok(c, gated_ffn != 0, B, L, packed_rows, encoder_switches()) ? 1 : 0;
 }
 
 // host only: the plan of a forward at the current switches (include/openmatch_hip.h)
@@ -219,6 +204,17 @@ extern "C" int om_debug_encoder_plan(const OmEncoderConfig* c, int gated_ffn, in
     return -1;
   }
   return p.path | (int)p.few_rows << 8 | (int)p.two << 9 | p.lo8 << 10;
+}
+
+// host only: whether a padded forward would skip its pad rows on the device (include/openmatch_hip.h)
+extern "C" int om_debug_encoder_skip_pad(const OmEncoderConfig* c, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int want_hidden) {
+  if (!c) {
+    om_set_error("om_debug_encoder_skip_pad: null argument");
+    return -1;
+  }
+  const EncPlanIn in = {c, B, L, 0, want_hidden != 0, gated_ffn != 0, has_rel_bias != 0, c->type_vocab > 0};
+  const EncSwitches sw = encoder_switches();
+  return encoder_skip_pad(in, encoder_plan(in, sw), sw) ? 1 : 0;
 }
 
 extern "C" int om_t5_relative_bucket(int relative_position, int num_buckets, int max_distance) {
@@ -253,6 +249,8 @@ struct EncCall {
   const int* row_map;     // packed rows: ws.row_map (the token of each row: NomicBERT's rotary positions), else NULL
   void* out_hidden;
   hipStream_t s;
+  const int* rows_dev;    // a padded call that skips its pad rows: &cu[B], the token count on the device, for every contraction of the
+                          //   fused loops (GemmEpilogue::rows_dev); else NULL
 };
 
 // Where a layer loop left the stream that the last normalisation reads (final_norm below).
@@ -324,13 +322,13 @@ static int bert_fused(const EncCall& k, EncStream* out) {
     GemmEpilogue e = {};
     // ---- QKV: x0 for the first layer, LN2_{l-1}(y2) folded afterwards
     if (l == 0) {
-      e.bias = lw.qkv_b; e.reverse = OM_WALK();
+      e.bias = lw.qkv_b; e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
       RUN(omk_gemm(dt, ws.x, H, lw.qkv_w, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
     } else {
       const OmLayerWeights& pw = Ls[l - 1];
       const void* wf; const float *cs, *bfp;
       RUN(folded_weights(c, k.w, l, false, lw.qkv_w, pw.ln2_g, pw.ln2_b, lw.qkv_b, 3 * H, H, ws.wfold, ws.colsum, ws.bfold, s, &wf, &cs, &bfp));
-      e.bias = bfp; e.ln_stats = st2p; e.ln_colsum = cs; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.reverse = OM_WALK();
+      e.bias = bfp; e.ln_stats = st2p; e.ln_colsum = cs; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
       RUN(omk_gemm(dt, ws.x1, H, wf, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
     }
     NOMIC_ROPE();
@@ -346,7 +344,7 @@ static int bert_fused(const EncCall& k, EncStream* out) {
       e.resid = ws.x1; e.rln_stats = st2p; e.rln_g = pw.ln2_g; e.rln_b = pw.ln2_b;
       if (two) e.resid_lo = ws.x1_lo;
     }
-    e.reverse = OM_WALK();
+    e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
     RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.y, H, Mg, H, H, e, s));
     RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st1, s));
     // ---- FFN1 on LN1(y1), folded
@@ -354,7 +352,7 @@ static int bert_fused(const EncCall& k, EncStream* out) {
     RUN(folded_weights(c, k.w, l, true, lw.ffn1_w, lw.ln1_g, lw.ln1_b, lw.ffn1_b, F1, H, ws.wfold, ws.colsum, ws.bfold, s, &wf1, &cs1, &bf1));
     e = GemmEpilogue{};
     e.bias = bf1; e.act = act1; e.ln_stats = st1; e.ln_colsum = cs1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
-    e.reverse = OM_WALK();
+    e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
     RUN(omk_gemm(dt, ws.y, H, wf1, H, dt, ws.ff, F1, Mg, F1, H, e, s));
     NOMIC_SWIGLU();
     // ---- FFN2 + LN1(y1) as the residual -> y2, statistics of LN2
@@ -362,7 +360,7 @@ static int bert_fused(const EncCall& k, EncStream* out) {
     e.bias = lw.ffn2_b; e.resid = ws.y; e.ldr = H; e.rln_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
     e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
     if (two) { e.resid_lo = ws.y_lo; e.out_lo = ws.x1_lo; e.lo8 = lo8; }
-    e.reverse = OM_WALK();
+    e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
     RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, ws.x1, H, Mg, H, F, e, s));
     RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
   }
@@ -517,7 +515,7 @@ static int t5_fused(const EncCall& k, EncStream* out) {
     (void)cs; (void)bfp;            // RMSNorm: no mean, no shift -- only the folded weight is used
     GemmEpilogue e = {};
     e.act = act_; e.resid = res_; e.ldr = ldr_;
-    e.ln_stats = stats_; e.ln_rms = 1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
+    e.ln_stats = stats_; e.ln_rms = 1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.rows_dev = k.rows_dev;
     return omk_gemm(dt, A_, H, wf, H, dt, C_, N_, Mg, N_, H, e, s);
   };
   for (int l = 0; l < c->n_layers; ++l) {
@@ -526,18 +524,20 @@ static int t5_fused(const EncCall& k, EncStream* out) {
     float* st2 = ws.stats2 + (size_t)l * Mg * 2;                     // sum(x'^2): input of the next layer's first norm
     if (l == 0) {
       RUN(omk_layernorm(dt, ws.x, H, ws.y, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));
-      GEMM(ws.y, H, lw.qkv_w, H, ws.qkv, 3 * H, 3 * H, H, nullptr, nullptr, 0, OM_ACT_NONE);
+      GemmEpilogue e0 = {};            // (om_gemm_nt's plain epilogue, with the row count)
+      e0.rows_dev = k.rows_dev;
+      RUN(omk_gemm(dt, ws.y, H, lw.qkv_w, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e0, s));
     } else {
       RUN(folded(l, false, ws.x, lw.qkv_w, lw.ln1_g, ws.stats2 + (size_t)(l - 1) * Mg * 2, ws.qkv, 3 * H, OM_ACT_NONE, nullptr, 0));
     }
     RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, 1.0f, 0.f, 0, s, 0, ws.kmax, k.cu));
     GemmEpilogue e = {};
-    e.resid = ws.x; e.ldr = H; e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
+    e.resid = ws.x; e.ldr = H; e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.rows_dev = k.rows_dev;
     RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.x, H, Mg, H, H, e, s));           // x += o(ctx), sum(x^2)
     RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st1, s));
     RUN(folded(l, true, ws.x, lw.ffn1_w, lw.ln2_g, st1, ws.ff, F, c->act, nullptr, 0));      // (the plan excludes gated layers)
     e = GemmEpilogue{};
-    e.resid = ws.x; e.ldr = H; e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
+    e.resid = ws.x; e.ldr = H; e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.rows_dev = k.rows_dev;
     RUN(omk_gemm(dt, ws.ff, F, lw.ffn2_w, F, dt, ws.x, H, Mg, H, F, e, s));         // x += wo(ff), sum(x^2)
     RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
   }
@@ -612,6 +612,43 @@ int omk_pooled_tail(const OmEncoderConfig* c, const OmEncoderWeights* w, const f
   return 0;
 }
 
+// Pad rows skipped on the device (encoder_plan.h encoder_skip_pad): cu [B + 2] | cls_rows [B] | row_map [rows] of such a call.  They cannot
+// come from the caller's workspace -- om_encoder_workspace_bytes of a padded call is what it was -- so the library keeps one buffer
+// per (device, stream): calls on a stream are stream-ordered, so reusing it is safe; two streams get two buffers.  Grow-only and kept
+// for the life of the process, like the library's other device caches (om_t5_lut_device); growing waits for the device before it
+// frees.  A buffer that a capturing stream was handed is never freed (a captured graph replays its address): it is retired.
+// *out stays NULL -- the call then runs over all its rows -- when the buffer would have to be created or grown while `s` is capturing.
+// Limits (include/openmatch_hip.h states them for the caller): entries are never pruned, so a process keeps one buffer per distinct
+// stream handle it ever encoded on; growing synchronises the device and allocates, which invalidates a capture another thread has
+// open in global mode on another stream; a retired or captured buffer is shared by the graph's replays and later eager calls on that
+// stream, which is stream-ordered only if the graph is replayed on the stream it was captured on.
+static int skip_pad_buffer(hipStream_t s, size_t ints, int** out) {
+  struct Buf { int* p = nullptr; size_t n = 0; bool captured = false; };
+  static std::mutex mu;
+  static std::map<std::pair<int, hipStream_t>, Buf> bufs;
+  *out = nullptr;
+  int dev = 0;
+  OM_HIP(hipGetDevice(&dev));
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) {      // (cannot tell: as if capturing with nothing to hand out)
+    (void)hipGetLastError();
+    return 0;
+  }
+  const bool capturing = st != hipStreamCaptureStatusNone;
+  std::lock_guard<std::mutex> lk(mu);
+  Buf& b = bufs[std::make_pair(dev, s)];
+  if (b.n < ints) {
+    if (capturing) return 0;
+    if (b.p && !b.captured) { OM_HIP(hipDeviceSynchronize()); OM_HIP(hipFree(b.p)); }
+    b = Buf{};
+    OM_HIP(hipMalloc(&b.p, ints * sizeof(int)));
+    b.n = ints;
+  }
+  b.captured |= capturing;
+  *out = b.p;
+  return 0;
+}
+
 // plan, carve, the plan's layer loop, the last normalisation, pooling
 static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* w,
                                 const int64_t* input_ids, const int64_t* attention_mask,
@@ -623,30 +660,48 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   if (B <= 0) return 0;
   const OmLayerWeights* Ls = w->layers_host;
   if (!Ls) OM_FAIL("layers_host is null");
-  const EncPlan plan = encoder_plan_checked(EncPlanIn{c, B, L, packed_rows, out_hidden != nullptr, c->n_layers > 0 && Ls[0].ffn1g_w != nullptr,
-                                                      w->rel_bias != nullptr, w->type_emb != nullptr}, encoder_switches());
-  const bool packed = packed_rows > 0, bert = enc_bert_family(c);
+  const EncPlanIn plan_in = {c, B, L, packed_rows, out_hidden != nullptr, c->n_layers > 0 && Ls[0].ffn1g_w != nullptr, w->rel_bias != nullptr,
+                             w->type_emb != nullptr};
+  const EncSwitches sw = encoder_switches();
+  const EncPlan plan = encoder_plan_checked(plan_in, sw);
+  const bool bert = enc_bert_family(c);
   if (om_option(OM_OPT_ENCODER_DEBUG) && plan.path && bert)
     fprintf(stderr, "om_encoder_forward: M=%ld fused_ln=%d packed=%d few_rows=%d pending_ln=%d L=%ld head_dim=%d rel_bias=%d\n", (long)plan.M,
-            (int)(plan.path == OM_ENC_PATH_BERT_FUSED), (int)packed, (int)plan.few_rows, (int)(plan.path == OM_ENC_PATH_BERT_PENDING_LN), (long)L,
+            (int)(plan.path == OM_ENC_PATH_BERT_FUSED), (int)(packed_rows > 0), (int)plan.few_rows, (int)(plan.path == OM_ENC_PATH_BERT_PENDING_LN), (long)L,
             c->head_dim, (int)plan.rel_bias);
   if (om_option(OM_OPT_ENCODER_DEBUG) && plan.path && c->arch == OM_ARCH_T5)
-    fprintf(stderr, "om_encoder_forward (t5): M=%ld fused_norm=%d packed=%d\n", (long)plan.M, (int)(plan.path == OM_ENC_PATH_T5_FUSED), (int)packed);
+    fprintf(stderr, "om_encoder_forward (t5): M=%ld fused_norm=%d packed=%d\n", (long)plan.M, (int)(plan.path == OM_ENC_PATH_T5_FUSED), (int)(packed_rows > 0));
   if (plan.error) OM_FAIL(plan.error);
   if (c->arch == OM_ARCH_T5 && !w->final_ln_g) OM_FAIL("T5 needs rel_bias and final_ln_g");
   if (c->arch == OM_ARCH_MODERNBERT && (!w->emb_ln_g || !w->final_ln_g)) OM_FAIL("ModernBERT needs emb_ln_g and final_ln_g");
   if (c->arch == OM_ARCH_NOMICBERT && (!w->type_emb || w->pos_emb || w->rel_bias)) OM_FAIL("NomicBERT needs type_emb and takes no pos_emb or rel_bias");
   if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  const EncWs ws = carve(c, plan, B, L, packed_rows, (char*)workspace);
+  EncWs ws = carve(c, plan, B, L, packed_rows, (char*)workspace);
   if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
   if (c->pooling != OM_POOL_NONE && !out_reps) OM_FAIL("out_reps required when pooling is set");
   hipStream_t s = (hipStream_t)stream;
   const int dt = c->dtype, H = c->hidden;
   const int64_t M = plan.M;
+  // A padded call that skips its pad rows (encoder_skip_pad) IS the packed call with the bound roundup256(B * L) from here on -- the
+  // same plan but for its row counts, which stay the padded call's (M = B * L <= the bound: every token has a row below M, so the
+  // per-row kernels need no more; Mp = Mg = the bound, the height of the workspace's buffers) -- with its three arrays in the
+  // library's side buffer, and the contractions stop at the token count the packing launch leaves in cu[B].
+  int64_t pack_bound = packed_rows;
+  bool skip = false;
+  if (encoder_skip_pad(plan_in, plan, sw)) {
+    int* side = nullptr;
+    RUN(skip_pad_buffer(s, (size_t)(plan.Mp + 2 * B + 2), &side));
+    if (side) {
+      skip = true;
+      pack_bound = plan.Mp;
+      ws.cu = side; ws.cls_rows = side + (B + 2); ws.row_map = ws.cls_rows + B;
+    }
+  }
+  const bool packed = pack_bound > 0;      // the token axis holds packed rows
   const int* const row_map = packed ? ws.row_map : nullptr;
 
   RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-  if (packed) RUN(omk_pack_rows(ws.kmax, B, (int)L, packed_rows, ws.cu, ws.cls_rows, ws.row_map, s));
+  if (packed) RUN(omk_pack_rows(ws.kmax, B, (int)L, pack_bound, ws.cu, ws.cls_rows, ws.row_map, s));
   // Relative-position bias (T5; MPNet): one bucket table for all layers, expanded once per forward to [heads, L, L] and handed to EVERY
   // attention launch (BERT family: next to the BERT scale, the kernels scale q.k only)
   if (plan.rel_bias) {
@@ -664,7 +719,8 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   else
     RUN(omk_embed(dt, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
 
-  const EncCall k = {c, w, attention_mask, B, L, plan, ws, plan.rel_bias ? ws.posbias : nullptr, packed ? ws.cu : nullptr, row_map, out_hidden, s};
+  const EncCall k = {c, w, attention_mask, B, L, plan, ws, plan.rel_bias ? ws.posbias : nullptr, packed ? ws.cu : nullptr, row_map, out_hidden, s,
+                     skip ? ws.cu + B : nullptr};
   EncStream stream_out;
   switch (plan.path) {
     case OM_ENC_PATH_BERT_FUSED: RUN(bert_fused(k, &stream_out)); break;
@@ -689,7 +745,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
       RUN(omk_pool(OM_F32, f32_rows, attention_mask, pooled, B, (int)L, H, c->pooling, s, k.cu));
     else
       RUN(omk_pool(dt, final_hidden, attention_mask, pooled, B, (int)L, H, c->pooling, s));
-    RUN(omk_pooled_tail(c, w, pooled, out_reps, B, k.cu, packed_rows, s));
+    RUN(omk_pooled_tail(c, w, pooled, out_reps, B, k.cu, pack_bound, s));
   }
   return 0;
 }

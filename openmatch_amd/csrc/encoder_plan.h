@@ -17,12 +17,14 @@ struct EncSwitches {
   int skinny_m;       // OM_OPT_GEMM_SKINNY_M: most rows of the few-rows paths
   int few_ln_fuse;    // OM_OPT_FEW_ROWS_LN_FUSE: most rows of the pending-LayerNorm path
   int attention_fast; // OM_OPT_ATTENTION_FAST: read by om_encoder_packed_supported only (attn_plan.h decides the attention kernel itself)
+  int skip_pad;       // OM_OPT_ENCODER_SKIP_PAD: read by encoder_skip_pad only (the plan itself does not change with it)
 };
 
 // every switch the planner reads, read once per call (omk_gemm_ln_fusable reads OM_OPT_GEMM_VARIANT and om_debug_gemm_gen itself)
 static EncSwitches encoder_switches() {
   return EncSwitches{om_option(OM_OPT_ENCODER_FUSED_LN), om_option(OM_OPT_ENCODER_TWO_PLANE), om_option(OM_OPT_ENCODER_PINGPONG),
-                     om_option(OM_OPT_GEMM_SKINNY_M), om_option(OM_OPT_FEW_ROWS_LN_FUSE), om_option(OM_OPT_ATTENTION_FAST)};
+                     om_option(OM_OPT_GEMM_SKINNY_M), om_option(OM_OPT_FEW_ROWS_LN_FUSE), om_option(OM_OPT_ATTENTION_FAST),
+                     om_option(OM_OPT_ENCODER_SKIP_PAD)};
 }
 
 struct EncPlanIn {
@@ -191,4 +193,39 @@ static EncPlan encoder_plan(const EncPlanIn& in, const EncSwitches sw) {
     return p;
   }
   return encoder_plan_checked(in, sw);
+}
+
+// om_encoder_packed_supported at given switches: whether om_encoder_forward_packed would take (c, B, L, packed_rows) -- the plan of
+// that call names a path and no refusal.  Three clauses are STRICTER than the plan: (a), (b), (c).
+static bool encoder_packed_ok(const OmEncoderConfig* c, bool gated_ffn, int64_t B, int64_t L, int64_t packed_rows, const EncSwitches sw) {
+  if (!c || B <= 0 || packed_rows <= 0) return false;
+  if ((c->dtype != OM_BF16 && c->dtype != OM_F16) || (!enc_bert_family(c) && c->arch != OM_ARCH_T5)) return false;      // (what it keeps of rule 1)
+  // (a) few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so only a
+  // batch whose PADDED form is that small is sent back (B = 64, L = 128 with 1 024 real tokens would otherwise run the tile kernels
+  // over all 8 192 padded rows: ADVICE r5)
+  if (B * L <= (int64_t)sw.skinny_m) return false;
+  // (b) 64-wide bfloat16 heads without the 16-bit attention kernels: the forward would fail in its first attention launch
+  // (restates attn_plan.h; kept as it was written, 32-wide heads included, which attn_plan_fwd would take)
+  if (c->dtype == OM_BF16 && !sw.attention_fast) return false;
+  // (c) float16 T5: ReLU only (the forward takes tanh-GELU as well)
+  if (c->arch == OM_ARCH_T5 && c->dtype == OM_F16 && c->act != OM_ACT_RELU) return false;
+  // the call it plans: the fields the host may leave unset (it asks with widths, format and rows) are set so that they refuse nothing
+  OmEncoderConfig q = *c;
+  q.pooling = OM_POOL_FIRST;
+  q.max_pos = 1024;
+  const bool rel = c->arch == OM_ARCH_T5 || c->rel_buckets > 0;
+  const EncPlan p = encoder_plan_checked(EncPlanIn{&q, B, L, packed_rows, false, gated_ffn, rel, false}, sw);
+  return p.path && !p.error;
+}
+
+// Whether a PADDED call (in.packed_rows == 0) whose plan is p skips its pad rows on the device ("pad rows"): it then
+// runs the packed layer loops with the loose bound roundup256(B * L) -- a bound that always holds, so the host need not know the
+// token count -- and its contractions read the count from device memory (GemmEpilogue::rows_dev).  The rule, stated once: the switch
+// is on, the caller wants representations only, and the call plans a fused path that om_encoder_forward_packed would take at that
+// bound.  Everything else -- float32, ModernBERT, few rows, widths off 256, gated T5, hidden states, an A/B switch that unfuses --
+// runs as before.
+static bool encoder_skip_pad(const EncPlanIn& in, const EncPlan& p, const EncSwitches sw) {
+  if (!sw.skip_pad || in.packed_rows != 0 || in.want_hidden || in.c->pooling == OM_POOL_NONE) return false;
+  if (p.error || (p.path != OM_ENC_PATH_BERT_FUSED && p.path != OM_ENC_PATH_T5_FUSED)) return false;
+  return encoder_packed_ok(in.c, in.gated_ffn, in.B, in.L, p.Mp, sw);      // (p.Mp = roundup256(B * L) on a fused path)
 }

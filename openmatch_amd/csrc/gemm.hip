@@ -168,6 +168,7 @@ static GemmEpilogue debug_epilogue(const OmDebugGemmEpilogue& d) {
   ep.a_ln32 = d.a_ln32; ep.a_ln_g = d.a_ln_g; ep.a_ln_b = d.a_ln_b; ep.a_ln_stats_out = d.a_ln_stats_out;
   ep.rln32 = d.rln32; ep.rln32_stats = d.rln32_stats;
   ep.lo8 = d.lo8; ep.ln_inv_h = d.ln_inv_h; ep.ln_eps = d.ln_eps; ep.ln_rms = d.ln_rms; ep.reverse = d.reverse;
+  ep.rows_dev = d.rows_dev;
   return ep;
 }
 extern "C" int om_debug_gemm_ex(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc,

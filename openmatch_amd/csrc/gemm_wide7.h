@@ -65,6 +65,17 @@ typedef unsigned int g7_u32x4 __attribute__((ext_vector_type(4)));
 #define G7_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 #define G7_FENCE_() __builtin_amdgcn_sched_barrier(0)
 
+// Rows the tile walk covers: M, or under ep.rows_dev (kernels.h) the count an earlier launch left in device memory, clamped to [0, M]
+// and rounded up to whole tiles -- so no value of that word takes a workgroup outside the buffers (M is a multiple of 256).  Every
+// workgroup reads the same word before it forms its walk, so all agree on it (reversed walk, XCD order and next-tile prefetch included);
+// one whose first tile is past the count returns before its first DMA.
+__device__ __forceinline__ int64_t g7_rows(const GemmEpilogue& ep, int64_t M) {
+  if (!ep.rows_dev) return M;
+  int64_t r = *ep.rows_dev;
+  r = r < 0 ? 0 : (r > M ? M : r);
+  return (r + 255) & ~(int64_t)255;
+}
+
 // work id -> tile, XCD aware: the 32 workgroups of an XCD (block b runs on XCD b % 8) take 32 CONSECUTIVE tiles of the
 // grouped order (group_m row tiles sweeping the column tiles) in every round, so the panels they share stay in that L2.
 __device__ __forceinline__ bool g7_tile(int it, int64_t ntm, int64_t ntn, int group_m, int64_t& m0, int64_t& n0) {
@@ -155,7 +166,7 @@ __global__ __launch_bounds__(G6_THREADS) void gemm_nt_kernel7(
   const int lane0 = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int64_t ntm = M / 256, ntn = N / 256;
+  const int64_t ntm = g7_rows(ep, M) / 256, ntn = N / 256;      // (M itself stays the pitch of ep.stats_out)
   const int nk = (int)((K * 2) / G7_ROW_BYTES);
   const EpiScalars es(ep);
   constexpr int R = RESID ? (TWO ? 8 : 4) : 0; // DMA instructions per residual patch
@@ -649,7 +660,7 @@ __global__ __launch_bounds__(G6_THREADS) void gemm_nt_kernel7c16(
   const int lane0 = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int64_t ntm = M / 256, ntn = N / 256;
+  const int64_t ntm = g7_rows(ep, M) / 256, ntn = N / 256;      // (M itself stays the pitch of ep.stats_out)
   const int nk = (int)((K * 2) / G7_ROW_BYTES);
   const EpiScalars es(ep);
 
@@ -965,7 +976,7 @@ __global__ __launch_bounds__(G6_THREADS) void gemm_nt_kernel7r16(
   const int lane0 = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int64_t ntm = M / 256, ntn = N / 256;
+  const int64_t ntm = g7_rows(ep, M) / 256, ntn = N / 256;      // (M itself stays the pitch of ep.stats_out)
   const int nk = (int)((K * 2) / G7_ROW_BYTES);
   const EpiScalars es(ep);
   const uint32_t lds_base = g7_lds_addr(smem);
@@ -1427,6 +1438,7 @@ static int g7_num_cus() {
 // The one launcher of the generation-7 kernels.  The persistent families run one workgroup per CU, fewer under OM_OPT_GEMM_MAX_GRID or where
 // the tiles run out; OM_GEMM_FAMILY_G7_ONE_TILE runs one workgroup per tile with the plain group of 8.  The restart-per-tile kernel
 // (OM_GEMM_FAMILY_G7) gets no stagger bits, deliberately: the OM_GEMM_STAGGER probe lives in the continuous kernels only (g7_stagger).
+// The grid is sized by the host's M also under ep.rows_dev (the host does not know the count): workgroups without a tile return at once.
 template <auto KERN, typename T>
 static int g7_launch(int family, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
                      int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s) {
@@ -1444,10 +1456,19 @@ static int g7_launch(int family, const void* A, int64_t lda, const void* B, int6
     attr_set = true;
   }
   const bool timing = om_timing_on();
+  // timing mode prices the rows the kernel walks, not M: the count is copied back and the stream waited for (it was written by an
+  // earlier launch on this stream).  With timing off nothing here copies, waits or allocates.
+  int64_t rows_run = M;
+  if (timing && ep.rows_dev) {
+    int r = 0;
+    OM_HIP(hipMemcpyAsync(&r, ep.rows_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+    OM_HIP(hipStreamSynchronize(s));
+    rows_run = ((int64_t)std::min<int64_t>(std::max(r, 0), M) + 255) / 256 * 256;
+  }
   if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
   omk_gemm_note(family);
   hipLaunchKernelGGL(KERN, dim3((unsigned)grid), dim3(G6_THREADS), G7_LDS_BYTES, s, (const T*)A, lda, (const T*)B, ldb, (T*)C, ldc, M, N, K, ep, gm_arg);
-  if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
+  if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)rows_run * (double)N * (double)K);
   OM_LAUNCH_CHECK();
   return 0;
 }

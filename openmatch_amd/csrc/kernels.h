@@ -132,6 +132,10 @@ struct GemmEpilogue {
   int reverse;               // 1: walk the output tiles from the last row block to the first (persistent 16-bit kernel only).
                              //   A consumer that starts where its producer finished finds those rows in the memory-side cache
                              //   (256 MB; the encoder's activations are 200-800 MB per tensor) -- encoder.hip alternates.
+  const int* rows_dev;       // a row count in DEVICE memory (NULL: none), written by an earlier launch on the same stream: rows at or beyond
+                             //   roundup256(clamp(*rows_dev, 0, M)) need not be computed.  A hint -- the generation-7 kernels shorten their
+                             //   tile walk by it (gemm_wide7.h g7_rows), every other family ignores it and computes all M rows; the rows
+                             //   left out keep what their buffers held.  The encoder's padded batches: the token count (encoder.hip).
 };
 // Byte offset of element (m, n) of an [M, N] tensor's EIGHT-BIT second plane (float16 two-plane residual stream, round 6: gemm_wide7.h kernel
 // 7r16 with LNF == 3 writes and reads it in its own lane order -- tile (256 x 256) -> wave (128 x 128) -> patch (32 rows x 64 columns) ->

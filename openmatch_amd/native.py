@@ -114,7 +114,7 @@ class OmDebugGemmEpilogue(C.Structure):
                 ("stats_out", c_void_p), ("resid_lo", c_void_p), ("out_lo", c_void_p), ("resid32", c_void_p), ("out32", c_void_p),
                 ("a_ln32", c_void_p), ("a_ln_g", c_void_p), ("a_ln_b", c_void_p), ("a_ln_stats_out", c_void_p), ("rln32", c_void_p),
                 ("rln32_stats", c_void_p), ("lo8", c_int), ("ln_inv_h", c_float), ("ln_eps", c_float), ("ln_rms", c_int),
-                ("reverse", c_int)]
+                ("reverse", c_int), ("rows_dev", c_void_p)]
 
 
 class OmLnSite(C.Structure):
@@ -186,6 +186,7 @@ _SIGNATURES = {
                                           c_int, c_int, c_float, c_float, C.c_uint64, c_void_p, c_int, c_void_p]),
     "om_debug_attention_bwd_stats_bytes": (c_size_t, [c_int64, c_int]),
     "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
+    "om_debug_encoder_skip_pad": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int]),
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "om_debug_row_kernel_last": (c_int, []),
