@@ -267,6 +267,17 @@ int om_debug_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int n_heads, in
                          const float* k_norm_g, float eps, const float* inv_freq, float scaling, void* stream);
 int om_debug_qknorm_rope_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
                               const float* k_norm_g, float eps, const float* inv_freq, float scaling, const int* row_map, void* stream);
+/* Test hooks of the Gemma3 stack.  om_debug_attention_gqa_d256 (csrc/attention_d256.hip): bidirectional grouped-query attention over heads
+ * of 256 columns, qkv [rows, (n_heads + 2 n_kv_heads) * 256], ctx [rows, n_heads * 256]; key k visible from query q iff mask[b][k] != 0
+ * and, for 0 < w < L - 1, |q - k| <= w (w <= 0 or w >= L - 1: full attention).  om_debug_qknorm_rope_d256: om_debug_qknorm_rope at
+ * head_dim 256 in Gemma3's form -- g = 1 + weight from the caller, the normalised value not rounded before the weight multiply;
+ * inv_freq a HOST array of 128 frequencies.  om_debug_rmsnorm_add: x[f32] += (h * rsqrt(mean(h^2) + eps)) * g over M rows of H columns,
+ * h in `dtype` with pitch ldh, x f32 with pitch ldx. */
+int om_debug_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads, int n_kv_heads,
+                                float scale, int w, void* stream);
+int om_debug_qknorm_rope_d256(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, const float* q_norm_g, const float* k_norm_g,
+                              float eps, const float* inv_freq, float scaling, void* stream);
+int om_debug_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, void* stream);
 /* kmax[b] = 1 + the last unmasked key of mask row b (L when it has none) */
 int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
 /* cu [B + 2], cls_rows [B], row_map [rows] of the packed layout (csrc/kernels.h omk_pack_rows) */
@@ -618,6 +629,49 @@ size_t om_causal2_encoder_workspace_bytes_packed(const OmCausalConfig2* cfg, int
 int om_causal2_encoder_forward_packed(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
                                       const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows,
                                       float* out_reps, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * EmbeddingGemma (HF Gemma3TextModel with use_bidirectional_attention, HF:models/gemma3/modeling_gemma3.py; inference): the f32-residual
+ * pre-norm loop above with heads of 256 columns, grouped K / V, an RMSNorm over each q and k head before the rotation, rotary
+ * frequencies per layer TYPE, bidirectional attention -- full layers see every unmasked key, sliding layers key k from query q iff
+ * |q - k| <= half_window -- a tanh-GELU gated feed-forward, and FOUR RMSNorms per layer, two of which act on a sublayer's OUTPUT before
+ * the residual add.  An entry and a config struct of its own that EMBEDS OmCausalConfig (no layout above changes, OM_ABI_VERSION stays).
+ * Rules: base.base.arch = OM_ARCH_GEMMA3; head_dim 256 only (the attention width n_heads * 256 need not equal hidden); hidden and ffn
+ * multiples of 64, hidden <= 2048; n_kv_heads divides n_heads; act = OM_ACT_GELU_TANH ("gelu_pytorch_tanh"); no projection has a bias
+ * (attention_bias False); attn_logit_softcapping 0 (None); bidirectional 1 (a causal Gemma3 is refused); at most 64 layers; L <= 1024;
+ * pooling NONE / FIRST / MEAN; ln_eps = rms_norm_eps.  base.rope_attention_scaling and base.inv_freq are ignored.
+ * Weights: OmLayerWeights / OmEncoderWeights as they are, every norm weight handed over as g = 1 + weight in f32 (Gemma3RMSNorm
+ * multiplies by 1 + weight) --
+ *   word_emb = embed_tokens.weight * float32(sqrt(hidden)) (the f32 multiply HF applies to the looked-up row), final_ln_g = 1 + norm.weight
+ *   qkv_w [(n_heads + 2 n_kv_heads) * 256, H] rows q_proj | k_proj | v_proj;  o_w [H, n_heads * 256]
+ *   ln1_g = 1 + input_layernorm.weight, ln2_g = 1 + pre_feedforward_layernorm.weight
+ *   ffn1_w [F, H] gate_proj, ffn1g_w [F, H] up_proj, ffn2_w [H, F] down_proj
+ * and a HOST array of n_layers OmGemma3Norms (device pointers, f32, each 1 + weight).
+ * Padded rows only: no packed entry, no on-device pad skip, no training entry.
+ * ------------------------------------------------------------------------ */
+#define OM_ARCH_GEMMA3 5 /* OmGemma3Config.base.base.arch, served by om_gemma3_encoder_forward alone */
+typedef struct OmGemma3Config {
+  OmCausalConfig base;           /* at offset 0: arch, widths, n_kv_heads                                                             */
+  float attn_scale;              /* config.query_pre_attn_scalar ** -0.5: a field of its own, not head_dim ** -0.5                   */
+  int half_window;               /* config.sliding_window - 1, read AFTER construction (the config has already halved the window)    */
+  uint64_t sliding_layers;       /* bit l set: config.layer_types[l] == "sliding_attention"                                           */
+  float full_scaling;            /* rotary_emb.full_attention_scaling                                                                   */
+  float sliding_scaling;         /* rotary_emb.sliding_attention_scaling                                                                */
+  float attn_logit_softcapping;  /* 0: None (anything else is refused)                                                                  */
+  int bidirectional;             /* config.use_bidirectional_attention: 1 (0 is refused)                                                */
+  float full_inv_freq[128];      /* rotary_emb.full_attention_inv_freq, read on the host                                                */
+  float sliding_inv_freq[128];   /* rotary_emb.sliding_attention_inv_freq                                                               */
+} OmGemma3Config;
+typedef struct OmGemma3Norms {
+  const float* q_norm_g;                /* 1 + self_attn.q_norm.weight [256] f32, device     */
+  const float* k_norm_g;                /* 1 + self_attn.k_norm.weight [256]                 */
+  const float* post_attention_norm_g;   /* 1 + post_attention_layernorm.weight [hidden]      */
+  const float* post_feedforward_norm_g; /* 1 + post_feedforward_layernorm.weight [hidden]    */
+} OmGemma3Norms;
+size_t om_gemma3_encoder_workspace_bytes(const OmGemma3Config* cfg, int64_t B, int64_t L);
+int om_gemma3_encoder_forward(const OmGemma3Config* cfg, const OmEncoderWeights* w, const OmGemma3Norms* norms_host, const int64_t* input_ids,
+                              const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * One decoder position of a T5 encoder-decoder over the encoder's output (inference):

@@ -19,6 +19,8 @@
 //     contraction casts its operands.  Not reproduced: a model held in 16-bit outright (weights cast by .to(dtype)), where the weight
 //     multiply and each product of the rotation round to 16 bits as well.
 //     cos / sin come from omk_rope_table's device table of D / 2 columns per position.
+//     Gemma3 (gemma = 1, head_dim 256, 32 lanes per head): Gemma3RMSNorm multiplies the f32 normalised value by (1 + weight) and
+//     casts once at the end, so that mode has no rounding between the two multiplies and takes g = 1 + w from the host.
 #include "attn_chunked128.h"
 
 namespace {
@@ -100,7 +102,9 @@ template <> struct QkIO<f16_t> : QkIO16<f16_t> {};
 // one thread: the pairs (i0 .. i0 + 3, D/2 + i0 .. D/2 + i0 + 3) of one q or k head of one row; D / 8 consecutive lanes: the head.
 // row_map != NULL (packed rows): the position of row t is row_map[t] % L, rows with row_map[t] < 0 are left as they are.  A group is
 // wholly inside or wholly outside the launch and the row test is the same for all of its lanes, so the shuffles below meet live lanes.
-template <typename T, int D>
+// RAW (Gemma3RMSNorm: (x.float() * rsqrt(..)) * (1.0 + weight.float()), cast once at the end): the normalised value is NOT rounded to
+// the storage format before the weight multiply, and g is the host's 1 + w.  D = 256 (32 lanes per head) exists in this mode only.
+template <typename T, int D, bool RAW = false>
 __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ qkv, const float2* __restrict__ tab, int64_t M, int L, int heads,
                                                           int rot_heads, int pitch, const float* __restrict__ qg, const float* __restrict__ kg,
                                                           float eps, const int* __restrict__ row_map) {
@@ -135,8 +139,13 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ qkv, c
     const float wa[4] = {ga.x, ga.y, ga.z, ga.w}, wb[4] = {gb.x, gb.y, gb.z, gb.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      a[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(a[e], r)), wa[e]);
-      b[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(b[e], r)), wb[e]);
+      if constexpr (RAW) {
+        a[e] = __fmul_rn(__fmul_rn(a[e], r), wa[e]);
+        b[e] = __fmul_rn(__fmul_rn(b[e], r), wb[e]);
+      } else {
+        a[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(a[e], r)), wa[e]);
+        b[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(b[e], r)), wb[e]);
+      }
     }
   }
   const float2* const t = tab + (size_t)pos * (D / 2) + i0;
@@ -156,7 +165,8 @@ void qknorm_rope_launch_as(T* qkv, const float2* tab, int64_t M, int L, int head
                            const int* row_map, hipStream_t s) {
   const int rot = heads + kv_heads, pitch = (heads + 2 * kv_heads) * D;
   const unsigned grid = (unsigned)((M * rot * (D / 8) + 255) / 256);
-  if (D == 128) hipLaunchKernelGGL((qknorm_rope_kernel<T, 128>), dim3(grid), dim3(256), 0, s, qkv, tab, M, L, heads, rot, pitch, qg, kg, eps, row_map);
+  if (D == 256) hipLaunchKernelGGL((qknorm_rope_kernel<T, 256, true>), dim3(grid), dim3(256), 0, s, qkv, tab, M, L, heads, rot, pitch, qg, kg, eps, row_map);
+  else if (D == 128) hipLaunchKernelGGL((qknorm_rope_kernel<T, 128>), dim3(grid), dim3(256), 0, s, qkv, tab, M, L, heads, rot, pitch, qg, kg, eps, row_map);
   else hipLaunchKernelGGL((qknorm_rope_kernel<T, 64>), dim3(grid), dim3(256), 0, s, qkv, tab, M, L, heads, rot, pitch, qg, kg, eps, row_map);
 }
 
@@ -169,10 +179,13 @@ int check_gqa_d(int heads, int kv_heads, int head_dim) {
 }  // namespace
 
 int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, int head_dim, const float* q_norm_g, const float* k_norm_g,
-                    float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map) {
+                    float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map, int gemma) {
   if (M <= 0) return 0;
   if (L < 1 || L > 1024) OM_FAIL("rotary positions: sequence length must be in [1,1024]");
-  if (check_gqa_d(heads, kv_heads, head_dim)) return 1;
+  // head_dim 256 is Gemma3's: its norm is not rounded before the weight multiply, and that instantiation alone exists at 256
+  if (gemma ? (head_dim != 256 || !q_norm_g || !k_norm_g) : head_dim == 256)
+    OM_FAIL("q / k norm and rotary positions: head_dim 256 with both norm weights is the Gemma3 form, and the Gemma3 form is head_dim 256 only");
+  if (check_gqa_d(heads, kv_heads, gemma ? 128 : head_dim)) return 1;
   if (!inv_freq_host) OM_FAIL("rotary positions: a frequency table of head_dim / 2 values");
   if (M * (heads + kv_heads) * (head_dim / 8) > 0x7fffffffLL * 256) OM_FAIL("q / k norm and rotary positions: too many rows for one launch");
   const float2* tab = nullptr;
@@ -274,4 +287,12 @@ extern "C" int om_debug_qknorm_rope_rows(int dtype, void* qkv, int64_t rows, int
   if (!qkv || !inv_freq || !row_map) OM_FAIL("null argument");
   if (debug_dtype(dtype)) return 1;
   return omk_qknorm_rope(dtype, qkv, rows, L, n_heads, n_kv_heads, head_dim, q_norm_g, k_norm_g, eps, inv_freq, scaling, (hipStream_t)stream, row_map);
+}
+
+// Gemma3's form alone (tests/test_gemma3_kernels.py): head_dim 256, g = 1 + w from the caller, no rounding before the weight multiply
+extern "C" int om_debug_qknorm_rope_d256(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, const float* q_norm_g,
+                                         const float* k_norm_g, float eps, const float* inv_freq, float scaling, void* stream) {
+  if (!qkv || !inv_freq || !q_norm_g || !k_norm_g) OM_FAIL("null argument");
+  if (debug_dtype(dtype)) return 1;
+  return omk_qknorm_rope(dtype, qkv, M, L, n_heads, n_kv_heads, 256, q_norm_g, k_norm_g, eps, inv_freq, scaling, (hipStream_t)stream, nullptr, 1);
 }

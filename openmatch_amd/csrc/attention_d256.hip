@@ -1,0 +1,110 @@
+// Grouped-query attention over heads of 256 columns (gfx950, inference): what EmbeddingGemma's Gemma3TextModel with
+// use_bidirectional_attention needs (HF:models/gemma3/modeling_gemma3.py) -- full layers where every unmasked key is visible and
+// sliding layers where key k is visible from query q iff |q - k| <= w and k is unmasked.
+//
+//   * omk_attention_gqa_d256: softmax(Q K^T * scale + mask) V over the grouped projection [M, (heads + 2 kv_heads) * 256]
+//     (q heads | k heads | v heads) into ctx [M, heads * 256]; query head h reads K / V head h / (heads / kv_heads) (HF repeat_kv).
+//     The scale is the caller's (Gemma3: query_pre_attn_scalar ** -0.5, a config field of its own).  One workgroup of 256 threads per
+//     (sequence, query head, 128-query block) walks 64-key chunks clipped to kmax[b] (keys at or past it are padding); with a band it
+//     walks only the keys [qb - w, qb + 127 + w] its queries can reach.  0 < w < L - 1 is the band (AttnBand), anything else full
+//     attention (AttnFull): a window that reaches every key never takes the band kernel, so the two give the same bits there.
+//     Padded layout only.  The bodies are attn_chunked256.h; four kernels: 16-bit x {full, band} per format, float32 x {full, band}.
+//     A wave of either body holds more than 256 registers (no __launch_bounds__ second argument): one workgroup per CU.
+#include "attn_chunked256.h"
+
+namespace {
+
+// rows of the grouped projection and of ctx for the sequence whose first row is row0, query head h (attention_causal.hip causal_rows
+// with 256 columns per head)
+template <typename T>
+__device__ __forceinline__ AttnRows<T> gqa_rows_d256(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
+  const int kvh = h / (heads / kv_heads);
+  const int pitch = (heads + 2 * kv_heads) * 256;
+  const T* const row = qkv + row0 * pitch;
+  const T* const k = row + (heads + kvh) * 256;
+  return {row + h * 256, k, k + kv_heads * 256, pitch, ctx + row0 * (int64_t)(heads * 256) + h * 256, heads * 256};
+}
+
+template <typename T, typename Policy>
+__global__ __launch_bounds__(256) void attention_d256_16_kernel(
+    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale, Policy pol,
+    const int* __restrict__ kmax) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int kend = kmax ? __builtin_amdgcn_readfirstlane(kmax[b]) : L;
+  attn_chunked16_d256<T, Policy>(gqa_rows_d256(qkv, ctx, b * L, heads, kv_heads, h), pol, mask + b * L, L, kend, blockIdx.y * 128, scale);
+}
+
+template <typename Policy>
+__global__ __launch_bounds__(256) void attention_d256_32_kernel(
+    const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale, Policy pol,
+    const int* __restrict__ kmax) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  attn_chunked32_d256<Policy>(gqa_rows_d256(qkv, ctx, b * L, heads, kv_heads, h), pol, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128, scale);
+}
+
+template <typename T, typename Policy>
+int launch16(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* kmax,
+             hipStream_t s) {
+  if (attn_lds_once<attention_d256_16_kernel<T, Policy>>(kAttn16D256Lds)) return 1;
+  hipLaunchKernelGGL((attention_d256_16_kernel<T, Policy>), grid, dim3(256), kAttn16D256Lds, s, (const T*)qkv, (T*)ctx, mask, L, heads, kv_heads, scale,
+                     pol, kmax);
+  return 0;
+}
+
+template <typename Policy>
+int launch32(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* kmax,
+             hipStream_t s) {
+  if (attn_lds_once<attention_d256_32_kernel<Policy>>(kAttn32D256Lds)) return 1;
+  hipLaunchKernelGGL((attention_d256_32_kernel<Policy>), grid, dim3(256), kAttn32D256Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads,
+                     scale, pol, kmax);
+  return 0;
+}
+
+template <typename Policy>
+int launch_policy(int dtype, const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol,
+                  const int* kmax, hipStream_t s) {
+  if (dtype == OM_F16) return launch16<f16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, kmax, s);
+  if (dtype == OM_BF16) return launch16<bf16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, kmax, s);
+  return launch32(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, kmax, s);
+}
+
+int check_args(int64_t B, int L, int heads, int kv_heads) {
+  if (L < 1 || L > 1024) OM_FAIL("attention (head_dim 256): sequence length must be in [1,1024]");
+  if (heads < 1 || kv_heads < 1 || heads % kv_heads) OM_FAIL("grouped heads: n_kv_heads must be at least 1 and divide n_heads");
+  if (B * heads > 0x7fffffffLL) OM_FAIL("attention (head_dim 256): batch too large for one launch");
+  // the LDS-DMA addresses a sequence's K / V rows with a 32-bit byte offset from its first row
+  if ((int64_t)L * (heads + 2 * kv_heads) * 512 > 0x7fffffffLL) OM_FAIL("attention (head_dim 256): too many heads for one sequence's 32-bit row offsets");
+  return 0;
+}
+
+}  // namespace
+
+int omk_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale, int w,
+                           const int* kmax, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (check_args(B, L, heads, kv_heads)) return 1;
+  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
+  int rc;
+  if (w > 0 && w < L - 1) rc = launch_policy(dtype, qkv, ctx, mask, grid, L, heads, kv_heads, scale, AttnBand{w}, kmax, s);
+  else rc = launch_policy(dtype, qkv, ctx, mask, grid, L, heads, kv_heads, scale, AttnFull{}, kmax, s);
+  if (rc) return 1;
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// Test hook (tests/test_gemma3_kernels.py, tools/gemma3_bench.py): the kernels alone; the key extents go into the grow-only device
+// buffer the causal hooks keep per device (omk_causal_debug_kmax)
+extern "C" int om_debug_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads,
+                                           int n_kv_heads, float scale, int w, void* stream) {
+  if (!qkv || !ctx || !mask) OM_FAIL("null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
+  if (B <= 0) return 0;
+  if (check_args(B, L, n_heads, n_kv_heads)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int* kmax = nullptr;
+  if (omk_causal_debug_kmax(B, &kmax)) return 1;
+  if (omk_mask_extent(mask, B, L, kmax, s)) return 1;
+  return omk_attention_gqa_d256(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, w, kmax, s);
+}

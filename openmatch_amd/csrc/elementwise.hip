@@ -387,6 +387,58 @@ int omk_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int6
   return launch_ln<float, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
 }
 
+// x[f32] += rms(h) * g: the RMSNorm of a sublayer OUTPUT h (compute format) added into a residual stream kept in f32 (Gemma3's
+// post_attention_layernorm / post_feedforward_layernorm; g = 1 + w from the host).  One wave per row, the row arithmetic of ln_row.h:
+// y = (h * rstd) * g in f32 as norm_and_store's RMS branch, then ONE f32 add.  The reference's autocast rounds y to the 16-bit format
+// before that add; this kernel does not (the unrounded sum is the closer one to the fp32 model).
+template <typename TIn, int MAX_VEC>
+__global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void rmsnorm_add_kernel(const TIn* __restrict__ h, int64_t ldh, float* __restrict__ x, int64_t ldx,
+                                                                          const float* __restrict__ g, int64_t M, int H, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nvec = (H / 4 + 63) / 64;
+  float v[MAX_VEC][4];
+#pragma unroll
+  for (int j = 0; j < MAX_VEC; ++j) {
+    const int c = (lane + 64 * j) * 4;
+    if (j < nvec && c < H) Vec4<TIn>::load(h + row * ldh + c, v[j]);
+  }
+  float mean, rstd;
+  ln_row_stats<MAX_VEC>(v, nvec, lane, H, eps, 1, mean, rstd);
+  float* const xr = x + row * ldx;
+#pragma unroll
+  for (int j = 0; j < MAX_VEC; ++j) {
+    const int c = (lane + 64 * j) * 4;
+    if (j < nvec && c < H) {
+      float gv[4], xv[4];
+      Vec4<float>::load(g + c, gv);
+      Vec4<float>::load(xr + c, xv);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xv[e] = __fadd_rn(xv[e], __fmul_rn(__fmul_rn(v[j][e], rstd), gv[e]));
+      Vec4<float>::store(xr + c, xv);
+    }
+  }
+}
+
+template <typename TIn>
+static void launch_rmsnorm_add(const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s) {
+  const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+  if (H <= 1024) hipLaunchKernelGGL((rmsnorm_add_kernel<TIn, 4>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, (const TIn*)h, ldh, x, ldx, g, M, H, eps);
+  else hipLaunchKernelGGL((rmsnorm_add_kernel<TIn, 8>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, (const TIn*)h, ldh, x, ldx, g, M, H, eps);
+}
+
+int omk_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s) {
+  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
+  if (ldh % 4 || ldx % 4) OM_FAIL("norm-add: row pitches of whole four-element vectors");
+  if (M <= 0) return 0;
+  if (dtype == OM_BF16) launch_rmsnorm_add<bf16_t>(h, ldh, x, ldx, g, M, H, eps, s);
+  else if (dtype == OM_F16) launch_rmsnorm_add<f16_t>(h, ldh, x, ldx, g, M, H, eps, s);
+  else launch_rmsnorm_add<float>(h, ldh, x, ldx, g, M, H, eps, s);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
 // x in the compute format (optionally two planes, bf16) -> y in f32
 int omk_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b,
                          int64_t M, int H, float eps, int rms, hipStream_t s, const void* x_lo, const int* rows, int lo8) {
@@ -579,6 +631,13 @@ extern "C" int om_debug_layernorm_f32out(int dtype, const void* x, int64_t ldx, 
   if (!x || !y || !g) OM_FAIL("om_debug_layernorm_f32out: null argument");
   OM_DBG_DTYPE("om_debug_layernorm_f32out");
   return omk_layernorm_f32out(dtype, x, ldx, y, ldy, g, b, M, H, eps, rms, (hipStream_t)stream, x_lo, rows, lo8);
+}
+/* x[f32] += rms(h) * g (Gemma3's norm of a sublayer output added into the f32 residual stream) */
+extern "C" int om_debug_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps,
+                                    void* stream) {
+  if (!h || !x || !g) OM_FAIL("om_debug_rmsnorm_add: null argument");
+  OM_DBG_DTYPE("om_debug_rmsnorm_add");
+  return omk_rmsnorm_add(dtype, h, ldh, x, ldx, g, M, H, eps, (hipStream_t)stream);
 }
 extern "C" int om_debug_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b,
                                            int64_t M, int H, float eps, int rms, void* stream) {

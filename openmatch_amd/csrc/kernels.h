@@ -71,7 +71,15 @@ int omk_attention_causal_d128(int dtype, const void* qkv, void* ctx, const int64
 int omk_attention_causal_d128_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads,
                                      float scale, const int* cu, hipStream_t s);
 int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, int head_dim, const float* q_norm_g, const float* k_norm_g,
-                    float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map = nullptr);
+                    float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map = nullptr,
+                    int gemma = 0 /* 1: Gemma3's form -- head_dim 256, g = 1 + w, the normalised value not rounded before the weight multiply */);
+// Gemma3 (attention_d256.hip): bidirectional grouped-query attention over heads of 256 columns -- qkv [M, (heads + 2 kv_heads) * 256],
+// ctx [M, heads * 256], the caller's score scale; 0 < w < L - 1: key k visible from query q iff |q - k| <= w, else every unmasked key.
+int omk_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale, int w,
+                           const int* kmax, hipStream_t s);
+// x[f32] += rms(h) * g over M rows of H columns (elementwise.hip): the norm of a sublayer OUTPUT h (compute dtype) added into the f32
+// residual stream (Gemma3's post_attention_layernorm / post_feedforward_layernorm); g = 1 + w from the host
+int omk_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s);
 // attention_causal.hip: the device table [1024 positions][n] of (cos, sin) * scaling for n host frequencies, cached per (device,
 // frequencies, scaling); the grow-only device buffer of key extents the causal test hooks share
 int omk_rope_table(const float* inv_freq, int n, float scaling, const float2** out);

@@ -1,7 +1,8 @@
 """Host side of the HIP encoder: turns a HF `BertModel` / `RobertaModel` / `DistilBertModel` / `MPNetModel` / `T5EncoderModel` /
-`ModernBertModel` / `NomicBertModel` / `LlamaModel` / `Qwen2Model` (the parameter
+`ModernBertModel` / `NomicBertModel` / `LlamaModel` / `Qwen2Model` / `Qwen3Model` / `Gemma3TextModel` (the parameter
 container the reference keeps in `DRModel.lm_q / lm_p`) into the packed device weights that
-`om_encoder_forward` (`om_causal_encoder_forward` for the decoder-only backbones) consumes, and launches it.
+`om_encoder_forward` (`om_causal_encoder_forward` for the decoder-only backbones, `om_gemma3_encoder_forward` for EmbeddingGemma)
+consumes, and launches it.
 
 The HF module's own `forward` is never called on this path; it stays the owner of the
 parameters so `state_dict()` / `save_pretrained()` keep the reference's checkpoint layout
@@ -49,6 +50,8 @@ def inference_code(model, code, seq_len):
     if _arch_of(model) == "causal":              # Llama / Qwen2: float16 and bfloat16 as asked (nothing clamps, as under the reference's autocast)
         return code
     if _arch_of(model) == "nomicbert":           # float16 under BERT's no-clamp statement: as asked
+        return code
+    if _arch_of(model) == "gemma3":              # as for the decoder-only stacks: the format asked for, nothing clamps
         return code
     if _arch_of(model) == "modernbert":          # the GeGLU feed-forward with erf-GELU: float16 as for erf-GELU BERT
         return code if getattr(cfg, "hidden_activation", None) == "gelu" else N.OM_BF16
@@ -131,8 +134,20 @@ def shadows_of(param):
 _CAUSAL_CLASSES = ("LlamaModel", "Qwen2Model", "Qwen3Model")
 
 
+# what AutoModel returns for google/embeddinggemma-300m and its fine-tunes; the multimodal wrapper, the LM-head wrappers and the
+# classification heads carry a Gemma3TextModel inside and are refused by name
+_GEMMA3_REFUSED = ("Gemma3Model", "Gemma3ForCausalLM", "Gemma3ForConditionalGeneration", "Gemma3ForSequenceClassification",
+                   "Gemma3TextForSequenceClassification", "Gemma3PreTrainedModel")
+
+
 def _arch_of(model):
     name = type(model).__name__
+    if name == "Gemma3TextModel":        # EmbeddingGemma: bidirectional Gemma3, heads of 256 columns, sliding and full layers
+        return "gemma3"
+    if name in _GEMMA3_REFUSED or name.startswith("Gemma3"):
+        raise NotImplementedError(
+            f"openmatch_amd serves Gemma3 through Gemma3TextModel with use_bidirectional_attention (EmbeddingGemma, inference) only; "
+            f"got {name}: hand over its text model (AutoModel of an EmbeddingGemma checkpoint returns Gemma3TextModel)")
     if "T5" in name:
         return "t5"
     if name.startswith("ModernBert"):    # ModernBertModel: pre-LayerNorm stack with rotary positions and sliding-window layers
@@ -148,7 +163,8 @@ def _arch_of(model):
         return "bert"
     raise NotImplementedError(
         f"openmatch_amd has HIP encoders for BERT / RoBERTa / DistilBERT / MPNet, T5-encoder, ModernBERT, NomicBERT (NomicBertModel, "
-        f"inference) and Llama / Qwen2 (head_dim 64, inference) / Qwen3 (head_dim 64 or 128, inference) backbones; got {name}")
+        f"inference), Llama / Qwen2 (head_dim 64, inference) / Qwen3 (head_dim 64 or 128, inference) and bidirectional Gemma3 "
+        f"(Gemma3TextModel / EmbeddingGemma, head_dim 256, inference) backbones; got {name}")
 
 
 def position_offset(model):
@@ -486,6 +502,143 @@ def qwen3_config_fields(cfg, model):
                 n_kv_heads=n_kv, rope_attention_scaling=float(rot.attention_scaling), inv_freq=[float(v) for v in inv], qk_norm=1)
 
 
+def gemma3_config_fields(cfg, model):
+    """The OmGemma3Config fields of a bidirectional `Gemma3TextModel` (EmbeddingGemma) that do not depend on the compute format, after
+    refusing (naming Gemma3TextModel and the limit, before anything touches the device) what the HIP stack does not serve.  The half
+    window is `config.sliding_window - 1` read AFTER construction: with use_bidirectional_attention the config has already replaced
+    sliding_window by sliding_window // 2 + 1, and a sliding layer sees key k from query q iff |q - k| < config.sliding_window.  The two
+    sets of 128 rotary frequencies and their cos / sin scalings are the module's own buffers (`rotary_emb.<layer type>_inv_freq`,
+    `rotary_emb.<layer type>_attention_scaling`); the score scale is query_pre_attn_scalar ** -0.5, a config field of its own."""
+    name = "Gemma3TextModel"
+    heads, hidden, ffn = int(cfg.num_attention_heads), int(cfg.hidden_size), int(cfg.intermediate_size)
+    head_dim = int(getattr(cfg, "head_dim", None) or hidden // heads)
+    if head_dim != 256:
+        raise NotImplementedError(f"{name}: head_dim {head_dim} is not supported by the HIP encoder (the Gemma3 stack has attention kernels for head_dim 256 only)")
+    if not getattr(cfg, "use_bidirectional_attention", False):
+        raise NotImplementedError(f"{name} with use_bidirectional_attention = False (a causal Gemma3) is not supported by the HIP encoder; "
+                                  "EmbeddingGemma's bidirectional encoder is")
+    n_kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
+    if n_kv < 1 or heads % n_kv:
+        raise NotImplementedError(f"{name}: num_key_value_heads ({n_kv}) must divide num_attention_heads ({heads})")
+    if hidden % 64 or ffn % 64 or hidden > 2048:
+        raise NotImplementedError(f"{name}: hidden_size and intermediate_size must be multiples of 64, hidden_size at most 2048 "
+                                  f"(got {hidden}, {ffn}): the row kernels hold a row of at most 2048 columns")
+    if cfg.hidden_activation != "gelu_pytorch_tanh":
+        raise NotImplementedError(f"{name}: hidden_activation must be 'gelu_pytorch_tanh'; got {cfg.hidden_activation!r}")
+    if getattr(cfg, "attention_bias", False):
+        raise NotImplementedError(f"{name} with attention_bias = True is not supported by the HIP encoder")
+    if getattr(cfg, "attn_logit_softcapping", None) is not None:
+        raise NotImplementedError(f"{name}: attn_logit_softcapping must be None; got {cfg.attn_logit_softcapping}")
+    types = list(cfg.layer_types)
+    if len(types) != cfg.num_hidden_layers or any(t not in ("full_attention", "sliding_attention") for t in types):
+        raise NotImplementedError(f"{name}: layer_types must name full_attention / sliding_attention per layer; got {types}")
+    if len(types) > 64:
+        raise NotImplementedError(f"{name}: at most 64 layers")
+    rp = getattr(cfg, "rope_parameters", None) or {}
+    rot = model.rotary_emb
+    freqs, scalings = {}, {}
+    for kind in ("full_attention", "sliding_attention"):
+        if kind not in types:                      # (no layer reads this table)
+            freqs[kind], scalings[kind] = [0.0] * 128, 1.0
+            continue
+        rope_type = (rp.get(kind) or {}).get("rope_type", "default")
+        if rope_type not in ("default", "linear"):
+            raise NotImplementedError(f"{name}: rope type {rope_type!r} ({kind}) is not supported by the HIP encoder; default and linear are")
+        inv = getattr(rot, f"{kind}_inv_freq").detach().to("cpu", torch.float32).reshape(-1)
+        if inv.numel() != 128:
+            raise NotImplementedError(f"{name}: expected 128 rotary frequencies for {kind} (head_dim 256, full rotation); got {inv.numel()}")
+        freqs[kind] = [float(v) for v in inv]
+        scalings[kind] = float(getattr(rot, f"{kind}_attention_scaling"))
+    mask = 0
+    for i, t in enumerate(types):
+        if t == "sliding_attention":
+            mask |= 1 << i
+    half_window = int(cfg.sliding_window) - 1 if mask else 0
+    if mask and half_window < 1:
+        raise NotImplementedError(f"{name}: sliding layers need config.sliding_window of at least 2; got {cfg.sliding_window}")
+    return dict(arch=N.ARCH_GEMMA3, hidden=hidden, n_layers=int(cfg.num_hidden_layers), n_heads=heads, head_dim=256, ffn=ffn,
+                vocab=int(cfg.vocab_size), max_pos=0, type_vocab=0, act=N.ACT_GELU_TANH, ln_eps=float(cfg.rms_norm_eps), rel_buckets=0,
+                rel_max_dist=0, n_kv_heads=n_kv, attn_scale=float(cfg.query_pre_attn_scalar) ** -0.5, half_window=half_window,
+                sliding_layers=mask, full_scaling=scalings["full_attention"], sliding_scaling=scalings["sliding_attention"],
+                full_inv_freq=freqs["full_attention"], sliding_inv_freq=freqs["sliding_attention"])
+
+
+_GEMMA3_OWN = ("n_kv_heads", "attn_scale", "half_window", "sliding_layers", "full_scaling", "sliding_scaling", "full_inv_freq", "sliding_inv_freq")
+
+
+def gemma3_config(pk_cfg, pooling, normalize):
+    """The OmGemma3Config of a packed Gemma3TextModel (`_pack_gemma3`'s cfg dict + the head fields) for one call."""
+    base = N.OmEncoderConfig(pooling=pooling, normalize=int(bool(normalize)), **{k: v for k, v in pk_cfg.items() if k not in _GEMMA3_OWN})
+    inner = N.OmCausalConfig(base=base, n_kv_heads=pk_cfg["n_kv_heads"], rope_attention_scaling=1.0, inv_freq=(C.c_float * 32)(*([0.0] * 32)))
+    return N.OmGemma3Config(base=inner, attn_scale=pk_cfg["attn_scale"], half_window=pk_cfg["half_window"], sliding_layers=pk_cfg["sliding_layers"],
+                            full_scaling=pk_cfg["full_scaling"], sliding_scaling=pk_cfg["sliding_scaling"], attn_logit_softcapping=0.0,
+                            bidirectional=1, full_inv_freq=(C.c_float * 128)(*pk_cfg["full_inv_freq"]),
+                            sliding_inv_freq=(C.c_float * 128)(*pk_cfg["sliding_inv_freq"]))
+
+
+def _pack_gemma3(model, code, device):
+    """Gemma3TextModel: the matrices in the compute dtype, q / k / v fused to rows q | k | v of [(heads + 2 kv) * 256, H]; every
+    RMSNorm weight as g = 1 + weight in f32 (Gemma3RMSNorm multiplies by 1.0 + weight.float(): the same f32 sum), the four that
+    OmLayerWeights has no field for in pk.norms (an OmGemma3Norms array); the embedding table multiplied in f32 by float32(sqrt(hidden)),
+    the factor HF applies to the looked-up row."""
+    cfg = model.config
+    fields = gemma3_config_fields(cfg, model)
+    wd = torch_dtype_of(code)
+    f32 = torch.float32
+    pk = _Packed()
+    w = pk.weights
+    one_plus = lambda p: pk.dev(1.0 + p.detach().to(f32), f32, device)       # noqa: E731
+    scale = torch.tensor(cfg.hidden_size ** 0.5, dtype=f32)
+    w.word_emb = pk.dev(model.embed_tokens.weight.detach().to(f32) * scale.to(model.embed_tokens.weight.device), f32, device)
+    w.final_ln_g = one_plus(model.norm.weight)
+    layers = (N.OmLayerWeights * cfg.num_hidden_layers)()
+    norms = (N.OmGemma3Norms * cfg.num_hidden_layers)()
+    for i, layer in enumerate(model.layers):
+        sa, mlp, lw = layer.self_attn, layer.mlp, layers[i]
+        projs = [sa.q_proj, sa.k_proj, sa.v_proj]
+        if any(p.bias is not None for p in projs) or sa.o_proj.bias is not None:
+            raise NotImplementedError("Gemma3TextModel with attention_bias = True is not supported by the HIP encoder")
+        lw.qkv_w = pk.dev(torch.cat([p.weight for p in projs], 0), wd, device, [p.weight for p in projs])
+        lw.o_w = pk.dev(sa.o_proj.weight, wd, device)
+        lw.ln1_g = one_plus(layer.input_layernorm.weight)
+        lw.ln2_g = one_plus(layer.pre_feedforward_layernorm.weight)
+        lw.ffn1_w = pk.dev(mlp.gate_proj.weight, wd, device)
+        lw.ffn1g_w = pk.dev(mlp.up_proj.weight, wd, device)
+        lw.ffn2_w = pk.dev(mlp.down_proj.weight, wd, device)
+        norms[i].q_norm_g = one_plus(sa.q_norm.weight)
+        norms[i].k_norm_g = one_plus(sa.k_norm.weight)
+        norms[i].post_attention_norm_g = one_plus(layer.post_attention_layernorm.weight)
+        norms[i].post_feedforward_norm_g = one_plus(layer.post_feedforward_layernorm.weight)
+    pk.layers = layers
+    pk.norms = norms
+    w.layers_host = C.cast(layers, C.POINTER(N.OmLayerWeights))
+    pk.cfg = dict(dtype=code, **fields)
+    return pk
+
+
+def _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden):
+    """hip_encode for a packed Gemma3TextModel: om_gemma3_encoder_forward over the B * L padded rows (it has no packed entry)."""
+    device = ids.device
+    cfg = gemma3_config(pk.cfg, _POOL[pooling], normalize)
+    B, L = ids.shape
+    base = cfg.base.base
+    H = base.hidden
+    D = base.head_out if base.head_in > 0 else H
+    lib = N.lib()
+    norms = C.cast(pk.norms, C.POINTER(N.OmGemma3Norms)) if len(pk.norms) else None
+    LAST_CALL.update(rows=B * L, packed=False)
+    with torch.cuda.device(device):
+        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
+        nbytes = lib.om_gemma3_encoder_workspace_bytes(C.byref(cfg), B, L)
+        if not nbytes:
+            raise N.NativeError(lib.om_last_error().decode("utf-8", "replace"))
+        ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
+        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
+        N.check(lib.om_gemma3_encoder_forward(C.byref(cfg), C.byref(pk.weights), norms, N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
+                                              C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+    return hidden, reps
+
+
 def _pack_causal(model, code, device):
     """LlamaModel / Qwen2Model / Qwen3Model: the embedding table and the RMSNorm weights in f32, the matrices in the compute dtype;
     q / k / v fused to rows q | k | v of [(heads + 2 kv) * head_dim, H] (a missing bias of a projection that has siblings with one
@@ -548,7 +701,8 @@ def causal_config(pk_cfg, pooling, normalize):
                             inv_freq=(C.c_float * 32)(*pk_cfg["inv_freq"]))
 
 
-_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert, "causal": _pack_causal, "nomicbert": _pack_nomicbert}
+_PACKERS = {"bert": _pack_bert, "t5": _pack_t5, "modernbert": _pack_modernbert, "causal": _pack_causal, "nomicbert": _pack_nomicbert,
+            "gemma3": _pack_gemma3}
 
 
 def _pack_t5_decoder(model, code, device):
@@ -637,7 +791,7 @@ def _ensure_folded(pk, device):
     if getattr(pk, "fold_done", False):
         return
     pk.fold_done = True
-    if pk.cfg.get("arch") == N.ARCH_CAUSAL:      # (no fused-norm path: nothing to fold)
+    if pk.cfg.get("arch") in (N.ARCH_CAUSAL, N.ARCH_GEMMA3):      # (no fused-norm path: nothing to fold)
         return
     lib = N.lib()
     cfg = N.OmEncoderConfig(pooling=N.POOL_NONE, normalize=0, **pk.cfg)
@@ -797,6 +951,8 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     pk = packed_weights(model, head, code, device)
     if _arch_of(model) == "causal":
         return _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
+    if _arch_of(model) == "gemma3":
+        return _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden)
     _ensure_folded(pk, device)
     cfg = N.OmEncoderConfig(pooling=_POOL[pooling], normalize=int(bool(normalize)), **pk.cfg)
     B, L = ids.shape

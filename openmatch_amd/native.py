@@ -16,7 +16,7 @@ ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_GELU_TANH = 0, 1, 2, 3
 ACT_SILU = 5
 ACT_MUL_RESID = 0x100
 ACT_GELU_ERF_GRAD, ACT_PRE_GRAD = 4, 0x200      # training epilogues (csrc/kernels.h; include/openmatch_hip.h), om_debug_gemm_ex only
-ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL, ARCH_NOMICBERT = 0, 1, 2, 3, 4
+ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL, ARCH_NOMICBERT, ARCH_GEMMA3 = 0, 1, 2, 3, 4, 5
 POOL_NONE, POOL_FIRST, POOL_MEAN, POOL_LAST = 0, 1, 2, 3
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
 OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
@@ -66,6 +66,19 @@ class OmCausalConfig2(C.Structure):
 class OmCausalQkNorm(C.Structure):
     """One layer's q_norm.weight / k_norm.weight: device pointers to [head_dim] f32."""
     _fields_ = [("q_norm_g", c_void_p), ("k_norm_g", c_void_p)]
+
+
+class OmGemma3Config(C.Structure):
+    """EmbeddingGemma (om_gemma3_encoder_forward): OmCausalConfig, untouched, followed by the score scale, the band, the per-layer-type
+    rotary tables and the two switches the entry refuses by name."""
+    _fields_ = [("base", OmCausalConfig), ("attn_scale", c_float), ("half_window", c_int), ("sliding_layers", C.c_uint64),
+                ("full_scaling", c_float), ("sliding_scaling", c_float), ("attn_logit_softcapping", c_float), ("bidirectional", c_int),
+                ("full_inv_freq", c_float * 128), ("sliding_inv_freq", c_float * 128)]
+
+
+class OmGemma3Norms(C.Structure):
+    """One layer's q_norm / k_norm / post_attention_layernorm / post_feedforward_layernorm as g = 1 + weight: device pointers, f32."""
+    _fields_ = [(n, c_void_p) for n in ("q_norm_g", "k_norm_g", "post_attention_norm_g", "post_feedforward_norm_g")]
 
 
 class OmEncoderWeights(C.Structure):
@@ -176,6 +189,10 @@ _SIGNATURES = {
                                      c_float, c_void_p]),
     "om_debug_qknorm_rope_rows": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(c_float),
                                           c_float, c_void_p, c_void_p]),
+    "om_debug_attention_gqa_d256": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "om_debug_qknorm_rope_d256": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(c_float), c_float,
+                                          c_void_p]),
+    "om_debug_rmsnorm_add": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p]),
     "om_debug_mask_extent": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_debug_attention_last": (c_int, []),
@@ -244,6 +261,9 @@ _SIGNATURES = {
     "om_causal2_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmCausalConfig2), c_int64, c_int64, c_int64]),
     "om_causal2_encoder_forward_packed": (c_int, [C.POINTER(OmCausalConfig2), C.POINTER(OmEncoderWeights), C.POINTER(OmCausalQkNorm), c_void_p,
                                                   c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_gemma3_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmGemma3Config), c_int64, c_int64]),
+    "om_gemma3_encoder_forward": (c_int, [C.POINTER(OmGemma3Config), C.POINTER(OmEncoderWeights), C.POINTER(OmGemma3Norms), c_void_p, c_void_p,
+                                          c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_encoder_packed_supported": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int64, c_int64, c_int64]),
     "om_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64, c_int64]),
     "om_encoder_forward_packed": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p,

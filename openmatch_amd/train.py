@@ -232,6 +232,9 @@ def encode_train(model, head, items, pooling, normalize, code, training, packed_
     if _arch_of(model) == "nomicbert":
         raise NotImplementedError("NomicBERT training is not supported by the HIP encoder (inference only: encode in eval "
                                   "mode under torch.no_grad())")
+    if _arch_of(model) == "gemma3":
+        raise NotImplementedError("Gemma3 training is not supported by the HIP encoder (inference only: encode in eval "
+                                  "mode under torch.no_grad())")
     if type(model).__name__ == "Qwen3Model":
         raise NotImplementedError("Qwen3 training is not supported by the HIP encoder (inference only: encode in eval "
                                   "mode under torch.no_grad())")
