@@ -272,11 +272,19 @@ int om_debug_qknorm_rope_rows(int dtype, void* qkv, int64_t rows, int L, int n_h
  * and, for 0 < w < L - 1, |q - k| <= w (w <= 0 or w >= L - 1: full attention).  om_debug_qknorm_rope_d256: om_debug_qknorm_rope at
  * head_dim 256 in Gemma3's form -- g = 1 + weight from the caller, the normalised value not rounded before the weight multiply;
  * inv_freq a HOST array of 128 frequencies.  om_debug_rmsnorm_add: x[f32] += (h * rsqrt(mean(h^2) + eps)) * g over M rows of H columns,
- * h in `dtype` with pitch ldh, x f32 with pitch ldx. */
+ * h in `dtype` with pitch ldh, x f32 with pitch ldx.
+ * The _packed / _rows forms are the kernels of om_gemma3_encoder_forward_packed alone, over the layout om_debug_mask_extent +
+ * om_debug_pack_rows describe: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (L stays the pitch of mask and decides band or
+ * full as above, so the packed launch runs the kernel body the padded launch of the batch runs; rows outside are neither read nor
+ * written), and the position of row t is row_map[t] % L (rows with row_map[t] < 0 are left as they are). */
 int om_debug_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads, int n_kv_heads,
                                 float scale, int w, void* stream);
 int om_debug_qknorm_rope_d256(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, const float* q_norm_g, const float* k_norm_g,
                               float eps, const float* inv_freq, float scaling, void* stream);
+int om_debug_attention_gqa_d256_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L, int n_heads,
+                                       int n_kv_heads, float scale, int w, void* stream);
+int om_debug_qknorm_rope_d256_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* q_norm_g,
+                                   const float* k_norm_g, float eps, const float* inv_freq, float scaling, const int* row_map, void* stream);
 int om_debug_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, void* stream);
 /* kmax[b] = 1 + the last unmasked key of mask row b (L when it has none) */
 int om_debug_mask_extent(const int64_t* mask, int64_t B, int L, int* kmax, void* stream);
@@ -647,9 +655,24 @@ int om_causal2_encoder_forward_packed(const OmCausalConfig2* cfg, const OmEncode
  *   ln1_g = 1 + input_layernorm.weight, ln2_g = 1 + pre_feedforward_layernorm.weight
  *   ffn1_w [F, H] gate_proj, ffn1g_w [F, H] up_proj, ffn2_w [H, F] down_proj
  * and a HOST array of n_layers OmGemma3Norms (device pointers, f32, each 1 + weight).
- * Padded rows only: no packed entry, no on-device pad skip, no training entry.
+ *
+ * om_gemma3_encoder_forward_packed: the same representations from PACKED rows, under the contract of om_causal_encoder_forward_packed --
+ * each sequence's rows up to its last unmasked token, back to back; ids and mask keep their [B, L] layout; packed_rows is the caller's
+ * bound on the token count, a multiple of 256, at most B * L + 255; a batch that holds more tokens returns NaN in every representation
+ * (checked on the device, nothing is read or written out of range).  The same launch sequence (one layer loop serves both entries)
+ * over packed_rows rows instead of B * L, in f32, f16 and bf16; a position is the token's COLUMN, so rotary phases survive packing; a
+ * sequence with leading pad tokens keeps them inside its extent, masked; a sliding layer takes the band kernel exactly when the padded
+ * entry would (decided on L, not on a sequence's extent).  Representations only: pooling FIRST or MEAN, no out_hidden.
+ * om_gemma3_encoder_packed_supported: 1 when the packed entry takes (cfg, B, L, packed_rows), else 0 -- the host layer asks and falls
+ * back to om_gemma3_encoder_forward.  1 iff the config passes the rules above, L <= 1024, packed_rows is a multiple of 256 and at most
+ * B * L + 255, and BOTH B * L and packed_rows lie above OM_OPT_GEMM_SKINNY_M: all five contractions of a layer are format-in /
+ * format-out, so a 16-bit call of at most that many rows plans the few-rows kernel where the padded call plans a wide tile.  Where
+ * the planner picks the same kernel family for both row counts on every contraction the two entries agree bit for bit (DESIGN.md
+ * section 8 lists the row counts where the families part).  Workspace: om_gemma3_encoder_workspace_bytes_packed (0 for a refused config).
+ * Not built: the on-device pad skip of the padded 16-bit entries (it rests on a row count only the whole-tile generation-7 kernels
+ * read; EmbeddingGemma's feed-forward width 1152 is no multiple of 256, so its contractions run on the generic tiles) and training.
  * ------------------------------------------------------------------------ */
-#define OM_ARCH_GEMMA3 5 /* OmGemma3Config.base.base.arch, served by om_gemma3_encoder_forward alone */
+#define OM_ARCH_GEMMA3 5 /* OmGemma3Config.base.base.arch, served by the om_gemma3_* entries alone */
 typedef struct OmGemma3Config {
   OmCausalConfig base;           /* at offset 0: arch, widths, n_kv_heads                                                             */
   float attn_scale;              /* config.query_pre_attn_scalar ** -0.5: a field of its own, not head_dim ** -0.5                   */
@@ -672,6 +695,11 @@ size_t om_gemma3_encoder_workspace_bytes(const OmGemma3Config* cfg, int64_t B, i
 int om_gemma3_encoder_forward(const OmGemma3Config* cfg, const OmEncoderWeights* w, const OmGemma3Norms* norms_host, const int64_t* input_ids,
                               const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace,
                               size_t workspace_bytes, void* stream);
+int om_gemma3_encoder_packed_supported(const OmGemma3Config* cfg, int64_t B, int64_t L, int64_t packed_rows);
+size_t om_gemma3_encoder_workspace_bytes_packed(const OmGemma3Config* cfg, int64_t B, int64_t L, int64_t packed_rows);
+int om_gemma3_encoder_forward_packed(const OmGemma3Config* cfg, const OmEncoderWeights* w, const OmGemma3Norms* norms_host,
+                                     const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows,
+                                     float* out_reps, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * One decoder position of a T5 encoder-decoder over the encoder's output (inference):

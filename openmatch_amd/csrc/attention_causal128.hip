@@ -296,3 +296,13 @@ extern "C" int om_debug_qknorm_rope_d256(int dtype, void* qkv, int64_t M, int L,
   if (debug_dtype(dtype)) return 1;
   return omk_qknorm_rope(dtype, qkv, M, L, n_heads, n_kv_heads, 256, q_norm_g, k_norm_g, eps, inv_freq, scaling, (hipStream_t)stream, nullptr, 1);
 }
+
+// the same over packed rows (tests/test_gemma3_packed_kernels.py): the position of row t is row_map[t] % L, rows with row_map[t] < 0 are
+// left as they are
+extern "C" int om_debug_qknorm_rope_d256_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* q_norm_g,
+                                              const float* k_norm_g, float eps, const float* inv_freq, float scaling, const int* row_map,
+                                              void* stream) {
+  if (!qkv || !inv_freq || !q_norm_g || !k_norm_g || !row_map) OM_FAIL("null argument");
+  if (debug_dtype(dtype)) return 1;
+  return omk_qknorm_rope(dtype, qkv, rows, L, n_heads, n_kv_heads, 256, q_norm_g, k_norm_g, eps, inv_freq, scaling, (hipStream_t)stream, row_map, 1);
+}

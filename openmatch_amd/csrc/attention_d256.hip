@@ -8,8 +8,16 @@
 //     (sequence, query head, 128-query block) walks 64-key chunks clipped to kmax[b] (keys at or past it are padding); with a band it
 //     walks only the keys [qb - w, qb + 127 + w] its queries can reach.  0 < w < L - 1 is the band (AttnBand), anything else full
 //     attention (AttnFull): a window that reaches every key never takes the band kernel, so the two give the same bits there.
-//     Padded layout only.  The bodies are attn_chunked256.h; four kernels: 16-bit x {full, band} per format, float32 x {full, band}.
+//     The bodies are attn_chunked256.h; 16-bit x {full, band} per format, float32 x {full, band}.
 //     A wave of either body holds more than 256 registers (no __launch_bounds__ second argument): one workgroup per CU.
+//
+//   * omk_attention_gqa_d256_packed: the same over PACKED rows, under the contract of attention_causal16_d128_packed_kernel: sequence b
+//     is rows cu[b] .. cu[b + 1] - 1 of qkv and ctx, the body's L and key extent are the sequence's own row count Lb, the mask row keeps
+//     the padded pitch (mask + b * L: masked tokens inside an extent stay masked).  The grid is the padded launch's; a workgroup whose
+//     query block starts at or past Lb returns before its first barrier, and row loads stay clamped to Lb - 1, so the last sequence
+//     reads nothing past the buffer.  Band or full is decided on the PADDED L, as above: the packed launch runs the body the padded
+//     launch of the same batch runs and agrees with it bit for bit on every row up to each extent.  Thin wrappers over the same two
+//     bodies: six more kernels with the padded ones' register counts and no scratch.
 #include "attn_chunked256.h"
 
 namespace {
@@ -44,30 +52,71 @@ __global__ __launch_bounds__(256) void attention_d256_32_kernel(
   attn_chunked32_d256<Policy>(gqa_rows_d256(qkv, ctx, b * L, heads, kv_heads, h), pol, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128, scale);
 }
 
+// packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1, the mask row keeps the padded pitch Lp; a query block at or past the
+// sequence's end leaves before it touches LDS or memory
 template <typename T, typename Policy>
-int launch16(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* kmax,
-             hipStream_t s) {
+__global__ __launch_bounds__(256) void attention_d256_16_packed_kernel(
+    const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale, Policy pol,
+    const int* __restrict__ cu) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int row0 = __builtin_amdgcn_readfirstlane(cu[b]);
+  const int Lb = __builtin_amdgcn_readfirstlane(cu[b + 1]) - row0;
+  const int qb = blockIdx.y * 128;
+  if (qb >= Lb) return;
+  attn_chunked16_d256<T, Policy>(gqa_rows_d256(qkv, ctx, (int64_t)row0, heads, kv_heads, h), pol, mask + b * Lp, Lb, Lb, qb, scale);
+}
+
+template <typename Policy>
+__global__ __launch_bounds__(256) void attention_d256_32_packed_kernel(
+    const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale, Policy pol,
+    const int* __restrict__ cu) {
+  const int h = blockIdx.x % heads;
+  const int64_t b = blockIdx.x / heads;
+  const int row0 = cu[b];
+  const int Lb = cu[b + 1] - row0;
+  const int qb = blockIdx.y * 128;
+  if (qb >= Lb) return;
+  attn_chunked32_d256<Policy>(gqa_rows_d256(qkv, ctx, (int64_t)row0, heads, kv_heads, h), pol, mask + b * Lp, Lb, Lb, qb, scale);
+}
+
+// ext: kmax [B] (padded rows) or cu [B + 1] (PACKED rows): one launch function per body for both forms
+template <typename T, typename Policy>
+int launch16(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* ext,
+             bool packed, hipStream_t s) {
+  if (packed) {
+    if (attn_lds_once<attention_d256_16_packed_kernel<T, Policy>>(kAttn16D256Lds)) return 1;
+    hipLaunchKernelGGL((attention_d256_16_packed_kernel<T, Policy>), grid, dim3(256), kAttn16D256Lds, s, (const T*)qkv, (T*)ctx, mask, L, heads,
+                       kv_heads, scale, pol, ext);
+    return 0;
+  }
   if (attn_lds_once<attention_d256_16_kernel<T, Policy>>(kAttn16D256Lds)) return 1;
   hipLaunchKernelGGL((attention_d256_16_kernel<T, Policy>), grid, dim3(256), kAttn16D256Lds, s, (const T*)qkv, (T*)ctx, mask, L, heads, kv_heads, scale,
-                     pol, kmax);
+                     pol, ext);
   return 0;
 }
 
 template <typename Policy>
-int launch32(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* kmax,
-             hipStream_t s) {
+int launch32(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* ext,
+             bool packed, hipStream_t s) {
+  if (packed) {
+    if (attn_lds_once<attention_d256_32_packed_kernel<Policy>>(kAttn32D256Lds)) return 1;
+    hipLaunchKernelGGL((attention_d256_32_packed_kernel<Policy>), grid, dim3(256), kAttn32D256Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads,
+                       kv_heads, scale, pol, ext);
+    return 0;
+  }
   if (attn_lds_once<attention_d256_32_kernel<Policy>>(kAttn32D256Lds)) return 1;
   hipLaunchKernelGGL((attention_d256_32_kernel<Policy>), grid, dim3(256), kAttn32D256Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads,
-                     scale, pol, kmax);
+                     scale, pol, ext);
   return 0;
 }
 
 template <typename Policy>
 int launch_policy(int dtype, const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol,
-                  const int* kmax, hipStream_t s) {
-  if (dtype == OM_F16) return launch16<f16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, kmax, s);
-  if (dtype == OM_BF16) return launch16<bf16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, kmax, s);
-  return launch32(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, kmax, s);
+                  const int* ext, bool packed, hipStream_t s) {
+  if (dtype == OM_F16) return launch16<f16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, ext, packed, s);
+  if (dtype == OM_BF16) return launch16<bf16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, ext, packed, s);
+  return launch32(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, ext, packed, s);
 }
 
 int check_args(int64_t B, int L, int heads, int kv_heads) {
@@ -79,19 +128,31 @@ int check_args(int64_t B, int L, int heads, int kv_heads) {
   return 0;
 }
 
-}  // namespace
-
-int omk_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale, int w,
-                           const int* kmax, hipStream_t s) {
+// both forms: the grid and the choice of body come from the PADDED L, so a packed launch runs what the padded launch of the batch runs
+int attention_gqa_d256_launch(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                              int w, const int* ext, bool packed, hipStream_t s) {
   if (B <= 0) return 0;
   if (check_args(B, L, heads, kv_heads)) return 1;
   const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
   int rc;
-  if (w > 0 && w < L - 1) rc = launch_policy(dtype, qkv, ctx, mask, grid, L, heads, kv_heads, scale, AttnBand{w}, kmax, s);
-  else rc = launch_policy(dtype, qkv, ctx, mask, grid, L, heads, kv_heads, scale, AttnFull{}, kmax, s);
+  if (w > 0 && w < L - 1) rc = launch_policy(dtype, qkv, ctx, mask, grid, L, heads, kv_heads, scale, AttnBand{w}, ext, packed, s);
+  else rc = launch_policy(dtype, qkv, ctx, mask, grid, L, heads, kv_heads, scale, AttnFull{}, ext, packed, s);
   if (rc) return 1;
   OM_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+int omk_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale, int w,
+                           const int* kmax, hipStream_t s) {
+  return attention_gqa_d256_launch(dtype, qkv, ctx, mask, B, L, heads, kv_heads, scale, w, kmax, false, s);
+}
+
+int omk_attention_gqa_d256_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                                  int w, const int* cu, hipStream_t s) {
+  if (B > 0 && !cu) OM_FAIL("attention (head_dim 256) over packed rows: the sequence offsets cu");
+  return attention_gqa_d256_launch(dtype, qkv, ctx, mask, B, L, heads, kv_heads, scale, w, cu, true, s);
 }
 
 // Test hook (tests/test_gemma3_kernels.py, tools/gemma3_bench.py): the kernels alone; the key extents go into the grow-only device
@@ -107,4 +168,12 @@ extern "C" int om_debug_attention_gqa_d256(int dtype, const void* qkv, void* ctx
   if (omk_causal_debug_kmax(B, &kmax)) return 1;
   if (omk_mask_extent(mask, B, L, kmax, s)) return 1;
   return omk_attention_gqa_d256(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, w, kmax, s);
+}
+
+// the packed kernels alone (tests/test_gemma3_packed_kernels.py, tools/gemma3_bench.py): cu [B + 1] as om_debug_pack_rows writes it
+extern "C" int om_debug_attention_gqa_d256_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                                  int n_heads, int n_kv_heads, float scale, int w, void* stream) {
+  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
+  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
+  return omk_attention_gqa_d256_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, w, cu, (hipStream_t)stream);
 }

@@ -77,6 +77,9 @@ int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_he
 // ctx [M, heads * 256], the caller's score scale; 0 < w < L - 1: key k visible from query q iff |q - k| <= w, else every unmasked key.
 int omk_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale, int w,
                            const int* kmax, hipStream_t s);
+// the same over packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv and ctx, L the pitch of mask (and what decides band or full)
+int omk_attention_gqa_d256_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
+                                  int w, const int* cu, hipStream_t s);
 // x[f32] += rms(h) * g over M rows of H columns (elementwise.hip): the norm of a sublayer OUTPUT h (compute dtype) added into the f32
 // residual stream (Gemma3's post_attention_layernorm / post_feedforward_layernorm); g = 1 + w from the host
 int omk_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s);

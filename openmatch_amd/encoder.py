@@ -616,8 +616,24 @@ def _pack_gemma3(model, code, device):
     return pk
 
 
-def _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden):
-    """hip_encode for a packed Gemma3TextModel: om_gemma3_encoder_forward over the B * L padded rows (it has no packed entry)."""
+def gemma3_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
+    """Whether om_gemma3_encoder_forward_packed takes this call (cfg: an OmGemma3Config) and pays: representations only, whole 256-row
+    tiles above the few-rows threshold with at least one tile saved -- a left-padded batch's bound is B * L, so it stays on the padded
+    entry -- and the library's own view (include/openmatch_hip.h om_gemma3_encoder_packed_supported).  OM_ENCODER_PACKED=0 keeps every
+    batch on the padded entry."""
+    if os.environ.get("OM_ENCODER_PACKED", "1") == "0":
+        return False
+    if want_hidden or pooling is None:
+        return False
+    skinny = N.lib().om_debug_option_value(N.OPT_GEMM_SKINNY_M)
+    if not (rows % 256 == 0 and skinny < rows <= (B * L) // 256 * 256 - 256):
+        return False
+    return bool(N.lib().om_gemma3_encoder_packed_supported(C.byref(cfg), B, L, rows))
+
+
+def _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
+    """hip_encode for a packed Gemma3TextModel: om_gemma3_encoder_forward_packed over `packed_rows` rows where gemma3_packed_rows_apply
+    admits the call, om_gemma3_encoder_forward over the B * L padded rows otherwise."""
     device = ids.device
     cfg = gemma3_config(pk.cfg, _POOL[pooling], normalize)
     B, L = ids.shape
@@ -626,9 +642,19 @@ def _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden):
     D = base.head_out if base.head_in > 0 else H
     lib = N.lib()
     norms = C.cast(pk.norms, C.POINTER(N.OmGemma3Norms)) if len(pk.norms) else None
-    LAST_CALL.update(rows=B * L, packed=False)
+    if packed_rows and not gemma3_packed_rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
+        packed_rows = None
+    LAST_CALL.update(rows=int(packed_rows) if packed_rows else B * L, packed=bool(packed_rows))
     with torch.cuda.device(device):
         reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
+        if packed_rows:
+            nbytes = lib.om_gemma3_encoder_workspace_bytes_packed(C.byref(cfg), B, L, int(packed_rows))
+            if not nbytes:
+                raise N.NativeError(lib.om_last_error().decode("utf-8", "replace"))
+            ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
+            N.check(lib.om_gemma3_encoder_forward_packed(C.byref(cfg), C.byref(pk.weights), norms, N.ptr(ids), N.ptr(mask), B, L, int(packed_rows),
+                                                         N.ptr(reps), C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+            return None, reps
         nbytes = lib.om_gemma3_encoder_workspace_bytes(C.byref(cfg), B, L)
         if not nbytes:
             raise N.NativeError(lib.om_last_error().decode("utf-8", "replace"))
@@ -932,7 +958,8 @@ def packed_rows_apply(cfg, B, L, rows, want_hidden, pooling, gated=False):
 def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, packed_rows=None):
     """(hidden [B,L,H], reps [B,D] f32) through om_encoder_forward.  `items` holds
     input_ids / attention_mask / optional token_type_ids as int64 device tensors.
-    packed_rows (with want_hidden=False): run om_encoder_forward_packed (Llama / Qwen2: om_causal_encoder_forward_packed) over
+    packed_rows (with want_hidden=False): run om_encoder_forward_packed (Llama / Qwen2 / Qwen3: om_causal[2]_encoder_forward_packed;
+    Gemma3TextModel: om_gemma3_encoder_forward_packed) over
     that many rows (packed_rows_bound of the mask, computed where the mask still lives on the host) instead of B * L padded ones."""
     check_pooling(model, pooling)
     ids = items["input_ids"]
@@ -952,7 +979,7 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     if _arch_of(model) == "causal":
         return _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
     if _arch_of(model) == "gemma3":
-        return _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden)
+        return _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
     _ensure_folded(pk, device)
     cfg = N.OmEncoderConfig(pooling=_POOL[pooling], normalize=int(bool(normalize)), **pk.cfg)
     B, L = ids.shape

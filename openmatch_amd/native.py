@@ -192,6 +192,10 @@ _SIGNATURES = {
     "om_debug_attention_gqa_d256": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "om_debug_qknorm_rope_d256": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(c_float), c_float,
                                           c_void_p]),
+    "om_debug_attention_gqa_d256_packed": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int,
+                                                   c_void_p]),
+    "om_debug_qknorm_rope_d256_rows": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(c_float),
+                                               c_float, c_void_p, c_void_p]),
     "om_debug_rmsnorm_add": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p]),
     "om_debug_mask_extent": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -264,6 +268,10 @@ _SIGNATURES = {
     "om_gemma3_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmGemma3Config), c_int64, c_int64]),
     "om_gemma3_encoder_forward": (c_int, [C.POINTER(OmGemma3Config), C.POINTER(OmEncoderWeights), C.POINTER(OmGemma3Norms), c_void_p, c_void_p,
                                           c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_gemma3_encoder_packed_supported": (c_int, [C.POINTER(OmGemma3Config), c_int64, c_int64, c_int64]),
+    "om_gemma3_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmGemma3Config), c_int64, c_int64, c_int64]),
+    "om_gemma3_encoder_forward_packed": (c_int, [C.POINTER(OmGemma3Config), C.POINTER(OmEncoderWeights), C.POINTER(OmGemma3Norms), c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_encoder_packed_supported": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int64, c_int64, c_int64]),
     "om_encoder_workspace_bytes_packed": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64, c_int64]),
     "om_encoder_forward_packed": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmEncoderWeights), c_void_p,
