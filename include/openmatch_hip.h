@@ -214,7 +214,11 @@ int om_debug_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B
                                       om_debug_encoder_skip_pad says so -- the rows up to each sequence's last unmasked token are packed back to back by
                                       a launch, and the persistent contractions read the token count from device memory (no copy to the host, no
                                       synchronisation); the representations keep their bits.  0 (A/B, tests): every contraction runs over all B * L rows */
-#define OM_OPT_COUNT 23
+#define OM_OPT_ENCODER_CLS_TAIL 23  /* 1 (default; env OM_ENCODER_CLS_TAIL): where om_debug_encoder_cls_tail says so, the fused BERT forward runs what follows
+                                      its LAST layer's attention (out-proj, FFN1, FFN2, their row statistics) over the B [CLS] rows that pooling
+                                      "first" reads -- gathered into roundup256(B) compact rows -- instead of every token row; the representations
+                                      keep their bits.  0 (A/B, tests): the last layer runs over every row like the others */
+#define OM_OPT_COUNT 24
 int om_debug_option(int opt, int value);
 /* the current value of a run-time switch (OM_OPT_*), so a test can restore exactly what it changed; -1 for an unknown option */
 int om_debug_option_value(int opt);
@@ -350,6 +354,18 @@ int om_debug_encoder_plan(const struct OmEncoderConfig* cfg, int gated_ffn, int 
  * the call plans OM_ENC_PATH_BERT_FUSED or OM_ENC_PATH_T5_FUSED, and om_encoder_packed_supported takes the bound roundup256(B * L).
  * 0 otherwise (a call the forward refuses included), -1 for a NULL cfg.  The plan word above does not change with it. */
 int om_debug_encoder_skip_pad(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int want_hidden);
+/* host only: 1 if om_encoder_forward (packed_rows == 0) or om_encoder_forward_packed would run its last layer's per-row tail over the
+ * [CLS] rows alone at the current switches (csrc/encoder_plan.h encoder_cls_tail): OM_OPT_ENCODER_CLS_TAIL is set, the
+ * call plans OM_ENC_PATH_BERT_FUSED without the eight-bit plane, pooling is OM_POOL_FIRST, no hidden states are wanted, n_layers >= 2,
+ * B >= 512 and 4 * roundup256(B) is at most the call's token rows in whole tiles.  0 otherwise (a call the forward refuses included),
+ * -1 for a NULL cfg.  The plan word and the workspace size do not change with it. */
+int om_debug_encoder_cls_tail(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
+                              int want_hidden);
+/* Test hook of the row gather behind it (csrc/kernels.h omk_gather_rows): output row r < Mc of every given destination copies source row
+ * idx(min(r, B - 1)), idx(b) = rows ? rows[b] : b * L.  Up to three 16-bit planes of H columns (src_i / dst_i, NULL pairs are skipped; H
+ * a multiple of 8, 16-byte aligned buffers) and one [., 2] f32 array (stats_src / stats_dst, or NULL). */
+int om_debug_gather_rows(const void* src0, void* dst0, const void* src1, void* dst1, const void* src2, void* dst2, const float* stats_src,
+                         float* stats_dst, const int* rows, int64_t B, int64_t L, int64_t Mc, int H, void* stream);
 /* host only: 1 if attention-probability dropout keeps (b, h, q, key) at rate p under `seed`; Lm is the mask's row pitch */
 int om_debug_attn_drop_keep(uint64_t seed, int64_t b, int h, int heads, int Lm, int q, int key, float p);
 /* self-check of the LayerNorm row reduction (csrc/ln_row.h): every group of 64 consecutive floats of `in` summed by the __shfl_xor butterfly

@@ -118,6 +118,8 @@ void opt_init() {
   g_opt[OM_OPT_FEW_ROWS_LN_FUSE] = e ? atoi(e) : 64;
   e = getenv("OM_ENCODER_SKIP_PAD");
   g_opt[OM_OPT_ENCODER_SKIP_PAD] = e ? atoi(e) : 1;
+  e = getenv("OM_ENCODER_CLS_TAIL");
+  g_opt[OM_OPT_ENCODER_CLS_TAIL] = e ? atoi(e) : 1;
   g_opt_init.store(true);
 }
 }  // namespace

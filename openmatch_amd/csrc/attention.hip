@@ -500,9 +500,13 @@ __global__ void mask_extent_kernel(const int64_t* __restrict__ mask, int64_t B, 
   if (lane == 0) kmax[b] = last ? last : L;
 }
 // packed rows: cu[0..B] = exclusive scan of kmax clamped to `rows`; row_map[t] = b * L + pos of packed row t (-1 for the pad rows
-// up to `rows`).  One workgroup (B is a few thousand at most).  More tokens than `rows`: the sequences past the bound get the
+// up to `rows`).  More tokens than `rows`: the sequences past the bound get the
 // rows that are left (possibly none) so that no kernel leaves the buffers, cu[B + 1] keeps the true count, and the pooling
 // tail turns every representation into NaN (omk_pack_overflow_poison) instead of returning a silently truncated batch.
+// One launch, the row_map fill spread over the rows: EVERY workgroup repeats the scan (thread j sums its `per` consecutive sequences, an
+// inclusive scan of the 1024 sums in LDS: B integers from L2), then fills its own 1024-row slices of row_map -- one row per thread,
+// consecutive threads consecutive rows -- by searching the scanned sums for the row's chunk of sequences and walking that chunk.
+// Workgroup 0 also writes cu and cls_rows as the single-workgroup kernel did.
 __global__ __launch_bounds__(1024) void pack_rows_kernel(const int* __restrict__ kmax, int64_t B, int L, int64_t rows, int* __restrict__ cu,
                                                           int* __restrict__ cls_rows, int* __restrict__ row_map) {
   __shared__ int part[1024];
@@ -518,23 +522,37 @@ __global__ __launch_bounds__(1024) void pack_rows_kernel(const int* __restrict__
     part[tid] += v;
     __syncthreads();
   }
-  int run = part[tid] - sum;                       // exclusive prefix of this thread's rows
-  const int cap = (int)rows;
-  for (int64_t i = lo; i < hi; ++i) {
-    cu[i] = run < cap ? run : cap;
-    cls_rows[i] = run < cap ? run : cap - 1;
-    const int n = kmax[i];
-    for (int k = 0; k < n; ++k) if (run + k < cap) row_map[run + k] = (int)(i * L + k);
-    run += n;
-  }
   const int total = part[1023];
-  if (tid == 1023) { cu[B] = total < cap ? total : cap; cu[B + 1] = total; }
-  for (int64_t t = total + tid; t < rows; t += 1024) row_map[t] = -1;
+  const int cap = (int)rows;
+  if (blockIdx.x == 0) {
+    int run = part[tid] - sum;                     // exclusive prefix of this thread's sequences
+    for (int64_t i = lo; i < hi; ++i) {
+      cu[i] = run < cap ? run : cap;
+      cls_rows[i] = run < cap ? run : cap - 1;
+      run += kmax[i];
+    }
+    if (tid == 1023) { cu[B] = total < cap ? total : cap; cu[B + 1] = total; }
+  }
+  for (int64_t t = (int64_t)blockIdx.x * 1024 + tid; t < rows; t += (int64_t)gridDim.x * 1024) {
+    int v = -1;
+    if (t < total) {
+      // the first chunk j whose inclusive sum exceeds t holds row t (chunks of no tokens are passed over)
+      int a = 0, b = 1023;
+      while (a < b) { const int m = (a + b) >> 1; if (part[m] > (int)t) b = m; else a = m + 1; }
+      int64_t i = a * per;
+      int run = a ? part[a - 1] : 0;
+      for (int n = kmax[i]; run + n <= (int)t; n = kmax[++i]) run += n;
+      v = (int)(i * L + ((int)t - run));
+    }
+    row_map[t] = v;
+  }
 }
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s) {
   if (B <= 0) return 0;
   if (rows > 0x7fffffff || B * (int64_t)L > 0x7fffffff) OM_FAIL("packed rows: token counts below 2^31");
-  hipLaunchKernelGGL(pack_rows_kernel, dim3(1), dim3(1024), 0, s, kmax, B, L, rows, cu, cls_rows, row_map);
+  const int64_t slices = (rows + 1023) / 1024;
+  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)(slices < 1 ? 1 : slices > 1024 ? 1024 : slices)), dim3(1024), 0, s, kmax, B, L, rows, cu, cls_rows,
+                     row_map);
   OM_LAUNCH_CHECK();
   return 0;
 }

@@ -377,6 +377,52 @@ int omk_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, h
   return 0;
 }
 
+// Row gather of the [CLS] tail (kernels.h omk_gather_rows).  One thread per 16-byte vector of an output row: H / 8 consecutive threads
+// copy one row of each plane (coalesced on both sides), the first of them also the row's statistics pair.  blockDim.x is a multiple of
+// H / 8 up to 256, so a workgroup holds whole rows and the grid is Mc / (rows per workgroup): hundreds of workgroups for Mc >= 512.
+struct GatherArgs { const uint4* src[3]; uint4* dst[3]; const float2* st_src; float2* st_dst; };
+__global__ __launch_bounds__(256) void gather_rows_kernel(GatherArgs a, const int* __restrict__ rows, int64_t B, int64_t L, int64_t Mc, int vec) {
+  const int rpb = blockDim.x / vec;                      // rows per workgroup
+  const int64_t r = (int64_t)blockIdx.x * rpb + threadIdx.x / vec;
+  const int v = threadIdx.x % vec;
+  if (r >= Mc) return;
+  const int64_t b = r < B ? r : B - 1;
+  const int64_t sr = rows ? (int64_t)rows[b] : b * L;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+    if (a.src[p]) a.dst[p][r * vec + v] = a.src[p][sr * vec + v];
+  if (v == 0 && a.st_src) a.st_dst[r] = a.st_src[sr];
+}
+int omk_gather_rows(const GatherPlane (&planes)[3], const float* stats_src, float* stats_dst, const int* rows, int64_t B, int64_t L, int64_t Mc,
+                    int H, hipStream_t s) {
+  if (B <= 0 || Mc <= 0) return 0;
+  if (H < 8 || H % 8 || L < 1) OM_FAIL("row gather: rows of whole 16-byte vectors");
+  GatherArgs a = {};
+  uintptr_t align = (uintptr_t)stats_src | (uintptr_t)stats_dst;
+  for (int p = 0; p < 3; ++p) {
+    if (!planes[p].src || !planes[p].dst) continue;
+    a.src[p] = (const uint4*)planes[p].src; a.dst[p] = (uint4*)planes[p].dst;
+    align |= (uintptr_t)planes[p].src | (uintptr_t)planes[p].dst;
+  }
+  if (stats_src && stats_dst) { a.st_src = (const float2*)stats_src; a.st_dst = (float2*)stats_dst; }
+  if (align & 15) OM_FAIL("row gather: 16-byte aligned buffers");
+  const int vec = H / 8;
+  const int threads = vec >= 256 ? vec : 256 / vec * vec;
+  if (threads > 256) OM_FAIL("row gather: at most 2048 columns");
+  const int64_t grid = (Mc + threads / vec - 1) / (threads / vec);
+  if (grid > 0x7fffffffLL) OM_FAIL("row gather: too many rows for one launch");
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)grid), dim3(threads), 0, s, a, rows, B, L, Mc, vec);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int om_debug_gather_rows(const void* src0, void* dst0, const void* src1, void* dst1, const void* src2, void* dst2, const float* stats_src,
+                                    float* stats_dst, const int* rows, int64_t B, int64_t L, int64_t Mc, int H, void* stream) {
+  if (!src0 || !dst0) OM_FAIL("om_debug_gather_rows: null argument");
+  if (B < 1 || Mc < B) OM_FAIL("om_debug_gather_rows: 1 <= B <= Mc");
+  const GatherPlane planes[3] = {{src0, dst0}, {src1, dst1}, {src2, dst2}};
+  return omk_gather_rows(planes, stats_src, stats_dst, rows, B, L, Mc, H, (hipStream_t)stream);
+}
+
 // x in f32 (a residual stream kept in f32 under a 16-bit compute format: encoder_causal.hip) -> y in the compute format
 int omk_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
                            float eps, int rms, hipStream_t s) {

@@ -217,6 +217,18 @@ extern "C" int om_debug_encoder_skip_pad(const OmEncoderConfig* c, int gated_ffn
   return encoder_skip_pad(in, encoder_plan(in, sw), sw) ? 1 : 0;
 }
 
+// host only: whether a forward would run its last layer's per-row tail over the [CLS] rows alone (include/openmatch_hip.h)
+extern "C" int om_debug_encoder_cls_tail(const OmEncoderConfig* c, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
+                                         int want_hidden) {
+  if (!c) {
+    om_set_error("om_debug_encoder_cls_tail: null argument");
+    return -1;
+  }
+  const EncPlanIn in = {c, B, L, packed_rows, want_hidden != 0, gated_ffn != 0, has_rel_bias != 0, c->type_vocab > 0};
+  const EncSwitches sw = encoder_switches();
+  return encoder_cls_tail(in, encoder_plan(in, sw), sw) ? 1 : 0;
+}
+
 extern "C" int om_t5_relative_bucket(int relative_position, int num_buckets, int max_distance) {
   // bidirectional: half the buckets for each sign; exact below max_exact, log-spaced above
   int nb = num_buckets / 2;
@@ -251,6 +263,7 @@ struct EncCall {
   hipStream_t s;
   const int* rows_dev;    // a padded call that skips its pad rows: &cu[B], the token count on the device, for every contraction of the
                           //   fused loops (GemmEpilogue::rows_dev); else NULL
+  int64_t cls_mc;         // > 0 (encoder_cls_tail): bert_fused runs its last layer's per-row tail over this many compact rows, the [CLS] rows
 };
 
 // Where a layer loop left the stream that the last normalisation reads (final_norm below).
@@ -263,6 +276,7 @@ struct EncStream {
   void* spare;            //   where the normalised rows go in the compute type when the caller gave no out_hidden
   char* hidden;           // x == NULL: the rows in the compute type as they are (a BERT stack of no layers), or already normalised
   const float* rows32;    //   ... in both forms (the two omk_layernorm_dual paths): their f32 copy, all M rows
+  bool cls_compact;       // x / x_lo hold the B [CLS] rows alone, row b = sequence b, pitch H (bert_fused under encoder_cls_tail)
 };
 
 #define GEMM(A_, lda_, W_, ldw_, C_, ldc_, N_, K_, bias_, res_, ldr_, act_)                        \
@@ -284,7 +298,7 @@ struct EncStream {
   const int F1 = enc_ffn1_cols(c), act1 = nomic ? OM_ACT_NONE : c->act;                                             \
   const void* const ffa = nomic ? ws.ff2 : ws.ff
 #define NOMIC_ROPE() do { if (nomic) RUN(omk_rope(dt, ws.qkv, M, (int)L, H, c->rope_theta_global, s, k.row_map)); } while (0)
-#define NOMIC_SWIGLU() do { if (nomic) RUN(omk_swiglu_rows(dt, ws.ff, ws.ff2, Mg, F, s)); } while (0)
+#define NOMIC_SWIGLU(rows_) do { if (nomic) RUN(omk_swiglu_rows(dt, ws.ff, ws.ff2, rows_, F, s)); } while (0)
 
 // LayerNorm fused across the GEMMs (16-bit, large batches): the LayerNorm outputs are never
 // written.  The GEMM that produces a pre-LayerNorm sum y also accumulates its row statistics; the
@@ -313,12 +327,30 @@ static int bert_fused(const EncCall& k, EncStream* out) {
   // memory-side cache instead of HBM.  OM_OPT_ENCODER_PINGPONG = 0 walks every kernel first row to last.
   const bool pingpong = k.p.pingpong;
   int walk = 1;               // the embedding kernel wrote first row to last
+  // [CLS] rows of the last layer (encoder_plan.h encoder_cls_tail): after that layer's attention every launch is per-row work and
+  // pooling "first" reads B rows, so the rows are gathered -- Mc = roundup256(B) of them, the pad replicating sequence B - 1 -- and the
+  // three contractions run one or a few tiles each, with the epilogue fields of the full-row launches: a row's bits do not depend on
+  // the tile it sits in.  The compact buffers live in ws.qkv, dead once attention has read it (seven planes [Mc, H] and two statistics
+  // arrays against [Mp, 3H]: the rule's 4 Mc <= Mp); FFN1's compact output takes the head of ws.ff, dead as well.
+  const int64_t Mc = k.cls_mc;
+  const size_t cplane = (size_t)Mc * H * 2;
+  char* const cbase = ws.qkv;
+  float* const cst2p = (float*)(cbase + 7 * cplane);
+  float* const cst1 = cst2p + 2 * Mc;
+  if (Mc > 0 && ((char*)(cst1 + 2 * Mc) > ws.qkv + (size_t)Mg * 3 * H * 2 || Mc > Mg || c->n_layers < 2 || lo8))
+    OM_FAIL("[CLS] tail: the compact buffers do not fit the qkv area");
 #define OM_WALK() (pingpong ? (walk ^= 1, walk ^ 1) : 0)
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
-    float* st1 = ws.stats1 + (size_t)l * Mg * 2;                     // LN1 of this layer
+    const bool last = l == c->n_layers - 1, tail = last && Mc > 0;
+    float* st1 = tail ? cst1 : ws.stats1 + (size_t)l * Mg * 2;      // LN1 of this layer
     float* st2 = ws.stats2 + (size_t)l * Mg * 2;                     // LN2 of this layer
     const float* st2p = l ? ws.stats2 + (size_t)(l - 1) * Mg * 2 : nullptr;   // LN2 of the previous one
+    // what the three per-row contractions read and write: the full-height buffers, or under `tail` their compact counterparts
+    const int64_t Mr = tail ? Mc : Mg;
+    const int* const rdev = tail ? nullptr : k.rows_dev;
+    const char *ctx = ws.ctx, *xin = ws.x1, *xin_lo = ws.x1_lo;
+    char *y = ws.y, *y_lo = ws.y_lo, *xout = ws.x1, *xout_lo = ws.x1_lo;
     GemmEpilogue e = {};
     // ---- QKV: x0 for the first layer, LN2_{l-1}(y2) folded afterwards
     if (l == 0) {
@@ -333,40 +365,48 @@ static int bert_fused(const EncCall& k, EncStream* out) {
     }
     NOMIC_ROPE();
     RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, OM_WALK(), ws.kmax, k.cu));
+    if (tail) {
+      const GatherPlane planes[3] = {{ws.ctx, cbase}, {ws.x1, cbase + cplane}, {two ? ws.x1_lo : nullptr, cbase + 2 * cplane}};
+      RUN(omk_gather_rows(planes, st2p, cst2p, k.cu ? ws.cls_rows : nullptr, B, L, Mc, H, s));
+      ctx = cbase; xin = cbase + cplane; xin_lo = cbase + 2 * cplane; st2p = cst2p;
+      y = cbase + 3 * cplane; y_lo = cbase + 4 * cplane; xout = cbase + 5 * cplane; xout_lo = cbase + 6 * cplane;
+    }
     // ---- attention output + residual -> y1, statistics of LN1
     e = GemmEpilogue{};
     e.bias = lw.o_b; e.ldr = H; e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
-    if (two) { e.out_lo = ws.y_lo; e.lo8 = lo8; }
+    if (two) { e.out_lo = y_lo; e.lo8 = lo8; }
     if (l == 0) {
       e.resid = ws.x;                    // the embedding output: one plane
     } else {
       const OmLayerWeights& pw = Ls[l - 1];
-      e.resid = ws.x1; e.rln_stats = st2p; e.rln_g = pw.ln2_g; e.rln_b = pw.ln2_b;
-      if (two) e.resid_lo = ws.x1_lo;
+      e.resid = xin; e.rln_stats = st2p; e.rln_g = pw.ln2_g; e.rln_b = pw.ln2_b;
+      if (two) e.resid_lo = xin_lo;
     }
-    e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
-    RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.y, H, Mg, H, H, e, s));
-    RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st1, s));
+    e.reverse = OM_WALK(); e.rows_dev = rdev;
+    RUN(omk_gemm(dt, ctx, H, lw.o_w, H, dt, y, H, Mr, H, H, e, s));
+    RUN(omk_ln_stats_reduce(ws.slots, nslots, Mr, st1, s));
     // ---- FFN1 on LN1(y1), folded
     const void* wf1; const float *cs1, *bf1;
     RUN(folded_weights(c, k.w, l, true, lw.ffn1_w, lw.ln1_g, lw.ln1_b, lw.ffn1_b, F1, H, ws.wfold, ws.colsum, ws.bfold, s, &wf1, &cs1, &bf1));
     e = GemmEpilogue{};
     e.bias = bf1; e.act = act1; e.ln_stats = st1; e.ln_colsum = cs1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
-    e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
-    RUN(omk_gemm(dt, ws.y, H, wf1, H, dt, ws.ff, F1, Mg, F1, H, e, s));
-    NOMIC_SWIGLU();
+    e.reverse = OM_WALK(); e.rows_dev = rdev;
+    RUN(omk_gemm(dt, y, H, wf1, H, dt, ws.ff, F1, Mr, F1, H, e, s));
+    NOMIC_SWIGLU(Mr);
     // ---- FFN2 + LN1(y1) as the residual -> y2, statistics of LN2
     e = GemmEpilogue{};
-    e.bias = lw.ffn2_b; e.resid = ws.y; e.ldr = H; e.rln_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
+    e.bias = lw.ffn2_b; e.resid = y; e.ldr = H; e.rln_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
     e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
-    if (two) { e.resid_lo = ws.y_lo; e.out_lo = ws.x1_lo; e.lo8 = lo8; }
-    e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
-    RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, ws.x1, H, Mg, H, F, e, s));
-    RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
+    if (two) { e.resid_lo = y_lo; e.out_lo = xout_lo; e.lo8 = lo8; }
+    e.reverse = OM_WALK(); e.rows_dev = rdev;
+    RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, xout, H, Mr, H, F, e, s));
+    // (the last layer's LN2 is final_norm's, which computes its own statistics: the slots the kernel had to write are not reduced)
+    if (!last) RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
   }
 #undef OM_WALK
-  const OmLayerWeights& last = Ls[c->n_layers - 1];
-  *out = EncStream{ws.x1, two ? ws.x1_lo : nullptr, lo8, last.ln2_g, last.ln2_b, 0, ws.x};
+  const OmLayerWeights& lastw = Ls[c->n_layers - 1];
+  *out = EncStream{ws.x1, two ? ws.x1_lo : nullptr, lo8, lastw.ln2_g, lastw.ln2_b, 0, ws.x};
+  if (Mc > 0) { out->x = cbase + 5 * cplane; out->x_lo = two ? cbase + 6 * cplane : nullptr; out->cls_compact = true; }
   return 0;
 }
 
@@ -401,7 +441,7 @@ static int bert_pending_ln(const EncCall& k, EncStream* out) {
     e.bias = lw.ffn1_b; e.act = act1; e.ln_eps = c->ln_eps;
     e.a_ln32 = y_a; e.a_ln_g = lw.ln1_g; e.a_ln_b = lw.ln1_b; e.a_ln_stats_out = st1;
     RUN(omk_gemm(dt, ws.x1, H, lw.ffn1_w, H, dt, ws.ff, F1, Mg, F1, H, e, s));
-    NOMIC_SWIGLU();
+    NOMIC_SWIGLU(Mg);
     e = GemmEpilogue{};
     e.bias = lw.ffn2_b; e.ldr = H; e.out32 = y_b; e.ln_eps = c->ln_eps;
     e.rln32 = y_a; e.rln32_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
@@ -435,7 +475,7 @@ static int bert_few32(const EncCall& k, EncStream* out) {
     RUN(omk_gemm(dt, ws.ctx, H, lw.o_w, H, dt, ws.y, H, Mg, H, H, e, s));                  // y32 = ctx Wo^T + b + x (f32)
     RUN(omk_layernorm_dual(dt, ws.y32, H, ws.x1, ws.r32b, H, lw.ln1_g, lw.ln1_b, M, H, c->ln_eps, s));
     GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F1, F1, H, lw.ffn1_b, nullptr, 0, act1);
-    NOMIC_SWIGLU();
+    NOMIC_SWIGLU(Mg);
     e = GemmEpilogue{};
     e.bias = lw.ffn2_b; e.resid32 = ws.r32b; e.ldr = H; e.out32 = ws.y32;
     RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, ws.y, H, Mg, H, F, e, s));                   // y32 = ff W2^T + b + x1 (f32)
@@ -463,7 +503,7 @@ static int bert_plain(const EncCall& k, EncStream* out) {
     GEMM(ws.ctx, H, lw.o_w, H, ws.y, H, H, H, lw.o_b, ws.x, H, OM_ACT_NONE);
     RUN(omk_layernorm(dt, ws.y, H, ws.x1, H, lw.ln1_g, lw.ln1_b, M, H, c->ln_eps, 0, s));
     GEMM(ws.x1, H, lw.ffn1_w, H, ws.ff, F1, F1, H, lw.ffn1_b, nullptr, 0, act1);
-    NOMIC_SWIGLU();
+    NOMIC_SWIGLU(Mg);
     GEMM(ffa, F, lw.ffn2_w, F, ws.y, H, H, F, lw.ffn2_b, ws.x1, H, OM_ACT_NONE);
   }
   *out = EncStream{};
@@ -588,8 +628,8 @@ static int final_norm(const EncCall& k, const EncStream& n, char** hidden, const
     *hidden = (char*)dst;
   }
   if (pooled32 && c->pooling == OM_POOL_FIRST) {
-    const int* rows = k.cu ? ws.cls_rows : nullptr;
-    RUN(omk_layernorm_f32out(dt, n.x, rows ? H : L * H, ws.final32, H, n.g, n.b, B, H, c->ln_eps, n.rms, s, n.x_lo, rows, n.lo8));
+    const int* rows = k.cu && !n.cls_compact ? ws.cls_rows : nullptr;
+    RUN(omk_layernorm_f32out(dt, n.x, rows || n.cls_compact ? H : L * H, ws.final32, H, n.g, n.b, B, H, c->ln_eps, n.rms, s, n.x_lo, rows, n.lo8));
     *n32 = B;
   } else if (pooled32) {
     RUN(omk_layernorm_f32out(dt, n.x, H, ws.final32, H, n.g, n.b, M, H, c->ln_eps, n.rms, s, n.x_lo, nullptr, n.lo8));
@@ -698,6 +738,8 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
     }
   }
   const bool packed = pack_bound > 0;      // the token axis holds packed rows
+  int64_t cls_mc = 0;                      // the last layer's per-row tail over the [CLS] rows alone (encoder_plan.h encoder_cls_tail)
+  if (!encoder_cls_tail(plan_in, plan, sw, &cls_mc)) cls_mc = 0;
   const int* const row_map = packed ? ws.row_map : nullptr;
 
   RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
@@ -720,8 +762,8 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
     RUN(omk_embed(dt, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
 
   const EncCall k = {c, w, attention_mask, B, L, plan, ws, plan.rel_bias ? ws.posbias : nullptr, packed ? ws.cu : nullptr, row_map, out_hidden, s,
-                     skip ? ws.cu + B : nullptr};
-  EncStream stream_out;
+                     skip ? ws.cu + B : nullptr, cls_mc};
+  EncStream stream_out = {};
   switch (plan.path) {
     case OM_ENC_PATH_BERT_FUSED: RUN(bert_fused(k, &stream_out)); break;
     case OM_ENC_PATH_BERT_PENDING_LN: RUN(bert_pending_ln(k, &stream_out)); break;

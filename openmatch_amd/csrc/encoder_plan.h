@@ -18,13 +18,14 @@ struct EncSwitches {
   int few_ln_fuse;    // OM_OPT_FEW_ROWS_LN_FUSE: most rows of the pending-LayerNorm path
   int attention_fast; // OM_OPT_ATTENTION_FAST: read by om_encoder_packed_supported only (attn_plan.h decides the attention kernel itself)
   int skip_pad;       // OM_OPT_ENCODER_SKIP_PAD: read by encoder_skip_pad only (the plan itself does not change with it)
+  int cls_tail;       // OM_OPT_ENCODER_CLS_TAIL: read by encoder_cls_tail only (likewise)
 };
 
 // every switch the planner reads, read once per call (omk_gemm_ln_fusable reads OM_OPT_GEMM_VARIANT and om_debug_gemm_gen itself)
 static EncSwitches encoder_switches() {
   return EncSwitches{om_option(OM_OPT_ENCODER_FUSED_LN), om_option(OM_OPT_ENCODER_TWO_PLANE), om_option(OM_OPT_ENCODER_PINGPONG),
                      om_option(OM_OPT_GEMM_SKINNY_M), om_option(OM_OPT_FEW_ROWS_LN_FUSE), om_option(OM_OPT_ATTENTION_FAST),
-                     om_option(OM_OPT_ENCODER_SKIP_PAD)};
+                     om_option(OM_OPT_ENCODER_SKIP_PAD), om_option(OM_OPT_ENCODER_CLS_TAIL)};
 }
 
 struct EncPlanIn {
@@ -228,4 +229,21 @@ static bool encoder_skip_pad(const EncPlanIn& in, const EncPlan& p, const EncSwi
   if (!sw.skip_pad || in.packed_rows != 0 || in.want_hidden || in.c->pooling == OM_POOL_NONE) return false;
   if (p.error || (p.path != OM_ENC_PATH_BERT_FUSED && p.path != OM_ENC_PATH_T5_FUSED)) return false;
   return encoder_packed_ok(in.c, in.gated_ffn, in.B, in.L, p.Mp, sw);      // (p.Mp = roundup256(B * L) on a fused path)
+}
+
+// Whether a call whose plan is p runs the per-row tail of its LAST layer -- out-proj, FFN1, FFN2 and the two statistics reductions,
+// everything after the last attention -- over the B [CLS] rows alone ("[CLS] rows of the last layer").  Pooling "first"
+// reads nothing else of that layer, and after attention no row sees another.  The rule, stated once: the switch is on, the call plans
+// the fused BERT path with 16-bit second planes (the eight-bit plane is stored tile by tile: not worth a gather), pooling is "first",
+// no hidden states are wanted, there are at least two layers, B >= 512 (below that the compact launches would be mostly pad rows and
+// the forward is launch-bound anyway), and the compact height Mc = roundup256(B) is at most a quarter of the buffers' (else the gain
+// is not worth three launches; it is also what lets the compact buffers alias the dead qkv area, encoder.hip).  All three entry
+// forms -- padded with or without pad-skip, packed -- plan alike: Mp covers each.  *Mc: the compact height where the rule holds.
+static bool encoder_cls_tail(const EncPlanIn& in, const EncPlan& p, const EncSwitches sw, int64_t* Mc = nullptr) {
+  if (!sw.cls_tail || p.error || p.path != OM_ENC_PATH_BERT_FUSED || p.lo8) return false;
+  if (in.c->pooling != OM_POOL_FIRST || in.want_hidden || in.c->n_layers < 2 || in.B < 512) return false;
+  const int64_t mc = (in.B + 255) / 256 * 256;
+  if (4 * mc > p.Mp) return false;
+  if (Mc) *Mc = mc;
+  return true;
 }

@@ -162,6 +162,13 @@ __host__ __device__ inline size_t omk_lo8_offset(int64_t m, int64_t n, int64_t N
 }
 // (sum, sum of squares) per row from the slot partials a GEMM with stats_out left: out[m] = sum over slots, in slot order
 int omk_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, hipStream_t s);
+// The rows pooling "first" reads, gathered (encoder_plan.h encoder_cls_tail): output row r < Mc of every destination copies source row
+// idx(min(r, B - 1)), idx(b) = rows ? rows[b] : b * L -- the rows past B replicate sequence B - 1's, so every compact row is finite data
+// that already existed.  Up to three 16-bit planes [., H] (a NULL src or dst: that pair is skipped) and one [., 2] f32 statistics array.
+// H a multiple of 8, buffers 16-byte aligned; the destinations must not overlap the sources.
+struct GatherPlane { const void* src; void* dst; };
+int omk_gather_rows(const GatherPlane (&planes)[3], const float* stats_src, float* stats_dst, const int* rows, int64_t B, int64_t L, int64_t Mc,
+                    int H, hipStream_t s);
 // What omk_gemm's planner (gemm_plan.h) decided: the kernel family (OM_GEMM_FAMILY_*; 0: launch nothing -- an empty problem, or a
 // refusal with its reason in `error`) and the kernel coordinates the launchers switch on.  Generation 7's launchers take it as it is.
 struct GemmPlan { int family; const char* error; int act /* ep.act & 0xff */; bool resid, train /* ep.pre_act or dropout */; int lnf /* gemm_lnf */; };

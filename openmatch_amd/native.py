@@ -208,6 +208,9 @@ _SIGNATURES = {
     "om_debug_attention_bwd_stats_bytes": (c_size_t, [c_int64, c_int]),
     "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "om_debug_encoder_skip_pad": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int]),
+    "om_debug_encoder_cls_tail": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
+    "om_debug_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                     c_int64, c_int, c_void_p]),
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "om_debug_row_kernel_last": (c_int, []),
