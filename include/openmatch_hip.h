@@ -944,8 +944,24 @@ int om_sim_topk(int mode, const float* queries, int64_t n_queries, const float* 
 /* Diagnostics of the calling thread's last om_sim_topk: out[0] = scan precision that produced
  * the result (0 f32, 1 f16+rescore), [1] = scan rounds, [2] = overflow fallbacks (chunks redone
  * densely), [3] = longest candidate list, [4] = 1 if the certified f16 margin was too wide and
- * the call fell back to the f32 scan. */
+ * the call fell back to the f32 scan, [5] = OM_SCAN_FAMILY_* of the last filtered-scan round
+ * (0: every row was scored densely). */
 void om_sim_topk_info(int64_t out[8]);
+
+/* Which kernel a filtered-scan round of om_sim_topk runs (csrc/search_plan.h scan_plan: no launch, no HIP call, no pointer read). */
+#define OM_SCAN_FAMILY_GENERIC 1   /* sim_filter_kernel: the 128-query tile of generation 2 (also the ragged tail behind a stream kernel)      */
+#define OM_SCAN_FAMILY_WIDE 2      /* more than 128 queries: the 256 x 256 kernels (generation 7 / 7c / 7c16 over whole tiles, generation 6)  */
+#define OM_SCAN_FAMILY_STREAM32 3  /* sim_stream_reg_kernel: 32-query blocks resident in registers, f16 index, 256 <= d <= 1024, <= 128 queries */
+#define OM_SCAN_FAMILY_STREAM16 4  /* sim_stream_reg_kernel<.., 32, 16>: 16-query blocks on 16 x 16 x 32 MFMAs, 1088 <= d <= 2048, <= 64 queries         */
+/* half: the 16-bit index (OM_SEARCH_F16_RESCORE) or the float32 one.  out = {family, queries per resident block (32 | 16 | 0), resident
+ * blocks per workgroup (1 | 2 | 4 | 0), K steps of 64 columns compiled in (12 | 16 | 32 | 0)}, under the calling thread's switches. */
+int om_debug_scan_plan(int half, int64_t nq, int d, int out[4]);
+/* One launch of exactly the stream instantiation om_debug_scan_plan names for (nq, d): rows16 [nrows, d] f16 with nrows a multiple of 128
+ * (row r has id row_base + r), queries16 [>= nq, d] f16 as om_sim_topk's query preparation leaves them, thr[q] the score a row must
+ * reach (128 floats, +inf beyond nq), keys [nq][8192] and cnt [nq] the candidate lists (cnt counts every survivor, keys holds the
+ * first 8192 as (orderable score) << 32 | ~id), on `grid` persistent workgroups.  Refuses a shape the plan sends elsewhere. */
+int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,
+                        uint64_t* keys, unsigned* cnt, int grid, void* stream);
 
 /* Merge W partial results (utils.py:215-229 merge_retrieval_results_by_score /
  * faiss shard merge): parts are [W][Q,k_in] row-major, each row descending;

@@ -26,6 +26,7 @@
 #include "gemm_core6.h"
 #include "gemm_wide7.h"
 #include "kernels.h"
+#include "search_plan.h"
 
 #define SORT_CAP 8192      // keys one workgroup sorts in LDS (64 KiB)
 #define DENSE_CHUNK 4096   // rows scored densely per bootstrap / fallback step
@@ -741,15 +742,196 @@ __global__ __launch_bounds__(G6_THREADS) void sim_filter_kernel7c16(
 #define SR_UBYTES (SR_UROWS * G7_ROW_BYTES)
 #define SR_LDS (SR_RING * SR_UBYTES)
 #define SR_IPU (SR_UROWS / 32)                  // DMA instructions per wave and unit
-#define SR_NKMAX 12
-// DBG (timing probes only, OM_OPT_SEARCH_DEBUG bits 3 / 4; the results are wrong): 1 = every second MFMA sub-step skipped (does
-// the pass's time follow its matrix-core work?), 2 = no MFMA at all
-template <typename T, int NB, int DBG = 0>
-__global__ __launch_bounds__(G6_THREADS) void sim_stream_reg_kernel(
+
+// The pass of sim_stream_reg_kernel (below) for 1088 <= d <= 2048 (round 7), its QB = 16 body.  A 32-query block at d = 2048 is 128 KiB, a
+// wave's whole register file; a SIXTEEN-query block on 16 x 16 x 32 MFMAs is d / 8 registers, 256 at d = 2048, and its accumulators are 4
+// registers per 16-row block:
+//     NB = 1 (Q <= 16)    the four waves share the block and take 32 rows of a unit each (two 16-row blocks)
+//     NB = 2 (Q <= 32)    waves 0, 2 / 1, 3 hold block 0 / 1 and take 64 rows each
+//     NB = 4 (Q <= 64)    one block per wave, every wave takes all 128 rows
+// Operand A = index rows (lane: row lane & 15, k 8 (lane >> 4) + j of the 32-wide sub-step), B = the query block (same map), so
+// acc[rt][r] = <row 16 rt + 4 (lane >> 4) + r of the wave's share, query 16 nb + (lane & 15)>: the layout sim_filter_kernel7c16 filters.
+// Ring, DMA swizzle (row r keeps source chunk c at c ^ ((r >> 1) & 7); r & 15 = lane & 15 here), non-temporal stream, split append and
+// end-of-launch retire are those of the 32-query body; a K step is two sub-steps instead of four, and a lane has ONE list (its query) for
+// all its 8 NB scores of a tile, so one atomic per lane and tile.  Registers: the 4 RB accumulators are pinned into the accumulation half
+// with the fragments of the first 32 - NB K steps (8 registers each), the last NB K steps' fragments into the other half.
+template <typename T, int NB>
+__device__ __forceinline__ void sim_stream_reg16_body(
     const T* __restrict__ rows, int64_t nrows, uint32_t row_base, const T* __restrict__ queries, int64_t nq, int64_t d,
     const float* __restrict__ thr, u64* __restrict__ keys, unsigned* __restrict__ cnt, int nt) {
   typedef typename MmaOps<T>::frag_t frag_t;
+  constexpr int NKMAX = SCAN_NKMAX16;
+  constexpr int RB = 2 * NB;                     // 16-row blocks per wave and unit: 4 / NB waves share a query block
+  constexpr int NVK = NB;                        // K steps whose query fragments live in VGPRs: 8 registers each, 4 RB accumulators
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int lane = threadIdx.x & 63;
+  asm volatile("" : "+v"(lane));
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nk = (int)((d * 2) / G7_ROW_BYTES);
+  const int64_t ntiles = nrows / SR_UROWS;
+  const int my_tiles = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
+  if (my_tiles <= 0) return;
+  const int units = my_tiles * nk;
+  const uint32_t lds0 = g7_lds_addr(smem);
+  const int quad = lane >> 4, l15 = lane & 15, key = l15 >> 1;
+  const int nb = wave % NB, rgroup = wave / NB;   // this wave's query block and its share of a unit's rows
+
+  frag_t bq[NKMAX][2];
+  {
+    const int qr = nb * 16 + l15;
+    const int rr = qr < nq ? qr : (int)nq - 1;                  // padding rows repeat the last query (their threshold is +inf)
+    const T* qrow = queries + (int64_t)rr * d + quad * 8;
+#pragma unroll
+    for (int ks = 0; ks < NKMAX; ++ks)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+        bq[ks][kk] = ks < nk ? *(const frag_t*)(qrow + ks * 64 + kk * 32) : __builtin_bit_cast(frag_t, z4);
+      }
+  }
+  const float th = nb * 16 + l15 < nq ? thr[nb * 16 + l15] : __builtin_inff();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // before the first hand-counted DMA: nothing of the compiler's is in flight
+#pragma unroll
+  for (int ks = 0; ks < NKMAX - NVK; ++ks)
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) asm volatile("" : "+a"(bq[ks][kk]));
+#pragma unroll
+  for (int ks = NKMAX - NVK; ks < NKMAX; ++ks)
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) asm volatile("" : "+v"(bq[ks][kk]));
+
+  uint32_t off[SR_IPU];
+#pragma unroll
+  for (int i = 0; i < SR_IPU; ++i) {
+    const int r = (i * 4 + wave) * 8 + (lane >> 3);
+    off[i] = (uint32_t)(r * d * 2) + ((((lane & 7) ^ ((r >> 1) & 7))) << 4);
+  }
+  const char* i_base = (const char*)(rows + (int64_t)blockIdx.x * SR_UROWS * d);
+  const int64_t i_tile_step = (int64_t)gridDim.x * SR_UROWS * d * 2 - (int64_t)nk * G7_ROW_BYTES;   // last K step of a tile -> first of the next
+  int i_ks = 0, i_slot = 0, issued = 0;
+  auto issue = [&]() {
+    const char* base = i_base;
+    const uint32_t dst = lds0 + i_slot * SR_UBYTES + wave * 1024;
+    if (nt) {
+#pragma unroll
+      for (int i = 0; i < SR_IPU; ++i) g7_dma_nt(base, off[i], dst + i * 4096);
+    } else {
+#pragma unroll
+      for (int i = 0; i < SR_IPU; ++i) g7_dma(base, off[i], dst + i * 4096);
+    }
+    i_base += G7_ROW_BYTES;
+    if (++i_ks == nk) { i_ks = 0; i_base += i_tile_step; }
+    if (++i_slot == SR_RING) i_slot = 0;
+    ++issued;
+  };
+  for (int u = 0; u < SR_RING - 1; ++u)
+    if (u < units) issue();
+
+  const int arow = (rgroup * (16 * RB) + l15) * G7_ROW_BYTES;    // + rt * 16 rows
+  f32x4_t acc[RB];
+#pragma unroll
+  for (int rt = 0; rt < RB; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[rt][r] = 0.f;
+  f32x4_t sh[RB];                                                // the previous tile's scores while its list position is in flight
+  unsigned pn = 0, ppos = 0;
+  bool pend = false;                                             // (wave-uniform) a tile's appends are in flight
+  int64_t ptile = 0;
+  int since = 0;                                                 // units issued since its atomics
+  const int qi = nb * 16 + l15;
+  auto retire = [&]() {
+    if (since >= 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("" : "+v"(ppos));                               // (the result is read after the wait)
+    if (pn) {
+      const uint32_t id0 = row_base + (uint32_t)(ptile * SR_UROWS) + rgroup * (16 * RB) + 4 * quad;
+      unsigned pos = ppos;
+      u64* const kq = keys + (int64_t)qi * SORT_CAP;
+#pragma unroll
+      for (int rt = 0; rt < RB; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (sh[rt][r] >= th) {
+            if (pos < SORT_CAP) kq[pos] = pack_key(sh[rt][r], id0 + rt * 16 + r);
+            ++pos;
+          }
+    }
+    pend = false;
+  };
+  int c_slot = 0, u = 0;
+  int64_t tile = blockIdx.x;
+  frag_t a[2][RB];
+  for (int ti = 0; ti < my_tiles; ++ti) {
+#pragma unroll
+    for (int ks = 0; ks < NKMAX; ++ks) {
+      if (ks < nk) {                                             // wave-uniform
+        const int younger = issued - 1 - u;
+        if (younger == SR_RING - 2) G7_WAIT_VM((SR_RING - 2) * SR_IPU);
+        else G7_WAIT_VM(0);
+        __builtin_amdgcn_s_barrier();                            // ... for every wave; and unit u - 1 has been read by all
+        if (issued < units) { issue(); ++since; }                // into the slot of unit u - 1
+        const char* ua = smem + c_slot * SR_UBYTES + arow;
+#pragma unroll
+        for (int rt = 0; rt < RB; ++rt) a[0][rt] = *(const frag_t*)(ua + rt * 16 * G7_ROW_BYTES + ((quad ^ key) << 4));
+        G7_FENCE_();
+#pragma unroll
+        for (int rt = 0; rt < RB; ++rt) a[1][rt] = *(const frag_t*)(ua + rt * 16 * G7_ROW_BYTES + (((4 | quad) ^ key) << 4));
+        G7_FENCE_();
+#pragma unroll
+        for (int rt = 0; rt < RB; ++rt) Mma16c<T>::mma(a[0][rt], bq[ks][0], acc[rt]);
+        G7_FENCE_();
+#pragma unroll
+        for (int rt = 0; rt < RB; ++rt) Mma16c<T>::mma(a[1][rt], bq[ks][1], acc[rt]);
+        G7_FENCE_();
+#pragma unroll
+        for (int rt = 0; rt < RB; ++rt) asm volatile("" : "+a"(acc[rt]));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (++c_slot == SR_RING) c_slot = 0;
+        ++u;
+        if (ks == 3 && pend) retire();                           // the previous tile's appends: positions are back by now
+      }
+#pragma unroll
+      for (int rt = 0; rt < RB; ++rt) asm volatile("" : "+a"(acc[rt]));   // (also where the skipped and the taken K step meet)
+    }
+    unsigned n = 0;
+#pragma unroll
+    for (int rt = 0; rt < RB; ++rt) {
+      sh[rt] = acc[rt];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { n += sh[rt][r] >= th ? 1u : 0u; acc[rt][r] = 0.f; }
+    }
+    pn = n;
+    if (n) {
+      unsigned* const cp = cnt + qi;
+      asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=&v"(ppos) : "v"(cp), "v"(n) : "memory");
+    }
+    if (__builtin_amdgcn_ballot_w64(n != 0) != 0) { pend = true; ptile = tile; since = 0; }
+    tile += gridDim.x;
+  }
+  if (pend) { since = 0; retire(); }
+  G7_WAIT_VM(0);
+}
+
+// DBG (timing probes only, OM_OPT_SEARCH_DEBUG bits 3 / 4; the results are wrong): 1 = every second MFMA sub-step skipped (does
+// the pass's time follow its matrix-core work?), 2 = no MFMA at all
+// NKMAX (round 7): the K steps compiled in.  12 serves 256 <= d <= 768 and is the kernel above, instruction for instruction.  16 serves
+// 832 <= d <= 1024: the query block is then 256 registers, the whole accumulation half, and the accumulators pinned there as well would
+// have no home.  So the fragments of the last NVK = NB K steps (16 registers each, as many as the 16 NB accumulators need) are pinned into
+// the OTHER half -- the matrix core reads B from either -- which holds 8 NB row-fragment and 16 NB shadow registers besides: 64 / 106 /
+// 192 VGPRs and 256 AGPRs for NB = 1 / 2 / 4, no scratch, and no v_accvgpr move in the unit loop.
+// QB (round 7): queries per resident block.  16 with NKMAX = 32 is the body above (1088 <= d <= 2048), 32 the one below.
+template <typename T, int NB, int DBG = 0, int NKMAX = SCAN_NKMAX32_NARROW, int QB = 32>
+__global__ __launch_bounds__(G6_THREADS) void sim_stream_reg_kernel(
+    const T* __restrict__ rows, int64_t nrows, uint32_t row_base, const T* __restrict__ queries, int64_t nq, int64_t d,
+    const float* __restrict__ thr, u64* __restrict__ keys, unsigned* __restrict__ cnt, int nt) {
+  if constexpr (QB == 16) {
+    static_assert(NKMAX == SCAN_NKMAX16 && DBG == 0, "the 16-query body compiles 32 K steps and has no probe variants");
+    sim_stream_reg16_body<T, NB>(rows, nrows, row_base, queries, nq, d, thr, keys, cnt, nt);
+    return;
+  }
+  typedef typename MmaOps<T>::frag_t frag_t;
   constexpr int RBW = NB;                        // 32-row blocks per wave and unit: 4 / NB waves share a query block
+  constexpr int NVK = NKMAX * 16 + RBW * 16 > 256 ? (NKMAX * 16 + RBW * 16 - 256) / 16 : 0;      // K steps whose query fragments live in VGPRs
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int lane = threadIdx.x & 63;
   asm volatile("" : "+v"(lane));
@@ -764,13 +946,13 @@ __global__ __launch_bounds__(G6_THREADS) void sim_stream_reg_kernel(
   const int nb = wave % NB, rgroup = wave / NB;   // this wave's query block and its share of a unit's rows
 
   // the wave's query block, in MFMA fragment order, straight from global memory (once per launch)
-  frag_t bq[SR_NKMAX][4];
+  frag_t bq[NKMAX][4];
   {
     const int qr = nb * 32 + l31;
     const int rr = qr < nq ? qr : (int)nq - 1;                  // padding rows repeat the last query (their threshold is +inf)
     const T* qrow = queries + (int64_t)rr * d + half * 8;
 #pragma unroll
-    for (int ks = 0; ks < SR_NKMAX; ++ks)
+    for (int ks = 0; ks < NKMAX; ++ks)
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
@@ -780,10 +962,14 @@ __global__ __launch_bounds__(G6_THREADS) void sim_stream_reg_kernel(
   const float th = thr[nb * 32 + l31];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // before the first hand-counted DMA: nothing of the compiler's is in flight
 #pragma unroll
-  for (int ks = 0; ks < SR_NKMAX; ++ks)
+  for (int ks = 0; ks < NKMAX - NVK; ++ks)
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) asm volatile("" : "+a"(bq[ks][kk]));    // in the accumulation half of the register file (the matrix core
                                                                             // reads B from there as well): 192 + 16 NB of its 256; the other half stays free for the row fragments
+#pragma unroll
+  for (int ks = NKMAX - NVK; ks < NKMAX; ++ks)
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) asm volatile("" : "+v"(bq[ks][kk]));    // (NKMAX = 16 only: see above)
 
   // DMA offsets of a unit: instruction i of this wave moves rows (i*4 + wave)*8 .. +7, lane -> row (lane >> 3),
   // physical chunk (lane & 7) <- source chunk (lane & 7) ^ ((row >> 1) & 7)
@@ -871,7 +1057,7 @@ __global__ __launch_bounds__(G6_THREADS) void sim_stream_reg_kernel(
   frag_t a[2][RBW];
   for (int ti = 0; ti < my_tiles; ++ti) {
 #pragma unroll
-    for (int ks = 0; ks < SR_NKMAX; ++ks) {
+    for (int ks = 0; ks < NKMAX; ++ks) {
       if (ks < nk) {                                             // wave-uniform
         // unit u landed; up to RING - 1 younger units may be in flight
         const int younger = issued - 1 - u;
@@ -1170,8 +1356,13 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
   if (lane == 0) {
     const float qn = sqrtf(n2), qe = sqrtf(e2), qbn = sqrtf(b2);
     const float Ep = stats[0], Pn = stats[1];
-    // f32 accumulation of the 16-bit scan and of the f32 re-score: each <= d * 2^-24 * |q||p|
-    const float slop = 3.0f * (float)d * 5.9604645e-8f * fmaxf(qn, qbn) * (Pn + Ep);
+    // f32 accumulation of the 16-bit scan and of the f32 re-score, bounded by DEPTH (the additions one product takes part in), not by
+    // the d additions of the whole sum -- 3 d 2^-24 was 46 % of the margin at d = 2048 and sent searches a 16-bit scan serves to the
+    // float32 one.  Products of two f16 values are exact in f32.  Scan (and the dense bootstrap's GEMM): at most the 32 k values of one
+    // MFMA (16 x 16 x 32; 16 of 32 x 32 x 16), then one addition per later MFMA of the chain (d / 16 at most), each taken at 2^-23 -- a
+    // matrix core may truncate where the VALU rounds.  Re-score: a lane's chain of d / 64 fmaf, six butterfly additions, + 2 spare.
+    const float depth = 2.0f * (32.0f + (float)d / 16.0f) + ((float)d / 64.0f + 8.0f);
+    const float slop = depth * 5.9604645e-8f * fmaxf(qn, qbn) * (Pn + Ep);
     margin[row] = 1.01f * (qn * Ep + qe * Pn) + slop;
   }
 }
@@ -1305,10 +1496,54 @@ extern "C" void om_sim_topk_info(int64_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = g_info[i];
 }
 
+extern "C" int om_debug_scan_plan(int half, int64_t nq, int d, int out[4]) {
+  if (!out) OM_FAIL("null argument");
+  const ScanPlan p = scan_plan(half != 0, nq, d, scan_switches());
+  out[0] = p.family; out[1] = p.qblock; out[2] = p.nb; out[3] = p.nkmax;
+  return 0;
+}
+
 extern "C" size_t om_sim_topk_workspace_bytes(int64_t n_queries, int d, int k) {
   (void)k;
   if (n_queries <= 0 || d <= 0) return 0;
   return carve_search(n_queries, d, nullptr).total;
+}
+
+// The stream instantiation a plan names, over whole 128-row tiles on `grid` workgroups (Scan::filter_step and om_debug_sim_stream)
+static int stream_attrs() {
+  static std::atomic<bool> done{false};
+  if (done) return 0;
+#define SR_ATTR(...) OM_HIP(hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, SR_LDS))
+  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 0>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 0>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 0>);
+  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 1>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 1>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 1>);
+  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 2>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 2>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 2>);
+  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX32_WIDE>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX32_WIDE>);
+  SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX32_WIDE>);
+  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX16, 16>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX16, 16>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX16, 16>);
+#undef SR_ATTR
+  done = true;
+  return 0;
+}
+static void stream_launch(const ScanPlan& plan, const f16_t* rows, int64_t nrows, uint32_t row_base, const f16_t* queries, int64_t nq, int d,
+                          const float* thr, u64* keys, unsigned* cnt, int grid, hipStream_t s) {
+  const int nt = (om_option(OM_OPT_SEARCH_DEBUG) & 4) ? 0 : 1;
+#define STREAM_(...) hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)grid), dim3(G6_THREADS), SR_LDS, s, rows, nrows, row_base, queries, nq, (int64_t)d, \
+                                        thr, keys, cnt, nt)
+#ifdef OM_PROBE_KERNELS      // timing variants with MFMAs compiled out (WRONG results): probe builds only (python -m openmatch_amd._build --probe)
+#define STREAM(NB_) do { const int dbg_ = (om_option(OM_OPT_SEARCH_DEBUG) >> 3) & 3; if (dbg_ == 1) STREAM_(sim_stream_reg_kernel<f16_t, NB_, 1>); else if (dbg_ == 2) STREAM_(sim_stream_reg_kernel<f16_t, NB_, 2>); else STREAM_(sim_stream_reg_kernel<f16_t, NB_, 0>); } while (0)
+#else
+#define STREAM(NB_) STREAM_(sim_stream_reg_kernel<f16_t, NB_, 0>)
+#endif
+  if (plan.family == OM_SCAN_FAMILY_STREAM16) {
+    if (plan.nb == 1) STREAM_(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX16, 16>); else if (plan.nb == 2) STREAM_(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX16, 16>); else STREAM_(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX16, 16>);
+  } else if (plan.nkmax == SCAN_NKMAX32_WIDE) {
+    if (plan.nb == 1) STREAM_(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX32_WIDE>); else if (plan.nb == 2) STREAM_(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX32_WIDE>);
+    else STREAM_(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX32_WIDE>);
+  } else {
+    if (plan.nb == 1) STREAM(1); else if (plan.nb == 2) STREAM(2); else STREAM(4);
+  }
+#undef STREAM
+#undef STREAM_
 }
 
 namespace {
@@ -1362,7 +1597,9 @@ struct Scan {
     return select(bf16);
   }
   int filter_step(int64_t r0, int64_t n, bool bf16, bool check = true /* false: the selection that follows flags overflows */) {
-    const bool wide = nq > 128;
+    const ScanPlan plan = scan_plan(bf16, nq, d, scan_switches());
+    g_info[5] = plan.family;
+    const bool wide = plan.family == OM_SCAN_FAMILY_WIDE;
     const int64_t ntm = (n + 255) / 256, ntn = wide ? (nq + G6_BM - 1) / G6_BM : (nq + G2_BN - 1) / G2_BN;
     if (ntm * ntn > 0x7fffffffLL) OM_FAIL("scan grid too large");
     const bool timing = om_timing_on();
@@ -1393,23 +1630,14 @@ struct Scan {
           hipLaunchKernelGGL((sim_filter_kernel6<f16_t>), dim3((unsigned)ntn), dim3(G6_THREADS), G6_LDS_BYTES, s, idx16 + (r0 + whole) * d,
                              n - whole, (uint32_t)(r0 + whole), ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8);
       } else if (wide) SCAN(sim_filter_kernel6, G6_THREADS, G6_LDS_BYTES, f16_t, idx16, ws.qb);
-      else if (nq <= 128 && (d * 2) / G7_ROW_BYTES <= SR_NKMAX && (d * 2) / G7_ROW_BYTES >= 4 && om_option(OM_OPT_SCAN_GEN7)) {
+      else if (plan.family == OM_SCAN_FAMILY_STREAM32 || plan.family == OM_SCAN_FAMILY_STREAM16) {
         // the HBM-speed pass for small batches (queries in registers, the whole LDS a ring) over the whole 128-row tiles;
         // the generic kernel takes the ragged tail
         const int64_t whole = n & ~(int64_t)127;
         if (whole) {
           int ncu = g7_num_cus();
           if (whole / SR_UROWS < ncu) ncu = (int)(whole / SR_UROWS);
-#define STREAM_(NB_, DBG_) hipLaunchKernelGGL((sim_stream_reg_kernel<f16_t, NB_, DBG_>), dim3((unsigned)ncu), dim3(G6_THREADS), SR_LDS, s, idx16 + r0 * d, whole, \
-                                       (uint32_t)r0, ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, (om_option(OM_OPT_SEARCH_DEBUG) & 4) ? 0 : 1)
-#ifdef OM_PROBE_KERNELS      // timing variants with MFMAs compiled out (WRONG results): probe builds only (python -m openmatch_amd._build --probe)
-#define STREAM(NB_) do { const int dbg_ = (om_option(OM_OPT_SEARCH_DEBUG) >> 3) & 3; if (dbg_ == 1) STREAM_(NB_, 1); else if (dbg_ == 2) STREAM_(NB_, 2); else STREAM_(NB_, 0); } while (0)
-#else
-#define STREAM(NB_) STREAM_(NB_, 0)
-#endif
-          if (nq <= 32) STREAM(1); else if (nq <= 64) STREAM(2); else STREAM(4);
-#undef STREAM
-#undef STREAM_
+          stream_launch(plan, idx16 + r0 * d, whole, (uint32_t)r0, ws.qb, nq, d, ws.thr, ws.keys, ws.cnt, ncu, s);
         }
         if (n > whole)
           hipLaunchKernelGGL((sim_filter_kernel<f16_t>), dim3((unsigned)((nq + G2_BN - 1) / G2_BN)), dim3(G2_THREADS), G2_LDS_BYTES, s, idx16 + (r0 + whole) * d, n - whole,
@@ -1596,9 +1824,7 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
                                hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS_BYTES));
     OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel6<f16_t>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS_BYTES));
-#define SR_ATTR(NB_, DBG_) OM_HIP(hipFuncSetAttribute((const void*)sim_stream_reg_kernel<f16_t, NB_, DBG_>, hipFuncAttributeMaxDynamicSharedMemorySize, SR_LDS))
-    SR_ATTR(1, 0); SR_ATTR(2, 0); SR_ATTR(4, 0); SR_ATTR(1, 1); SR_ATTR(2, 1); SR_ATTR(4, 1); SR_ATTR(1, 2); SR_ATTR(2, 2); SR_ATTR(4, 2);
-#undef SR_ATTR
+    if (stream_attrs()) return 1;
     OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel7<f16_t>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
     OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel7c<f16_t>,
@@ -1631,6 +1857,20 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
   }
   hipLaunchKernelGGL(emit_kernel, dim3((unsigned)n_queries), dim3(256), 0, s, sc.ws.keys, sc.ws.cnt, k,
                      id_offset, out_scores, out_ids);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,
+                                   uint64_t* keys, unsigned* cnt, int grid, void* stream) {
+  if (!rows16 || !queries16 || !thr || !keys || !cnt) OM_FAIL("null argument");
+  if (nrows <= 0 || nrows % SR_UROWS != 0) OM_FAIL("whole 128-row tiles only");
+  if (grid < 1 || grid > 65535) OM_FAIL("grid must be in [1,65535]");
+  const ScanPlan plan = scan_plan(true, nq, d, scan_switches());
+  if (plan.family != OM_SCAN_FAMILY_STREAM32 && plan.family != OM_SCAN_FAMILY_STREAM16)
+    OM_FAIL("the scan plan sends this (nq, d) to no stream kernel");
+  if (stream_attrs()) return 1;
+  stream_launch(plan, (const f16_t*)rows16, nrows, row_base, (const f16_t*)queries16, nq, d, thr, (u64*)keys, cnt, grid, (hipStream_t)stream);
   OM_LAUNCH_CHECK();
   return 0;
 }

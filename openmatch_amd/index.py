@@ -99,7 +99,7 @@ class FlatIPIndex:
         lib.om_sim_topk_info(info)
         self.last_search_info = {"scan": "f16+rescore" if info[0] == 1 else "f32", "rounds": int(info[1]),
                                  "overflow_fallbacks": int(info[2]), "max_list": int(info[3]),
-                                 "margin_too_wide": bool(info[4])}
+                                 "margin_too_wide": bool(info[4]), "kernel": N.SCAN_FAMILY_NAME[int(info[5])]}
         return D, I
 
     def search(self, x, k: int):

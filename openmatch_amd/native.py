@@ -29,6 +29,10 @@ ATTN_FAMILY = {"generic": 1, "fwd16": 2, "fwd16_kmax4": 3, "fwd16c": 4, "long": 
 ATTN_BWD_FAMILY = {"bwd16": 1, "generic": 2, "long": 3, "d32": 4}
 # om_debug_encoder_plan codes (OM_ENC_PATH_*); the call returns path | few_rows << 8 | two << 9 | lo8 << 10
 ENC_PATH = {"bert_fused": 1, "bert_pending_ln": 2, "bert_few32": 3, "bert_plain": 4, "modernbert": 5, "t5_fused": 6, "t5_plain": 7}
+# om_debug_scan_plan / om_sim_topk_info[5] codes (OM_SCAN_FAMILY_*); 0: the search never left the dense path
+SCAN_FAMILY = {"dense": 0, "generic": 1, "wide": 2, "stream32": 3, "stream16": 4}
+SCAN_FAMILY_NAME = {v: k for k, v in SCAN_FAMILY.items()}
+OPT_SCAN_GEN7 = 3
 OPT_ATTENTION_FAST = 2
 SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
 ABI_VERSION = 6
@@ -320,6 +324,8 @@ _SIGNATURES = {
     "om_sim_topk": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                             c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_sim_topk_info": (None, [C.POINTER(c_int64)]),
+    "om_debug_scan_plan": (c_int, [c_int, c_int64, c_int, C.POINTER(c_int)]),
+    "om_debug_sim_stream": (c_int, [c_void_p, c_int64, C.c_uint32, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "om_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p,
                               c_void_p]),
     "om_contrastive_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
