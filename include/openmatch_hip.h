@@ -218,7 +218,13 @@ int om_debug_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B
                                       its LAST layer's attention (out-proj, FFN1, FFN2, their row statistics) over the B [CLS] rows that pooling
                                       "first" reads -- gathered into roundup256(B) compact rows -- instead of every token row; the representations
                                       keep their bits.  0 (A/B, tests): the last layer runs over every row like the others */
-#define OM_OPT_COUNT 24
+#define OM_OPT_ENCODER_LANES 24  /* 65536 (default; env OM_ENCODER_LANES): the least PADDED token rows of a lane.  Where om_debug_encoder_lanes says so,
+                                      om_encoder_forward runs a padded fused-BERT batch as two half-batches: sequences [0, B0) on the caller's stream,
+                                      the rest on a stream the library owns (one per (device, caller stream), non-blocking, created on first use and
+                                      kept for the life of the process), over two views of the one workspace, forked and joined with events so the
+                                      caller's stream is ordered after both; the representations keep their bits.  Not while the stream is capturing,
+                                      not under om_kernel_timing_enable(1), not without OmEncoderWeights::folded.  0 (A/B, tests): one chain */
+#define OM_OPT_COUNT 25
 int om_debug_option(int opt, int value);
 /* the current value of a run-time switch (OM_OPT_*), so a test can restore exactly what it changed; -1 for an unknown option */
 int om_debug_option_value(int opt);
@@ -361,6 +367,24 @@ int om_debug_encoder_skip_pad(const struct OmEncoderConfig* cfg, int gated_ffn, 
  * -1 for a NULL cfg.  The plan word and the workspace size do not change with it. */
 int om_debug_encoder_cls_tail(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
                               int want_hidden);
+/* host only: 1 if om_encoder_forward would run this padded call as two lanes at the current switches (csrc/encoder_plan.h
+ * encoder_lanes), with lane 0's sequence count in *B0 (B0 may be NULL): OM_OPT_ENCODER_LANES is not 0, packed_rows is 0,
+ * a pooling is set, no hidden states are wanted, the call plans OM_ENC_PATH_BERT_FUSED without a relative-position bias, B0 -- the
+ * largest count <= B / 2 with B0 * L a multiple of 256 -- and B - B0 both have at least that many token rows and fewer than 131 072 (measured slower from there on), and each lane planned
+ * as a call of its own gets the whole's path, planes and walk and the whole's om_debug_encoder_skip_pad / om_debug_encoder_cls_tail
+ * answers.  0 otherwise, -1 for a NULL cfg.  The forward itself declines as well while its stream is capturing, in timing mode, without
+ * OmEncoderWeights::folded, or where a contraction would plan another GEMM family at a lane's height.  The plan word and the workspace
+ * size do not change with it. */
+int om_debug_encoder_lanes(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
+                           int want_hidden, int64_t* B0);
+/* host only: the byte ranges of lane `lane` (0 | 1) inside the workspace of the call (B, L), as (offset, bytes) pairs in out[0 .. 2 n):
+ * x, y, x1, qkv, ctx, ff, ff2, pooled, headout, kmax, final32, stats, slots, y_lo, x1_lo (n = 15; a field the configuration does not
+ * use has 0 bytes).  Returns n, or -1 where om_debug_encoder_lanes is not 1 or cap < 2 n. */
+#define OM_ENCODER_LANE_RANGES 15
+int om_debug_encoder_lane_ranges(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int lane,
+                                 int64_t* out, int cap);
+/* how many forwards have forked into two lanes since the library was loaded */
+int64_t om_debug_encoder_lane_forks(void);
 /* Test hook of the row gather behind it (csrc/kernels.h omk_gather_rows): output row r < Mc of every given destination copies source row
  * idx(min(r, B - 1)), idx(b) = rows ? rows[b] : b * L.  Up to three 16-bit planes of H columns (src_i / dst_i, NULL pairs are skipped; H
  * a multiple of 8, 16-byte aligned buffers) and one [., 2] f32 array (stats_src / stats_dst, or NULL). */

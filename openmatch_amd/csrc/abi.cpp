@@ -120,6 +120,8 @@ void opt_init() {
   g_opt[OM_OPT_ENCODER_SKIP_PAD] = e ? atoi(e) : 1;
   e = getenv("OM_ENCODER_CLS_TAIL");
   g_opt[OM_OPT_ENCODER_CLS_TAIL] = e ? atoi(e) : 1;
+  e = getenv("OM_ENCODER_LANES");
+  g_opt[OM_OPT_ENCODER_LANES] = e ? atoi(e) : 65536;
   g_opt_init.store(true);
 }
 }  // namespace

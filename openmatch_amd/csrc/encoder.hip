@@ -1,5 +1,6 @@
 // om_encoder_forward: the whole eval-mode encoder (BERT post-LN -- NomicBERT on the same loops --, T5 pre-RMSNorm or ModernBERT pre-LN stack)
-// + pooling + LinearHead + normalise, as a fixed sequence of launches on ONE stream.
+// + pooling + LinearHead + normalise, as a fixed sequence of launches on ONE stream -- or, for a large padded fused-BERT batch, as
+// two such sequences over two halves of the batch on two streams, forked and joined on the caller's (encoder_fork).
 // Stands in for DRModel.encode (modeling/dense_retrieval_model.py:133-155) and the HF model
 // it calls (HF:models/bert/modeling_bert.py:623-684 / HF:models/t5/modeling_t5.py T5Stack).
 //
@@ -15,6 +16,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -264,6 +266,9 @@ struct EncCall {
   const int* rows_dev;    // a padded call that skips its pad rows: &cu[B], the token count on the device, for every contraction of the
                           //   fused loops (GemmEpilogue::rows_dev); else NULL
   int64_t cls_mc;         // > 0 (encoder_cls_tail): bert_fused runs its last layer's per-row tail over this many compact rows, the [CLS] rows
+  std::vector<int>* families;   // not NULL (bert_fused, asked by encoder_fork): launch nothing; append the GEMM family each contraction plans
+  int64_t whole_mg, whole_mc;   // a lane (bert_fused): the whole call's Mg and compact height -- its contractions choose their tile
+                                //   generation as for those (omk_gemm's plan_m), so a lane runs the kernels the whole would; else 0
 };
 
 // Where a layer loop left the stream that the last normalisation reads (final_norm below).
@@ -332,6 +337,16 @@ static int bert_fused(const EncCall& k, EncStream* out) {
   // three contractions run one or a few tiles each, with the epilogue fields of the full-row launches: a row's bits do not depend on
   // the tile it sits in.  The compact buffers live in ws.qkv, dead once attention has read it (seven planes [Mc, H] and two statistics
   // arrays against [Mp, 3H]: the rule's 4 Mc <= Mp); FFN1's compact output takes the head of ws.ff, dead as well.
+  // k.families: the loop as a question -- which family does each contraction plan, with the pointers and epilogues it would launch with
+  const bool probe = k.families != nullptr;
+  auto gemm = [&](const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t rows, int64_t N, int64_t K,
+                  const GemmEpilogue& ep) {
+    const int64_t as = rows == Mg ? k.whole_mg : k.whole_mc;
+    if (!probe) return omk_gemm(dt, A, lda, W, ldw, dt, C, ldc, rows, N, K, ep, s, as);
+    k.families->push_back(omk_gemm_family(dt, A, lda, W, ldw, dt, C, ldc, rows, N, K, ep, as));
+    return 0;
+  };
+#define LAUNCH(expr) do { if (!probe) RUN(expr); } while (0)
   const int64_t Mc = k.cls_mc;
   const size_t cplane = (size_t)Mc * H * 2;
   char* const cbase = ws.qkv;
@@ -355,19 +370,20 @@ static int bert_fused(const EncCall& k, EncStream* out) {
     // ---- QKV: x0 for the first layer, LN2_{l-1}(y2) folded afterwards
     if (l == 0) {
       e.bias = lw.qkv_b; e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
-      RUN(omk_gemm(dt, ws.x, H, lw.qkv_w, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
+      RUN(gemm(ws.x, H, lw.qkv_w, H, ws.qkv, 3 * H, Mg, 3 * H, H, e));
     } else {
       const OmLayerWeights& pw = Ls[l - 1];
       const void* wf; const float *cs, *bfp;
       RUN(folded_weights(c, k.w, l, false, lw.qkv_w, pw.ln2_g, pw.ln2_b, lw.qkv_b, 3 * H, H, ws.wfold, ws.colsum, ws.bfold, s, &wf, &cs, &bfp));
       e.bias = bfp; e.ln_stats = st2p; e.ln_colsum = cs; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps; e.reverse = OM_WALK(); e.rows_dev = k.rows_dev;
-      RUN(omk_gemm(dt, ws.x1, H, wf, H, dt, ws.qkv, 3 * H, Mg, 3 * H, H, e, s));
+      RUN(gemm(ws.x1, H, wf, H, ws.qkv, 3 * H, Mg, 3 * H, H, e));
     }
-    NOMIC_ROPE();
-    RUN(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, OM_WALK(), ws.kmax, k.cu));
+    if (!probe) NOMIC_ROPE();
+    const int attn_walk = OM_WALK();
+    LAUNCH(omk_attention(dt, ws.qkv, ws.ctx, k.mask, k.posbias, B, (int)L, H, nh, scale, 0.f, 0, s, attn_walk, ws.kmax, k.cu));
     if (tail) {
       const GatherPlane planes[3] = {{ws.ctx, cbase}, {ws.x1, cbase + cplane}, {two ? ws.x1_lo : nullptr, cbase + 2 * cplane}};
-      RUN(omk_gather_rows(planes, st2p, cst2p, k.cu ? ws.cls_rows : nullptr, B, L, Mc, H, s));
+      LAUNCH(omk_gather_rows(planes, st2p, cst2p, k.cu ? ws.cls_rows : nullptr, B, L, Mc, H, s));
       ctx = cbase; xin = cbase + cplane; xin_lo = cbase + 2 * cplane; st2p = cst2p;
       y = cbase + 3 * cplane; y_lo = cbase + 4 * cplane; xout = cbase + 5 * cplane; xout_lo = cbase + 6 * cplane;
     }
@@ -383,26 +399,27 @@ static int bert_fused(const EncCall& k, EncStream* out) {
       if (two) e.resid_lo = xin_lo;
     }
     e.reverse = OM_WALK(); e.rows_dev = rdev;
-    RUN(omk_gemm(dt, ctx, H, lw.o_w, H, dt, y, H, Mr, H, H, e, s));
-    RUN(omk_ln_stats_reduce(ws.slots, nslots, Mr, st1, s));
+    RUN(gemm(ctx, H, lw.o_w, H, y, H, Mr, H, H, e));
+    LAUNCH(omk_ln_stats_reduce(ws.slots, nslots, Mr, st1, s));
     // ---- FFN1 on LN1(y1), folded
     const void* wf1; const float *cs1, *bf1;
     RUN(folded_weights(c, k.w, l, true, lw.ffn1_w, lw.ln1_g, lw.ln1_b, lw.ffn1_b, F1, H, ws.wfold, ws.colsum, ws.bfold, s, &wf1, &cs1, &bf1));
     e = GemmEpilogue{};
     e.bias = bf1; e.act = act1; e.ln_stats = st1; e.ln_colsum = cs1; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
     e.reverse = OM_WALK(); e.rows_dev = rdev;
-    RUN(omk_gemm(dt, y, H, wf1, H, dt, ws.ff, F1, Mr, F1, H, e, s));
-    NOMIC_SWIGLU(Mr);
+    RUN(gemm(y, H, wf1, H, ws.ff, F1, Mr, F1, H, e));
+    if (!probe) NOMIC_SWIGLU(Mr);
     // ---- FFN2 + LN1(y1) as the residual -> y2, statistics of LN2
     e = GemmEpilogue{};
     e.bias = lw.ffn2_b; e.resid = y; e.ldr = H; e.rln_stats = st1; e.rln_g = lw.ln1_g; e.rln_b = lw.ln1_b;
     e.stats_out = ws.slots; e.ln_inv_h = inv_h; e.ln_eps = c->ln_eps;
     if (two) { e.resid_lo = y_lo; e.out_lo = xout_lo; e.lo8 = lo8; }
     e.reverse = OM_WALK(); e.rows_dev = rdev;
-    RUN(omk_gemm(dt, ffa, F, lw.ffn2_w, F, dt, xout, H, Mr, H, F, e, s));
+    RUN(gemm(ffa, F, lw.ffn2_w, F, xout, H, Mr, H, F, e));
     // (the last layer's LN2 is final_norm's, which computes its own statistics: the slots the kernel had to write are not reduced)
-    if (!last) RUN(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
+    if (!last) LAUNCH(omk_ln_stats_reduce(ws.slots, nslots, Mg, st2, s));
   }
+#undef LAUNCH
 #undef OM_WALK
   const OmLayerWeights& lastw = Ls[c->n_layers - 1];
   *out = EncStream{ws.x1, two ? ws.x1_lo : nullptr, lo8, lastw.ln2_g, lastw.ln2_b, 0, ws.x};
@@ -689,7 +706,200 @@ static int skip_pad_buffer(hipStream_t s, size_t ints, int** out) {
   return 0;
 }
 
-// plan, carve, the plan's layer loop, the last normalisation, pooling
+// One chain of launches on one stream: the whole call, or one lane of it (encoder_fork below).  `in` / `plan` are the CHAIN's own -- a
+// lane is planned as the call (B_h, L) it is -- and `ws` is its view of the workspace.
+struct EncChain {
+  const OmEncoderConfig* c;
+  const OmEncoderWeights* w;
+  const int64_t *input_ids, *attention_mask, *token_type_ids;
+  void* out_hidden;
+  float* out_reps;
+  EncPlanIn in;
+  EncPlan plan;
+  EncSwitches sw;
+  EncWs ws;
+  hipStream_t s;
+  int* side;      // encoder_skip_pad holds and skip_pad_buffer(s) had a buffer: cu | cls_rows | row_map of the chain; else NULL
+  int64_t whole_mg, whole_mc;      // a lane: EncCall's fields of these names; the whole call: 0
+};
+
+// Two views of one workspace (encoder_plan.h encoder_lanes): lane 0 takes token rows [0, B0 * L) and sequences [0, B0) of every buffer
+// of the whole call's carve, lane 1 the rest -- B0 * L is in whole tiles, so lane 1's height Mp - B0 * L is roundup256((B - B0) * L),
+// what a call of its own would carve.  The statistics and slot arrays are indexed with the chain's own Mg as pitch (bert_fused), so
+// each is split into two contiguous blocks sized by the lanes' heights.  Nothing is carved twice: om_encoder_workspace_bytes is what it
+// was.  What a lane never touches is NULL in its view: the fold scratch (w->folded is given), the bias table, the f32 stream, and the
+// three packed-row arrays (a lane that skips its pad rows has them in the side buffer of its own stream).
+static EncWs lane_view(const OmEncoderConfig* c, const EncWs& w, const EncPlan& lane, int h, int64_t B0, int64_t L) {
+  const size_t H = c->hidden, F = c->ffn, F1 = enc_ffn1_cols(c), es = 2;
+  const size_t row0 = h ? (size_t)(B0 * L) : 0, seq0 = h ? (size_t)B0 : 0;
+  EncWs v = {};
+  v.x = w.x + row0 * H * es; v.y = w.y + row0 * H * es; v.x1 = w.x1 + row0 * H * es;
+  v.qkv = w.qkv + row0 * 3 * H * es;
+  v.ctx = w.ctx + row0 * H * es;
+  v.ff = w.ff + row0 * F1 * es;
+  v.ff2 = c->arch == OM_ARCH_NOMICBERT ? w.ff2 + row0 * F * es : w.ff2;
+  v.y_lo = w.y_lo + row0 * H * es; v.x1_lo = w.x1_lo + row0 * H * es;
+  v.pooled = w.pooled + seq0 * H;
+  v.headout = w.headout + seq0 * (size_t)(c->head_out > 0 ? c->head_out : 1);
+  v.kmax = w.kmax + seq0;
+  v.final32 = w.final32 + (c->pooling == OM_POOL_FIRST ? seq0 : row0) * H;
+  v.stats1 = w.stats1 + 4 * (size_t)c->n_layers * row0;
+  v.stats2 = v.stats1 + (size_t)c->n_layers * (size_t)lane.Mg * 2;
+  v.slots = w.slots + 4 * ((H + 255) / 256) * row0;
+  v.total = w.total;
+  return v;
+}
+
+// (offset, bytes) of every field of a lane's view, in the order include/openmatch_hip.h documents (om_debug_encoder_lane_ranges)
+static void lane_ranges(const OmEncoderConfig* c, const EncWs& v, const EncPlan& lane, int64_t Bh, const char* base, int64_t* out) {
+  const size_t H = c->hidden, F = c->ffn, F1 = enc_ffn1_cols(c), es = 2, M = (size_t)lane.Mp, B = (size_t)Bh;
+  const bool nomic = c->arch == OM_ARCH_NOMICBERT;
+  const std::pair<const void*, size_t> f[OM_ENCODER_LANE_RANGES] = {
+      {v.x, M * H * es}, {v.y, M * H * es}, {v.x1, M * H * es}, {v.qkv, M * 3 * H * es}, {v.ctx, M * H * es}, {v.ff, M * F1 * es},
+      {v.ff2, nomic ? M * F * es : 0}, {v.pooled, B * H * 4}, {v.headout, B * (size_t)(c->head_out > 0 ? c->head_out : 1) * 4}, {v.kmax, B * 4},
+      {v.final32, (c->pooling == OM_POOL_FIRST ? B : (size_t)lane.M) * H * 4}, {v.stats1, (size_t)2 * c->n_layers * M * 8},
+      {v.slots, (size_t)2 * ((H + 255) / 256) * M * 8}, {v.y_lo, M * H * es}, {v.x1_lo, M * H * es}};
+  for (int i = 0; i < OM_ENCODER_LANE_RANGES; ++i) {
+    out[2 * i] = (int64_t)((const char*)f[i].first - base);
+    out[2 * i + 1] = (int64_t)f[i].second;
+  }
+}
+
+// host only: the lanes rule at the current switches (include/openmatch_hip.h)
+extern "C" int om_debug_encoder_lanes(const OmEncoderConfig* c, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
+                                      int want_hidden, int64_t* B0) {
+  if (!c) {
+    om_set_error("om_debug_encoder_lanes: null argument");
+    return -1;
+  }
+  const EncPlanIn in = {c, B, L, packed_rows, want_hidden != 0, gated_ffn != 0, has_rel_bias != 0, c->type_vocab > 0};
+  const EncSwitches sw = encoder_switches();
+  return encoder_lanes(in, encoder_plan(in, sw), sw, B0) ? 1 : 0;
+}
+
+// host only: where lane `lane` of the call (B, L) lives in the call's workspace (include/openmatch_hip.h)
+extern "C" int om_debug_encoder_lane_ranges(const OmEncoderConfig* c, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int lane,
+                                            int64_t* out, int cap) {
+  if (!c || !out || cap < 2 * OM_ENCODER_LANE_RANGES || (lane != 0 && lane != 1)) {
+    om_set_error("om_debug_encoder_lane_ranges: null argument, a lane other than 0 | 1, or room for fewer than 15 pairs");
+    return -1;
+  }
+  EncPlanIn in = {c, B, L, 0, false, gated_ffn != 0, has_rel_bias != 0, c->type_vocab > 0};
+  const EncSwitches sw = encoder_switches();
+  const EncPlan whole = encoder_plan(in, sw);
+  int64_t B0 = 0;
+  if (!encoder_lanes(in, whole, sw, &B0)) {
+    om_set_error("om_debug_encoder_lane_ranges: this call does not fork (om_debug_encoder_lanes)");
+    return -1;
+  }
+  static char origin[1];      // (offsets are differences of addresses: any base will do)
+  const EncWs ws = carve(c, whole, B, L, 0, origin);
+  in.B = lane ? B - B0 : B0;
+  const EncPlan lp = encoder_plan_checked(in, sw);
+  lane_ranges(c, lane_view(c, ws, lp, lane, B0, L), lp, in.B, origin, out);
+  return OM_ENCODER_LANE_RANGES;
+}
+
+static std::atomic<int64_t> g_lane_forks{0};
+extern "C" int64_t om_debug_encoder_lane_forks(void) { return g_lane_forks.load(); }
+
+// The stream lane 1 runs on and the two events of the fork and the join: one per (device, caller stream), created on first use, kept
+// for the life of the process like skip_pad_buffer's entries (train.hip's WgradLane is the precedent).  Non-blocking: torch's default
+// stream is the null stream, and a blocking stream would serialise against it.
+struct LaneStream { hipStream_t side = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+static int lane_stream(hipStream_t s, LaneStream* out) {
+  static std::mutex mu;
+  static std::map<std::pair<int, hipStream_t>, LaneStream> lanes;
+  int dev = 0;
+  OM_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  LaneStream& l = lanes[std::make_pair(dev, s)];
+  if (!l.side) {
+    LaneStream n;
+    OM_HIP(hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking));
+    OM_HIP(hipEventCreateWithFlags(&n.fork, hipEventDisableTiming));
+    OM_HIP(hipEventCreateWithFlags(&n.join, hipEventDisableTiming));
+    l = n;
+  }
+  *out = l;
+  return 0;
+}
+
+static int encoder_chain(const EncChain& q, std::vector<int>* families);
+
+// A padded call as two lanes (encoder_plan.h encoder_lanes).  *forked = 0 and nothing enqueued: the caller runs the one
+// chain it always ran -- a no is never an error.  Beyond the rule, decided here with host checks alone:
+//   - w->folded: without it every lane would fold into the one workspace scratch;
+//   - the stream is not capturing: a captured graph stays one linear chain;
+//   - not in timing mode: hipEvents around co-running kernels price nothing, so the roofline pass keeps measuring one stream;
+//   - every contraction of the layer loop (and the head's) plans the same GEMM family at each lane's height as at the whole's, asked
+//     with the pointers and epilogues the launches carry (bert_fused under EncCall::families).  Within a family a row's bits do not
+//     depend on the rows beside it; across families they may.  The one place where the family moves with M is the tile-choice model
+//     of gemm_plan.h rule 5 (the first layer's plain QKV at small shapes), so a lane's contractions are priced at the WHOLE's height
+//     (EncCall::whole_mg / whole_mc -> omk_gemm's plan_m): the lanes then run the kernels the whole call would, and this check is what
+//     proves it call by call instead of assuming it.
+// After the fork the join is made whatever the lanes return, so the caller's stream is never left unordered against the side stream.
+static int encoder_fork(const EncChain& whole, int* forked) {
+  *forked = 0;
+  const OmEncoderConfig* c = whole.c;
+  const int64_t B = whole.in.B, L = whole.in.L;
+  int64_t B0 = 0;
+  if (!whole.w->folded || om_timing_on() || !encoder_lanes(whole.in, whole.plan, whole.sw, &B0)) return 0;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(whole.s, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  if (st != hipStreamCaptureStatusNone) return 0;
+  LaneStream ls;
+  RUN(lane_stream(whole.s, &ls));
+  const bool skip = encoder_skip_pad(whole.in, whole.plan, whole.sw);
+  int64_t whole_mc = 0;
+  if (!encoder_cls_tail(whole.in, whole.plan, whole.sw, &whole_mc)) whole_mc = 0;
+  const int64_t D =c->head_in > 0 && whole.w->head_w ? c->head_out : c->hidden;
+  EncChain lane[2] = {whole, whole};
+  for (int h = 0; h < 2; ++h) {
+    EncChain& q = lane[h];
+    const int64_t seq0 = h ? B0 : 0;
+    q.in.B = h ? B - B0 : B0;
+    q.plan = encoder_plan_checked(q.in, q.sw);
+    q.ws = lane_view(c, whole.ws, q.plan, h, B0, L);
+    q.input_ids += seq0 * L; q.attention_mask += seq0 * L;
+    if (q.token_type_ids) q.token_type_ids += seq0 * L;
+    q.out_reps += seq0 * D;
+    if (h) q.s = ls.side;
+    q.whole_mg = whole.plan.Mg; q.whole_mc = whole_mc;
+    q.side = nullptr;
+    if (skip) {
+      RUN(skip_pad_buffer(q.s, (size_t)(q.plan.Mp + 2 * q.in.B + 2), &q.side));
+      if (!q.side) return 0;
+    }
+  }
+  if (lane[0].plan.Mp != B0 * L || lane[0].plan.Mp + lane[1].plan.Mp != whole.plan.Mp) return 0;      // (the rule's B0: cannot happen)
+  EncChain ask = whole;
+  ask.side = lane[0].side;      // any address: the planner tests it for null only
+  std::vector<int> fam_whole, fam_lane[2];
+  if (encoder_chain(ask, &fam_whole) || encoder_chain(lane[0], &fam_lane[0]) || encoder_chain(lane[1], &fam_lane[1])) return 0;
+  if (fam_lane[0] != fam_whole || fam_lane[1] != fam_whole || std::find_if(fam_whole.begin(), fam_whole.end(), [](int f) { return f <= 0; }) != fam_whole.end())
+    return 0;
+
+  OM_HIP(hipEventRecord(ls.fork, whole.s));
+  OM_HIP(hipStreamWaitEvent(ls.side, ls.fork, 0));
+  *forked = 1;
+  g_lane_forks.fetch_add(1);
+  // lane 0 first: the head start its host enqueue order gives keeps the two chains out of phase
+  int rc = encoder_chain(lane[0], nullptr);
+  if (!rc) rc = encoder_chain(lane[1], nullptr);
+  hipError_t e = hipEventRecord(ls.join, ls.side);
+  if (e == hipSuccess) e = hipStreamWaitEvent(whole.s, ls.join, 0);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ls.side);      // no event to wait on: order the caller's stream by waiting here
+    if (!rc) OM_FAIL(std::string("encoder lanes: join failed: ") + hipGetErrorString(e));
+  }
+  return rc;
+}
+
+// plan, carve, then the call's chain -- or its two lanes
 static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* w,
                                 const int64_t* input_ids, const int64_t* attention_mask,
                                 const int64_t* token_type_ids, int64_t B, int64_t L,
@@ -704,8 +914,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
                              w->type_emb != nullptr};
   const EncSwitches sw = encoder_switches();
   const EncPlan plan = encoder_plan_checked(plan_in, sw);
-  const bool bert = enc_bert_family(c);
-  if (om_option(OM_OPT_ENCODER_DEBUG) && plan.path && bert)
+  if (om_option(OM_OPT_ENCODER_DEBUG) && plan.path && enc_bert_family(c))
     fprintf(stderr, "om_encoder_forward: M=%ld fused_ln=%d packed=%d few_rows=%d pending_ln=%d L=%ld head_dim=%d rel_bias=%d\n", (long)plan.M,
             (int)(plan.path == OM_ENC_PATH_BERT_FUSED), (int)(packed_rows > 0), (int)plan.few_rows, (int)(plan.path == OM_ENC_PATH_BERT_PENDING_LN), (long)L,
             c->head_dim, (int)plan.rel_bias);
@@ -716,10 +925,28 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   if (c->arch == OM_ARCH_MODERNBERT && (!w->emb_ln_g || !w->final_ln_g)) OM_FAIL("ModernBERT needs emb_ln_g and final_ln_g");
   if (c->arch == OM_ARCH_NOMICBERT && (!w->type_emb || w->pos_emb || w->rel_bias)) OM_FAIL("NomicBERT needs type_emb and takes no pos_emb or rel_bias");
   if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  EncWs ws = carve(c, plan, B, L, packed_rows, (char*)workspace);
-  if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
+  EncChain whole = {c, w, input_ids, attention_mask, token_type_ids, out_hidden, out_reps, plan_in, plan, sw,
+                    carve(c, plan, B, L, packed_rows, (char*)workspace), (hipStream_t)stream, nullptr, 0, 0};
+  if (whole.ws.total > workspace_bytes) OM_FAIL("workspace too small");
   if (c->pooling != OM_POOL_NONE && !out_reps) OM_FAIL("out_reps required when pooling is set");
-  hipStream_t s = (hipStream_t)stream;
+  int forked = 0;
+  RUN(encoder_fork(whole, &forked));
+  if (forked) return 0;
+  if (encoder_skip_pad(plan_in, plan, sw)) RUN(skip_pad_buffer(whole.s, (size_t)(plan.Mp + 2 * B + 2), &whole.side));
+  return encoder_chain(whole, nullptr);
+}
+
+// the chain's layer loop, the last normalisation, pooling.  families: launch nothing, answer which GEMM family each contraction of the
+// fused BERT loop and the head would plan (encoder_fork)
+static int encoder_chain(const EncChain& q, std::vector<int>* families) {
+  const OmEncoderConfig* c = q.c; const OmEncoderWeights* w = q.w;
+  const int64_t *input_ids = q.input_ids, *attention_mask = q.attention_mask, *token_type_ids = q.token_type_ids;
+  void* const out_hidden = q.out_hidden; float* const out_reps = q.out_reps;
+  const EncPlanIn& plan_in = q.in; const EncPlan& plan = q.plan; const EncSwitches sw = q.sw;
+  const int64_t B = q.in.B, L = q.in.L, packed_rows = q.in.packed_rows;
+  const bool bert = enc_bert_family(c);
+  EncWs ws = q.ws;
+  hipStream_t s = q.s;
   const int dt = c->dtype, H = c->hidden;
   const int64_t M = plan.M;
   // A padded call that skips its pad rows (encoder_skip_pad) IS the packed call with the bound roundup256(B * L) from here on -- the
@@ -727,20 +954,26 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
   // per-row kernels need no more; Mp = Mg = the bound, the height of the workspace's buffers) -- with its three arrays in the
   // library's side buffer, and the contractions stop at the token count the packing launch leaves in cu[B].
   int64_t pack_bound = packed_rows;
-  bool skip = false;
-  if (encoder_skip_pad(plan_in, plan, sw)) {
-    int* side = nullptr;
-    RUN(skip_pad_buffer(s, (size_t)(plan.Mp + 2 * B + 2), &side));
-    if (side) {
-      skip = true;
-      pack_bound = plan.Mp;
-      ws.cu = side; ws.cls_rows = side + (B + 2); ws.row_map = ws.cls_rows + B;
-    }
+  const bool skip = q.side != nullptr;
+  if (skip) {
+    pack_bound = plan.Mp;
+    ws.cu = q.side; ws.cls_rows = q.side + (B + 2); ws.row_map = ws.cls_rows + B;
   }
   const bool packed = pack_bound > 0;      // the token axis holds packed rows
   int64_t cls_mc = 0;                      // the last layer's per-row tail over the [CLS] rows alone (encoder_plan.h encoder_cls_tail)
   if (!encoder_cls_tail(plan_in, plan, sw, &cls_mc)) cls_mc = 0;
   const int* const row_map = packed ? ws.row_map : nullptr;
+  if (families) {
+    if (plan.path != OM_ENC_PATH_BERT_FUSED) OM_FAIL("encoder lanes: the fused BERT path only");
+    const EncCall k = {c, w, attention_mask, B, L, plan, ws, nullptr, packed ? ws.cu : nullptr, row_map, out_hidden, s, skip ? ws.cu + B : nullptr,
+                       cls_mc, families, q.whole_mg, q.whole_mc};
+    EncStream unused = {};
+    RUN(bert_fused(k, &unused));
+    if (c->head_in > 0 && w->head_w)      // omk_pooled_tail's contraction
+      families->push_back(omk_gemm_family(OM_F32, ws.pooled, c->hidden, w->head_w, c->head_in, OM_F32, out_reps, c->head_out, B, c->head_out,
+                                          c->head_in, GemmEpilogue{}));
+    return 0;
+  }
 
   RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
   if (packed) RUN(omk_pack_rows(ws.kmax, B, (int)L, pack_bound, ws.cu, ws.cls_rows, ws.row_map, s));
@@ -762,7 +995,7 @@ static int encoder_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights
     RUN(omk_embed(dt, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
 
   const EncCall k = {c, w, attention_mask, B, L, plan, ws, plan.rel_bias ? ws.posbias : nullptr, packed ? ws.cu : nullptr, row_map, out_hidden, s,
-                     skip ? ws.cu + B : nullptr, cls_mc};
+                     skip ? ws.cu + B : nullptr, cls_mc, nullptr, q.whole_mg, q.whole_mc};
   EncStream stream_out = {};
   switch (plan.path) {
     case OM_ENC_PATH_BERT_FUSED: RUN(bert_fused(k, &stream_out)); break;

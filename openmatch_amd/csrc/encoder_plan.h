@@ -19,13 +19,14 @@ struct EncSwitches {
   int attention_fast; // OM_OPT_ATTENTION_FAST: read by om_encoder_packed_supported only (attn_plan.h decides the attention kernel itself)
   int skip_pad;       // OM_OPT_ENCODER_SKIP_PAD: read by encoder_skip_pad only (the plan itself does not change with it)
   int cls_tail;       // OM_OPT_ENCODER_CLS_TAIL: read by encoder_cls_tail only (likewise)
+  int lanes;          // OM_OPT_ENCODER_LANES: read by encoder_lanes only (likewise): the least padded token rows per lane, 0: off
 };
 
 // every switch the planner reads, read once per call (omk_gemm_ln_fusable reads OM_OPT_GEMM_VARIANT and om_debug_gemm_gen itself)
 static EncSwitches encoder_switches() {
   return EncSwitches{om_option(OM_OPT_ENCODER_FUSED_LN), om_option(OM_OPT_ENCODER_TWO_PLANE), om_option(OM_OPT_ENCODER_PINGPONG),
                      om_option(OM_OPT_GEMM_SKINNY_M), om_option(OM_OPT_FEW_ROWS_LN_FUSE), om_option(OM_OPT_ATTENTION_FAST),
-                     om_option(OM_OPT_ENCODER_SKIP_PAD), om_option(OM_OPT_ENCODER_CLS_TAIL)};
+                     om_option(OM_OPT_ENCODER_SKIP_PAD), om_option(OM_OPT_ENCODER_CLS_TAIL), om_option(OM_OPT_ENCODER_LANES)};
 }
 
 struct EncPlanIn {
@@ -245,5 +246,39 @@ static bool encoder_cls_tail(const EncPlanIn& in, const EncPlan& p, const EncSwi
   const int64_t mc = (in.B + 255) / 256 * 256;
   if (4 * mc > p.Mp) return false;
   if (Mc) *Mc = mc;
+  return true;
+}
+
+// Whether a PADDED call whose plan is p runs as two half-batches -- "lanes" -- on two streams ("two lanes"): sequences
+// [0, B0) on the caller's stream, [B0, B) on a stream the library owns, each the whole chain of a call of its own over its rows of the
+// one workspace.  Since the pad rows are skipped, a launch's last round of tiles leaves most of the chip empty; the other lane's
+// workgroups take those CUs.  The rule, stated once: the switch is on (its value is the least PADDED token rows a lane must have); it is
+// the padded entry; a pooling is set and no hidden states are wanted; the call plans the fused BERT path without a relative-position
+// bias; B0 -- the largest count <= B / 2 with B0 * L in whole 256-row tiles, so that lane 1's buffers start on a tile -- and B - B0
+// both have that many rows; and each lane, planned as the call (B0, L) / (B - B0, L) it is, gets the whole's path, planes and walk,
+// the whole's pad-skip decision and the whole's [CLS]-tail decision: a lane runs the kernels the whole call would, over fewer rows,
+// and every kernel of the chain keeps a row's bits whatever rides along.  A lane of ENC_LANE_ROWS_END padded rows or more does not
+// fork either: the tail a lane can fill is one round of a launch however tall the launch is, while two chains that share the caches
+// slow each other in proportion to their size -- 2 048 x 128 (lanes of 131 072 rows) measured 2.4 % SLOWER forked, 1 024 x 128 4.3 %
+// faster, the batches between them 0.5-1.7 % faster.  What the forward adds at fork time (no capture, no timing
+// mode, folded weights given, the same GEMM family per contraction): encoder.hip encoder_fork.  *B0: lane 0's sequences.
+static const int64_t ENC_LANE_ROWS_END = 131072;
+static bool encoder_lanes(const EncPlanIn& in, const EncPlan& p, const EncSwitches sw, int64_t* B0 = nullptr) {
+  if (sw.lanes <= 0 || in.packed_rows != 0 || in.want_hidden || in.has_rel_bias || in.c->pooling == OM_POOL_NONE) return false;
+  if (p.error || p.path != OM_ENC_PATH_BERT_FUSED || p.rel_bias || in.B < 2 || in.L < 1) return false;
+  int64_t step = 256;      // sequences per whole number of tiles: 256 / gcd(L, 256)
+  for (int64_t l = in.L; step > 1 && l % 2 == 0; l /= 2) step /= 2;
+  const int64_t b0 = in.B / 2 / step * step;
+  if (b0 <= 0 || b0 * in.L < (int64_t)sw.lanes || (in.B - b0) * in.L < (int64_t)sw.lanes) return false;
+  if ((in.B - b0) * in.L >= ENC_LANE_ROWS_END) return false;
+  const bool skip = encoder_skip_pad(in, p, sw), tail = encoder_cls_tail(in, p, sw);
+  for (const int64_t bh : {b0, in.B - b0}) {
+    EncPlanIn li = in;
+    li.B = bh;
+    const EncPlan lp = encoder_plan_checked(li, sw);
+    if (lp.error || lp.path != p.path || lp.two != p.two || lp.lo8 != p.lo8 || lp.pingpong != p.pingpong) return false;
+    if (encoder_skip_pad(li, lp, sw) != skip || encoder_cls_tail(li, lp, sw) != tail) return false;
+  }
+  if (B0) *B0 = b0;
   return true;
 }

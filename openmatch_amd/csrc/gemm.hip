@@ -118,10 +118,12 @@ int omk_gemm_skinny(int dtype, const void* A, int64_t lda, const void* W, int64_
                     int64_t K, const GemmEpilogue& ep, hipStream_t s);
 
 int omk_gemm(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, void* C, int64_t ldc, int64_t M,
-             int64_t N, int64_t K, const GemmEpilogue& ep_in, hipStream_t s) {
+             int64_t N, int64_t K, const GemmEpilogue& ep_in, hipStream_t s, int64_t plan_m) {
   GemmEpilogue ep = ep_in;
   ep.trace = g_trace, g_gemm_last = 0;
-  const GemmPlan p = gemm_plan(in_dtype, (uintptr_t)A, lda, (uintptr_t)B, ldb, out_dtype, (uintptr_t)C, ldc, M, N, K, ep, gemm_switches(g_debug_gen));
+  GemmSwitches sw = gemm_switches(g_debug_gen);
+  sw.plan_m = plan_m;
+  const GemmPlan p = gemm_plan(in_dtype, (uintptr_t)A, lda, (uintptr_t)B, ldb, out_dtype, (uintptr_t)C, ldc, M, N, K, ep, sw);
   if (p.error) OM_FAIL(p.error);
 #define OM_GEMM_GO(TI, TO)                                                                                      \
   return p.family == OM_GEMM_FAMILY_V2 ? launch_gemm2<TI, TO>(A, lda, B, ldb, C, ldc, M, N, K, ep, s)           \
@@ -145,6 +147,15 @@ int omk_gemm(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ld
   }
 #undef OM_GEMM_GO
   OM_FAIL("the plan names no launcher");
+}
+
+// the plan alone, for a caller that must know the family before it launches (encoder.hip encoder_fork)
+int omk_gemm_family(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, const void* C, int64_t ldc, int64_t M,
+                    int64_t N, int64_t K, const GemmEpilogue& ep, int64_t plan_m) {
+  GemmSwitches sw = gemm_switches(g_debug_gen);
+  sw.plan_m = plan_m;
+  const GemmPlan p = gemm_plan(in_dtype, (uintptr_t)A, lda, (uintptr_t)B, ldb, out_dtype, (uintptr_t)C, ldc, M, N, K, ep, sw);
+  return p.error ? -1 : p.family;
 }
 
 // test hook (openmatch_hip.h): the family om_gemm_nt would launch, -1 for a refusal; the pointers are addresses only

@@ -16,11 +16,13 @@ struct GemmSwitches {
   int cont;         // OM_OPT_GEMM_CONT: the bit mask of the continuous-ring kernels
   int skinny_m;     // OM_OPT_GEMM_SKINNY_M: most rows of the few-rows kernel
   int debug_gen;    // om_debug_gemm_gen: 0 default; 6: never generation 7; 70: generation 7 with one tile per workgroup (A/B)
+  int64_t plan_m;   // > 0: rule 5 prices the tile generations as for a contraction of this many rows (omk_gemm_as: a lane of the
+                    //   encoder forward runs the kernels its whole batch would); 0: the call's own M
 };
 
 // every switch the planner reads, read once per call
 static GemmSwitches gemm_switches(int debug_gen) {
-  return GemmSwitches{om_option(OM_OPT_GEMM_VARIANT), om_option(OM_OPT_GEMM_CONT), om_option(OM_OPT_GEMM_SKINNY_M), debug_gen};
+  return GemmSwitches{om_option(OM_OPT_GEMM_VARIANT), om_option(OM_OPT_GEMM_CONT), om_option(OM_OPT_GEMM_SKINNY_M), debug_gen, 0};
 }
 
 // the continuous ring needs three K steps (its prefetch reaches at most one tile ahead)
@@ -89,8 +91,9 @@ static GemmPlan gemm_plan(int in_dtype, uintptr_t A, int64_t lda, uintptr_t B, i
   int gen = 1;
   if (wide) {
     // cost = rounds x (work a CU has in flight per round) / efficiency; v1 keeps 2 workgroups per CU
+    const int64_t Mt = sw.plan_m > 0 ? sw.plan_m : M;
     auto rounds = [&](int64_t bm, int64_t bn, int64_t slots) {
-      const int64_t tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+      const int64_t tiles = ((Mt + bm - 1) / bm) * ((N + bn - 1) / bn);
       return (double)((tiles + slots - 1) / slots);
     };
     const double c4 = N >= 256 ? rounds(256, 256, 256) * (256.0 * 256.0) / 1.00 : 1e30;

@@ -199,7 +199,10 @@ int omk_gemm_wide6_f32(int in_dtype, const void* A, int64_t lda, const void* B, 
                        void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep, hipStream_t s);
 int omk_gemm(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype,
              void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep,
-             hipStream_t s);
+             hipStream_t s, int64_t plan_m = 0);      // plan_m > 0: choose the tile generation as for that many rows (gemm_plan.h GemmSwitches)
+// host only: the family (OM_GEMM_FAMILY_*) omk_gemm would launch for these arguments at the current switches, -1: it would refuse them
+int omk_gemm_family(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int out_dtype, const void* C, int64_t ldc, int64_t M,
+                    int64_t N, int64_t K, const GemmEpilogue& ep, int64_t plan_m = 0);
 // the kernel family (OM_GEMM_FAMILY_*) the calling thread's last omk_gemm launched: one host store per launch (om_debug_gemm_last)
 void omk_gemm_note(int family);
 

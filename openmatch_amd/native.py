@@ -213,6 +213,9 @@ _SIGNATURES = {
     "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "om_debug_encoder_skip_pad": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int]),
     "om_debug_encoder_cls_tail": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
+    "om_debug_encoder_lanes": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int, C.POINTER(c_int64)]),
+    "om_debug_encoder_lane_ranges": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int, C.POINTER(c_int64), c_int]),
+    "om_debug_encoder_lane_forks": (c_int64, []),
     "om_debug_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                      c_int64, c_int, c_void_p]),
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
