@@ -1004,6 +1004,7 @@ int om_topk_merge(const float* part_scores, const int64_t* part_ids, int W, int6
  *   q[q_row0 : q_row0+q_rows], p[p_row0 : p_row0+p_rows] (the reference's
  *   all_gather re-inserts only the local tensor: :247-258).
  * scores (f32 [Qg,Pg]) may be NULL; d_q / d_p may be NULL (forward only).
+ * Any d >= 1; q and p need the alignment of a float only.
  * workspace: (2*Qg*Pg + Qg) floats.
  * ------------------------------------------------------------------------ */
 int om_contrastive_fwd_bwd(const float* q, const float* p, int Qg, int Pg, int d, int n_psg,

@@ -90,6 +90,20 @@ __global__ __launch_bounds__(256) void scores_small_kernel(const float* __restri
   if (lane == 0) S[w] = acc;
 }
 
+// the same wave per dot product with 4-byte loads: any d >= 1, rows and pointers aligned to a float only
+__global__ __launch_bounds__(256) void scores_scalar_kernel(const float* __restrict__ q, const float* __restrict__ p,
+                                                             float* __restrict__ S, int Qg, int Pg, int d) {
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= (int64_t)Qg * Pg) return;
+  const int i = (int)(w / Pg), j = (int)(w % Pg), lane = threadIdx.x & 63;
+  const float* a = q + (int64_t)i * d;
+  const float* b = p + (int64_t)j * d;
+  float acc = 0.f;
+  for (int c = lane; c < d; c += 64) acc = fmaf(a[c], b[c], acc);
+  acc = wave_sum(acc);
+  if (lane == 0) S[w] = acc;
+}
+
 // d_q[i,c] = sum_j dS[q_row0+i, j] * p[j,c]
 __global__ void dq_kernel(const float* __restrict__ dS, const float* __restrict__ p,
                           float* __restrict__ dq, int Pg, int d, int q_row0) {
@@ -117,7 +131,7 @@ extern "C" int om_contrastive_fwd_bwd_ex(const float* q, const float* p, int Qg,
                                          int n_psg, int reduction, const float* row_grad, float loss_scale, int q_row0,
                                          int q_rows, int p_row0, int p_rows, float* loss, float* scores, float* d_q,
                                          float* d_p, float* workspace, void* stream) {
-  if (Qg <= 0 || Pg <= 0) OM_FAIL("empty batch");
+  if (Qg <= 0 || Pg <= 0 || d <= 0) OM_FAIL("empty batch");
   if (!target && (int64_t)(Qg - 1) * n_psg >= Pg) OM_FAIL("target index out of range (Pg < Qg * n_psg)");
   if (reduction < OM_CE_MEAN || reduction > OM_CE_NONE) OM_FAIL("reduction must be 0 (mean), 1 (sum) or 2 (none)");
   if (!workspace || !loss) OM_FAIL("null argument");
@@ -130,11 +144,21 @@ extern "C" int om_contrastive_fwd_bwd_ex(const float* q, const float* p, int Qg,
   float* row_loss = dS + (size_t)Qg * Pg;
   float* valid = row_loss + Qg;
   const bool bwd = d_q || d_p;
-  if ((int64_t)Qg * Pg <= 65536 && d % 4 == 0 && !(((uintptr_t)q | (uintptr_t)p) & 15)) {
-    hipLaunchKernelGGL(scores_small_kernel, dim3((unsigned)(((int64_t)Qg * Pg + 3) / 4)), dim3(256), 0, s, q, p, S, Qg, Pg, d);
+  // Scores: above 65536 of them the exact-f32 GEMM, where its planner takes the operands (d % 32 == 0, 16-byte aligned q and p);
+  // everywhere else one wave per dot product, with float4 loads where d % 4 == 0 and both pointers are 16-byte aligned and with
+  // 4-byte loads otherwise, so every d >= 1 and every float-aligned q / p has a path at every batch size.
+  omk_gemm_note(0);                      // om_debug_gemm_last reads 0 after a call that ran no GEMM
+  const int64_t n_scores = (int64_t)Qg * Pg;
+  const bool vec4 = d % 4 == 0 && !(((uintptr_t)q | (uintptr_t)p) & 15);
+  const GemmEpilogue no_ep = {};
+  if (n_scores > 65536 && omk_gemm_family(OM_F32, q, d, p, d, OM_F32, S, Pg, Qg, Pg, d, no_ep) > 0) {
+    if (om_gemm_nt(OM_F32, q, d, p, d, OM_F32, S, Pg, Qg, Pg, d, nullptr, nullptr, 0, OM_ACT_NONE, s)) return 1;
+  } else {
+    if ((n_scores + 3) / 4 > 0x7fffffff) OM_FAIL("score matrix too large for the wave-per-dot kernel");
+    const dim3 grid((unsigned)((n_scores + 3) / 4));
+    if (vec4) hipLaunchKernelGGL(scores_small_kernel, grid, dim3(256), 0, s, q, p, S, Qg, Pg, d);
+    else hipLaunchKernelGGL(scores_scalar_kernel, grid, dim3(256), 0, s, q, p, S, Qg, Pg, d);
     OM_LAUNCH_CHECK();
-  } else if (om_gemm_nt(OM_F32, q, d, p, d, OM_F32, S, Pg, Qg, Pg, d, nullptr, nullptr, 0, OM_ACT_NONE, s)) {
-    return 1;
   }
   if (target) {
     hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(64), 0, s, target, Qg, valid);

@@ -121,6 +121,9 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(const OmAdamTensor* __re
     mv += (gv - mv) * (1.0f - a.beta1);
     vv = vv * a.beta2 + gv * gv * (1.0f - a.beta2);
     pv -= a.step_size * (mv / (sqrtf(vv) * a.bc2_sqrt_inv + a.eps));
+    // A shadow is the STORED float32 rounded once.  Left alone, the compiler folds the last fma into the f16 conversion
+    // (v_fma_mixlo_f16), which rounds the unstored sum instead: the empty statement makes pv the rounded float32 for every use.
+    asm volatile("" : "+v"(pv));
     p[i] = pv; m[i] = mv; v[i] = vv;
     for (int k = 0; k < 2; ++k) {
       void* sh = k ? t.shadow1 : t.shadow0;

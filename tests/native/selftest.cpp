@@ -250,7 +250,7 @@ static void test_merge() {
 static void test_contrastive() {
   const int Qg = 16, n_psg = 4, Pg = 64, d = 128; const float scale = 2.f;
   auto q = randn(Qg * d, 0.3f), p = randn(Pg * d, 0.3f);
-  float *dq = upload(q), *dp = upload(p), *dl = dalloc<float>(1), *ds = dalloc<float>(Qg * Pg), *gq = dalloc<float>(8 * d), *gp = dalloc<float>(32 * d), *ws = dalloc<float>(2 * Qg * Pg + Qg);
+  float *dq = upload(q), *dp = upload(p), *dl = dalloc<float>(1), *ds = dalloc<float>(Qg * Pg), *gq = dalloc<float>(8 * d), *gp = dalloc<float>(32 * d), *ws = dalloc<float>(2 * Qg * Pg + Qg + 1);
   OMCK(om_contrastive_fwd_bwd(dq, dp, Qg, Pg, d, n_psg, scale, 8, 8, 32, 32, dl, ds, gq, gp, ws, nullptr)); CK(hipDeviceSynchronize());
   std::vector<double> S(Qg * Pg), dS(Qg * Pg); double loss = 0;
   for (int i = 0; i < Qg; ++i) { double mx = -1e300; for (int j = 0; j < Pg; ++j) { double a = 0; for (int c = 0; c < d; ++c) a += (double)q[i * d + c] * p[j * d + c]; S[i * Pg + j] = a; mx = std::max(mx, a); } double sum = 0; for (int j = 0; j < Pg; ++j) sum += exp(S[i * Pg + j] - mx); loss += mx + log(sum) - S[i * Pg + i * n_psg]; for (int j = 0; j < Pg; ++j) dS[i * Pg + j] = (exp(S[i * Pg + j] - mx) / sum - (j == i * n_psg)) * scale / Qg; }

@@ -75,7 +75,7 @@ kernel's order, rounded to the storage type); worst error / bound of each at the
 Measured constants: see RSQRT_MEASURED and DIVSQRT_MEASURED below.
 
 Still untested at kernel level (whole-model tests only): the transposes (omk_transpose, omk_transpose_batch), the T5 activation,
-embedding and bias kernels, omk_small_nn / omk_small_tn, omk_zero_rows_from and the GEMM epilogue's dropout.
+embedding and bias kernels, omk_zero_rows_from and the GEMM epilogue's dropout.
 """
 import ctypes as C
 import math
