@@ -958,12 +958,38 @@ size_t om_sim_topk_workspace_bytes(int64_t n_queries, int d, int k);
  * id_offset + row, padded with (-3.4028235e38, -1) when N < k (faiss semantics).
  * Ties are ordered by ascending row.  mode OM_SEARCH_F16_RESCORE needs
  * index_f16 + stats from om_index_to_f16; returned scores are always the
- * exact f32 inner products.  Synchronises `stream` internally (reads back
- * overflow flags between scan rounds).  k <= 2048. */
+ * exact f32 inner products.  k <= 2048.
+ * NOT stream-ordered for the host: om_sim_topk synchronises `stream` ONCE per call (it reads the
+ * overflow flags back at the end of its fast schedule; more often on the rare careful path), so
+ * it blocks its caller, cannot be captured in a graph and cannot overlap a second search of the
+ * same thread.  om_sim_topk_async below is the entry that only enqueues. */
 int om_sim_topk(int mode, const float* queries, int64_t n_queries, const float* index_f32,
                 const void* index_f16, const float* stats, int64_t N, int d, int k,
                 int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
                 size_t workspace_bytes, void* stream);
+
+/* The same search, stream-ordered: arguments, argument checks, output layout, padding and tie rule of om_sim_topk, but the entry only
+ * ENQUEUES work on `stream` -- no stream / device / event synchronisation, no blocking copy, no allocation, no host read of device
+ * memory.  After one eager call has set the kernels' function attributes it is legal on a capturing stream.  What om_sim_topk decides
+ * on the host from its flags is decided per query on the device: a query whose candidate list overflowed (masses of exact ties:
+ * duplicated rows), whose certified f16 margin was too wide, or whose list outgrew the re-score is recomputed exactly by an on-device
+ * radix select over all rows (csrc/search.hip, "on-device redo"); the other queries of the batch keep the bits om_sim_topk returns.
+ * A redone query's scores are the f32 dot products of the f16 mode's re-score, in both modes.
+ * status: device memory, 8 x int64, not NULL, written by the last kernel of the chain: [0] scan precision as om_sim_topk_info reports it
+ * (1 f16+rescore, 0 f32; a too-wide margin does not change it here), [1] rounds, [2] queries redone on the device, [3] longest list,
+ * [4] queries whose certified margin was too wide, [5] OM_SCAN_FAMILY_* of the last filtered round, [6] 1, written last (0 from the
+ * start of the chain), [7] 0.  Refuses when OM_OPT_SCAN_GEN7 = 0 has switched the fast schedule off, and d > 16384.
+ * workspace: om_sim_topk_async_workspace_bytes (>= om_sim_topk_workspace_bytes; 0 for n_queries <= 0), 256-byte aligned, owned by the
+ * call until the stream has passed it: two searches in flight need two workspaces.  om_sim_topk_info is not touched. */
+size_t om_sim_topk_async_workspace_bytes(int64_t n_queries, int d, int k);
+int om_sim_topk_async(int mode, const float* queries, int64_t n_queries, const float* index_f32,
+                      const void* index_f16, const float* stats, int64_t N, int d, int k,
+                      int64_t id_offset, float* out_scores, int64_t* out_ids, int64_t* status,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* The fast schedule both entries run (csrc/search_plan.h search_schedule: no launch, no HIP call): behind the dense bootstrap of the
+ * first 4096 rows, *n filtered rounds; chunks[i], i < min(*n, cap), is the number of rows of round i, the first of which starts at row
+ * 4096.  N <= 4096 has no rounds.  mode: OM_SEARCH_*; under the calling thread's switches (OM_OPT_SCAN_GROWTH). */
+int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* chunks, int cap, int* n);
 
 /* Diagnostics of the calling thread's last om_sim_topk: out[0] = scan precision that produced
  * the result (0 f32, 1 f16+rescore), [1] = scan rounds, [2] = overflow fallbacks (chunks redone

@@ -33,6 +33,13 @@
 #define LIST_MAX (SORT_CAP - DENSE_CHUNK)
 #define K_MAX 2048
 #define SORT_THREADS 512
+static_assert(SORT_CAP == SEARCH_SORT_CAP && DENSE_CHUNK == SEARCH_DENSE_CHUNK, "search_plan.h schedules for these list and bootstrap sizes");
+
+// Per-query sticky status of the asynchronous entry (`qstat`, nullptr on om_sim_topk's path): a query with any bit set is recomputed by the
+// on-device redo.  The global flags (flag[0] overflow, flag[1] longest list, flag[2] margin too wide) stay as they are.
+#define QSTAT_OVERFLOW 1u    // the list exceeded SORT_CAP in some round: appends were dropped
+#define QSTAT_WIDE 2u        // a certified list outgrew LIST_MAX (or the certified margin is not finite)
+#define QSTAT_COVER 4u       // the final list is longer than the re-score cover
 
 typedef unsigned long long u64;
 static thread_local int64_t g_info[8];   // last om_sim_topk call: see om_sim_topk_info()
@@ -1138,11 +1145,17 @@ __global__ void append_dense_kernel(const float* __restrict__ S, int64_t ldS, in
   if (threadIdx.x == 0) cnt[q] = base + n;
 }
 
-// flag[0] |= any list overflowed
+// flag[0] |= any list overflowed; with qstat also the per-query bits: overflow, and a list longer than the `cover` slots a re-score reaches
 __global__ void check_overflow_kernel(const unsigned* __restrict__ cnt, int64_t nq,
-                                      unsigned* __restrict__ flag) {
+                                      unsigned* __restrict__ flag, unsigned* __restrict__ qstat, unsigned cover) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < nq && cnt[q] > SORT_CAP) atomicOr(flag, 1u);
+  if (q >= nq) return;
+  const unsigned n = cnt[q];
+  if (n > SORT_CAP) atomicOr(flag, 1u);
+  if (qstat) {
+    const unsigned bits = (n > SORT_CAP ? QSTAT_OVERFLOW : 0u) | (n > cover ? QSTAT_COVER : 0u);
+    if (bits) atomicOr(qstat + q, bits);
+  }
 }
 __global__ void restore_cnt_kernel(unsigned* __restrict__ cnt, const unsigned* __restrict__ prev,
                                    int64_t nq) {
@@ -1172,13 +1185,17 @@ __device__ inline void bitonic_sort_desc(u64* s, int P, int tid, int nthr) {
 // flag[2] |= a certified list outgrew LIST_MAX.
 __global__ __launch_bounds__(SORT_THREADS) void select_kernel(
     u64* __restrict__ keys, unsigned* __restrict__ cnt, unsigned* __restrict__ cnt_prev,
-    float* __restrict__ thr, const float* __restrict__ margin, int k, unsigned* __restrict__ flag) {
+    float* __restrict__ thr, const float* __restrict__ margin, int k, unsigned* __restrict__ flag,
+    unsigned* __restrict__ qstat) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   u64* s = (u64*)smem;
   const int64_t q = blockIdx.x;
   const int tid = threadIdx.x;
   unsigned n = cnt[q];
-  if (n > SORT_CAP) n = SORT_CAP;
+  if (n > SORT_CAP) {
+    n = SORT_CAP;
+    if (qstat && tid == 0) atomicOr(qstat + q, QSTAT_OVERFLOW);
+  }
   int P = 2;
   while (P < (int)n) P <<= 1;
   u64* list = keys + q * SORT_CAP;
@@ -1213,6 +1230,7 @@ __global__ __launch_bounds__(SORT_THREADS) void select_kernel(
     thr[q] = th;
     atomicMax(flag + 1, keep);
     if (keep > LIST_MAX) atomicOr(flag + 2, 1u);
+    if (qstat && margin && (keep > LIST_MAX || !(margin[q] < INFINITY))) atomicOr(qstat + q, QSTAT_WIDE);
   }
 }
 
@@ -1223,7 +1241,7 @@ __global__ __launch_bounds__(SORT_THREADS) void select_kernel(
 // than the 8192-key bitonic sort it replaces between rounds (profiles/r01_bench_v8_kernel_stats.csv: 8 x 2.3 ms).
 __global__ __launch_bounds__(256) void select_radix_kernel(
     u64* __restrict__ keys, unsigned* __restrict__ cnt, float* __restrict__ thr, const float* __restrict__ margin,
-    int k, unsigned* __restrict__ flag, int cap) {
+    int k, unsigned* __restrict__ flag, int cap, unsigned* __restrict__ qstat) {
   // cap: keys the LDS copy holds (SORT_CAP, or less when the host expects short lists: 64 KiB of LDS per workgroup
   // leaves two workgroups per CU, 32 KiB four -- this kernel is a chain of barriers and wants the occupancy)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1234,9 +1252,14 @@ __global__ __launch_bounds__(256) void select_radix_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   unsigned n = cnt[q];
   if (n > SORT_CAP) {                                        // appends beyond the capacity were dropped: the round is void
-    if (tid == 0) atomicOr(flag, 1u);                        // (sticky; the step-by-step loop uses check_overflow_kernel)
+    if (tid == 0) {
+      atomicOr(flag, 1u);                                    // (sticky; the step-by-step loop uses check_overflow_kernel)
+      if (qstat) atomicOr(qstat + q, QSTAT_OVERFLOW);
+    }
     n = SORT_CAP;
   }
+  // (a margin that is not finite -- a value of the index beyond f16 -- certifies nothing: inf - inf is a NaN cut that keeps no key)
+  if (qstat && margin && tid == 0 && !(margin[q] < INFINITY)) atomicOr(qstat + q, QSTAT_WIDE);
   u64* list = keys + q * SORT_CAP;
   // a list longer than the LDS copy (rare: the host sizes `cap` with a 2x margin) is read from global memory in every
   // pass (64 KiB, L2-resident) and only the survivors are staged
@@ -1315,7 +1338,10 @@ __global__ __launch_bounds__(256) void select_radix_kernel(
     __syncthreads();
     unsigned kept = misc[2];                                  // one value for the whole workgroup (no writer until the barrier below)
     if (kept > (unsigned)cap) {                               // masses of ties (duplicated rows): treated as an overflow
-      if (tid == 0) atomicOr(flag, 1u);
+      if (tid == 0) {
+        atomicOr(flag, 1u);
+        if (qstat) atomicOr(qstat + q, QSTAT_OVERFLOW);
+      }
       kept = (unsigned)cap;
     }
     for (unsigned i = tid; i < kept; i += 256) list[i] = s[i];
@@ -1327,7 +1353,10 @@ __global__ __launch_bounds__(256) void select_radix_kernel(
     cnt[q] = keep;
     thr[q] = cut;
     atomicMax(flag + 1, keep);
-    if (margin && keep > LIST_MAX) atomicOr(flag + 2, 1u);
+    if (margin && keep > LIST_MAX) {
+      atomicOr(flag + 2, 1u);
+      if (qstat) atomicOr(qstat + q, QSTAT_WIDE);
+    }
   }
 }
 
@@ -1367,6 +1396,19 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
   }
 }
 
+// The exact f32 score of the re-score and of the on-device redo: each lane's fmaf chain over columns c = lane * 4, step 256, then the
+// butterfly sum -- every lane returns the same value, and the same (query, row) gives the same bits wherever it is computed.
+__device__ __forceinline__ float rescore_dot(const float* __restrict__ qv, const float* __restrict__ pv, int d, int lane) {
+  float acc = 0.f;
+  for (int c = lane * 4; c < d; c += 256) {
+    const float4 a = *(const float4*)(qv + c);
+    const float4 b = *(const float4*)(pv + c);
+    acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc);
+    acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
+  }
+  return wave_sum(acc);
+}
+
 // exact f32 re-score of every surviving candidate: one wavefront per (query, slot)
 __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ q,
                                                       const float* __restrict__ index,
@@ -1378,17 +1420,29 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
   if (slot >= (int)cnt[qi]) return;
   u64* kp = keys + qi * SORT_CAP + slot;
   const uint32_t row = key_payload(*kp);
-  const float* qv = q + qi * d;
-  const float* pv = index + (int64_t)row * d;
-  float acc = 0.f;
-  for (int c = lane * 4; c < d; c += 256) {
-    const float4 a = *(const float4*)(qv + c);
-    const float4 b = *(const float4*)(pv + c);
-    acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc);
-    acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
-  }
-  acc = wave_sum(acc);
+  const float acc = rescore_dot(q + qi * d, index + (int64_t)row * d, d, lane);
   if (lane == 0) *kp = pack_key(acc, row);
+}
+
+// The same re-score on a FIXED grid (the asynchronous entry above 128 queries: the host does not know the list lengths, and a grid of
+// nq x cover workgroups sized for the longest list the estimate allows would launch millions of empty ones).  Work item (query, j) is
+// the slots j, j + RESCORE_SPLIT, ... < cnt[query]; the grid's wavefronts stride over the items.
+#define RESCORE_SPLIT 32
+__global__ __launch_bounds__(256) void rescore_strided_kernel(const float* __restrict__ q, const float* __restrict__ index,
+                                                              u64* __restrict__ keys, const unsigned* __restrict__ cnt, int64_t nq, int d) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  for (int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); item < nq * RESCORE_SPLIT; item += nwaves) {
+    const int64_t qi = item / RESCORE_SPLIT;
+    unsigned n = cnt[qi];
+    if (n > SORT_CAP) n = SORT_CAP;
+    for (unsigned slot = (unsigned)(item % RESCORE_SPLIT); slot < n; slot += RESCORE_SPLIT) {
+      u64* kp = keys + qi * SORT_CAP + slot;
+      const uint32_t row = key_payload(*kp);
+      const float acc = rescore_dot(q + qi * d, index + (int64_t)row * d, d, lane);
+      if (lane == 0) *kp = pack_key(acc, row);
+    }
+  }
 }
 
 __global__ void emit_kernel(const u64* __restrict__ keys, const unsigned* __restrict__ cnt, int k,
@@ -1413,6 +1467,150 @@ __global__ void init_lists_kernel(unsigned* cnt, unsigned* cnt_prev, float* thr,
   if (q < 16) flag[q] = 0;                                            // the 64-byte flag block (one launch less than a memset)
   if (q < nq) { cnt[q] = 0; cnt_prev[q] = 0; thr[q] = -INFINITY; }
   else if (q < (nq + 255) / 256 * 256 + 256) thr[q] = INFINITY;       // queries that do not exist never have survivors
+}
+
+// ---- on-device redo of the asynchronous entry ----------------------------------------------------------------------------------------
+// The exact top-k of every query whose qstat is not zero, without a word to the host: an MSB-first radix select over the 64-bit keys
+// pack_key(score, row) of ALL rows.  Ordering by that key is score descending, then row ascending, and no two keys tie -- so the k-th
+// key T is unique, exactly min(k, N) keys are >= T whatever ties the scores have, and the number of tied groups does not matter.
+// The host enqueues a FIXED chain (it does not know n_bad): compact -> begin -> REDO_PASSES x (histogram pass over the index -> pick)
+// -> collect pass.  Every kernel reads n_bad first and returns at once when it is 0: with nothing to redo the chain is 15 empty launches.
+// No device-wide barrier, no spin on a flag, no cooperative launch: the stream orders the passes.
+//   pass      one launch on a fixed grid streams the f32 index once for ALL bad queries: a workgroup stages a tile of rows in LDS, then
+//             loops over the bad queries (their vectors come from L2); a wavefront scores one (row, query) at a time with rescore_dot --
+//             the same bits in every pass -- and counts the current digit of the keys whose higher digits equal the query's prefix;
+//   pick      one workgroup: per bad query the digit that holds the remaining rank (suffix sums over the histogram, highest digit
+//             first), the rank left inside it, and the histogram zeroed for the next pass;
+//   collect   after the last pick the prefix IS T: one more pass writes every key >= T into the query's list from slot 0 and leaves
+//             cnt = min(k, N).  The final select_kernel sorts the list like any other.
+// Digits of 11 bits (the last one 9): six histogram passes and one collect pass over the index, 8 KiB of histogram per bad query.
+#define REDO_BINS 2048
+#define REDO_PASSES 6
+#define REDO_TILE_BYTES 32768
+#define REDO_RS_BAD 0         // rs[0]: queries to redo;  rs[1]: of those, with QSTAT_WIDE
+#define REDO_RS_WIDE 1
+__host__ __device__ inline int redo_shift(int pass) { return pass < 5 ? 53 - 11 * pass : 0; }      // 53, 42, 31, 20, 9, 0
+__host__ __device__ inline int redo_width(int pass) { return pass < 5 ? 11 : 9; }
+
+__global__ void async_init_kernel(unsigned* __restrict__ qstat, unsigned* __restrict__ rs, int64_t* __restrict__ status, int64_t nq) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < nq) qstat[q] = 0;
+  if (q < 16) rs[q] = 0;
+  if (q < 8) status[q] = 0;                      // status[6] turns 1 when the chain has finished
+}
+
+__global__ void redo_compact_kernel(const unsigned* __restrict__ qstat, int64_t nq, unsigned* __restrict__ rs, unsigned* __restrict__ bad) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const unsigned st = qstat[q];
+  if (!st) return;
+  bad[atomicAdd(rs + REDO_RS_BAD, 1u)] = (unsigned)q;
+  if (st & QSTAT_WIDE) atomicAdd(rs + REDO_RS_WIDE, 1u);
+}
+
+__global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restrict__ rs, u64* __restrict__ prefix, unsigned* __restrict__ remaining,
+                                                         unsigned* __restrict__ hist, unsigned want) {
+  const unsigned n_bad = rs[REDO_RS_BAD];
+  if (!n_bad) return;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = i0; i < (int64_t)n_bad * REDO_BINS; i += step) hist[i] = 0;
+  for (int64_t b = i0; b < n_bad; b += step) { prefix[b] = 0; remaining[b] = want; }
+}
+
+// COLLECT = false: hist[b][digit at `shift`] += 1 for every row whose key agrees with prefix[b] above the digit;
+// COLLECT = true: every key >= prefix[b] (= T) appended to list bad[b].  Rows [0, N) of `index`, tiles of R rows (R * d * 4 bytes of LDS).
+template <bool COLLECT>
+__global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict__ q32, const float* __restrict__ index, int64_t N, int d, int R,
+                                                        const unsigned* __restrict__ rs, const unsigned* __restrict__ bad,
+                                                        const u64* __restrict__ prefix, unsigned* __restrict__ hist, int shift, int width,
+                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt) {
+  const unsigned n_bad = rs[REDO_RS_BAD];
+  if (!n_bad) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* tile = (float*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t ntiles = (N + R - 1) / R;
+  const int hi = shift + width;                   // bits [hi, 64) are decided
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t r0 = t * R;
+    const int nr = (int)(N - r0 < R ? N - r0 : R);
+    __syncthreads();                              // the tile before has been read
+    const float4* src = (const float4*)(index + r0 * d);
+    for (int i = tid; i < nr * (d / 4); i += 256) ((float4*)tile)[i] = src[i];
+    __syncthreads();
+    for (unsigned b = 0; b < n_bad; ++b) {
+      const unsigned q = bad[b];
+      const float* qv = q32 + (int64_t)q * d;
+      const u64 P = prefix[b];
+      for (int r = wave; r < nr; r += 4) {
+        const float sc = rescore_dot(qv, tile + (int64_t)r * d, d, lane);
+        if (lane != 0) continue;
+        const u64 key = pack_key(sc, (uint32_t)(r0 + r));
+        if (COLLECT) {
+          if (key >= P) {
+            const unsigned pos = atomicAdd(cnt + q, 1u);
+            if (pos < SORT_CAP) keys[(int64_t)q * SORT_CAP + pos] = key;
+          }
+        } else if (hi >= 64 || (key >> hi) == (P >> hi)) {
+          atomicAdd(hist + (int64_t)b * REDO_BINS + (unsigned)((key >> shift) & ((1u << width) - 1u)), 1u);
+        }
+      }
+    }
+  }
+}
+
+// one workgroup, bad query after bad query: thread t owns bins [8 t, 8 t + 8)
+__global__ __launch_bounds__(256) void redo_pick_kernel(const unsigned* __restrict__ rs, const unsigned* __restrict__ bad, u64* __restrict__ prefix,
+                                                        unsigned* __restrict__ remaining, unsigned* __restrict__ hist, int shift,
+                                                        unsigned* __restrict__ cnt, int last) {
+  const unsigned n_bad = rs[REDO_RS_BAD];
+  if (!n_bad) return;
+  __shared__ unsigned wtot[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (unsigned b = 0; b < n_bad; ++b) {
+    unsigned* h = hist + (int64_t)b * REDO_BINS + tid * 8;
+    unsigned c[8], own = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { c[i] = h[i]; h[i] = 0; own += c[i]; }
+    unsigned suf = own;                           // own bins and those of the higher lanes of this wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned up = __shfl_down(suf, o, 64);
+      if (lane + o < 64) suf += up;
+    }
+    if (lane == 0) wtot[wave] = suf;
+    const unsigned rem = remaining[b];
+    __syncthreads();
+    unsigned above = suf - own;                   // keys in bins above this thread's
+    for (int w = wave + 1; w < 4; ++w) above += wtot[w];
+    if (above < rem && above + own >= rem) {      // the digit is one of this thread's: exactly one thread gets here
+      unsigned acc = above;
+      int digit = 0;
+#pragma unroll
+      for (int i = 7; i >= 0; --i) {
+        if (acc < rem && acc + c[i] >= rem) { digit = i; remaining[b] = rem - acc; }
+        acc += c[i];
+      }
+      prefix[b] |= (u64)(unsigned)(tid * 8 + digit) << shift;
+      if (last) cnt[bad[b]] = 0;                  // the collect pass fills the list from slot 0
+    }
+    __syncthreads();
+  }
+}
+
+// the last kernel of the chain: status[6] = 1 is written behind everything else
+__global__ void async_status_kernel(const unsigned* __restrict__ flag, const unsigned* __restrict__ rs, int64_t* __restrict__ status, int scan,
+                                    int rounds, int family) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  status[0] = scan;
+  status[1] = rounds;
+  status[2] = rs[REDO_RS_BAD];
+  status[3] = flag[1];
+  status[4] = rs[REDO_RS_WIDE];
+  status[5] = family;
+  status[7] = 0;
+  __threadfence();
+  *(volatile int64_t*)(status + 6) = 1;
 }
 
 // ---- K14: merge W sorted partial lists per query ------------------------------------------
@@ -1492,6 +1690,25 @@ static SearchWs carve_search(int64_t nq, int d, char* base) {
   return w;
 }
 
+// what the asynchronous entry needs behind om_sim_topk's own workspace
+struct AsyncWs {
+  unsigned *qstat, *rs, *bad, *remaining, *hist; u64* prefix;
+  size_t total;
+};
+static AsyncWs carve_async(int64_t nq, int d, char* base) {
+  size_t off = carve_search(nq, d, nullptr).total;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
+  AsyncWs w;
+  w.qstat = (unsigned*)take((size_t)nq * 4);
+  w.rs = (unsigned*)take(64);
+  w.bad = (unsigned*)take((size_t)nq * 4);
+  w.remaining = (unsigned*)take((size_t)nq * 4);
+  w.prefix = (u64*)take((size_t)nq * 8);
+  w.hist = (unsigned*)take((size_t)nq * REDO_BINS * 4);
+  w.total = off;
+  return w;
+}
+
 extern "C" void om_sim_topk_info(int64_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = g_info[i];
 }
@@ -1507,6 +1724,19 @@ extern "C" size_t om_sim_topk_workspace_bytes(int64_t n_queries, int d, int k) {
   (void)k;
   if (n_queries <= 0 || d <= 0) return 0;
   return carve_search(n_queries, d, nullptr).total;
+}
+
+extern "C" size_t om_sim_topk_async_workspace_bytes(int64_t n_queries, int d, int k) {
+  (void)k;
+  if (n_queries <= 0 || d <= 0) return 0;
+  return carve_async(n_queries, d, nullptr).total;
+}
+
+extern "C" int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* chunks, int cap, int* n) {
+  if (!n || (cap > 0 && !chunks)) OM_FAIL("null argument");
+  if (nq < 1 || N < 0 || k < 1 || k > K_MAX) OM_FAIL("nq >= 1, N >= 0 and k in [1,2048]");
+  *n = search_schedule(mode == OM_SEARCH_F16_RESCORE, nq, N, k, scan_switches(), chunks, cap < 0 ? 0 : cap).n;
+  return 0;
 }
 
 // The stream instantiation a plan names, over whole 128-row tiles on `grid` workgroups (Scan::filter_step and om_debug_sim_stream)
@@ -1550,17 +1780,18 @@ namespace {
 struct Scan {
   int mode; const float* q32; const float* idx32; const f16_t* idx16; int64_t nq, N; int d, k;
   SearchWs ws; hipStream_t s;
+  unsigned* qstat = nullptr;      // per-query sticky status: the asynchronous entry only
 
-  int select(bool certified) {
+  int select(bool certified, bool mark = true) {
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s,
                        ws.keys, ws.cnt, ws.cnt_prev, ws.thr, certified ? ws.margin : nullptr, k,
-                       ws.flag);
+                       ws.flag, mark ? qstat : nullptr);
     OM_LAUNCH_CHECK();
     return 0;
   }
   int select_radix(bool certified, int cap = SORT_CAP) {
     hipLaunchKernelGGL(select_radix_kernel, dim3((unsigned)nq), dim3(256), (size_t)cap * 8 + 1024 + 64, s,
-                       ws.keys, ws.cnt, ws.thr, certified ? ws.margin : nullptr, k, ws.flag, cap);
+                       ws.keys, ws.cnt, ws.thr, certified ? ws.margin : nullptr, k, ws.flag, cap, qstat);
     OM_LAUNCH_CHECK();
     return 0;
   }
@@ -1652,7 +1883,7 @@ struct Scan {
     OM_LAUNCH_CHECK();
     if (!check) return 0;
     hipLaunchKernelGGL(check_overflow_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s,
-                       ws.cnt, nq, ws.flag);
+                       ws.cnt, nq, ws.flag, (unsigned*)nullptr, 0u);
     OM_LAUNCH_CHECK();
     return 0;
   }
@@ -1688,27 +1919,18 @@ struct Scan {
       if (dense_gemm_append(0, DENSE_CHUNK, bf16)) return 1;
       if (select_radix(bf16, DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
       g_info[1]++;
-      const int64_t list = bf16 ? (int64_t)k * 13 / 10 + 64 : (int64_t)k + 16;       // estimate (certified: + the margin's ties)
-      // few queries: the scan is one HBM pass whatever the thresholds, the per-round launches are what costs -- few, long
-      // rounds; many queries: an append costs the scan a slow path, the selection ~0.3 ms -- many short rounds with
-      // tight thresholds (profiles/r02_scan_trace_*.log).  Expected survivors of a chunk ~ list * chunk / at.
-      // (33-128 queries, one index pass per round set on the register-resident stream kernel: 100 % measured best of 60 / 100 / 200)
-      const double growth = nq <= 32 ? 400.0 : (nq <= 128 && !om_option_is_set(OM_OPT_SCAN_GROWTH) ? 100.0 : (double)std::max(5, om_option(OM_OPT_SCAN_GROWTH)));
-      const double room = 0.75 * (double)(SORT_CAP - list);
-      const double want = std::min(room, (double)list * growth / 100.0);
-      // selection launches of the rounds: lists are ~list + want keys long; when twice that margin fits 4096 keys the
-      // LDS copy is sized for 4096 (four workgroups per CU instead of two); a longer list is read from global memory
-      const int sel_cap = (double)list + 2.0 * want + 256.0 < 4096.0 ? 4096 : SORT_CAP;
+      // the list estimate, the growth per round, the selection's LDS copy and the chunks: search_plan.h search_schedule, shared with
+      // the asynchronous entry
+      int64_t chunks[SEARCH_SCHED_MAX];
+      const SearchSchedule sched = search_schedule(bf16, nq, N, k, scan_switches(), chunks, SEARCH_SCHED_MAX);
+      if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
+      const int64_t list = sched.list;
       int64_t at = DENSE_CHUNK;
-      while (at < N) {
-        int64_t chunk = (int64_t)((double)at * want / (double)list);
-        chunk = std::max<int64_t>(chunk, DENSE_CHUNK) & ~(int64_t)255;      // whole tiles (DENSE_CHUNK is one)
-        chunk = std::min<int64_t>(chunk, N - at);
-        if (N - at - chunk < chunk / 4) chunk = N - at;           // no sliver of a last round
-        if (filter_step(at, chunk, bf16, false)) return 1;
-        if (select_radix(bf16, sel_cap)) return 1;
+      for (int i = 0; i < sched.n; ++i) {
+        if (filter_step(at, chunks[i], bf16, false)) return 1;
+        if (select_radix(bf16, sched.sel_cap)) return 1;
         g_info[1]++;
-        at += chunk;
+        at += chunks[i];
       }
       // Few queries: the exact re-score and the final sort are queued BEHIND the last round before the flags are read, so
       // the host's wake-up overlaps them instead of idling the device (a 34 us hole per search at one query).  They
@@ -1790,28 +2012,85 @@ struct Scan {
     return 0;
   }
   const float* stats;
+
+  // The asynchronous chain (om_sim_topk_async): the fast schedule above with every decision the host used to take from the flags moved
+  // to the device.  Enqueues only: no synchronisation, no copy to the host, no allocation.  Order: init -> query prep -> dense bootstrap
+  // -> rounds -> re-score -> redo of every query with a sticky bit -> ONE final sort of all lists -> emit -> status.
+  int run_async(bool bf16, const AsyncWs& aw, int64_t id_offset, float* out_scores, int64_t* out_ids, int64_t* status) {
+    const unsigned qblocks = (unsigned)((nq + 255) / 256);
+    hipLaunchKernelGGL(init_lists_kernel, dim3(qblocks + 2), dim3(256), 0, s, ws.cnt, ws.cnt_prev, ws.thr, nq, ws.flag);
+    hipLaunchKernelGGL(async_init_kernel, dim3(qblocks), dim3(256), 0, s, aw.qstat, aw.rs, status, nq);
+    OM_LAUNCH_CHECK();
+    int rounds = 0, family = 0;
+    if (N > 0) {
+      if (bf16) {
+        hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
+                           ws.qb, ws.margin, stats, nq, d);
+        OM_LAUNCH_CHECK();
+      }
+      int64_t list = bf16 ? (int64_t)k * 13 / 10 + 64 : (int64_t)k + 16;
+      if (N <= DENSE_CHUNK) {                      // one dense step, no rounds (what om_sim_topk does for a shard this small)
+        if (dense_step(0, (int)N, bf16)) return 1;
+        rounds = 1;
+      } else {
+        if (dense_gemm_append(0, DENSE_CHUNK, bf16)) return 1;
+        if (select_radix(bf16, DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
+        int64_t chunks[SEARCH_SCHED_MAX];
+        const SearchSchedule sched = search_schedule(bf16, nq, N, k, scan_switches(), chunks, SEARCH_SCHED_MAX);
+        if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
+        list = sched.list;
+        int64_t at = DENSE_CHUNK;
+        for (int i = 0; i < sched.n; ++i) {
+          if (filter_step(at, chunks[i], bf16, false)) return 1;
+          if (select_radix(bf16, sched.sel_cap)) return 1;
+          at += chunks[i];
+        }
+        rounds = 1 + sched.n;
+        family = (int)g_info[5];
+      }
+      if (bf16) {
+        // exact f32 re-score of the certified candidates.  Up to 128 queries: om_sim_topk's own launch, covering lists up to twice the
+        // estimate -- a longer list is marked (QSTAT_COVER) and redone; above: the fixed grid, which reaches every slot below cnt.
+        // A marked query's list is still well-formed here: cnt <= SORT_CAP after a selection, and every key below cnt names a row.
+        if (nq <= 128) {
+          const unsigned cover = (unsigned)std::min<int64_t>(2 * list, SORT_CAP);
+          hipLaunchKernelGGL(check_overflow_kernel, dim3(qblocks), dim3(256), 0, s, ws.cnt, nq, ws.flag, qstat, cover);
+          OM_LAUNCH_CHECK();
+          if (rescore(cover)) return 1;
+        } else {
+          hipLaunchKernelGGL(rescore_strided_kernel, dim3((unsigned)(g7_num_cus() * 8)), dim3(256), 0, s, q32, idx32, ws.keys, ws.cnt, nq, d);
+          OM_LAUNCH_CHECK();
+        }
+      }
+      // redo: a fixed chain, empty launches when no query is marked
+      hipLaunchKernelGGL(redo_compact_kernel, dim3(qblocks), dim3(256), 0, s, qstat, nq, aw.rs, aw.bad);
+      hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.prefix, aw.remaining, aw.hist, (unsigned)std::min<int64_t>(k, N));
+      OM_LAUNCH_CHECK();
+      const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
+      const size_t lds = (size_t)R * d * 4;
+      const dim3 pgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + R - 1) / R, (int64_t)g7_num_cus() * 4)));
+      for (int p = 0; p < REDO_PASSES; ++p) {
+        hipLaunchKernelGGL(redo_pass_kernel<false>, pgrid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
+                           redo_shift(p), redo_width(p), ws.keys, ws.cnt);
+        hipLaunchKernelGGL(redo_pick_kernel, dim3(1), dim3(256), 0, s, aw.rs, aw.bad, aw.prefix, aw.remaining, aw.hist, redo_shift(p), ws.cnt,
+                           p == REDO_PASSES - 1 ? 1 : 0);
+        OM_LAUNCH_CHECK();
+      }
+      hipLaunchKernelGGL(redo_pass_kernel<true>, pgrid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys,
+                         ws.cnt);
+      OM_LAUNCH_CHECK();
+      if (select(false, false)) return 1;          // best k of every list, in order
+    }
+    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, out_scores, out_ids);
+    hipLaunchKernelGGL(async_status_kernel, dim3(1), dim3(64), 0, s, ws.flag, aw.rs, status, bf16 ? 1 : 0, rounds, family);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
 };
 }  // namespace
 
-extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
-                           const float* index_f32, const void* index_f16, const float* stats,
-                           int64_t N, int d, int k, int64_t id_offset, float* out_scores,
-                           int64_t* out_ids, void* workspace, size_t workspace_bytes,
-                           void* stream) {
-  if (n_queries <= 0) return 0;
-  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1,2048]");
-  if (N < 0 || N > 0xffffffffLL) OM_FAIL("shard rows must fit in 32 bits");
-  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) OM_FAIL("d must be a multiple of 64 (pad with zeros)");
-  if (n_queries > 65535) OM_FAIL("at most 65535 queries per call");
-  if (!queries || !out_scores || !out_ids) OM_FAIL("null argument");
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  Scan sc;
-  sc.ws = carve_search(n_queries, d, (char*)workspace);
-  if (sc.ws.total > workspace_bytes) OM_FAIL("workspace too small");
-  sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
-  sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = s; sc.stats = stats;
-
+// dynamic-LDS attributes of every kernel a search launches: host calls, made once (a capturing stream must not meet them)
+static int search_attrs() {
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     OM_HIP(hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1835,6 +2114,29 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
                                SORT_CAP * 8 + 1024 + 64));
     attr_set = true;
   }
+  return 0;
+}
+
+extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
+                           const float* index_f32, const void* index_f16, const float* stats,
+                           int64_t N, int d, int k, int64_t id_offset, float* out_scores,
+                           int64_t* out_ids, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (n_queries <= 0) return 0;
+  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1,2048]");
+  if (N < 0 || N > 0xffffffffLL) OM_FAIL("shard rows must fit in 32 bits");
+  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) OM_FAIL("d must be a multiple of 64 (pad with zeros)");
+  if (n_queries > 65535) OM_FAIL("at most 65535 queries per call");
+  if (!queries || !out_scores || !out_ids) OM_FAIL("null argument");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  Scan sc;
+  sc.ws = carve_search(n_queries, d, (char*)workspace);
+  if (sc.ws.total > workspace_bytes) OM_FAIL("workspace too small");
+  sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
+  sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = s; sc.stats = stats;
+
+  if (search_attrs()) return 1;
   for (auto& v : g_info) v = 0;
   if (N > 0) {
     if (!index_f32) OM_FAIL("index_f32 is null");
@@ -1859,6 +2161,44 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
                      id_offset, out_scores, out_ids);
   OM_LAUNCH_CHECK();
   return 0;
+}
+
+// The asynchronous search: om_sim_topk's arguments, checks and output; everything on `stream`, nothing read back.
+extern "C" int om_sim_topk_async(int mode, const float* queries, int64_t n_queries,
+                                 const float* index_f32, const void* index_f16, const float* stats,
+                                 int64_t N, int d, int k, int64_t id_offset, float* out_scores,
+                                 int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  if (n_queries <= 0) return 0;
+  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1,2048]");
+  if (N < 0 || N > 0xffffffffLL) OM_FAIL("shard rows must fit in 32 bits");
+  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) OM_FAIL("d must be a multiple of 64 (pad with zeros)");
+  if (d > 16384) OM_FAIL("d above 16384: a row does not fit the redo's LDS tile (use om_sim_topk)");
+  if (n_queries > 65535) OM_FAIL("at most 65535 queries per call");
+  if (!queries || !out_scores || !out_ids) OM_FAIL("null argument");
+  if (!status) OM_FAIL("status is null: the asynchronous entry reports through 8 x int64 of device memory");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
+  if (!om_option(OM_OPT_SCAN_GEN7))
+    OM_FAIL("OM_OPT_SCAN_GEN7 is 0: the fast schedule this entry runs is switched off (use om_sim_topk)");
+  const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
+  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes)");
+  const bool bf16 = mode == OM_SEARCH_F16_RESCORE;
+  if (N > 0) {
+    if (!index_f32) OM_FAIL("index_f32 is null");
+    if (bf16 && (!index_f16 || !stats)) OM_FAIL("f16 mode needs index_f16 and stats");
+  }
+  Scan sc;
+  sc.ws = carve_search(n_queries, d, (char*)workspace);
+  sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
+  sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = (hipStream_t)stream; sc.stats = stats;
+  sc.qstat = aw.qstat;
+  if (search_attrs()) return 1;
+  int64_t keep[8];                           // om_sim_topk_info keeps describing the thread's last om_sim_topk
+  for (int i = 0; i < 8; ++i) keep[i] = g_info[i];
+  g_info[5] = 0;
+  const int rc = sc.run_async(bf16, aw, id_offset, out_scores, out_ids, status);
+  for (int i = 0; i < 8; ++i) g_info[i] = keep[i];
+  return rc;
 }
 
 extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,

@@ -8,10 +8,14 @@
 struct ScanSwitches {
   int gen7;         // OM_OPT_SCAN_GEN7: 1 the persistent kernels (generation 7 for wide batches, the register-resident stream for small
                     // ones); 0 the tile-at-a-time kernels of generations 2 and 6
+  int growth_set;   // OM_OPT_SCAN_GROWTH was given by the caller (else 33-128 queries take their own measured value)
+  int growth;       // OM_OPT_SCAN_GROWTH: rows per round of the fast schedule, in percent of the rows already scanned
 };
 
 // every switch the planner reads, read once per call
-static ScanSwitches scan_switches() { return ScanSwitches{om_option(OM_OPT_SCAN_GEN7)}; }
+static ScanSwitches scan_switches() {
+  return ScanSwitches{om_option(OM_OPT_SCAN_GEN7), om_option_is_set(OM_OPT_SCAN_GROWTH) ? 1 : 0, om_option(OM_OPT_SCAN_GROWTH)};
+}
 
 #define SCAN_KSTEP 64            // index columns per K step of the stream kernels (one 128-byte LDS row of 16-bit values)
 #define SCAN_NKMAX32_NARROW 12   // K steps compiled into the 32-query stream kernel: 256 <= d <= 768 ...
@@ -43,5 +47,47 @@ static ScanPlan scan_plan(bool half, int64_t nq, int d, const ScanSwitches sw) {
   if (nk <= SCAN_NKMAX32_WIDE) return stream(OM_SCAN_FAMILY_STREAM32, 32, SCAN_NKMAX32_WIDE);
   // 5. wider rows: a 32-query block no longer fits a wave's registers, a 16-query block does up to d = 2048 -- at most 64 queries
   if (nk <= SCAN_NKMAX16 && nq <= 64) return stream(OM_SCAN_FAMILY_STREAM16, 16, SCAN_NKMAX16);
+  return p;
+}
+
+// ---- the fast schedule's chunk arithmetic (one function for om_sim_topk and om_sim_topk_async, so the two cannot drift apart) --------
+// Bootstrap on the first SEARCH_DENSE_CHUNK rows, scored densely; then filtered rounds over chunks whose sizes are fixed on the host from
+// an ESTIMATE of the list length after a selection (it hardly moves: k plus ties / the certified margin).  Expected survivors of a chunk
+// ~ list * chunk / at.  Few queries: the scan is one HBM pass whatever the thresholds, the per-round launches are what costs -- few, long
+// rounds; many queries: an append costs the scan a slow path, the selection ~0.3 ms -- many short rounds with tight thresholds
+// (profiles/r02_scan_trace_*.log; 33-128 queries, one index pass per round set on the register-resident stream kernel: 100 % measured
+// best of 60 / 100 / 200).  Pure: no launch, no HIP call, no global read (om_debug_search_schedule returns it alone).
+#define SEARCH_SORT_CAP 8192        // keys of one candidate list (search.hip SORT_CAP)
+#define SEARCH_DENSE_CHUNK 4096     // rows of the dense bootstrap (search.hip DENSE_CHUNK)
+#define SEARCH_SCHED_MAX 1024       // rounds a schedule can have: at the smallest growth (5 %) 2^32 rows take fewer than 320
+
+struct SearchSchedule {
+  int64_t list;     // estimated list length after a selection (certified: + the margin's ties)
+  int sel_cap;      // keys the LDS copy of the rounds' selection holds: 4096 when twice the expected growth fits, else SEARCH_SORT_CAP
+  int n;            // filtered rounds; chunks[0 .. min(n, cap)) are their sizes in rows, the first starts at row SEARCH_DENSE_CHUNK
+};
+
+static SearchSchedule search_schedule(bool half, int64_t nq, int64_t N, int k, const ScanSwitches sw, int64_t* chunks, int cap) {
+  SearchSchedule p;
+  p.list = half ? (int64_t)k * 13 / 10 + 64 : (int64_t)k + 16;
+  const double growth = nq <= 32 ? 400.0 : (nq <= 128 && !sw.growth_set ? 100.0 : (double)(sw.growth > 5 ? sw.growth : 5));
+  const double room = 0.75 * (double)(SEARCH_SORT_CAP - p.list);
+  const double grow = (double)p.list * growth / 100.0;
+  const double want = room < grow ? room : grow;
+  // selection launches of the rounds: lists are ~list + want keys long; when twice that margin fits 4096 keys the
+  // LDS copy is sized for 4096 (four workgroups per CU instead of two); a longer list is read from global memory
+  p.sel_cap = (double)p.list + 2.0 * want + 256.0 < 4096.0 ? 4096 : SEARCH_SORT_CAP;
+  p.n = 0;
+  int64_t at = SEARCH_DENSE_CHUNK;
+  while (at < N) {
+    int64_t chunk = (int64_t)((double)at * want / (double)p.list);
+    if (chunk < SEARCH_DENSE_CHUNK) chunk = SEARCH_DENSE_CHUNK;
+    chunk &= ~(int64_t)255;                                   // whole tiles (SEARCH_DENSE_CHUNK is one)
+    if (chunk > N - at) chunk = N - at;
+    if (N - at - chunk < chunk / 4) chunk = N - at;           // no sliver of a last round
+    if (chunks && p.n < cap) chunks[p.n] = chunk;
+    ++p.n;
+    at += chunk;
+  }
   return p;
 }

@@ -16,6 +16,32 @@ from . import native as N
 _GROW = 1.5
 
 
+class SearchHandle:
+    """A search in flight (`FlatIPIndex.search_device_async`).  `D` [Q,k] f32 and `I` [Q,k] int64 are device tensors, valid in the order
+    of the stream the search was enqueued on; the handle keeps the workspace, the status words and the query copy of every chunk of
+    at most 32 768 queries alive."""
+
+    def __init__(self, D, I, queries, chunks, device):
+        self.D, self.I = D, I
+        self._queries, self._chunks, self._device = queries, chunks, device
+
+    def info(self):
+        """Synchronises the device, then the `last_search_info` keys (of the last chunk; `max_list` / `margin_too_wide` over all chunks)
+        plus `redone`: queries the on-device redo recomputed.  `overflow_fallbacks` is always 0: no batch is ever started over."""
+        torch.cuda.synchronize(self._device)
+        st = [s.cpu().tolist() for _buf, s in self._chunks]
+        if not st:
+            return {"scan": "f32", "rounds": 0, "overflow_fallbacks": 0, "max_list": 0, "margin_too_wide": False, "kernel": "dense",
+                    "redone": 0}
+        if any(s[6] != 1 for s in st):
+            raise N.NativeError("the search has not run (a captured search reports after its first replay)")
+        last = st[-1]
+        return {"scan": "f16+rescore" if last[0] == 1 else "f32", "rounds": int(last[1]), "overflow_fallbacks": 0,
+                "max_list": max(int(s[3]) for s in st), "margin_too_wide": any(s[4] != 0 for s in st),
+                "kernel": N.SCAN_FAMILY_NAME[int(last[5])], "redone": sum(int(s[2]) for s in st),
+                "margin_too_wide_queries": sum(int(s[4]) for s in st)}
+
+
 class FlatIPIndex:
     def __init__(self, d: int, device=None, precision: str = "f16_rescore"):
         """precision: 'f16_rescore' (f16 MFMA scan with a certified margin + exact f32 re-score;
@@ -101,6 +127,40 @@ class FlatIPIndex:
                                  "overflow_fallbacks": int(info[2]), "max_list": int(info[3]),
                                  "margin_too_wide": bool(info[4]), "kernel": N.SCAN_FAMILY_NAME[int(info[5])]}
         return D, I
+
+    def search_device_async(self, queries: torch.Tensor, k: int, id_offset: int = 0):
+        """`search_device` without the host in the loop (`om_sim_topk_async`): only enqueues on the current stream and returns a
+        `SearchHandle` whose `.D` / `.I` are valid in the order of that stream.  The handle owns its workspace, its status words and
+        its padded query copy, so several searches can be in flight (back to back, on several streams, or captured in a graph: the
+        handle then has to outlive the graph).  The index must not be added to or reset while a search is in flight."""
+        if queries.dim() != 2 or queries.shape[1] != self.d:
+            raise ValueError(f"expected [q,{self.d}] queries")
+        q = queries.to(device=self.device, dtype=torch.float32)
+        if self.dpad != self.d:            # zero-padded to the kernels' K step
+            qp = torch.zeros(q.shape[0], self.dpad, dtype=torch.float32, device=self.device)
+            qp[:, :self.d].copy_(q)
+            q = qp
+        q = q.contiguous()
+        nq = q.shape[0]
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        mode = N.SEARCH_F16_RESCORE if self.precision == "f16_rescore" else N.SEARCH_F32
+        lib = N.lib()
+        step = 32768
+        chunks = []
+        with torch.cuda.device(self.device):
+            for s in range(0, nq, step):
+                n = min(step, nq - s)
+                nbytes = lib.om_sim_topk_async_workspace_bytes(n, self.dpad, k)
+                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
+                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
+                status = torch.zeros(8, dtype=torch.int64, device=self.device)
+                N.check(lib.om_sim_topk_async(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16),
+                                              N.ptr(self._stats), self.ntotal, self.dpad, k, int(id_offset),
+                                              N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
+                                              N.stream_ptr(self.device)))
+                chunks.append((buf, status))
+        return SearchHandle(D, I, q, chunks, self.device)
 
     def search(self, x, k: int):
         """faiss-style: numpy in, (D, I) numpy out, I = insertion indices, -1 padded."""

@@ -326,6 +326,10 @@ _SIGNATURES = {
     "om_sim_topk_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "om_sim_topk": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                             c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_sim_topk_async_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "om_sim_topk_async": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                  c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_debug_search_schedule": (c_int, [c_int, c_int64, c_int64, c_int, C.POINTER(c_int64), c_int, C.POINTER(c_int)]),
     "om_sim_topk_info": (None, [C.POINTER(c_int64)]),
     "om_debug_scan_plan": (c_int, [c_int, c_int64, c_int, C.POINTER(c_int)]),
     "om_debug_sim_stream": (c_int, [c_void_p, c_int64, C.c_uint32, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
