@@ -190,14 +190,15 @@ int om_debug_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* B
                                     * two half-batch encoder forwards on two streams share the chip with 128 each */
 #define OM_OPT_GEMM_CONT 16        /* bit mask (env OM_GEMM_CONT, default 495 = bits 0-3, 5, 6, 7, 8) of the persistent 16-bit GEMM's continuous ring (the K loop of a tile
                                     * prefetches the next tile's first two steps; epilogue and accumulator initialisation of the next tile interleaved).
-                                    * bit 0: the variants without a residual; bit 1: the one-plane residual variants; bit 2: the f16 index scan of wide
-                                    * query batches; bit 3: (no effect since round 5: the continuous GEMM kernels exist on 16 x 16 x 32 MFMAs only);
+                                    * bit 0: the variants without a residual; bit 1: the one-plane residual variants; bit 2: (no effect any more: the index scan
+                                    * of wide query batches is on the continuous ring wherever it fits, csrc/search_plan.h); bit 3: (no effect since round 5: the continuous GEMM kernels exist on 16 x 16 x 32 MFMAs only);
                                     * bit 4 (A/B, off): plain whole-tile bf16 shapes prefer the continuous kernels even when they leave CUs idle;
                                     * bit 5: the training forward's FFN1 (gelu + gelu' to the tape) on the continuous kernel with a two-output
                                     * epilogue; bit 6: generation 2 priced at its measured 0.55 of a 256 x 256 tile's rate when choosing between it and the
                                     * continuous kernel for plain whole-tile 16-bit shapes; bit 7 (round 5): plain float16 contractions follow the tile-choice model as
                                     * bfloat16 does (cleared: every whole-tile float16 shape on the persistent kernel); bits 8 / 9 (round 6): the float16 / bfloat16 TWO-plane residual variants on the continuous
-                                    * ring (cleared -- bit 9 by default -- : the restart-per-tile kernel of round 3); a cleared bit 0 / 1: the ring restarts per tile as in round 3 */
+                                    * ring (cleared -- bit 9 by default -- : the restart-per-tile kernel of round 3); a cleared bit 0 / 1: the ring restarts per tile as in round 3;
+                                    * bit 10: (no effect any more: it put the wide index scan on 16 x 16 x 32 MFMAs, measured a wash -- profiles/r06_scan_16x16x32_ab.txt) */
 #define OM_OPT_TRAIN_TAPE_GRAD 17  /* 1 (default): the bf16 BERT training forward keeps gelu'(f) on its tape instead of f (env OM_TRAIN_TAPE_GRAD) */
 #define OM_OPT_TRAIN_RES32 18      /* 1 (default): the bf16 BERT training FORWARD keeps its residual stream in f32, as the reference's autocast does (layer_norm
                                     * runs and returns fp32): pre-LayerNorm sums in f32 on the tape, every LayerNorm output also unrounded for the next
@@ -995,17 +996,31 @@ int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* ch
  * the result (0 f32, 1 f16+rescore), [1] = scan rounds, [2] = overflow fallbacks (chunks redone
  * densely), [3] = longest candidate list, [4] = 1 if the certified f16 margin was too wide and
  * the call fell back to the f32 scan, [5] = OM_SCAN_FAMILY_* of the last filtered-scan round
- * (0: every row was scored densely). */
+ * (0: every row was scored densely), [6] = OM_SCAN_KERNEL_* of that round's main launch (its tail's
+ * where the round held no whole tile; 0: every row was scored densely), [7] = 0.  Written by
+ * om_sim_topk alone, on every return behind its argument checks. */
 void om_sim_topk_info(int64_t out[8]);
 
 /* Which kernel a filtered-scan round of om_sim_topk runs (csrc/search_plan.h scan_plan: no launch, no HIP call, no pointer read). */
 #define OM_SCAN_FAMILY_GENERIC 1   /* sim_filter_kernel: the 128-query tile of generation 2 (also the ragged tail behind a stream kernel)      */
-#define OM_SCAN_FAMILY_WIDE 2      /* more than 128 queries: the 256 x 256 kernels (generation 7 / 7c / 7c16 over whole tiles, generation 6)  */
+#define OM_SCAN_FAMILY_WIDE 2      /* more than 128 queries: the 256 x 256 kernels (generation 7 / 7c over whole tiles, generation 6)         */
 #define OM_SCAN_FAMILY_STREAM32 3  /* sim_stream_reg_kernel: 32-query blocks resident in registers, f16 index, 256 <= d <= 1024, <= 128 queries */
 #define OM_SCAN_FAMILY_STREAM16 4  /* sim_stream_reg_kernel<.., 32, 16>: 16-query blocks on 16 x 16 x 32 MFMAs, 1088 <= d <= 2048, <= 64 queries         */
 /* half: the 16-bit index (OM_SEARCH_F16_RESCORE) or the float32 one.  out = {family, queries per resident block (32 | 16 | 0), resident
  * blocks per workgroup (1 | 2 | 4 | 0), K steps of 64 columns compiled in (12 | 16 | 32 | 0)}, under the calling thread's switches. */
 int om_debug_scan_plan(int half, int64_t nq, int d, int out[4]);
+/* The launches of one filtered round (csrc/search_plan.h scan_round: no launch, no HIP call, no pointer read). */
+#define OM_SCAN_KERNEL_TILE2 1     /* sim_filter_kernel: 256 rows x 128 queries per workgroup, generation 2, both index formats                */
+#define OM_SCAN_KERNEL_TILE6 2     /* sim_filter_kernel6: 256 rows x 256 queries per workgroup, generation 6, both index formats               */
+#define OM_SCAN_KERNEL_WIDE7 3     /* sim_filter_kernel7: persistent over 256 x 256 tiles, the ring restarted per tile, 16-bit index           */
+#define OM_SCAN_KERNEL_WIDE7C 4    /* sim_filter_kernel7c: the same on the continuous ring (rows of at least three 128-byte K steps)           */
+#define OM_SCAN_KERNEL_STREAM 5    /* sim_stream_reg_kernel: the instantiation om_debug_scan_plan names by qblock, nb and nkmax                */
+/* The round over `rows` index rows of a search of nq queries of width d on a device of `cus` compute units: a main launch and a ragged
+ * tail, either of which may be empty (all four words 0).  out = {main kernel OM_SCAN_KERNEL_*, rows, grid, group, tail kernel, rows,
+ * grid, group}; the tail starts behind the main launch's rows; group is the kernel's last argument (tile kernels: group_m | qgroup << 8;
+ * stream kernel: 1 = non-temporal index loads).  Under the calling thread's switches (OM_OPT_SCAN_GEN7, OM_OPT_SCAN_QGROUP,
+ * OM_OPT_SEARCH_DEBUG).  Refuses a grid above 2^31 - 1 workgroups, as the search does. */
+int om_debug_scan_round(int half, int64_t nq, int d, int64_t rows, int cus, int64_t out[8]);
 /* One launch of exactly the stream instantiation om_debug_scan_plan names for (nq, d): rows16 [nrows, d] f16 with nrows a multiple of 128
  * (row r has id row_base + r), queries16 [>= nq, d] f16 as om_sim_topk's query preparation leaves them, thr[q] the score a row must
  * reach (128 floats, +inf beyond nq), keys [nq][8192] and cnt [nq] the candidate lists (cnt counts every survivor, keys holds the

@@ -568,164 +568,6 @@ __global__ __launch_bounds__(G6_THREADS) void sim_filter_kernel7c(
   G7_WAIT_VM(0);
 }
 
-// ---- the continuous-ring scan on 16 x 16 x 32 MFMAs (round 6) -------------------------------------------------------------------
-// The K loop of the encoder's kernels 7c16 / 7r16 (gemm_core7.h gemm_mainloop7_cont16: 28.3 k cycles per K = 768 tile where the
-// 32 x 32 x 16 loop above takes ~30 k) under the same filter.  Accumulator layout: acc[ti][fj][r] = score(query q0 + wm*128 + ti*16 +
-// (lane & 15), row r0 + wn*128 + fj*16 + 4*(lane >> 4) + r): a lane holds EIGHT queries' thresholds and 32 scores per query block.
-// Ring protocol of that loop: it enters with A(1) AND all of B(1) issued (the 32 x 32 loop issues the second half of B(1) itself), so
-// all eight B(1) requests go out behind the filter; its last step issues nothing (empty tail: vmcnt(0) at the last barrier) and the
-// tile starts from zero inside the loop (ZERO_FIRST).  Same staging, same survivor records, same lists as kernel 7c.
-// Measured (profiles/r06_scan_16x16x32_ab.txt): in shader cycles the tile is LONGER (K loop 29.3 k against 26.8 k, filter 6.3 k against
-// 4.7 k: eight query blocks per lane instead of four) and the clock higher (the small MFMA shape draws less); end to end +1.4 % on one
-// box, -0.8 % on another.  A wash: the 32 x 32 x 16 kernel stays the default, this one is OM_GEMM_CONT bit 10.
-// One query block (ti: 16 queries) against the wave's 128 index rows: 32 scores per lane, 11 v_max3, one compare and one branch when
-// none reaches its query's threshold; the survivor path behind it as cold code.  (Tried: ONE branch per four blocks with the survivor
-// path re-reading the accumulators -- 7.7 k cycles per tile against 6.3 k: with 3.4 survivors per wave and tile most groups of four
-// blocks hold one, and then pay the reads and the maxima twice.)
-template <int TI0, int TI1>
-__device__ __forceinline__ void sc7c16_filter(f32x4_t (&acc)[8][8], const float (&th)[8], uint32_t id0, uint32_t ql0, int lane, const Sc7cStage& st,
-                                              unsigned& wcount, int64_t q0, u64* __restrict__ keys, unsigned* __restrict__ cnt) {
-#pragma unroll
-  for (int ti = TI0; ti < TI1; ++ti) {
-    f32x4_t a[8];
-    float bm[8];
-#pragma unroll
-    for (int fj = 0; fj < 8; ++fj) {
-      asm volatile("" : "+a"(acc[ti][fj]));            // stays in its AGPRs until this point
-      a[fj] = acc[ti][fj];
-      bm[fj] = sc7c_max3(sc7c_max3(a[fj][0], a[fj][1], a[fj][2]), a[fj][3], a[fj][3]);
-    }
-    const float mx = sc7c_max3(sc7c_max3(bm[0], bm[1], bm[2]), sc7c_max3(bm[3], bm[4], bm[5]), sc7c_max3(bm[6], bm[7], bm[7]));
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx >= th[ti]) != 0, 0)) {          // wave-uniform: some lane holds a survivor
-#pragma unroll
-      for (int fj = 0; fj < 8; ++fj) {
-        if (__builtin_amdgcn_ballot_w64(bm[fj] >= th[ti]) == 0) continue;
-        if (wcount > SC7C_CAP - 256) { sc7c_flush(st, 0u, wcount, lane, q0, keys, cnt); wcount = 0; }      // a block adds at most 256
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool pass = a[fj][r] >= th[ti];
-          const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
-          if (m != 0) {
-            if (pass) {
-              const unsigned pos = wcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-              *(u64*)sc7c_key_slot(st, pos) = pack_key(a[fj][r], id0 + (uint32_t)(fj * 16 + r));
-              *sc7c_q_slot(st, pos) = (uint16_t)(ql0 + ti * 16);
-            }
-            wcount += (unsigned)__builtin_popcountll(m);
-          }
-        }
-      }
-    }
-    G7_FENCE_();
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(G6_THREADS) void sim_filter_kernel7c16(
-    const T* __restrict__ rows, int64_t nrows, uint32_t row_base, const T* __restrict__ queries,
-    int64_t nq, int64_t d, const float* __restrict__ thr, u64* __restrict__ keys,
-    unsigned* __restrict__ cnt, int group_m, unsigned long long* __restrict__ trace) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane0 = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int64_t ntr = (nrows + 255) / 256, ntq = (nq + 255) / 256;
-  const int nk = (int)((d * 2) / G7_ROW_BYTES);
-  unsigned wcount = 0;                     // records in this wave's staging area (wave-uniform)
-  unsigned pend_n = 0;                     // records of the previous tile held in registers, one per lane (wave-uniform)
-  u64 pend_key = 0; uint32_t pend_q = 0;
-  int64_t r0, q0;
-  const int qgroup = group_m >> 8;
-  group_m &= 255;
-  Sc7Walk walk;
-  if (!walk.init(ntr, ntq, group_m, qgroup, r0, q0)) return;
-  G7SrcU src;
-  g7_offsets_u<T>(src, d, d, wave, lane0);         // every row of every tile exists (padded query panel, whole row tiles)
-  G7Ring ring;
-  g7_ring_reset(ring);
-  const uint32_t lds_base = g7_lds_addr(smem);
-  const char* cur_a = (const char*)(queries + q0 * d);
-  const char* cur_b = (const char*)(rows + r0 * d);
-  g7_dma((const char*)(thr + q0 + wm * 128), lane0 * 16, lds_base + ring.sp + (7 * 4 + wave) * 1024);
-  g7_fill_a(src, cur_a, smem + ring.ac, wave);
-  g7_fill_b(src, cur_b, smem + ring.bc, wave);
-  g7_fill_a(src, cur_a + G7_ROW_BYTES, smem + ring.an, wave);
-  g7_fill_b(src, cur_b + G7_ROW_BYTES, smem + ring.bn, wave);
-  G7_WAIT_VM(16);                                  // the thresholds and K step 0 (A(1), B(1) may be outstanding)
-  __builtin_amdgcn_s_barrier();                    // first pair only: K step 0 published
-  int64_t r1 = r0, q1 = q0;
-  bool has_next = walk.next(r1, q1);
-  for (;;) {
-    unsigned long long* tr = nullptr;
-    if (trace) {
-      const int64_t tile_id = (r0 / 256) * ntq + q0 / 256;
-      if (tile_id < 8192) tr = trace + tile_id * 32;
-    }
-    if (tr && threadIdx.x == 0) { tr[0] = tr[1] = clock64(); tr[30] = wall_clock64(); }
-    float th[8];
-    f32x4_t acc[8][8];           // (starts from zero inside the K loop: ZERO_FIRST -- no initialising pass)
-    {
-      int lane_i = lane0;
-      asm volatile("" : "+v"(lane_i));
-      const char* const tab = smem + ring.sp + (7 * 4 + wave) * 1024;      // this pair's thresholds (fetched under the previous filter)
-#pragma unroll
-      for (int ti = 0; ti < 8; ++ti) th[ti] = *(const float*)(tab + (ti * 16 + (lane_i & 15)) * 4);
-    }
-    const char* const next_a = (const char*)(queries + q1 * d);      // (no next pair: this one again -- a harmless prefetch)
-    const char* const next_b = (const char*)(rows + r1 * d);
-    gemm_mainloop7_cont16<T, true, G7NoTail, true>(src, cur_a, cur_b, next_a, next_b, nk, smem, ring, acc, tr);
-    if (tr && threadIdx.x == 0) tr[15] = clock64();
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
-    const Sc7cStage st = {smem + ring.bn + wave * 1024, smem + ring.sp + wave * 1024};
-    // the previous tile's records: list positions requested now, consumed half a filter later
-    unsigned pend_pos = 0;
-    if (pend_n && (unsigned)lane < pend_n) pend_pos = atomicAdd(cnt + pend_q, 1u);
-    // under the filter: A(1) of the next pair (into the unit the filter does not use) and its thresholds
-    g7_fill_a(src, next_a + G7_ROW_BYTES, smem + ring.an, wave);
-    g7_dma((const char*)(thr + q1 + wm * 128), lane0 * 16, g7_lds_addr(st.sp) + 7 * 4096);
-    G7_FENCE_();
-    if (tr && threadIdx.x == 0) tr[16] = clock64();
-    {
-      const uint32_t id0 = row_base + (uint32_t)r0 + (uint32_t)(wn * 128 + 4 * (lane >> 4));    // row id of (fj = 0, r = 0)
-      const uint32_t ql0 = (uint32_t)(wm * 128 + (lane & 15));
-      sc7c16_filter<0, 4>(acc, th, id0, ql0, lane, st, wcount, q0, keys, cnt);
-      if (pend_n) {
-        if ((unsigned)lane < pend_n && pend_pos < SORT_CAP) keys[(int64_t)pend_q * SORT_CAP + pend_pos] = pend_key;
-        pend_n = 0;
-      }
-      G7_FENCE_();
-      if (tr && threadIdx.x == 0) tr[17] = clock64();
-      sc7c16_filter<4, 8>(acc, th, id0, ql0, lane, st, wcount, q0, keys, cnt);
-      if (tr && threadIdx.x == 0) { tr[18] = clock64(); tr[20] = wcount; }
-      if (wcount > 64) sc7c_flush(st, 64u, wcount, lane, q0, keys, cnt);
-      pend_n = wcount < 64u ? wcount : 64u;
-      if ((unsigned)lane < pend_n) {
-        pend_key = *(const u64*)sc7c_key_slot(st, (unsigned)lane);
-        pend_q = (uint32_t)q0 + *sc7c_q_slot(st, (unsigned)lane);
-      }
-      wcount = 0;
-    }
-    // A(1) and the thresholds were fetched a whole filter ago; everything issued since (the key stores of the pending records, half a
-    // filter old; a synchronous flush, rare) is older than any DMA of the next K loop.  The staging area has been read (lgkmcnt): B(1)
-    // may overwrite it -- all eight requests (the 16 x 16 x 32 loop enters with the whole unit issued).
-    if (tr && threadIdx.x == 0) tr[19] = clock64();
-    G7_WAIT_VM(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (tr && threadIdx.x == 0) tr[21] = clock64();
-    g7_fill_b(src, next_b + G7_ROW_BYTES, smem + ring.bn, wave);
-    if (tr && threadIdx.x == 0) { tr[28] = clock64(); tr[29] = blockIdx.x; tr[31] = wall_clock64(); }
-    if (!has_next) break;
-    cur_a = next_a; cur_b = next_b; r0 = r1; q0 = q1;
-    has_next = walk.next(r1, q1);
-  }
-  if (pend_n && (unsigned)lane0 < pend_n) {
-    const unsigned pos = atomicAdd(cnt + pend_q, 1u);
-    if (pos < SORT_CAP) keys[(int64_t)pend_q * SORT_CAP + pos] = pend_key;
-  }
-  G7_WAIT_VM(0);
-}
-
 // Small query batches (<= 128 queries): the scan is a pass over the whole f16 index (13.6 GB at 8.8 M x 768) that has to
 // run at HBM speed.  The generic 128-query tile spends 1.7 PFLOP of matrix-core time on padding at Q = 1 (3.99 ms per
 // search in round 1, profiles/r01_search_shapes.jsonl).  Round 2 kept one or two 32-query blocks resident in LDS beside a
@@ -757,7 +599,7 @@ __global__ __launch_bounds__(G6_THREADS) void sim_filter_kernel7c16(
 //     NB = 2 (Q <= 32)    waves 0, 2 / 1, 3 hold block 0 / 1 and take 64 rows each
 //     NB = 4 (Q <= 64)    one block per wave, every wave takes all 128 rows
 // Operand A = index rows (lane: row lane & 15, k 8 (lane >> 4) + j of the 32-wide sub-step), B = the query block (same map), so
-// acc[rt][r] = <row 16 rt + 4 (lane >> 4) + r of the wave's share, query 16 nb + (lane & 15)>: the layout sim_filter_kernel7c16 filters.
+// acc[rt][r] = <row 16 rt + 4 (lane >> 4) + r of the wave's share, query 16 nb + (lane & 15)>: the 16 x 16 x 32 MFMA's own layout.
 // Ring, DMA swizzle (row r keeps source chunk c at c ^ ((r >> 1) & 7); r & 15 = lane & 15 here), non-temporal stream, split append and
 // end-of-launch retire are those of the 32-query body; a K step is two sub-steps instead of four, and a lane has ONE list (its query) for
 // all its 8 NB scores of a tile, so one atomic per lane and tile.  Registers: the 4 RB accumulators are pinned into the accumulation half
@@ -1720,6 +1562,19 @@ extern "C" int om_debug_scan_plan(int half, int64_t nq, int d, int out[4]) {
   return 0;
 }
 
+extern "C" int om_debug_scan_round(int half, int64_t nq, int d, int64_t rows, int cus, int64_t out[8]) {
+  if (!out) OM_FAIL("null argument");
+  if (nq < 1 || d < 1 || rows < 0 || cus < 1) OM_FAIL("nq >= 1, d >= 1, rows >= 0 and cus >= 1");
+  const ScanSwitches sw = scan_switches();
+  const ScanRound r = scan_round(scan_plan(half != 0, nq, d, sw), half != 0, nq, d, rows, cus, sw);
+  if (!r.ok) OM_FAIL("scan grid too large");
+  const ScanLaunch* const part[2] = {&r.main, &r.tail};
+  for (int i = 0; i < 2; ++i) {
+    out[4 * i] = part[i]->kernel; out[4 * i + 1] = part[i]->rows; out[4 * i + 2] = part[i]->grid; out[4 * i + 3] = part[i]->group;
+  }
+  return 0;
+}
+
 extern "C" size_t om_sim_topk_workspace_bytes(int64_t n_queries, int d, int k) {
   (void)k;
   if (n_queries <= 0 || d <= 0) return 0;
@@ -1739,41 +1594,69 @@ extern "C" int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, 
   return 0;
 }
 
-// The stream instantiation a plan names, over whole 128-row tiles on `grid` workgroups (Scan::filter_step and om_debug_sim_stream)
-static int stream_attrs() {
+// ---- the scan kernels: one table for their LDS attributes and their launches ---------------------------------------------------------
+// The tile kernels by [OM_SCAN_KERNEL_*][index format: 0 float32, 1 16-bit], the stream kernel by [instantiation][nb: 1 | 2 | 4].  All
+// take (rows, nrows, row_base, queries, nq, d, thr, keys, cnt, int); generation 7 appends the trace buffer.  fn == nullptr: no such kernel.
+struct ScanKernel { const void* fn; int threads; int lds; bool trace; };
+#define SCAN_KERNEL_(FN, THREADS, LDS, TRACE) {(const void*)FN, THREADS, LDS, TRACE}
+#define SCAN_NONE_ {nullptr, 0, 0, false}
+static const ScanKernel g_tile_kernels[OM_SCAN_KERNEL_WIDE7C + 1][2] = {
+    {SCAN_NONE_, SCAN_NONE_},
+    {SCAN_KERNEL_(sim_filter_kernel<float>, G2_THREADS, G2_LDS_BYTES, false), SCAN_KERNEL_(sim_filter_kernel<f16_t>, G2_THREADS, G2_LDS_BYTES, false)},
+    {SCAN_KERNEL_(sim_filter_kernel6<float>, G6_THREADS, G6_LDS_BYTES, false), SCAN_KERNEL_(sim_filter_kernel6<f16_t>, G6_THREADS, G6_LDS_BYTES, false)},
+    {SCAN_NONE_, SCAN_KERNEL_(sim_filter_kernel7<f16_t>, G6_THREADS, G7_LDS_BYTES, true)},
+    {SCAN_NONE_, SCAN_KERNEL_(sim_filter_kernel7c<f16_t>, G6_THREADS, G7_LDS_BYTES, true)},
+};
+#define STREAM_ROW_(...)                                                                                                            \
+  {SCAN_KERNEL_((sim_stream_reg_kernel<f16_t, 1, __VA_ARGS__>), G6_THREADS, SR_LDS, false),                                          \
+   SCAN_KERNEL_((sim_stream_reg_kernel<f16_t, 2, __VA_ARGS__>), G6_THREADS, SR_LDS, false),                                          \
+   SCAN_KERNEL_((sim_stream_reg_kernel<f16_t, 4, __VA_ARGS__>), G6_THREADS, SR_LDS, false)}
+static const ScanKernel g_stream_kernels[][3] = {
+    STREAM_ROW_(0, SCAN_NKMAX32_NARROW, 32),      // 256 <= d <= 768
+    STREAM_ROW_(0, SCAN_NKMAX32_WIDE, 32),        // 832 <= d <= 1024
+    STREAM_ROW_(0, SCAN_NKMAX16, 16),             // 1088 <= d <= 2048, 16-query blocks
+#ifdef OM_PROBE_KERNELS      // timing variants with MFMAs compiled out (WRONG results): probe builds only (python -m openmatch_amd._build --probe)
+    STREAM_ROW_(1, SCAN_NKMAX32_NARROW, 32),
+    STREAM_ROW_(2, SCAN_NKMAX32_NARROW, 32),
+#endif
+};
+#undef STREAM_ROW_
+#undef SCAN_NONE_
+#undef SCAN_KERNEL_
+
+// the table row of a planned launch
+static const ScanKernel& scan_kernel(int kernel, bool half, const ScanPlan& plan, const ScanSwitches& sw) {
+  if (kernel != OM_SCAN_KERNEL_STREAM) return g_tile_kernels[kernel][half ? 1 : 0];
+  int inst = plan.family == OM_SCAN_FAMILY_STREAM16 ? 2 : plan.nkmax == SCAN_NKMAX32_WIDE ? 1 : 0;
+#ifdef OM_PROBE_KERNELS
+  if (inst == 0 && (sw.probe == 1 || sw.probe == 2)) inst = 2 + sw.probe;
+#endif
+  (void)sw;
+  return g_stream_kernels[inst][plan.nb == 1 ? 0 : plan.nb == 2 ? 1 : 2];
+}
+
+// dynamic-LDS attribute of every scan kernel: host calls, made once (a capturing stream must not meet them)
+static int scan_attrs() {
   static std::atomic<bool> done{false};
   if (done) return 0;
-#define SR_ATTR(...) OM_HIP(hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, SR_LDS))
-  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 0>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 0>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 0>);
-  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 1>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 1>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 1>);
-  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 2>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 2>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 2>);
-  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX32_WIDE>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX32_WIDE>);
-  SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX32_WIDE>);
-  SR_ATTR(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX16, 16>); SR_ATTR(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX16, 16>); SR_ATTR(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX16, 16>);
-#undef SR_ATTR
+  for (const auto& row : g_tile_kernels)
+    for (const ScanKernel& kn : row)
+      if (kn.fn) OM_HIP(hipFuncSetAttribute(kn.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kn.lds));
+  for (const auto& row : g_stream_kernels)
+    for (const ScanKernel& kn : row) OM_HIP(hipFuncSetAttribute(kn.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kn.lds));
   done = true;
   return 0;
 }
-static void stream_launch(const ScanPlan& plan, const f16_t* rows, int64_t nrows, uint32_t row_base, const f16_t* queries, int64_t nq, int d,
-                          const float* thr, u64* keys, unsigned* cnt, int grid, hipStream_t s) {
-  const int nt = (om_option(OM_OPT_SEARCH_DEBUG) & 4) ? 0 : 1;
-#define STREAM_(...) hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)grid), dim3(G6_THREADS), SR_LDS, s, rows, nrows, row_base, queries, nq, (int64_t)d, \
-                                        thr, keys, cnt, nt)
-#ifdef OM_PROBE_KERNELS      // timing variants with MFMAs compiled out (WRONG results): probe builds only (python -m openmatch_amd._build --probe)
-#define STREAM(NB_) do { const int dbg_ = (om_option(OM_OPT_SEARCH_DEBUG) >> 3) & 3; if (dbg_ == 1) STREAM_(sim_stream_reg_kernel<f16_t, NB_, 1>); else if (dbg_ == 2) STREAM_(sim_stream_reg_kernel<f16_t, NB_, 2>); else STREAM_(sim_stream_reg_kernel<f16_t, NB_, 0>); } while (0)
-#else
-#define STREAM(NB_) STREAM_(sim_stream_reg_kernel<f16_t, NB_, 0>)
-#endif
-  if (plan.family == OM_SCAN_FAMILY_STREAM16) {
-    if (plan.nb == 1) STREAM_(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX16, 16>); else if (plan.nb == 2) STREAM_(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX16, 16>); else STREAM_(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX16, 16>);
-  } else if (plan.nkmax == SCAN_NKMAX32_WIDE) {
-    if (plan.nb == 1) STREAM_(sim_stream_reg_kernel<f16_t, 1, 0, SCAN_NKMAX32_WIDE>); else if (plan.nb == 2) STREAM_(sim_stream_reg_kernel<f16_t, 2, 0, SCAN_NKMAX32_WIDE>);
-    else STREAM_(sim_stream_reg_kernel<f16_t, 4, 0, SCAN_NKMAX32_WIDE>);
-  } else {
-    if (plan.nb == 1) STREAM(1); else if (plan.nb == 2) STREAM(2); else STREAM(4);
-  }
-#undef STREAM
-#undef STREAM_
+
+// The one launcher of the scan kernels: rows [nrows, d] with ids from row_base against the queries, survivors appended to keys / cnt.
+static int scan_launch(const ScanKernel& kn, const void* rows, int64_t nrows, uint32_t row_base, const void* queries, int64_t nq, int d,
+                       const float* thr, u64* keys, unsigned* cnt, int64_t grid, int group, hipStream_t s) {
+  if (!kn.fn) OM_FAIL("the scan plan names a kernel that does not exist");
+  int64_t d64 = d;
+  unsigned long long* trace = kn.trace ? omk_debug_trace() : nullptr;
+  void* args[] = {&rows, &nrows, &row_base, &queries, &nq, &d64, &thr, &keys, &cnt, &group, &trace};      // (trace: generation 7 only)
+  OM_HIP(hipLaunchKernel(kn.fn, dim3((unsigned)grid), dim3((unsigned)kn.threads), args, (size_t)kn.lds, s));
+  return 0;
 }
 
 namespace {
@@ -1781,6 +1664,12 @@ struct Scan {
   int mode; const float* q32; const float* idx32; const f16_t* idx16; int64_t nq, N; int d, k;
   SearchWs ws; hipStream_t s;
   unsigned* qstat = nullptr;      // per-query sticky status: the asynchronous entry only
+  ScanSwitches sw;                // the thread's switches, read once by the entry
+  // diagnostics, accumulated over the 16-bit run and the float32 retry (om_sim_topk publishes them, the asynchronous entry's status
+  // kernel takes rounds and family): rounds, chunks redone densely or schedules started over, longest list seen by the host,
+  // OM_SCAN_FAMILY_* and OM_SCAN_KERNEL_* of the last filtered round (its tail's where the round had no whole tile)
+  int64_t rounds = 0, fallbacks = 0, max_list = 0;
+  int family = 0, launch = 0;
 
   int select(bool certified, bool mark = true) {
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s,
@@ -1827,58 +1716,21 @@ struct Scan {
     if (dense_gemm_append(r0, n, bf16)) return 1;
     return select(bf16);
   }
+  // one filtered round over rows [r0, r0 + n): what scan_round plans, launched from the kernel table
   int filter_step(int64_t r0, int64_t n, bool bf16, bool check = true /* false: the selection that follows flags overflows */) {
-    const ScanPlan plan = scan_plan(bf16, nq, d, scan_switches());
-    g_info[5] = plan.family;
-    const bool wide = plan.family == OM_SCAN_FAMILY_WIDE;
-    const int64_t ntm = (n + 255) / 256, ntn = wide ? (nq + G6_BM - 1) / G6_BM : (nq + G2_BN - 1) / G2_BN;
-    if (ntm * ntn > 0x7fffffffLL) OM_FAIL("scan grid too large");
+    const ScanPlan plan = scan_plan(bf16, nq, d, sw);
+    const ScanRound round = scan_round(plan, bf16, nq, d, n, g7_num_cus(), sw);
+    if (!round.ok) OM_FAIL("scan grid too large");
+    family = plan.family;
+    launch = round.main.rows ? round.main.kernel : round.tail.kernel;
+    const char* const rows = bf16 ? (const char*)idx16 : (const char*)idx32;
+    const void* const queries = bf16 ? (const void*)ws.qb : (const void*)q32;
+    const int64_t row_bytes = (int64_t)d * (bf16 ? 2 : 4);
     const bool timing = om_timing_on();
     if (timing) om_timing_begin(OM_TIMING_SCAN, s);
-    const dim3 grid((unsigned)(ntm * ntn));
-#define SCAN(KERNEL, THREADS, LDS, TT, ROWS, QUERIES)                                              \
-  hipLaunchKernelGGL((KERNEL<TT>), grid, dim3(THREADS), LDS, s, ROWS + r0 * d, n, (uint32_t)r0, QUERIES, \
-                     nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8)
-    if (bf16) {
-      if (wide && om_option(OM_OPT_SCAN_GEN7)) {
-        // generation 7 takes the whole 256-row tiles, generation 6 the ragged tail of the chunk (if any)
-        const int64_t whole = n & ~(int64_t)255;
-        if (whole) {
-          int ncu = g7_num_cus();
-          const int64_t tiles = (whole / 256) * ntn;
-          if (tiles < ncu) ncu = (int)tiles;
-          if ((d * 2) / G7_ROW_BYTES >= 3 && (om_option(OM_OPT_GEMM_CONT) & 4) && (om_option(OM_OPT_GEMM_CONT) & 1024))      // bit 10 (round 6): ... on 16 x 16 x 32 MFMAs
-            hipLaunchKernelGGL((sim_filter_kernel7c16<f16_t>), dim3((unsigned)ncu), dim3(G6_THREADS), G7_LDS_BYTES, s, idx16 + r0 * d, whole,
-                               (uint32_t)r0, ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8 | (std::max(1, om_option(OM_OPT_SCAN_QGROUP)) << 8), omk_debug_trace());
-          else if ((d * 2) / G7_ROW_BYTES >= 3 && (om_option(OM_OPT_GEMM_CONT) & 4))      // bit 2: the scan on the continuous ring
-            hipLaunchKernelGGL((sim_filter_kernel7c<f16_t>), dim3((unsigned)ncu), dim3(G6_THREADS), G7_LDS_BYTES, s, idx16 + r0 * d, whole,
-                               (uint32_t)r0, ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8 | (std::max(1, om_option(OM_OPT_SCAN_QGROUP)) << 8), omk_debug_trace());
-          else
-          hipLaunchKernelGGL((sim_filter_kernel7<f16_t>), dim3((unsigned)ncu), dim3(G6_THREADS), G7_LDS_BYTES, s, idx16 + r0 * d, whole,
-                             (uint32_t)r0, ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8 | (std::max(1, om_option(OM_OPT_SCAN_QGROUP)) << 8), omk_debug_trace());
-        }
-        if (n > whole)
-          hipLaunchKernelGGL((sim_filter_kernel6<f16_t>), dim3((unsigned)ntn), dim3(G6_THREADS), G6_LDS_BYTES, s, idx16 + (r0 + whole) * d,
-                             n - whole, (uint32_t)(r0 + whole), ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8);
-      } else if (wide) SCAN(sim_filter_kernel6, G6_THREADS, G6_LDS_BYTES, f16_t, idx16, ws.qb);
-      else if (plan.family == OM_SCAN_FAMILY_STREAM32 || plan.family == OM_SCAN_FAMILY_STREAM16) {
-        // the HBM-speed pass for small batches (queries in registers, the whole LDS a ring) over the whole 128-row tiles;
-        // the generic kernel takes the ragged tail
-        const int64_t whole = n & ~(int64_t)127;
-        if (whole) {
-          int ncu = g7_num_cus();
-          if (whole / SR_UROWS < ncu) ncu = (int)(whole / SR_UROWS);
-          stream_launch(plan, idx16 + r0 * d, whole, (uint32_t)r0, ws.qb, nq, d, ws.thr, ws.keys, ws.cnt, ncu, s);
-        }
-        if (n > whole)
-          hipLaunchKernelGGL((sim_filter_kernel<f16_t>), dim3((unsigned)((nq + G2_BN - 1) / G2_BN)), dim3(G2_THREADS), G2_LDS_BYTES, s, idx16 + (r0 + whole) * d, n - whole,
-                             (uint32_t)(r0 + whole), ws.qb, nq, (int64_t)d, ws.thr, ws.keys, ws.cnt, 8);
-      } else SCAN(sim_filter_kernel, G2_THREADS, G2_LDS_BYTES, f16_t, idx16, ws.qb);
-    } else {
-      if (wide) SCAN(sim_filter_kernel6, G6_THREADS, G6_LDS_BYTES, float, idx32, q32);
-      else SCAN(sim_filter_kernel, G2_THREADS, G2_LDS_BYTES, float, idx32, q32);
-    }
-#undef SCAN
+    for (const ScanLaunch* l : {&round.main, &round.tail})
+      if (l->rows && scan_launch(scan_kernel(l->kernel, bf16, plan, sw), rows + (r0 + l->row0) * row_bytes, l->rows, (uint32_t)(r0 + l->row0),
+                                 queries, nq, d, ws.thr, ws.keys, ws.cnt, l->grid, l->group, s)) return 1;
     if (timing) om_timing_end(OM_TIMING_SCAN, s, 2.0 * (double)n * (double)nq * (double)d);
     OM_LAUNCH_CHECK();
     if (!check) return 0;
@@ -1888,9 +1740,51 @@ struct Scan {
     return 0;
   }
 
+  // empty lists, thresholds at -inf (+inf beyond nq, a whole query tile further: the generation-7 scan reads whole tiles), flags cleared
+  int init_lists() {
+    hipLaunchKernelGGL(init_lists_kernel, dim3((unsigned)((nq + 255) / 256 + 2)), dim3(256), 0, s,
+                       ws.cnt, ws.cnt_prev, ws.thr, nq, ws.flag);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
+  // What every search starts with: the lists, the asynchronous entry's status words (aw != nullptr) and, for the 16-bit scan of a
+  // non-empty shard, the 16-bit query panel with its certified margins.
+  int begin(bool bf16, const AsyncWs* aw = nullptr, int64_t* status = nullptr) {
+    if (init_lists()) return 1;
+    if (aw) {
+      hipLaunchKernelGGL(async_init_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, aw->qstat, aw->rs, status, nq);
+      OM_LAUNCH_CHECK();
+    }
+    if (bf16 && N > 0) {
+      hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
+                         ws.qb, ws.margin, stats, nq, d);
+      OM_LAUNCH_CHECK();
+    }
+    return 0;
+  }
+  // The fast schedule's rounds, for both entries (N > DENSE_CHUNK): the dense bootstrap and its selection, then per round the filtered
+  // scan and a radix selection, which also flags overflows -- back to back, nothing read by the host.  The list estimate, the growth
+  // per round, the selection's LDS copy and the chunks are search_plan.h's search_schedule, returned in `sched`.
+  int fast_rounds(bool bf16, SearchSchedule& sched) {
+    if (dense_gemm_append(0, DENSE_CHUNK, bf16)) return 1;
+    if (select_radix(bf16, DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
+    rounds++;
+    int64_t chunks[SEARCH_SCHED_MAX];
+    sched = search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
+    if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
+    int64_t at = DENSE_CHUNK;
+    for (int i = 0; i < sched.n; ++i) {
+      if (filter_step(at, chunks[i], bf16, false)) return 1;
+      if (select_radix(bf16, sched.sel_cap)) return 1;
+      rounds++;
+      at += chunks[i];
+    }
+    return 0;
+  }
+
   void trace(const char* what, int64_t done, int64_t chunk, const unsigned (&f)[4]) {
-    g_info[1]++;                                  // rounds
-    if (f[1] > (unsigned)g_info[3]) g_info[3] = f[1];
+    rounds++;
+    max_list = std::max<int64_t>(max_list, f[1]);
     const bool dbg = (om_option(OM_OPT_SEARCH_DEBUG) & 1) != 0;
     if (dbg) fprintf(stderr, "[om_sim_topk] %-8s done=%ld chunk=%ld overflow=%u max_list=%u too_wide=%u\n",
                      what, (long)done, (long)chunk, f[0], f[1], f[2]);
@@ -1898,14 +1792,7 @@ struct Scan {
 
   // returns 0 ok, 1 error, 2 certified margin too wide (caller retries in f32)
   int run(bool bf16) {
-    hipLaunchKernelGGL(init_lists_kernel, dim3((unsigned)((nq + 255) / 256 + 2)), dim3(256), 0, s,
-                       ws.cnt, ws.cnt_prev, ws.thr, nq, ws.flag);
-    OM_LAUNCH_CHECK();
-    if (bf16) {
-      hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
-                         ws.qb, ws.margin, stats, nq, d);
-      OM_LAUNCH_CHECK();
-    }
+    if (begin(bf16)) return 1;
     int64_t done = 0;
     unsigned f[4] = {0, 0, 0, 0};
     bool unsorted = false;
@@ -1915,23 +1802,10 @@ struct Scan {
     // it.  One read of the flags at the very end; an overflow or a too-wide margin anywhere (adversarial row order,
     // heavily duplicated rows) falls back to the step-by-step loop below from scratch, which is always exact.
     bool careful = true;
-    if (om_option(OM_OPT_SCAN_GEN7) && N > DENSE_CHUNK) {
-      if (dense_gemm_append(0, DENSE_CHUNK, bf16)) return 1;
-      if (select_radix(bf16, DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
-      g_info[1]++;
-      // the list estimate, the growth per round, the selection's LDS copy and the chunks: search_plan.h search_schedule, shared with
-      // the asynchronous entry
-      int64_t chunks[SEARCH_SCHED_MAX];
-      const SearchSchedule sched = search_schedule(bf16, nq, N, k, scan_switches(), chunks, SEARCH_SCHED_MAX);
-      if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
+    if (sw.gen7 && N > DENSE_CHUNK) {
+      SearchSchedule sched;
+      if (fast_rounds(bf16, sched)) return 1;
       const int64_t list = sched.list;
-      int64_t at = DENSE_CHUNK;
-      for (int i = 0; i < sched.n; ++i) {
-        if (filter_step(at, chunks[i], bf16, false)) return 1;
-        if (select_radix(bf16, sched.sel_cap)) return 1;
-        g_info[1]++;
-        at += chunks[i];
-      }
       // Few queries: the exact re-score and the final sort are queued BEHIND the last round before the flags are read, so
       // the host's wake-up overlaps them instead of idling the device (a 34 us hole per search at one query).  They
       // cover lists up to twice the estimate; a longer list (never seen) counts as a failed fast schedule.
@@ -1946,7 +1820,7 @@ struct Scan {
       }
       unsigned g[4];
       if (read_flags(g)) return 1;
-      if (g[1] > (unsigned)g_info[3]) g_info[3] = g[1];
+      max_list = std::max<int64_t>(max_list, g[1]);
       if (!g[0] && !g[2] && !(spec && g[1] > spec_cover)) {
         if (spec) return 0;                      // everything is done
         done = N;
@@ -1954,10 +1828,8 @@ struct Scan {
         unsorted = true;                         // the lists are cut but not ordered: one sort at the very end
         careful = false;
       } else {                                   // rare: start over on the careful path
-        g_info[2]++;
-        hipLaunchKernelGGL(init_lists_kernel, dim3((unsigned)((nq + 255) / 256 + 2)), dim3(256), 0, s,
-                           ws.cnt, ws.cnt_prev, ws.thr, nq, ws.flag);
-        OM_LAUNCH_CHECK();
+        fallbacks++;
+        if (init_lists()) return 1;
       }
     }
     if (careful) {                               // bootstrap of the step-by-step loop
@@ -1983,7 +1855,7 @@ struct Scan {
       if (!f[0]) {
         if (select(bf16)) return 1;
       } else {
-        g_info[2]++;
+        fallbacks++;
         // a list overflowed: rewind to the pre-chunk lists and redo the chunk densely
         hipLaunchKernelGGL(restore_cnt_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s,
                            ws.cnt, ws.cnt_prev, nq);
@@ -2018,36 +1890,15 @@ struct Scan {
   // -> rounds -> re-score -> redo of every query with a sticky bit -> ONE final sort of all lists -> emit -> status.
   int run_async(bool bf16, const AsyncWs& aw, int64_t id_offset, float* out_scores, int64_t* out_ids, int64_t* status) {
     const unsigned qblocks = (unsigned)((nq + 255) / 256);
-    hipLaunchKernelGGL(init_lists_kernel, dim3(qblocks + 2), dim3(256), 0, s, ws.cnt, ws.cnt_prev, ws.thr, nq, ws.flag);
-    hipLaunchKernelGGL(async_init_kernel, dim3(qblocks), dim3(256), 0, s, aw.qstat, aw.rs, status, nq);
-    OM_LAUNCH_CHECK();
-    int rounds = 0, family = 0;
+    if (begin(bf16, &aw, status)) return 1;
     if (N > 0) {
-      if (bf16) {
-        hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
-                           ws.qb, ws.margin, stats, nq, d);
-        OM_LAUNCH_CHECK();
-      }
-      int64_t list = bf16 ? (int64_t)k * 13 / 10 + 64 : (int64_t)k + 16;
+      SearchSchedule sched;
       if (N <= DENSE_CHUNK) {                      // one dense step, no rounds (what om_sim_topk does for a shard this small)
+        sched = search_schedule(bf16, nq, N, k, sw, nullptr, 0);      // (its list estimate alone)
         if (dense_step(0, (int)N, bf16)) return 1;
-        rounds = 1;
-      } else {
-        if (dense_gemm_append(0, DENSE_CHUNK, bf16)) return 1;
-        if (select_radix(bf16, DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
-        int64_t chunks[SEARCH_SCHED_MAX];
-        const SearchSchedule sched = search_schedule(bf16, nq, N, k, scan_switches(), chunks, SEARCH_SCHED_MAX);
-        if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
-        list = sched.list;
-        int64_t at = DENSE_CHUNK;
-        for (int i = 0; i < sched.n; ++i) {
-          if (filter_step(at, chunks[i], bf16, false)) return 1;
-          if (select_radix(bf16, sched.sel_cap)) return 1;
-          at += chunks[i];
-        }
-        rounds = 1 + sched.n;
-        family = (int)g_info[5];
-      }
+        rounds++;
+      } else if (fast_rounds(bf16, sched)) return 1;
+      const int64_t list = sched.list;
       if (bf16) {
         // exact f32 re-score of the certified candidates.  Up to 128 queries: om_sim_topk's own launch, covering lists up to twice the
         // estimate -- a longer list is marked (QSTAT_COVER) and redone; above: the fixed grid, which reaches every slot below cnt.
@@ -2082,11 +1933,56 @@ struct Scan {
       if (select(false, false)) return 1;          // best k of every list, in order
     }
     hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, out_scores, out_ids);
-    hipLaunchKernelGGL(async_status_kernel, dim3(1), dim3(64), 0, s, ws.flag, aw.rs, status, bf16 ? 1 : 0, rounds, family);
+    hipLaunchKernelGGL(async_status_kernel, dim3(1), dim3(64), 0, s, ws.flag, aw.rs, status, bf16 ? 1 : 0, (int)rounds, family);
     OM_LAUNCH_CHECK();
     return 0;
   }
+
+  // om_sim_topk behind its checks: the 16-bit scan, the float32 one when that was asked for or the certified margin is too wide, emit
+  int run_sync(int64_t id_offset, float* out_scores, int64_t* out_ids) {
+    if (N > 0) {
+      int rc = 2;
+      if (mode == OM_SEARCH_F16_RESCORE) {
+        rc = run(true);
+        if (rc == 1) return 1;
+        precision = 1;
+        if (rc == 2) too_wide = 1;
+      }
+      if (rc == 2) {                           // f32 scan (requested, or margin too wide)
+        precision = 0;
+        if (run(false)) return 1;
+      }
+    } else {
+      hipLaunchKernelGGL(init_lists_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s,
+                         ws.cnt, ws.cnt_prev, ws.thr, nq, ws.flag);
+      OM_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, out_scores, out_ids);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
+  int precision = 0, too_wide = 0;      // om_sim_topk_info [0] and [4]
 };
+
+// The argument checks and the set-up the two entries share (n_queries > 0).  Returns the refusal, nullptr when there is none: the entry
+// fails with it under its own name.
+const char* scan_setup(Scan& sc, int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
+                       const float* stats, int64_t N, int d, int k, const float* out_scores, const int64_t* out_ids, void* workspace,
+                       void* stream) {
+  if (k < 1 || k > K_MAX) return "k must be in [1,2048]";
+  if (N < 0 || N > 0xffffffffLL) return "shard rows must fit in 32 bits";
+  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) return "d must be a multiple of 64 (pad with zeros)";
+  if (n_queries > 65535) return "at most 65535 queries per call";
+  if (!queries || !out_scores || !out_ids) return "null argument";
+  if (!workspace || ((uintptr_t)workspace & 255)) return "workspace must be 256-byte aligned";
+  if (N > 0 && !index_f32) return "index_f32 is null";
+  if (N > 0 && mode == OM_SEARCH_F16_RESCORE && (!index_f16 || !stats)) return "f16 mode needs index_f16 and stats";
+  sc.ws = carve_search(n_queries, d, (char*)workspace);
+  sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
+  sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = (hipStream_t)stream; sc.stats = stats;
+  sc.sw = scan_switches();
+  return nullptr;
+}
 }  // namespace
 
 // dynamic-LDS attributes of every kernel a search launches: host calls, made once (a capturing stream must not meet them)
@@ -2095,21 +1991,7 @@ static int search_attrs() {
   if (!attr_set) {
     OM_HIP(hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                SORT_CAP * 8 + 16));
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel<float>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES));
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel<f16_t>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES));
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel6<float>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS_BYTES));
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel6<f16_t>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS_BYTES));
-    if (stream_attrs()) return 1;
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel7<f16_t>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel7c<f16_t>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
-    OM_HIP(hipFuncSetAttribute((const void*)sim_filter_kernel7c16<f16_t>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS_BYTES));
+    if (scan_attrs()) return 1;
     OM_HIP(hipFuncSetAttribute((const void*)select_radix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                SORT_CAP * 8 + 1024 + 64));
     attr_set = true;
@@ -2123,82 +2005,38 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
                            int64_t* out_ids, void* workspace, size_t workspace_bytes,
                            void* stream) {
   if (n_queries <= 0) return 0;
-  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1,2048]");
-  if (N < 0 || N > 0xffffffffLL) OM_FAIL("shard rows must fit in 32 bits");
-  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) OM_FAIL("d must be a multiple of 64 (pad with zeros)");
-  if (n_queries > 65535) OM_FAIL("at most 65535 queries per call");
-  if (!queries || !out_scores || !out_ids) OM_FAIL("null argument");
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
   Scan sc;
-  sc.ws = carve_search(n_queries, d, (char*)workspace);
+  if (const char* why = scan_setup(sc, mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, stream))
+    OM_FAIL(why);
   if (sc.ws.total > workspace_bytes) OM_FAIL("workspace too small");
-  sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
-  sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = s; sc.stats = stats;
-
   if (search_attrs()) return 1;
   for (auto& v : g_info) v = 0;
-  if (N > 0) {
-    if (!index_f32) OM_FAIL("index_f32 is null");
-    int rc = 2;
-    if (mode == OM_SEARCH_F16_RESCORE) {
-      if (!index_f16 || !stats) OM_FAIL("f16 mode needs index_f16 and stats");
-      rc = sc.run(true);
-      if (rc == 1) return 1;
-      g_info[0] = 1;
-      if (rc == 2) g_info[4] = 1;
-    }
-    if (rc == 2) {                           // f32 scan (requested, or margin too wide)
-      g_info[0] = 0;
-      if (sc.run(false)) return 1;
-    }
-  } else {
-    hipLaunchKernelGGL(init_lists_kernel, dim3((unsigned)((n_queries + 255) / 256)), dim3(256), 0, s,
-                       sc.ws.cnt, sc.ws.cnt_prev, sc.ws.thr, n_queries, sc.ws.flag);
-    OM_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(emit_kernel, dim3((unsigned)n_queries), dim3(256), 0, s, sc.ws.keys, sc.ws.cnt, k,
-                     id_offset, out_scores, out_ids);
-  OM_LAUNCH_CHECK();
-  return 0;
+  const int rc = sc.run_sync(id_offset, out_scores, out_ids);
+  g_info[0] = sc.precision; g_info[1] = sc.rounds; g_info[2] = sc.fallbacks; g_info[3] = sc.max_list;
+  g_info[4] = sc.too_wide; g_info[5] = sc.family; g_info[6] = sc.launch;
+  return rc;
 }
 
-// The asynchronous search: om_sim_topk's arguments, checks and output; everything on `stream`, nothing read back.
+// The asynchronous search: om_sim_topk's arguments, checks and output; everything on `stream`, nothing read back, and the thread's
+// om_sim_topk_info left as it is.
 extern "C" int om_sim_topk_async(int mode, const float* queries, int64_t n_queries,
                                  const float* index_f32, const void* index_f16, const float* stats,
                                  int64_t N, int d, int k, int64_t id_offset, float* out_scores,
                                  int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   if (n_queries <= 0) return 0;
-  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1,2048]");
-  if (N < 0 || N > 0xffffffffLL) OM_FAIL("shard rows must fit in 32 bits");
-  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) OM_FAIL("d must be a multiple of 64 (pad with zeros)");
+  Scan sc;
+  if (const char* why = scan_setup(sc, mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, stream))
+    OM_FAIL(why);
   if (d > 16384) OM_FAIL("d above 16384: a row does not fit the redo's LDS tile (use om_sim_topk)");
-  if (n_queries > 65535) OM_FAIL("at most 65535 queries per call");
-  if (!queries || !out_scores || !out_ids) OM_FAIL("null argument");
   if (!status) OM_FAIL("status is null: the asynchronous entry reports through 8 x int64 of device memory");
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  if (!om_option(OM_OPT_SCAN_GEN7))
+  if (!sc.sw.gen7)
     OM_FAIL("OM_OPT_SCAN_GEN7 is 0: the fast schedule this entry runs is switched off (use om_sim_topk)");
   const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
   if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes)");
-  const bool bf16 = mode == OM_SEARCH_F16_RESCORE;
-  if (N > 0) {
-    if (!index_f32) OM_FAIL("index_f32 is null");
-    if (bf16 && (!index_f16 || !stats)) OM_FAIL("f16 mode needs index_f16 and stats");
-  }
-  Scan sc;
-  sc.ws = carve_search(n_queries, d, (char*)workspace);
-  sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
-  sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = (hipStream_t)stream; sc.stats = stats;
   sc.qstat = aw.qstat;
   if (search_attrs()) return 1;
-  int64_t keep[8];                           // om_sim_topk_info keeps describing the thread's last om_sim_topk
-  for (int i = 0; i < 8; ++i) keep[i] = g_info[i];
-  g_info[5] = 0;
-  const int rc = sc.run_async(bf16, aw, id_offset, out_scores, out_ids, status);
-  for (int i = 0; i < 8; ++i) g_info[i] = keep[i];
-  return rc;
+  return sc.run_async(mode == OM_SEARCH_F16_RESCORE, aw, id_offset, out_scores, out_ids, status);
 }
 
 extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,
@@ -2206,11 +2044,13 @@ extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t r
   if (!rows16 || !queries16 || !thr || !keys || !cnt) OM_FAIL("null argument");
   if (nrows <= 0 || nrows % SR_UROWS != 0) OM_FAIL("whole 128-row tiles only");
   if (grid < 1 || grid > 65535) OM_FAIL("grid must be in [1,65535]");
-  const ScanPlan plan = scan_plan(true, nq, d, scan_switches());
+  const ScanSwitches sw = scan_switches();
+  const ScanPlan plan = scan_plan(true, nq, d, sw);
   if (plan.family != OM_SCAN_FAMILY_STREAM32 && plan.family != OM_SCAN_FAMILY_STREAM16)
     OM_FAIL("the scan plan sends this (nq, d) to no stream kernel");
-  if (stream_attrs()) return 1;
-  stream_launch(plan, (const f16_t*)rows16, nrows, row_base, (const f16_t*)queries16, nq, d, thr, (u64*)keys, cnt, grid, (hipStream_t)stream);
+  if (scan_attrs()) return 1;
+  if (scan_launch(scan_kernel(OM_SCAN_KERNEL_STREAM, true, plan, sw), rows16, nrows, row_base, queries16, nq, d, thr, (u64*)keys, cnt, grid, sw.nt,
+                  (hipStream_t)stream)) return 1;
   OM_LAUNCH_CHECK();
   return 0;
 }

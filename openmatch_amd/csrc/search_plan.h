@@ -1,8 +1,14 @@
-// Which kernel a filtered scan round runs: scan_plan() maps (index format, queries, width, switches) to a ScanPlan and does nothing
-// else -- no launch, no HIP call, no global written, no pointer dereferenced.  Scan::filter_step (search.hip) launches what it returns;
-// om_debug_scan_plan returns the plan alone, so the table is testable on a machine without a GPU, and om_debug_sim_stream launches the
-// stream instantiation it names over a caller's buffers.  DESIGN.md 4f lists the rules in the order they are tested here.
+// What a filtered scan round launches: scan_plan() maps (index format, queries, width, switches) to a ScanPlan -- the kernel family and,
+// for the stream kernels, the instantiation -- and scan_round() maps (plan, rows of the round, CUs) to the round's launches: kernel id,
+// rows, grid and `group` argument of a main launch and of a ragged tail.  Neither does anything else -- no launch, no HIP call, no global
+// read or written, no pointer dereferenced.  Scan::filter_step (search.hip) asks for the round and launches it from the kernel table;
+// om_debug_scan_plan / om_debug_scan_round return the plan / the round alone, so the rules are testable on a machine without a GPU, and
+// om_debug_sim_stream launches the stream instantiation a plan names over a caller's buffers.  DESIGN.md 4f lists the rules in the order
+// they are tested here.
 #pragma once
+#include <algorithm>
+
+#include "gemm_plan.h"      // g7_ring_ok
 #include "kernels.h"
 
 struct ScanSwitches {
@@ -10,11 +16,16 @@ struct ScanSwitches {
                     // ones); 0 the tile-at-a-time kernels of generations 2 and 6
   int growth_set;   // OM_OPT_SCAN_GROWTH was given by the caller (else 33-128 queries take their own measured value)
   int growth;       // OM_OPT_SCAN_GROWTH: rows per round of the fast schedule, in percent of the rows already scanned
+  int qgroup;       // OM_OPT_SCAN_QGROUP: query tiles an XCD keeps resident while the generation-7 scan sweeps the index rows
+  int nt;           // OM_OPT_SEARCH_DEBUG bit 2 clear: the stream kernels fetch the index with non-temporal loads
+  int probe;        // OM_OPT_SEARCH_DEBUG bits 3-4: the timing variant of the stream kernel (probe builds only; 0 the real one)
 };
 
-// every switch the planner reads, read once per call
+// every switch the planner reads, read once per entry call
 static ScanSwitches scan_switches() {
-  return ScanSwitches{om_option(OM_OPT_SCAN_GEN7), om_option_is_set(OM_OPT_SCAN_GROWTH) ? 1 : 0, om_option(OM_OPT_SCAN_GROWTH)};
+  const int debug = om_option(OM_OPT_SEARCH_DEBUG);
+  return ScanSwitches{om_option(OM_OPT_SCAN_GEN7), om_option_is_set(OM_OPT_SCAN_GROWTH) ? 1 : 0, om_option(OM_OPT_SCAN_GROWTH),
+                      om_option(OM_OPT_SCAN_QGROUP), (debug & 4) ? 0 : 1, (debug >> 3) & 3};
 }
 
 #define SCAN_KSTEP 64            // index columns per K step of the stream kernels (one 128-byte LDS row of 16-bit values)
@@ -34,8 +45,7 @@ static ScanPlan scan_plan(bool half, int64_t nq, int d, const ScanSwitches sw) {
     p.family = family; p.qblock = qblock; p.nb = blocks <= 1 ? 1 : blocks <= 2 ? 2 : 4; p.nkmax = nkmax;
     return p;
   };
-  // 1. more than one 128-query tile: the 256 x 256 kernels (generation 7 / 7c / 7c16 over whole tiles, generation 6 for the ragged
-  //    tail and with the switch off: filter_step's own sub-choice), in both index formats
+  // 1. more than one 128-query tile: the 256 x 256 kernels, in both index formats (which of them: scan_round)
   if (nq > 128) { p.family = OM_SCAN_FAMILY_WIDE; return p; }
   // 2. the float32 index, the switch off, no whole K step: the 128-query tile of generation 2
   if (!half || !sw.gen7 || nq < 1 || d < SCAN_KSTEP || d % SCAN_KSTEP != 0) return p;
@@ -48,6 +58,41 @@ static ScanPlan scan_plan(bool half, int64_t nq, int d, const ScanSwitches sw) {
   // 5. wider rows: a 32-query block no longer fits a wave's registers, a 16-query block does up to d = 2048 -- at most 64 queries
   if (nk <= SCAN_NKMAX16 && nq <= 64) return stream(OM_SCAN_FAMILY_STREAM16, 16, SCAN_NKMAX16);
   return p;
+}
+
+// One launch of a round: kernel OM_SCAN_KERNEL_* (the stream instantiation is the plan's qblock / nb / nkmax), rows [row0, row0 + rows) of
+// the round on `grid` workgroups; group: the kernel's last argument -- group_m | qgroup << 8 of the tile walk, for the stream kernel 1
+// when it fetches the index with non-temporal loads.  rows == 0: no launch (kernel 0).
+struct ScanLaunch { int kernel; int64_t row0, rows, grid; int group; };
+struct ScanRound { bool ok; ScanLaunch main, tail; };      // !ok: a grid above 2^31 - 1 workgroups
+
+// The launches of one filtered round over `rows` index rows on a device of `cus` compute units.  The persistent kernels take the whole
+// tiles on at most one workgroup per CU and leave the ragged rest to a tile-at-a-time kernel; either part may be empty.
+static ScanRound scan_round(const ScanPlan& plan, bool half, int64_t nq, int d, int64_t rows, int cus, const ScanSwitches& sw) {
+  ScanRound r = {true, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
+  const int64_t tiles256 = (rows + 255) / 256, q256 = (nq + 255) / 256, q128 = (nq + 127) / 128;
+  auto split = [&](int kernel, int64_t unit, int64_t grid_per_unit, int group, int tail_kernel, int64_t tail_grid) {
+    const int64_t whole = rows - rows % unit;
+    if (whole) r.main = {kernel, 0, whole, std::min<int64_t>(cus, whole / unit * grid_per_unit), group};
+    if (rows > whole) r.tail = {tail_kernel, whole, rows - whole, tail_grid, 8};
+  };
+  if (plan.family == OM_SCAN_FAMILY_WIDE && half && sw.gen7) {
+    // 1. wide batches on the 16-bit index: generation 7 over the whole 256-row tiles -- on the continuous ring where the rows hold its
+    //    three K steps -- and generation 6 over the ragged tail
+    split(g7_ring_ok(d) ? OM_SCAN_KERNEL_WIDE7C : OM_SCAN_KERNEL_WIDE7, 256, q256, 8 | (std::max(1, sw.qgroup) << 8), OM_SCAN_KERNEL_TILE6, q256);
+  } else if (plan.family == OM_SCAN_FAMILY_WIDE) {
+    // 2. wide batches with the switch off, or on the float32 index: generation 6, one workgroup per (row tile, query tile)
+    r.main = {OM_SCAN_KERNEL_TILE6, 0, rows, tiles256 * q256, 8};
+    r.ok = r.main.grid <= 0x7fffffffLL;
+  } else if (plan.family == OM_SCAN_FAMILY_STREAM32 || plan.family == OM_SCAN_FAMILY_STREAM16) {
+    // 3. the stream kernels over the whole 128-row tiles, the generic tile over the ragged tail
+    split(OM_SCAN_KERNEL_STREAM, 128, 1, sw.nt, OM_SCAN_KERNEL_TILE2, q128);
+  } else {
+    // 4. the generic tile, one workgroup per (256 rows, 128 queries)
+    r.main = {OM_SCAN_KERNEL_TILE2, 0, rows, tiles256 * q128, 8};
+  }
+  if (!r.main.rows) r.main = {0, 0, 0, 0, 0};
+  return r;
 }
 
 // ---- the fast schedule's chunk arithmetic (one function for om_sim_topk and om_sim_topk_async, so the two cannot drift apart) --------

@@ -96,8 +96,9 @@ class FlatIPIndex:
         self._stats.zero_()
 
     # -- search ----------------------------------------------------------------------------
-    def search_device(self, queries: torch.Tensor, k: int, id_offset: int = 0):
-        """Local-shard search on device tensors: returns (D [Q,k] f32, I [Q,k] int64) on the GPU."""
+    def _search_args(self, queries, k):
+        """What both searches start from: the float32 query panel [Q, dpad] on the index's device, the outputs D [Q,k] f32 and
+        I [Q,k] int64, and the native mode."""
         if queries.dim() != 2 or queries.shape[1] != self.d:
             raise ValueError(f"expected [q,{self.d}] queries")
         q = queries.to(device=self.device, dtype=torch.float32)
@@ -106,10 +107,14 @@ class FlatIPIndex:
             qp[:, :self.d].copy_(q)
             q = qp
         q = q.contiguous()
+        D = torch.empty(q.shape[0], k, dtype=torch.float32, device=self.device)
+        I = torch.empty(q.shape[0], k, dtype=torch.int64, device=self.device)
+        return q, D, I, N.SEARCH_F16_RESCORE if self.precision == "f16_rescore" else N.SEARCH_F32
+
+    def search_device(self, queries: torch.Tensor, k: int, id_offset: int = 0):
+        """Local-shard search on device tensors: returns (D [Q,k] f32, I [Q,k] int64) on the GPU."""
+        q, D, I, mode = self._search_args(queries, k)
         nq = q.shape[0]
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        mode = N.SEARCH_F16_RESCORE if self.precision == "f16_rescore" else N.SEARCH_F32
         lib = N.lib()
         step = 32768                       # the kernel takes <= 65535 queries per call
         with torch.cuda.device(self.device):
@@ -125,7 +130,8 @@ class FlatIPIndex:
         lib.om_sim_topk_info(info)
         self.last_search_info = {"scan": "f16+rescore" if info[0] == 1 else "f32", "rounds": int(info[1]),
                                  "overflow_fallbacks": int(info[2]), "max_list": int(info[3]),
-                                 "margin_too_wide": bool(info[4]), "kernel": N.SCAN_FAMILY_NAME[int(info[5])]}
+                                 "margin_too_wide": bool(info[4]), "kernel": N.SCAN_FAMILY_NAME[int(info[5])],
+                                 "launch": N.SCAN_KERNEL_NAME[int(info[6])]}
         return D, I
 
     def search_device_async(self, queries: torch.Tensor, k: int, id_offset: int = 0):
@@ -133,18 +139,8 @@ class FlatIPIndex:
         `SearchHandle` whose `.D` / `.I` are valid in the order of that stream.  The handle owns its workspace, its status words and
         its padded query copy, so several searches can be in flight (back to back, on several streams, or captured in a graph: the
         handle then has to outlive the graph).  The index must not be added to or reset while a search is in flight."""
-        if queries.dim() != 2 or queries.shape[1] != self.d:
-            raise ValueError(f"expected [q,{self.d}] queries")
-        q = queries.to(device=self.device, dtype=torch.float32)
-        if self.dpad != self.d:            # zero-padded to the kernels' K step
-            qp = torch.zeros(q.shape[0], self.dpad, dtype=torch.float32, device=self.device)
-            qp[:, :self.d].copy_(q)
-            q = qp
-        q = q.contiguous()
+        q, D, I, mode = self._search_args(queries, k)
         nq = q.shape[0]
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        mode = N.SEARCH_F16_RESCORE if self.precision == "f16_rescore" else N.SEARCH_F32
         lib = N.lib()
         step = 32768
         chunks = []

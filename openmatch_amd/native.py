@@ -32,6 +32,9 @@ ENC_PATH = {"bert_fused": 1, "bert_pending_ln": 2, "bert_few32": 3, "bert_plain"
 # om_debug_scan_plan / om_sim_topk_info[5] codes (OM_SCAN_FAMILY_*); 0: the search never left the dense path
 SCAN_FAMILY = {"dense": 0, "generic": 1, "wide": 2, "stream32": 3, "stream16": 4}
 SCAN_FAMILY_NAME = {v: k for k, v in SCAN_FAMILY.items()}
+# om_debug_scan_round / om_sim_topk_info[6] codes (OM_SCAN_KERNEL_*): the main launch of the last filtered round
+SCAN_KERNEL = {"dense": 0, "tile2": 1, "tile6": 2, "wide7": 3, "wide7c": 4, "stream": 5}
+SCAN_KERNEL_NAME = {v: k for k, v in SCAN_KERNEL.items()}
 OPT_SCAN_GEN7 = 3
 OPT_ATTENTION_FAST = 2
 SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
@@ -332,6 +335,7 @@ _SIGNATURES = {
     "om_debug_search_schedule": (c_int, [c_int, c_int64, c_int64, c_int, C.POINTER(c_int64), c_int, C.POINTER(c_int)]),
     "om_sim_topk_info": (None, [C.POINTER(c_int64)]),
     "om_debug_scan_plan": (c_int, [c_int, c_int64, c_int, C.POINTER(c_int)]),
+    "om_debug_scan_round": (c_int, [c_int, c_int64, c_int, c_int64, c_int, C.POINTER(c_int64)]),
     "om_debug_sim_stream": (c_int, [c_void_p, c_int64, C.c_uint32, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "om_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p,
                               c_void_p]),

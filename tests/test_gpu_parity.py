@@ -2545,9 +2545,11 @@ def test_few_rows_forward_tracks_f32_path_and_is_batch_invariant(dtype, arch):
         assert few_sum < tile_sum, (few_sum, tile_sum)
 
 
-def test_index_scan_on_16x16x32_mfmas_returns_the_lists_of_the_default_kernel():
-    """OM_GEMM_CONT bit 10 (round 6, opt-in: a wash end to end, profiles/r06_scan_16x16x32_ab.txt): the wide-batch scan on the encoder's
-    16 x 16 x 32 K loop.  Same scores, same ids as the default 32 x 32 x 16 kernel, k-way ties included, on a ragged row count."""
+def test_index_scan_with_the_persistent_kernels_switched_off_returns_the_lists_of_the_default_kernel():
+    """OM_OPT_SCAN_GEN7 = 0: the wide-batch scan on the tile-at-a-time kernel of generation 6 under the careful schedule.  Same scores,
+    same ids as the default search (generation 7 on the continuous ring, the fast schedule), k-way ties included, on a ragged row count:
+    both return the re-score's float32 dot products of the exact top-k in the header's tie order.  (Until the scan kernel on 16 x 16 x 32
+    MFMAs was retired -- a wash end to end, profiles/r06_scan_16x16x32_ab.txt -- this test compared that kernel with the default one.)"""
     from openmatch_amd import native as N_
     from openmatch_amd.index import FlatIPIndex
     g = torch.Generator().manual_seed(9)
@@ -2559,11 +2561,12 @@ def test_index_scan_on_16x16x32_mfmas_returns_the_lists_of_the_default_kernel():
     idx = FlatIPIndex(d, device=DEV)
     idx.add(rows.numpy())
     D0, I0 = idx.search(q.numpy(), k)
-    N_.check(N_.lib().om_debug_option(16, 495 | 1024))
+    before = N_.lib().om_debug_option_value(N_.OPT_SCAN_GEN7)
+    N_.check(N_.lib().om_debug_option(N_.OPT_SCAN_GEN7, 0))
     try:
         D1, I1 = idx.search(q.numpy(), k)
     finally:
-        N_.check(N_.lib().om_debug_option(16, 495))
+        N_.check(N_.lib().om_debug_option(N_.OPT_SCAN_GEN7, before))
     assert np.array_equal(I0, I1) and np.array_equal(D0, D1)
 
 

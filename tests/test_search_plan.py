@@ -85,3 +85,101 @@ def test_switch_off_sends_small_batches_to_the_generic_tile(d):
 def test_null_output_is_refused():
     assert N.lib().om_debug_scan_plan(1, 1, 768, None) == 1
     assert b"null argument" in N.lib().om_last_error()
+
+
+# ---- the launches of a round (scan_round through om_debug_scan_round), on a device of 256 compute units -------------------------------
+TILE2, TILE6, WIDE7, WIDE7C, STREAM = (N.SCAN_KERNEL[k] for k in ("tile2", "tile6", "wide7", "wide7c", "stream"))
+OPT_SCAN_QGROUP, OPT_SEARCH_DEBUG, OPT_GEMM_CONT = 7, 13, 16          # include/openmatch_hip.h
+NONE = (0, 0, 0, 0)
+QGROUP8 = 8 | 8 << 8                                                   # group_m 8, OM_OPT_SCAN_QGROUP's default 8
+
+
+def scan_round(half, nq, d, rows, cus=256):
+    """((kernel, rows, grid, group) of the main launch, the same of the tail)"""
+    out = (C.c_int64 * 8)()
+    N.check(N.lib().om_debug_scan_round(int(half), nq, d, rows, cus, out))
+    return tuple(out[:4]), tuple(out[4:])
+
+
+def test_a_wide_round_splits_into_whole_tiles_on_the_ring_and_a_ragged_tail():
+    # 3629 = 14 * 256 + 45 rows, 300 queries = 2 query tiles: 28 (row tile, query tile) pairs, fewer than the CUs
+    assert scan_round(1, 300, 768, 3629) == ((WIDE7C, 3584, 28, QGROUP8), (TILE6, 45, 2, 8))
+    assert scan_round(1, 300, 768, 255) == (NONE, (TILE6, 255, 2, 8))
+    assert scan_round(1, 300, 768, 4096) == ((WIDE7C, 4096, 32, QGROUP8), NONE)
+    assert scan_round(1, 300, 768, 256) == ((WIDE7C, 256, 2, QGROUP8), NONE)
+
+
+def test_the_continuous_ring_needs_three_k_steps():
+    for d, kernel in ((64, WIDE7), (128, WIDE7), (192, WIDE7C), (256, WIDE7C)):
+        assert scan_round(1, 300, d, 3629) == ((kernel, 3584, 28, QGROUP8), (TILE6, 45, 2, 8)), d
+
+
+@pytest.mark.parametrize("cont", [495, 495 & ~4, 495 | 1024, (495 & ~4) | 1024, 0])
+def test_bits_2_and_10_of_the_gemm_switch_change_nothing(cont):
+    with switched(OPT_GEMM_CONT, cont):
+        assert scan_round(1, 300, 768, 3629) == ((WIDE7C, 3584, 28, QGROUP8), (TILE6, 45, 2, 8))
+        assert scan_round(1, 300, 128, 3629) == ((WIDE7, 3584, 28, QGROUP8), (TILE6, 45, 2, 8))
+        assert scan_round(1, 64, 768, 3629) == ((STREAM, 3584, 28, 1), (TILE2, 45, 1, 8))
+
+
+def test_switch_off_is_one_launch_of_a_tile_kernel():
+    with switched(OPT_SCAN_GEN7, 0):
+        assert scan_round(1, 300, 768, 3629) == ((TILE6, 3629, 15 * 2, 8), NONE)      # 15 row tiles x 2 query tiles
+        assert scan_round(1, 64, 768, 3629) == ((TILE2, 3629, 15 * 1, 8), NONE)       # 15 row tiles x 1 query tile of 128
+        assert scan_round(1, 300, 768, 4096) == ((TILE6, 4096, 32, 8), NONE)
+
+
+def test_the_float32_index_is_one_launch_of_a_tile_kernel():
+    assert scan_round(0, 300, 768, 3629) == ((TILE6, 3629, 30, 8), NONE)
+    assert scan_round(0, 64, 768, 3629) == ((TILE2, 3629, 15, 8), NONE)
+    assert scan_round(0, 128, 768, 256) == ((TILE2, 256, 1, 8), NONE)
+    assert scan_round(0, 257, 64, 257) == ((TILE6, 257, 4, 8), NONE)                  # 2 row tiles x 2 query tiles
+
+
+def test_a_stream_round_splits_into_128_row_tiles_and_a_generic_tail():
+    # 3629 = 28 * 128 + 45
+    for nq, d in ((1, 768), (64, 768), (128, 1024), (64, 2048)):
+        assert scan_round(1, nq, d, 3629) == ((STREAM, 3584, 28, 1), (TILE2, 45, 1, 8)), (nq, d)
+    assert scan_round(1, 64, 768, 127) == (NONE, (TILE2, 127, 1, 8))
+    assert scan_round(1, 64, 768, 3584) == ((STREAM, 3584, 28, 1), NONE)
+    assert scan_round(1, 64, 192, 3629) == ((TILE2, 3629, 15, 8), NONE)               # no stream kernel below four K steps
+
+
+def test_persistent_grids_never_exceed_the_compute_units():
+    rows = 1 << 20
+    assert scan_round(1, 300, 768, rows) == ((WIDE7C, rows, 256, QGROUP8), NONE)       # 4096 x 2 pairs
+    assert scan_round(1, 300, 128, rows + 45) == ((WIDE7, rows, 256, QGROUP8), (TILE6, 45, 2, 8))
+    assert scan_round(1, 64, 768, rows) == ((STREAM, rows, 256, 1), NONE)               # 8192 tiles
+    assert scan_round(1, 300, 768, rows, cus=7)[0] == (WIDE7C, rows, 7, QGROUP8)
+    assert scan_round(1, 64, 768, rows, cus=7)[0] == (STREAM, rows, 7, 1)
+    for cus in (1, 13, 256, 304):
+        for nq, d in ((300, 768), (4096, 128), (1, 768), (64, 2048)):
+            for r in (128, 256, 3629, rows):
+                main, _tail = scan_round(1, nq, d, r, cus=cus)
+                assert main == NONE or 1 <= main[2] <= cus, (cus, nq, d, r, main)
+
+
+def test_the_query_group_switch_appears_in_the_group_argument():
+    with switched(OPT_SCAN_QGROUP, 3):
+        assert scan_round(1, 300, 768, 3629) == ((WIDE7C, 3584, 28, 8 | 3 << 8), (TILE6, 45, 2, 8))
+    with switched(OPT_SCAN_QGROUP, 0):                                                  # at least one tile
+        assert scan_round(1, 300, 768, 3629)[0] == (WIDE7C, 3584, 28, 8 | 1 << 8)
+    assert scan_round(1, 300, 768, 3629)[0] == (WIDE7C, 3584, 28, QGROUP8)              # restored
+
+
+def test_the_cache_policy_switch_appears_in_the_stream_kernels_last_argument():
+    with switched(OPT_SEARCH_DEBUG, 4):
+        assert scan_round(1, 64, 768, 3629) == ((STREAM, 3584, 28, 0), (TILE2, 45, 1, 8))
+    assert scan_round(1, 64, 768, 3629)[0] == (STREAM, 3584, 28, 1)
+
+
+def test_a_grid_above_31_bits_is_refused_where_it_is_one_workgroup_per_tile():
+    rows = (1 << 32) - 1                                                                # 2^24 row tiles x 128 query tiles = 2^31
+    assert N.lib().om_debug_scan_round(0, 32768, 768, rows, 256, (C.c_int64 * 8)()) == 1
+    assert b"scan grid too large" in N.lib().om_last_error()
+    assert scan_round(1, 32768, 768, rows)[0] == (WIDE7C, rows & ~255, 256, QGROUP8)    # persistent: the grid is the CUs
+
+
+def test_null_round_output_is_refused():
+    assert N.lib().om_debug_scan_round(1, 1, 768, 4096, 256, None) == 1
+    assert b"null argument" in N.lib().om_last_error()
