@@ -441,6 +441,21 @@ int om_debug_dropout(int dtype, const void* x, void* y, int64_t n, float p, uint
 int om_debug_ln_fold(int dtype, const void* W, const float* gamma, const float* beta, const float* b, void* Wf, float* colsum,
                      float* bf, int N, int K, void* stream);
 int om_debug_ln_stats_reduce(const float* slots, int nslots, int64_t M, float* out, void* stream);
+/* Test hooks of the remaining training kernels (tests/test_train_leftover_kernels.py), in the same manner: pointers and dtype checked,
+ * every argument forwarded.  om_debug_transpose: out[c][r] = op(in[r][c]) for r < R, zero for R <= r < Rp (op 0 copy, 1 erf-GELU);
+ * om_debug_transpose_batch: n dense transposes, 40 to a launch; om_debug_zero_rows_from: rows [*first, M) of a row-major tensor <- 0,
+ * `first` in device memory; the T5 feed-forward activation (kind 0 relu, 1 gelu_new(f) * f2) and its backward; the T5 embedding
+ * backward (ids clamped to [0, vocab - 1]; row_map NULL or a token per row of dy, < 0: the row is skipped); the relative-position bias
+ * gather out[h][q][k] = table[lut[k - q + L - 1]][h] and its backward dtable[lut[r]][h] += drel[h][r]. */
+int om_debug_transpose(int dtype, const void* in, int64_t ldi, int64_t R, int C, void* out, int64_t ldo, int64_t Rp, int op, void* stream);
+int om_debug_transpose_batch(int dtype, const void* const* in, void* const* out, const int* R, const int* C, int n, void* stream);
+int om_debug_zero_rows_from(void* p, int64_t row_bytes, const int* first, int64_t M, void* stream);
+int om_debug_t5_act_fwd(int dtype, const void* f, const void* f2, void* g, int64_t n, int kind, void* stream);
+int om_debug_t5_act_bwd(int dtype, const void* dg, const void* f, const void* f2, void* df, void* df2, int64_t n, int kind, void* stream);
+int om_debug_t5_embed_bwd(int dtype, const void* dy, const int64_t* ids, float* dword, int64_t M, int H, int vocab, const int* row_map,
+                          void* stream);
+int om_debug_t5_bias(const float* table, const int* lut, float* out, int L, int heads, void* stream);
+int om_debug_t5_bias_bwd(const float* drel, const int* lut, float* dtable, int L, int heads, void* stream);
 int om_kernel_timing_enable(int enable);
 int om_kernel_timing_read(int kernel_class, double* total_ms, int64_t* launches, double* flops);
 
@@ -462,7 +477,7 @@ int om_gemm_nt(int in_dtype, const void* A, int64_t lda, const void* B, int64_t 
  * ACCUMULATED into -- zero them first for a plain product).  Replaces autograd's
  * dW = dY^T X / db = sum(dY) of every nn.Linear under DRModel.forward + backward
  * (modeling/dense_retrieval_model.py:89-131).  Requires N % 128 == 0, K % 128 == 0,
- * lda / ldb multiples of 8, 16-byte aligned operands; bias may be NULL.
+ * lda / ldb multiples of 8 and below 2^25 elements, 16-byte aligned operands; bias may be NULL.
  * ------------------------------------------------------------------------ */
 int om_gemm_tn_acc(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb,
                    float* C, int64_t ldc, float* bias, int64_t M, int64_t N, int64_t K, void* stream);
@@ -479,6 +494,18 @@ typedef struct OmTnProblem {
   int64_t lda, ldb, ldc, N, K;
 } OmTnProblem;
 int om_gemm_tn_acc_batch(int in_dtype, const OmTnProblem* problems, int n, int64_t M, void* stream);
+/* Test hooks (tests/test_gemm_tn_kernels.py).  om_debug_gemm_tn_last: what the calling thread's last om_gemm_tn_acc or
+ * om_gemm_tn_acc_batch launched, eight words --
+ *   [0] bit mask: 1 the LDS-DMA kernel, 2 the register-staged kernel, 4 the 256 x 256 kernel; 0: nothing was launched (a refusal too)
+ *   om_gemm_tn_acc:        [1] rows of the DMA kernel  [2] its slices  [3] its 64-token steps per slice
+ *                          [4] rows of the register-staged kernel  [5] its slices  [6] its rows per slice  [7] 0
+ *   om_gemm_tn_acc_batch:  [1] whole 32-token steps  [2] 256 x 256 tiles over all problems  [3] tiles per XCD (chunk) of the last launch
+ *                          [4] launches (48 problems each)  [5] tail rows  [6] slices and [7] rows per slice of the last problem's tail
+ * om_debug_gemm_tn_plan: the same words for the call that WOULD be made at the current switches (OM_OPT_WGRAD_DEBUG) -- batch 0:
+ * om_gemm_tn_acc; batch n > 0: om_gemm_tn_acc_batch over n problems of this shape.  Returns 0, all words zero for an empty problem, -1
+ * for a refusal with its reason in om_last_error().  Host only: no GPU is touched and om_debug_gemm_tn_last keeps its value. */
+int om_debug_gemm_tn_last(int64_t out[8]);
+int om_debug_gemm_tn_plan(int dtype, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int batch, int64_t out[8]);
 
 /* ------------------------------------------------------------------------
  * Encoder forward:  ids -> hidden [B,L,H] -> pooled/head/normalised reps [B,D]

@@ -734,6 +734,11 @@ int omk_t5_bias(const float* table, const int* lut, float* out, int L, int heads
   OM_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int om_debug_t5_bias(const float* table, const int* lut, float* out, int L, int heads, void* stream) {
+  if (!table || !lut || !out) OM_FAIL("om_debug_t5_bias: null argument");
+  if (L < 1 || heads < 1) OM_FAIL("om_debug_t5_bias: L and heads must be at least 1");
+  return omk_t5_bias(table, lut, out, L, heads, (hipStream_t)stream);
+}
 
 extern "C" int om_index_to_f16(const float* rows_f32, int64_t N, int d, void* rows_f16,
                                float* stats, void* stream) {

@@ -20,8 +20,10 @@
 #include <string.h>
 
 #include <atomic>
+#include <string>
 
 #include "gemm_core7.h"
+#include "gemm_tn_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -499,58 +501,95 @@ __global__ __launch_bounds__(TN_THREADS, 1) void gemm_tn_wide_kernel(const TwBat
 }
 }  // namespace
 
-bool omk_gemm_tn_ok(int dtype, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
-  return (dtype == OM_BF16 || dtype == OM_F16) && M > 0 && N % 128 == 0 && K % 128 == 0 && lda % 8 == 0 && ldb % 8 == 0 && N <= (1 << 20) && K <= (1 << 20);
+// ---- what the calling thread's last om_gemm_tn_acc / om_gemm_tn_acc_batch launched (om_debug_gemm_tn_last) ---------------------------------
+// [0] bit mask: 1 gemm_tn_dma_kernel, 2 gemm_tn_kernel, 4 gemm_tn_wide_kernel; 0 after a call that launched nothing
+// single call:  [1] DMA rows  [2] DMA slices  [3] DMA steps per slice  [4] register-staged rows  [5] its slices  [6] its rows per slice
+// batch call:   [1] whole 32-token steps  [2] tiles (all problems)  [3] chunk of the last launch  [4] launches  [5] tail rows
+//               [6] slices  [7] rows per slice of the last problem's tail
+struct TnLast { int64_t v[8]; };
+static thread_local TnLast g_tn_last = {{0, 0, 0, 0, 0, 0, 0, 0}};
+extern "C" int om_debug_gemm_tn_last(int64_t out[8]) {
+  if (!out) OM_FAIL("om_debug_gemm_tn_last: null argument");
+  memcpy(out, g_tn_last.v, sizeof(g_tn_last.v));
+  return 0;
+}
+static void tn_plan_words(const TnPlan& p, bool batch, int64_t n, int64_t v[8]) {
+  for (int i = 0; i < 8; ++i) v[i] = 0;
+  if (batch) {
+    int64_t last = n % TN_PLAN_WIDE_MAXP ? n % TN_PLAN_WIDE_MAXP : TN_PLAN_WIDE_MAXP;      // n identical problems, 48 to a launch
+    v[0] = 4 | (p.tail_rows ? 2 : 0); v[1] = p.wide_steps; v[2] = n * p.wide_tiles; v[3] = tn_plan_chunk(last * p.wide_tiles);
+    v[4] = (n + TN_PLAN_WIDE_MAXP - 1) / TN_PLAN_WIDE_MAXP; v[5] = p.tail_rows; v[6] = p.reg_slices; v[7] = p.reg_per;
+  } else {
+    v[0] = (p.dma_rows ? 1 : 0) | (p.reg_rows ? 2 : 0);
+    v[1] = p.dma_rows; v[2] = p.dma_slices; v[3] = p.dma_steps; v[4] = p.reg_rows; v[5] = p.reg_slices; v[6] = p.reg_per;
+  }
+}
+// the shipped library keeps the selection bits of OM_OPT_WGRAD_DEBUG (3: register-staged kernel, >> 4: grid aim); bits 1 and 2 (plain stores
+// instead of atomics, one step of the token loop) BREAK the result: timing probes, honoured only in a probe build (python -m openmatch_amd._build --probe)
+static int tn_debug_word() {
+#ifdef OM_PROBE_KERNELS
+  return om_option(OM_OPT_WGRAD_DEBUG);
+#else
+  return om_option(OM_OPT_WGRAD_DEBUG) & ~6;
+#endif
+}
+// host only: what om_gemm_tn_acc (batch == 0) or om_gemm_tn_acc_batch over `batch` problems of this shape would launch at the current
+// switches, in the words of om_debug_gemm_tn_last; 0, all words zero, for an empty problem; -1 for a refusal (its reason in
+// om_last_error).  Touches no GPU and leaves om_debug_gemm_tn_last as it is.
+extern "C" int om_debug_gemm_tn_plan(int dtype, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int batch, int64_t out[8]) {
+  if (!out) OM_FAIL("om_debug_gemm_tn_plan: null argument");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (batch < 0) { om_set_error(std::string(__func__) + ": batch must be 0 (a single call) or a problem count"); return -1; }
+  if (M <= 0 || (!batch && (N <= 0 || K <= 0))) return 0;
+  const TnPlan p = tn_plan(dtype, M, N, K, lda, ldb, tn_debug_word(), batch != 0);
+  if (p.error) { om_set_error(std::string(__func__) + ": " + p.error); return -1; }
+  tn_plan_words(p, batch != 0, batch, out);
+  return 0;
 }
 
+bool omk_gemm_tn_ok(int dtype, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
+  return !tn_plan(dtype, M, N, K, lda, ldb, 0, false).error;
+}
+
+// the register-staged kernel over `slices` slices of `per` rows (tn_plan's reg_slices, reg_per)
 template <typename T>
 static int launch_tn_regs_t(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* bias, int64_t M,
-                          int64_t N, int64_t K, int dbg, hipStream_t s) {
+                          int64_t N, int64_t K, int64_t slices, int64_t per, int dbg, hipStream_t s) {
   const int64_t tiles = (N / 128) * (K / 128);
-  const int64_t steps = (M + TN_BM - 1) / TN_BM;
-  const int64_t want = (dbg >> 4) ? (dbg >> 4) * 64 : 320;             // workgroups: one round of two per CU, and no more --
-  int64_t slices = (want + tiles - 1) / tiles;                          // every workgroup flushes 16 384 memory-side atomics
-  if (slices > steps / 4) slices = steps / 4 > 0 ? steps / 4 : 1;       // at least 256 tokens per slice
-  const int64_t per = (steps + slices - 1) / slices;
-  slices = (steps + per - 1) / per;
   static std::atomic<bool> attr{false};
   if (!attr) {
     OM_HIP(hipFuncSetAttribute((const void*)gemm_tn_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS));
     attr = true;
   }
   hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)tiles, (unsigned)slices), dim3(TN_THREADS), TN_LDS, s, (const bf16_t*)A, lda,
-                     (const bf16_t*)B, ldb, C, ldc, bias, M, (int)N, (int)K, (int)(per * TN_BM), dbg);
+                     (const bf16_t*)B, ldb, C, ldc, bias, M, (int)N, (int)K, (int)per, dbg);
   OM_LAUNCH_CHECK();
+  g_tn_last.v[0] |= 2;
   return 0;
 }
 
 static int launch_tn_regs(int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* bias, int64_t M,
-                          int64_t N, int64_t K, int dbg, hipStream_t s) {
-  if (dtype == OM_F16) return launch_tn_regs_t<f16_t>(A, lda, B, ldb, C, ldc, bias, M, N, K, dbg, s);
-  return launch_tn_regs_t<bf16_t>(A, lda, B, ldb, C, ldc, bias, M, N, K, dbg, s);
+                          int64_t N, int64_t K, int64_t slices, int64_t per, int dbg, hipStream_t s) {
+  if (dtype == OM_F16) return launch_tn_regs_t<f16_t>(A, lda, B, ldb, C, ldc, bias, M, N, K, slices, per, dbg, s);
+  return launch_tn_regs_t<bf16_t>(A, lda, B, ldb, C, ldc, bias, M, N, K, slices, per, dbg, s);
 }
 
 int omk_gemm_tn(int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* bias,
                 int64_t M, int64_t N, int64_t K, hipStream_t s) {
-  if (!omk_gemm_tn_ok(dtype, M, N, K, lda, ldb)) OM_FAIL("gemm_tn: 16-bit operands with N and K multiples of 128 only");
+  g_tn_last = TnLast{{0, 0, 0, 0, 0, 0, 0, 0}};
+  const int dbg = tn_debug_word();
+  const TnPlan p = tn_plan(dtype, M, N, K, lda, ldb, dbg, false);
+  if (p.error) OM_FAIL(p.error);
   if (((uintptr_t)A & 15) || ((uintptr_t)B & 15)) OM_FAIL("gemm_tn: operands must be 16-byte aligned");
-  // bits 1 and 2 (plain stores instead of atomics, one step of the token loop) BREAK the result: timing probes, honoured only in a probe
-  // build (python -m openmatch_amd._build --probe); the shipped library keeps the selection bits (3: register-staged kernel, >> 4: grid aim)
-#ifdef OM_PROBE_KERNELS
-  const int dbg = om_option(OM_OPT_WGRAD_DEBUG);
-#else
-  const int dbg = om_option(OM_OPT_WGRAD_DEBUG) & ~6;
-#endif
   const bool timing = om_timing_on();
   if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
-  const int64_t whole = (dbg & 8) ? 0 : M / TN_BM;             // (dbg 8: the register-staged kernel for everything)
-  if (whole >= 8 && 64 * lda * 2 < (1ll << 31) && 64 * ldb * 2 < (1ll << 31)) {
+  TnLast note;
+  tn_plan_words(p, false, 0, note.v);
+  note.v[0] = 0;                                       // the mask is set launch by launch
+  g_tn_last = note;
+  if (p.dma_rows) {
     const int64_t tiles = (N / 128) * (K / 128);
-    const int64_t want = (dbg >> 4) ? (dbg >> 4) * 64 : 320;
-    int64_t slices = (want + tiles - 1) / tiles;
-    if (slices > whole / 4) slices = whole / 4 > 0 ? whole / 4 : 1;
-    const int64_t per = (whole + slices - 1) / slices;
-    slices = (whole + per - 1) / per;
+    const int64_t whole = p.dma_rows / TN_BM;
     static std::atomic<bool> attr{false};
     if (!attr) {
       OM_HIP(hipFuncSetAttribute((const void*)gemm_tn_dma_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TD_STAGE));
@@ -558,23 +597,25 @@ int omk_gemm_tn(int dtype, const void* A, int64_t lda, const void* B, int64_t ld
       attr = true;
     }
     if (dtype == OM_F16)
-      hipLaunchKernelGGL(gemm_tn_dma_kernel<f16_t>, dim3((unsigned)tiles, (unsigned)slices), dim3(TN_THREADS), 2 * TD_STAGE, s, (const bf16_t*)A, lda,
-                         (const bf16_t*)B, ldb, C, ldc, bias, (int)N, (int)K, (int)per, (int)whole, dbg);
+      hipLaunchKernelGGL(gemm_tn_dma_kernel<f16_t>, dim3((unsigned)tiles, (unsigned)p.dma_slices), dim3(TN_THREADS), 2 * TD_STAGE, s, (const bf16_t*)A, lda,
+                         (const bf16_t*)B, ldb, C, ldc, bias, (int)N, (int)K, (int)p.dma_steps, (int)whole, dbg);
     else
-      hipLaunchKernelGGL(gemm_tn_dma_kernel<bf16_t>, dim3((unsigned)tiles, (unsigned)slices), dim3(TN_THREADS), 2 * TD_STAGE, s, (const bf16_t*)A, lda,
-                         (const bf16_t*)B, ldb, C, ldc, bias, (int)N, (int)K, (int)per, (int)whole, dbg);
+      hipLaunchKernelGGL(gemm_tn_dma_kernel<bf16_t>, dim3((unsigned)tiles, (unsigned)p.dma_slices), dim3(TN_THREADS), 2 * TD_STAGE, s, (const bf16_t*)A, lda,
+                         (const bf16_t*)B, ldb, C, ldc, bias, (int)N, (int)K, (int)p.dma_steps, (int)whole, dbg);
     OM_LAUNCH_CHECK();
-    const int64_t done = whole * TN_BM;
-    if (M > done && launch_tn_regs(dtype, (const bf16_t*)A + done * lda, lda, (const bf16_t*)B + done * ldb, ldb, C, ldc, bias, M - done, N, K, dbg, s)) return 1;
-  } else if (launch_tn_regs(dtype, A, lda, B, ldb, C, ldc, bias, M, N, K, dbg, s)) {
-    return 1;
+    g_tn_last.v[0] |= 1;
   }
+  const int64_t done = p.dma_rows;
+  if (p.reg_rows && launch_tn_regs(dtype, (const bf16_t*)A + done * lda, lda, (const bf16_t*)B + done * ldb, ldb, C, ldc, bias, p.reg_rows, N, K,
+                                   p.reg_slices, p.reg_per, dbg, s))
+    return 1;
   if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, 2.0 * (double)M * (double)N * (double)K);
   return 0;
 }
 
 extern "C" int om_gemm_tn_acc(int in_dtype, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc,
                               float* bias, int64_t M, int64_t N, int64_t K, void* stream) {
+  g_tn_last = TnLast{{0, 0, 0, 0, 0, 0, 0, 0}};
   if (!A || !B || !C) OM_FAIL("null argument");
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   return omk_gemm_tn(in_dtype, A, lda, B, ldb, C, ldc, bias, M, N, K, (hipStream_t)stream);
@@ -582,18 +623,20 @@ extern "C" int om_gemm_tn_acc(int in_dtype, const void* A, int64_t lda, const vo
 
 // ---- batched launch ----------------------------------------------------------------------------------------------------------
 bool omk_gemm_tn_batch_ok(int dtype, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
-  return (dtype == OM_BF16 || dtype == OM_F16) && M >= TW_TOK && N % 256 == 0 && K % 256 == 0 && lda % 8 == 0 && ldb % 8 == 0 && N <= (1 << 20) &&
-         K <= (1 << 20) && (int64_t)TW_TOK * lda * 2 < (1ll << 31) && (int64_t)TW_TOK * ldb * 2 < (1ll << 31);
+  return !tn_plan(dtype, M, N, K, lda, ldb, 0, true).error;
 }
 
 int omk_gemm_tn_batch(int dtype, const OmTnProblem* probs, int n, int64_t M, hipStream_t s) {
+  g_tn_last = TnLast{{0, 0, 0, 0, 0, 0, 0, 0}};
   if (n <= 0 || M <= 0) return 0;
   if (!probs) OM_FAIL("gemm_tn_batch: null problem list");
+  TnPlan tail = {nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = 0; i < n; ++i) {
     const OmTnProblem& q = probs[i];
     if (!q.A || !q.B || !q.C) OM_FAIL("gemm_tn_batch: null operand");
-    if (!omk_gemm_tn_batch_ok(dtype, M, q.N, q.K, q.lda, q.ldb) || q.ldc > 0x7fffffffLL)
-      OM_FAIL("gemm_tn_batch: 16-bit operands with N and K multiples of 256 and at least 32 tokens only");
+    tail = tn_plan(dtype, M, q.N, q.K, q.lda, q.ldb, 0, true);
+    if (tail.error) OM_FAIL(tail.error);
+    if (q.ldc > 0x7fffffffLL) OM_FAIL("gemm_tn_batch: 16-bit operands with N and K multiples of 256 and at least 32 tokens only");
     if (((uintptr_t)q.A & 15) || ((uintptr_t)q.B & 15)) OM_FAIL("gemm_tn_batch: operands must be 16-byte aligned");
   }
   static std::atomic<bool> attr{false};
@@ -603,7 +646,8 @@ int omk_gemm_tn_batch(int dtype, const OmTnProblem* probs, int n, int64_t M, hip
     attr = true;
   }
   const bool timing = om_timing_on();
-  const int64_t whole = M / TW_TOK;
+  const int64_t whole = tail.wide_steps;                 // M / 32: the same for every problem
+  g_tn_last.v[1] = whole; g_tn_last.v[5] = tail.tail_rows;
   for (int first = 0; first < n; first += TW_MAXP) {
     const int cnt = n - first < TW_MAXP ? n - first : TW_MAXP;
     TwBatch bt;
@@ -622,11 +666,12 @@ int omk_gemm_tn_batch(int dtype, const OmTnProblem* probs, int n, int64_t M, hip
     }
     bt.tile_start[cnt] = (int)total;
     bt.total = (int)total;
-    bt.chunk = (int)((total + 7) / 8);
+    bt.chunk = (int)tn_plan_chunk(total);
     if (timing) om_timing_begin(OM_TIMING_GEMM_BF16, s);
     if (dtype == OM_F16) hipLaunchKernelGGL(gemm_tn_wide_kernel<f16_t>, dim3((unsigned)(bt.chunk * 8)), dim3(TN_THREADS), TW_STAGES * TW_STAGE, s, bt);
     else hipLaunchKernelGGL(gemm_tn_wide_kernel<bf16_t>, dim3((unsigned)(bt.chunk * 8)), dim3(TN_THREADS), TW_STAGES * TW_STAGE, s, bt);
     OM_LAUNCH_CHECK();
+    g_tn_last.v[0] |= 4; g_tn_last.v[2] += total; g_tn_last.v[3] = bt.chunk; g_tn_last.v[4] += 1;
     if (timing) om_timing_end(OM_TIMING_GEMM_BF16, s, flops * (double)(whole * TW_TOK) / (double)M);
   }
   // tokens past the last whole 32-token step: the split kernels above (atomics; ordered behind the launch on the stream)
@@ -634,8 +679,10 @@ int omk_gemm_tn_batch(int dtype, const OmTnProblem* probs, int n, int64_t M, hip
   if (M > done) {
     for (int i = 0; i < n; ++i) {
       const OmTnProblem& q = probs[i];
+      const TnPlan p = tn_plan(dtype, M, q.N, q.K, q.lda, q.ldb, 0, true);
       if (launch_tn_regs(dtype, (const bf16_t*)q.A + done * q.lda, q.lda, (const bf16_t*)q.B + done * q.ldb, q.ldb, q.C, q.ldc, q.bias,
-                         M - done, q.N, q.K, 0, s)) return 1;
+                         p.reg_rows, q.N, q.K, p.reg_slices, p.reg_per, 0, s)) return 1;
+      g_tn_last.v[6] = p.reg_slices; g_tn_last.v[7] = p.reg_per;
     }
   }
   return 0;

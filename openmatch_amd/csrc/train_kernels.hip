@@ -98,6 +98,23 @@ int omk_transpose_batch(int dtype, const void* const* in, void* const* out, cons
   return 0;
 }
 
+// ---- test hooks of the transposes (include/openmatch_hip.h): argument checks, then the launcher as it is ----
+#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+extern "C" int om_debug_transpose(int dtype, const void* in, int64_t ldi, int64_t R, int C, void* out, int64_t ldo, int64_t Rp, int op,
+                                  void* stream) {
+  if (!in || !out) OM_FAIL("om_debug_transpose: null argument");
+  OM_DBG_DTYPE("om_debug_transpose");
+  return omk_transpose(dtype, in, ldi, R, C, out, ldo, Rp, op, (hipStream_t)stream);
+}
+extern "C" int om_debug_transpose_batch(int dtype, const void* const* in, void* const* out, const int* R, const int* C, int n, void* stream) {
+  if (n > 0 && (!in || !out || !R || !C)) OM_FAIL("om_debug_transpose_batch: null argument");
+  OM_DBG_DTYPE("om_debug_transpose_batch");
+  for (int i = 0; i < n; ++i)
+    if (R[i] > 0 && C[i] > 0 && (!in[i] || !out[i])) OM_FAIL("om_debug_transpose_batch: null argument");
+  return omk_transpose_batch(dtype, in, out, R, C, n, (hipStream_t)stream);
+}
+#undef OM_DBG_DTYPE
+
 // out[c] += sum_r x[r][c]      (out is f32 and zero-initialised by the caller)
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, int64_t ld, int64_t M,
@@ -577,6 +594,11 @@ int omk_zero_rows_from(void* p, int64_t row_bytes, const int* first, int64_t M, 
   hipLaunchKernelGGL(zero_rows_from_kernel, dim3((unsigned)(M < 512 ? M : 512)), dim3(256), 0, s, (char*)p, row_bytes, first, M);
   OM_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int om_debug_zero_rows_from(void* p, int64_t row_bytes, const int* first, int64_t M, void* stream) {
+  if (!p || !first) OM_FAIL("om_debug_zero_rows_from: null argument");
+  return omk_zero_rows_from(p, row_bytes, first, M, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1427,3 +1449,30 @@ int omk_t5_bias_bwd(const float* drel, const int* lut, float* dtable, int L, int
   OM_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- test hooks of the T5 kernels (include/openmatch_hip.h): argument checks, then the launcher as it is ----
+#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+extern "C" int om_debug_t5_act_fwd(int dtype, const void* f, const void* f2, void* g, int64_t n, int kind, void* stream) {
+  if (!f || !g || (kind && !f2)) OM_FAIL("om_debug_t5_act_fwd: null argument");
+  OM_DBG_DTYPE("om_debug_t5_act_fwd");
+  return omk_t5_act_fwd(dtype, f, f2, g, n, kind, (hipStream_t)stream);
+}
+extern "C" int om_debug_t5_act_bwd(int dtype, const void* dg, const void* f, const void* f2, void* df, void* df2, int64_t n, int kind,
+                                   void* stream) {
+  if (!dg || !f || !df || (kind && (!f2 || !df2))) OM_FAIL("om_debug_t5_act_bwd: null argument");
+  OM_DBG_DTYPE("om_debug_t5_act_bwd");
+  return omk_t5_act_bwd(dtype, dg, f, f2, df, df2, n, kind, (hipStream_t)stream);
+}
+extern "C" int om_debug_t5_embed_bwd(int dtype, const void* dy, const int64_t* ids, float* dword, int64_t M, int H, int vocab,
+                                     const int* row_map, void* stream) {
+  if (!dy || !ids || !dword) OM_FAIL("om_debug_t5_embed_bwd: null argument");
+  OM_DBG_DTYPE("om_debug_t5_embed_bwd");
+  if (H < 1 || vocab < 1) OM_FAIL("om_debug_t5_embed_bwd: H and vocab must be at least 1");
+  return omk_t5_embed_bwd(dtype, dy, ids, dword, M, H, vocab, (hipStream_t)stream, row_map);
+}
+extern "C" int om_debug_t5_bias_bwd(const float* drel, const int* lut, float* dtable, int L, int heads, void* stream) {
+  if (!drel || !lut || !dtable) OM_FAIL("om_debug_t5_bias_bwd: null argument");
+  if (L < 1 || heads < 1) OM_FAIL("om_debug_t5_bias_bwd: L and heads must be at least 1");
+  return omk_t5_bias_bwd(drel, lut, dtable, L, heads, (hipStream_t)stream);
+}
+#undef OM_DBG_DTYPE

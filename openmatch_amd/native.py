@@ -20,6 +20,7 @@ ARCH_BERT, ARCH_T5, ARCH_MODERNBERT, ARCH_CAUSAL, ARCH_NOMICBERT, ARCH_GEMMA3 = 
 POOL_NONE, POOL_FIRST, POOL_MEAN, POOL_LAST = 0, 1, 2, 3
 # om_debug_option switches used from Python (include/openmatch_hip.h: OM_OPT_*)
 OPT_TRAIN_WGRAD_BATCH, OPT_GEMM_MAX_GRID, OPT_GEMM_CONT = 14, 15, 16
+OPT_WGRAD_DEBUG = 5              # bit 3: the register-staged weight-gradient kernel for everything; value >> 4: workgroups aimed at / 64
 OPT_GEMM_GROUP_M, OPT_GEMM_VARIANT, OPT_GEMM_SKINNY_M = 6, 12, 19
 # om_debug_gemm_last codes (include/openmatch_hip.h: OM_GEMM_FAMILY_*)
 GEMM_FAMILY = {"v1": 1, "v2": 2, "v6": 6, "g7": 7, "g7_one_tile": 70, "7c16": 71, "7r16": 72, "skinny": 9}
@@ -256,6 +257,16 @@ _SIGNATURES = {
     "om_gemm_tn_acc": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                c_int64, c_int64, c_int64, c_void_p]),
     "om_gemm_tn_acc_batch": (c_int, [c_int, C.POINTER(OmTnProblem), c_int, c_int64, c_void_p]),
+    "om_debug_gemm_tn_last": (c_int, [C.POINTER(c_int64)]),
+    "om_debug_gemm_tn_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, C.POINTER(c_int64)]),
+    "om_debug_transpose": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "om_debug_transpose_batch": (c_int, [c_int, C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), c_int, c_void_p]),
+    "om_debug_zero_rows_from": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "om_debug_t5_act_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "om_debug_t5_act_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "om_debug_t5_embed_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "om_debug_t5_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "om_debug_t5_bias_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "om_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64]),
     "om_t5_decoder_workspace_bytes": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64]),
     "om_t5_decoder_step": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmT5DecoderWeights), c_void_p, c_void_p,

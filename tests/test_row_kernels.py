@@ -74,8 +74,9 @@ kernel's order, rounded to the storage type); worst error / bound of each at the
 
 Measured constants: see RSQRT_MEASURED and DIVSQRT_MEASURED below.
 
-Still untested at kernel level (whole-model tests only): the transposes (omk_transpose, omk_transpose_batch), the T5 activation,
-embedding and bias kernels, omk_zero_rows_from and the GEMM epilogue's dropout.
+What this list used to name as untested at kernel level now has its tests: the transposes (omk_transpose, omk_transpose_batch), the T5 activation,
+embedding and bias kernels and omk_zero_rows_from are in tests/test_train_leftover_kernels.py, the weight-gradient contractions in
+tests/test_gemm_tn_kernels.py, the GEMM epilogue's dropout in tests/test_gemm_epilogues.py (test_dropout_residual, test_pre_act).
 """
 import ctypes as C
 import math
