@@ -79,6 +79,8 @@ extern "C" {
 /* search precision */
 #define OM_SEARCH_F32 0           /* exact f32 MFMA scan                                   */
 #define OM_SEARCH_F16_RESCORE 1   /* f16 MFMA candidate scan + exact f32 re-score (same ids)  */
+#define OM_SEARCH_F16_ONLY 2      /* the float16 rows ARE the index (2 bytes per element): the same scan, the re-score and the
+                                   * on-device redo read the float16 rows; index_f32 is not read and may be NULL */
 
 const char* om_last_error(void);
 int om_abi_version(void);
@@ -974,11 +976,22 @@ int om_loss_scale_update(const float* gnorm_sq, float* state4, int growth_interv
 /* index.add(): make the 16-bit shadow copy of rows [0,N) and accumulate the rounding
  * statistics the certified candidate margin needs.  The shadow is IEEE f16, not bf16: same
  * MFMA rate, 8x smaller rounding error, which is what keeps the certified margin (and with it
- * the candidate lists) narrow on anisotropic embedding sets.
+ * the candidate lists) narrow on anisotropic embedding sets.  (OM_SEARCH_F16_ONLY keeps no float32 rows at all: om_index_add_f16.)
  * stats: device float[2] = {max_i ||p_i - f16(p_i)||_2 , max_i ||f16(p_i)||_2}, updated with
  * max (initialise to 0 before the first add; +inf if a value overflows f16 -> f32 scan). */
 int om_index_to_f16(const float* rows_f32, int64_t N, int d, void* rows_f16, float* stats,
                     void* stream);
+
+/* index.add() of a float16-only index (OM_SEARCH_F16_ONLY): rows [N, d] in in_dtype -- OM_F32: rounded to nearest even, the bits of
+ * torch.Tensor.half(); OM_F16: copied bit for bit -- stored to rows_f16 [N, d].  No float32 copy is made or needed.
+ * stats: device float[2] as above; stats[1] is max-updated with the 2-norm of the STORED float16 rows (the reduction om_index_to_f16 uses:
+ * the same values leave the same word), stats[0] is never written and stays 0 -- the rows carry no rounding error against themselves, so
+ * the certified margin keeps only the query-rounding term ||q - f16(q)|| * stats[1] and the accumulation slop.
+ * nonfinite: device unsigned, not NULL; the number of stored values that are inf or NaN (a float32 input beyond +-65504 rounds to inf) is
+ * ADDED to it: zero it before the call, read it after the stream has passed.  A non-finite row leaves stats[1] inf or NaN, which no
+ * margin certifies.  One wave per row; 16-byte accesses when d % 8 == 0 and both planes are 16-byte aligned.  rows and rows_f16 must
+ * not overlap. */
+int om_index_add_f16(int in_dtype, const void* rows, int64_t N, int d, void* rows_f16, float* stats, unsigned* nonfinite, void* stream);
 
 size_t om_sim_topk_workspace_bytes(int64_t n_queries, int d, int k);
 
@@ -990,7 +1003,14 @@ size_t om_sim_topk_workspace_bytes(int64_t n_queries, int d, int k);
  * NOT stream-ordered for the host: om_sim_topk synchronises `stream` ONCE per call (it reads the
  * overflow flags back at the end of its fast schedule; more often on the rare careful path), so
  * it blocks its caller, cannot be captured in a graph and cannot overlap a second search of the
- * same thread.  om_sim_topk_async below is the entry that only enqueues. */
+ * same thread.  om_sim_topk_async below is the entry that only enqueues.
+ * mode OM_SEARCH_F16_ONLY: the exact top-k of <q, widen(index_f16)> with float32 queries -- bit for bit what OM_SEARCH_F16_RESCORE
+ * returns over index_f32 = widen(index_f16) when it took no float32 retry.  index_f32 is not read and may be NULL; index_f16 and stats
+ * (om_index_add_f16) are required.  There is no float32 plane to retry on: the entry enqueues om_sim_topk_async's chain -- certified
+ * scan, re-score from the float16 rows, on-device redo of every query with an overflowed list, a too-wide or non-finite margin or a list
+ * beyond the re-score's cover -- and synchronises once.  It needs the workspace of om_sim_topk_async_workspace_bytes, and like that
+ * entry it refuses d > 16384 and OM_OPT_SCAN_GEN7 = 0.  A redone query costs seven passes over the index on the VALU per block of
+ * queries -- far more than the float32 scan the two-copy mode falls back to; om_sim_topk_info [4] and [7] tell when it was paid. */
 int om_sim_topk(int mode, const float* queries, int64_t n_queries, const float* index_f32,
                 const void* index_f16, const float* stats, int64_t N, int d, int k,
                 int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
@@ -1008,7 +1028,9 @@ int om_sim_topk(int mode, const float* queries, int64_t n_queries, const float* 
  * [4] queries whose certified margin was too wide, [5] OM_SCAN_FAMILY_* of the last filtered round, [6] 1, written last (0 from the
  * start of the chain), [7] 0.  Refuses when OM_OPT_SCAN_GEN7 = 0 has switched the fast schedule off, and d > 16384.
  * workspace: om_sim_topk_async_workspace_bytes (>= om_sim_topk_workspace_bytes; 0 for n_queries <= 0), 256-byte aligned, owned by the
- * call until the stream has passed it: two searches in flight need two workspaces.  om_sim_topk_info is not touched. */
+ * call until the stream has passed it: two searches in flight need two workspaces.  om_sim_topk_info is not touched.
+ * mode OM_SEARCH_F16_ONLY: as described at om_sim_topk; the chain is this one with the re-score and the redo reading the float16 rows,
+ * status[0] = 1, and the two refusals above name the mode. */
 size_t om_sim_topk_async_workspace_bytes(int64_t n_queries, int d, int k);
 int om_sim_topk_async(int mode, const float* queries, int64_t n_queries, const float* index_f32,
                       const void* index_f16, const float* stats, int64_t N, int d, int k,
@@ -1018,6 +1040,14 @@ int om_sim_topk_async(int mode, const float* queries, int64_t n_queries, const f
  * first 4096 rows, *n filtered rounds; chunks[i], i < min(*n, cap), is the number of rows of round i, the first of which starts at row
  * 4096.  N <= 4096 has no rounds.  mode: OM_SEARCH_*; under the calling thread's switches (OM_OPT_SCAN_GROWTH). */
 int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* chunks, int cap, int* n);
+/* The row-typed kernels of the re-score and the redo over a caller's candidates, without a search: rows [N, d] in row_dtype (OM_F32 |
+ * OM_F16), queries [n_queries, d] f32, cand [n_queries][m] row numbers (uint32, device; repeats allowed; a number >= N is not followed and
+ * scores NaN), out_scores [n_queries][m] f32.  kernel 0: rescore_kernel, 1: rescore_strided_kernel -- out[q][j] = <query q, row cand[q][j]>;
+ * 2: the redo's collect pass over ALL rows (cand is not read and may be NULL, m must be N <= 8192) -- out[q][r] = <query q, row r>.
+ * The float16 and the float32 form return the same bits on rows that hold the same values.  d a multiple of 64, at most 16384;
+ * workspace: om_sim_topk_async_workspace_bytes(n_queries, d, 1), 256-byte aligned. */
+int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows, int64_t N, int d, const float* queries, int64_t n_queries,
+                          const uint32_t* cand, int m, float* out_scores, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Diagnostics of the calling thread's last om_sim_topk: out[0] = scan precision that produced
  * the result (0 f32, 1 f16+rescore), [1] = scan rounds, [2] = overflow fallbacks (chunks redone
@@ -1025,7 +1055,9 @@ int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* ch
  * the call fell back to the f32 scan, [5] = OM_SCAN_FAMILY_* of the last filtered-scan round
  * (0: every row was scored densely), [6] = OM_SCAN_KERNEL_* of that round's main launch (its tail's
  * where the round held no whole tile; 0: every row was scored densely), [7] = 0.  Written by
- * om_sim_topk alone, on every return behind its argument checks. */
+ * om_sim_topk alone, on every return behind its argument checks.
+ * OM_SEARCH_F16_ONLY: [0] = 1, [2] = 0 (nothing is ever started over), [4] = the NUMBER of queries whose certified margin was too wide
+ * (they were redone on the device, there is no float32 scan), [7] = queries redone on the device for any reason. */
 void om_sim_topk_info(int64_t out[8]);
 
 /* Which kernel a filtered-scan round of om_sim_topk runs (csrc/search_plan.h scan_plan: no launch, no HIP call, no pointer read). */

@@ -337,8 +337,74 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void index_to_f16_kernel(
   }
 }
 
+// index.add() of a float16-only index (OM_SEARCH_F16_ONLY): the stored rows from float32 (round to nearest even) or float16 (bit for bit)
+// input, one wave per row, one pass.  VEC: 16-byte accesses, eight values per lane and step (d % 8 == 0, both planes 16-byte aligned).
+// The row norm of the STORED values is summed as index_to_f16_kernel sums it -- lane l adds columns l, l + 64, ... in that order -- so the
+// same values leave the same stats[1] there and here: the vector path passes each 512-column step through a wave-private LDS slice to get
+// from "eight consecutive columns per lane" to that order.  stats[0] is not written: the rows carry no rounding error against themselves.
+#define ADD16_STEP 512      // columns of one vector step: 64 lanes x 8
+template <typename TIn, bool VEC>
+__global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void index_add_f16_kernel(
+    const TIn* __restrict__ x, f16_t* __restrict__ y, int64_t N, int d, unsigned* stats, unsigned* nonfinite) {
+  __shared__ __attribute__((aligned(16))) f16_t stage[ROWS_PER_BLOCK][ADD16_STEP];
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+  if (row >= N) return;                    // (a whole wave: nothing below synchronises across waves)
+  const TIn* xr = x + row * d;
+  f16_t* yr = y + row * d;
+  float n2 = 0.f;
+  float bad = 0.f;                         // stored values that are inf or NaN (a float: wave_sum adds it; at most d / 64 + 7 per lane)
+  auto note = [&](f16_t r) { bad += ((__builtin_bit_cast(unsigned short, r) & 0x7c00u) == 0x7c00u) ? 1.f : 0.f; };
+  if (VEC) {
+    f16_t* st = stage[threadIdx.x >> 6];
+    for (int c0 = 0; c0 < d; c0 += ADD16_STEP) {       // (wave-uniform trip count)
+      const int c = c0 + lane * 8;
+      if (c < d) {
+        f16x8_t h;
+        if constexpr (sizeof(TIn) == 4) {
+          const float4 a = *(const float4*)(xr + c), b = *(const float4*)(xr + c + 4);
+          h[0] = (f16_t)a.x; h[1] = (f16_t)a.y; h[2] = (f16_t)a.z; h[3] = (f16_t)a.w;
+          h[4] = (f16_t)b.x; h[5] = (f16_t)b.y; h[6] = (f16_t)b.z; h[7] = (f16_t)b.w;
+        } else {
+          h = *(const f16x8_t*)(xr + c);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) note(h[i]);
+        *(f16x8_t*)(yr + c) = h;
+        *(f16x8_t*)(st + lane * 8) = h;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the slice is this wave's alone: its own writes, then its own reads
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int i = 0; i < ADD16_STEP / 64; ++i)
+        if (c0 + lane + 64 * i < d) {
+          const float rv = (float)st[lane + 64 * i];
+          n2 += rv * rv;
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // read before the next step overwrites it
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  } else {
+    for (int c = lane; c < d; c += 64) {
+      const f16_t r = (f16_t)xr[c];
+      const float rv = (float)r;
+      note(r);
+      yr[c] = r;
+      n2 += rv * rv;
+    }
+  }
+  n2 = wave_sum(n2); bad = wave_sum(bad);
+  if (lane == 0) {
+    const unsigned un = __float_as_uint(sqrtf(n2) * 1.0001f);
+    if (un > stats[1]) atomicMax(stats + 1, un);      // (inf or NaN of a non-finite row orders above every norm: no margin certifies then)
+    if (bad != 0.f) atomicAdd(nonfinite, (unsigned)bad);
+  }
+}
+
 // ---- host launchers ---------------------------------------------------------
-static thread_local int g_row_last = 0;      // the OM_ROW_* word of this thread's last normalisation launch (include/openmatch_hip.h)
+static thread_local int g_row_last = 0;     // the OM_ROW_* word of this thread's last normalisation launch (include/openmatch_hip.h)
 void omk_row_note(int word) { g_row_last = word; }
 extern "C" int om_debug_row_kernel_last(void) { return g_row_last; }
 template <typename T> constexpr int row_dt() { return sizeof(T) == 4 ? OM_F32 : (std::is_same<T, bf16_t>::value ? OM_BF16 : OM_F16); }
@@ -746,6 +812,30 @@ extern "C" int om_index_to_f16(const float* rows_f32, int64_t N, int d, void* ro
   const unsigned grid = (unsigned)((N + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   hipLaunchKernelGGL(index_to_f16_kernel, dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0,
                      (hipStream_t)stream, rows_f32, (f16_t*)rows_f16, N, d, (unsigned*)stats);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int om_index_add_f16(int in_dtype, const void* rows, int64_t N, int d, void* rows_f16, float* stats, unsigned* nonfinite,
+                                void* stream) {
+  if (in_dtype != OM_F32 && in_dtype != OM_F16) OM_FAIL("om_index_add_f16: in_dtype must be OM_F32 or OM_F16");
+  if (N <= 0) return 0;
+  if (!rows || !rows_f16 || !stats || !nonfinite) OM_FAIL("om_index_add_f16: null argument");
+  if (d < 1) OM_FAIL("om_index_add_f16: d must be at least 1");
+  if (N > 0x7fffffffLL * ROWS_PER_BLOCK) OM_FAIL("om_index_add_f16: too many rows for one call");
+  const unsigned grid = (unsigned)((N + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+  const bool vec = d % 8 == 0 && (((uintptr_t)rows | (uintptr_t)rows_f16) & 15) == 0;
+  const dim3 block(64 * ROWS_PER_BLOCK);
+  const hipStream_t s = (hipStream_t)stream;
+  f16_t* y = (f16_t*)rows_f16;
+  unsigned* st = (unsigned*)stats;
+  if (in_dtype == OM_F32) {
+    if (vec) hipLaunchKernelGGL((index_add_f16_kernel<float, true>), dim3(grid), block, 0, s, (const float*)rows, y, N, d, st, nonfinite);
+    else hipLaunchKernelGGL((index_add_f16_kernel<float, false>), dim3(grid), block, 0, s, (const float*)rows, y, N, d, st, nonfinite);
+  } else {
+    if (vec) hipLaunchKernelGGL((index_add_f16_kernel<f16_t, true>), dim3(grid), block, 0, s, (const f16_t*)rows, y, N, d, st, nonfinite);
+    else hipLaunchKernelGGL((index_add_f16_kernel<f16_t, false>), dim3(grid), block, 0, s, (const f16_t*)rows, y, N, d, st, nonfinite);
+  }
   OM_LAUNCH_CHECK();
   return 0;
 }

@@ -1240,11 +1240,20 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
 
 // The exact f32 score of the re-score and of the on-device redo: each lane's fmaf chain over columns c = lane * 4, step 256, then the
 // butterfly sum -- every lane returns the same value, and the same (query, row) gives the same bits wherever it is computed.
-__device__ __forceinline__ float rescore_dot(const float* __restrict__ qv, const float* __restrict__ pv, int d, int lane) {
+// TRow: the row's storage, float or f16_t (OM_SEARCH_F16_ONLY: one 8-byte load of four halves, widened -- exactly -- to float32; the
+// column -> lane map and the chain are the float32 form's, so a float16 row and a float32 row holding the same values give the same bits).
+__device__ __forceinline__ float4 rescore_load4(const float* __restrict__ p) { return *(const float4*)p; }
+__device__ __forceinline__ float4 rescore_load4(const f16_t* __restrict__ p) {
+  typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+  const f16x4_t h = *(const f16x4_t*)p;
+  return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+}
+template <typename TRow>
+__device__ __forceinline__ float rescore_dot(const float* __restrict__ qv, const TRow* __restrict__ pv, int d, int lane) {
   float acc = 0.f;
   for (int c = lane * 4; c < d; c += 256) {
     const float4 a = *(const float4*)(qv + c);
-    const float4 b = *(const float4*)(pv + c);
+    const float4 b = rescore_load4(pv + c);
     acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc);
     acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
   }
@@ -1252,8 +1261,9 @@ __device__ __forceinline__ float rescore_dot(const float* __restrict__ qv, const
 }
 
 // exact f32 re-score of every surviving candidate: one wavefront per (query, slot)
+template <typename TRow>
 __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ q,
-                                                      const float* __restrict__ index,
+                                                      const TRow* __restrict__ index,
                                                       u64* __restrict__ keys,
                                                       const unsigned* __restrict__ cnt, int d) {
   const int64_t qi = blockIdx.y;
@@ -1270,7 +1280,8 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
 // nq x cover workgroups sized for the longest list the estimate allows would launch millions of empty ones).  Work item (query, j) is
 // the slots j, j + RESCORE_SPLIT, ... < cnt[query]; the grid's wavefronts stride over the items.
 #define RESCORE_SPLIT 32
-__global__ __launch_bounds__(256) void rescore_strided_kernel(const float* __restrict__ q, const float* __restrict__ index,
+template <typename TRow>
+__global__ __launch_bounds__(256) void rescore_strided_kernel(const float* __restrict__ q, const TRow* __restrict__ index,
                                                               u64* __restrict__ keys, const unsigned* __restrict__ cnt, int64_t nq, int d) {
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -1338,7 +1349,7 @@ __global__ void async_init_kernel(unsigned* __restrict__ qstat, unsigned* __rest
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q < nq) qstat[q] = 0;
   if (q < 16) rs[q] = 0;
-  if (q < 8) status[q] = 0;                      // status[6] turns 1 when the chain has finished
+  if (status && q < 8) status[q] = 0;            // status[6] turns 1 when the chain has finished (nullptr: om_sim_topk in OM_SEARCH_F16_ONLY reads flag / rs itself)
 }
 
 __global__ void redo_compact_kernel(const unsigned* __restrict__ qstat, int64_t nq, unsigned* __restrict__ rs, unsigned* __restrict__ bad) {
@@ -1361,8 +1372,10 @@ __global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restr
 
 // COLLECT = false: hist[b][digit at `shift`] += 1 for every row whose key agrees with prefix[b] above the digit;
 // COLLECT = true: every key >= prefix[b] (= T) appended to list bad[b].  Rows [0, N) of `index`, tiles of R rows (R * d * 4 bytes of LDS).
-template <bool COLLECT>
-__global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict__ q32, const float* __restrict__ index, int64_t N, int d, int R,
+// TRow = f16_t (OM_SEARCH_F16_ONLY): the tile is filled from 16-byte loads of eight halves and staged WIDENED to float32, so R, the LDS
+// bytes and the scoring loop are those of the float32 rows.
+template <bool COLLECT, typename TRow>
+__global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict__ q32, const TRow* __restrict__ index, int64_t N, int d, int R,
                                                         const unsigned* __restrict__ rs, const unsigned* __restrict__ bad,
                                                         const u64* __restrict__ prefix, unsigned* __restrict__ hist, int shift, int width,
                                                         u64* __restrict__ keys, unsigned* __restrict__ cnt) {
@@ -1377,8 +1390,17 @@ __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict_
     const int64_t r0 = t * R;
     const int nr = (int)(N - r0 < R ? N - r0 : R);
     __syncthreads();                              // the tile before has been read
-    const float4* src = (const float4*)(index + r0 * d);
-    for (int i = tid; i < nr * (d / 4); i += 256) ((float4*)tile)[i] = src[i];
+    if constexpr (sizeof(TRow) == 4) {
+      const float4* src = (const float4*)(index + r0 * d);
+      for (int i = tid; i < nr * (d / 4); i += 256) ((float4*)tile)[i] = src[i];
+    } else {
+      const f16x8_t* src = (const f16x8_t*)(index + r0 * d);
+      for (int i = tid; i < nr * (d / 8); i += 256) {
+        const f16x8_t h = src[i];
+        ((float4*)tile)[2 * i] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+        ((float4*)tile)[2 * i + 1] = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
+      }
+    }
     __syncthreads();
     for (unsigned b = 0; b < n_bad; ++b) {
       const unsigned q = bad[b];
@@ -1590,7 +1612,7 @@ extern "C" size_t om_sim_topk_async_workspace_bytes(int64_t n_queries, int d, in
 extern "C" int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* chunks, int cap, int* n) {
   if (!n || (cap > 0 && !chunks)) OM_FAIL("null argument");
   if (nq < 1 || N < 0 || k < 1 || k > K_MAX) OM_FAIL("nq >= 1, N >= 0 and k in [1,2048]");
-  *n = search_schedule(mode == OM_SEARCH_F16_RESCORE, nq, N, k, scan_switches(), chunks, cap < 0 ? 0 : cap).n;
+  *n = search_schedule(search_mode_half(mode), nq, N, k, scan_switches(), chunks, cap < 0 ? 0 : cap).n;
   return 0;
 }
 
@@ -1692,11 +1714,25 @@ struct Scan {
     for (int i = 0; i < 4; ++i) f[i] = pinned[i];
     return 0;
   }
+  bool rows16() const { return mode == OM_SEARCH_F16_ONLY; }      // the re-score and the redo read the float16 rows: there are no others
   int rescore(unsigned maxlist) {
-    hipLaunchKernelGGL(rescore_kernel, dim3((maxlist + 3) / 4, (unsigned)nq), dim3(256), 0, s, q32,
-                       idx32, ws.keys, ws.cnt, d);
+    if (rows16())
+      hipLaunchKernelGGL(rescore_kernel<f16_t>, dim3((maxlist + 3) / 4, (unsigned)nq), dim3(256), 0, s, q32, idx16, ws.keys, ws.cnt, d);
+    else
+      hipLaunchKernelGGL(rescore_kernel<float>, dim3((maxlist + 3) / 4, (unsigned)nq), dim3(256), 0, s, q32,
+                         idx32, ws.keys, ws.cnt, d);
     OM_LAUNCH_CHECK();
     return 0;
+  }
+  // one pass of the on-device redo over the rows the mode stores (COLLECT: the last one, which fills the lists)
+  template <bool COLLECT>
+  void redo_pass(const AsyncWs& aw, dim3 grid, size_t lds, int R, int shift, int width) {
+    if (rows16())
+      hipLaunchKernelGGL((redo_pass_kernel<COLLECT, f16_t>), grid, dim3(256), lds, s, q32, idx16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
+                         shift, width, ws.keys, ws.cnt);
+    else
+      hipLaunchKernelGGL((redo_pass_kernel<COLLECT, float>), grid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
+                         shift, width, ws.keys, ws.cnt);
   }
   // dense-score rows [r0, r0+n) and merge them into the lists (always exact, HBM heavy)
   int dense_gemm_append(int64_t r0, int n, bool bf16) {
@@ -1909,7 +1945,9 @@ struct Scan {
           OM_LAUNCH_CHECK();
           if (rescore(cover)) return 1;
         } else {
-          hipLaunchKernelGGL(rescore_strided_kernel, dim3((unsigned)(g7_num_cus() * 8)), dim3(256), 0, s, q32, idx32, ws.keys, ws.cnt, nq, d);
+          const dim3 rgrid((unsigned)(g7_num_cus() * 8));
+          if (rows16()) hipLaunchKernelGGL(rescore_strided_kernel<f16_t>, rgrid, dim3(256), 0, s, q32, idx16, ws.keys, ws.cnt, nq, d);
+          else hipLaunchKernelGGL(rescore_strided_kernel<float>, rgrid, dim3(256), 0, s, q32, idx32, ws.keys, ws.cnt, nq, d);
           OM_LAUNCH_CHECK();
         }
       }
@@ -1921,20 +1959,32 @@ struct Scan {
       const size_t lds = (size_t)R * d * 4;
       const dim3 pgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + R - 1) / R, (int64_t)g7_num_cus() * 4)));
       for (int p = 0; p < REDO_PASSES; ++p) {
-        hipLaunchKernelGGL(redo_pass_kernel<false>, pgrid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
-                           redo_shift(p), redo_width(p), ws.keys, ws.cnt);
+        redo_pass<false>(aw, pgrid, lds, R, redo_shift(p), redo_width(p));
         hipLaunchKernelGGL(redo_pick_kernel, dim3(1), dim3(256), 0, s, aw.rs, aw.bad, aw.prefix, aw.remaining, aw.hist, redo_shift(p), ws.cnt,
                            p == REDO_PASSES - 1 ? 1 : 0);
         OM_LAUNCH_CHECK();
       }
-      hipLaunchKernelGGL(redo_pass_kernel<true>, pgrid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys,
-                         ws.cnt);
+      redo_pass<true>(aw, pgrid, lds, R, 0, 0);
       OM_LAUNCH_CHECK();
       if (select(false, false)) return 1;          // best k of every list, in order
     }
     hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, out_scores, out_ids);
-    hipLaunchKernelGGL(async_status_kernel, dim3(1), dim3(64), 0, s, ws.flag, aw.rs, status, bf16 ? 1 : 0, (int)rounds, family);
+    if (status) hipLaunchKernelGGL(async_status_kernel, dim3(1), dim3(64), 0, s, ws.flag, aw.rs, status, bf16 ? 1 : 0, (int)rounds, family);
     OM_LAUNCH_CHECK();
+    return 0;
+  }
+
+  // om_sim_topk in OM_SEARCH_F16_ONLY: there is no float32 plane to retry on, so the entry enqueues the asynchronous chain -- whose redo
+  // serves every query the margin does not certify -- without status words, and reads the chain's own counters back: ONE synchronisation.
+  // out: {queries redone, of those with a too-wide margin, longest list}
+  int run_sync16(const AsyncWs& aw, int64_t id_offset, float* out_scores, int64_t* out_ids, unsigned (&out)[3]) {
+    if (run_async(true, aw, id_offset, out_scores, out_ids, nullptr)) return 1;
+    static thread_local unsigned* pinned = nullptr;
+    if (!pinned) OM_HIP(hipHostMalloc((void**)&pinned, 128, hipHostMallocPortable));
+    OM_HIP(hipMemcpyAsync(pinned, ws.flag, 64, hipMemcpyDeviceToHost, s));
+    OM_HIP(hipMemcpyAsync(pinned + 16, aw.rs, 64, hipMemcpyDeviceToHost, s));
+    OM_HIP(hipStreamSynchronize(s));
+    out[0] = pinned[16 + REDO_RS_BAD]; out[1] = pinned[16 + REDO_RS_WIDE]; out[2] = pinned[1];
     return 0;
   }
 
@@ -1975,12 +2025,22 @@ const char* scan_setup(Scan& sc, int mode, const float* queries, int64_t n_queri
   if (n_queries > 65535) return "at most 65535 queries per call";
   if (!queries || !out_scores || !out_ids) return "null argument";
   if (!workspace || ((uintptr_t)workspace & 255)) return "workspace must be 256-byte aligned";
-  if (N > 0 && !index_f32) return "index_f32 is null";
+  if (N > 0 && mode != OM_SEARCH_F16_ONLY && !index_f32) return "index_f32 is null";
   if (N > 0 && mode == OM_SEARCH_F16_RESCORE && (!index_f16 || !stats)) return "f16 mode needs index_f16 and stats";
+  if (N > 0 && mode == OM_SEARCH_F16_ONLY && !index_f16) return "OM_SEARCH_F16_ONLY: index_f16 is null (the float16 rows are the index)";
+  if (N > 0 && mode == OM_SEARCH_F16_ONLY && !stats) return "OM_SEARCH_F16_ONLY: stats is null (om_index_add_f16 leaves them)";
   sc.ws = carve_search(n_queries, d, (char*)workspace);
   sc.mode = mode; sc.q32 = queries; sc.idx32 = index_f32; sc.idx16 = (const f16_t*)index_f16;
   sc.nq = n_queries; sc.N = N; sc.d = d; sc.k = k; sc.s = (hipStream_t)stream; sc.stats = stats;
   sc.sw = scan_switches();
+  return nullptr;
+}
+
+// What OM_SEARCH_F16_ONLY refuses in BOTH entries: it always runs the stream-ordered chain, and neither entry has another path to offer.
+const char* f16_only_refusal(const Scan& sc) {
+  if (sc.d > 16384) return "OM_SEARCH_F16_ONLY: d above 16384: a row does not fit the redo's LDS tile, and the mode has no float32 scan to fall back to";
+  if (!sc.sw.gen7)
+    return "OM_SEARCH_F16_ONLY: OM_OPT_SCAN_GEN7 is 0: the fast schedule this mode runs is switched off, and it has no step-by-step path";
   return nullptr;
 }
 }  // namespace
@@ -2008,6 +2068,19 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
   Scan sc;
   if (const char* why = scan_setup(sc, mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, stream))
     OM_FAIL(why);
+  if (mode == OM_SEARCH_F16_ONLY) {
+    if (const char* why = f16_only_refusal(sc)) OM_FAIL(why);
+    const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
+    if (aw.total > workspace_bytes) OM_FAIL("workspace too small: OM_SEARCH_F16_ONLY needs om_sim_topk_async_workspace_bytes");
+    sc.qstat = aw.qstat;
+    if (search_attrs()) return 1;
+    for (auto& v : g_info) v = 0;
+    unsigned redo[3] = {0, 0, 0};
+    const int rc = sc.run_sync16(aw, id_offset, out_scores, out_ids, redo);
+    g_info[0] = 1; g_info[1] = sc.rounds; g_info[3] = redo[2]; g_info[4] = redo[1]; g_info[5] = sc.family; g_info[6] = sc.launch;
+    g_info[7] = redo[0];
+    return rc;
+  }
   if (sc.ws.total > workspace_bytes) OM_FAIL("workspace too small");
   if (search_attrs()) return 1;
   for (auto& v : g_info) v = 0;
@@ -2028,6 +2101,9 @@ extern "C" int om_sim_topk_async(int mode, const float* queries, int64_t n_queri
   Scan sc;
   if (const char* why = scan_setup(sc, mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, stream))
     OM_FAIL(why);
+  if (mode == OM_SEARCH_F16_ONLY) {
+    if (const char* why = f16_only_refusal(sc)) OM_FAIL(why);
+  }
   if (d > 16384) OM_FAIL("d above 16384: a row does not fit the redo's LDS tile (use om_sim_topk)");
   if (!status) OM_FAIL("status is null: the asynchronous entry reports through 8 x int64 of device memory");
   if (!sc.sw.gen7)
@@ -2036,7 +2112,7 @@ extern "C" int om_sim_topk_async(int mode, const float* queries, int64_t n_queri
   if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes)");
   sc.qstat = aw.qstat;
   if (search_attrs()) return 1;
-  return sc.run_async(mode == OM_SEARCH_F16_RESCORE, aw, id_offset, out_scores, out_ids, status);
+  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
 }
 
 extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,
@@ -2051,6 +2127,81 @@ extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t r
   if (scan_attrs()) return 1;
   if (scan_launch(scan_kernel(OM_SCAN_KERNEL_STREAM, true, plan, sw), rows16, nrows, row_base, queries16, nq, d, thr, (u64*)keys, cnt, grid, sw.nt,
                   (hipStream_t)stream)) return 1;
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- om_debug_rescore_rows: the row-typed kernels (re-score, strided re-score, the redo's collect pass) over a caller's candidates ----
+// cand -> lists: list q = rows cand[q][0 .. m) in order, scores 0.  A row number beyond the index is not followed (its score comes back NaN).
+__global__ void debug_fill_lists_kernel(const uint32_t* __restrict__ cand, int m, int64_t N, u64* __restrict__ keys, unsigned* __restrict__ cnt) {
+  const int64_t q = blockIdx.x;
+  for (int j = threadIdx.x; j < m; j += blockDim.x) {
+    const uint32_t row = cand[q * m + j];
+    keys[q * SORT_CAP + j] = pack_key(0.f, (int64_t)row < N ? row : 0u);
+  }
+  if (threadIdx.x == 0) cnt[q] = (unsigned)m;
+}
+// every query marked for the redo with prefix 0 (every key passes the collect pass), lists emptied
+__global__ void debug_mark_all_kernel(int64_t nq, unsigned* __restrict__ rs, unsigned* __restrict__ bad, u64* __restrict__ prefix,
+                                      unsigned* __restrict__ cnt) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < 16) rs[q] = q == REDO_RS_BAD ? (unsigned)nq : 0u;
+  if (q < nq) { bad[q] = (unsigned)q; prefix[q] = 0; cnt[q] = 0; }
+}
+// by_row = 0: out[q][j] = score of slot j (cand[q][j] beyond the index: NaN);  by_row = 1: out[q][row] = score of the slot that names row
+__global__ void debug_read_lists_kernel(const u64* __restrict__ keys, const unsigned* __restrict__ cnt, const uint32_t* __restrict__ cand, int m,
+                                        int64_t N, int by_row, float* __restrict__ out) {
+  const int64_t q = blockIdx.x;
+  const unsigned n = cnt[q] < (unsigned)m ? cnt[q] : (unsigned)m;
+  for (unsigned j = threadIdx.x; j < n; j += blockDim.x) {
+    const u64 key = keys[q * SORT_CAP + j];
+    if (by_row) {
+      if (key_payload(key) < (uint32_t)m) out[q * m + key_payload(key)] = key_score(key);
+    } else {
+      out[q * m + j] = (int64_t)cand[q * m + j] < N ? key_score(key) : __builtin_nanf("");
+    }
+  }
+}
+
+extern "C" int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows, int64_t N, int d, const float* queries, int64_t n_queries,
+                                     const uint32_t* cand, int m, float* out_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  if (row_dtype != OM_F32 && row_dtype != OM_F16) OM_FAIL("om_debug_rescore_rows: row dtype must be OM_F32 or OM_F16");
+  if (kernel < 0 || kernel > 2) OM_FAIL("om_debug_rescore_rows: kernel must be 0 (re-score), 1 (strided re-score) or 2 (redo collect pass)");
+  if (!rows || !queries || !out_scores || (kernel != 2 && !cand)) OM_FAIL("om_debug_rescore_rows: null argument");
+  if (N < 1 || N > 0xffffffffLL || n_queries < 1 || n_queries > 65535) OM_FAIL("om_debug_rescore_rows: N in [1, 2^32) and 1 to 65535 queries");
+  if (d <= 0 || d % 64 != 0 || d > 16384) OM_FAIL("om_debug_rescore_rows: d must be a multiple of 64, at most 16384");
+  if (m < 1 || m > SORT_CAP) OM_FAIL("om_debug_rescore_rows: 1 to 8192 candidates per query");
+  if (kernel == 2 && (int64_t)m != N) OM_FAIL("om_debug_rescore_rows: the redo pass scores every row: m must be N (at most 8192)");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("om_debug_rescore_rows: workspace must be 256-byte aligned");
+  const SearchWs ws = carve_search(n_queries, d, (char*)workspace);
+  const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
+  if (aw.total > workspace_bytes) OM_FAIL("om_debug_rescore_rows: workspace too small (om_sim_topk_async_workspace_bytes)");
+  const hipStream_t s = (hipStream_t)stream;
+  const bool h = row_dtype == OM_F16;
+  const f16_t* r16 = (const f16_t*)rows;
+  const float* r32 = (const float*)rows;
+  const unsigned nq = (unsigned)n_queries;
+  if (kernel == 2) {
+    hipLaunchKernelGGL(debug_mark_all_kernel, dim3((nq + 255) / 256 + 1), dim3(256), 0, s, n_queries, aw.rs, aw.bad, aw.prefix, ws.cnt);
+    const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
+    const size_t lds = (size_t)R * d * 4;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + R - 1) / R, (int64_t)g7_num_cus() * 4)));
+    if (h) hipLaunchKernelGGL((redo_pass_kernel<true, f16_t>), grid, dim3(256), lds, s, queries, r16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt);
+    else hipLaunchKernelGGL((redo_pass_kernel<true, float>), grid, dim3(256), lds, s, queries, r32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt);
+  } else {
+    hipLaunchKernelGGL(debug_fill_lists_kernel, dim3(nq), dim3(256), 0, s, cand, m, N, ws.keys, ws.cnt);
+    if (kernel == 0) {
+      const dim3 grid(((unsigned)m + 3) / 4, nq);
+      if (h) hipLaunchKernelGGL(rescore_kernel<f16_t>, grid, dim3(256), 0, s, queries, r16, ws.keys, ws.cnt, d);
+      else hipLaunchKernelGGL(rescore_kernel<float>, grid, dim3(256), 0, s, queries, r32, ws.keys, ws.cnt, d);
+    } else {
+      const dim3 grid((unsigned)(g7_num_cus() * 8));
+      if (h) hipLaunchKernelGGL(rescore_strided_kernel<f16_t>, grid, dim3(256), 0, s, queries, r16, ws.keys, ws.cnt, n_queries, d);
+      else hipLaunchKernelGGL(rescore_strided_kernel<float>, grid, dim3(256), 0, s, queries, r32, ws.keys, ws.cnt, n_queries, d);
+    }
+  }
+  OM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(debug_read_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, cand, m, N, kernel == 2 ? 1 : 0, out_scores);
   OM_LAUNCH_CHECK();
   return 0;
 }

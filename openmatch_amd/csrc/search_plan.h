@@ -28,6 +28,10 @@ static ScanSwitches scan_switches() {
                       om_option(OM_OPT_SCAN_QGROUP), (debug & 4) ? 0 : 1, (debug >> 3) & 3};
 }
 
+// OM_SEARCH_* -> `half` of scan_plan, scan_round and search_schedule: OM_SEARCH_F16_ONLY scans the same 16-bit plane with the same certified
+// margin as OM_SEARCH_F16_RESCORE, so its plan, its launches and its schedule are that mode's; only what the re-score reads differs.
+static inline bool search_mode_half(int mode) { return mode == OM_SEARCH_F16_RESCORE || mode == OM_SEARCH_F16_ONLY; }
+
 #define SCAN_KSTEP 64            // index columns per K step of the stream kernels (one 128-byte LDS row of 16-bit values)
 #define SCAN_NKMAX32_NARROW 12   // K steps compiled into the 32-query stream kernel: 256 <= d <= 768 ...
 #define SCAN_NKMAX32_WIDE 16     // ... and 832 <= d <= 1024

@@ -3,7 +3,7 @@ methods the reference uses (`add`, `search`, `reset`, `ntotal`;
 src/openmatch/retriever/dense_retriever.py:38-41,105,135,180) and no faiss underneath.
 
 Rows stay on the GPU that encoded them (f32, plus an IEEE-f16 shadow copy for the MFMA candidate
-scan); `search` runs `om_sim_topk` on the local shard and, when the process group has more than
+scan; with precision="f16" the float16 rows alone, 2 bytes per element instead of 6); `search` runs `om_sim_topk` on the local shard and, when the process group has more than
 one rank, all-gathers the queries, searches every shard in parallel and merges the per-shard
 top-k with `om_topk_merge` — the reference's "rank 0 loads every pickle and calls faiss" step
 (:94-106,166-192) without the filesystem round trip and with all GPUs busy.
@@ -45,11 +45,17 @@ class SearchHandle:
 class FlatIPIndex:
     def __init__(self, d: int, device=None, precision: str = "f16_rescore"):
         """precision: 'f16_rescore' (f16 MFMA scan with a certified margin + exact f32 re-score;
-        same ids as the f32 scan) or 'f32' (exact f32 MFMA scan)."""
+        same ids as the f32 scan), 'f32' (exact f32 MFMA scan) or 'f16' (alias 'f16_only': the rows are STORED in float16, as
+        faiss's IndexScalarQuantizer(QT_fp16) stores them, and searched exactly -- the top-k of <q, widen(row)> with float32 queries, bit
+        for bit what an 'f16_rescore' index built from the widened rows returns; no float32 plane is allocated.  A query the certified
+        margin cannot serve is recomputed on the device by a radix select over all rows, which is far slower than a scan:
+        `last_search_info["margin_too_wide_queries"]` / `SearchHandle.info()` tell when that was paid)."""
         if precision in ("bf16_rescore", "fp16_rescore"):     # accepted aliases
             precision = "f16_rescore"
-        if precision not in ("f16_rescore", "f32"):
-            raise ValueError("precision must be 'f16_rescore' or 'f32'")
+        if precision == "f16_only":
+            precision = "f16"
+        if precision not in ("f16_rescore", "f32", "f16"):
+            raise ValueError("precision must be 'f16_rescore', 'f32' or 'f16'")
         self.d = int(d)
         self.dpad = (self.d + 63) // 64 * 64      # kernels need d % 64 == 0; zero columns are free
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -60,27 +66,74 @@ class FlatIPIndex:
         self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
 
     # -- storage ---------------------------------------------------------------------------
-    def _reserve(self, n):
-        cap = 0 if self._f32 is None else self._f32.shape[0]
+    @property
+    def capacity(self):
+        """Rows the planes hold without growing."""
+        return 0 if self._f16 is None else self._f16.shape[0]
+
+    def _reserve(self, n, exact=False):
+        cap = self.capacity
         if n <= cap:
             return
-        new_cap = max(n, int(cap * _GROW), 1024)
-        f32 = torch.zeros(new_cap, self.dpad, dtype=torch.float32, device=self.device)
+        new_cap = n if exact else max(n, int(cap * _GROW), 1024)
         b16 = torch.zeros(new_cap, self.dpad, dtype=torch.float16, device=self.device)
         if self.ntotal:
-            f32[:self.ntotal].copy_(self._f32[:self.ntotal])
             b16[:self.ntotal].copy_(self._f16[:self.ntotal])
-        self._f32, self._f16 = f32, b16
+        self._f16 = b16
+        if self.precision == "f16":                # the float16 plane is the index: nothing else to grow
+            return
+        f32 = torch.zeros(new_cap, self.dpad, dtype=torch.float32, device=self.device)
+        if self.ntotal:
+            f32[:self.ntotal].copy_(self._f32[:self.ntotal])
+        self._f32 = f32
+
+    def reserve(self, n: int):
+        """Room for `n` rows in all, in ONE allocation of exactly that size: called before the first `add`, a large index never holds an
+        old and a new copy of its planes while it grows (growing on demand peaks at 2.5x the rows stored).  Never shrinks."""
+        self._reserve(int(n), exact=True)
+
+    def _add_f16(self, x):
+        """`add` of a float16-only index: rows in float32 or float16 (bfloat16 goes through float32) straight into the float16 plane
+        (om_index_add_f16), a device-side float16 tensor without a float32 round trip."""
+        n = x.shape[0]
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.to(self.device)
+        if self.dpad != self.d:                    # the kernel converts whole rows of the plane's width: zero columns behind d
+            xp = torch.zeros(n, self.dpad, dtype=x.dtype, device=self.device)
+            xp[:, :self.d].copy_(x)
+            x = xp
+        x = x.contiguous()
+        self._reserve(self.ntotal + n)
+        stats = self._stats.clone()                # committed only when every stored value is finite
+        bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().om_index_add_f16(N.OM_F32 if x.dtype == torch.float32 else N.OM_F16, N.ptr(x), n, self.dpad,
+                                              N.ptr(self._f16[self.ntotal:self.ntotal + n]), N.ptr(stats), N.ptr(bad),
+                                              N.stream_ptr(self.device)))
+        n_bad = int(bad.item())                    # the one synchronisation of an add
+        if n_bad:
+            self._f16[self.ntotal:self.ntotal + n].zero_()      # rows beyond ntotal stay what an allocation leaves: zeros
+            raise ValueError(f"{n_bad} value(s) of the added rows are not finite in float16 (inf, NaN, or beyond the float16 range "
+                             f"of +-65504): a precision='f16' index stores float16 rows; nothing was added")
+        self._stats = stats
+        self.ntotal += n
 
     def add(self, x):
-        """Append rows (numpy array or tensor, any device) in insertion order."""
+        """Append rows (numpy array or tensor, any device) in insertion order.
+        precision='f16': float32, float16 or bfloat16 rows; float32 is rounded to nearest even (`torch.Tensor.half()`), float16 is stored bit
+        for bit.  The add reads a counter of non-finite stored values back -- ONE host synchronisation per `add` -- and raises
+        ValueError, leaving `ntotal` and the stored rows as they were, when a value is inf, NaN or beyond the float16 range."""
         if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+            keep = self.precision == "f16" and x.dtype == np.float16
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float16 if keep else np.float32))
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError(f"expected [n,{self.d}] rows")
         n = x.shape[0]
         if n == 0:
             return
+        if self.precision == "f16":
+            return self._add_f16(x)
         self._reserve(self.ntotal + n)
         dst = self._f32[self.ntotal:self.ntotal + n]
         dst[:, :self.d].copy_(x.to(device=self.device, dtype=torch.float32), non_blocking=True)
@@ -109,7 +162,7 @@ class FlatIPIndex:
         q = q.contiguous()
         D = torch.empty(q.shape[0], k, dtype=torch.float32, device=self.device)
         I = torch.empty(q.shape[0], k, dtype=torch.int64, device=self.device)
-        return q, D, I, N.SEARCH_F16_RESCORE if self.precision == "f16_rescore" else N.SEARCH_F32
+        return q, D, I, {"f16_rescore": N.SEARCH_F16_RESCORE, "f32": N.SEARCH_F32, "f16": N.SEARCH_F16_ONLY}[self.precision]
 
     def search_device(self, queries: torch.Tensor, k: int, id_offset: int = 0):
         """Local-shard search on device tensors: returns (D [Q,k] f32, I [Q,k] int64) on the GPU."""
@@ -120,7 +173,8 @@ class FlatIPIndex:
         with torch.cuda.device(self.device):
             for s in range(0, nq, step):
                 n = min(step, nq - s)
-                nbytes = lib.om_sim_topk_workspace_bytes(n, self.dpad, k)
+                # (the float16-only mode runs the stream-ordered chain behind the synchronous entry too: that chain's workspace)
+                nbytes = (lib.om_sim_topk_async_workspace_bytes if mode == N.SEARCH_F16_ONLY else lib.om_sim_topk_workspace_bytes)(n, self.dpad, k)
                 _buf, ws = N.Workspace.get(self.device, nbytes, "search")
                 N.check(lib.om_sim_topk(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16),
                                         N.ptr(self._stats), self.ntotal, self.dpad, k, int(id_offset),
@@ -132,6 +186,8 @@ class FlatIPIndex:
                                  "overflow_fallbacks": int(info[2]), "max_list": int(info[3]),
                                  "margin_too_wide": bool(info[4]), "kernel": N.SCAN_FAMILY_NAME[int(info[5])],
                                  "launch": N.SCAN_KERNEL_NAME[int(info[6])]}
+        if mode == N.SEARCH_F16_ONLY:      # no float32 retry: the queries the margin could not certify were redone on the device
+            self.last_search_info.update(margin_too_wide_queries=int(info[4]), redone=int(info[7]))
         return D, I
 
     def search_device_async(self, queries: torch.Tensor, k: int, id_offset: int = 0):

@@ -38,7 +38,7 @@ SCAN_KERNEL = {"dense": 0, "tile2": 1, "tile6": 2, "wide7": 3, "wide7c": 4, "str
 SCAN_KERNEL_NAME = {v: k for k, v in SCAN_KERNEL.items()}
 OPT_SCAN_GEN7 = 3
 OPT_ATTENTION_FAST = 2
-SEARCH_F32, SEARCH_F16_RESCORE = 0, 1
+SEARCH_F32, SEARCH_F16_RESCORE, SEARCH_F16_ONLY = 0, 1, 2
 ABI_VERSION = 6
 
 c_void_p, c_int, c_int64, c_float, c_size_t = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -337,6 +337,9 @@ _SIGNATURES = {
                                              C.POINTER(OmT5DecoderGrads), c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_linear_f32_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "om_index_to_f16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "om_index_add_f16": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "om_debug_rescore_rows": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "om_sim_topk_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "om_sim_topk": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                             c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
