@@ -1040,6 +1040,36 @@ int om_sim_topk_async(int mode, const float* queries, int64_t n_queries, const f
  * first 4096 rows, *n filtered rounds; chunks[i], i < min(*n, cap), is the number of rows of round i, the first of which starts at row
  * 4096.  N <= 4096 has no rounds.  mode: OM_SEARCH_*; under the calling thread's switches (OM_OPT_SCAN_GROWTH). */
 int om_debug_search_schedule(int mode, int64_t nq, int64_t N, int k, int64_t* chunks, int cap, int* n);
+
+/* Filtered exact search: the top-k over the ALLOWED rows of the shard only -- per query exactly what om_sim_topk_async of the same mode
+ * returns over an index that holds only the allowed rows in their original order: the same scores (the re-score's bits in the two
+ * 16-bit modes), ties by ascending row, ids = id_offset + the ORIGINAL row, (-3.4028235e38, -1) padding when fewer than k rows are allowed.
+ * allow_bits: device memory, (N + 31) / 32 uint32 words, bit r & 31 of word r >> 5 is row r; one bitmap for all queries of the call; bits
+ * at and beyond N are ignored.  n_allowed: the number of set bits among [0, N), as the host knows it -- it sizes the schedule only; the
+ * rank of the redo's select comes from a count taken on the device at the head of the chain, so a stale value costs speed, never
+ * correctness.  The entry only ENQUEUES, as om_sim_topk_async does, and runs that entry's chain: the scan kernels do not know the
+ * filter -- a disallowed row above the threshold enters a list like any row -- and a small kernel drops the disallowed keys of every
+ * list in front of EVERY selection (the dense bootstrap's included), so thresholds, certified margins and the re-score only ever see
+ * allowed rows.  The lists therefore fill as those of a search for k_eff = ceil(k N / n_allowed): the schedule below sizes its rounds
+ * for that, and scores a longer head of the shard densely.  A query whose list overflows all the same is redone on the device, and the
+ * redo skips disallowed rows.  A filter whose allowed rows are scarce at the head of [0, N) and dense later defeats the bootstrap (no
+ * threshold exists before k allowed rows were seen): every query is then redone by seven VALU passes over the index; status[2] tells.
+ * status: as om_sim_topk_async's, but may be NULL.  Refuses what om_sim_topk_async refuses (OM_OPT_SCAN_GEN7 = 0, d > 16384, k > 2048),
+ * a null bitmap and n_allowed outside [0, N].  workspace: om_sim_topk_filtered_workspace_bytes, 256-byte aligned. */
+size_t om_sim_topk_filtered_workspace_bytes(int64_t n_queries, int d, int k);
+int om_sim_topk_filtered(int mode, const float* queries, int64_t n_queries, const float* index_f32,
+                         const void* index_f16, const float* stats, int64_t N, int d, int k,
+                         int64_t id_offset, const uint32_t* allow_bits, int64_t n_allowed, float* out_scores,
+                         int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The schedule of om_sim_topk_filtered (csrc/search_plan.h search_schedule_filtered: no launch, no HIP call): *boot dense chunks of 4096
+ * rows -- the smallest count whose expected allowed rows reach 2 k, at most all rows -- then *n filtered rounds of chunks[i] rows, the
+ * first of which starts at row *boot * 4096, sized from the list estimate of k_eff.  n_allowed == N: om_debug_search_schedule's. */
+int om_debug_search_schedule_filtered(int mode, int64_t nq, int64_t N, int k, int64_t n_allowed, int64_t* chunks, int cap, int* n,
+                                      int64_t* boot);
+/* What decides between scanning under the bitmap and gathering the allowed rows (openmatch_amd/index.py filter_route): *list_eff, the
+ * list estimate that schedule sizes its rounds from -- that of k_eff = ceil(k N / n_allowed) in the mode's own formula -- and *list_max,
+ * the longest list a selection may leave.  N >= 1, n_allowed in [1, N].  Pure: no launch, no HIP call. */
+int om_debug_search_filter_estimate(int mode, int64_t N, int k, int64_t n_allowed, int64_t* list_eff, int64_t* list_max);
 /* The row-typed kernels of the re-score and the redo over a caller's candidates, without a search: rows [N, d] in row_dtype (OM_F32 |
  * OM_F16), queries [n_queries, d] f32, cand [n_queries][m] row numbers (uint32, device; repeats allowed; a number >= N is not followed and
  * scores NaN), out_scores [n_queries][m] f32.  kernel 0: rescore_kernel, 1: rescore_strided_kernel -- out[q][j] = <query q, row cand[q][j]>;

@@ -1322,6 +1322,68 @@ __global__ void init_lists_kernel(unsigned* cnt, unsigned* cnt_prev, float* thr,
   else if (q < (nq + 255) / 256 * 256 + 256) thr[q] = INFINITY;       // queries that do not exist never have survivors
 }
 
+// ---- the row filter of om_sim_topk_filtered ------------------------------------------------------------------------------------------
+// allow: bit r & 31 of word r >> 5 is row r of the shard; bits at and beyond N are never read as rows (count_allowed_kernel masks them,
+// no scan names such a row, the redo stops at N).
+__device__ __forceinline__ bool row_allowed(const uint32_t* __restrict__ allow, uint32_t row) { return (allow[row >> 5] >> (row & 31u)) & 1u; }
+
+// *out += allowed rows among [0, N): the rank of the redo's select is min(k, this), whatever count the host was told
+__global__ __launch_bounds__(256) void count_allowed_kernel(const uint32_t* __restrict__ allow, int64_t N, unsigned* __restrict__ out) {
+  const int64_t words = (N + 31) / 32;
+  unsigned c = 0;
+  for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t v = allow[w];
+    if (w == words - 1 && (N & 31)) v &= (1u << (N & 31)) - 1u;
+    c += (unsigned)__builtin_popcount(v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+
+// Drop before every selection: list q compacted IN PLACE to the keys whose row (the low 32 bits, complemented) the filter allows, in
+// their order, so thresholds, margins, the LIST_MAX test and the re-score only ever see allowed rows.  One workgroup per query, 256 keys
+// per step: every key of a step is in a register before the barrier, and a step writes only below what it has read (out <= base), so
+// no staging copy is needed.  Position inside a step: wave ballot + the totals of the lower waves.  A list beyond SORT_CAP lost
+// appends: clamped and marked here as the selections do, or the compaction would hide it from them.
+__global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ keys, unsigned* __restrict__ cnt, const uint32_t* __restrict__ allow,
+                                                              uint32_t nrows, unsigned* __restrict__ flag, unsigned* __restrict__ qstat) {
+  __shared__ unsigned wtot[4];
+  const int64_t q = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned n = cnt[q];
+  if (n > SORT_CAP) {
+    if (tid == 0) {
+      atomicOr(flag, 1u);
+      if (qstat) atomicOr(qstat + q, QSTAT_OVERFLOW);
+    }
+    n = SORT_CAP;
+  }
+  u64* list = keys + q * SORT_CAP;
+  unsigned out = 0;
+  for (unsigned base = 0; base < n; base += 256) {
+    const unsigned i = base + (unsigned)tid;
+    u64 key = 0ull;
+    bool ok = false;
+    if (i < n) {
+      key = list[i];
+      const uint32_t row = key_payload(key);
+      ok = row < nrows && row_allowed(allow, row);
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
+    const unsigned below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (lane == 0) wtot[wave] = (unsigned)__builtin_popcountll(m);
+    __syncthreads();                               // the step's keys are read, the wave totals written
+    unsigned off = out;
+    for (int w = 0; w < wave; ++w) off += wtot[w];
+    if (ok) list[off + below] = key;
+    out += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    __syncthreads();                               // the totals are read
+  }
+  __syncthreads();                                 // (an empty list: every thread has read cnt[q])
+  if (tid == 0) cnt[q] = out;
+}
+
 // ---- on-device redo of the asynchronous entry ----------------------------------------------------------------------------------------
 // The exact top-k of every query whose qstat is not zero, without a word to the host: an MSB-first radix select over the 64-bit keys
 // pack_key(score, row) of ALL rows.  Ordering by that key is score descending, then row ascending, and no two keys tie -- so the k-th
@@ -1342,6 +1404,7 @@ __global__ void init_lists_kernel(unsigned* cnt, unsigned* cnt_prev, float* thr,
 #define REDO_TILE_BYTES 32768
 #define REDO_RS_BAD 0         // rs[0]: queries to redo;  rs[1]: of those, with QSTAT_WIDE
 #define REDO_RS_WIDE 1
+#define REDO_RS_ALLOWED 2     // rs[2]: rows the filter allows among [0, N) (om_sim_topk_filtered: count_allowed_kernel)
 __host__ __device__ inline int redo_shift(int pass) { return pass < 5 ? 53 - 11 * pass : 0; }      // 53, 42, 31, 20, 9, 0
 __host__ __device__ inline int redo_width(int pass) { return pass < 5 ? 11 : 9; }
 
@@ -1362,14 +1425,16 @@ __global__ void redo_compact_kernel(const unsigned* __restrict__ qstat, int64_t 
 }
 
 __global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restrict__ rs, u64* __restrict__ prefix, unsigned* __restrict__ remaining,
-                                                         unsigned* __restrict__ hist, unsigned want) {
+                                                         unsigned* __restrict__ hist, unsigned want, const unsigned* __restrict__ n_allowed) {
   const unsigned n_bad = rs[REDO_RS_BAD];
   if (!n_bad) return;
+  if (n_allowed && *n_allowed < want) want = *n_allowed;      // under a row filter the rank is min(k, allowed rows), counted on the device
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = i0; i < (int64_t)n_bad * REDO_BINS; i += step) hist[i] = 0;
   for (int64_t b = i0; b < n_bad; b += step) { prefix[b] = 0; remaining[b] = want; }
 }
 
+// allow: the row filter of om_sim_topk_filtered (nullptr: every row counts).
 // COLLECT = false: hist[b][digit at `shift`] += 1 for every row whose key agrees with prefix[b] above the digit;
 // COLLECT = true: every key >= prefix[b] (= T) appended to list bad[b].  Rows [0, N) of `index`, tiles of R rows (R * d * 4 bytes of LDS).
 // TRow = f16_t (OM_SEARCH_F16_ONLY): the tile is filled from 16-byte loads of eight halves and staged WIDENED to float32, so R, the LDS
@@ -1378,7 +1443,7 @@ template <bool COLLECT, typename TRow>
 __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict__ q32, const TRow* __restrict__ index, int64_t N, int d, int R,
                                                         const unsigned* __restrict__ rs, const unsigned* __restrict__ bad,
                                                         const u64* __restrict__ prefix, unsigned* __restrict__ hist, int shift, int width,
-                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt) {
+                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt, const uint32_t* __restrict__ allow) {
   const unsigned n_bad = rs[REDO_RS_BAD];
   if (!n_bad) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1407,6 +1472,7 @@ __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict_
       const float* qv = q32 + (int64_t)q * d;
       const u64 P = prefix[b];
       for (int r = wave; r < nr; r += 4) {
+        if (allow && !row_allowed(allow, (uint32_t)(r0 + r))) continue;      // (wave-uniform) a row the filter drops has no key
         const float sc = rescore_dot(qv, tile + (int64_t)r * d, d, lane);
         if (lane != 0) continue;
         const u64 key = pack_key(sc, (uint32_t)(r0 + r));
@@ -1447,7 +1513,9 @@ __global__ __launch_bounds__(256) void redo_pick_kernel(const unsigned* __restri
     __syncthreads();
     unsigned above = suf - own;                   // keys in bins above this thread's
     for (int w = wave + 1; w < 4; ++w) above += wtot[w];
-    if (above < rem && above + own >= rem) {      // the digit is one of this thread's: exactly one thread gets here
+    if (rem == 0) {                               // a row filter that allows no row: no key is wanted, T = the largest key
+      if (tid == 0) { prefix[b] = ~0ull; if (last) cnt[bad[b]] = 0; }
+    } else if (above < rem && above + own >= rem) {      // the digit is one of this thread's: exactly one thread gets here
       unsigned acc = above;
       int digit = 0;
 #pragma unroll
@@ -1687,13 +1755,26 @@ struct Scan {
   SearchWs ws; hipStream_t s;
   unsigned* qstat = nullptr;      // per-query sticky status: the asynchronous entry only
   ScanSwitches sw;                // the thread's switches, read once by the entry
+  // om_sim_topk_filtered only (nullptr: no filter, and not one launch differs): the bitmap over rows [0, N) and the host's count of its bits
+  const uint32_t* allow = nullptr;
+  int64_t n_allowed = 0;
   // diagnostics, accumulated over the 16-bit run and the float32 retry (om_sim_topk publishes them, the asynchronous entry's status
   // kernel takes rounds and family): rounds, chunks redone densely or schedules started over, longest list seen by the host,
   // OM_SCAN_FAMILY_* and OM_SCAN_KERNEL_* of the last filtered round (its tail's where the round had no whole tile)
   int64_t rounds = 0, fallbacks = 0, max_list = 0;
   int family = 0, launch = 0;
 
+  // under a row filter every selection is preceded by the drop of the keys it does not allow
+  // (mark: as the selection it precedes -- the last one of the chain, behind the redo, marks no query: nothing reads the marks any more)
+  int drop(bool mark = true) {
+    if (!allow) return 0;
+    hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, allow, (uint32_t)N, ws.flag,
+                       mark ? qstat : nullptr);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
   int select(bool certified, bool mark = true) {
+    if (drop(mark)) return 1;
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s,
                        ws.keys, ws.cnt, ws.cnt_prev, ws.thr, certified ? ws.margin : nullptr, k,
                        ws.flag, mark ? qstat : nullptr);
@@ -1701,6 +1782,7 @@ struct Scan {
     return 0;
   }
   int select_radix(bool certified, int cap = SORT_CAP) {
+    if (drop()) return 1;
     hipLaunchKernelGGL(select_radix_kernel, dim3((unsigned)nq), dim3(256), (size_t)cap * 8 + 1024 + 64, s,
                        ws.keys, ws.cnt, ws.thr, certified ? ws.margin : nullptr, k, ws.flag, cap, qstat);
     OM_LAUNCH_CHECK();
@@ -1729,10 +1811,10 @@ struct Scan {
   void redo_pass(const AsyncWs& aw, dim3 grid, size_t lds, int R, int shift, int width) {
     if (rows16())
       hipLaunchKernelGGL((redo_pass_kernel<COLLECT, f16_t>), grid, dim3(256), lds, s, q32, idx16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
-                         shift, width, ws.keys, ws.cnt);
+                         shift, width, ws.keys, ws.cnt, allow);
     else
       hipLaunchKernelGGL((redo_pass_kernel<COLLECT, float>), grid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
-                         shift, width, ws.keys, ws.cnt);
+                         shift, width, ws.keys, ws.cnt, allow);
   }
   // dense-score rows [r0, r0+n) and merge them into the lists (always exact, HBM heavy)
   int dense_gemm_append(int64_t r0, int n, bool bf16) {
@@ -1790,6 +1872,11 @@ struct Scan {
     if (aw) {
       hipLaunchKernelGGL(async_init_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, aw->qstat, aw->rs, status, nq);
       OM_LAUNCH_CHECK();
+      if (allow && N > 0) {                        // behind the kernel that zeroes rs
+        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(((N + 31) / 32 + 255) / 256, 1024));
+        hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, allow, N, aw->rs + REDO_RS_ALLOWED);
+        OM_LAUNCH_CHECK();
+      }
     }
     if (bf16 && N > 0) {
       hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
@@ -1801,14 +1888,19 @@ struct Scan {
   // The fast schedule's rounds, for both entries (N > DENSE_CHUNK): the dense bootstrap and its selection, then per round the filtered
   // scan and a radix selection, which also flags overflows -- back to back, nothing read by the host.  The list estimate, the growth
   // per round, the selection's LDS copy and the chunks are search_plan.h's search_schedule, returned in `sched`.
+  // Under a row filter the schedule is search_schedule_filtered's: `boot` dense chunks, each with its drop and selection, then the rounds.
   int fast_rounds(bool bf16, SearchSchedule& sched) {
-    if (dense_gemm_append(0, DENSE_CHUNK, bf16)) return 1;
-    if (select_radix(bf16, DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
-    rounds++;
     int64_t chunks[SEARCH_SCHED_MAX];
-    sched = search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
+    int64_t boot = 1;
+    sched = allow ? search_schedule_filtered(bf16, nq, N, k, n_allowed, sw, chunks, SEARCH_SCHED_MAX, &boot)
+                  : search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
     if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
-    int64_t at = DENSE_CHUNK;
+    for (int64_t b = 0; b < boot && b * DENSE_CHUNK < N; ++b) {
+      if (dense_gemm_append(b * DENSE_CHUNK, (int)std::min<int64_t>(DENSE_CHUNK, N - b * DENSE_CHUNK), bf16)) return 1;
+      if (select_radix(bf16, b == 0 && DENSE_CHUNK <= 4096 ? 4096 : SORT_CAP)) return 1;
+      rounds++;
+    }
+    int64_t at = boot * DENSE_CHUNK;
     for (int i = 0; i < sched.n; ++i) {
       if (filter_step(at, chunks[i], bf16, false)) return 1;
       if (select_radix(bf16, sched.sel_cap)) return 1;
@@ -1953,7 +2045,8 @@ struct Scan {
       }
       // redo: a fixed chain, empty launches when no query is marked
       hipLaunchKernelGGL(redo_compact_kernel, dim3(qblocks), dim3(256), 0, s, qstat, nq, aw.rs, aw.bad);
-      hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.prefix, aw.remaining, aw.hist, (unsigned)std::min<int64_t>(k, N));
+      hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.prefix, aw.remaining, aw.hist, (unsigned)std::min<int64_t>(k, N),
+                         allow ? (const unsigned*)(aw.rs + REDO_RS_ALLOWED) : (const unsigned*)nullptr);
       OM_LAUNCH_CHECK();
       const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
       const size_t lds = (size_t)R * d * 4;
@@ -2115,6 +2208,54 @@ extern "C" int om_sim_topk_async(int mode, const float* queries, int64_t n_queri
   return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
 }
 
+// The stream-ordered search under a row filter: om_sim_topk_async's chain (Scan::run_async itself) with the bitmap set, which adds the
+// count of the allowed rows behind the init, the drop in front of every selection, the filtered schedule and the redo's row test.
+extern "C" int om_sim_topk_filtered(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
+                                    const float* stats, int64_t N, int d, int k, int64_t id_offset, const uint32_t* allow_bits,
+                                    int64_t n_allowed, float* out_scores, int64_t* out_ids, int64_t* status, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (n_queries <= 0) return 0;
+  Scan sc;
+  if (const char* why = scan_setup(sc, mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, stream))
+    OM_FAIL(why);
+  if (mode == OM_SEARCH_F16_ONLY) {
+    if (const char* why = f16_only_refusal(sc)) OM_FAIL(why);
+  }
+  if (d > 16384) OM_FAIL("d above 16384: a row does not fit the redo's LDS tile");
+  if (!sc.sw.gen7) OM_FAIL("OM_OPT_SCAN_GEN7 is 0: the fast schedule this entry runs is switched off");
+  if (!allow_bits) OM_FAIL("allow_bits is null: the filtered search needs the bitmap of the allowed rows (om_sim_topk_async searches all rows)");
+  if (n_allowed < 0 || n_allowed > N) OM_FAIL("n_allowed must be in [0, N]");
+  const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
+  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_filtered_workspace_bytes)");
+  sc.qstat = aw.qstat;
+  sc.allow = allow_bits;
+  sc.n_allowed = n_allowed;
+  if (search_attrs()) return 1;
+  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+}
+
+extern "C" size_t om_sim_topk_filtered_workspace_bytes(int64_t n_queries, int d, int k) {
+  return om_sim_topk_async_workspace_bytes(n_queries, d, k);
+}
+
+extern "C" int om_debug_search_schedule_filtered(int mode, int64_t nq, int64_t N, int k, int64_t n_allowed, int64_t* chunks, int cap, int* n,
+                                                 int64_t* boot) {
+  if (!n || !boot || (cap > 0 && !chunks)) OM_FAIL("null argument");
+  if (nq < 1 || N < 0 || k < 1 || k > K_MAX) OM_FAIL("nq >= 1, N >= 0 and k in [1,2048]");
+  if (n_allowed < 0 || n_allowed > N) OM_FAIL("n_allowed must be in [0, N]");
+  *n = search_schedule_filtered(search_mode_half(mode), nq, N, k, n_allowed, scan_switches(), chunks, cap < 0 ? 0 : cap, boot).n;
+  return 0;
+}
+
+extern "C" int om_debug_search_filter_estimate(int mode, int64_t N, int k, int64_t n_allowed, int64_t* list_eff, int64_t* list_max) {
+  if (!list_eff || !list_max) OM_FAIL("null argument");
+  if (N < 1 || k < 1 || k > K_MAX) OM_FAIL("N >= 1 and k in [1,2048]");
+  if (n_allowed < 1 || n_allowed > N) OM_FAIL("n_allowed must be in [1, N]");
+  *list_eff = search_list_estimate(search_mode_half(mode), search_k_eff(k, N, n_allowed));
+  *list_max = LIST_MAX;
+  return 0;
+}
+
 extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,
                                    uint64_t* keys, unsigned* cnt, int grid, void* stream) {
   if (!rows16 || !queries16 || !thr || !keys || !cnt) OM_FAIL("null argument");
@@ -2186,8 +2327,8 @@ extern "C" int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows
     const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
     const size_t lds = (size_t)R * d * 4;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + R - 1) / R, (int64_t)g7_num_cus() * 4)));
-    if (h) hipLaunchKernelGGL((redo_pass_kernel<true, f16_t>), grid, dim3(256), lds, s, queries, r16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt);
-    else hipLaunchKernelGGL((redo_pass_kernel<true, float>), grid, dim3(256), lds, s, queries, r32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt);
+    if (h) hipLaunchKernelGGL((redo_pass_kernel<true, f16_t>), grid, dim3(256), lds, s, queries, r16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt, (const uint32_t*)nullptr);
+    else hipLaunchKernelGGL((redo_pass_kernel<true, float>), grid, dim3(256), lds, s, queries, r32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt, (const uint32_t*)nullptr);
   } else {
     hipLaunchKernelGGL(debug_fill_lists_kernel, dim3(nq), dim3(256), 0, s, cand, m, N, ws.keys, ws.cnt);
     if (kernel == 0) {

@@ -116,20 +116,29 @@ struct SearchSchedule {
   int n;            // filtered rounds; chunks[0 .. min(n, cap)) are their sizes in rows, the first starts at row SEARCH_DENSE_CHUNK
 };
 
-static SearchSchedule search_schedule(bool half, int64_t nq, int64_t N, int k, const ScanSwitches sw, int64_t* chunks, int cap) {
+// The list estimate after a selection for k: certified scans keep the margin's ties too.
+static int64_t search_list_estimate(bool half, int64_t k) { return half ? k * 13 / 10 + 64 : k + 16; }
+
+// The round loop of both schedules: rounds from row `first` to N, `list` the estimate the re-score covers, `list_grow` the estimate the
+// lists fill by between two selections (the same number without a filter; that of k_eff under one).
+static SearchSchedule search_schedule_rounds(int64_t list, int64_t list_grow, int64_t first, int64_t nq, int64_t N, const ScanSwitches sw,
+                                             int64_t* chunks, int cap) {
   SearchSchedule p;
-  p.list = half ? (int64_t)k * 13 / 10 + 64 : (int64_t)k + 16;
+  p.list = list;
   const double growth = nq <= 32 ? 400.0 : (nq <= 128 && !sw.growth_set ? 100.0 : (double)(sw.growth > 5 ? sw.growth : 5));
-  const double room = 0.75 * (double)(SEARCH_SORT_CAP - p.list);
-  const double grow = (double)p.list * growth / 100.0;
-  const double want = room < grow ? room : grow;
-  // selection launches of the rounds: lists are ~list + want keys long; when twice that margin fits 4096 keys the
+  const double room = 0.75 * (double)(SEARCH_SORT_CAP - list_grow);
+  const double grow = (double)list_grow * growth / 100.0;
+  // never below 5 % a round, the least `growth` asks for: without a filter room is far above it (list_grow <= 2726 at k = 2048) and this
+  // changes nothing; a forced scan of a sparse filter (list_grow near or beyond SEARCH_SORT_CAP, room <= 0) still ends within
+  // SEARCH_SCHED_MAX rounds, and a list that overflows all the same is the redo's
+  const double want = std::max(room < grow ? room : grow, (double)list_grow * 5.0 / 100.0);      // (`grow` at growth = 5: never above it)
+  // selection launches of the rounds: lists are ~list_grow + want keys long; when twice that margin fits 4096 keys the
   // LDS copy is sized for 4096 (four workgroups per CU instead of two); a longer list is read from global memory
-  p.sel_cap = (double)p.list + 2.0 * want + 256.0 < 4096.0 ? 4096 : SEARCH_SORT_CAP;
+  p.sel_cap = (double)list_grow + 2.0 * want + 256.0 < 4096.0 ? 4096 : SEARCH_SORT_CAP;
   p.n = 0;
-  int64_t at = SEARCH_DENSE_CHUNK;
+  int64_t at = first;
   while (at < N) {
-    int64_t chunk = (int64_t)((double)at * want / (double)p.list);
+    int64_t chunk = (int64_t)((double)at * want / (double)list_grow);
     if (chunk < SEARCH_DENSE_CHUNK) chunk = SEARCH_DENSE_CHUNK;
     chunk &= ~(int64_t)255;                                   // whole tiles (SEARCH_DENSE_CHUNK is one)
     if (chunk > N - at) chunk = N - at;
@@ -139,4 +148,38 @@ static SearchSchedule search_schedule(bool half, int64_t nq, int64_t N, int k, c
     at += chunk;
   }
   return p;
+}
+
+static SearchSchedule search_schedule(bool half, int64_t nq, int64_t N, int k, const ScanSwitches sw, int64_t* chunks, int cap) {
+  const int64_t list = search_list_estimate(half, k);
+  return search_schedule_rounds(list, list, SEARCH_DENSE_CHUNK, nq, N, sw, chunks, cap);
+}
+
+// ---- the same schedule under a row filter (om_sim_topk_filtered) ----------------------------------------------------------------------
+// Only n_allowed of the N rows may be returned.  The scan kernels do not know the filter: a selection keeps about k ALLOWED keys, so its
+// threshold is the k-th best allowed score -- which about k_eff = ceil(k N / n_allowed) rows of any kind reach -- and the lists fill
+// between two selections as those of an unfiltered search for k_eff would.  So the growth per round (and the selection's LDS copy) is
+// sized from the list estimate of k_eff, and the dense bootstrap covers `boot` chunks of SEARCH_DENSE_CHUNK rows: the smallest count
+// whose EXPECTED allowed rows reach 2 k (a threshold exists only once k allowed rows were seen; until then every scanned row is appended),
+// at most all the rows.  The first round starts at row boot * SEARCH_DENSE_CHUNK.  `list` stays the estimate for k: after the last
+// drop and selection a list holds allowed keys only, and that is what the re-score has to cover.
+// n_allowed >= N returns exactly search_schedule (boot = 1); n_allowed < 1 counts as 1 (everything is scored densely).  Pure.
+static int64_t search_k_eff(int64_t k, int64_t N, int64_t n_allowed) {                 // N < 2^32, k <= 2048: no overflow
+  const int64_t na = n_allowed < 1 ? 1 : n_allowed;
+  return na >= N ? k : (k * N + na - 1) / na;
+}
+
+static SearchSchedule search_schedule_filtered(bool half, int64_t nq, int64_t N, int k, int64_t n_allowed, const ScanSwitches sw,
+                                               int64_t* chunks, int cap, int64_t* boot) {
+  if (n_allowed >= N) {
+    if (boot) *boot = 1;
+    return search_schedule(half, nq, N, k, sw, chunks, cap);
+  }
+  const int64_t na = n_allowed < 1 ? 1 : n_allowed;
+  const int64_t all = (N + SEARCH_DENSE_CHUNK - 1) / SEARCH_DENSE_CHUNK;
+  int64_t b = (2 * (int64_t)k * N + SEARCH_DENSE_CHUNK * na - 1) / (SEARCH_DENSE_CHUNK * na);
+  b = b < 1 ? 1 : (b > all ? all : b);
+  if (boot) *boot = b;
+  return search_schedule_rounds(search_list_estimate(half, k), search_list_estimate(half, search_k_eff(k, N, na)), b * SEARCH_DENSE_CHUNK,
+                                nq, N, sw, chunks, cap);
 }

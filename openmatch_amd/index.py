@@ -21,25 +21,113 @@ class SearchHandle:
     of the stream the search was enqueued on; the handle keeps the workspace, the status words and the query copy of every chunk of
     at most 32 768 queries alive."""
 
-    def __init__(self, D, I, queries, chunks, device):
+    def __init__(self, D, I, queries, chunks, device, extra=None):
         self.D, self.I = D, I
         self._queries, self._chunks, self._device = queries, chunks, device
+        self._extra = extra                # a filtered search: {"route", "n_allowed"} (and whatever else has to stay alive)
 
     def info(self):
         """Synchronises the device, then the `last_search_info` keys (of the last chunk; `max_list` / `margin_too_wide` over all chunks)
-        plus `redone`: queries the on-device redo recomputed.  `overflow_fallbacks` is always 0: no batch is ever started over."""
+        plus `redone`: queries the on-device redo recomputed.  `overflow_fallbacks` is always 0: no batch is ever started over.
+        A filtered search adds `route` and `n_allowed`."""
         torch.cuda.synchronize(self._device)
         st = [s.cpu().tolist() for _buf, s in self._chunks]
+        extra = {k: v for k, v in (self._extra or {}).items() if not k.startswith("_")}
         if not st:
             return {"scan": "f32", "rounds": 0, "overflow_fallbacks": 0, "max_list": 0, "margin_too_wide": False, "kernel": "dense",
-                    "redone": 0}
+                    "redone": 0, **extra}
         if any(s[6] != 1 for s in st):
             raise N.NativeError("the search has not run (a captured search reports after its first replay)")
         last = st[-1]
         return {"scan": "f16+rescore" if last[0] == 1 else "f32", "rounds": int(last[1]), "overflow_fallbacks": 0,
                 "max_list": max(int(s[3]) for s in st), "margin_too_wide": any(s[4] != 0 for s in st),
                 "kernel": N.SCAN_FAMILY_NAME[int(last[5])], "redone": sum(int(s[2]) for s in st),
-                "margin_too_wide_queries": sum(int(s[4]) for s in st)}
+                "margin_too_wide_queries": sum(int(s[4]) for s in st), **extra}
+
+
+LIST_MAX = 4096            # csrc/search.hip: the longest list a selection may leave (SORT_CAP - DENSE_CHUNK).  This and filter_route's
+#                            estimate repeat native code; tests/test_search_filter_host.py holds both to om_debug_search_filter_estimate
+ROUTES = ("empty", "range", "scan", "gather")
+
+
+def filter_route(precision: str, k: int, first: int, last: int, n_allowed: int, route=None):
+    """Which way a filtered search goes (pure: no tensor, no device).  `first` / `last`: the lowest and the highest allowed row.
+    In order:  'empty' nothing is allowed;  a forced `route` ('scan' | 'gather');  'range' the allowed rows are one contiguous run;
+    'scan' the list estimate of k_eff = ceil(k * rows / n_allowed) -- in the precision's own formula (csrc/search_plan.h), over the rows
+    the scan would read: `first` rounded down to 256 through `last` -- is at most LIST_MAX;  'gather' anything sparser."""
+    if route not in (None, "scan", "gather"):
+        raise ValueError("route must be None, 'scan' or 'gather'")
+    if n_allowed <= 0:
+        return "empty"
+    if route is not None:
+        return route
+    if last - first + 1 == n_allowed:
+        return "range"
+    rows = last + 1 - first // 256 * 256
+    k_eff = (k * rows + n_allowed - 1) // n_allowed
+    est = k_eff * 13 // 10 + 64 if precision in ("f16_rescore", "f16") else k_eff + 16
+    return "scan" if est <= LIST_MAX else "gather"
+
+
+class RowFilter:
+    """The rows of one index a filtered search may return: a bitmap over [0, ntotal) shared by all queries of a call.
+    allowed: a bool mask [ntotal], or a tensor / array / sequence of row ids (`invert=True`: the ids are an exclusion list).
+    Construction packs the bitmap on the index's device and reads `n_allowed` and the first and last allowed row back: ONE host
+    synchronisation.  A filter names ROW NUMBERS, not contents: it serves any index of `ntotal` rows on its device, and an index that
+    was reset and filled again with as many rows is searched over the same row numbers of its new contents.  The planes of the
+    'gather' route are cached here on first use, for one index as it then was: an `add` or `reset` of that index since (its
+    generation count) or another index makes the next gather search build them anew."""
+
+    def __init__(self, index, allowed, invert: bool = False):
+        self.ntotal = int(index.ntotal)
+        self.device = index.device
+        if isinstance(allowed, np.ndarray):
+            allowed = torch.from_numpy(allowed)
+        elif not isinstance(allowed, torch.Tensor):
+            allowed = torch.as_tensor(list(allowed), dtype=torch.int64)
+        allowed = allowed.to(self.device)
+        bad = torch.zeros((), dtype=torch.int64, device=self.device)
+        if allowed.dtype == torch.bool:
+            if allowed.dim() != 1 or allowed.shape[0] != self.ntotal:
+                raise ValueError(f"the mask has {tuple(allowed.shape)} entries, the index {self.ntotal} rows")
+            mask = ~allowed if invert else allowed
+        else:
+            ids = allowed.reshape(-1).to(torch.int64)
+            mask = torch.zeros(self.ntotal, dtype=torch.bool, device=self.device)
+            if ids.numel() and not self.ntotal:
+                raise ValueError("row ids for an empty index")
+            if ids.numel():
+                bad = ((ids < 0) | (ids >= self.ntotal)).sum()          # read back with the counts below
+                mask[ids.clamp(0, self.ntotal - 1)] = True
+            if invert:
+                mask = ~mask
+        self.mask = mask
+        self.words = self.pack(mask)
+        if self.ntotal:
+            pos = torch.arange(self.ntotal, device=self.device)
+            big = torch.full_like(pos, self.ntotal)
+            n, first, last, bad = torch.stack([mask.sum(), torch.where(mask, pos, big).min(), torch.where(mask, pos, -big).max(), bad]).tolist()
+            if bad:
+                raise ValueError(f"{bad} row id(s) outside [0, {self.ntotal})")
+        else:
+            n, first, last = 0, 0, -1
+        self.n_allowed, self.first, self.last = int(n), int(first), int(last)
+        self._gathered = None              # (index it was built from, that index's generation then, ids, sub-index over the allowed rows)
+
+    @staticmethod
+    def pack(mask: torch.Tensor) -> torch.Tensor:
+        """bool [n] -> int32 words [(n + 31) // 32]: bit r & 31 of word r >> 5 is mask[r] (the uint32 words of om_sim_topk_filtered, in
+        torch's int32); the bits of the last word beyond n are 0.  Pure: any device."""
+        n = mask.shape[0]
+        words = (n + 31) // 32
+        m = torch.zeros(words * 32, dtype=torch.int64, device=mask.device)
+        m[:n] = mask.to(torch.int64)
+        v = (m.view(words, 32) << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(1)
+        return torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32)
+
+    def ids(self):
+        """The allowed rows, ascending (int64, on the device)."""
+        return self.mask.nonzero().reshape(-1)
 
 
 class FlatIPIndex:
@@ -61,6 +149,7 @@ class FlatIPIndex:
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.precision = precision
         self.ntotal = 0
+        self._generation = 0                       # counts `add`s and `reset`s: what a RowFilter was built against
         self._f32 = None
         self._f16 = None
         self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
@@ -118,6 +207,7 @@ class FlatIPIndex:
                              f"of +-65504): a precision='f16' index stores float16 rows; nothing was added")
         self._stats = stats
         self.ntotal += n
+        self._generation += 1
 
     def add(self, x):
         """Append rows (numpy array or tensor, any device) in insertion order.
@@ -142,9 +232,11 @@ class FlatIPIndex:
                                              N.ptr(self._f16[self.ntotal:self.ntotal + n]),
                                              N.ptr(self._stats), N.stream_ptr(self.device)))
         self.ntotal += n
+        self._generation += 1
 
     def reset(self):
         self.ntotal = 0
+        self._generation += 1
         self._f32 = self._f16 = None
         self._stats.zero_()
 
@@ -196,6 +288,11 @@ class FlatIPIndex:
         its padded query copy, so several searches can be in flight (back to back, on several streams, or captured in a graph: the
         handle then has to outlive the graph).  The index must not be added to or reset while a search is in flight."""
         q, D, I, mode = self._search_args(queries, k)
+        return SearchHandle(D, I, q, self._enqueue(q, D, I, mode, k, self._f32, self._f16, self.ntotal, id_offset), self.device)
+
+    def _enqueue(self, q, D, I, mode, k, f32, f16, nrows, id_offset, words=None, n_allowed=0):
+        """The stream-ordered chain over rows [0, nrows) of the planes `f32` / `f16`, in chunks of at most 32 768 queries: om_sim_topk_async,
+        or with `words` (the bitmap over those rows) om_sim_topk_filtered.  Returns the (workspace, status) pairs a handle keeps alive."""
         nq = q.shape[0]
         lib = N.lib()
         step = 32768
@@ -203,16 +300,84 @@ class FlatIPIndex:
         with torch.cuda.device(self.device):
             for s in range(0, nq, step):
                 n = min(step, nq - s)
-                nbytes = lib.om_sim_topk_async_workspace_bytes(n, self.dpad, k)
+                nbytes = lib.om_sim_topk_async_workspace_bytes(n, self.dpad, k) if words is None else lib.om_sim_topk_filtered_workspace_bytes(n, self.dpad, k)
                 buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
                 ws = buf.data_ptr() + (-buf.data_ptr()) % 256
                 status = torch.zeros(8, dtype=torch.int64, device=self.device)
-                N.check(lib.om_sim_topk_async(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16),
-                                              N.ptr(self._stats), self.ntotal, self.dpad, k, int(id_offset),
-                                              N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
-                                              N.stream_ptr(self.device)))
+                if words is None:
+                    N.check(lib.om_sim_topk_async(mode, N.ptr(q[s:s + n]), n, N.ptr(f32), N.ptr(f16),
+                                                  N.ptr(self._stats), nrows, self.dpad, k, int(id_offset),
+                                                  N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
+                                                  N.stream_ptr(self.device)))
+                else:
+                    N.check(lib.om_sim_topk_filtered(mode, N.ptr(q[s:s + n]), n, N.ptr(f32), N.ptr(f16),
+                                                     N.ptr(self._stats), nrows, self.dpad, k, int(id_offset), N.ptr(words), int(n_allowed),
+                                                     N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
+                                                     N.stream_ptr(self.device)))
                 chunks.append((buf, status))
-        return SearchHandle(D, I, q, chunks, self.device)
+        return chunks
+
+    # -- filtered search ---------------------------------------------------------------------
+    def search_device_filtered_async(self, queries: torch.Tensor, k: int, row_filter: "RowFilter", id_offset: int = 0, route=None):
+        """The exact top-k over the rows `row_filter` allows, stream-ordered: per query what an index of the same precision holding
+        only the allowed rows (in their order) returns, with the ORIGINAL row numbers (+ `id_offset`), (-3.4028235e38, -1) padded when
+        fewer than k rows are allowed.  Returns a `SearchHandle`; its `info()` adds `route` (see `filter_route`) and `n_allowed`.
+        route: None, or 'scan' / 'gather' to force one (tests, benchmarks: the result is exact either way -- where a forced scan of a
+        sparse filter overflows its lists the on-device redo recomputes the queries, `redone` tells how many)."""
+        if not isinstance(row_filter, RowFilter):
+            raise TypeError("row_filter must be a RowFilter")
+        if row_filter.ntotal != self.ntotal or row_filter.device != self.device:
+            raise ValueError(f"the filter was built for an index of {row_filter.ntotal} rows on {row_filter.device}, "
+                             f"this one holds {self.ntotal} on {self.device}")
+        rf = row_filter
+        q, D, I, mode = self._search_args(queries, k)
+        way = filter_route(self.precision, k, rf.first, rf.last, rf.n_allowed, route)
+        extra = {"route": way, "n_allowed": rf.n_allowed, "_filter": rf}
+        if way == "empty" or q.shape[0] == 0:
+            D.fill_(torch.finfo(torch.float32).min)
+            I.fill_(-1)
+            return SearchHandle(D, I, q, [], self.device, extra)
+        cut = lambda plane, lo, hi: None if plane is None else plane[lo:hi]
+        if way == "range":                 # a slice of the planes is an index: the unfiltered chain, ids shifted by the slice's first row
+            lo, hi = rf.first, rf.last + 1
+            chunks = self._enqueue(q, D, I, mode, k, cut(self._f32, lo, hi), cut(self._f16, lo, hi), hi - lo, int(id_offset) + lo)
+        elif way == "scan":                # the bitmap's word of row lo is whole: lo is a multiple of 256
+            lo, hi = rf.first // 256 * 256, rf.last + 1
+            chunks = self._enqueue(q, D, I, mode, k, cut(self._f32, lo, hi), cut(self._f16, lo, hi), hi - lo, int(id_offset) + lo,
+                                   words=rf.words[lo // 32:], n_allowed=rf.n_allowed)
+        else:
+            ids, sub = self._gathered(rf)
+            Is = torch.empty_like(I)       # rows of the gathered planes, mapped back through the id list on the same stream
+            chunks = sub._enqueue(q, D, Is, mode, k, sub._f32, sub._f16, sub.ntotal, 0)
+            torch.where(Is >= 0, ids[Is.clamp(min=0)] + int(id_offset), Is, out=I)
+            extra["_rows"] = Is
+        return SearchHandle(D, I, q, chunks, self.device, extra)
+
+    def _gathered(self, rf):
+        """The 'gather' route's index over the allowed rows, cached on the filter: `index_select` of the planes (n_allowed * dpad * 2 or 6
+        bytes) under THIS index's rounding statistics -- maxima over all rows, so still valid bounds for the certified margin."""
+        if rf._gathered is None or rf._gathered[0] is not self or rf._gathered[1] != self._generation:
+            ids = rf.ids()
+            sub = FlatIPIndex(self.d, device=self.device, precision=self.precision)
+            sub._f16 = self._f16.index_select(0, ids)
+            sub._f32 = None if self._f32 is None else self._f32.index_select(0, ids)
+            sub._stats = self._stats
+            sub.ntotal = int(ids.shape[0])
+            rf._gathered = (self, self._generation, ids, sub)
+        return rf._gathered[2], rf._gathered[3]
+
+    def search_device_filtered(self, queries: torch.Tensor, k: int, row_filter: "RowFilter", id_offset: int = 0, route=None):
+        """`search_device_filtered_async`, waited for: (D [Q,k] f32, I [Q,k] int64) on the GPU, and `last_search_info` with `route`,
+        `n_allowed` and `redone`."""
+        h = self.search_device_filtered_async(queries, k, row_filter, id_offset=id_offset, route=route)
+        self.last_search_info = h.info()
+        return h.D, h.I
+
+    def search_filtered(self, x, k: int, row_filter: "RowFilter"):
+        """faiss-style, as `search`: numpy in, (D, I) numpy out."""
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
+        D, I = self.search_device_filtered(q, k, row_filter)
+        return D.cpu().numpy(), I.cpu().numpy()
 
     def search(self, x, k: int):
         """faiss-style: numpy in, (D, I) numpy out, I = insertion indices, -1 padded."""

@@ -29,7 +29,7 @@ from tqdm import tqdm
 from ..arguments import InferenceArguments as EncodingArguments
 from ..dataset import DRInferenceCollator
 from ..feed import model_batch
-from ..index import FlatIPIndex, merge_topk, sharded_topk
+from ..index import FlatIPIndex, RowFilter, merge_topk, sharded_topk
 from ..modeling import DRModelForInference, DROutput
 from ..utils import merge_retrieval_results_by_score
 
@@ -211,24 +211,40 @@ class Retriever:
             lookup.extend(ids)
         return np.concatenate(encoded), lookup
 
-    def _hits_to_dict(self, D, I, topk):
+    def _hits_to_dict(self, D, I, topk, drop_padding=False):
         original = np.array(self.doc_lookup)[I]      # I == -1 (fewer than k rows) -> last doc, as in faiss+numpy
         out = {}
         for q in range(D.shape[0]):
             qid = str(self.query_lookup[q])
-            out[qid] = {str(doc): float(score) for doc, score in zip(original[q], D[q])}
+            # drop_padding (a doc_filter): the padding is no hit -- it would name the last document, kept by the filter or not
+            hits = zip(original[q], D[q], I[q])
+            out[qid] = {str(doc): float(score) for doc, score, row in hits if not (drop_padding and row < 0)}
         return out
 
-    def search(self, topk: int = 100):
+    def _doc_row_filter(self, doc_filter):
+        """`doc_filter` (a collection of doc ids to keep; ids the index does not hold are ignored) -> RowFilter through `doc_lookup`."""
+        row_of = {str(doc): row for row, doc in enumerate(self.doc_lookup)}
+        rows = sorted({row_of[str(doc)] for doc in doc_filter if str(doc) in row_of})
+        return RowFilter(self.index, torch.tensor(rows, dtype=torch.int64))
+
+    def search(self, topk: int = 100, doc_filter=None):
+        """doc_filter: None, or a collection of doc ids: only those documents are returned (an exact filtered search:
+        `FlatIPIndex.search_filtered`).  Where fewer than `topk` of them are in the index a query gets that many hits and no more:
+        the search's padding is dropped, not mapped to a document as the unfiltered path's is (`_hits_to_dict`)."""
         logger.info("Searching")
         if self.index is None:
             raise ValueError("Index is not initialized")
+        if doc_filter is not None and (self._sharded or self.args.world_size > 1):
+            raise NotImplementedError("doc_filter with an index sharded across ranks: the filtered search serves one local index only")
         if self._sharded:
             return self._search_sharded(topk)
         encoded, lookup = self._load_queries()
         self.query_lookup.extend(lookup)
-        D, I = self.index.search(encoded, topk)
-        result = self._hits_to_dict(D, I, topk)
+        if doc_filter is not None:
+            D, I = self.index.search_filtered(encoded, topk, self._doc_row_filter(doc_filter))
+        else:
+            D, I = self.index.search(encoded, topk)
+        result = self._hits_to_dict(D, I, topk, drop_padding=doc_filter is not None)
         logger.info("End searching with {} queries".format(len(result)))
         return result
 
