@@ -33,7 +33,7 @@
 #include <tuple>
 #include <vector>
 
-#include "attn_chunked.h"
+#include "attn_chunked_wide.h"
 
 namespace {
 
@@ -133,66 +133,56 @@ __global__ __launch_bounds__(256) void rope_gqa_rows_kernel(T* __restrict__ qkv,
   rope_rotate4(qkv + row * (int64_t)pitch + (int64_t)seg * 64 + i0, tab + (size_t)(tok % L) * 32 + i0);
 }
 
-// rows of the grouped projection [M, (heads + 2 kv_heads) * 64] (q heads | k heads | v heads) and of ctx [M, heads * 64] for the
-// sequence whose first row is row0 (b * L padded, cu[b] packed), query head h: it reads K / V head h / (heads / kv_heads) (HF repeat_kv)
-template <typename T>
-__device__ __forceinline__ AttnRows<T> causal_rows(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
-  const int kvh = h / (heads / kv_heads);
-  const int pitch = (heads + 2 * kv_heads) * 64;
-  const T* const row = qkv + row0 * pitch;
-  const T* const k = row + (heads + kvh) * 64;
-  return {row + h * 64, k, k + kv_heads * 64, pitch, ctx + row0 * (int64_t)(heads * 64) + h * 64, heads * 64};
-}
-
+// The wrappers: what they do is written once in attn_chunked_wide.h (attn_grouped_padded / attn_grouped_packed).
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attention_causal16_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale,
     const int* __restrict__ kmax) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int kend = kmax ? __builtin_amdgcn_readfirstlane(kmax[b]) : L;
-  attn_chunked16<T, AttnCausal, false, false>(causal_rows(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kend, blockIdx.y * 128, scale,
-                                              AttnFullArgs{});
+  attn_grouped_padded<64>(qkv, ctx, mask, L, heads, kv_heads, scale, AttnCausal{}, kmax);
 }
 
 __global__ __launch_bounds__(256) void attention_causal32_kernel(
     const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale,
     const int* __restrict__ kmax) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  attn_chunked_qreg<float, AttnCausal>(causal_rows(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128,
-                                       scale, AttnFullArgs{});
+  attn_grouped_padded<64>(qkv, ctx, mask, L, heads, kv_heads, scale, AttnCausal{}, kmax);
 }
 
-// Packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 (omk_pack_rows), which is the body's L and its key extent; the mask row keeps
-// the padded pitch Lp, so leading pad tokens inside the extent stay masked.  The grid is the padded launch's, (heads * B,
-// ceil(Lp / 128)): a query block at or past the sequence's end -- every block of a sequence the row bound clamped to no rows -- leaves
-// before it touches LDS or memory, so no row outside [cu[b], cu[b + 1]) is read or written.
+// Packed rows: a query block at or past its sequence's end leaves before it touches LDS or memory.
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attention_causal16_packed_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
     const int* __restrict__ cu) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int row0 = __builtin_amdgcn_readfirstlane(cu[b]);
-  const int Lb = __builtin_amdgcn_readfirstlane(cu[b + 1]) - row0;
-  const int qb = blockIdx.y * 128;
-  if (qb >= Lb) return;
-  attn_chunked16<T, AttnCausal, false, false>(causal_rows(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale,
-                                              AttnFullArgs{});
+  attn_grouped_packed<64>(qkv, ctx, mask, Lp, heads, kv_heads, scale, AttnCausal{}, cu);
 }
 
 __global__ __launch_bounds__(256) void attention_causal32_packed_kernel(
     const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
     const int* __restrict__ cu) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int row0 = cu[b];
-  const int Lb = cu[b + 1] - row0;
-  const int qb = blockIdx.y * 128;
-  if (qb >= Lb) return;
-  attn_chunked_qreg<float, AttnCausal>(causal_rows(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale,
-                                       AttnFullArgs{});
+  attn_grouped_packed<64>(qkv, ctx, mask, Lp, heads, kv_heads, scale, AttnCausal{}, cu);
+}
+
+// ext: kmax [B] (padded rows) or cu [B + 1] (packed rows)
+template <typename T>
+int causal_launch_as(bool packed, dim3 grid, hipStream_t s, const void* qkv, void* ctx, const int64_t* mask, int L, int heads, int kv_heads, float scale,
+                     const int* ext) {
+  if constexpr (std::is_same<T, float>::value) {
+    constexpr int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
+    return attn_launch_form<attention_causal32_kernel, attention_causal32_packed_kernel, float>(packed, grid, lds, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext);
+  } else {
+    constexpr int lds = 2 * 128 * 128 + 128 * 4;
+    return attn_launch_form<attention_causal16_kernel<T>, attention_causal16_packed_kernel<T>, T>(packed, grid, lds, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext);
+  }
+}
+
+// both forms, after the entry's checks: float32, or one of the 16-bit formats (every other dtype code counts as bfloat16)
+int causal_launch(int dtype, bool packed, int64_t B, int L, int heads, int kv_heads, const void* qkv, void* ctx, const int64_t* mask, float scale,
+                  const int* ext, hipStream_t s) {
+  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
+  const int rc = dtype == OM_F32 ? causal_launch_as<float>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext)
+                                 : attn_with_type16(dtype, [&](auto t) { return causal_launch_as<decltype(t)>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext); });
+  if (rc) return 1;
+  OM_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
@@ -250,20 +240,7 @@ int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* m
   if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
   if (check_gqa(heads, kv_heads)) return 1;
   if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
-  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
-  if (dtype == OM_F32) {
-    const int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
-    if (attn_lds_once<attention_causal32_kernel>(lds)) return 1;
-    hipLaunchKernelGGL(attention_causal32_kernel, grid, dim3(256), lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, kmax);
-  } else {
-    const int lds = 2 * 128 * 128 + 128 * 4;
-    if (dtype == OM_F16)
-      hipLaunchKernelGGL(attention_causal16_kernel<f16_t>, grid, dim3(256), lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
-    else
-      hipLaunchKernelGGL(attention_causal16_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
-  }
-  OM_LAUNCH_CHECK();
-  return 0;
+  return causal_launch(dtype, false, B, L, heads, kv_heads, qkv, ctx, mask, scale, kmax, s);
 }
 
 // the same two bodies over packed rows: cu [B + 1] from omk_pack_rows (its offsets are clamped to the row bound, so a bound that is too
@@ -275,20 +252,7 @@ int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int
   if (check_gqa(heads, kv_heads)) return 1;
   if (!cu) OM_FAIL("causal attention over packed rows: the sequence offsets cu");
   if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
-  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
-  if (dtype == OM_F32) {
-    const int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
-    if (attn_lds_once<attention_causal32_packed_kernel>(lds)) return 1;
-    hipLaunchKernelGGL(attention_causal32_packed_kernel, grid, dim3(256), lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, cu);
-  } else {
-    const int lds = 2 * 128 * 128 + 128 * 4;
-    if (dtype == OM_F16)
-      hipLaunchKernelGGL(attention_causal16_packed_kernel<f16_t>, grid, dim3(256), lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
-    else
-      hipLaunchKernelGGL(attention_causal16_packed_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
-  }
-  OM_LAUNCH_CHECK();
-  return 0;
+  return causal_launch(dtype, true, B, L, heads, kv_heads, qkv, ctx, mask, scale, cu, s);
 }
 
 // Test hooks (tests/test_attention_causal.py, tools/causal_lm_bench.py; attention_causal128.hip's share the buffer).  The key extents go into a grow-only device buffer the hook

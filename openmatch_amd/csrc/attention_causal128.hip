@@ -4,7 +4,7 @@
 //     [M, (heads + 2 kv_heads) * 128] (q heads | k heads | v heads), ctx rows [M, heads * 128].  Grid, policy (AttnCausal), key
 //     extents and the packed form are those of omk_attention_causal: one workgroup of 256 threads per (sequence, query head,
 //     128-query block) walking 128-key chunks up to the diagonal chunk, clipped to kmax[b] or the packed extent.  The bodies are
-//     attn_chunked128.h.
+//     attn_chunked_wide.h at D = 128.
 //
 //   * omk_qknorm_rope: the per-head RMSNorm of q and k (Qwen3Attention.forward: q_norm(q_proj(x).view(.., head_dim)), k_norm alike)
 //     and the rotary positions in ONE pass over the q and k columns, for head_dim 64 or 128, norm or no norm (a NULL weight vector:
@@ -21,64 +21,48 @@
 //     cos / sin come from omk_rope_table's device table of D / 2 columns per position.
 //     Gemma3 (gemma = 1, head_dim 256, 32 lanes per head): Gemma3RMSNorm multiplies the f32 normalised value by (1 + weight) and
 //     casts once at the end, so that mode has no rounding between the two multiplies and takes g = 1 + w from the host.
-#include "attn_chunked128.h"
+#include "attn_chunked_wide.h"
 
 namespace {
 
-// attention_causal.hip's causal_rows with 128 columns per head
-template <typename T>
-__device__ __forceinline__ AttnRows<T> causal_rows_d128(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
-  const int kvh = h / (heads / kv_heads);
-  const int pitch = (heads + 2 * kv_heads) * 128;
-  const T* const row = qkv + row0 * pitch;
-  const T* const k = row + (heads + kvh) * 128;
-  return {row + h * 128, k, k + kv_heads * 128, pitch, ctx + row0 * (int64_t)(heads * 128) + h * 128, heads * 128};
-}
-
+// The wrappers: what they do is written once in attn_chunked_wide.h (attn_grouped_padded / attn_grouped_packed).
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attention_causal16_d128_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale,
     const int* __restrict__ kmax) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int kend = kmax ? __builtin_amdgcn_readfirstlane(kmax[b]) : L;
-  attn_chunked16_d128<T, AttnCausal>(causal_rows_d128(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kend, blockIdx.y * 128, scale);
+  attn_grouped_padded<128>(qkv, ctx, mask, L, heads, kv_heads, scale, AttnCausal{}, kmax);
 }
 
 __global__ __launch_bounds__(256) void attention_causal32_d128_kernel(
     const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale,
     const int* __restrict__ kmax) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  attn_chunked32_d128<AttnCausal>(causal_rows_d128(qkv, ctx, b * L, heads, kv_heads, h), AttnCausal{}, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128,
-                                  scale);
+  attn_grouped_padded<128>(qkv, ctx, mask, L, heads, kv_heads, scale, AttnCausal{}, kmax);
 }
 
-// packed rows, as attention_causal16_packed_kernel: sequence b is rows cu[b] .. cu[b + 1] - 1, the mask row keeps the padded pitch Lp;
-// a query block at or past the sequence's end leaves before it touches LDS or memory
+// Packed rows: a query block at or past its sequence's end leaves before it touches LDS or memory.
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attention_causal16_d128_packed_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
     const int* __restrict__ cu) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int row0 = __builtin_amdgcn_readfirstlane(cu[b]);
-  const int Lb = __builtin_amdgcn_readfirstlane(cu[b + 1]) - row0;
-  const int qb = blockIdx.y * 128;
-  if (qb >= Lb) return;
-  attn_chunked16_d128<T, AttnCausal>(causal_rows_d128(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale);
+  attn_grouped_packed<128>(qkv, ctx, mask, Lp, heads, kv_heads, scale, AttnCausal{}, cu);
 }
 
 __global__ __launch_bounds__(256) void attention_causal32_d128_packed_kernel(
     const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale,
     const int* __restrict__ cu) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int row0 = cu[b];
-  const int Lb = cu[b + 1] - row0;
-  const int qb = blockIdx.y * 128;
-  if (qb >= Lb) return;
-  attn_chunked32_d128<AttnCausal>(causal_rows_d128(qkv, ctx, (int64_t)row0, heads, kv_heads, h), AttnCausal{}, mask + b * Lp, Lb, Lb, qb, scale);
+  attn_grouped_packed<128>(qkv, ctx, mask, Lp, heads, kv_heads, scale, AttnCausal{}, cu);
+}
+
+// ext: kmax [B] (padded rows) or cu [B + 1] (packed rows)
+template <typename T>
+int causal_d128_launch_as(bool packed, dim3 grid, hipStream_t s, const void* qkv, void* ctx, const int64_t* mask, int L, int heads, int kv_heads,
+                          float scale, const int* ext) {
+  if constexpr (std::is_same<T, float>::value)
+    return attn_launch_form<attention_causal32_d128_kernel, attention_causal32_d128_packed_kernel, float>(packed, grid, AttnWide<128>::LDS32, s, qkv, ctx, mask, L,
+                                                                                                            heads, kv_heads, scale, ext);
+  else
+    return attn_launch_form<attention_causal16_d128_kernel<T>, attention_causal16_d128_packed_kernel<T>, T>(packed, grid, AttnWide<128>::LDS16, s, qkv, ctx, mask, L,
+                                                                                                              heads, kv_heads, scale, ext);
 }
 
 // ---- q / k RMSNorm + rotary positions ---------------------------------------------------------------------------------------
@@ -205,31 +189,12 @@ static int attention_causal_d128_launch(int dtype, const void* qkv, void* ctx, c
   if (check_gqa_d(heads, kv_heads, 128)) return 1;
   if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
   const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
-  if (dtype == OM_F32) {
-    if (cu) {
-      if (attn_lds_once<attention_causal32_d128_packed_kernel>(kAttn32D128Lds)) return 1;
-      hipLaunchKernelGGL(attention_causal32_d128_packed_kernel, grid, dim3(256), kAttn32D128Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, cu);
-    } else {
-      if (attn_lds_once<attention_causal32_d128_kernel>(kAttn32D128Lds)) return 1;
-      hipLaunchKernelGGL(attention_causal32_d128_kernel, grid, dim3(256), kAttn32D128Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads, scale, kmax);
-    }
-  } else if (dtype == OM_F16) {
-    if (cu) {
-      if (attn_lds_once<attention_causal16_d128_packed_kernel<f16_t>>(kAttn16D128Lds)) return 1;
-      hipLaunchKernelGGL(attention_causal16_d128_packed_kernel<f16_t>, grid, dim3(256), kAttn16D128Lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
-    } else {
-      if (attn_lds_once<attention_causal16_d128_kernel<f16_t>>(kAttn16D128Lds)) return 1;
-      hipLaunchKernelGGL(attention_causal16_d128_kernel<f16_t>, grid, dim3(256), kAttn16D128Lds, s, (const f16_t*)qkv, (f16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
-    }
-  } else {
-    if (cu) {
-      if (attn_lds_once<attention_causal16_d128_packed_kernel<bf16_t>>(kAttn16D128Lds)) return 1;
-      hipLaunchKernelGGL(attention_causal16_d128_packed_kernel<bf16_t>, grid, dim3(256), kAttn16D128Lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, cu);
-    } else {
-      if (attn_lds_once<attention_causal16_d128_kernel<bf16_t>>(kAttn16D128Lds)) return 1;
-      hipLaunchKernelGGL(attention_causal16_d128_kernel<bf16_t>, grid, dim3(256), kAttn16D128Lds, s, (const bf16_t*)qkv, (bf16_t*)ctx, mask, L, heads, kv_heads, scale, kmax);
-    }
-  }
+  // float32, or one of the 16-bit formats (every other dtype code counts as bfloat16)
+  const bool packed = cu != nullptr;
+  const int* const ext = packed ? cu : kmax;
+  const int rc = dtype == OM_F32 ? causal_d128_launch_as<float>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext)
+                                 : attn_with_type16(dtype, [&](auto t) { return causal_d128_launch_as<decltype(t)>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext); });
+  if (rc) return 1;
   OM_LAUNCH_CHECK();
   return 0;
 }

@@ -8,7 +8,7 @@
 //     (sequence, query head, 128-query block) walks 64-key chunks clipped to kmax[b] (keys at or past it are padding); with a band it
 //     walks only the keys [qb - w, qb + 127 + w] its queries can reach.  0 < w < L - 1 is the band (AttnBand), anything else full
 //     attention (AttnFull): a window that reaches every key never takes the band kernel, so the two give the same bits there.
-//     The bodies are attn_chunked256.h; 16-bit x {full, band} per format, float32 x {full, band}.
+//     The bodies are attn_chunked_wide.h at D = 256; 16-bit x {full, band} per format, float32 x {full, band}.
 //     A wave of either body holds more than 256 registers (no __launch_bounds__ second argument): one workgroup per CU.
 //
 //   * omk_attention_gqa_d256_packed: the same over PACKED rows, under the contract of attention_causal16_d128_packed_kernel: sequence b
@@ -18,105 +18,53 @@
 //     reads nothing past the buffer.  Band or full is decided on the PADDED L, as above: the packed launch runs the body the padded
 //     launch of the same batch runs and agrees with it bit for bit on every row up to each extent.  Thin wrappers over the same two
 //     bodies: six more kernels with the padded ones' register counts and no scratch.
-#include "attn_chunked256.h"
+#include "attn_chunked_wide.h"
 
 namespace {
 
-// rows of the grouped projection and of ctx for the sequence whose first row is row0, query head h (attention_causal.hip causal_rows
-// with 256 columns per head)
-template <typename T>
-__device__ __forceinline__ AttnRows<T> gqa_rows_d256(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
-  const int kvh = h / (heads / kv_heads);
-  const int pitch = (heads + 2 * kv_heads) * 256;
-  const T* const row = qkv + row0 * pitch;
-  const T* const k = row + (heads + kvh) * 256;
-  return {row + h * 256, k, k + kv_heads * 256, pitch, ctx + row0 * (int64_t)(heads * 256) + h * 256, heads * 256};
-}
-
+// The wrappers: what they do is written once in attn_chunked_wide.h (attn_grouped_padded / attn_grouped_packed).
 template <typename T, typename Policy>
 __global__ __launch_bounds__(256) void attention_d256_16_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale, Policy pol,
     const int* __restrict__ kmax) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int kend = kmax ? __builtin_amdgcn_readfirstlane(kmax[b]) : L;
-  attn_chunked16_d256<T, Policy>(gqa_rows_d256(qkv, ctx, b * L, heads, kv_heads, h), pol, mask + b * L, L, kend, blockIdx.y * 128, scale);
+  attn_grouped_padded<256>(qkv, ctx, mask, L, heads, kv_heads, scale, pol, kmax);
 }
 
 template <typename Policy>
 __global__ __launch_bounds__(256) void attention_d256_32_kernel(
     const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int L, int heads, int kv_heads, float scale, Policy pol,
     const int* __restrict__ kmax) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  attn_chunked32_d256<Policy>(gqa_rows_d256(qkv, ctx, b * L, heads, kv_heads, h), pol, mask + b * L, L, kmax ? kmax[b] : L, blockIdx.y * 128, scale);
+  attn_grouped_padded<256>(qkv, ctx, mask, L, heads, kv_heads, scale, pol, kmax);
 }
 
-// packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1, the mask row keeps the padded pitch Lp; a query block at or past the
-// sequence's end leaves before it touches LDS or memory
+// Packed rows: a query block at or past its sequence's end leaves before it touches LDS or memory.
 template <typename T, typename Policy>
 __global__ __launch_bounds__(256) void attention_d256_16_packed_kernel(
     const T* __restrict__ qkv, T* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale, Policy pol,
     const int* __restrict__ cu) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int row0 = __builtin_amdgcn_readfirstlane(cu[b]);
-  const int Lb = __builtin_amdgcn_readfirstlane(cu[b + 1]) - row0;
-  const int qb = blockIdx.y * 128;
-  if (qb >= Lb) return;
-  attn_chunked16_d256<T, Policy>(gqa_rows_d256(qkv, ctx, (int64_t)row0, heads, kv_heads, h), pol, mask + b * Lp, Lb, Lb, qb, scale);
+  attn_grouped_packed<256>(qkv, ctx, mask, Lp, heads, kv_heads, scale, pol, cu);
 }
 
 template <typename Policy>
 __global__ __launch_bounds__(256) void attention_d256_32_packed_kernel(
     const float* __restrict__ qkv, float* __restrict__ ctx, const int64_t* __restrict__ mask, int Lp, int heads, int kv_heads, float scale, Policy pol,
     const int* __restrict__ cu) {
-  const int h = blockIdx.x % heads;
-  const int64_t b = blockIdx.x / heads;
-  const int row0 = cu[b];
-  const int Lb = cu[b + 1] - row0;
-  const int qb = blockIdx.y * 128;
-  if (qb >= Lb) return;
-  attn_chunked32_d256<Policy>(gqa_rows_d256(qkv, ctx, (int64_t)row0, heads, kv_heads, h), pol, mask + b * Lp, Lb, Lb, qb, scale);
+  attn_grouped_packed<256>(qkv, ctx, mask, Lp, heads, kv_heads, scale, pol, cu);
 }
 
-// ext: kmax [B] (padded rows) or cu [B + 1] (PACKED rows): one launch function per body for both forms
-template <typename T, typename Policy>
-int launch16(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* ext,
-             bool packed, hipStream_t s) {
-  if (packed) {
-    if (attn_lds_once<attention_d256_16_packed_kernel<T, Policy>>(kAttn16D256Lds)) return 1;
-    hipLaunchKernelGGL((attention_d256_16_packed_kernel<T, Policy>), grid, dim3(256), kAttn16D256Lds, s, (const T*)qkv, (T*)ctx, mask, L, heads,
-                       kv_heads, scale, pol, ext);
-    return 0;
-  }
-  if (attn_lds_once<attention_d256_16_kernel<T, Policy>>(kAttn16D256Lds)) return 1;
-  hipLaunchKernelGGL((attention_d256_16_kernel<T, Policy>), grid, dim3(256), kAttn16D256Lds, s, (const T*)qkv, (T*)ctx, mask, L, heads, kv_heads, scale,
-                     pol, ext);
-  return 0;
-}
-
-template <typename Policy>
-int launch32(const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol, const int* ext,
-             bool packed, hipStream_t s) {
-  if (packed) {
-    if (attn_lds_once<attention_d256_32_packed_kernel<Policy>>(kAttn32D256Lds)) return 1;
-    hipLaunchKernelGGL((attention_d256_32_packed_kernel<Policy>), grid, dim3(256), kAttn32D256Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads,
-                       kv_heads, scale, pol, ext);
-    return 0;
-  }
-  if (attn_lds_once<attention_d256_32_kernel<Policy>>(kAttn32D256Lds)) return 1;
-  hipLaunchKernelGGL((attention_d256_32_kernel<Policy>), grid, dim3(256), kAttn32D256Lds, s, (const float*)qkv, (float*)ctx, mask, L, heads, kv_heads,
-                     scale, pol, ext);
-  return 0;
-}
-
+// ext: kmax [B] (padded rows) or cu [B + 1] (PACKED rows); every dtype code but the two 16-bit ones counts as float32
 template <typename Policy>
 int launch_policy(int dtype, const void* qkv, void* ctx, const int64_t* mask, dim3 grid, int L, int heads, int kv_heads, float scale, Policy pol,
                   const int* ext, bool packed, hipStream_t s) {
-  if (dtype == OM_F16) return launch16<f16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, ext, packed, s);
-  if (dtype == OM_BF16) return launch16<bf16_t>(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, ext, packed, s);
-  return launch32(qkv, ctx, mask, grid, L, heads, kv_heads, scale, pol, ext, packed, s);
+  return attn_with_type(dtype, [&](auto t) {
+    typedef decltype(t) T;
+    if constexpr (std::is_same<T, float>::value)
+      return attn_launch_form<attention_d256_32_kernel<Policy>, attention_d256_32_packed_kernel<Policy>, float>(packed, grid, AttnWide<256>::LDS32, s, qkv, ctx, mask, L,
+                                                                                                                  heads, kv_heads, scale, pol, ext);
+    else
+      return attn_launch_form<attention_d256_16_kernel<T, Policy>, attention_d256_16_packed_kernel<T, Policy>, T>(packed, grid, AttnWide<256>::LDS16, s, qkv, ctx, mask, L,
+                                                                                                                    heads, kv_heads, scale, pol, ext);
+  });
 }
 
 int check_args(int64_t B, int L, int heads, int kv_heads) {

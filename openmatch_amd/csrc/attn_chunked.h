@@ -37,6 +37,17 @@ __device__ __forceinline__ AttnRows<T> attn_rows_fused(const T* qkv, T* ctx, int
   return {base, base + H, base + 2 * H, 3 * (int64_t)H, ctx + row0 * (int64_t)H + h * 64, H};
 }
 
+// the grouped projection [M, (heads + 2 kv_heads) * D] (q heads | k heads | v heads) and ctx [M, heads * D] for the sequence whose
+// first row is row0 (b * L padded, cu[b] packed), query head h: it reads K / V head h / (heads / kv_heads) (HF repeat_kv)
+template <int D, typename T>
+__device__ __forceinline__ AttnRows<T> attn_rows_grouped(const T* qkv, T* ctx, int64_t row0, int heads, int kv_heads, int h) {
+  const int kvh = h / (heads / kv_heads);
+  const int pitch = (heads + 2 * kv_heads) * D;
+  const T* const row = qkv + row0 * pitch;
+  const T* const k = row + (heads + kvh) * D;
+  return {row + h * D, k, k + kv_heads * D, pitch, ctx + row0 * (int64_t)(heads * D) + h * D, heads * D};
+}
+
 // What the full-attention kernels alone take: the T5 bias table and dropout, both keyed with the padded pitch Lm (also for packed
 // rows: the backward kernels and a packed step regenerate the same dropout mask).  Band and causal pass AttnFullArgs{}.
 struct AttnFullArgs {

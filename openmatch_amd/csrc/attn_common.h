@@ -38,6 +38,19 @@ static int attn_lds_once(int lds) {
   }
   return 0;
 }
+// Launch the Padded or the Packed kernel of one body (one signature: the projection, ctx, then `rest`, whose last argument is kmax
+// for the one and cu for the other) on `grid` x 256 threads with `lds` bytes of dynamic LDS; the caller checks the launch.
+template <auto Padded, auto Packed, typename T, typename... Rest>
+static int attn_launch_form(bool packed, dim3 grid, int lds, hipStream_t s, const void* qkv, void* ctx, Rest... rest) {
+  if (packed) {
+    if (attn_lds_once<Packed>(lds)) return 1;
+    hipLaunchKernelGGL(Packed, grid, dim3(256), lds, s, (const T*)qkv, (T*)ctx, rest...);
+  } else {
+    if (attn_lds_once<Padded>(lds)) return 1;
+    hipLaunchKernelGGL(Padded, grid, dim3(256), lds, s, (const T*)qkv, (T*)ctx, rest...);
+  }
+  return 0;
+}
 
 template <typename T> struct AttnGeom;
 template <> struct AttnGeom<bf16_t> {

@@ -1,5 +1,5 @@
 """The kernels EmbeddingGemma adds, alone: bidirectional grouped-query attention over heads of 256 columns, full and banded
-(csrc/attention_d256.hip, csrc/attn_chunked256.h), against the float64 restatement of tests/test_attention_kernels.py under its
+(csrc/attention_d256.hip, csrc/attn_chunked_wide.h), against the float64 restatement of tests/test_attention_kernels.py under its
 per-element bound with D = 256; the q / k RMSNorm + rotary pass at D = 256 in Gemma3's form against HF's own Gemma3RMSNorm and
 apply_rotary_pos_emb; and the norm of a sublayer output added into the f32 residual stream against float64 under ln_fwd_bound."""
 import ctypes as C

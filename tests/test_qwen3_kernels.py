@@ -1,4 +1,4 @@
-"""The kernels a Qwen3 embedder adds, alone (csrc/attention_causal128.hip, csrc/attn_chunked128.h): causal grouped-query attention over
+"""The kernels a Qwen3 embedder adds, alone (csrc/attention_causal128.hip, csrc/attn_chunked_wide.h): causal grouped-query attention over
 heads of 128 columns against the float64 restatement of tests/test_attention_kernels.py under its per-element bound (error_bound takes
 D), padded and packed, and the q / k RMSNorm + rotary pass against HF's own Qwen3RMSNorm and apply_rotary_pos_emb."""
 import ctypes as C
