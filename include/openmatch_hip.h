@@ -1078,6 +1078,30 @@ int om_debug_search_filter_estimate(int mode, int64_t N, int k, int64_t n_allowe
  * workspace: om_sim_topk_async_workspace_bytes(n_queries, d, 1), 256-byte aligned. */
 int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows, int64_t N, int d, const float* queries, int64_t n_queries,
                           const uint32_t* cand, int m, float* out_scores, void* workspace, size_t workspace_bytes, void* stream);
+/* The list kernels of a search -- everything between the scan's appends and (D, I) -- over a caller's lists, without a search; each is
+ * launched as the search launches it (grid, block, dynamic LDS, the workspace's own arrays).
+ * Lists in: scores / rows [n_queries][m] (f32 / uint32, device); list q gets pack_key(scores[q][j], rows[q][j]) in slot j < m and STALE keys
+ * (score +inf, row 0xf0000000 + slot) in the slots m .. 8191 of its 8192-slot stride.  counts [n_queries] (uint32, device) is written to the
+ * list counters as it is: a count above m names stale slots, one above 8192 is a round whose appends were dropped (at most 16384 is taken).
+ * Before the kernel: cnt_prev = 0xffffffff, thr = NaN (bits 0x7fc00000), flag[0..15] = 0, qstat = 0.
+ * op: */
+#define OM_DEBUG_LISTS_RADIX 0     /* select_radix_kernel(k, margin, cap: 4096 | 8192)                                                  */
+#define OM_DEBUG_LISTS_SORT 1      /* select_kernel(k, margin)                                                                          */
+#define OM_DEBUG_LISTS_DROP 2      /* drop_disallowed_kernel(allow: (nrows + 31) / 32 words on the device, nrows >= 1)                  */
+#define OM_DEBUG_LISTS_APPEND 3    /* append_dense_kernel(S [n_queries][ldS] f32, 1 <= n <= 4096, ldS >= n, row_base), then check_overflow_kernel(cover) */
+#define OM_DEBUG_LISTS_EMIT 4      /* emit_kernel(k, id_offset) into emit_scores / emit_ids [n_queries][k]                              */
+/* margin [n_queries] (f32, device) or NULL: certified or exact mode of the two selections (copied into the workspace's margins).
+ * use_qstat 0: the kernels get a null qstat, as on om_sim_topk's path.  Arguments an op does not take are not read.
+ * Lists out (any of the three may be NULL): out_scores / out_rows [n_queries][8192], the whole stride of every list, stale slots included;
+ * out_state [n_queries][4] uint32 = {cnt, cnt_prev, bits of thr, qstat}, followed by flag[0..3].
+ * 1 to 65535 queries, k in [1, 2048], m in [1, 8192]; workspace: om_sim_topk_async_workspace_bytes(n_queries, 64, 1), 256-byte aligned. */
+int om_debug_select_lists(int op, int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts, int k,
+                          const float* margin, int use_qstat, int cap, const uint32_t* allow, uint32_t nrows, const float* S, int64_t ldS,
+                          int n, uint32_t row_base, uint32_t cover, int64_t id_offset, float* emit_scores, int64_t* emit_ids,
+                          float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes, void* stream);
+/* query_prep_kernel on the grid of the search: queries [n_queries][d] f32 and stats[2] = {max ||p - f16(p)||, max ||f16(p)||} on the
+ * device -> out_q16 [round_up(n_queries, 256)][d] float16 (rows beyond n_queries zero) and the certified margins out_margin [n_queries]. */
+int om_debug_query_prep(const float* queries, int64_t n_queries, int d, const float* stats, void* out_q16, float* out_margin, void* stream);
 
 /* Diagnostics of the calling thread's last om_sim_topk: out[0] = scan precision that produced
  * the result (0 f32, 1 f16+rescore), [1] = scan rounds, [2] = overflow fallbacks (chunks redone

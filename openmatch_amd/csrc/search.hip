@@ -36,7 +36,8 @@
 static_assert(SORT_CAP == SEARCH_SORT_CAP && DENSE_CHUNK == SEARCH_DENSE_CHUNK, "search_plan.h schedules for these list and bootstrap sizes");
 
 // Per-query sticky status of the asynchronous entry (`qstat`, nullptr on om_sim_topk's path): a query with any bit set is recomputed by the
-// on-device redo.  The global flags (flag[0] overflow, flag[1] longest list, flag[2] margin too wide) stay as they are.
+// on-device redo.  The global flags (flag[0] overflow, flag[1] longest list, flag[2] margin too wide or not finite) stay as they are: they
+// are all om_sim_topk's path has.
 #define QSTAT_OVERFLOW 1u    // the list exceeded SORT_CAP in some round: appends were dropped
 #define QSTAT_WIDE 2u        // a certified list outgrew LIST_MAX (or the certified margin is not finite)
 #define QSTAT_COVER 4u       // the final list is longer than the re-score cover
@@ -1024,7 +1025,7 @@ __device__ inline void bitonic_sort_desc(u64* s, int P, int tid, int nthr) {
 
 // Sort one list, keep the best k (exact mode) or everything within margin[q] of the k-th
 // best (certified f16 mode), publish the new threshold.  flag[1] = max list length,
-// flag[2] |= a certified list outgrew LIST_MAX.
+// flag[2] |= a certified list outgrew LIST_MAX, or the certified margin is not finite.
 __global__ __launch_bounds__(SORT_THREADS) void select_kernel(
     u64* __restrict__ keys, unsigned* __restrict__ cnt, unsigned* __restrict__ cnt_prev,
     float* __restrict__ thr, const float* __restrict__ margin, int k, unsigned* __restrict__ flag,
@@ -1071,8 +1072,9 @@ __global__ __launch_bounds__(SORT_THREADS) void select_kernel(
     cnt_prev[q] = keep;
     thr[q] = th;
     atomicMax(flag + 1, keep);
-    if (keep > LIST_MAX) atomicOr(flag + 2, 1u);
-    if (qstat && margin && (keep > LIST_MAX || !(margin[q] < INFINITY))) atomicOr(qstat + q, QSTAT_WIDE);
+    const bool wide = keep > LIST_MAX || (margin && !(margin[q] < INFINITY));
+    if (wide) atomicOr(flag + 2, 1u);
+    if (qstat && margin && wide) atomicOr(qstat + q, QSTAT_WIDE);
   }
 }
 
@@ -1100,8 +1102,12 @@ __global__ __launch_bounds__(256) void select_radix_kernel(
     }
     n = SORT_CAP;
   }
-  // (a margin that is not finite -- a value of the index beyond f16 -- certifies nothing: inf - inf is a NaN cut that keeps no key)
-  if (qstat && margin && tid == 0 && !(margin[q] < INFINITY)) atomicOr(qstat + q, QSTAT_WIDE);
+  // (a margin that is not finite -- a value of the index or of the query beyond f16 -- certifies nothing: inf - inf is a NaN cut that
+  // keeps no key.  flag[2] as well: om_sim_topk has no qstat, and a list cut down to nothing would never outgrow LIST_MAX)
+  if (margin && tid == 0 && !(margin[q] < INFINITY)) {
+    atomicOr(flag + 2, 1u);
+    if (qstat) atomicOr(qstat + q, QSTAT_WIDE);
+  }
   u64* list = keys + q * SORT_CAP;
   // a list longer than the LDS copy (rare: the host sizes `cap` with a 2x margin) is read from global memory in every
   // pass (64 KiB, L2-resident) and only the survivors are staged
@@ -2343,6 +2349,106 @@ extern "C" int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows
   }
   OM_LAUNCH_CHECK();
   hipLaunchKernelGGL(debug_read_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, cand, m, N, kernel == 2 ? 1 : 0, out_scores);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- om_debug_select_lists / om_debug_query_prep: the list kernels (selections, drop, dense append, emit) and the query preparation -------
+// over a caller's lists, launched as Scan launches them
+#define DEBUG_STALE_ROW 0xf0000000u      // stale slots: score +inf, row DEBUG_STALE_ROW + slot
+__global__ void debug_put_lists_kernel(const float* __restrict__ scores, const uint32_t* __restrict__ rows, const uint32_t* __restrict__ counts,
+                                       const float* __restrict__ margin_in, int m, u64* __restrict__ keys, unsigned* __restrict__ cnt,
+                                       unsigned* __restrict__ cnt_prev, float* __restrict__ thr, float* __restrict__ margin,
+                                       unsigned* __restrict__ flag, unsigned* __restrict__ qstat) {
+  const int64_t q = blockIdx.x;
+  for (int j = threadIdx.x; j < SORT_CAP; j += blockDim.x)
+    keys[q * SORT_CAP + j] = j < m ? pack_key(scores[q * m + j], rows[q * m + j]) : pack_key(INFINITY, DEBUG_STALE_ROW + (uint32_t)j);
+  if (threadIdx.x == 0) {
+    cnt[q] = counts[q] < 2u * SORT_CAP ? counts[q] : 2u * SORT_CAP;
+    cnt_prev[q] = 0xffffffffu;
+    thr[q] = __builtin_nanf("");
+    margin[q] = margin_in ? margin_in[q] : 0.f;
+    qstat[q] = 0u;
+  }
+  if (q == 0 && threadIdx.x < 16) flag[threadIdx.x] = 0u;
+}
+__global__ void debug_get_lists_kernel(const u64* __restrict__ keys, const unsigned* __restrict__ cnt, const unsigned* __restrict__ cnt_prev,
+                                       const float* __restrict__ thr, const unsigned* __restrict__ flag, const unsigned* __restrict__ qstat,
+                                       float* __restrict__ out_scores, uint32_t* __restrict__ out_rows, uint32_t* __restrict__ out_state) {
+  const int64_t q = blockIdx.x, nq = gridDim.x;
+  for (int j = threadIdx.x; j < SORT_CAP; j += blockDim.x) {
+    const u64 key = keys[q * SORT_CAP + j];
+    if (out_scores) out_scores[q * SORT_CAP + j] = key_score(key);
+    if (out_rows) out_rows[q * SORT_CAP + j] = key_payload(key);
+  }
+  if (out_state && threadIdx.x == 0) {
+    out_state[q * 4] = cnt[q]; out_state[q * 4 + 1] = cnt_prev[q];
+    out_state[q * 4 + 2] = __builtin_bit_cast(uint32_t, thr[q]); out_state[q * 4 + 3] = qstat[q];
+  }
+  if (out_state && q == 0 && threadIdx.x < 4) out_state[nq * 4 + threadIdx.x] = flag[threadIdx.x];
+}
+
+extern "C" int om_debug_select_lists(int op, int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts, int k,
+                                     const float* margin, int use_qstat, int cap, const uint32_t* allow, uint32_t nrows, const float* S,
+                                     int64_t ldS, int n, uint32_t row_base, uint32_t cover, int64_t id_offset, float* emit_scores,
+                                     int64_t* emit_ids, float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (op < OM_DEBUG_LISTS_RADIX || op > OM_DEBUG_LISTS_EMIT)
+    OM_FAIL("op must be 0 (radix selection), 1 (sorting selection), 2 (drop), 3 (dense append + overflow check) or 4 (emit)");
+  if (!scores || !rows || !counts) OM_FAIL("null argument: scores, rows and counts describe the lists");
+  if (n_queries < 1 || n_queries > 65535) OM_FAIL("1 to 65535 queries");
+  if (m < 1 || m > SORT_CAP) OM_FAIL("m must be in [1, 8192]");
+  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1, 2048]");
+  if (op == OM_DEBUG_LISTS_RADIX && cap != 4096 && cap != SORT_CAP) OM_FAIL("cap must be 4096 or 8192");
+  if (op == OM_DEBUG_LISTS_DROP && (!allow || nrows < 1)) OM_FAIL("the drop needs the bitmap (null argument) and nrows >= 1");
+  if (op == OM_DEBUG_LISTS_APPEND && (!S || n < 1 || n > DENSE_CHUNK || ldS < n)) OM_FAIL("the dense append needs S (null argument), n in [1, 4096] and ldS >= n");
+  if (op == OM_DEBUG_LISTS_EMIT && (!emit_scores || !emit_ids)) OM_FAIL("null argument: emit writes emit_scores and emit_ids");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
+  const SearchWs ws = carve_search(n_queries, 64, (char*)workspace);
+  const AsyncWs aw = carve_async(n_queries, 64, (char*)workspace);
+  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes(n_queries, 64, 1))");
+  if (search_attrs()) return 1;
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned nq = (unsigned)n_queries;
+  unsigned* const qstat = use_qstat ? aw.qstat : nullptr;
+  const float* const mg = margin ? ws.margin : nullptr;
+  hipLaunchKernelGGL(debug_put_lists_kernel, dim3(nq), dim3(256), 0, s, scores, rows, counts, margin, m, ws.keys, ws.cnt, ws.cnt_prev, ws.thr,
+                     ws.margin, ws.flag, aw.qstat);
+  OM_LAUNCH_CHECK();
+  switch (op) {
+    case OM_DEBUG_LISTS_RADIX:
+      hipLaunchKernelGGL(select_radix_kernel, dim3(nq), dim3(256), (size_t)cap * 8 + 1024 + 64, s, ws.keys, ws.cnt, ws.thr, mg, k, ws.flag, cap,
+                         qstat);
+      break;
+    case OM_DEBUG_LISTS_SORT:
+      hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, mg, k, ws.flag,
+                         qstat);
+      break;
+    case OM_DEBUG_LISTS_DROP:
+      hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, allow, nrows, ws.flag, qstat);
+      break;
+    case OM_DEBUG_LISTS_APPEND:
+      hipLaunchKernelGGL(append_dense_kernel, dim3(nq), dim3(256), 0, s, S, ldS, n, row_base, ws.keys, ws.cnt);
+      OM_LAUNCH_CHECK();
+      hipLaunchKernelGGL(check_overflow_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, ws.cnt, n_queries, ws.flag, qstat, cover);
+      break;
+    default:
+      hipLaunchKernelGGL(emit_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, emit_scores, emit_ids);
+      break;
+  }
+  OM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
+                     out_rows, out_state);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int om_debug_query_prep(const float* queries, int64_t n_queries, int d, const float* stats, void* out_q16, float* out_margin,
+                                   void* stream) {
+  if (!queries || !stats || !out_q16 || !out_margin) OM_FAIL("null argument");
+  if (n_queries < 1 || n_queries > 65535 || d < 1 || d > 16384) OM_FAIL("1 to 65535 queries, d in [1, 16384]");
+  hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((n_queries + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, (hipStream_t)stream, queries,
+                     (f16_t*)out_q16, out_margin, stats, n_queries, d);
   OM_LAUNCH_CHECK();
   return 0;
 }

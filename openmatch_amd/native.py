@@ -39,6 +39,7 @@ SCAN_KERNEL_NAME = {v: k for k, v in SCAN_KERNEL.items()}
 OPT_SCAN_GEN7 = 3
 OPT_ATTENTION_FAST = 2
 SEARCH_F32, SEARCH_F16_RESCORE, SEARCH_F16_ONLY = 0, 1, 2
+DEBUG_LISTS = {"radix": 0, "sort": 1, "drop": 2, "append": 3, "emit": 4}      # OM_DEBUG_LISTS_*: the op of om_debug_select_lists
 ABI_VERSION = 6
 
 c_void_p, c_int, c_int64, c_float, c_size_t = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -340,6 +341,10 @@ _SIGNATURES = {
     "om_index_add_f16": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_debug_rescore_rows": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    "om_debug_select_lists": (c_int, [c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, C.c_uint32,
+                                      c_void_p, c_int64, c_int, C.c_uint32, C.c_uint32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_debug_query_prep": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_sim_topk_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "om_sim_topk": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                             c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
