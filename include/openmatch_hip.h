@@ -1061,6 +1061,40 @@ int om_sim_topk_filtered(int mode, const float* queries, int64_t n_queries, cons
                          const void* index_f16, const float* stats, int64_t N, int d, int k,
                          int64_t id_offset, const uint32_t* allow_bits, int64_t n_allowed, float* out_scores,
                          int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The filtered search with a bitmap PER QUERY: per query exactly what om_sim_topk_filtered returns for that query alone under its
+ * bitmap -- the same scores (the re-score's bits in the two 16-bit modes), ties by ascending row, ids = id_offset + the ORIGINAL row,
+ * (-3.4028235e38, -1) padding when fewer than k rows are allowed -- in ONE chain, so one pass over the index serves every filter.
+ * allow_bits: device memory; bitmap f is the (N + 31) / 32 words at allow_bits + f * words_pitch (words_pitch >= (N + 31) / 32: a padded
+ * pitch is legal, bits at and beyond N and the padding are ignored).  filter_of: device [n_queries] int32, query q is searched under
+ * bitmap filter_of[q]; a value below 0 is "no filter" -- the query returns what om_sim_topk_async returns for it, so filtered and
+ * unfiltered queries share a batch; a value >= n_filters is "nothing allowed" and is never used as an address.  filter_of == NULL: query q
+ * is under bitmap q, and n_filters must equal n_queries.  n_allowed_min: the host's count of set bits among [0, N) of the SPARSEST bitmap
+ * the call uses, N when every query is unfiltered.  It sizes the schedule only (om_debug_search_schedule_filtered with this count): the
+ * lists of a query under a denser bitmap fill more slowly than planned, which costs nothing; the rank of the redo's select is
+ * min(k, a count of the query's own bitmap taken on the device), so a stale value costs speed, never correctness.
+ * The chain is om_sim_topk_filtered's: the drop in front of every selection, the count and the redo read the bitmap of their query.
+ * Enqueues only; legal on a capturing stream after one eager call.  status: as om_sim_topk_async's, may be NULL.
+ * Refuses what om_sim_topk_filtered refuses, n_filters outside [1, 65535], words_pitch below (N + 31) / 32, a NULL filter_of with
+ * n_filters != n_queries, and n_allowed_min outside [0, N].  workspace: om_sim_topk_filtered_multi_workspace_bytes, 256-byte aligned. */
+size_t om_sim_topk_filtered_multi_workspace_bytes(int64_t n_queries, int d, int k, int64_t n_filters);
+int om_sim_topk_filtered_multi(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
+                               const float* stats, int64_t N, int d, int k, int64_t id_offset, const uint32_t* allow_bits,
+                               int64_t words_pitch, int64_t n_filters, const int32_t* filter_of, int64_t n_allowed_min, float* out_scores,
+                               int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The exact top-k of every query over its OWN candidate rows (dense re-ranking of a first-stage run): cand [n_queries][cand_pitch] int32 on
+ * the device, cand[q][j] a row number; any value outside [0, N) is a hole -- skipped, never dereferenced.  Rows must be DISTINCT within a
+ * query: a repeated row is returned twice (openmatch_amd/index.py removes repeats before the call).  Scores are the re-score's dot product
+ * over the rows the mode's re-score reads -- the float32 rows for OM_SEARCH_F32 and OM_SEARCH_F16_RESCORE (index_f16 is not read), the
+ * float16 rows for OM_SEARCH_F16_ONLY (index_f32 is not read) -- so in the two 16-bit modes the bits are those a filtered search returns
+ * for the same rows.  Ties by ascending row, ids = id_offset + row, (-3.4028235e38, -1) padding.  No scan, no margin, no redo: the
+ * chain is fixed by cand_pitch alone -- per block of 4096 candidate columns one scoring kernel (a wavefront per (query, candidate)) and one
+ * sorting selection -- and costs n_queries * cand_pitch * d whatever N.  Enqueues only; capturable after one eager call.
+ * Refuses k outside [1, 2048], d no multiple of 64, more than 65535 queries, N above 2^31 - 1, a misaligned workspace, cand_pitch < 1, a
+ * NULL cand, and a NULL plane of the kind the mode reads.  workspace: om_sim_topk_candidates_workspace_bytes, 256-byte aligned. */
+size_t om_sim_topk_candidates_workspace_bytes(int64_t n_queries, int d, int k);
+int om_sim_topk_candidates(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16, int64_t N, int d,
+                           int k, int64_t id_offset, const int32_t* cand, int64_t cand_pitch, float* out_scores, int64_t* out_ids,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* The schedule of om_sim_topk_filtered (csrc/search_plan.h search_schedule_filtered: no launch, no HIP call): *boot dense chunks of 4096
  * rows -- the smallest count whose expected allowed rows reach 2 k, at most all rows -- then *n filtered rounds of chunks[i] rows, the
  * first of which starts at row *boot * 4096, sized from the list estimate of k_eff.  n_allowed == N: om_debug_search_schedule's. */
@@ -1099,6 +1133,14 @@ int om_debug_select_lists(int op, int64_t n_queries, int m, const float* scores,
                           const float* margin, int use_qstat, int cap, const uint32_t* allow, uint32_t nrows, const float* S, int64_t ldS,
                           int n, uint32_t row_base, uint32_t cover, int64_t id_offset, float* emit_scores, int64_t* emit_ids,
                           float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes, void* stream);
+/* OM_DEBUG_LISTS_DROP with the bitmaps of om_sim_topk_filtered_multi: drop_disallowed_kernel launched as that entry launches it, over
+ * lists put and read back as om_debug_select_lists does (the same stale keys, counts and out_* layout).  allow / words_pitch / n_filters /
+ * filter_of: as om_sim_topk_filtered_multi's, over rows [0, nrows).  A query under no filter keeps its list (a count above 8192 is
+ * clamped and marked all the same), one with nothing allowed ends with count 0. */
+int om_debug_drop_lists_multi(int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts, int use_qstat,
+                              const uint32_t* allow, uint32_t nrows, int64_t words_pitch, int64_t n_filters, const int32_t* filter_of,
+                              float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes,
+                              void* stream);
 /* query_prep_kernel on the grid of the search: queries [n_queries][d] f32 and stats[2] = {max ||p - f16(p)||, max ||f16(p)||} on the
  * device -> out_q16 [round_up(n_queries, 256)][d] float16 (rows beyond n_queries zero) and the certified margins out_margin [n_queries]. */
 int om_debug_query_prep(const float* queries, int64_t n_queries, int d, const float* stats, void* out_q16, float* out_margin, void* stream);

@@ -1304,6 +1304,27 @@ __global__ __launch_bounds__(256) void rescore_strided_kernel(const float* __res
   }
 }
 
+// om_sim_topk_candidates: one wavefront per (query, candidate column) of the columns [col0, col0 + ncols) of cand [nq][pitch] -- the key
+// pack_key(rescore_dot(query, row), row) appended to list q.  A value outside [0, N) is a hole: skipped, never followed.  The host keeps
+// ncols <= CAND_BLOCK with at most K_MAX keys already in the list, so a slot always exists (the test on pos guards the memory all the same).
+#define CAND_BLOCK 4096
+static_assert(K_MAX + CAND_BLOCK <= SORT_CAP, "a list holds the kept k and one block of candidates");
+template <typename TRow>
+__global__ __launch_bounds__(256) void score_candidates_kernel(const float* __restrict__ q, const TRow* __restrict__ index, int64_t N, int d,
+                                                               const int32_t* __restrict__ cand, int64_t pitch, int64_t col0, int ncols,
+                                                               u64* __restrict__ keys, unsigned* __restrict__ cnt) {
+  const int64_t qi = blockIdx.y;
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (j >= ncols) return;
+  const int64_t row = cand[qi * pitch + col0 + j];     // (wave-uniform)
+  if (row < 0 || row >= N) return;
+  const float acc = rescore_dot(q + qi * d, index + row * d, d, lane);
+  if (lane != 0) return;
+  const unsigned pos = atomicAdd(cnt + qi, 1u);
+  if (pos < SORT_CAP) keys[qi * SORT_CAP + pos] = pack_key(acc, (uint32_t)row);
+}
+
 __global__ void emit_kernel(const u64* __restrict__ keys, const unsigned* __restrict__ cnt, int k,
                             int64_t id_offset, float* __restrict__ out_scores,
                             int64_t* __restrict__ out_ids) {
@@ -1328,13 +1349,32 @@ __global__ void init_lists_kernel(unsigned* cnt, unsigned* cnt_prev, float* thr,
   else if (q < (nq + 255) / 256 * 256 + 256) thr[q] = INFINITY;       // queries that do not exist never have survivors
 }
 
-// ---- the row filter of om_sim_topk_filtered ------------------------------------------------------------------------------------------
-// allow: bit r & 31 of word r >> 5 is row r of the shard; bits at and beyond N are never read as rows (count_allowed_kernel masks them,
+// ---- the row filters of om_sim_topk_filtered and om_sim_topk_filtered_multi ---------------------------------------------------------------
+// A bitmap: bit r & 31 of word r >> 5 is row r of the shard; bits at and beyond N are never read as rows (count_allowed_kernel masks them,
 // no scan names such a row, the redo stops at N).
 __device__ __forceinline__ bool row_allowed(const uint32_t* __restrict__ allow, uint32_t row) { return (allow[row >> 5] >> (row & 31u)) & 1u; }
 
-// *out += allowed rows among [0, N): the rank of the redo's select is min(k, this), whatever count the host was told
-__global__ __launch_bounds__(256) void count_allowed_kernel(const uint32_t* __restrict__ allow, int64_t N, unsigned* __restrict__ out) {
+// Which bitmap a query is under.  bits == nullptr: no filter in the call.  per_query == 0 (om_sim_topk_filtered): every query under the one
+// bitmap at `bits`.  per_query == 1 (om_sim_topk_filtered_multi): bitmap f is the words at bits + f * pitch, query q is under bitmap of[q]
+// (of == nullptr: bitmap q); a value below 0 is "every row", one at or beyond n is "no row" and is never used as an address.
+struct RowFilters {
+  const uint32_t* bits;
+  int64_t pitch, n;
+  const int32_t* of;
+  int per_query;
+};
+#define FILTER_EVERY_ROW (-1)
+#define FILTER_NO_ROW (-2)
+__device__ __forceinline__ int64_t filter_index(const RowFilters& F, int64_t q) {
+  if (!F.bits) return FILTER_EVERY_ROW;
+  if (!F.per_query) return 0;
+  const int64_t f = F.of ? (int64_t)F.of[q] : q;
+  return f < 0 ? FILTER_EVERY_ROW : (f >= F.n ? FILTER_NO_ROW : f);
+}
+
+// out[f] += rows bitmap f = blockIdx.y allows among [0, N): the rank of the redo's select is min(k, this), whatever count the host was told
+__global__ __launch_bounds__(256) void count_allowed_kernel(const RowFilters F, int64_t N, unsigned* __restrict__ out) {
+  const uint32_t* __restrict__ allow = F.bits + (int64_t)blockIdx.y * F.pitch;
   const int64_t words = (N + 31) / 32;
   unsigned c = 0;
   for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (int64_t)gridDim.x * blockDim.x) {
@@ -1344,19 +1384,22 @@ __global__ __launch_bounds__(256) void count_allowed_kernel(const uint32_t* __re
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out + blockIdx.y, c);
 }
 
-// Drop before every selection: list q compacted IN PLACE to the keys whose row (the low 32 bits, complemented) the filter allows, in
+// Drop before every selection: list q compacted IN PLACE to the keys whose row (the low 32 bits, complemented) the query's filter allows, in
 // their order, so thresholds, margins, the LIST_MAX test and the re-score only ever see allowed rows.  One workgroup per query, 256 keys
 // per step: every key of a step is in a register before the barrier, and a step writes only below what it has read (out <= base), so
 // no staging copy is needed.  Position inside a step: wave ballot + the totals of the lower waves.  A list beyond SORT_CAP lost
 // appends: clamped and marked here as the selections do, or the compaction would hide it from them.
-__global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ keys, unsigned* __restrict__ cnt, const uint32_t* __restrict__ allow,
+// A query under no filter keeps its list (clamped and marked all the same); one whose filter allows no row ends with an empty list.
+__global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ keys, unsigned* __restrict__ cnt, const RowFilters F,
                                                               uint32_t nrows, unsigned* __restrict__ flag, unsigned* __restrict__ qstat) {
   __shared__ unsigned wtot[4];
   const int64_t q = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t f = filter_index(F, q);              // (workgroup-uniform)
+  const uint32_t* __restrict__ allow = F.bits + (f > 0 ? f : 0) * F.pitch;
   unsigned n = cnt[q];
   if (n > SORT_CAP) {
     if (tid == 0) {
@@ -1364,6 +1407,11 @@ __global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ 
       if (qstat) atomicOr(qstat + q, QSTAT_OVERFLOW);
     }
     n = SORT_CAP;
+  }
+  if (f < 0) {
+    __syncthreads();                                 // every thread has read cnt[q]
+    if (tid == 0) cnt[q] = f == FILTER_NO_ROW ? 0u : n;
+    return;
   }
   u64* list = keys + q * SORT_CAP;
   unsigned out = 0;
@@ -1410,7 +1458,7 @@ __global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ 
 #define REDO_TILE_BYTES 32768
 #define REDO_RS_BAD 0         // rs[0]: queries to redo;  rs[1]: of those, with QSTAT_WIDE
 #define REDO_RS_WIDE 1
-#define REDO_RS_ALLOWED 2     // rs[2]: rows the filter allows among [0, N) (om_sim_topk_filtered: count_allowed_kernel)
+#define REDO_RS_ALLOWED 2     // rs[2]: rows the filter allows among [0, N) (om_sim_topk_filtered: count_allowed_kernel; the multi entry counts into its own words)
 __host__ __device__ inline int redo_shift(int pass) { return pass < 5 ? 53 - 11 * pass : 0; }      // 53, 42, 31, 20, 9, 0
 __host__ __device__ inline int redo_width(int pass) { return pass < 5 ? 11 : 9; }
 
@@ -1430,17 +1478,24 @@ __global__ void redo_compact_kernel(const unsigned* __restrict__ qstat, int64_t 
   if (st & QSTAT_WIDE) atomicAdd(rs + REDO_RS_WIDE, 1u);
 }
 
-__global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restrict__ rs, u64* __restrict__ prefix, unsigned* __restrict__ remaining,
-                                                         unsigned* __restrict__ hist, unsigned want, const unsigned* __restrict__ n_allowed) {
+// F, n_allowed: the call's row filters and the device's count of every bitmap's rows (F.bits == nullptr: no filter, neither is read)
+__global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restrict__ rs, const unsigned* __restrict__ bad, u64* __restrict__ prefix,
+                                                         unsigned* __restrict__ remaining, unsigned* __restrict__ hist, unsigned want,
+                                                         const RowFilters F, const unsigned* __restrict__ n_allowed) {
   const unsigned n_bad = rs[REDO_RS_BAD];
   if (!n_bad) return;
-  if (n_allowed && *n_allowed < want) want = *n_allowed;      // under a row filter the rank is min(k, allowed rows), counted on the device
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = i0; i < (int64_t)n_bad * REDO_BINS; i += step) hist[i] = 0;
-  for (int64_t b = i0; b < n_bad; b += step) { prefix[b] = 0; remaining[b] = want; }
+  for (int64_t b = i0; b < n_bad; b += step) {
+    // under a row filter the rank is min(k, rows the query's bitmap allows), counted on the device
+    const int64_t f = filter_index(F, bad[b]);
+    const unsigned have = f == FILTER_EVERY_ROW ? want : (f == FILTER_NO_ROW ? 0u : n_allowed[f]);
+    prefix[b] = 0;
+    remaining[b] = have < want ? have : want;
+  }
 }
 
-// allow: the row filter of om_sim_topk_filtered (nullptr: every row counts).
+// F: the call's row filters (F.bits == nullptr: every row counts for every query).
 // COLLECT = false: hist[b][digit at `shift`] += 1 for every row whose key agrees with prefix[b] above the digit;
 // COLLECT = true: every key >= prefix[b] (= T) appended to list bad[b].  Rows [0, N) of `index`, tiles of R rows (R * d * 4 bytes of LDS).
 // TRow = f16_t (OM_SEARCH_F16_ONLY): the tile is filled from 16-byte loads of eight halves and staged WIDENED to float32, so R, the LDS
@@ -1449,7 +1504,7 @@ template <bool COLLECT, typename TRow>
 __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict__ q32, const TRow* __restrict__ index, int64_t N, int d, int R,
                                                         const unsigned* __restrict__ rs, const unsigned* __restrict__ bad,
                                                         const u64* __restrict__ prefix, unsigned* __restrict__ hist, int shift, int width,
-                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt, const uint32_t* __restrict__ allow) {
+                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt, const RowFilters F) {
   const unsigned n_bad = rs[REDO_RS_BAD];
   if (!n_bad) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1477,6 +1532,9 @@ __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict_
       const unsigned q = bad[b];
       const float* qv = q32 + (int64_t)q * d;
       const u64 P = prefix[b];
+      const int64_t f = filter_index(F, q);                                  // (workgroup-uniform) the bad query's own bitmap
+      if (f == FILTER_NO_ROW) continue;
+      const uint32_t* __restrict__ allow = f < 0 ? nullptr : F.bits + f * F.pitch;
       for (int r = wave; r < nr; r += 4) {
         if (allow && !row_allowed(allow, (uint32_t)(r0 + r))) continue;      // (wave-uniform) a row the filter drops has no key
         const float sc = rescore_dot(qv, tile + (int64_t)r * d, d, lane);
@@ -1762,8 +1820,10 @@ struct Scan {
   unsigned* qstat = nullptr;      // per-query sticky status: the asynchronous entry only
   ScanSwitches sw;                // the thread's switches, read once by the entry
   // om_sim_topk_filtered only (nullptr: no filter, and not one launch differs): the bitmap over rows [0, N) and the host's count of its bits
-  const uint32_t* allow = nullptr;
+  // (om_sim_topk_filtered_multi: the bitmaps of the call, n_allowed the count of the sparsest one in use, fcount one device count per bitmap)
+  RowFilters filt = {nullptr, 0, 0, nullptr, 0};
   int64_t n_allowed = 0;
+  unsigned* fcount = nullptr;
   // diagnostics, accumulated over the 16-bit run and the float32 retry (om_sim_topk publishes them, the asynchronous entry's status
   // kernel takes rounds and family): rounds, chunks redone densely or schedules started over, longest list seen by the host,
   // OM_SCAN_FAMILY_* and OM_SCAN_KERNEL_* of the last filtered round (its tail's where the round had no whole tile)
@@ -1773,8 +1833,8 @@ struct Scan {
   // under a row filter every selection is preceded by the drop of the keys it does not allow
   // (mark: as the selection it precedes -- the last one of the chain, behind the redo, marks no query: nothing reads the marks any more)
   int drop(bool mark = true) {
-    if (!allow) return 0;
-    hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, allow, (uint32_t)N, ws.flag,
+    if (!filt.bits) return 0;
+    hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, filt, (uint32_t)N, ws.flag,
                        mark ? qstat : nullptr);
     OM_LAUNCH_CHECK();
     return 0;
@@ -1817,10 +1877,10 @@ struct Scan {
   void redo_pass(const AsyncWs& aw, dim3 grid, size_t lds, int R, int shift, int width) {
     if (rows16())
       hipLaunchKernelGGL((redo_pass_kernel<COLLECT, f16_t>), grid, dim3(256), lds, s, q32, idx16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
-                         shift, width, ws.keys, ws.cnt, allow);
+                         shift, width, ws.keys, ws.cnt, filt);
     else
       hipLaunchKernelGGL((redo_pass_kernel<COLLECT, float>), grid, dim3(256), lds, s, q32, idx32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
-                         shift, width, ws.keys, ws.cnt, allow);
+                         shift, width, ws.keys, ws.cnt, filt);
   }
   // dense-score rows [r0, r0+n) and merge them into the lists (always exact, HBM heavy)
   int dense_gemm_append(int64_t r0, int n, bool bf16) {
@@ -1878,9 +1938,11 @@ struct Scan {
     if (aw) {
       hipLaunchKernelGGL(async_init_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, aw->qstat, aw->rs, status, nq);
       OM_LAUNCH_CHECK();
-      if (allow && N > 0) {                        // behind the kernel that zeroes rs
+      if (filt.bits && N > 0) {                    // behind the kernel that zeroes rs
         const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(((N + 31) / 32 + 255) / 256, 1024));
-        hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, allow, N, aw->rs + REDO_RS_ALLOWED);
+        // one bitmap: counted into rs[REDO_RS_ALLOWED]; a bitmap per query: one grid row and one word of the entry's own counts per bitmap
+        if (filt.per_query) OM_HIP(hipMemsetAsync(fcount, 0, (size_t)filt.n * 4, s));
+        hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)blocks, (unsigned)(filt.per_query ? filt.n : 1)), dim3(256), 0, s, filt, N, fcount);
         OM_LAUNCH_CHECK();
       }
     }
@@ -1898,7 +1960,7 @@ struct Scan {
   int fast_rounds(bool bf16, SearchSchedule& sched) {
     int64_t chunks[SEARCH_SCHED_MAX];
     int64_t boot = 1;
-    sched = allow ? search_schedule_filtered(bf16, nq, N, k, n_allowed, sw, chunks, SEARCH_SCHED_MAX, &boot)
+    sched = filt.bits ? search_schedule_filtered(bf16, nq, N, k, n_allowed, sw, chunks, SEARCH_SCHED_MAX, &boot)
                   : search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
     if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
     for (int64_t b = 0; b < boot && b * DENSE_CHUNK < N; ++b) {
@@ -2051,8 +2113,8 @@ struct Scan {
       }
       // redo: a fixed chain, empty launches when no query is marked
       hipLaunchKernelGGL(redo_compact_kernel, dim3(qblocks), dim3(256), 0, s, qstat, nq, aw.rs, aw.bad);
-      hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.prefix, aw.remaining, aw.hist, (unsigned)std::min<int64_t>(k, N),
-                         allow ? (const unsigned*)(aw.rs + REDO_RS_ALLOWED) : (const unsigned*)nullptr);
+      hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.bad, aw.prefix, aw.remaining, aw.hist,
+                         (unsigned)std::min<int64_t>(k, N), filt, (const unsigned*)fcount);
       OM_LAUNCH_CHECK();
       const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
       const size_t lds = (size_t)R * d * 4;
@@ -2234,10 +2296,119 @@ extern "C" int om_sim_topk_filtered(int mode, const float* queries, int64_t n_qu
   const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
   if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_filtered_workspace_bytes)");
   sc.qstat = aw.qstat;
-  sc.allow = allow_bits;
+  sc.filt = RowFilters{allow_bits, 0, 1, nullptr, 0};
   sc.n_allowed = n_allowed;
+  sc.fcount = aw.rs + REDO_RS_ALLOWED;
   if (search_attrs()) return 1;
   return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+}
+
+// The same chain with a bitmap per query: the three kernels that read a bitmap -- the drop, the count, the redo -- take it from
+// filter_of[q]; one count per bitmap lives in n_filters words behind the asynchronous workspace.  The schedule is the single-filter one of
+// the sparsest bitmap in use (search_plan.h).
+static size_t multi_counts_offset(int64_t n_queries, int d) { return carve_async(n_queries, d, nullptr).total; }
+extern "C" size_t om_sim_topk_filtered_multi_workspace_bytes(int64_t n_queries, int d, int k, int64_t n_filters) {
+  (void)k;
+  if (n_queries <= 0 || d <= 0 || n_filters < 1) return 0;
+  return multi_counts_offset(n_queries, d) + align_up((size_t)n_filters * 4, 256);
+}
+
+extern "C" int om_sim_topk_filtered_multi(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
+                                          const float* stats, int64_t N, int d, int k, int64_t id_offset, const uint32_t* allow_bits,
+                                          int64_t words_pitch, int64_t n_filters, const int32_t* filter_of, int64_t n_allowed_min,
+                                          float* out_scores, int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  if (n_queries <= 0) return 0;
+  Scan sc;
+  if (const char* why = scan_setup(sc, mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, stream))
+    OM_FAIL(why);
+  if (mode == OM_SEARCH_F16_ONLY) {
+    if (const char* why = f16_only_refusal(sc)) OM_FAIL(why);
+  }
+  if (d > 16384) OM_FAIL("d above 16384: a row does not fit the redo's LDS tile");
+  if (!sc.sw.gen7) OM_FAIL("OM_OPT_SCAN_GEN7 is 0: the fast schedule this entry runs is switched off");
+  if (!allow_bits) OM_FAIL("allow_bits is null: the filtered search needs the bitmaps of the allowed rows (om_sim_topk_async searches all rows)");
+  if (n_filters < 1 || n_filters > 65535) OM_FAIL("n_filters must be in [1, 65535]");
+  if (words_pitch < (N + 31) / 32) OM_FAIL("words_pitch is below (N + 31) / 32, the words of one bitmap");
+  if (!filter_of && n_filters != n_queries) OM_FAIL("filter_of is null: query q is under bitmap q, which needs n_filters == n_queries");
+  if (n_allowed_min < 0 || n_allowed_min > N) OM_FAIL("n_allowed_min must be in [0, N]");
+  const AsyncWs aw = carve_async(n_queries, d, (char*)workspace);
+  if (om_sim_topk_filtered_multi_workspace_bytes(n_queries, d, k, n_filters) > workspace_bytes)
+    OM_FAIL("workspace too small (om_sim_topk_filtered_multi_workspace_bytes)");
+  sc.qstat = aw.qstat;
+  sc.filt = RowFilters{allow_bits, words_pitch, n_filters, filter_of, 1};
+  sc.n_allowed = n_allowed_min;
+  sc.fcount = (unsigned*)((char*)workspace + multi_counts_offset(n_queries, d));
+  if (search_attrs()) return 1;
+  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+}
+
+// ---- om_sim_topk_candidates: the exact top-k of every query over its OWN candidate rows ------------------------------------------------
+// No scan, no margin, no redo: init -> per block of CAND_BLOCK candidate columns (score_candidates_kernel -> select_kernel in exact mode,
+// which keeps the best k by the 64-bit key) -> emit.  A list never holds more than k + CAND_BLOCK <= SORT_CAP keys, and keys of distinct
+// rows never tie, so there is nothing to overflow and nothing to redo.  The chain is fixed by cand_pitch alone; the cost is
+// n_queries * cand_pitch * d, whatever N.
+struct CandWs { u64* keys; unsigned *cnt, *cnt_prev, *flag; float* thr; size_t total; };
+static CandWs carve_candidates(int64_t nq, char* base) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
+  CandWs w;
+  w.keys = (u64*)take((size_t)nq * SORT_CAP * 8);
+  w.cnt = (unsigned*)take((size_t)nq * 4);
+  w.cnt_prev = (unsigned*)take((size_t)nq * 4);
+  w.flag = (unsigned*)take(64);
+  w.thr = (float*)take(((size_t)(nq + 255) / 256 * 256 + 256) * 4);      // init_lists_kernel writes a whole tile beyond nq
+  w.total = off;
+  return w;
+}
+
+extern "C" size_t om_sim_topk_candidates_workspace_bytes(int64_t n_queries, int d, int k) {
+  (void)d; (void)k;
+  if (n_queries <= 0) return 0;
+  return carve_candidates(n_queries, nullptr).total;
+}
+
+extern "C" int om_sim_topk_candidates(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16, int64_t N,
+                                      int d, int k, int64_t id_offset, const int32_t* cand, int64_t cand_pitch, float* out_scores,
+                                      int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_queries <= 0) return 0;
+  if (mode != OM_SEARCH_F32 && mode != OM_SEARCH_F16_RESCORE && mode != OM_SEARCH_F16_ONLY) OM_FAIL("mode must be one of OM_SEARCH_*");
+  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1,2048]");
+  if (N < 0 || N > 0x7fffffffLL) OM_FAIL("N: a candidate is an int32 row number, the shard holds at most 2^31 - 1 rows");
+  if (d <= 0 || (d * 2) % GEMM_ROW_BYTES != 0) OM_FAIL("d must be a multiple of 64 (pad with zeros)");
+  if (n_queries > 65535) OM_FAIL("at most 65535 queries per call");
+  if (!queries || !out_scores || !out_ids) OM_FAIL("null argument");
+  if (!cand) OM_FAIL("cand is null: the candidate rows of every query");
+  if (cand_pitch < 1) OM_FAIL("cand_pitch must be at least 1");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
+  const bool rows16 = mode == OM_SEARCH_F16_ONLY;
+  if (N > 0 && rows16 && !index_f16) OM_FAIL("OM_SEARCH_F16_ONLY: index_f16 is null (the float16 rows are the index)");
+  if (N > 0 && !rows16 && !index_f32) OM_FAIL("index_f32 is null: the candidates are scored on the float32 rows");
+  const CandWs ws = carve_candidates(n_queries, (char*)workspace);
+  if (ws.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_candidates_workspace_bytes)");
+  if (search_attrs()) return 1;
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned nq = (unsigned)n_queries;
+  hipLaunchKernelGGL(init_lists_kernel, dim3((unsigned)((n_queries + 255) / 256 + 2)), dim3(256), 0, s, ws.cnt, ws.cnt_prev, ws.thr, n_queries,
+                     ws.flag);
+  OM_LAUNCH_CHECK();
+  for (int64_t col0 = 0; col0 < cand_pitch; col0 += CAND_BLOCK) {
+    const int ncols = (int)std::min<int64_t>(CAND_BLOCK, cand_pitch - col0);
+    const dim3 grid((unsigned)((ncols + 3) / 4), nq);
+    if (rows16)
+      hipLaunchKernelGGL(score_candidates_kernel<f16_t>, grid, dim3(256), 0, s, queries, (const f16_t*)index_f16, N, d, cand, cand_pitch, col0,
+                         ncols, ws.keys, ws.cnt);
+    else
+      hipLaunchKernelGGL(score_candidates_kernel<float>, grid, dim3(256), 0, s, queries, index_f32, N, d, cand, cand_pitch, col0, ncols, ws.keys,
+                         ws.cnt);
+    OM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr,
+                       (const float*)nullptr, k, ws.flag, (unsigned*)nullptr);
+    OM_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(emit_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, out_scores, out_ids);
+  OM_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" size_t om_sim_topk_filtered_workspace_bytes(int64_t n_queries, int d, int k) {
@@ -2333,8 +2504,8 @@ extern "C" int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows
     const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
     const size_t lds = (size_t)R * d * 4;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + R - 1) / R, (int64_t)g7_num_cus() * 4)));
-    if (h) hipLaunchKernelGGL((redo_pass_kernel<true, f16_t>), grid, dim3(256), lds, s, queries, r16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt, (const uint32_t*)nullptr);
-    else hipLaunchKernelGGL((redo_pass_kernel<true, float>), grid, dim3(256), lds, s, queries, r32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt, (const uint32_t*)nullptr);
+    if (h) hipLaunchKernelGGL((redo_pass_kernel<true, f16_t>), grid, dim3(256), lds, s, queries, r16, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt, RowFilters{nullptr, 0, 0, nullptr, 0});
+    else hipLaunchKernelGGL((redo_pass_kernel<true, float>), grid, dim3(256), lds, s, queries, r32, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist, 0, 0, ws.keys, ws.cnt, RowFilters{nullptr, 0, 0, nullptr, 0});
   } else {
     hipLaunchKernelGGL(debug_fill_lists_kernel, dim3(nq), dim3(256), 0, s, cand, m, N, ws.keys, ws.cnt);
     if (kernel == 0) {
@@ -2425,7 +2596,7 @@ extern "C" int om_debug_select_lists(int op, int64_t n_queries, int m, const flo
                          qstat);
       break;
     case OM_DEBUG_LISTS_DROP:
-      hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, allow, nrows, ws.flag, qstat);
+      hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowFilters{allow, 0, 1, nullptr, 0}, nrows, ws.flag, qstat);
       break;
     case OM_DEBUG_LISTS_APPEND:
       hipLaunchKernelGGL(append_dense_kernel, dim3(nq), dim3(256), 0, s, S, ldS, n, row_base, ws.keys, ws.cnt);
@@ -2436,6 +2607,36 @@ extern "C" int om_debug_select_lists(int op, int64_t n_queries, int m, const flo
       hipLaunchKernelGGL(emit_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, k, id_offset, emit_scores, emit_ids);
       break;
   }
+  OM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
+                     out_rows, out_state);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// om_debug_select_lists' OM_DEBUG_LISTS_DROP with the bitmaps of om_sim_topk_filtered_multi: the drop as that entry launches it
+extern "C" int om_debug_drop_lists_multi(int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts, int use_qstat,
+                                         const uint32_t* allow, uint32_t nrows, int64_t words_pitch, int64_t n_filters, const int32_t* filter_of,
+                                         float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  if (!scores || !rows || !counts) OM_FAIL("null argument: scores, rows and counts describe the lists");
+  if (n_queries < 1 || n_queries > 65535) OM_FAIL("1 to 65535 queries");
+  if (m < 1 || m > SORT_CAP) OM_FAIL("m must be in [1, 8192]");
+  if (!allow || nrows < 1) OM_FAIL("the drop needs the bitmaps (allow is null) and nrows >= 1");
+  if (n_filters < 1) OM_FAIL("n_filters must be at least 1");
+  if (words_pitch < ((int64_t)nrows + 31) / 32) OM_FAIL("words_pitch is below (nrows + 31) / 32, the words of one bitmap");
+  if (!filter_of && n_filters != n_queries) OM_FAIL("filter_of is null: query q is under bitmap q, which needs n_filters == n_queries");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
+  const SearchWs ws = carve_search(n_queries, 64, (char*)workspace);
+  const AsyncWs aw = carve_async(n_queries, 64, (char*)workspace);
+  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes(n_queries, 64, 1))");
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned nq = (unsigned)n_queries;
+  hipLaunchKernelGGL(debug_put_lists_kernel, dim3(nq), dim3(256), 0, s, scores, rows, counts, (const float*)nullptr, m, ws.keys, ws.cnt,
+                     ws.cnt_prev, ws.thr, ws.margin, ws.flag, aw.qstat);
+  OM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowFilters{allow, words_pitch, n_filters, filter_of, 1},
+                     nrows, ws.flag, use_qstat ? aw.qstat : (unsigned*)nullptr);
   OM_LAUNCH_CHECK();
   hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
                      out_rows, out_state);

@@ -164,6 +164,10 @@ static SearchSchedule search_schedule(bool half, int64_t nq, int64_t N, int k, c
 // at most all the rows.  The first round starts at row boot * SEARCH_DENSE_CHUNK.  `list` stays the estimate for k: after the last
 // drop and selection a list holds allowed keys only, and that is what the re-score has to cover.
 // n_allowed >= N returns exactly search_schedule (boot = 1); n_allowed < 1 counts as 1 (everything is scored densely).  Pure.
+// Rule for a bitmap per query (om_sim_topk_filtered_multi): ONE schedule serves the call, this function's for n_allowed = the count of
+// the SPARSEST bitmap any query of the call is under (N when every query is unfiltered).  The bootstrap and the rounds are then long
+// enough for that query; the lists of a query under a denser bitmap -- or under none -- reach their threshold earlier and fill more
+// slowly than planned, which costs nothing.  The count is a planning number only: the redo's rank is counted per bitmap on the device.
 static int64_t search_k_eff(int64_t k, int64_t N, int64_t n_allowed) {                 // N < 2^32, k <= 2048: no overflow
   const int64_t na = n_allowed < 1 ? 1 : n_allowed;
   return na >= N ? k : (k * N + na - 1) / na;

@@ -69,6 +69,115 @@ def filter_route(precision: str, k: int, first: int, last: int, n_allowed: int, 
     return "scan" if est <= LIST_MAX else "gather"
 
 
+class MultiSearchHandle(SearchHandle):
+    """A filtered search of several parts in flight (`FlatIPIndex.search_device_filtered_multi_async`): `D` / `I` in the caller's query
+    order; the handle keeps every part's handle -- workspace, status words, query slice -- alive."""
+
+    def __init__(self, D, I, queries, parts, device, keep=None):
+        super().__init__(D, I, queries, [], device, {"route": "multi"})
+        self._parts = parts                # [(route, SearchHandle, queries, n_filters)]
+        self._keep = keep
+
+    def info(self):
+        """Synchronises the device; the keys of `SearchHandle.info()` taken from the 'scan' part where there is one (else the first part),
+        `max_list` / `margin_too_wide` over all parts, `redone` summed over them, and `parts`: [{route, queries, n_filters}]."""
+        if not self._parts:
+            return {**super().info(), "parts": []}
+        infos = [h.info() for _way, h, _nq, _nf in self._parts]
+        ways = [way for way, _h, _nq, _nf in self._parts]
+        out = dict(infos[ways.index("scan")] if "scan" in ways else infos[0])
+        out.pop("n_allowed", None)
+        out.update(route="multi", redone=sum(i["redone"] for i in infos), max_list=max(i["max_list"] for i in infos),
+                   margin_too_wide=any(i["margin_too_wide"] for i in infos),
+                   parts=[{"route": way, "queries": nq, "n_filters": nf} for way, _h, nq, nf in self._parts])
+        return out
+
+
+# A sparse group of at most CANDIDATES_MAX_QUERIES queries whose filter allows at most CANDIDATES_MAX_ROWS rows is scored from candidate
+# lists, any other sparse group gathers its rows.  Measured (tools/search_multi_filter_bench.py, DESIGN.md 4f): at 1 000 allowed rows lists
+# are faster than the gather route with CACHED planes up to 8 queries (equal at 8) and than a gather that builds its planes up to 16; at
+# 19 944 allowed rows gathering wins at every query count.  4 096 is one block of the candidates chain (not measured between the two).
+CANDIDATES_MAX_QUERIES = 8
+CANDIDATES_MAX_ROWS = 4096
+MULTI_ROUTES = ("single", "scan", "candidates", "gather")
+
+
+def multi_filter_route(precision: str, k: int, groups, unfiltered: int = 0, ntotal=None, route=None):
+    """How a search with a filter per query is split into parts (pure: no tensor, no device).
+    groups: [(n_queries, n_allowed, first, last)] per DISTINCT filter in use (`first` / `last`: its lowest and highest allowed row);
+    unfiltered: queries under no filter (`ntotal`, the rows of the index, is needed when there are any).
+    Returns a list of parts {"route", "groups": indices into `groups`, "unfiltered": bool, "rows": (lo, hi) of a 'scan' part,
+    "n_allowed_min": the sparsest bitmap of a 'scan' part}.  In order:
+      one distinct filter and every query under it, no forced route: one 'single' part -- `search_device_filtered_async` itself;
+      a forced `route` ('scan' | 'candidates'): ONE part of that route for everything (unfiltered queries cannot be 'candidates');
+      groups whose own `filter_route` is 'scan' or 'range', and the unfiltered queries: together ONE 'scan' part over the rows from the
+        smallest `first` rounded down to 256 through the largest `last` -- all rows when an unfiltered query is present;
+      'empty' groups, and 'gather' groups of at most CANDIDATES_MAX_QUERIES queries and CANDIDATES_MAX_ROWS allowed rows: together ONE
+        'candidates' part;
+      every other 'gather' group: a 'gather' part of its own.
+    Where the two bounds come from: candidate lists re-read a row once per query, Q_g * C * d * s bytes; gathering moves about
+    3 * C * d * s (read, write, scan once), after which the queries share one MFMA scan.  That byte count put the split at 3 queries;
+    the measurement put it at 8 for 1 000 rows and found no query count at which lists win for 20 000."""
+    if route not in (None, "scan", "candidates"):
+        raise ValueError("route must be None, 'scan' or 'candidates'")
+    groups = [tuple(int(v) for v in g) for g in groups]
+    if unfiltered and ntotal is None:
+        raise ValueError("ntotal is needed to place the unfiltered queries")
+    if not groups and not unfiltered:
+        return []
+
+    def scan_part(members):
+        part = {"route": "scan", "groups": members, "unfiltered": bool(unfiltered), "rows": None, "n_allowed_min": 0}
+        live = [groups[g] for g in members if groups[g][1] > 0]
+        if unfiltered:
+            lo, hi = 0, int(ntotal)
+        elif live:
+            lo, hi = min(g[2] for g in live) // 256 * 256, max(g[3] for g in live) + 1
+        else:
+            lo, hi = 0, 0
+        part["rows"] = (lo, hi)
+        part["n_allowed_min"] = min([groups[g][1] for g in members], default=hi - lo)
+        return part
+
+    if route is None and len(groups) == 1 and not unfiltered:
+        return [{"route": "single", "groups": [0], "unfiltered": False, "rows": None, "n_allowed_min": groups[0][1]}]
+    if route == "scan":
+        return [scan_part(list(range(len(groups))))]
+    if route == "candidates":
+        if unfiltered:
+            raise ValueError("route='candidates': a query under no filter has no candidate list")
+        return [{"route": "candidates", "groups": list(range(len(groups))), "unfiltered": False, "rows": None, "n_allowed_min": 0}]
+    scan, lists, parts = [], [], []
+    for g, (nq, n_allowed, first, last) in enumerate(groups):
+        way = filter_route(precision, k, first, last, n_allowed)
+        if way in ("scan", "range"):
+            scan.append(g)
+        elif way == "empty" or (nq <= CANDIDATES_MAX_QUERIES and n_allowed <= CANDIDATES_MAX_ROWS):
+            lists.append(g)
+        else:
+            parts.append({"route": "gather", "groups": [g], "unfiltered": False, "rows": None, "n_allowed_min": n_allowed})
+    if scan or unfiltered:
+        parts.insert(0, scan_part(scan))
+    if lists:
+        parts.append({"route": "candidates", "groups": lists, "unfiltered": False, "rows": None, "n_allowed_min": 0})
+    return parts
+
+
+def prepare_candidates(cand: torch.Tensor, ntotal: int):
+    """The candidate tensor of `om_sim_topk_candidates` from a caller's [Q, C] ids padded with -1 (pure: any device): every row sorted,
+    a repeated id kept once and its repeats set to -1 (the kernel would return a repeated row twice), int32.  Returns (cand int32 [Q, C],
+    bad: a 0-d tensor counting ids >= ntotal or < -1, not read here)."""
+    if cand.dim() != 2:
+        raise ValueError("cand must be [Q, C] row ids, padded with -1")
+    c = cand.to(torch.int64)
+    bad = ((c < -1) | (c >= ntotal)).sum()
+    c, _ = torch.sort(torch.where((c < 0) | (c >= ntotal), torch.full_like(c, -1), c), dim=1)      # out of range: a hole, whoever reads `bad`
+    if c.shape[1] > 1:
+        repeat = c[:, 1:] == c[:, :-1]
+        c = torch.cat([c[:, :1], torch.where(repeat, torch.full_like(c[:, 1:], -1), c[:, 1:])], dim=1)
+    return c.to(torch.int32).contiguous(), bad
+
+
 class RowFilter:
     """The rows of one index a filtered search may return: a bitmap over [0, ntotal) shared by all queries of a call.
     allowed: a bool mask [ntotal], or a tensor / array / sequence of row ids (`invert=True`: the ids are an exclusion list).
@@ -377,6 +486,231 @@ class FlatIPIndex:
         """faiss-style, as `search`: numpy in, (D, I) numpy out."""
         q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
         D, I = self.search_device_filtered(q, k, row_filter)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- candidate lists: every query scored over its own rows --------------------------------
+    def _enqueue_candidates(self, q, D, I, mode, k, cand, id_offset):
+        """om_sim_topk_candidates over `cand` (int32 [Q, C] on the device, distinct rows per query, holes -1), in chunks of at most 32 768
+        queries.  Returns the workspaces a handle keeps alive."""
+        lib = N.lib()
+        step = 32768
+        if cand.dtype != torch.int32 or cand.device != self.device or cand.shape[0] != q.shape[0]:
+            raise ValueError("candidates must be int32 [Q, C] on the index's device")
+        cand = cand.contiguous()
+        keep = [cand]
+        if cand.shape[1] == 0 or self.ntotal == 0:
+            D.fill_(torch.finfo(torch.float32).min)
+            I.fill_(-1)
+            return keep
+        with torch.cuda.device(self.device):
+            for s in range(0, q.shape[0], step):
+                n = min(step, q.shape[0] - s)
+                nbytes = lib.om_sim_topk_candidates_workspace_bytes(n, self.dpad, k)
+                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
+                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
+                N.check(lib.om_sim_topk_candidates(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16), self.ntotal, self.dpad, k,
+                                                   int(id_offset), N.ptr(cand[s:s + n]), cand.shape[1], N.ptr(D[s:s + n]), N.ptr(I[s:s + n]),
+                                                   N.c_void_p(ws), nbytes, N.stream_ptr(self.device)))
+                keep.append(buf)
+        return keep
+
+    def search_device_candidates_async(self, queries: torch.Tensor, k: int, cand, id_offset: int = 0):
+        """The exact top-k of query q over ITS OWN candidate rows `cand[q]` (an int tensor or array [Q, C], padded with -1), stream-ordered:
+        scores are the re-score's (in the 16-bit precisions the bits a filtered search returns for those rows), ties to the ascending row,
+        ids the row numbers + `id_offset`, (-3.4028235e38, -1) padded when a query has fewer than k candidates.  The cost is Q * C * d,
+        whatever `ntotal`.  Repeats within a row are removed on the device (sort, equal neighbours to -1).
+        Ids >= ntotal or < -1 raise ValueError: candidates given on the HOST (array, list, CPU tensor) are checked there, without any
+        synchronisation; a DEVICE tensor is checked by a count read back once -- the call's only synchronisation -- except while the
+        current stream is capturing, where nothing may be read: such ids are then holes, like -1 (the kernel never follows them)."""
+        q, D, I, mode = self._search_args(queries, k)
+        if isinstance(cand, np.ndarray):
+            cand = torch.from_numpy(cand)
+        elif not isinstance(cand, torch.Tensor):
+            cand = torch.as_tensor(cand, dtype=torch.int64)
+        if cand.dim() != 2 or cand.shape[0] != q.shape[0] or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+            raise ValueError(f"cand must be [{q.shape[0]}, C] integer row ids, padded with -1")
+        if self.ntotal >= 2 ** 31:
+            raise ValueError("candidate lists name rows as int32: the index holds 2^31 rows or more")
+        on_host = not cand.is_cuda
+        c32, bad = prepare_candidates(cand, self.ntotal)      # (where the candidates are: host ids are prepared and checked on the host)
+        if on_host or not torch.cuda.is_current_stream_capturing():
+            n_bad = int(bad.item())
+            if n_bad:
+                raise ValueError(f"{n_bad} candidate id(s) outside [-1, {self.ntotal})")
+        c32 = c32.to(self.device)
+        keep = self._enqueue_candidates(q, D, I, mode, k, c32, id_offset)
+        return SearchHandle(D, I, q, [], self.device, {"route": "candidates", "candidates": int(cand.shape[1]), "_keep": keep})
+
+    def search_device_candidates(self, queries: torch.Tensor, k: int, cand, id_offset: int = 0):
+        """`search_device_candidates_async`, waited for: (D, I) on the GPU, and `last_search_info`."""
+        h = self.search_device_candidates_async(queries, k, cand, id_offset=id_offset)
+        self.last_search_info = h.info()
+        return h.D, h.I
+
+    def search_candidates(self, x, k: int, cand):
+        """faiss-style, as `search`: numpy in, (D, I) numpy out."""
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
+        D, I = self.search_device_candidates(q, k, cand)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- a filter per query --------------------------------------------------------------------
+    def _multi_plan(self, k, filters, filter_of, nq, route):
+        """Everything of a multi-filter search that does not depend on the queries: the parts (`multi_filter_route`), the permutation that
+        makes each part a contiguous slice, and per part its device tensors (stacked bitmaps and filter_of, or candidate lists).  The
+        last plan is kept on the index: the same call again -- the one a graph captures after its eager run -- uploads and reads nothing."""
+        filters = list(filters)
+        for rf in filters:
+            if rf is None:
+                continue
+            if not isinstance(rf, RowFilter):
+                raise TypeError("filters must hold RowFilter objects or None")
+            if rf.ntotal != self.ntotal or rf.device != self.device:
+                raise ValueError(f"a filter was built for an index of {rf.ntotal} rows on {rf.device}, "
+                                 f"this one holds {self.ntotal} on {self.device}")
+        if filter_of is None:
+            if len(filters) != nq:
+                raise ValueError(f"{len(filters)} filters for {nq} queries: give one per query, or filter_of")
+            of = list(range(nq))
+        else:
+            of = [int(v) for v in (filter_of.tolist() if hasattr(filter_of, "tolist") else filter_of)]
+            if len(of) != nq:
+                raise ValueError(f"filter_of has {len(of)} entries for {nq} queries")
+            if any(v >= len(filters) for v in of):
+                raise ValueError(f"filter_of names a filter at or beyond {len(filters)}")
+        of = [v if v >= 0 and filters[v] is not None else -1 for v in of]
+        key = (self._generation, k, route, tuple(of))
+        last = getattr(self, "_multi_last", None)
+        if last is not None and last["key"] == key and len(last["filters"]) == len(filters) and all(a is b for a, b in zip(last["filters"], filters)):
+            return last
+        distinct, members, free = [], [], []        # distinct filters in use (by identity), their queries, the unfiltered queries
+        slot = {}
+        for qi, v in enumerate(of):
+            if v < 0:
+                free.append(qi)
+                continue
+            g = slot.setdefault(id(filters[v]), len(distinct))
+            if g == len(distinct):
+                distinct.append(filters[v])
+                members.append([])
+            members[g].append(qi)
+        groups = [(len(m), rf.n_allowed, rf.first, rf.last) for rf, m in zip(distinct, members)]
+        parts = multi_filter_route(self.precision, k, groups, unfiltered=len(free), ntotal=self.ntotal, route=route)
+        dev = self.device
+        order = []
+        for part in parts:
+            qs = [qi for g in part["groups"] for qi in members[g]] + (free if part["unfiltered"] else [])
+            part["start"], part["queries"] = len(order), len(qs)
+            order += qs
+            if part["route"] == "scan":
+                lo, hi = part["rows"]
+                used = [distinct[g] for g in part["groups"]]
+                words = [rf.words[lo // 32:] for rf in used] or [torch.zeros(max(1, (self.ntotal + 31) // 32 - lo // 32), dtype=torch.int32, device=dev)]
+                part["words"] = torch.stack(words).contiguous()
+                fo = [i for i, g in enumerate(part["groups"]) for _ in members[g]] + [-1] * (len(free) if part["unfiltered"] else 0)
+                # one bitmap per query, in the queries' order, in one native call: the entry's NULL filter_of says just that
+                direct = fo == list(range(len(used))) and len(fo) <= 32768
+                part["filter_of"] = None if direct else torch.tensor(fo, dtype=torch.int32).to(dev)
+            elif part["route"] == "candidates":
+                used = [distinct[g] for g in part["groups"]]
+                width = max([rf.n_allowed for rf in used] + [1])
+                lists = torch.full((len(used), width), -1, dtype=torch.int32, device=dev)
+                for i, rf in enumerate(used):
+                    if rf.n_allowed:
+                        lists[i, :rf.n_allowed] = rf.ids().to(torch.int32)
+                rows = torch.tensor([i for i, g in enumerate(part["groups"]) for _ in members[g]], dtype=torch.int64).to(dev)
+                part["cand"] = lists.index_select(0, rows)
+            else:
+                part["filter"] = distinct[part["groups"][0]]
+        inverse = [0] * nq
+        for pos, qi in enumerate(order):
+            inverse[qi] = pos
+        identity = order == list(range(nq))
+        plan = {"key": key, "filters": filters, "parts": parts, "identity": identity,
+                "order": None if identity else torch.tensor(order, dtype=torch.int64).to(dev),
+                "inverse": None if identity else torch.tensor(inverse, dtype=torch.int64).to(dev)}
+        self._multi_last = plan
+        return plan
+
+    def search_device_filtered_multi_async(self, queries: torch.Tensor, k: int, filters, filter_of=None, id_offset: int = 0, route=None):
+        """The exact top-k of every query over the rows ITS OWN filter allows, stream-ordered: per query what
+        `search_device_filtered_async` returns for it alone under its filter.
+        filters: a sequence of `RowFilter` or None (no filter) -- one per query, or indexed by `filter_of` ([Q] host ints: a list, an
+        array or a CPU tensor; -1 is "no filter"; a device tensor is read back, which costs a synchronisation and cannot be captured).
+        `multi_filter_route` splits the work: queries are permuted so that every part is a contiguous slice, every part enqueues on the
+        current stream, and one `index_select` puts D and I back in the caller's order.  Nothing is read back beyond what building the
+        filters cost; the first call with a set of filters uploads the plan (and reads the id lists of sparse filters), the same call
+        again reuses it.  route: None, or 'scan' / 'candidates' to force ONE part for everything (tests, benchmarks; a forced scan of a
+        sparse filter stays exact: the on-device redo serves it).  The handle's `info()` adds `parts` and sums `redone`."""
+        q, D, I, mode = self._search_args(queries, k)
+        nq = q.shape[0]
+        plan = self._multi_plan(int(k), filters, filter_of, nq, route)
+        parts = plan["parts"]
+        if len(parts) == 1 and parts[0]["route"] == "single":
+            h = self.search_device_filtered_async(queries, k, parts[0]["filter"], id_offset=id_offset)
+            h._extra["parts"] = [{"route": h._extra["route"], "queries": nq, "n_filters": 1}]
+            return h
+        if nq == 0:
+            return MultiSearchHandle(D, I, q, [], self.device)
+        cut = lambda plane, lo, hi: None if plane is None else plane[lo:hi]
+        qp = q if plan["identity"] else q.index_select(0, plan["order"])
+        Dp, Ip = (D, I) if plan["identity"] else (torch.empty_like(D), torch.empty_like(I))
+        handles = []
+        for part in parts:
+            s, n = part["start"], part["queries"]
+            qs, Ds, Is = qp[s:s + n], Dp[s:s + n], Ip[s:s + n]
+            if part["route"] == "scan":
+                lo, hi = part["rows"]
+                h = SearchHandle(Ds, Is, qs, self._enqueue_multi(qs, Ds, Is, mode, k, cut(self._f32, lo, hi), cut(self._f16, lo, hi), hi - lo,
+                                                                 int(id_offset) + lo, part["words"], part["filter_of"], part["n_allowed_min"]),
+                                 self.device)
+                n_filters = len(part["groups"])
+            elif part["route"] == "candidates":
+                keep = self._enqueue_candidates(qs, Ds, Is, mode, k, part["cand"], id_offset)
+                h = SearchHandle(Ds, Is, qs, [], self.device, {"_keep": keep})
+                n_filters = len(part["groups"])
+            else:
+                h = self.search_device_filtered_async(qs[:, :self.d], k, part["filter"], id_offset=id_offset, route="gather")
+                Ds.copy_(h.D)
+                Is.copy_(h.I)
+                n_filters = 1
+            handles.append((part["route"], h, n, n_filters))
+        if not plan["identity"]:
+            torch.index_select(Dp, 0, plan["inverse"], out=D)
+            torch.index_select(Ip, 0, plan["inverse"], out=I)
+        return MultiSearchHandle(D, I, q, handles, self.device, keep=(plan, qp, Dp, Ip))
+
+    def _enqueue_multi(self, q, D, I, mode, k, f32, f16, nrows, id_offset, words, filter_of, n_allowed_min):
+        """om_sim_topk_filtered_multi over rows [0, nrows) of the planes: `words` [F, pitch] int32 bitmaps over those rows, `filter_of`
+        int32 [Q] on the device (None: F == Q <= 32 768 and query q is under bitmap q).  Chunks of at most 32 768 queries; returns the (workspace, status) pairs a handle keeps alive."""
+        lib = N.lib()
+        step = 32768
+        chunks = []
+        n_filters, pitch = words.shape
+        with torch.cuda.device(self.device):
+            for s in range(0, q.shape[0], step):
+                n = min(step, q.shape[0] - s)
+                nbytes = lib.om_sim_topk_filtered_multi_workspace_bytes(n, self.dpad, k, n_filters)
+                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
+                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
+                status = torch.zeros(8, dtype=torch.int64, device=self.device)
+                N.check(lib.om_sim_topk_filtered_multi(mode, N.ptr(q[s:s + n]), n, N.ptr(f32), N.ptr(f16), N.ptr(self._stats), nrows, self.dpad, k,
+                                                       int(id_offset), N.ptr(words), pitch, n_filters,
+                                                       N.ptr(None if filter_of is None else filter_of[s:s + n]),
+                                                       int(n_allowed_min), N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws),
+                                                       nbytes, N.stream_ptr(self.device)))
+                chunks.append((buf, status))
+        return chunks
+
+    def search_device_filtered_multi(self, queries: torch.Tensor, k: int, filters, filter_of=None, id_offset: int = 0, route=None):
+        """`search_device_filtered_multi_async`, waited for: (D, I) on the GPU, and `last_search_info` with `parts` and `redone`."""
+        h = self.search_device_filtered_multi_async(queries, k, filters, filter_of=filter_of, id_offset=id_offset, route=route)
+        self.last_search_info = h.info()
+        return h.D, h.I
+
+    def search_filtered_multi(self, x, k: int, filters, filter_of=None):
+        """faiss-style, as `search`: numpy in, (D, I) numpy out."""
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
+        D, I = self.search_device_filtered_multi(q, k, filters, filter_of=filter_of)
         return D.cpu().numpy(), I.cpu().numpy()
 
     def search(self, x, k: int):

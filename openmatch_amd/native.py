@@ -355,6 +355,14 @@ _SIGNATURES = {
     "om_sim_topk_filtered_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "om_sim_topk_filtered": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_sim_topk_filtered_multi_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int64]),
+    "om_sim_topk_filtered_multi": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
+                                           c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_sim_topk_candidates_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "om_sim_topk_candidates": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_debug_drop_lists_multi": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, C.c_uint32, c_int64, c_int64, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_debug_search_schedule_filtered": (c_int, [c_int, c_int64, c_int64, c_int, c_int64, C.POINTER(c_int64), c_int, C.POINTER(c_int),
                                                   C.POINTER(c_int64)]),
     "om_debug_search_filter_estimate": (c_int, [c_int, c_int64, c_int, c_int64, C.POINTER(c_int64), C.POINTER(c_int64)]),

@@ -218,7 +218,8 @@ class Retriever:
             qid = str(self.query_lookup[q])
             # drop_padding (a doc_filter): the padding is no hit -- it would name the last document, kept by the filter or not
             hits = zip(original[q], D[q], I[q])
-            out[qid] = {str(doc): float(score) for doc, score, row in hits if not (drop_padding and row < 0)}
+            drop = drop_padding if isinstance(drop_padding, bool) else bool(drop_padding[q])      # (per query under doc_filters)
+            out[qid] = {str(doc): float(score) for doc, score, row in hits if not (drop and row < 0)}
         return out
 
     def _doc_row_filter(self, doc_filter):
@@ -227,24 +228,52 @@ class Retriever:
         rows = sorted({row_of[str(doc)] for doc in doc_filter if str(doc) in row_of})
         return RowFilter(self.index, torch.tensor(rows, dtype=torch.int64))
 
-    def search(self, topk: int = 100, doc_filter=None):
+    def _doc_candidates(self, doc_filters, qids):
+        """`doc_filters` ({query id: collection of doc ids}; a {qid: {docid: score}} run works) -> per query of `qids` the ascending rows of
+        its documents through `doc_lookup` (doc ids the index does not hold are ignored; an empty collection gives []), or None for a
+        query id the mapping does not hold: that query is searched unfiltered."""
+        row_of = {str(doc): row for row, doc in enumerate(self.doc_lookup)}
+        by_qid = {str(qid): docs for qid, docs in doc_filters.items()}
+        return [sorted({row_of[str(doc)] for doc in by_qid[str(qid)] if str(doc) in row_of}) if str(qid) in by_qid else None for qid in qids]
+
+    def search(self, topk: int = 100, doc_filter=None, doc_filters=None):
         """doc_filter: None, or a collection of doc ids: only those documents are returned (an exact filtered search:
         `FlatIPIndex.search_filtered`).  Where fewer than `topk` of them are in the index a query gets that many hits and no more:
-        the search's padding is dropped, not mapped to a document as the unfiltered path's is (`_hits_to_dict`)."""
+        the search's padding is dropped, not mapped to a document as the unfiltered path's is (`_hits_to_dict`).
+        doc_filters: None, or a mapping from query id to a collection of doc ids -- a first-stage run as `load_from_trec` returns it
+        works: every query is scored over ITS OWN documents (`FlatIPIndex.search_candidates`: dense re-ranking, no bitmap anywhere).  A
+        query id the mapping does not hold is searched unfiltered; one with an empty collection gets no hits; padding is dropped."""
         logger.info("Searching")
         if self.index is None:
             raise ValueError("Index is not initialized")
-        if doc_filter is not None and (self._sharded or self.args.world_size > 1):
+        if doc_filter is not None and doc_filters is not None:
+            raise ValueError("give doc_filter (one set of documents for all queries) or doc_filters (one per query), not both")
+        if (doc_filter is not None or doc_filters is not None) and (self._sharded or self.args.world_size > 1):
             raise NotImplementedError("doc_filter with an index sharded across ranks: the filtered search serves one local index only")
         if self._sharded:
             return self._search_sharded(topk)
         encoded, lookup = self._load_queries()
         self.query_lookup.extend(lookup)
+        drop = doc_filter is not None
         if doc_filter is not None:
             D, I = self.index.search_filtered(encoded, topk, self._doc_row_filter(doc_filter))
+        elif doc_filters is not None:
+            rows = self._doc_candidates(doc_filters, self.query_lookup[:len(encoded)])
+            own = np.array([r is not None for r in rows], dtype=bool)
+            D = np.full((len(rows), topk), np.finfo(np.float32).min, dtype=np.float32)
+            I = np.full((len(rows), topk), -1, dtype=np.int64)
+            if own.any():
+                lists = [r for r in rows if r is not None]
+                cand = np.full((len(lists), max(1, max(len(r) for r in lists))), -1, dtype=np.int64)
+                for i, r in enumerate(lists):
+                    cand[i, :len(r)] = r
+                D[own], I[own] = self.index.search_candidates(encoded[own], topk, cand)
+            if not own.all():
+                D[~own], I[~own] = self.index.search(encoded[~own], topk)
+            drop = own
         else:
             D, I = self.index.search(encoded, topk)
-        result = self._hits_to_dict(D, I, topk, drop_padding=doc_filter is not None)
+        result = self._hits_to_dict(D, I, topk, drop_padding=drop)
         logger.info("End searching with {} queries".format(len(result)))
         return result
 
