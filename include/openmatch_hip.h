@@ -458,6 +458,22 @@ int om_debug_t5_embed_bwd(int dtype, const void* dy, const int64_t* ids, float* 
                           void* stream);
 int om_debug_t5_bias(const float* table, const int* lut, float* out, int L, int heads, void* stream);
 int om_debug_t5_bias_bwd(const float* drel, const int* lut, float* dtable, int L, int heads, void* stream);
+/* Test hooks of the T5 decoder position's own kernels (csrc/decoder.hip, tests/test_decoder_kernels.py), in the same manner: pointers,
+ * dtype and ranges checked (L in [1, 1024], H == heads * 64, drop_p in [0, 1)), every argument forwarded to the launcher that
+ * om_t5_decoder_step and the train pair call.  q, ctx, dctx, dq: [B, H]; kv, dkv: [B, L, 2H] (K | V); mask: [B, L] int64.
+ * om_debug_dec_cross: single-query cross attention without the 1/sqrt(d) scale, dropout of the probabilities keyed on
+ * (b heads + h) L + l; om_debug_dec_cross_bwd: its backward (every row l < L of dkv is written); om_debug_dec_final: RMSNorm to f32;
+ * om_debug_dec_head_drop: v[b, h, :] scaled or zeroed by ONE draw per (b, h), in place; om_debug_dec_start: x[b, :] = emb[:];
+ * om_debug_dec_cast: f32 -> dtype.  om_debug_dec_site (host only, launches nothing): the seed of dropout site `site` of `layer`. */
+int om_debug_dec_cross(int dtype, const void* q, const void* kv, const int64_t* mask, void* ctx, int64_t B, int L, int H, int heads,
+                       float drop_p, uint64_t seed, void* stream);
+int om_debug_dec_cross_bwd(int dtype, const void* q, const void* kv, const int64_t* mask, const void* dctx, void* dq, void* dkv, int64_t B,
+                           int L, int H, int heads, float drop_p, uint64_t seed, void* stream);
+int om_debug_dec_final(int dtype, const void* x, const float* g, float* out, int64_t B, int H, float eps, void* stream);
+int om_debug_dec_head_drop(int dtype, void* v, int64_t B, int H, float p, uint64_t seed, void* stream);
+int om_debug_dec_start(int dtype, const float* emb, void* x, int64_t B, int H, void* stream);
+int om_debug_dec_cast(int dtype, const float* x, void* y, int64_t n, void* stream);
+uint64_t om_debug_dec_site(uint64_t seed, int layer, int site);
 int om_kernel_timing_enable(int enable);
 int om_kernel_timing_read(int kernel_class, double* total_ms, int64_t* launches, double* flops);
 

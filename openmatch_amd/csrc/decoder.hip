@@ -102,6 +102,33 @@ __global__ __launch_bounds__(256) void dec_final_kernel(const T* __restrict__ x,
   for (int c = threadIdx.x; c < H; c += 256) out[b * H + c] = ElemOps<T>::load(x + b * H + c) * rstd * g[c];
 }
 
+// ---- launchers: the dtype dispatch of each kernel above, one place for the step, the train pair and the test hooks ----
+int dec_start_launch(int dt, const float* emb, void* x, int64_t B, int H, hipStream_t s) {
+  const dim3 grid((unsigned)((B * H + 255) / 256));
+  if (dt == OM_BF16) hipLaunchKernelGGL((dec_start_kernel<bf16_t>), grid, dim3(256), 0, s, emb, (bf16_t*)x, B, H);
+  else if (dt == OM_F16) hipLaunchKernelGGL((dec_start_kernel<f16_t>), grid, dim3(256), 0, s, emb, (f16_t*)x, B, H);
+  else hipLaunchKernelGGL((dec_start_kernel<float>), grid, dim3(256), 0, s, emb, (float*)x, B, H);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+int dec_cross_launch(int dt, const void* q, const void* kv, const int64_t* mask, void* ctx, int64_t B, int L, int H, int heads,
+                     float drop_p, uint64_t seed, hipStream_t s) {
+  const dim3 grid((unsigned)(B * heads));
+  if (dt == OM_BF16) hipLaunchKernelGGL((dec_cross_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)q, (const bf16_t*)kv, mask, (bf16_t*)ctx, L, H, heads, drop_p, seed);
+  else if (dt == OM_F16) hipLaunchKernelGGL((dec_cross_kernel<f16_t>), grid, dim3(256), 0, s, (const f16_t*)q, (const f16_t*)kv, mask, (f16_t*)ctx, L, H, heads, drop_p, seed);
+  else hipLaunchKernelGGL((dec_cross_kernel<float>), grid, dim3(256), 0, s, (const float*)q, (const float*)kv, mask, (float*)ctx, L, H, heads, drop_p, seed);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+int dec_final_launch(int dt, const void* x, const float* g, float* out, int64_t B, int H, float eps, hipStream_t s) {
+  const dim3 grid((unsigned)B);
+  if (dt == OM_BF16) hipLaunchKernelGGL((dec_final_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)x, g, out, H, eps);
+  else if (dt == OM_F16) hipLaunchKernelGGL((dec_final_kernel<f16_t>), grid, dim3(256), 0, s, (const f16_t*)x, g, out, H, eps);
+  else hipLaunchKernelGGL((dec_final_kernel<float>), grid, dim3(256), 0, s, (const float*)x, g, out, H, eps);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
 struct DecWs { char *x, *n, *t, *ctx, *ff, *ff2, *kv; size_t total; };
 DecWs carve(const OmEncoderConfig* c, int64_t B, int64_t L, char* base) {
   size_t off = 0;
@@ -144,10 +171,7 @@ extern "C" int om_t5_decoder_step(const OmEncoderConfig* c, const OmT5DecoderWei
   do {                                                                                              \
     if (om_gemm_nt(dt, A_, lda_, W_, ldw_, dt, C_, ldc_, M_, N_, K_, nullptr, res_, ldr_, act_, s)) return 1; \
   } while (0)
-  if (dt == OM_BF16) hipLaunchKernelGGL((dec_start_kernel<bf16_t>), dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, s, w->start_emb, (bf16_t*)ws.x, B, H);
-  else if (dt == OM_F16) hipLaunchKernelGGL((dec_start_kernel<f16_t>), dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, s, w->start_emb, (f16_t*)ws.x, B, H);
-  else hipLaunchKernelGGL((dec_start_kernel<float>), dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, s, w->start_emb, (float*)ws.x, B, H);
-  OM_LAUNCH_CHECK();
+  RUN(dec_start_launch(dt, w->start_emb, ws.x, B, H, s));
   for (int l = 0; l < w->n_layers; ++l) {
     const OmT5DecoderLayer& lw = w->layers_host[l];
     if (!lw.sa_v_w || !lw.sa_o_w || !lw.sa_ln_g || !lw.ca_q_w || !lw.ca_kv_w || !lw.ca_o_w || !lw.ca_ln_g || !lw.ffn1_w ||
@@ -160,10 +184,7 @@ extern "C" int om_t5_decoder_step(const OmEncoderConfig* c, const OmT5DecoderWei
     RUN(omk_layernorm(dt, ws.x, H, ws.n, H, lw.ca_ln_g, nullptr, B, H, c->ln_eps, 1, s));
     GEMM(ws.n, H, lw.ca_q_w, H, ws.t, H, B, H, H, nullptr, 0, OM_ACT_NONE);
     GEMM(enc_hidden, H, lw.ca_kv_w, H, ws.kv, 2 * H, M, 2 * H, H, nullptr, 0, OM_ACT_NONE);
-    if (dt == OM_BF16) hipLaunchKernelGGL((dec_cross_kernel<bf16_t>), dim3((unsigned)(B * nh)), dim3(256), 0, s, (const bf16_t*)ws.t, (const bf16_t*)ws.kv, attention_mask, (bf16_t*)ws.ctx, (int)L, H, nh, 0.f, 0ull);
-    else if (dt == OM_F16) hipLaunchKernelGGL((dec_cross_kernel<f16_t>), dim3((unsigned)(B * nh)), dim3(256), 0, s, (const f16_t*)ws.t, (const f16_t*)ws.kv, attention_mask, (f16_t*)ws.ctx, (int)L, H, nh, 0.f, 0ull);
-    else hipLaunchKernelGGL((dec_cross_kernel<float>), dim3((unsigned)(B * nh)), dim3(256), 0, s, (const float*)ws.t, (const float*)ws.kv, attention_mask, (float*)ws.ctx, (int)L, H, nh, 0.f, 0ull);
-    OM_LAUNCH_CHECK();
+    RUN(dec_cross_launch(dt, ws.t, ws.kv, attention_mask, ws.ctx, B, (int)L, H, nh, 0.f, 0ull, s));
     GEMM(ws.ctx, H, lw.ca_o_w, H, ws.x, H, B, H, H, ws.x, H, OM_ACT_NONE);
     // feed-forward
     RUN(omk_layernorm(dt, ws.x, H, ws.n, H, lw.ffn_ln_g, nullptr, B, H, c->ln_eps, 1, s));
@@ -175,10 +196,7 @@ extern "C" int om_t5_decoder_step(const OmEncoderConfig* c, const OmT5DecoderWei
     }
     GEMM(ws.ff, F, lw.ffn2_w, F, ws.x, H, B, H, F, ws.x, H, OM_ACT_NONE);
   }
-  if (dt == OM_BF16) hipLaunchKernelGGL((dec_final_kernel<bf16_t>), dim3((unsigned)B), dim3(256), 0, s, (const bf16_t*)ws.x, w->final_ln_g, out_hidden, H, c->ln_eps);
-  else if (dt == OM_F16) hipLaunchKernelGGL((dec_final_kernel<f16_t>), dim3((unsigned)B), dim3(256), 0, s, (const f16_t*)ws.x, w->final_ln_g, out_hidden, H, c->ln_eps);
-  else hipLaunchKernelGGL((dec_final_kernel<float>), dim3((unsigned)B), dim3(256), 0, s, (const float*)ws.x, w->final_ln_g, out_hidden, H, c->ln_eps);
-  OM_LAUNCH_CHECK();
+  RUN(dec_final_launch(dt, ws.x, w->final_ln_g, out_hidden, B, H, c->ln_eps, s));
 #undef GEMM
   return 0;
 }
@@ -223,7 +241,8 @@ __global__ void dec_cast_kernel(const float* __restrict__ x, T* __restrict__ y, 
 //   p = softmax(q . K + mask),  pd = dropout(p),  ctx = pd V        (recomputed)
 //   dV[l] = pd_l dctx,  dpd_l = dctx . V[l],  dp = dropout'(dpd),  ds_l = p_l (dp_l - sum_j p_j dp_j)
 //   dK[l] = ds_l q,  dq = sum_l ds_l K[l]
-// dkv rows of masked keys come out as exact zeros (p_l = 0); every row l < L of the block's sequence is written.
+// dkv rows of masked keys come out as exact zeros, +0 in every bit (p_l = +0 whenever the sequence has an unmasked key; a sequence
+// without one is uniform over its L keys and has gradients); every row l < L of the block's sequence is written.
 template <typename T>
 __global__ __launch_bounds__(256) void dec_cross_bwd_kernel(const T* __restrict__ q, const T* __restrict__ kv,
                                                             const int64_t* __restrict__ mask, const T* __restrict__ dctx,
@@ -292,7 +311,8 @@ __global__ __launch_bounds__(256) void dec_cross_bwd_kernel(const T* __restrict_
     if (l < L) {
       T* dr = dkv + (b * L + l) * 2 * (int64_t)H + h * 64;
 #pragma unroll 8
-      for (int d = 0; d < 64; ++d) { ElemOps<T>::store(dr + d, ds * sq[d]); ElemOps<T>::store(dr + H + d, pd[j] * sd[d]); }
+      // + 0.f: a masked (or dropped) key has p_l = +0, and +0 times a negative factor is -0; the sum with +0 stores +0
+      for (int d = 0; d < 64; ++d) { ElemOps<T>::store(dr + d, ds * sq[d] + 0.f); ElemOps<T>::store(dr + H + d, pd[j] * sd[d] + 0.f); }
     }
   }
   __syncthreads();
@@ -302,6 +322,34 @@ __global__ __launch_bounds__(256) void dec_cross_bwd_kernel(const T* __restrict_
   part[grp][d] = acc;
   __syncthreads();
   if (tid < 64) ElemOps<T>::store(dq + b * H + h * 64 + tid, (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]));
+}
+
+// ---- launchers of the three training kernels (dtype dispatch).  dec_cast's grid is capped at 8 192 blocks and its kernel strides:
+// the cast of d_out [B, H] used to launch one block per 256 elements uncapped, the same grid up to 2 M elements and the same values beyond ----
+int dec_head_drop_launch(int dt, void* v, int64_t B, int H, float p, uint64_t seed, hipStream_t s) {
+  const dim3 grid((unsigned)((B * H + 255) / 256));
+  if (dt == OM_BF16) hipLaunchKernelGGL((dec_head_drop_kernel<bf16_t>), grid, dim3(256), 0, s, (bf16_t*)v, B, H, p, seed);
+  else if (dt == OM_F16) hipLaunchKernelGGL((dec_head_drop_kernel<f16_t>), grid, dim3(256), 0, s, (f16_t*)v, B, H, p, seed);
+  else hipLaunchKernelGGL((dec_head_drop_kernel<float>), grid, dim3(256), 0, s, (float*)v, B, H, p, seed);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+int dec_cast_launch(int dt, const float* x, void* y, int64_t n, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256));
+  if (dt == OM_BF16) hipLaunchKernelGGL((dec_cast_kernel<bf16_t>), grid, dim3(256), 0, s, x, (bf16_t*)y, n);
+  else if (dt == OM_F16) hipLaunchKernelGGL((dec_cast_kernel<f16_t>), grid, dim3(256), 0, s, x, (f16_t*)y, n);
+  else hipLaunchKernelGGL((dec_cast_kernel<float>), grid, dim3(256), 0, s, x, (float*)y, n);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+int dec_cross_bwd_launch(int dt, const void* q, const void* kv, const int64_t* mask, const void* dctx, void* dq, void* dkv, int64_t B,
+                         int L, int H, int heads, float drop_p, uint64_t seed, hipStream_t s) {
+  const dim3 grid((unsigned)(B * heads));
+  if (dt == OM_BF16) hipLaunchKernelGGL((dec_cross_bwd_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)q, (const bf16_t*)kv, mask, (const bf16_t*)dctx, (bf16_t*)dq, (bf16_t*)dkv, L, H, heads, drop_p, seed);
+  else if (dt == OM_F16) hipLaunchKernelGGL((dec_cross_bwd_kernel<f16_t>), grid, dim3(256), 0, s, (const f16_t*)q, (const f16_t*)kv, mask, (const f16_t*)dctx, (f16_t*)dq, (f16_t*)dkv, L, H, heads, drop_p, seed);
+  else hipLaunchKernelGGL((dec_cross_bwd_kernel<float>), grid, dim3(256), 0, s, (const float*)q, (const float*)kv, mask, (const float*)dctx, (float*)dq, (float*)dkv, L, H, heads, drop_p, seed);
+  OM_LAUNCH_CHECK();
+  return 0;
 }
 
 struct DecTape {
@@ -399,9 +447,7 @@ int dec_train_forward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, c
   const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nl = w->n_layers;
   const int64_t M = B * L;
   const int kind = (c->act & 0xff) == OM_ACT_GELU_TANH ? 1 : 0;
-  const unsigned gbh = (unsigned)((B * H + 255) / 256);
-  hipLaunchKernelGGL((dec_start_kernel<T>), dim3(gbh), dim3(256), 0, s, w->start_emb, (T*)t.at(0, t.o_x0), B, H);
-  OM_LAUNCH_CHECK();
+  RUN(dec_start_launch(dt, w->start_emb, t.at(0, t.o_x0), B, H, s));
   if (p > 0.f) RUN(omk_dropout(dt, t.at(0, t.o_x0), t.at(0, t.o_x0), B * H, p, dec_site(seed, 0, 0), s));
   for (int l = 0; l < nl; ++l) {
     const OmT5DecoderLayer& lw = w->layers_host[l];
@@ -411,15 +457,13 @@ int dec_train_forward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, c
     // self-attention over the single position
     RUN(omk_layernorm(dt, x0, H, ws.n, H, lw.sa_ln_g, nullptr, B, H, c->ln_eps, 1, s));
     RUN(dec_gemm(dt, ws.n, H, lw.sa_v_w, v, dt, B, H, nullptr, 0.f, 0, s));
-    if (p > 0.f) { hipLaunchKernelGGL((dec_head_drop_kernel<T>), dim3(gbh), dim3(256), 0, s, (T*)v, B, H, p, dec_site(seed, l, 1)); OM_LAUNCH_CHECK(); }
+    if (p > 0.f) RUN(dec_head_drop_launch(dt, v, B, H, p, dec_site(seed, l, 1), s));
     RUN(dec_gemm(dt, v, H, lw.sa_o_w, x1, dt, B, H, x0, p, dec_site(seed, l, 6), s));
     // cross-attention
     RUN(omk_layernorm(dt, x1, H, ws.n, H, lw.ca_ln_g, nullptr, B, H, c->ln_eps, 1, s));
     RUN(dec_gemm(dt, ws.n, H, lw.ca_q_w, q, dt, B, H, nullptr, 0.f, 0, s));
     RUN(dec_gemm(dt, enc_hidden, H, lw.ca_kv_w, kv, dt, M, 2 * H, nullptr, 0.f, 0, s));
-    hipLaunchKernelGGL((dec_cross_kernel<T>), dim3((unsigned)(B * nh)), dim3(256), 0, s, (const T*)q, (const T*)kv, attention_mask,
-                       (T*)ctx, (int)L, H, nh, p, dec_site(seed, l, 2));
-    OM_LAUNCH_CHECK();
+    RUN(dec_cross_launch(dt, q, kv, attention_mask, ctx, B, (int)L, H, nh, p, dec_site(seed, l, 2), s));
     RUN(dec_gemm(dt, ctx, H, lw.ca_o_w, x2, dt, B, H, x1, p, dec_site(seed, l, 3), s));
     // feed-forward
     RUN(omk_layernorm(dt, x2, H, ws.n, H, lw.ffn_ln_g, nullptr, B, H, c->ln_eps, 1, s));
@@ -441,7 +485,6 @@ int dec_train_backward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, 
   const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nl = w->n_layers;
   const int64_t M = B * L;
   const int kind = (c->act & 0xff) == OM_ACT_GELU_TANH ? 1 : 0;
-  const unsigned gbh = (unsigned)((B * H + 255) / 256);
   // every weight transposed once (the data-gradient GEMMs' B operands)
   {
     std::vector<const void*> in; std::vector<void*> out; std::vector<int> R, C;
@@ -461,8 +504,7 @@ int dec_train_backward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, 
   if (p > 0.f) { RUN(omk_dropout(OM_F32, d_out, ws.do32, B * H, p, dec_site(seed, nl, 1), s)); dof = ws.do32; }
   const void* dy = dof;
   if (dt != OM_F32) {
-    hipLaunchKernelGGL((dec_cast_kernel<T>), dim3(gbh), dim3(256), 0, s, dof, (T*)ws.dn, B * H);
-    OM_LAUNCH_CHECK();
+    RUN(dec_cast_launch(dt, dof, ws.dn, B * H, s));
     dy = ws.dn;
   }
   char* dx = ws.dxa;
@@ -496,9 +538,7 @@ int dec_train_backward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, 
     if (p > 0.f) { RUN(omk_dropout(dt, dx, ws.dd, B * H, p, dec_site(seed, l, 3), s)); dC = ws.dd; }
     RUN(dec_wgrad(dt, dC, H, ctx, H, lg.ca_o_w, B, ws, s));
     RUN(dec_gemm(dt, dC, H, wt.ca_o, ws.dctx, dt, B, H, nullptr, 0.f, 0, s));             // dctx = dC Wo
-    hipLaunchKernelGGL((dec_cross_bwd_kernel<T>), dim3((unsigned)(B * nh)), dim3(256), 0, s, (const T*)q, (const T*)kv, attention_mask,
-                       (const T*)ws.dctx, (T*)ws.dq, (T*)ws.dkv, (int)L, H, nh, p, dec_site(seed, l, 2));
-    OM_LAUNCH_CHECK();
+    RUN(dec_cross_bwd_launch(dt, q, kv, attention_mask, ws.dctx, ws.dq, ws.dkv, B, (int)L, H, nh, p, dec_site(seed, l, 2), s));
     RUN(dec_wgrad(dt, ws.dkv, 2 * H, enc_hidden, H, lg.ca_kv_w, M, ws, s));               // d(Wk | Wv)
     RUN(dec_gemm(dt, ws.dkv, 2 * H, wt.ca_kv, ws.dE, OM_F32, M, H, first_e ? nullptr : ws.dE, 0.f, 0, s));   // dE (+)= dkv Wkv
     first_e = false;
@@ -512,7 +552,7 @@ int dec_train_backward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, 
     if (p > 0.f) { RUN(omk_dropout(dt, dx, ws.dd, B * H, p, dec_site(seed, l, 6), s)); dA = ws.dd; }
     RUN(dec_wgrad(dt, dA, H, v, H, lg.sa_o_w, B, ws, s));
     RUN(dec_gemm(dt, dA, H, wt.sa_o, ws.dq, dt, B, H, nullptr, 0.f, 0, s));                // dv' = dA Wo
-    if (p > 0.f) { hipLaunchKernelGGL((dec_head_drop_kernel<T>), dim3(gbh), dim3(256), 0, s, (T*)ws.dq, B, H, p, dec_site(seed, l, 1)); OM_LAUNCH_CHECK(); }
+    if (p > 0.f) RUN(dec_head_drop_launch(dt, ws.dq, B, H, p, dec_site(seed, l, 1), s));
     RUN(omk_layernorm(dt, x0, H, ws.n, H, lw.sa_ln_g, nullptr, B, H, c->ln_eps, 1, s));
     RUN(dec_wgrad(dt, ws.dq, H, ws.n, H, lg.sa_v_w, B, ws, s));
     RUN(dec_gemm(dt, ws.dq, H, wt.sa_v, ws.dn, dt, B, H, nullptr, 0.f, 0, s));             // dn1 = dv Wv
@@ -527,9 +567,7 @@ int dec_train_backward_t(const OmEncoderConfig* c, const OmT5DecoderWeights* w, 
   if (dt == OM_F32) {
     OM_HIP(hipMemcpyAsync(d_enc_hidden, ws.dE, (size_t)M * H * 4, hipMemcpyDeviceToDevice, s));
   } else {
-    const int64_t n = M * H;
-    hipLaunchKernelGGL((dec_cast_kernel<T>), dim3((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256)), dim3(256), 0, s, ws.dE, (T*)d_enc_hidden, n);
-    OM_LAUNCH_CHECK();
+    RUN(dec_cast_launch(dt, ws.dE, d_enc_hidden, M * H, s));
   }
   return 0;
 }
@@ -572,6 +610,7 @@ extern "C" int om_t5_decoder_train_backward(const OmEncoderConfig* c, const OmT5
   if (dec_check(c, w, L)) return 1;
   if (!g->layers_host || !g->final_ln_g) OM_FAIL("incomplete decoder gradient buffers");
   if (((uintptr_t)workspace & 255) || ((uintptr_t)tape_mem & 255)) OM_FAIL("tape/workspace must be 256-byte aligned");
+  if (dropout < 0.f || dropout >= 1.f) OM_FAIL("dropout must be in [0, 1)");      // as the forward: the masks are regenerated from it
   const DecTape t = dec_tape(c, w->n_layers, B, L, (char*)const_cast<void*>(tape_mem));
   DecTrainWs ws = dec_train_ws(c, w->n_layers, B, L, (char*)workspace);
   if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
@@ -593,3 +632,60 @@ extern "C" int om_linear_f32_backward(const float* dy, const float* x, const flo
   if (dx) RUN(omk_small_nn(dy, w, dx, B, D, K, s));
   return 0;
 }
+
+// ---- test hooks of this file's kernels (include/openmatch_hip.h, tests/test_decoder_kernels.py): pointers, dtype and ranges
+// checked, then every argument forwarded to the launcher the step and the train pair call ----
+#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+#define OM_DBG_CROSS(what)                                                                           \
+  OM_DBG_DTYPE(what);                                                                                \
+  if (L < 1 || L > DEC_MAX_L) OM_FAIL(what ": sequence length must be in [1,1024]");                  \
+  if (heads < 1 || H != heads * 64) OM_FAIL(what ": H must be heads * 64");                           \
+  if (!(drop_p >= 0.f && drop_p < 1.f)) OM_FAIL(what ": drop_p must be in [0, 1)");                   \
+  if (B > 0x7fffffff / heads) OM_FAIL(what ": B * heads must fit a grid");                            \
+  if (B <= 0) return 0
+extern "C" int om_debug_dec_cross(int dtype, const void* q, const void* kv, const int64_t* mask, void* ctx, int64_t B, int L, int H,
+                                  int heads, float drop_p, uint64_t seed, void* stream) {
+  if (!q || !kv || !mask || !ctx) OM_FAIL("om_debug_dec_cross: null argument");
+  OM_DBG_CROSS("om_debug_dec_cross");
+  return dec_cross_launch(dtype, q, kv, mask, ctx, B, L, H, heads, drop_p, seed, (hipStream_t)stream);
+}
+extern "C" int om_debug_dec_cross_bwd(int dtype, const void* q, const void* kv, const int64_t* mask, const void* dctx, void* dq, void* dkv,
+                                      int64_t B, int L, int H, int heads, float drop_p, uint64_t seed, void* stream) {
+  if (!q || !kv || !mask || !dctx || !dq || !dkv) OM_FAIL("om_debug_dec_cross_bwd: null argument");
+  OM_DBG_CROSS("om_debug_dec_cross_bwd");
+  return dec_cross_bwd_launch(dtype, q, kv, mask, dctx, dq, dkv, B, L, H, heads, drop_p, seed, (hipStream_t)stream);
+}
+extern "C" int om_debug_dec_final(int dtype, const void* x, const float* g, float* out, int64_t B, int H, float eps, void* stream) {
+  if (!x || !g || !out) OM_FAIL("om_debug_dec_final: null argument");
+  OM_DBG_DTYPE("om_debug_dec_final");
+  if (H < 1 || B > 0x7fffffff) OM_FAIL("om_debug_dec_final: H must be at least 1 and B fit a grid");
+  if (B <= 0) return 0;
+  return dec_final_launch(dtype, x, g, out, B, H, eps, (hipStream_t)stream);
+}
+extern "C" int om_debug_dec_head_drop(int dtype, void* v, int64_t B, int H, float p, uint64_t seed, void* stream) {
+  if (!v) OM_FAIL("om_debug_dec_head_drop: null argument");
+  OM_DBG_DTYPE("om_debug_dec_head_drop");
+  if (H < 64 || H % 64) OM_FAIL("om_debug_dec_head_drop: H must be heads * 64");
+  if (!(p >= 0.f && p < 1.f)) OM_FAIL("om_debug_dec_head_drop: drop_p must be in [0, 1)");
+  if (B > (int64_t)0x7fffffff * 256 / H) OM_FAIL("om_debug_dec_head_drop: B * H must fit a grid");
+  if (B <= 0) return 0;
+  return dec_head_drop_launch(dtype, v, B, H, p, seed, (hipStream_t)stream);
+}
+extern "C" int om_debug_dec_start(int dtype, const float* emb, void* x, int64_t B, int H, void* stream) {
+  if (!emb || !x) OM_FAIL("om_debug_dec_start: null argument");
+  OM_DBG_DTYPE("om_debug_dec_start");
+  if (H < 1) OM_FAIL("om_debug_dec_start: H must be at least 1");
+  if (B > (int64_t)0x7fffffff * 256 / H) OM_FAIL("om_debug_dec_start: B * H must fit a grid");
+  if (B <= 0) return 0;
+  return dec_start_launch(dtype, emb, x, B, H, (hipStream_t)stream);
+}
+extern "C" int om_debug_dec_cast(int dtype, const float* x, void* y, int64_t n, void* stream) {
+  if (!x || !y) OM_FAIL("om_debug_dec_cast: null argument");
+  OM_DBG_DTYPE("om_debug_dec_cast");
+  if (n <= 0) return 0;
+  return dec_cast_launch(dtype, x, y, n, (hipStream_t)stream);
+}
+// host only: the per-site dropout seed, so that the tests' Python port of it is pinned to this file
+extern "C" uint64_t om_debug_dec_site(uint64_t seed, int layer, int site) { return dec_site(seed, layer, site); }
+#undef OM_DBG_CROSS
+#undef OM_DBG_DTYPE

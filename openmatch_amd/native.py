@@ -268,6 +268,14 @@ _SIGNATURES = {
     "om_debug_t5_embed_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "om_debug_t5_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "om_debug_t5_bias_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "om_debug_dec_cross": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, C.c_uint64, c_void_p]),
+    "om_debug_dec_cross_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                       c_float, C.c_uint64, c_void_p]),
+    "om_debug_dec_final": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
+    "om_debug_dec_head_drop": (c_int, [c_int, c_void_p, c_int64, c_int, c_float, C.c_uint64, c_void_p]),
+    "om_debug_dec_start": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "om_debug_dec_cast": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "om_debug_dec_site": (C.c_uint64, [C.c_uint64, c_int, c_int]),
     "om_encoder_workspace_bytes": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64]),
     "om_t5_decoder_workspace_bytes": (c_size_t, [C.POINTER(OmEncoderConfig), c_int64, c_int64]),
     "om_t5_decoder_step": (c_int, [C.POINTER(OmEncoderConfig), C.POINTER(OmT5DecoderWeights), c_void_p, c_void_p,

@@ -77,6 +77,9 @@ Measured constants: see RSQRT_MEASURED and DIVSQRT_MEASURED below.
 What this list used to name as untested at kernel level now has its tests: the transposes (omk_transpose, omk_transpose_batch), the T5 activation,
 embedding and bias kernels and omk_zero_rows_from are in tests/test_train_leftover_kernels.py, the weight-gradient contractions in
 tests/test_gemm_tn_kernels.py, the GEMM epilogue's dropout in tests/test_gemm_epilogues.py (test_dropout_residual, test_pre_act).
+One file was not on that list and had no kernel-level test either: csrc/decoder.hip, the T5 decoder position (dec_cross, dec_cross_bwd,
+dec_final, dec_head_drop, dec_start, dec_cast and the hand-written train forward / backward pair with its seven dropout sites per
+layer).  Its kernels and its whole step against float64 autograd under the kernels' own masks are in tests/test_decoder_kernels.py.
 """
 import ctypes as C
 import math
