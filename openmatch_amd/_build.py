@@ -17,7 +17,8 @@ LIB_PATH = os.path.join(CSRC, "libopenmatch_hip.so")
 ARCH = "gfx950"
 SOURCES = ["abi.cpp", "comm.cpp", "gemm.hip", "gemm_wide6_bf16.hip", "gemm_wide6_f32.hip", "gemm_wide7.hip", "gemm_wide7_ln.hip", "gemm_wide7_f16.hip", "gemm_tn.hip", "elementwise.hip", "attention.hip", "attention_d32.hip", "attention_band.hip", "attention_causal.hip", "attention_causal128.hip", "attention_d256.hip", "attention_bwd16.hip", "encoder.hip", "encoder_causal.hip", "encoder_gemma3.hip", "decoder.hip",
            "search.hip", "contrastive.hip", "train_kernels.hip", "train.hip", "optim.hip", "gemm_skinny.hip"]
-HEADERS = ["common.h", "gemm_core.h", "gemm_core2.h", "gemm_core6.h", "gemm_core7.h", "gemm_wide7.h", "gemm_wide6.h", "gemm_plan.h", "gemm_tn_plan.h", "gemm_epilogue.h", "gemm_epilogue6.h", "attn_common.h", "attn_chunked.h", "attn_chunked_wide.h", "attn_plan.h", "encoder_plan.h", "search_plan.h", "train_kernels.h", "kernels.h", os.path.join("..", "..", "include", "openmatch_hip.h")]
+# every header: a list by hand has missed one before, and then editing it did not rebuild its users
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "openmatch_hip.h")]
 
 
 def _hipcc():

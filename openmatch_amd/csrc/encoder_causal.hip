@@ -19,8 +19,10 @@
 // a peaked-attention model (q / k weights x 6, llama3 rope, 512 tokens) bfloat16 sat at 1 - cos 2.65e-3 against HF's own autocast
 // at 1.77e-3.
 //
-// Activation buffers ([M = B*L tokens] x width): x [M, H] f32 residual stream; in the compute dtype y normed input,
-// qkv [M, (heads + 2 kv) * head_dim], ctx [M, A = heads * head_dim], ff / ff2 [M, F].
+// What this stack shares with Gemma3's (encoder_gemma3.hip) lives in prenorm_stack.h: the workspace (PrenormWs: x [M, H] f32 residual
+// stream; in the compute dtype y, qkv, ctx, ff / ff2) and its carving, the argument checks, the launches in front of the layer loop
+// (mask extents, packed rows, embedding) and behind it (final norm, pooling first / last / mean, head), and the packed-rows rule.  Here:
+// check_cfg / check_cfg2, the per-layer pointer checks, the layer loop and the SwiGLU kernel.
 //
 // om_causal2_encoder_forward / _packed (Qwen3Model, HF:models/qwen3/modeling_qwen3.py) are the same loop with three things read from
 // their config instead of assumed: head_dim 64 or 128, an attention width A that need not equal H (o_proj contracts over A), and the
@@ -36,7 +38,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "kernels.h"
+#include "prenorm_stack.h"
 
 namespace {
 
@@ -88,59 +90,6 @@ int omk_silu_mul(int dtype, const void* gate, void* up, int64_t n, hipStream_t s
   return 0;
 }
 
-// rows[b] = the token row of sequence b's LAST unmasked token (kmax[b] = 1 + its index; L for a row without one: the last column)
-__global__ void last_rows_kernel(const int* __restrict__ kmax, int64_t B, int L, int* __restrict__ rows) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) rows[b] = (int)(b * L + kmax[b] - 1);
-}
-
-// packed rows: the row of sequence b's last unmasked token is cu[b] + kmax[b] - 1, clamped into the buffer as cls_rows is (a bound that
-// was too small: the representations are poisoned afterwards)
-__global__ void last_rows_packed_kernel(const int* __restrict__ kmax, const int* __restrict__ cu, int64_t B, int rows_cap, int* __restrict__ rows) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) rows[b] = min(cu[b] + kmax[b] - 1, rows_cap - 1);
-}
-
-struct CausalWs {
-  char *x, *y, *qkv, *ctx, *ff, *ff2;
-  float *pooled, *headout, *final32;
-  int *kmax, *last_rows;
-  int *cu, *cls_rows, *row_map;   // packed rows: sequence offsets [B + 2], first row of each sequence [B], token of each row [packed_rows]
-  int64_t Mp;       // row count the contractions run on: M rounded up to whole 256-row tiles for large 16-bit batches (as encoder.hip)
-  size_t total;
-};
-
-// head_dim: 64 for the Llama / Qwen2 entries; the config's own for the om_causal2_* entries, whose attention width A = n_heads * head_dim
-// need not equal the hidden size
-CausalWs carve(const OmCausalConfig* cc, int head_dim, int64_t B, int64_t L, char* base, int64_t packed_rows = 0) {
-  const OmEncoderConfig* c = &cc->base;
-  const bool half = c->dtype == OM_BF16 || c->dtype == OM_F16;
-  const size_t es = half ? 2 : 4;
-  const size_t Mreal = packed_rows > 0 ? (size_t)packed_rows : (size_t)B * L, H = c->hidden, F = c->ffn;
-  const size_t A = (size_t)c->n_heads * head_dim, P = (size_t)(c->n_heads + 2 * cc->n_kv_heads) * head_dim;
-  const size_t M = (half && Mreal >= 512) ? (Mreal + 255) / 256 * 256 : Mreal;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
-  CausalWs w;
-  w.x = take(M * H * 4);
-  w.y = take(M * H * es);
-  w.qkv = take(M * P * es);
-  w.ctx = take(M * A * es);
-  w.ff = take(M * F * es);
-  w.ff2 = take(M * F * es);
-  w.pooled = (float*)take((size_t)B * H * 4);
-  w.headout = (float*)take((size_t)B * (c->head_out > 0 ? c->head_out : 1) * 4);
-  w.kmax = (int*)take((size_t)B * 4);
-  w.last_rows = (int*)take((size_t)B * 4);
-  w.final32 = (float*)take(c->pooling == OM_POOL_MEAN ? Mreal * H * 4 : 0);      // mean pooling reads every row of the f32 final norm
-  w.cu = (int*)take(packed_rows > 0 ? (size_t)(B + 2) * 4 : 0);
-  w.cls_rows = (int*)take(packed_rows > 0 ? (size_t)B * 4 : 0);
-  w.row_map = (int*)take(packed_rows > 0 ? (size_t)packed_rows * 4 : 0);
-  w.Mp = (int64_t)M;
-  w.total = off;
-  return w;
-}
-
 int check_cfg(const OmCausalConfig* cc) {
   const OmEncoderConfig* c = &cc->base;
   if (c->dtype != OM_F32 && c->dtype != OM_BF16 && c->dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
@@ -182,13 +131,9 @@ int check_cfg2(const OmCausalConfig2* c2) {
   return 0;
 }
 
-bool packed_rows_rule(int64_t B, int64_t L, int64_t packed_rows) {
-  if (B <= 0 || L <= 0 || L > 1024 || packed_rows <= 0) return false;
-  if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) return false;
-  // few rows: the padded entry's contractions take the weight-streaming kernel -- decided there on ITS row count B * L, so a batch
-  // whose PADDED form is that small is sent back (as om_encoder_packed_supported)
-  return B * L > (int64_t)om_option(OM_OPT_GEMM_SKINNY_M);
-}
+// how the shared refusals read (prenorm_stack.h); both serve OM_POOL_LAST and take packed_rows from 512
+const PrenormFamily kCausal{"", 512, true, "layers_host is null", "Llama / Qwen2 need word_emb and final_ln_g (norm.weight)"};
+const PrenormFamily kQwen3{"", 512, true, "layers_host is null", "Qwen3 needs word_emb and final_ln_g (norm.weight)"};
 
 // What the one layer loop reads beyond OmCausalConfig: the Llama / Qwen2 entries fill it with head_dim 64, their 32 frequencies and no
 // norm; `v2` selects the names in messages and the q / k norm + rotation pass (the older entries keep omk_rope_gqa)
@@ -203,20 +148,20 @@ struct CausalExtra {
 
 extern "C" size_t om_causal_encoder_workspace_bytes(const OmCausalConfig* cfg, int64_t B, int64_t L) {
   if (!cfg || B <= 0 || L <= 0 || cfg->n_kv_heads < 1 || cfg->base.n_heads < 1) return 0;
-  return carve(cfg, 64, B, L, nullptr).total;
+  return prenorm_carve(&cfg->base, cfg->n_kv_heads, 64, true, B, L, nullptr).total;
 }
 
 // Whether om_causal_encoder_forward_packed takes (cfg, B, L, packed_rows): the stack is unfused, so every compute format and none of
 // the fused-LayerNorm switches enter.  No region is excluded on grounds of speed: the packed entry's throughput has not been measured
 // yet (DESIGN.md section 8 says what is to be done when it is).
 extern "C" int om_causal_encoder_packed_supported(const OmCausalConfig* cc, int64_t B, int64_t L, int64_t packed_rows) {
-  if (!cc || !packed_rows_rule(B, L, packed_rows)) return 0;
+  if (!cc || !prenorm_packed_rows_rule(B, L, packed_rows, kCausal.packed_floor)) return 0;
   return check_cfg(cc) ? 0 : 1;
 }
 
 extern "C" size_t om_causal_encoder_workspace_bytes_packed(const OmCausalConfig* cfg, int64_t B, int64_t L, int64_t packed_rows) {
   if (!cfg || B <= 0 || L <= 0 || packed_rows <= 0 || cfg->n_kv_heads < 1 || cfg->base.n_heads < 1) return 0;
-  return carve(cfg, 64, B, L, nullptr, packed_rows).total;
+  return prenorm_carve(&cfg->base, cfg->n_kv_heads, 64, true, B, L, nullptr, packed_rows).total;
 }
 
 // all four forward entries (the config is checked by the caller): packed_rows == 0 is the padded layout [B * L rows], > 0 the packed one
@@ -225,55 +170,33 @@ static int causal_forward_impl(const OmCausalConfig* cc, const CausalExtra& ex, 
                                size_t workspace_bytes, void* stream, int64_t packed_rows) {
   const OmEncoderConfig* c = &cc->base;
   if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("sequence length must be in [1,1024]");
-  const bool packed = packed_rows > 0;
-  if (packed) {
-    if (c->pooling == OM_POOL_NONE || out_hidden) OM_FAIL("packed rows: representations only (a pooling, no out_hidden)");
-    if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255) OM_FAIL("packed_rows: a multiple of 256 in [512, B * L + 255]");
-  }
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  CausalWs ws = carve(cc, ex.head_dim, B, L, (char*)workspace, packed_rows);
-  if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
-  if (c->pooling != OM_POOL_NONE && !out_reps) OM_FAIL("out_reps required when pooling is set");
+  PrenormWs ws;
+  RUN(prenorm_check(ex.v2 ? kQwen3 : kCausal, c, cc->n_kv_heads, ex.head_dim, w, w->layers_host != nullptr, B, L, out_hidden, out_reps, workspace,
+                    workspace_bytes, packed_rows, &ws));
+  // every layer's pointers are checked before the first launch: a refused call leaves nothing on the stream
   const OmLayerWeights* Ls = w->layers_host;
-  if (c->n_layers > 0 && !Ls) OM_FAIL("layers_host is null");
-  if (!w->word_emb || !w->final_ln_g) OM_FAIL(ex.v2 ? "Qwen3 needs word_emb and final_ln_g (norm.weight)" : "Llama / Qwen2 need word_emb and final_ln_g (norm.weight)");
-  hipStream_t s = (hipStream_t)stream;
-  const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nkv = cc->n_kv_heads;
-  const int hd = ex.head_dim, A = nh * hd, P = (nh + 2 * nkv) * hd;      // A: the attention width (ctx rows, o_proj's contraction)
-  const int64_t M = packed ? packed_rows : B * L, Mg = ws.Mp;
-  const int* const row_map = packed ? ws.row_map : nullptr;
-
-#define GEMM(A_, lda_, W_, ldw_, C_, ldc_, N_, K_, bias_, res_, ldr_)                                      \
-  do {                                                                                                     \
-    if (om_gemm_nt(dt, A_, lda_, W_, ldw_, dt, C_, ldc_, Mg, N_, K_, bias_, res_, ldr_, OM_ACT_NONE, s)) \
-      return 1;                                                                                            \
-  } while (0)
-  // x (f32) += A W^T (+ bias): operands in the compute dtype, f32 output and residual
-#define GEMM_ACC(A_, lda_, W_, ldw_, N_, K_, bias_)                                                              \
-  do {                                                                                                           \
-    if (om_gemm_nt(dt, A_, lda_, W_, ldw_, OM_F32, ws.x, N_, Mg, N_, K_, bias_, ws.x, N_, OM_ACT_NONE, s)) \
-      return 1;                                                                                                  \
-  } while (0)
-#define RUN(expr) do { if (expr) return 1; } while (0)
-
-  RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-  if (packed) {
-    RUN(omk_pack_rows(ws.kmax, B, (int)L, packed_rows, ws.cu, ws.cls_rows, ws.row_map, s));
-    OM_HIP(hipMemsetAsync(ws.ctx, 0, (size_t)M * A * (dt == OM_F32 ? 4 : 2), s));      // the tail rows: no attention workgroup writes them
-  }
-  RUN(omk_embed(OM_F32, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
-  const float scale = 1.0f / sqrtf((float)c->head_dim);
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
     if (!lw.qkv_w || !lw.o_w || !lw.ln1_g || !lw.ln2_g || !lw.ffn1_w || !lw.ffn1g_w || !lw.ffn2_w)
       OM_FAIL(ex.v2 ? "Qwen3 layers need qkv_w, o_w, ln1_g, ln2_g, ffn1_w (gate_proj), ffn1g_w (up_proj) and ffn2_w (down_proj)"
                     : "Llama / Qwen2 layers need qkv_w, o_w, ln1_g, ln2_g, ffn1_w (gate_proj), ffn1g_w (up_proj) and ffn2_w (down_proj)");
+    if (ex.qk_norm && (!ex.qk_norm[l].q_norm_g || !ex.qk_norm[l].k_norm_g)) OM_FAIL("Qwen3 layers with qk_norm need q_norm_g and k_norm_g");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const bool packed = packed_rows > 0;
+  const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nkv = cc->n_kv_heads, hd = ex.head_dim, A = ws.A, P = ws.P;
+  const int64_t M = ws.M;
+  const int* const row_map = packed ? ws.row_map : nullptr;
+  const PrenormGemm gemm{dt, ws.Mp, s};
+
+  RUN(prenorm_begin(c, w, ws, input_ids, attention_mask, B, L, packed_rows, s));
+  const float scale = 1.0f / sqrtf((float)c->head_dim);
+  for (int l = 0; l < c->n_layers; ++l) {
+    const OmLayerWeights& lw = Ls[l];
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));   // input_layernorm
-    GEMM(ws.y, H, lw.qkv_w, H, ws.qkv, P, P, H, lw.qkv_b, nullptr, 0);
+    RUN(gemm(ws.y, H, lw.qkv_w, H, dt, ws.qkv, P, P, H, lw.qkv_b));
     if (ex.v2) {                                                                                           // q_norm, k_norm, rotary positions
       const OmCausalQkNorm* qn = ex.qk_norm ? &ex.qk_norm[l] : nullptr;
-      if (qn && (!qn->q_norm_g || !qn->k_norm_g)) OM_FAIL("Qwen3 layers with qk_norm need q_norm_g and k_norm_g");
       RUN(omk_qknorm_rope(dt, ws.qkv, M, (int)L, nh, nkv, hd, qn ? qn->q_norm_g : nullptr, qn ? qn->k_norm_g : nullptr, c->ln_eps, ex.inv_freq,
                           cc->rope_attention_scaling, s, row_map));
     } else {
@@ -286,39 +209,15 @@ static int causal_forward_impl(const OmCausalConfig* cc, const CausalExtra& ex, 
       if (packed) RUN(omk_attention_causal_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
       else RUN(omk_attention_causal(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
     }
-    GEMM_ACC(ws.ctx, A, lw.o_w, A, H, A, lw.o_b);                                                          // x += o_proj(ctx)
+    // the residual sums: operands in the compute dtype, f32 output and residual (x += A W^T + bias)
+    RUN(gemm(ws.ctx, A, lw.o_w, A, OM_F32, ws.x, H, H, A, lw.o_b, ws.x, H));                               // x += o_proj(ctx)
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // post_attention_layernorm
-    GEMM(ws.y, H, lw.ffn1_w, H, ws.ff2, F, F, H, nullptr, nullptr, 0);                                     // gate_proj
-    GEMM(ws.y, H, lw.ffn1g_w, H, ws.ff, F, F, H, nullptr, nullptr, 0);                                     // up_proj
+    RUN(gemm(ws.y, H, lw.ffn1_w, H, dt, ws.ff2, F, F, H));                                                 // gate_proj
+    RUN(gemm(ws.y, H, lw.ffn1g_w, H, dt, ws.ff, F, F, H));                                                 // up_proj
     RUN(omk_silu_mul(dt, ws.ff2, ws.ff, M * F, s));                                                        // ff = silu(gate) * up
-    GEMM_ACC(ws.ff, F, lw.ffn2_w, F, H, F, nullptr);                                                       // x += down_proj(ff)
+    RUN(gemm(ws.ff, F, lw.ffn2_w, F, OM_F32, ws.x, H, H, F, nullptr, ws.x, H));                            // x += down_proj(ff)
   }
-  // norm: the hidden states in the compute dtype when asked for; the pooled rows ALWAYS as f32 rows of the normalisation of just the
-  // rows pooling reads (the reference's autocast leaves the norm's arithmetic in fp32), as the other stacks do
-  const float* fg = w->final_ln_g;
-  const float* xf = (const float*)ws.x;
-  if (out_hidden) RUN(omk_layernorm_from_f32(dt, xf, H, out_hidden, H, fg, nullptr, M, H, c->ln_eps, 1, s));
-  if (c->pooling != OM_POOL_NONE) {
-    float* pooled = c->head_in > 0 && w->head_w ? ws.pooled : out_reps;
-    if (c->pooling == OM_POOL_FIRST) {
-      if (packed) RUN(omk_layernorm_f32out(OM_F32, xf, H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s, nullptr, ws.cls_rows));
-      else RUN(omk_layernorm_f32out(OM_F32, xf, L * H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s));
-    } else if (c->pooling == OM_POOL_LAST) {
-      const dim3 grid((unsigned)((B + 255) / 256));
-      if (packed) hipLaunchKernelGGL(last_rows_packed_kernel, grid, dim3(256), 0, s, ws.kmax, ws.cu, B, (int)packed_rows, ws.last_rows);
-      else hipLaunchKernelGGL(last_rows_kernel, grid, dim3(256), 0, s, ws.kmax, B, (int)L, ws.last_rows);
-      OM_LAUNCH_CHECK();
-      RUN(omk_layernorm_f32out(OM_F32, xf, H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s, nullptr, ws.last_rows));
-    } else {
-      RUN(omk_layernorm_f32out(OM_F32, xf, H, ws.final32, H, fg, nullptr, M, H, c->ln_eps, 1, s));
-      RUN(omk_pool(OM_F32, ws.final32, attention_mask, pooled, B, (int)L, H, OM_POOL_MEAN, s, packed ? ws.cu : nullptr));
-    }
-    RUN(omk_pooled_tail(c, w, pooled, out_reps, B, packed ? ws.cu : nullptr, packed_rows, s));
-  }
-#undef GEMM_ACC
-#undef GEMM
-#undef RUN
-  return 0;
+  return prenorm_tail(c, w, ws, attention_mask, B, L, out_hidden, out_reps, packed_rows, s);
 }
 
 extern "C" int om_causal_encoder_forward(const OmCausalConfig* cc, const OmEncoderWeights* w, const int64_t* input_ids,
@@ -348,36 +247,39 @@ static CausalExtra extra_of(const OmCausalConfig2* c2, const OmCausalQkNorm* qk_
 
 extern "C" size_t om_causal2_encoder_workspace_bytes(const OmCausalConfig2* cfg, int64_t B, int64_t L) {
   if (!cfg || B <= 0 || L <= 0 || check_cfg2(cfg)) return 0;
-  return carve(&cfg->base, cfg->base.base.head_dim, B, L, nullptr).total;
+  return prenorm_carve(&cfg->base.base, cfg->base.n_kv_heads, cfg->base.base.head_dim, true, B, L, nullptr).total;
 }
 
 extern "C" int om_causal2_encoder_packed_supported(const OmCausalConfig2* cfg, int64_t B, int64_t L, int64_t packed_rows) {
-  if (!cfg || !packed_rows_rule(B, L, packed_rows)) return 0;
+  if (!cfg || !prenorm_packed_rows_rule(B, L, packed_rows, kQwen3.packed_floor)) return 0;
   return check_cfg2(cfg) ? 0 : 1;
 }
 
 extern "C" size_t om_causal2_encoder_workspace_bytes_packed(const OmCausalConfig2* cfg, int64_t B, int64_t L, int64_t packed_rows) {
   if (!cfg || B <= 0 || L <= 0 || packed_rows <= 0 || check_cfg2(cfg)) return 0;
-  return carve(&cfg->base, cfg->base.base.head_dim, B, L, nullptr, packed_rows).total;
+  return prenorm_carve(&cfg->base.base, cfg->base.n_kv_heads, cfg->base.base.head_dim, true, B, L, nullptr, packed_rows).total;
+}
+
+// the two Qwen3 forward entries: packed_rows == 0 is the padded one
+static int causal2_forward(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host, const int64_t* input_ids,
+                           const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace,
+                           size_t workspace_bytes, void* stream, int64_t packed_rows) {
+  if (!cfg || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
+  if (check_cfg2(cfg)) return 1;
+  if (cfg->qk_norm && cfg->base.base.n_layers > 0 && !qk_norm_host) OM_FAIL("Qwen3: qk_norm is set but the q / k norm weights are null");
+  return causal_forward_impl(&cfg->base, extra_of(cfg, qk_norm_host), w, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace,
+                             workspace_bytes, stream, packed_rows);
 }
 
 extern "C" int om_causal2_encoder_forward(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
                                           const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden,
                                           float* out_reps, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!cfg || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
-  if (check_cfg2(cfg)) return 1;
-  if (cfg->qk_norm && cfg->base.base.n_layers > 0 && !qk_norm_host) OM_FAIL("Qwen3: qk_norm is set but the q / k norm weights are null");
-  return causal_forward_impl(&cfg->base, extra_of(cfg, qk_norm_host), w, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace,
-                             workspace_bytes, stream, 0);
+  return causal2_forward(cfg, w, qk_norm_host, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace, workspace_bytes, stream, 0);
 }
 
 extern "C" int om_causal2_encoder_forward_packed(const OmCausalConfig2* cfg, const OmEncoderWeights* w, const OmCausalQkNorm* qk_norm_host,
                                                  const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L,
                                                  int64_t packed_rows, float* out_reps, void* workspace, size_t workspace_bytes, void* stream) {
   if (packed_rows <= 0) OM_FAIL("packed_rows must be positive");
-  if (!cfg || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
-  if (check_cfg2(cfg)) return 1;
-  if (cfg->qk_norm && cfg->base.base.n_layers > 0 && !qk_norm_host) OM_FAIL("Qwen3: qk_norm is set but the q / k norm weights are null");
-  return causal_forward_impl(&cfg->base, extra_of(cfg, qk_norm_host), w, input_ids, attention_mask, B, L, nullptr, out_reps, workspace,
-                             workspace_bytes, stream, packed_rows);
+  return causal2_forward(cfg, w, qk_norm_host, input_ids, attention_mask, B, L, nullptr, out_reps, workspace, workspace_bytes, stream, packed_rows);
 }

@@ -19,6 +19,10 @@
 // The residual stream x stays in f32 in every compute format, as the reference's autocast keeps it; o_proj and down_proj write the
 // compute format (their outputs are normalised before they are added).
 //
+// What this stack shares with the Llama / Qwen3 one lives in prenorm_stack.h: the workspace and its carving, the argument checks, the
+// launches in front of the layer loop (mask extents, packed rows, embedding) and behind it (final norm, pooling, head), and the
+// packed-rows rule.  Here: check_cfg, the per-layer pointer checks and the layer loop.
+//
 // om_gemma3_encoder_forward_packed is the SAME launch sequence (gemma3_forward_impl below, one layer loop for both entries, as
 // causal_forward_impl of encoder_causal.hip) with M = packed_rows: each sequence's rows up to its last unmasked token, back to back
 // (omk_pack_rows).  The embedding gathers through row_map, the q / k norm + rotation reads its position from it, attention walks cu,
@@ -31,46 +35,9 @@
 
 #include <cmath>
 
-#include "kernels.h"
+#include "prenorm_stack.h"
 
 namespace {
-
-struct Gemma3Ws {
-  char *x, *y, *qkv, *ctx, *ff, *ff2;
-  float *pooled, *headout, *final32;
-  int* kmax;
-  int *cu, *cls_rows, *row_map;   // packed rows: sequence offsets [B + 2], first row of each sequence [B], token of each row [packed_rows]
-  int64_t Mp;       // row count the contractions run on: M rounded up to whole 256-row tiles for large 16-bit batches (as encoder_causal.hip)
-  size_t total;
-};
-
-Gemma3Ws carve(const OmGemma3Config* gc, int64_t B, int64_t L, char* base, int64_t packed_rows = 0) {
-  const OmEncoderConfig* c = &gc->base.base;
-  const bool half = c->dtype == OM_BF16 || c->dtype == OM_F16;
-  const size_t es = half ? 2 : 4;
-  const size_t Mreal = packed_rows > 0 ? (size_t)packed_rows : (size_t)B * L, H = c->hidden, F = c->ffn;
-  const size_t A = (size_t)c->n_heads * 256, P = (size_t)(c->n_heads + 2 * gc->base.n_kv_heads) * 256;
-  const size_t M = (half && Mreal >= 512) ? (Mreal + 255) / 256 * 256 : Mreal;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
-  Gemma3Ws w;
-  w.x = take(M * H * 4);
-  w.y = take(M * H * es);
-  w.qkv = take(M * P * es);
-  w.ctx = take(M * A * es);
-  w.ff = take(M * F * es);
-  w.ff2 = take(M * F * es);
-  w.pooled = (float*)take((size_t)B * H * 4);
-  w.headout = (float*)take((size_t)B * (c->head_out > 0 ? c->head_out : 1) * 4);
-  w.kmax = (int*)take((size_t)B * 4);
-  w.final32 = (float*)take(c->pooling == OM_POOL_MEAN ? Mreal * H * 4 : 0);      // mean pooling reads every row of the f32 final norm
-  w.cu = (int*)take(packed_rows > 0 ? (size_t)(B + 2) * 4 : 0);
-  w.cls_rows = (int*)take(packed_rows > 0 ? (size_t)B * 4 : 0);
-  w.row_map = (int*)take(packed_rows > 0 ? (size_t)packed_rows * 4 : 0);
-  w.Mp = (int64_t)M;
-  w.total = off;
-  return w;
-}
 
 int check_cfg(const OmGemma3Config* gc) {
   const OmCausalConfig* cc = &gc->base;
@@ -100,69 +67,44 @@ int check_cfg(const OmGemma3Config* gc) {
   return 0;
 }
 
-// The causal rule (encoder_causal.hip packed_rows_rule) and one clause more: packed_rows itself must lie above OM_OPT_GEMM_SKINNY_M.  All
-// five contractions here are format-in / format-out, so a 16-bit call of at most that many rows plans the few-rows kernel where the padded
-// call plans a wide tile, and the two entries would part in bits and in speed.
-bool packed_rows_rule(int64_t B, int64_t L, int64_t packed_rows) {
-  if (B <= 0 || L <= 0 || L > 1024 || packed_rows <= 0) return false;
-  if (packed_rows % 256 || packed_rows > B * L + 255) return false;
-  const int64_t skinny = (int64_t)om_option(OM_OPT_GEMM_SKINNY_M);
-  return B * L > skinny && packed_rows > skinny;
-}
+
+const PrenormFamily kGemma3{"Gemma3", 0, false, "Gemma3: layers_host or the per-layer norm weights are null",
+                            "Gemma3 needs word_emb (scaled by sqrt(hidden)) and final_ln_g (1 + norm.weight)"};
 
 }  // namespace
 
 extern "C" size_t om_gemma3_encoder_workspace_bytes(const OmGemma3Config* cfg, int64_t B, int64_t L) {
   if (!cfg || B <= 0 || L <= 0 || check_cfg(cfg)) return 0;
-  return carve(cfg, B, L, nullptr).total;
+  return prenorm_carve(&cfg->base.base, cfg->base.n_kv_heads, 256, false, B, L, nullptr).total;
 }
 
 // Whether om_gemma3_encoder_forward_packed takes (cfg, B, L, packed_rows): every compute format.  No region is excluded on grounds of
-// speed (DESIGN.md section 8 holds what has been measured).
+// speed (DESIGN.md section 8 holds what has been measured).  The causal entries' rule with another lower bound: packed_rows itself must
+// lie above OM_OPT_GEMM_SKINNY_M.  All five contractions here are format-in / format-out, so a 16-bit call of at most that many rows
+// plans the few-rows kernel where the padded call plans a wide tile, and the two entries would part in bits and in speed.
 extern "C" int om_gemma3_encoder_packed_supported(const OmGemma3Config* cfg, int64_t B, int64_t L, int64_t packed_rows) {
-  if (!cfg || !packed_rows_rule(B, L, packed_rows)) return 0;
+  if (!cfg || !prenorm_packed_rows_rule(B, L, packed_rows, (int64_t)om_option(OM_OPT_GEMM_SKINNY_M) + 1)) return 0;
   return check_cfg(cfg) ? 0 : 1;
 }
 
 extern "C" size_t om_gemma3_encoder_workspace_bytes_packed(const OmGemma3Config* cfg, int64_t B, int64_t L, int64_t packed_rows) {
   if (!cfg || B <= 0 || L <= 0 || packed_rows <= 0 || check_cfg(cfg)) return 0;
-  return carve(cfg, B, L, nullptr, packed_rows).total;
+  return prenorm_carve(&cfg->base.base, cfg->base.n_kv_heads, 256, false, B, L, nullptr, packed_rows).total;
 }
 
-// both forward entries (arguments and config are checked by the caller): packed_rows == 0 is the padded layout [B * L rows], > 0 the
-// packed one
+// both forward entries: packed_rows == 0 is the padded layout [B * L rows], > 0 the packed one
 static int gemma3_forward_impl(const OmGemma3Config* gc, const OmEncoderWeights* w, const OmGemma3Norms* norms_host, const int64_t* input_ids,
                                const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace,
                                size_t workspace_bytes, void* stream, int64_t packed_rows) {
+  if (!gc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
+  if (check_cfg(gc)) return 1;
   const OmEncoderConfig* c = &gc->base.base;
   if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("Gemma3: sequence length must be in [1,1024]");
-  const bool packed = packed_rows > 0;
-  if (packed) {
-    if (c->pooling == OM_POOL_NONE || out_hidden) OM_FAIL("Gemma3 packed rows: representations only (a pooling, no out_hidden)");
-    if (packed_rows % 256 || packed_rows > B * L + 255) OM_FAIL("Gemma3 packed_rows: a multiple of 256, at most B * L + 255");
-  }
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  Gemma3Ws ws = carve(gc, B, L, (char*)workspace, packed_rows);
-  if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
-  if (c->pooling != OM_POOL_NONE && !out_reps) OM_FAIL("out_reps required when pooling is set");
-  const OmLayerWeights* Ls = w->layers_host;
-  if (c->n_layers > 0 && (!Ls || !norms_host)) OM_FAIL("Gemma3: layers_host or the per-layer norm weights are null");
-  if (!w->word_emb || !w->final_ln_g) OM_FAIL("Gemma3 needs word_emb (scaled by sqrt(hidden)) and final_ln_g (1 + norm.weight)");
-  hipStream_t s = (hipStream_t)stream;
-  const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nkv = gc->base.n_kv_heads;
-  const int A = nh * 256, P = (nh + 2 * nkv) * 256;
-  const int64_t M = packed ? packed_rows : B * L, Mg = ws.Mp;
-  const int* const row_map = packed ? ws.row_map : nullptr;
-
-#define GEMM(A_, lda_, W_, ldw_, C_, ldc_, N_, K_, res_, ldr_, act_)                                      \
-  do {                                                                                                     \
-    if (om_gemm_nt(dt, A_, lda_, W_, ldw_, dt, C_, ldc_, Mg, N_, K_, nullptr, res_, ldr_, act_, s))       \
-      return 1;                                                                                            \
-  } while (0)
-#define RUN(expr) do { if (expr) return 1; } while (0)
-
+  PrenormWs ws;
+  RUN(prenorm_check(kGemma3, c, gc->base.n_kv_heads, 256, w, w->layers_host && norms_host, B, L, out_hidden, out_reps, workspace, workspace_bytes,
+                    packed_rows, &ws));
   // every layer's pointers are checked before the first launch: a refused call leaves nothing on the stream
+  const OmLayerWeights* Ls = w->layers_host;
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
     const OmGemma3Norms& nw = norms_host[l];
@@ -172,56 +114,38 @@ static int gemma3_forward_impl(const OmGemma3Config* gc, const OmEncoderWeights*
       OM_FAIL("Gemma3 layers need q_norm_g, k_norm_g, post_attention_norm_g and post_feedforward_norm_g");
     if (lw.qkv_b || lw.o_b || lw.ffn1_b || lw.ffn2_b) OM_FAIL("Gemma3: attention_bias must be False (no projection has a bias)");
   }
-  RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-  if (packed) {
-    RUN(omk_pack_rows(ws.kmax, B, (int)L, packed_rows, ws.cu, ws.cls_rows, ws.row_map, s));
-    OM_HIP(hipMemsetAsync(ws.ctx, 0, (size_t)M * A * (dt == OM_F32 ? 4 : 2), s));      // the tail rows: no attention workgroup writes them
-  }
-  RUN(omk_embed(OM_F32, input_ids, nullptr, w->word_emb, nullptr, nullptr, nullptr, nullptr, ws.x, M, (int)L, H, c->vocab, 1, c->ln_eps, 0, s, row_map));
+  hipStream_t s = (hipStream_t)stream;
+  const bool packed = packed_rows > 0;
+  const int dt = c->dtype, H = c->hidden, F = c->ffn, nh = c->n_heads, nkv = gc->base.n_kv_heads, A = ws.A, P = ws.P;
+  const int64_t M = ws.M;
+  const int* const row_map = packed ? ws.row_map : nullptr;
+  const PrenormGemm gemm{dt, ws.Mp, s};
+
+  RUN(prenorm_begin(c, w, ws, input_ids, attention_mask, B, L, packed_rows, s));
   for (int l = 0; l < c->n_layers; ++l) {
     const OmLayerWeights& lw = Ls[l];
     const OmGemma3Norms& nw = norms_host[l];
     const bool sliding = (gc->sliding_layers >> l) & 1;
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));   // input_layernorm
-    GEMM(ws.y, H, lw.qkv_w, H, ws.qkv, P, P, H, nullptr, 0, OM_ACT_NONE);
+    RUN(gemm(ws.y, H, lw.qkv_w, H, dt, ws.qkv, P, P, H));
     RUN(omk_qknorm_rope(dt, ws.qkv, M, (int)L, nh, nkv, 256, nw.q_norm_g, nw.k_norm_g, c->ln_eps, sliding ? gc->sliding_inv_freq : gc->full_inv_freq,
                         sliding ? gc->sliding_scaling : gc->full_scaling, s, row_map, 1));
     if (packed) RUN(omk_attention_gqa_d256_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, gc->attn_scale, sliding ? gc->half_window : 0, ws.cu, s));
     else RUN(omk_attention_gqa_d256(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, gc->attn_scale, sliding ? gc->half_window : 0, ws.kmax, s));
-    GEMM(ws.ctx, A, lw.o_w, A, ws.y, H, H, A, nullptr, 0, OM_ACT_NONE);                                    // h = o_proj(ctx)
+    RUN(gemm(ws.ctx, A, lw.o_w, A, dt, ws.y, H, H, A));                                                    // h = o_proj(ctx)
     RUN(omk_rmsnorm_add(dt, ws.y, H, (float*)ws.x, H, nw.post_attention_norm_g, M, H, c->ln_eps, s));       // x += post_attention_layernorm(h)
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // pre_feedforward_layernorm
-    GEMM(ws.y, H, lw.ffn1g_w, H, ws.ff2, F, F, H, nullptr, 0, OM_ACT_NONE);                                // up_proj
-    GEMM(ws.y, H, lw.ffn1_w, H, ws.ff, F, F, H, ws.ff2, F, OM_ACT_GELU_TANH | OM_ACT_MUL_RESID);           // ff = gelu_tanh(gate_proj) * up
-    GEMM(ws.ff, F, lw.ffn2_w, F, ws.y, H, H, F, nullptr, 0, OM_ACT_NONE);                                  // h = down_proj(ff)
+    RUN(gemm(ws.y, H, lw.ffn1g_w, H, dt, ws.ff2, F, F, H));                                                // up_proj
+    RUN(gemm(ws.y, H, lw.ffn1_w, H, dt, ws.ff, F, F, H, nullptr, ws.ff2, F, OM_ACT_GELU_TANH | OM_ACT_MUL_RESID));   // ff = gelu_tanh(gate_proj) * up
+    RUN(gemm(ws.ff, F, lw.ffn2_w, F, dt, ws.y, H, H, F));                                                  // h = down_proj(ff)
     RUN(omk_rmsnorm_add(dt, ws.y, H, (float*)ws.x, H, nw.post_feedforward_norm_g, M, H, c->ln_eps, s));     // x += post_feedforward_layernorm(h)
   }
-  // norm: the hidden states in the compute dtype when asked for; the pooled rows ALWAYS as f32 rows of the normalisation of just the
-  // rows pooling reads, as the other stacks do
-  const float* fg = w->final_ln_g;
-  const float* xf = (const float*)ws.x;
-  if (out_hidden) RUN(omk_layernorm_from_f32(dt, xf, H, out_hidden, H, fg, nullptr, M, H, c->ln_eps, 1, s));
-  if (c->pooling != OM_POOL_NONE) {
-    float* pooled = c->head_in > 0 && w->head_w ? ws.pooled : out_reps;
-    if (c->pooling == OM_POOL_FIRST) {
-      if (packed) RUN(omk_layernorm_f32out(OM_F32, xf, H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s, nullptr, ws.cls_rows));
-      else RUN(omk_layernorm_f32out(OM_F32, xf, L * H, pooled, H, fg, nullptr, B, H, c->ln_eps, 1, s));
-    } else {
-      RUN(omk_layernorm_f32out(OM_F32, xf, H, ws.final32, H, fg, nullptr, M, H, c->ln_eps, 1, s));
-      RUN(omk_pool(OM_F32, ws.final32, attention_mask, pooled, B, (int)L, H, OM_POOL_MEAN, s, packed ? ws.cu : nullptr));
-    }
-    RUN(omk_pooled_tail(c, w, pooled, out_reps, B, packed ? ws.cu : nullptr, packed_rows, s));      // a bound below the token count poisons the representations
-  }
-#undef GEMM
-#undef RUN
-  return 0;
+  return prenorm_tail(c, w, ws, attention_mask, B, L, out_hidden, out_reps, packed_rows, s);
 }
 
 extern "C" int om_gemma3_encoder_forward(const OmGemma3Config* gc, const OmEncoderWeights* w, const OmGemma3Norms* norms_host, const int64_t* input_ids,
                                          const int64_t* attention_mask, int64_t B, int64_t L, void* out_hidden, float* out_reps, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  if (!gc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
-  if (check_cfg(gc)) return 1;
   return gemma3_forward_impl(gc, w, norms_host, input_ids, attention_mask, B, L, out_hidden, out_reps, workspace, workspace_bytes, stream, 0);
 }
 
@@ -229,7 +153,5 @@ extern "C" int om_gemma3_encoder_forward_packed(const OmGemma3Config* gc, const 
                                                 const int64_t* input_ids, const int64_t* attention_mask, int64_t B, int64_t L, int64_t packed_rows,
                                                 float* out_reps, void* workspace, size_t workspace_bytes, void* stream) {
   if (packed_rows <= 0) OM_FAIL("packed_rows must be positive");
-  if (!gc || !w || !input_ids || !attention_mask) OM_FAIL("null argument");
-  if (check_cfg(gc)) return 1;
   return gemma3_forward_impl(gc, w, norms_host, input_ids, attention_mask, B, L, nullptr, out_reps, workspace, workspace_bytes, stream, packed_rows);
 }

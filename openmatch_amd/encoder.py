@@ -616,55 +616,6 @@ def _pack_gemma3(model, code, device):
     return pk
 
 
-def gemma3_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
-    """Whether om_gemma3_encoder_forward_packed takes this call (cfg: an OmGemma3Config) and pays: representations only, whole 256-row
-    tiles above the few-rows threshold with at least one tile saved -- a left-padded batch's bound is B * L, so it stays on the padded
-    entry -- and the library's own view (include/openmatch_hip.h om_gemma3_encoder_packed_supported).  OM_ENCODER_PACKED=0 keeps every
-    batch on the padded entry."""
-    if os.environ.get("OM_ENCODER_PACKED", "1") == "0":
-        return False
-    if want_hidden or pooling is None:
-        return False
-    skinny = N.lib().om_debug_option_value(N.OPT_GEMM_SKINNY_M)
-    if not (rows % 256 == 0 and skinny < rows <= (B * L) // 256 * 256 - 256):
-        return False
-    return bool(N.lib().om_gemma3_encoder_packed_supported(C.byref(cfg), B, L, rows))
-
-
-def _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
-    """hip_encode for a packed Gemma3TextModel: om_gemma3_encoder_forward_packed over `packed_rows` rows where gemma3_packed_rows_apply
-    admits the call, om_gemma3_encoder_forward over the B * L padded rows otherwise."""
-    device = ids.device
-    cfg = gemma3_config(pk.cfg, _POOL[pooling], normalize)
-    B, L = ids.shape
-    base = cfg.base.base
-    H = base.hidden
-    D = base.head_out if base.head_in > 0 else H
-    lib = N.lib()
-    norms = C.cast(pk.norms, C.POINTER(N.OmGemma3Norms)) if len(pk.norms) else None
-    if packed_rows and not gemma3_packed_rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
-        packed_rows = None
-    LAST_CALL.update(rows=int(packed_rows) if packed_rows else B * L, packed=bool(packed_rows))
-    with torch.cuda.device(device):
-        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
-        if packed_rows:
-            nbytes = lib.om_gemma3_encoder_workspace_bytes_packed(C.byref(cfg), B, L, int(packed_rows))
-            if not nbytes:
-                raise N.NativeError(lib.om_last_error().decode("utf-8", "replace"))
-            ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
-            N.check(lib.om_gemma3_encoder_forward_packed(C.byref(cfg), C.byref(pk.weights), norms, N.ptr(ids), N.ptr(mask), B, L, int(packed_rows),
-                                                         N.ptr(reps), C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
-            return None, reps
-        nbytes = lib.om_gemma3_encoder_workspace_bytes(C.byref(cfg), B, L)
-        if not nbytes:
-            raise N.NativeError(lib.om_last_error().decode("utf-8", "replace"))
-        ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
-        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
-        N.check(lib.om_gemma3_encoder_forward(C.byref(cfg), C.byref(pk.weights), norms, N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
-                                              C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
-    return hidden, reps
-
-
 def _pack_causal(model, code, device):
     """LlamaModel / Qwen2Model / Qwen3Model: the embedding table and the RMSNorm weights in f32, the matrices in the compute dtype;
     q / k / v fused to rows q | k | v of [(heads + 2 kv) * head_dim, H] (a missing bias of a projection that has siblings with one
@@ -976,10 +927,8 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     device = ids.device
     code = inference_code(model, code, ids.shape[1])
     pk = packed_weights(model, head, code, device)
-    if _arch_of(model) == "causal":
-        return _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
-    if _arch_of(model) == "gemma3":
-        return _hip_encode_gemma3(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
+    if _arch_of(model) in ("causal", "gemma3"):
+        return _hip_encode_prenorm(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
     _ensure_folded(pk, device)
     cfg = N.OmEncoderConfig(pooling=_POOL[pooling], normalize=int(bool(normalize)), **pk.cfg)
     B, L = ids.shape
@@ -1012,75 +961,73 @@ def hip_encode(model, items, pooling, head, normalize, code, want_hidden=True, p
     return hidden, reps
 
 
-def causal_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
-    """Whether om_causal_encoder_forward_packed takes this call (cfg: an OmCausalConfig; an OmCausalConfig2: the om_causal2_* entry) and pays: representations only, at least one
-    256-row tile saved -- a left-padded batch's bound is B * L, so it stays on the padded entry -- and the library's own view
-    (include/openmatch_hip.h om_causal_encoder_packed_supported).  OM_ENCODER_PACKED=0 keeps every batch on the padded entry."""
+def _prenorm_packed_rows_apply(supported, least, cfg, B, L, rows, want_hidden, pooling):
+    """The one rule of the pre-norm stacks' packed entries: representations only, whole 256-row tiles from `least` rows with at least one
+    tile saved -- a left-padded batch's bound is B * L, so it stays on the padded entry -- and the library's own view (`supported`: the
+    family's om_*_encoder_packed_supported of include/openmatch_hip.h).  OM_ENCODER_PACKED=0 keeps every batch on the padded entry."""
     if os.environ.get("OM_ENCODER_PACKED", "1") == "0" or want_hidden or pooling is None:
         return False
-    if not (rows % 256 == 0 and 512 <= rows <= (B * L) // 256 * 256 - 256):
+    if not (rows % 256 == 0 and least <= rows <= (B * L) // 256 * 256 - 256):
         return False
-    if isinstance(cfg, N.OmCausalConfig2):
-        return bool(N.lib().om_causal2_encoder_packed_supported(C.byref(cfg), B, L, rows))
-    return bool(N.lib().om_causal_encoder_packed_supported(C.byref(cfg), B, L, rows))
+    return bool(getattr(N.lib(), supported)(C.byref(cfg), B, L, rows))
 
 
-def _hip_encode_causal(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
-    """hip_encode for a packed Llama / Qwen2: om_causal_encoder_forward_packed over `packed_rows` rows where causal_packed_rows_apply
-    admits the call, om_causal_encoder_forward over the B * L padded rows otherwise."""
+def causal_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
+    """Whether om_causal_encoder_forward_packed (cfg: an OmCausalConfig; an OmCausalConfig2: the om_causal2_* entry) takes this call and
+    pays: from 512 rows."""
+    v2 = "2" if isinstance(cfg, N.OmCausalConfig2) else ""
+    return _prenorm_packed_rows_apply(f"om_causal{v2}_encoder_packed_supported", 512, cfg, B, L, rows, want_hidden, pooling)
+
+
+def gemma3_packed_rows_apply(cfg, B, L, rows, want_hidden, pooling):
+    """Whether om_gemma3_encoder_forward_packed (cfg: an OmGemma3Config) takes this call and pays: above the few-rows threshold."""
+    least = N.lib().om_debug_option_value(N.OPT_GEMM_SKINNY_M) + 1
+    return _prenorm_packed_rows_apply("om_gemma3_encoder_packed_supported", least, cfg, B, L, rows, want_hidden, pooling)
+
+
+# The f32-residual pre-norm families (csrc/prenorm_stack.h): the config builder, the prefix of the four entries (om_<prefix>_encoder_
+# workspace_bytes[_packed] / _forward[_packed]), the packed-rows rule, and the per-layer array its forward takes after the weights (the
+# packer's attribute and the array's element type)
+_PRENORM = {
+    "causal": (causal_config, "om_causal", causal_packed_rows_apply, None),
+    "causal2": (causal2_config, "om_causal2", causal_packed_rows_apply, ("qk_norm", N.OmCausalQkNorm)),
+    "gemma3": (gemma3_config, "om_gemma3", gemma3_packed_rows_apply, ("norms", N.OmGemma3Norms)),
+}
+
+
+def _hip_encode_prenorm(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
+    """hip_encode for a packed Llama / Qwen2, Qwen3 (its cfg carries qk_norm) or Gemma3TextModel (sliding_layers): the family's
+    _forward_packed entry over `packed_rows` rows where its rule admits the call, its _forward entry over the B * L padded rows otherwise."""
+    family = "gemma3" if "sliding_layers" in pk.cfg else "causal2" if "qk_norm" in pk.cfg else "causal"
+    make_config, prefix, rows_apply, per_layer = _PRENORM[family]
     device = ids.device
-    if "qk_norm" in pk.cfg:
-        return _hip_encode_causal2(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows)
-    cfg = causal_config(pk.cfg, _POOL[pooling], normalize)
+    cfg = make_config(pk.cfg, _POOL[pooling], normalize)
     B, L = ids.shape
-    H = cfg.base.hidden
-    D = cfg.base.head_out if cfg.base.head_in > 0 else H
-    lib = N.lib()
-    if packed_rows and not causal_packed_rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
-        packed_rows = None
-    LAST_CALL.update(rows=int(packed_rows) if packed_rows else B * L, packed=bool(packed_rows))
-    with torch.cuda.device(device):
-        reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
-        if packed_rows:
-            nbytes = lib.om_causal_encoder_workspace_bytes_packed(C.byref(cfg), B, L, int(packed_rows))
-            ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
-            N.check(lib.om_causal_encoder_forward_packed(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask), B, L, int(packed_rows),
-                                                         N.ptr(reps), C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
-            return None, reps
-        nbytes = lib.om_causal_encoder_workspace_bytes(C.byref(cfg), B, L)
-        ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
-        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
-        N.check(lib.om_causal_encoder_forward(C.byref(cfg), C.byref(pk.weights), N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
-                                              C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
-    return hidden, reps
-
-
-def _hip_encode_causal2(pk, ids, mask, pooling, normalize, code, want_hidden, packed_rows=None):
-    """_hip_encode_causal for a packed Qwen3: the om_causal2_* entries, padded and packed, under the same causal_packed_rows_apply rule."""
-    device = ids.device
-    cfg = causal2_config(pk.cfg, _POOL[pooling], normalize)
-    B, L = ids.shape
-    base = cfg.base.base
+    base = cfg.base
+    while not isinstance(base, N.OmEncoderConfig):
+        base = base.base
     H = base.hidden
     D = base.head_out if base.head_in > 0 else H
     lib = N.lib()
-    qkn = C.cast(pk.qk_norm, C.POINTER(N.OmCausalQkNorm)) if pk.qk_norm is not None and len(pk.qk_norm) else None
-    if packed_rows and not causal_packed_rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
+    extra = ()
+    if per_layer is not None:
+        array, struct = getattr(pk, per_layer[0]), per_layer[1]
+        extra = (C.cast(array, C.POINTER(struct)) if array is not None and len(array) else None,)
+    if packed_rows and not rows_apply(cfg, B, L, int(packed_rows), want_hidden, pooling):
         packed_rows = None
     LAST_CALL.update(rows=int(packed_rows) if packed_rows else B * L, packed=bool(packed_rows))
+    rows = (int(packed_rows),) if packed_rows else ()
+    suffix = "_packed" if packed_rows else ""
     with torch.cuda.device(device):
         reps = torch.empty(B, D, device=device, dtype=torch.float32) if pooling is not None else None
-        if packed_rows:
-            nbytes = lib.om_causal2_encoder_workspace_bytes_packed(C.byref(cfg), B, L, int(packed_rows))
-            ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
-            N.check(lib.om_causal2_encoder_forward_packed(C.byref(cfg), C.byref(pk.weights), qkn, N.ptr(ids), N.ptr(mask), B, L, int(packed_rows),
-                                                          N.ptr(reps), C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
-            return None, reps
-        nbytes = lib.om_causal2_encoder_workspace_bytes(C.byref(cfg), B, L)
+        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None      # (never with packed rows: the rule)
+        nbytes = getattr(lib, f"{prefix}_encoder_workspace_bytes{suffix}")(C.byref(cfg), B, L, *rows)
+        if not nbytes:
+            raise N.NativeError(lib.om_last_error().decode("utf-8", "replace"))
         ws_buf, ws_ptr = N.Workspace.get(device, nbytes, "encoder")
-        hidden = torch.empty(B, L, H, device=device, dtype=torch_dtype_of(code)) if want_hidden else None
-        N.check(lib.om_causal2_encoder_forward(C.byref(cfg), C.byref(pk.weights), qkn, N.ptr(ids), N.ptr(mask), B, L, N.ptr(hidden), N.ptr(reps),
-                                               C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
+        out = (N.ptr(reps),) if packed_rows else (N.ptr(hidden), N.ptr(reps))
+        N.check(getattr(lib, f"{prefix}_encoder_forward{suffix}")(C.byref(cfg), C.byref(pk.weights), *extra, N.ptr(ids), N.ptr(mask), B, L, *rows, *out,
+                                                                  C.c_void_p(ws_ptr), nbytes, N.stream_ptr(device)))
     return hidden, reps
 
 

@@ -97,6 +97,38 @@ def test_workspace_bytes_of_packed_rows():
     assert lib.om_causal_encoder_workspace_bytes_packed(C.byref(cc), 16, 128, 0) == 0
 
 
+# (dtype, pooling, B, L, packed_rows or 0, bytes) for _causal_cfg's shape: what the library built from the commit BEFORE csrc/prenorm_stack.h
+# answered -- under 512 rows, 600 and 800 rows (16-bit: whole 256-row tiles), and packed
+WORKSPACE_BYTES = ((N.OM_BF16, N.POOL_LAST, 3, 40, 0, 556800), (N.OM_F16, N.POOL_FIRST, 5, 120, 0, 3544832), (N.OM_F32, N.POOL_MEAN, 5, 120, 0, 5535488),
+                   (N.OM_BF16, N.POOL_MEAN, 4, 200, 0, 5542656), (N.OM_F16, N.POOL_LAST, 16, 128, 1024, 4740352),
+                   (N.OM_BF16, N.POOL_MEAN, 4, 1024, 1280, 7219456), (N.OM_F32, N.POOL_FIRST, 16, 128, 1536, 12606720))
+
+
+def test_workspace_bytes_are_what_they_were():
+    lib = N.lib()
+    for dtype, pooling, B, L, rows, want in WORKSPACE_BYTES:
+        cc = _causal_cfg(dtype=dtype, pooling=pooling)
+        got = lib.om_causal_encoder_workspace_bytes_packed(C.byref(cc), B, L, rows) if rows else lib.om_causal_encoder_workspace_bytes(C.byref(cc), B, L)
+        assert got == want, (dtype, pooling, B, L, rows)
+
+
+def test_a_null_layer_pointer_is_refused_before_the_first_launch():
+    """o_w of layer 1 of 3 is null: the refusal comes back on a machine without a GPU, so nothing was launched for layer 0 (fake
+    non-null pointers, no stream: the call shape of tests/test_gemma3_host.py::test_every_refusal_comes_back_through_the_c_entry)"""
+    lib = N.lib()
+    layers = (N.OmLayerWeights * 3)()
+    for i in range(3):
+        for name in ("qkv_w", "o_w", "ln1_g", "ln2_g", "ffn1_w", "ffn1g_w", "ffn2_w"):
+            setattr(layers[i], name, 256)
+    layers[1].o_w = None
+    w = N.OmEncoderWeights(word_emb=256, final_ln_g=256, layers_host=C.cast(layers, C.POINTER(N.OmLayerWeights)))
+    cc = _causal_cfg(layers=3)
+    assert lib.om_causal_encoder_forward(C.byref(cc), C.byref(w), 16, 16, 1, 8, None, 16, 256, 1 << 40, None) != 0
+    assert b"Llama / Qwen2 layers need qkv_w, o_w" in lib.om_last_error()
+    assert lib.om_causal_encoder_forward_packed(C.byref(cc), C.byref(w), 16, 16, 16, 128, 1024, 16, 256, 1 << 40, None) != 0
+    assert b"Llama / Qwen2 layers need qkv_w, o_w" in lib.om_last_error()
+
+
 def test_forward_refuses_on_the_host():
     """the call shape of test_abi_is_unchanged_and_the_causal_struct_embeds_the_config: nothing is launched"""
     lib = N.lib()

@@ -140,6 +140,21 @@ def test_workspace_bytes_of_packed_rows():
     assert floor <= got <= floor + 16 * 256 + 2 * 4 * 768 * 4
 
 
+# (dtype, pooling, B, L, packed_rows or 0, bytes) for _c_config's shape: what the library built from the commit BEFORE csrc/prenorm_stack.h
+# answered -- under 512 rows, 600 and 800 rows (16-bit: whole 256-row tiles), and packed
+WORKSPACE_BYTES = ((N.OM_BF16, N.POOL_FIRST, 3, 40, 0, 1607168), (N.OM_F16, N.POOL_FIRST, 5, 120, 0, 10239488), (N.OM_F32, N.POOL_MEAN, 5, 120, 0, 15990272),
+                   (N.OM_BF16, N.POOL_MEAN, 4, 200, 0, 16101888), (N.OM_F16, N.POOL_FIRST, 16, 128, 1024, 13685760),
+                   (N.OM_BF16, N.POOL_MEAN, 4, 1024, 1280, 20989952), (N.OM_F32, N.POOL_FIRST, 16, 128, 1536, 36232192))
+
+
+def test_workspace_bytes_are_what_they_were():
+    lib = N.lib()
+    for dtype, pooling, B, L, rows, want in WORKSPACE_BYTES:
+        gc = _c_config(dtype=dtype, pooling=pooling)
+        got = lib.om_gemma3_encoder_workspace_bytes_packed(C.byref(gc), B, L, rows) if rows else lib.om_gemma3_encoder_workspace_bytes(C.byref(gc), B, L)
+        assert got == want, (dtype, pooling, B, L, rows)
+
+
 @pytest.mark.parametrize("key", list(BATCHES))
 def test_reference_batches_save_a_tile_and_plan_as_their_assertions_need(key):
     shape, n, L, lo, seed, kind = BATCHES[key]

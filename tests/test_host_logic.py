@@ -592,3 +592,8 @@ def test_host_side_token_counts_split_and_merge():
     chunks = split_dense_inputs({"passage": {"input_ids": m.clone(), "attention_mask": m, TOKEN_ROWS_KEY: ext, "note": 3}}, 4)
     assert [c["passage"][TOKEN_ROWS_KEY].tolist() for c in chunks] == [[128, 5, 127, 128], [64, 101]]
     assert all("note" not in c["passage"] and c["passage"]["attention_mask"].shape[0] == len(c["passage"][TOKEN_ROWS_KEY]) for c in chunks)
+
+
+def test_every_header_is_a_build_dependency():
+    from openmatch_amd import _build
+    assert {f for f in os.listdir(_build.CSRC) if f.endswith(".h")} <= set(_build.HEADERS)

@@ -150,3 +150,39 @@ def test_abi_is_unchanged_and_the_new_struct_embeds_the_causal_config():
     old = N.OmCausalConfig(base=cc.base.base, n_kv_heads=2, rope_attention_scaling=1.0, inv_freq=(C.c_float * 32)(*([0.5] * 32)))
     assert lib.om_causal_encoder_forward(C.byref(old), C.byref(w), 16, 16, 1, 8, None, 16, 256, 1 << 30, None) != 0
     assert b"head_dim 64" in lib.om_last_error()
+
+
+# (dtype, pooling, B, L, packed_rows or 0, bytes) for _cfg2's shape: what the library built from the commit BEFORE csrc/prenorm_stack.h
+# answered -- under 512 rows, 600 and 800 rows (16-bit: whole 256-row tiles), and packed
+WORKSPACE_BYTES = ((N.OM_BF16, N.POOL_LAST, 3, 40, 0, 741120), (N.OM_F16, N.POOL_FIRST, 5, 120, 0, 4724480), (N.OM_F32, N.POOL_MEAN, 5, 120, 0, 7378688),
+                   (N.OM_BF16, N.POOL_MEAN, 4, 200, 0, 7115520), (N.OM_F16, N.POOL_LAST, 16, 128, 1024, 6313216),
+                   (N.OM_BF16, N.POOL_MEAN, 4, 1024, 1280, 9185536), (N.OM_F32, N.POOL_FIRST, 16, 128, 1536, 17325312))
+
+
+def test_workspace_bytes_are_what_they_were():
+    lib = N.lib()
+    for dtype, pooling, B, L, rows, want in WORKSPACE_BYTES:
+        cc = _cfg2(dtype=dtype, pooling=pooling)
+        got = lib.om_causal2_encoder_workspace_bytes_packed(C.byref(cc), B, L, rows) if rows else lib.om_causal2_encoder_workspace_bytes(C.byref(cc), B, L)
+        assert got == want, (dtype, pooling, B, L, rows)
+
+
+def test_a_null_qk_norm_weight_is_refused_before_the_first_launch():
+    """k_norm_g of layer 2 of 3 is null: the refusal comes back on a machine without a GPU, so nothing was launched for layers 0 and 1
+    (fake non-null pointers, no stream: the call shape of tests/test_gemma3_host.py::test_every_refusal_comes_back_through_the_c_entry)"""
+    lib = N.lib()
+    layers = (N.OmLayerWeights * 3)()
+    qkn = (N.OmCausalQkNorm * 3)()
+    for i in range(3):
+        for name in ("qkv_w", "o_w", "ln1_g", "ln2_g", "ffn1_w", "ffn1g_w", "ffn2_w"):
+            setattr(layers[i], name, 256)
+        qkn[i].q_norm_g = qkn[i].k_norm_g = 256
+    qkn[2].k_norm_g = None
+    w = N.OmEncoderWeights(word_emb=256, final_ln_g=256, layers_host=C.cast(layers, C.POINTER(N.OmLayerWeights)))
+    cc = _cfg2()
+    cc.base.base.n_layers = 3
+    assert lib.om_causal2_encoder_forward(C.byref(cc), C.byref(w), qkn, 16, 16, 1, 8, None, 16, 256, 1 << 40, None) != 0
+    assert b"Qwen3 layers with qk_norm need q_norm_g and k_norm_g" in lib.om_last_error()
+    layers[0].ffn2_w = None                # the pointers of every layer, likewise
+    assert lib.om_causal2_encoder_forward(C.byref(cc), C.byref(w), qkn, 16, 16, 1, 8, None, 16, 256, 1 << 40, None) != 0
+    assert b"Qwen3 layers need qkv_w, o_w" in lib.om_last_error()
