@@ -1198,6 +1198,17 @@ int om_debug_scan_round(int half, int64_t nq, int d, int64_t rows, int cus, int6
  * first 8192 as (orderable score) << 32 | ~id), on `grid` persistent workgroups.  Refuses a shape the plan sends elsewhere. */
 int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t row_base, const void* queries16, int64_t nq, int d, const float* thr,
                         uint64_t* keys, unsigned* cnt, int grid, void* stream);
+/* One launch of a tile kernel of the scan's kernel table, as a filtered round of om_sim_topk launches it: kernel = OM_SCAN_KERNEL_TILE2,
+ * TILE6, WIDE7 or WIDE7C, half = 0 the float32 plane, 1 the float16 plane (rows and queries in that format), rows [nrows, d] with ids
+ * from row_base, grid and group as om_debug_scan_round returns them (generation 7: group = group_m | qgroup << 8).  Survivors
+ * (score >= thr[q]) are APPENDED: cnt[q] counts every one, keys[q] holds those whose position is below 8192.
+ * Refused, with nothing launched: a null argument; a kernel the table does not hold (generation 7 on the float32 plane, 0, STREAM);
+ * d <= 0 or d % 64 != 0; nrows < 1 or nq < 1; grid outside [1, 2^31 - 1]; group_m = 0; WIDE7 / WIDE7C with nrows % 256 != 0 (whole row
+ * tiles only); WIDE7C with d < 192; TILE2 / TILE6 with a grid other than one workgroup per (256-row tile, 128- / 256-query tile).
+ * NOT checked, the caller's to keep: for TILE6, WIDE7 and WIDE7C queries holds round_up(nq, 256) rows, zero beyond nq; thr is readable
+ * for round_up(nq, 256) + 256 entries and +inf beyond nq; keys is [nq][8192]; cnt is [nq] and is not cleared. */
+int om_debug_scan_kernel(int kernel, int half, const void* rows, int64_t nrows, uint32_t row_base, const void* queries, int64_t nq, int d,
+                         const float* thr, uint64_t* keys, unsigned* cnt, int64_t grid, int group, void* stream);
 
 /* Merge W partial results (utils.py:215-229 merge_retrieval_results_by_score /
  * faiss shard merge): parts are [W][Q,k_in] row-major, each row descending;

@@ -2449,6 +2449,41 @@ extern "C" int om_debug_sim_stream(const void* rows16, int64_t nrows, uint32_t r
   return 0;
 }
 
+// One launch of a tile kernel of g_tile_kernels over a caller's buffers, through scan_kernel / scan_attrs / scan_launch as
+// Scan::filter_step launches a planned round: `grid` and `group` are what scan_round would hand over (generation 7: group_m | qgroup << 8).
+// What is refused: below.  What CANNOT be checked here and is the caller's to keep, from the kernels' own comments:
+//   * generations 6 and 7 read whole 256-query tiles: `queries` holds round_up(nq, 256) rows, zero beyond nq (query_prep_kernel);
+//   * generation 7 fetches 256 thresholds from the middle of a query tile on: `thr` is readable for round_up(nq, 256) + 256 entries and
+//     +inf beyond nq (init_lists_kernel) -- a finite value there appends keys of the zero rows to lists that do not exist;
+//   * keys is [nq][SORT_CAP], cnt is [nq] and is NOT cleared: survivors are appended behind the cnt[q] keys a list already holds, cnt
+//     counts every survivor and keys holds those whose position is below SORT_CAP.
+extern "C" int om_debug_scan_kernel(int kernel, int half, const void* rows, int64_t nrows, uint32_t row_base, const void* queries, int64_t nq,
+                                    int d, const float* thr, uint64_t* keys, unsigned* cnt, int64_t grid, int group, void* stream) {
+  if (!rows || !queries || !thr || !keys || !cnt) OM_FAIL("null argument");
+  if (kernel < OM_SCAN_KERNEL_TILE2 || kernel > OM_SCAN_KERNEL_WIDE7C)
+    OM_FAIL("kernel must be OM_SCAN_KERNEL_TILE2, TILE6, WIDE7 or WIDE7C (the stream kernel: om_debug_sim_stream)");
+  const ScanSwitches sw = scan_switches();
+  const ScanKernel& kn = scan_kernel(kernel, half != 0, ScanPlan{OM_SCAN_FAMILY_GENERIC, 0, 0, 0}, sw);
+  if (!kn.fn) OM_FAIL("no such scan kernel: generation 7 scans the 16-bit index only");
+  if (d <= 0 || d % SCAN_KSTEP != 0) OM_FAIL("d must be a positive multiple of 64");
+  if (nrows < 1 || nq < 1) OM_FAIL("nrows >= 1 and nq >= 1");
+  if (grid < 1 || grid > 0x7fffffffLL) OM_FAIL("grid must be in [1, 2^31 - 1]");
+  if ((group & 255) < 1) OM_FAIL("group_m (the low byte of group) must be at least 1");
+  if (kernel >= OM_SCAN_KERNEL_WIDE7) {
+    if (nrows % 256 != 0) OM_FAIL("generation 7 takes whole 256-row tiles only");
+    if (kernel == OM_SCAN_KERNEL_WIDE7C && !g7_ring_ok(d)) OM_FAIL("the continuous ring needs three 128-byte K steps: d >= 192");
+  } else {
+    // a tile-at-a-time workgroup takes its tile from its block index and tests no bound: one workgroup per (row tile, query tile)
+    const int64_t qt = kernel == OM_SCAN_KERNEL_TILE2 ? (nq + 127) / 128 : (nq + 255) / 256;
+    if ((nrows + 255) / 256 > 0x7fffffffLL / qt || grid != (nrows + 255) / 256 * qt)
+      OM_FAIL("generations 2 and 6 take one workgroup per (256-row tile, query tile): grid must be their number");
+  }
+  if (scan_attrs()) return 1;
+  if (scan_launch(kn, rows, nrows, row_base, queries, nq, d, thr, (u64*)keys, cnt, grid, group, (hipStream_t)stream)) return 1;
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- om_debug_rescore_rows: the row-typed kernels (re-score, strided re-score, the redo's collect pass) over a caller's candidates ----
 // cand -> lists: list q = rows cand[q][0 .. m) in order, scores 0.  A row number beyond the index is not followed (its score comes back NaN).
 __global__ void debug_fill_lists_kernel(const uint32_t* __restrict__ cand, int m, int64_t N, u64* __restrict__ keys, unsigned* __restrict__ cnt) {

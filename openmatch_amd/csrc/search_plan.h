@@ -3,8 +3,8 @@
 // rows, grid and `group` argument of a main launch and of a ragged tail.  Neither does anything else -- no launch, no HIP call, no global
 // read or written, no pointer dereferenced.  Scan::filter_step (search.hip) asks for the round and launches it from the kernel table;
 // om_debug_scan_plan / om_debug_scan_round return the plan / the round alone, so the rules are testable on a machine without a GPU, and
-// om_debug_sim_stream launches the stream instantiation a plan names over a caller's buffers.  DESIGN.md 4f lists the rules in the order
-// they are tested here.
+// om_debug_sim_stream launches the stream instantiation a plan names over a caller's buffers, om_debug_scan_kernel one tile kernel with
+// the grid and group of a ScanLaunch.  DESIGN.md 4f lists the rules in the order they are tested here.
 #pragma once
 #include <algorithm>
 

@@ -378,6 +378,8 @@ _SIGNATURES = {
     "om_debug_scan_plan": (c_int, [c_int, c_int64, c_int, C.POINTER(c_int)]),
     "om_debug_scan_round": (c_int, [c_int, c_int64, c_int, c_int64, c_int, C.POINTER(c_int64)]),
     "om_debug_sim_stream": (c_int, [c_void_p, c_int64, C.c_uint32, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "om_debug_scan_kernel": (c_int, [c_int, c_int, c_void_p, c_int64, C.c_uint32, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_int, c_void_p]),
     "om_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p,
                               c_void_p]),
     "om_contrastive_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
