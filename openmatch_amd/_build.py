@@ -16,7 +16,7 @@ OBJ_DIR = os.path.join(REPO, "build", "obj")
 LIB_PATH = os.path.join(CSRC, "libopenmatch_hip.so")
 ARCH = "gfx950"
 SOURCES = ["abi.cpp", "comm.cpp", "gemm.hip", "gemm_wide6_bf16.hip", "gemm_wide6_f32.hip", "gemm_wide7.hip", "gemm_wide7_ln.hip", "gemm_wide7_f16.hip", "gemm_tn.hip", "elementwise.hip", "attention.hip", "attention_d32.hip", "attention_band.hip", "attention_causal.hip", "attention_causal128.hip", "attention_d256.hip", "attention_bwd16.hip", "encoder.hip", "encoder_causal.hip", "encoder_gemma3.hip", "decoder.hip",
-           "search.hip", "contrastive.hip", "train_kernels.hip", "train.hip", "optim.hip", "gemm_skinny.hip"]
+           "search.hip", "search_scan.hip", "contrastive.hip", "train_kernels.hip", "train.hip", "optim.hip", "gemm_skinny.hip"]
 # every header: a list by hand has missed one before, and then editing it did not rebuild its users
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "openmatch_hip.h")]
 

@@ -104,7 +104,7 @@ OM_DEFINE_LAUNCHER(launch_gemm2, gemm_nt_kernel2, G2_THREADS, G2_LDS_BYTES, G2_B
 
 static unsigned long long* g_trace = nullptr;
 extern "C" void om_debug_gemm_trace(unsigned long long* buf) { g_trace = buf; }
-unsigned long long* omk_debug_trace() { return g_trace; }      // the scan kernel of search.hip stamps into the same buffer
+unsigned long long* omk_debug_trace() { return g_trace; }      // the scan kernels of search_scan.hip stamp into the same buffer
 static int g_debug_gen = 0;     // GemmSwitches::debug_gen
 extern "C" void om_debug_gemm_gen(int gen) { g_debug_gen = gen; }
 

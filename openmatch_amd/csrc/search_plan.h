@@ -1,7 +1,7 @@
 // What a filtered scan round launches: scan_plan() maps (index format, queries, width, switches) to a ScanPlan -- the kernel family and,
 // for the stream kernels, the instantiation -- and scan_round() maps (plan, rows of the round, CUs) to the round's launches: kernel id,
 // rows, grid and `group` argument of a main launch and of a ragged tail.  Neither does anything else -- no launch, no HIP call, no global
-// read or written, no pointer dereferenced.  Scan::filter_step (search.hip) asks for the round and launches it from the kernel table;
+// read or written, no pointer dereferenced.  Scan::filter_step (search.hip) asks for the round and launches it from the kernel table (search_scan.hip, through scan_launch);
 // om_debug_scan_plan / om_debug_scan_round return the plan / the round alone, so the rules are testable on a machine without a GPU, and
 // om_debug_sim_stream launches the stream instantiation a plan names over a caller's buffers, om_debug_scan_kernel one tile kernel with
 // the grid and group of a ScanLaunch.  DESIGN.md 4f lists the rules in the order they are tested here.
@@ -106,7 +106,7 @@ static ScanRound scan_round(const ScanPlan& plan, bool half, int64_t nq, int d, 
 // rounds; many queries: an append costs the scan a slow path, the selection ~0.3 ms -- many short rounds with tight thresholds
 // (profiles/r02_scan_trace_*.log; 33-128 queries, one index pass per round set on the register-resident stream kernel: 100 % measured
 // best of 60 / 100 / 200).  Pure: no launch, no HIP call, no global read (om_debug_search_schedule returns it alone).
-#define SEARCH_SORT_CAP 8192        // keys of one candidate list (search.hip SORT_CAP)
+#define SEARCH_SORT_CAP 8192        // keys of one candidate list (search_keys.h SORT_CAP)
 #define SEARCH_DENSE_CHUNK 4096     // rows of the dense bootstrap (search.hip DENSE_CHUNK)
 #define SEARCH_SCHED_MAX 1024       // rounds a schedule can have: at the smallest growth (5 %) 2^32 rows take fewer than 320
 

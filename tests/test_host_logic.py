@@ -389,7 +389,7 @@ def test_packed_weight_cache_survives_deepcopy_and_pickle():
 
 
 def test_deferred_append_positions_are_not_read_before_their_wait():
-    """sim_stream_reg_kernel (csrc/search.hip) issues the list-counter atomics of a tile as inline assembly and reads
+    """sim_stream_reg_kernel (csrc/search_scan.hip) issues the list-counter atomics of a tile as inline assembly and reads
     their results only behind a hand-written s_waitcnt four units later -- the compiler does not know the destination
     registers are written asynchronously, so a copy it might insert (loop-carried value) would read them too early.
     Compile the translation unit to assembly and check, for every instantiation, that no instruction between an atomic
@@ -400,7 +400,7 @@ def test_deferred_append_positions_are_not_read_before_their_wait():
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(REPO, "openmatch_amd", "csrc", "search.hip")
+    src = os.path.join(REPO, "openmatch_amd", "csrc", "search_scan.hip")
     out = os.path.join(REPO, "build", "search_check.s")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-x", "hip", "-Wno-unused-result", "-w",
@@ -449,7 +449,7 @@ def test_mfma_loops_keep_their_accumulators_in_agprs():
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    units = ["search.hip", "gemm_wide6_bf16.hip", "gemm_tn.hip", "gemm_wide7.hip"]
+    units = ["search_scan.hip", "gemm_wide6_bf16.hip", "gemm_tn.hip", "gemm_wide7.hip"]
     # (the allow-list with per-iteration bounds is below)
     os.makedirs(os.path.join(REPO, "build"), exist_ok=True)
 

@@ -1,4 +1,4 @@
-"""Every launch branch of a filtered round (csrc/search_plan.h scan_round, launched from the kernel table of csrc/search.hip by
+"""Every launch branch of a filtered round (csrc/search_plan.h scan_round, launched from the kernel table of csrc/search_scan.hip by
 Scan::filter_step), once each, end to end at the smallest shape that reaches it: 20 013 rows, k = 100 -- the schedule is
 the dense bootstrap, three whole rounds of 4 096 rows and a last round of 3 629 = 14 x 256 + 45 = 28 x 128 + 45 rows, so the persistent
 kernel of a case and its ragged tail both run.  d = 64 is the one-K-step path of generation 7, d = 128 its two-K-step path, d = 192 the

@@ -1,4 +1,4 @@
-"""The four table kernels of the filtered scan (csrc/search.hip: sim_filter_kernel, sim_filter_kernel6, sim_filter_kernel7,
+"""The four table kernels of the filtered scan (csrc/search_scan.hip: sim_filter_kernel, sim_filter_kernel6, sim_filter_kernel7,
 sim_filter_kernel7c), each launched alone through om_debug_scan_kernel and held to its own contract: after a launch the
 list of every query is EXACTLY the set of rows with score >= thr[q] -- behind the keys the list already held, no id twice, the right
 score bits, cnt the true count -- and nothing else in keys or cnt has changed.
@@ -55,7 +55,7 @@ def f32_orderable(f):
 
 
 def pack_keys(scores, ids):
-    """csrc/search.hip pack_key: (orderable score) << 32 | ~id"""
+    """csrc/search_keys.h pack_key: (orderable score) << 32 | ~id"""
     return (f32_orderable(scores).astype(np.uint64) << np.uint64(32)) | (~np.asarray(ids, np.uint32)).astype(np.uint64)
 
 

@@ -49,7 +49,7 @@ def code(x):
 
 
 def keys_of(s, r):
-    """csrc/search.hip pack_key"""
+    """csrc/search_keys.h pack_key"""
     return (orderable(s).astype(np.uint64) << np.uint64(32)) | (~np.asarray(r, dtype=np.uint32)).astype(np.uint64)
 
 

@@ -1,4 +1,4 @@
-"""The register-resident stream scan beyond d = 768 (csrc/search.hip sim_stream_reg_kernel<.., 16> for 832 <= d <= 1024,
+"""The register-resident stream scan beyond d = 768 (csrc/search_scan.hip sim_stream_reg_kernel<.., 16> for 832 <= d <= 1024,
 sim_stream_reg_kernel<.., 32, 16> for 1088 <= d <= 2048).
 
 Kernel level, through om_debug_sim_stream: index rows and queries are integers in [-4, 4] stored as float16, so every product is an

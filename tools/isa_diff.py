@@ -1,6 +1,6 @@
 """Compare the gfx950 assembly of two source trees, kernel by kernel (CPU only: it compiles, it runs nothing).
 
-    python tools/isa_diff.py [--keep DIR] OLD_TREE NEW_TREE [unit.hip ...]
+    python tools/isa_diff.py [--keep DIR] [--pool a.hip,b.hip] ... OLD_TREE NEW_TREE [unit.hip ...]
     (no unit named: every .hip unit of _build.py's SOURCES; --keep: leave each kernel's normalised text in DIR/<unit>/{old,new}/ to diff)
 
 Each unit is compiled from both trees with the flags of openmatch_amd/_build.py plus `--cuda-device-only -S`.  Comments, the
@@ -10,6 +10,10 @@ alone moves).  What is left is split at the kernel symbols -- from a kernel's la
 .amdhsa_kernel block of register, scratch and LDS figures -- and the text of each kernel is compared for equality; nothing else is
 looked at.  The unit's remaining text (metadata, symbol directives) is one more entry, "<rest>", compared as a sorted list of lines for
 the same reason as the labels.  Exit status 0 when every entry of every unit is equal.
+
+--pool: the kernels of the listed units are pooled on each side -- a unit a tree does not have adds nothing -- and matched by symbol, so
+a kernel that moved between units is still compared (search.hip against search.hip + search_scan.hip: --pool search.hip,search_scan.hip).
+The pooled units leave the unit list, and their "<rest>" entries, which a move is bound to change, are not compared.
 
 A refactor of kernel code that claims "same code as before" is checked with
     git worktree add /tmp/parent HEAD~1 && python tools/isa_diff.py /tmp/parent .
@@ -69,9 +73,20 @@ def kernels(text):
 
 
 def diff_unit(old, new, unit, tmp, keep):
-    stem = os.path.splitext(unit)[0]
-    sides = {"old": kernels(assembly(old, unit, os.path.join(tmp, stem + ".old.s"))),
-             "new": kernels(assembly(new, unit, os.path.join(tmp, stem + ".new.s")))}
+    """unit: a file name, or a tuple of them to pool"""
+    pool = unit if isinstance(unit, tuple) else None
+    stem = "+".join(os.path.splitext(u)[0] for u in pool or [unit])
+    sides = {}
+    for side, tree in (("old", old), ("new", new)):
+        sides[side] = {}
+        for u in pool or [unit]:
+            if pool and not os.path.exists(os.path.join(tree, "openmatch_amd", "csrc", u)):
+                continue
+            parts = kernels(assembly(tree, u, os.path.join(tmp, f"{os.path.splitext(u)[0]}.{side}.s")))
+            if pool:
+                del parts["<rest>"]
+            sides[side].update(parts)
+    unit = " + ".join(pool or [unit])
     if keep:
         for side, parts in sides.items():
             os.makedirs(os.path.join(keep, stem, side), exist_ok=True)
@@ -87,17 +102,23 @@ def main(argv):
     keep = None
     if argv[:1] == ["--keep"]:
         keep, argv = argv[1], argv[2:]
+    pools = []
+    while argv[:1] == ["--pool"]:
+        pools.append(tuple(argv[1].split(",")))
+        argv = argv[2:]
     if len(argv) < 2:
         print(__doc__)
         return 2
     old, new = argv[0], argv[1]
-    units = argv[2:] or [s for s in B.SOURCES if s.endswith(".hip")]
+    pooled = {u for p in pools for u in p}
+    units = [u for u in argv[2:] or [s for s in B.SOURCES if s.endswith(".hip")] if u not in pooled] + pools
     bad = 0
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=8) as ex:
         for unit, rows in ex.map(lambda u: diff_unit(old, new, u, tmp, keep), units):
             wrong = [(k, st) for k, st in rows if st != "equal"]
             bad += len(wrong)
-            print(f"{unit}: {len(rows) - 1} kernels, {len(rows) - len(wrong)} of {len(rows)} entries equal", flush=True)
+            n_kernels = sum(1 for k, _ in rows if k != "<rest>")
+            print(f"{unit}: {n_kernels} kernels, {len(rows) - len(wrong)} of {len(rows)} entries equal", flush=True)
             for k, st in wrong:
                 print(f"  {st}: {k}")
     print("every kernel equal" if not bad else f"{bad} entries differ")
