@@ -358,6 +358,17 @@ size_t om_debug_attention_bwd_stats_bytes(int64_t B, int heads);
 struct OmEncoderConfig;
 int om_debug_encoder_plan(const struct OmEncoderConfig* cfg, int gated_ffn, int has_rel_bias, int64_t B, int64_t L, int64_t packed_rows,
                           int want_hidden);
+/* host only (no GPU needed): what om_encoder_train_forward[_packed|_hidden] (backward == 0) or om_encoder_train_backward[_packed|_hidden]
+ * would run for this call at the current switches (csrc/train_plan.h train_plan; DESIGN.md 4g lists the rules).  want_hidden: the
+ * _hidden entries; has_rel_bias: OmEncoderWeights::rel_bias is given; tape_flags: -1, or for a backward what its forward wrote on the
+ * tape (1: f32 pre-LayerNorm sums, 2: gelu'(f) in place of f).  Returns
+ *   tail (0 hidden states, 1 plain, 2 f32 from the [CLS] rows, 3 f32 mean) | t5 << 2 | gated << 3 | rel << 4 | packed << 5 | bert16 << 6 |
+ *   res32 << 7 | pre_grad << 8 | keep << 9 | early_wt << 10 | lane << 11 | ln_atomics << 12 | wbatch << 16
+ * (keep: the workspace holds keep slices; early_wt: the forward transposes the weights on the side stream / the backward may reuse them;
+ * lane, ln_atomics, wbatch: the BERT backward's side stream, LayerNorm sums by atomics, layers per deferred weight-gradient launch),
+ * 0 for an empty batch, -1 for a refusal with its reason in om_last_error. */
+int om_debug_train_plan(const struct OmEncoderConfig* cfg, int64_t B, int64_t L, int64_t packed_rows, int want_hidden, int has_rel_bias,
+                        int backward, int tape_flags);
 /* host only: 1 if om_encoder_forward (packed_rows == 0) would skip this call's pad rows on the device at the current switches
  * (csrc/encoder_plan.h encoder_skip_pad): OM_OPT_ENCODER_SKIP_PAD is set, no hidden states are wanted, a pooling is set,
  * the call plans OM_ENC_PATH_BERT_FUSED or OM_ENC_PATH_T5_FUSED, and om_encoder_packed_supported takes the bound roundup256(B * L).

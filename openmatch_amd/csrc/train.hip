@@ -16,37 +16,13 @@
 #include <vector>
 
 #include "train_kernels.h"
+#include "train_plan.h"
+
+#define RUN(expr) do { if (expr) return 1; } while (0)
 
 namespace {
-struct Dims {
-  int64_t M, Mp, B, L; int H, F, nl, nh, D; size_t es; bool t5, gated;
-  bool rel;          // a BERT-family stack with a relative-position bias table (MPNet: OmEncoderConfig::rel_buckets > 0)
-  bool packed;       // packed rows (round 5): M = the caller's row bound; sequence b lives in rows cu[b] .. cu[b + 1] - 1 of every [M, .] tensor
-  // what a 16-bit BERT tape holds (fixed by the FORWARD, remembered per tape: tape_flags below):
-  bool bert16;       // 16-bit BERT: the configurations the two flags below apply to
-  bool res32;        // the pre-LayerNorm sums y1 / y2 in f32 (the forward's residual stream stays in f32: OM_OPT_TRAIN_RES32)
-  bool pre_grad;     // gelu'(f) in place of f (OM_OPT_TRAIN_TAPE_GRAD)
-};
-constexpr int TAPE_RES32 = 1, TAPE_PRE_GRAD = 2;
-
-Dims dims_of(const OmEncoderConfig* c, int64_t B, int64_t L, int64_t packed_rows = 0) {
-  Dims d;
-  d.packed = packed_rows > 0;
-  d.B = B; d.L = L; d.M = d.packed ? packed_rows : B * L; d.Mp = (d.M + 63) / 64 * 64;
-  d.H = c->hidden; d.F = c->ffn; d.nl = c->n_layers; d.nh = c->n_heads;
-  d.D = c->head_in > 0 ? c->head_out : c->hidden;
-  d.es = (c->dtype == OM_BF16 || c->dtype == OM_F16) ? 2 : 4;
-  d.t5 = c->arch == OM_ARCH_T5;
-  d.rel = c->arch == OM_ARCH_BERT && c->rel_buckets > 0;
-  d.gated = d.t5 && (c->act & 0xff) == OM_ACT_GELU_TANH;      // T5 v1.1: gated gelu_new (wi_0, wi_1)
-  d.bert16 = !d.t5 && d.es == 2 && (size_t)d.F * d.es >= (size_t)d.H * 4;
-  d.res32 = d.bert16 && om_option(OM_OPT_TRAIN_RES32) != 0;
-  d.pre_grad = d.es == 2 && om_option(OM_OPT_TRAIN_TAPE_GRAD) != 0;
-  return d;
-}
-Dims dims_with_flags(Dims d, int flags) { d.res32 = (flags & TAPE_RES32) != 0; d.pre_grad = (flags & TAPE_PRE_GRAD) != 0; return d; }
-int flags_of(const Dims& d) { return (d.res32 ? TAPE_RES32 : 0) | (d.pre_grad ? TAPE_PRE_GRAD : 0); }
-
+// Every decision of a step -- shapes, tape format, tail, lane, deferred weight gradients -- is train_plan()'s (train_plan.h); the
+// code below carves by the plan `d` and launches what it names.
 // ---- tape: activations saved by the forward ------------------------------------------------
 struct Tape {
   char* x0pre;             // [M,H] embedding LayerNorm output BEFORE dropout (only if dropout)
@@ -57,9 +33,9 @@ struct Tape {
   float *pooled, *headout;             // [B,H], [B,D] (pre-normalise)
   size_t total;
   size_t sx, sqkv, sf;     // per-layer strides in bytes
-  size_t sy;               // stride of y1 / y2 (f32 when Dims::res32)
+  size_t sy;               // stride of y1 / y2 (f32 when TrainPlan::res32)
 };
-Tape carve_tape(const Dims& d, char* base) {
+Tape carve_tape(const TrainPlan& d, char* base) {
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
   Tape t;
@@ -107,8 +83,7 @@ struct Ws {
   int *kmax, *cu, *cls_rows, *row_map;      // packed rows: per-sequence extents, row offsets (+ total, true total), CLS rows, token of every row
   size_t total;
 };
-inline bool keep_ok(const Dims& d) { return !d.t5 && d.es == 2 && d.H % 256 == 0 && d.F % 256 == 0 && d.M >= 32; }
-Ws carve_ws(const Dims& d, char* base) {
+Ws carve_ws(const TrainPlan& d, char* base) {
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base + o; };
   Ws w;
@@ -131,7 +106,7 @@ Ws carve_ws(const Dims& d, char* base) {
   w.posbias = (float*)take(d.t5 || d.rel ? (size_t)d.nh * d.L * d.L * 4 : 0);
   w.drel = (float*)take(d.t5 || d.rel ? (size_t)d.nh * (2 * d.L) * 4 : 0);
   w.lut = (int*)take(d.t5 || d.rel ? (size_t)(2 * d.L) * 4 : 0);
-  w.skeep = keep_ok(d) ? align_up(5 * mh + mf, 256) : 0;
+  w.skeep = d.keep ? align_up(5 * mh + mf, 256) : 0;
   w.keep = take(w.skeep * d.nl);
   w.slnpart = d.t5 ? 0 : (size_t)OM_LNB_MAX_BLOCKS * 2 * d.H;
   w.lnpart = (float*)take(w.slnpart * 4 * 2 * d.nl);
@@ -146,7 +121,7 @@ Ws carve_ws(const Dims& d, char* base) {
 // W^T of every dense weight of the encoder, all layers in one launch: layer l at ws.wt + l * ws.swt holds
 // [Wqkv^T (H x 3H) | Wo^T (H x H) | W1^T (H x F) | W2^T (F x H) | gated T5: W1g^T (H x F)]
 struct WtView { const char *qkv, *o, *f1, *f2, *f1g; };
-WtView wt_of(const Dims& d, const Ws& ws, int l) {
+WtView wt_of(const TrainPlan& d, const Ws& ws, int l) {
   const char* p = ws.wt + ws.swt * l;
   WtView v;
   v.qkv = p; p += (size_t)3 * d.H * d.H * d.es;
@@ -156,7 +131,7 @@ WtView wt_of(const Dims& d, const Ws& ws, int l) {
   v.f1g = p;
   return v;
 }
-int transpose_weights(int dt, const OmLayerWeights* Ls, const Dims& d, Ws& ws, hipStream_t s) {
+int transpose_weights(int dt, const OmLayerWeights* Ls, const TrainPlan& d, Ws& ws, hipStream_t s) {
   std::vector<const void*> in; std::vector<void*> out; std::vector<int> R, C;
   for (int l = 0; l < d.nl; ++l) {
     const WtView v = wt_of(d, ws, l);
@@ -173,7 +148,7 @@ int transpose_weights(int dt, const OmLayerWeights* Ls, const Dims& d, Ws& ws, h
 // atomics into the caller-zeroed buffers.  16-bit runs read dY and X as they lie (gemm_tn.hip: transposing LDS reads,
 // the bias sums on the matrix core); f32 runs -- and widths that are not multiples of 128 -- transpose both operands
 // and use the NT split-K kernel.
-int wgrad(int dt, const void* dY, int N, const void* X, int K, float* dW, float* db, const Dims& d, Ws& ws, hipStream_t s) {
+int wgrad(int dt, const void* dY, int N, const void* X, int K, float* dW, float* db, const TrainPlan& d, Ws& ws, hipStream_t s) {
   if (omk_gemm_tn_ok(dt, d.M, N, K, N, K)) return omk_gemm_tn(dt, dY, N, X, K, dW, K, db, d.M, N, K, s);
   if (db && omk_colsum(dt, dY, N, d.M, N, db, s)) return 1;
   if (omk_transpose(dt, dY, N, d.M, N, ws.tl, d.Mp, d.Mp, 0, s)) return 1;
@@ -182,40 +157,17 @@ int wgrad(int dt, const void* dY, int N, const void* X, int K, float* dW, float*
 }
 
 int check_train_cfg(const OmEncoderConfig* c, int64_t L) {
-  if (c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) OM_FAIL("unknown arch");
-  if (c->dtype != OM_F32 && c->dtype != OM_BF16 && c->dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
-  // float16 training (the reference's --fp16 = torch.cuda.amp float16 + GradScaler for every backbone): BERT-family since round 5, T5 stacks
-  // since round 6 (ReLU / gated tanh-GELU feed-forwards; as under the reference's autocast nothing clamps -- a checkpoint whose feed-forward
-  // activations leave the float16 range overflows there and here alike, the loss scaler skips such steps)
-  if (c->dtype == OM_F16 && c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) OM_FAIL("float16 training: BERT-family and T5 encoders");
-  if (c->arch == OM_ARCH_T5 && (c->head_dim != 64 || c->n_heads * 64 != c->hidden)) OM_FAIL("T5 training: only d_kv 64 with n_heads*64 == d_model");
-  if ((c->head_dim != 32 && c->head_dim != 64) || c->n_heads * c->head_dim != c->hidden) OM_FAIL("head_dim must be 32 or 64 with n_heads*head_dim == hidden");
-  if (L < 1 || L > 512) OM_FAIL("training supports sequence lengths up to 512");      // (257 .. 512: round 6, the tile-at-a-time attention kernels)
-  // 32-wide heads (attention_d32.hip): one backward kernel with a whole score row in registers, every format
-  if (c->head_dim == 32 && L > 256) OM_FAIL("training with head_dim 32 supports sequence lengths up to 256");
-  if (c->dtype == OM_F32 && L > 192 && c->head_dim != 32) OM_FAIL("float32 training supports sequence lengths up to 192 (16-bit formats: 512)");
-  if (c->arch == OM_ARCH_BERT && c->act != OM_ACT_GELU_ERF) OM_FAIL("BERT training supports the erf-GELU FFN");
-  if (c->arch == OM_ARCH_T5 && (c->act & 0xff) != OM_ACT_RELU && (c->act & 0xff) != OM_ACT_GELU_TANH)
-    OM_FAIL("T5 training supports relu and gated gelu_new feed-forward layers");
-  const int es = c->dtype == OM_F32 ? 4 : 2;
-  if ((c->hidden * es) % 128 || (c->ffn * es) % 128) OM_FAIL("hidden/ffn rows must be multiples of 128 bytes");
-  if (c->pooling != OM_POOL_FIRST && c->pooling != OM_POOL_MEAN) OM_FAIL("pooling must be first or mean");
+  if (const char* why = train_cfg_error(c, L)) OM_FAIL(why);
   return 0;
 }
 
 inline uint64_t site_seed(uint64_t seed, int layer, int site) {
   return seed + 0x9E3779B97F4A7C15ull * (uint64_t)(16 * layer + site + 1);
 }
-#define RUN(expr) do { if (expr) return 1; } while (0)
 
 // relative-position bias [nh, L, L] from the bucket table (and the LUT the backward needs again)
-int rel_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Dims& d, Ws& ws, hipStream_t s);
-int t5_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Dims& d, Ws& ws, hipStream_t s) {
-  if (!w->rel_bias || !w->final_ln_g) OM_FAIL("T5 needs rel_bias and final_ln_g");
-  return rel_bias_setup(c, w, d, ws, s);
-}
 // (the BERT-family stack with a bucket table -- MPNet -- shares it: same bucket rule, same [nh, L, L] expansion)
-int rel_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Dims& d, Ws& ws, hipStream_t s) {
+int rel_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const TrainPlan& d, Ws& ws, hipStream_t s) {
   if (!w->rel_bias || c->rel_buckets < 4 || c->rel_buckets % 2 || c->rel_max_dist <= c->rel_buckets / 4)
     OM_FAIL("relative position bias: rel_bias with an even number of buckets >= 4 and a maximum distance beyond the exact buckets");
   const int L = (int)d.L;
@@ -224,12 +176,23 @@ int rel_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const Di
   ws.lut = const_cast<int*>(lut);                // the backward reads it again (never written)
   return omk_t5_bias(w->rel_bias, ws.lut, ws.posbias, L, d.nh, s);
 }
+int t5_bias_setup(const OmEncoderConfig* c, const OmEncoderWeights* w, const TrainPlan& d, Ws& ws, hipStream_t s) {
+  if (!w->rel_bias || !w->final_ln_g) OM_FAIL("T5 needs rel_bias and final_ln_g");
+  return rel_bias_setup(c, w, d, ws, s);
+}
+// the packed-row tables: per-sequence extents, row offsets, [CLS] rows and the token of every row (the workspace is not the tape:
+// the backward makes them again)
+int pack_tables(const TrainPlan& d, const int64_t* attention_mask, Ws& ws, hipStream_t s) {
+  if (!d.packed) return 0;
+  RUN(omk_mask_extent(attention_mask, d.B, (int)d.L, ws.kmax, s));
+  return omk_pack_rows(ws.kmax, d.B, (int)d.L, d.M, ws.cu, ws.cls_rows, ws.row_map, s);
+}
 
 // T5 encoder stack (pre-RMSNorm residual blocks, HF:models/t5/modeling_t5.py T5Stack / T5Block):
 //   x0 = drop(E[ids]);  per layer:  x1 = x + drop(Attn(rms(x)) Wo^T),  x' = x1 + drop(drop(act(rms(x1) Wi^T)) Wo2^T)
 //   out = drop(rms(x_last))
 int t5_train_forward(const OmEncoderConfig* c, const OmEncoderWeights* w, const int64_t* input_ids,
-                     const int64_t* attention_mask, const Dims& d, Tape& t, Ws& ws, float hd, float ad,
+                     const int64_t* attention_mask, const TrainPlan& d, Tape& t, Ws& ws, float hd, float ad,
                      uint64_t seed, char** final_hidden, hipStream_t s) {
   const int dt = c->dtype, H = d.H, F = d.F;
   const int64_t M = d.M;
@@ -373,16 +336,16 @@ static int lane_get(int n_layers, WgradLane** out) {
 
 // dx: gradient w.r.t. the stack's output (after the final dropout); returns through the grads struct
 int t5_train_backward(const OmEncoderConfig* c, const OmEncoderWeights* w, const int64_t* input_ids,
-                      const int64_t* attention_mask, const Dims& d, const Tape& t, Ws& ws, float hd, float ad,
+                      const int64_t* attention_mask, const TrainPlan& d, const Tape& t, Ws& ws, float hd, float ad,
                       uint64_t seed, char* dx, char* dx_other, const OmEncoderGrads* g, hipStream_t s) {
   const int dt = c->dtype, H = d.H, F = d.F;
-  const int64_t M = d.M, Mp = d.Mp;
+  const int64_t M = d.M;
   const OmLayerWeights* Ls = w->layers_host;
   const OmLayerGrads* Gs = g->layers_host;
   if (!g->final_ln_g || !g->rel_bias) OM_FAIL("T5 gradients need final_ln_g and rel_bias buffers");
   RUN(t5_bias_setup(c, w, d, ws, s));
   OM_HIP(hipMemsetAsync(ws.drel, 0, (size_t)d.nh * (2 * d.L) * 4, s));
-#define WGRAD(dY_, N_, X_, K_, dW_) RUN(wgrad(dt, dY_, N_, X_, K_, dW_, nullptr, d, ws, s))
+  auto wg = [&](const void* dY, int N, const void* X, int K, float* dW) { return wgrad(dt, dY, N, X, K, dW, nullptr, d, ws, s); };
   RUN(transpose_weights(dt, Ls, d, ws, s));
   // final dropout + RMSNorm
   const int* const cu = d.packed ? ws.cu : nullptr;                 // packed rows (round 6): the tables train_backward_impl rebuilt
@@ -406,16 +369,16 @@ int t5_train_backward(const OmEncoderConfig* c, const OmEncoderWeights* w, const
     if (hd > 0.f) { RUN(omk_dropout(dt, dx, ws.dd, M * H, hd, site_seed(seed, l, 4), s, row_map, H)); dO = ws.dd; }
     RUN(omk_t5_act_fwd(dt, f, f2, ws.g, M * F, kind, s));                     // g = act(f) [* f2]
     if (hd > 0.f) RUN(omk_dropout(dt, ws.g, ws.g, M * F, hd, site_seed(seed, l, 5), s, row_map, F));
-    WGRAD(dO, H, ws.g, F, lg.ffn2_w);                                         // dWo2 [H,F]
+    RUN(wg(dO, H, ws.g, F, lg.ffn2_w));                                        // dWo2 [H,F]
     GemmEpilogue e = {};
     RUN(omk_gemm(dt, dO, H, wt.f2, H, dt, ws.df, F, M, F, H, e, s));          // dg = dO Wo2;  Wo2^T [F,H]
     if (hd > 0.f) RUN(omk_dropout(dt, ws.df, ws.df, M * F, hd, site_seed(seed, l, 5), s, row_map, F));
     RUN(omk_t5_act_bwd(dt, ws.df, f, f2, ws.df, ws.df2, M * F, kind, s));     // df (in place), df2
     RUN(omk_layernorm(dt, x1, H, ws.nbuf, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // n2 again
-    WGRAD(ws.df, F, ws.nbuf, H, lg.ffn1_w);                                   // dWi (wi / wi_0) [F,H]
+    RUN(wg(ws.df, F, ws.nbuf, H, lg.ffn1_w));                                  // dWi (wi / wi_0) [F,H]
     if (d.gated) {
       if (!lg.ffn1g_w) OM_FAIL("gated T5 gradients need ffn1g_w");
-      WGRAD(ws.df2, F, ws.nbuf, H, lg.ffn1g_w);                               // dWi_1 [F,H]
+      RUN(wg(ws.df2, F, ws.nbuf, H, lg.ffn1g_w));                              // dWi_1 [F,H]
     }
     e = GemmEpilogue{};
     RUN(omk_gemm(dt, ws.df, F, wt.f1, F, dt, ws.dy, H, M, H, F, e, s));       // dn2 = df Wi;  Wi^T [H,F]
@@ -428,63 +391,153 @@ int t5_train_backward(const OmEncoderConfig* c, const OmEncoderWeights* w, const
     // ---- attention branch (dx_other now holds d/d x1)
     const char* dA = dx_other;
     if (hd > 0.f) { RUN(omk_dropout(dt, dx_other, ws.dd, M * H, hd, site_seed(seed, l, 3), s, row_map, H)); dA = ws.dd; }
-    WGRAD(dA, H, ctx, H, lg.o_w);
+    RUN(wg(dA, H, ctx, H, lg.o_w));
     e = GemmEpilogue{};
     RUN(omk_gemm(dt, dA, H, wt.o, H, dt, ws.dctx, H, M, H, H, e, s));         // dctx = dA Wo
     RUN(omk_attention_bwd(dt, qkv, ctx, ws.dctx, ws.dqkv, attention_mask, d.B, (int)d.L, H, d.nh, 1.0f, ad, site_seed(seed, l, 2), ws.posbias, ws.drel,
                           ws.astats, s, cu, d.packed));
     if (d.packed) RUN(omk_zero_rows_from(ws.dqkv, (int64_t)3 * H * d.es, ws.cu + d.B, M, s));      // rows the kernel does not own: zero, not stale
     RUN(omk_layernorm(dt, x, H, ws.nbuf, H, lw.ln1_g, nullptr, M, H, c->ln_eps, 1, s));    // n1 again
-    WGRAD(ws.dqkv, 3 * H, ws.nbuf, H, lg.qkv_w);
+    RUN(wg(ws.dqkv, 3 * H, ws.nbuf, H, lg.qkv_w));
     e = GemmEpilogue{};
     RUN(omk_gemm(dt, ws.dqkv, 3 * H, wt.qkv, 3 * H, dt, ws.dy, H, M, H, 3 * H, e, s));  // dn1
     RUN(omk_norm_bwd(dt, ws.dy, x, lw.ln1_g, dx, lg.ln1_g, nullptr, M, H, c->ln_eps, 1, dx_other, s));   // dx of layer input
     RUN(record_layer_event(l, s));
   }
-#undef WGRAD
   const char* de = dx;
   if (hd > 0.f) { RUN(omk_dropout(dt, dx, ws.dd, M * H, hd, site_seed(seed, 0, 0), s, row_map, H)); de = ws.dd; }
   RUN(omk_t5_embed_bwd(dt, de, input_ids, g->word_emb, M, H, c->vocab, s, row_map));
   RUN(omk_t5_bias_bwd(ws.drel, ws.lut, g->rel_bias, (int)d.L, d.nh, s));
-  RUN(record_layer_event(d.nl, s));
-  g_bwd_events = nullptr; g_bwd_nevents = 0;
+  return record_layer_event(d.nl, s);      // (train_backward_impl's BwdEventsScope consumes the events)
+}
+
+// The tail of both stacks' forwards: the final hidden state xf handed out (plan.tail none), or pool -> head or copy -> normalise ->
+// overflow poison.  16-bit BERT (the f32 tails): the pooled rows come from an f32 evaluation of the LAST LayerNorm (its input y2 is on
+// the tape) -- the reference's autocast runs layer_norm in fp32, so its representations are not rounded to 16 bits on the way to the
+// loss, and the loss of a contrastive batch lives in the DIFFERENCES between near-equal dot products (tests/golden/train_base.npz: the
+// bf16 rounding of the final hidden state alone moved the gradients by tens of percent on a random-init model).  The backward is
+// unchanged: the same function of y2; t.x[n_layers] stays on the tape in the compute format for callers that want the hidden state.
+int train_tail_forward(const TrainPlan& d, const OmEncoderConfig* c, const OmEncoderWeights* w, const int64_t* attention_mask,
+                       const char* xf, const Tape& t, Ws& ws, float* out_reps, void* out_hidden, hipStream_t s) {
+  const int dt = c->dtype, H = d.H;
+  const int64_t B = d.B, M = d.M;
+  const int L = (int)d.L;
+  const int* const cu = d.packed ? ws.cu : nullptr;
+  if (d.tail == TRAIN_TAIL_NONE) {
+    OM_HIP(hipMemcpyAsync(out_hidden, xf, (size_t)M * H * d.es, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  if (d.tail == TRAIN_TAIL_PLAIN) {
+    RUN(omk_pool(dt, xf, attention_mask, t.pooled, B, L, H, c->pooling, s, cu));
+  } else {
+    const OmLayerWeights& last = w->layers_host[d.nl - 1];
+    const char* y2_last = t.y2 + t.sy * (d.nl - 1);
+    const int ydt_last = d.res32 ? OM_F32 : dt;
+    if (d.tail == TRAIN_TAIL_F32_CLS) {
+      if (d.packed) RUN(omk_layernorm_f32out(ydt_last, y2_last, H, t.pooled, H, last.ln2_g, last.ln2_b, B, H, c->ln_eps, 0, s, nullptr, ws.cls_rows));
+      else RUN(omk_layernorm_f32out(ydt_last, y2_last, d.L * H, t.pooled, H, last.ln2_g, last.ln2_b, B, H, c->ln_eps, 0, s));
+    } else {
+      float* x32 = (float*)ws.df;                        // [M, H] f32 fits the [M, F] 16-bit scratch of the backward (bert16: F >= 2 H)
+      RUN(omk_layernorm_f32out(ydt_last, y2_last, H, x32, H, last.ln2_g, last.ln2_b, M, H, c->ln_eps, 0, s));
+      RUN(omk_pool(OM_F32, x32, attention_mask, t.pooled, B, L, H, c->pooling, s, cu));
+    }
+  }
+  float* pre = c->normalize ? t.headout : out_reps;      // value before F.normalize
+  if (c->head_in > 0 && w->head_w) {
+    if (om_gemm_nt(OM_F32, t.pooled, H, w->head_w, c->head_in, OM_F32, pre, d.D, B, d.D, c->head_in,
+                   nullptr, nullptr, 0, OM_ACT_NONE, s)) return 1;
+  } else {
+    OM_HIP(hipMemcpyAsync(pre, t.pooled, (size_t)B * H * 4, hipMemcpyDeviceToDevice, s));
+  }
+  if (c->normalize) RUN(omk_l2norm(t.headout, out_reps, B, d.D, s));
+  if (d.packed) RUN(omk_pack_overflow_poison(ws.cu, B, M, out_reps, B * (int64_t)d.D, s));      // a row bound below the token count: NaN, never a truncated batch
   return 0;
 }
-#undef RUN
+
+// The weight-gradient sites of the BERT backward: a site's contraction is recorded for the group's batched launch (plan.wbatch), or
+// launched on the lane's side stream between its ready / done events (plan.lane), or launched in line.
+struct WgradSites {
+  const TrainPlan& d;
+  int dt;
+  Ws& ws;
+  WgradLane* lane;
+  hipStream_t s;
+  std::vector<OmTnProblem> pend;
+  int site(int l, int i, const void* dY, int N, const void* X, int K, float* dW, float* db) {
+    if (d.wbatch) {
+      OmTnProblem q;
+      q.A = dY; q.B = X; q.C = dW; q.bias = db; q.lda = N; q.ldb = K; q.ldc = K; q.N = N; q.K = K;
+      pend.push_back(q);
+      return 0;
+    }
+    if (!lane) return wgrad(dt, dY, N, X, K, dW, db, d, ws, s);
+    OM_HIP(hipEventRecord(lane->ready[l * 4 + i], s));
+    OM_HIP(hipStreamWaitEvent(lane->side, lane->ready[l * 4 + i], 0));
+    RUN(wgrad(dt, dY, N, X, K, dW, db, d, ws, lane->side));
+    OM_HIP(hipEventRecord(lane->done[l * 4 + i], lane->side));
+    return 0;
+  }
+  // before the main stream rewrites a buffer that weight gradient i of layer l reads
+  int wait(int l, int i) {
+    if (lane && !d.wbatch && l < d.nl) OM_HIP(hipStreamWaitEvent(s, lane->done[l * 4 + i], 0));
+    return 0;
+  }
+};
+
+// Where a BERT layer's dY go: shared scratch, or (deferred weight gradients) the layer's keep slice [M,H] | [M,F] | [M,H] | [M,3H],
+// never rewritten inside the backward.  The operand of the FFN2 / out-proj sites is the dropout-masked gradient when there is
+// dropout, else the LayerNorm backward's output: that one is kept.
+struct LayerDy { char *dy2, *dd2, *df, *dy1, *dd1, *dqkv; };
+LayerDy layer_dy(const TrainPlan& d, const Ws& ws, int l, bool dropout) {
+  if (!d.wbatch) return LayerDy{ws.dy, ws.dd, ws.df, ws.dy, ws.dd, ws.dqkv};
+  const size_t mh = (size_t)d.M * d.H * d.es, mf = (size_t)d.M * d.F * d.es;
+  char* const kp = ws.keep + ws.skeep * l;
+  return LayerDy{dropout ? ws.dy : kp, dropout ? kp : ws.dd, kp + mh, dropout ? ws.dy : kp + mh + mf, dropout ? kp + mh + mf : ws.dd, kp + 2 * mh + mf};
+}
+
+// the plan of a call that only asks for sizes: the plan's shape is filled before any of its refusals
+TrainPlan sized(const OmEncoderConfig* c, int64_t B, int64_t L, int64_t packed_rows) {
+  return train_plan_checked(TrainPlanIn{c, B, L, packed_rows, false, false, false, -1}, train_switches());
+}
 }  // namespace
 
 extern "C" size_t om_encoder_tape_bytes(const OmEncoderConfig* cfg, int64_t B, int64_t L) {
   if (!cfg || B <= 0 || L <= 0) return 0;
-  return carve_tape(dims_of(cfg, B, L), nullptr).total;
+  return carve_tape(sized(cfg, B, L, 0), nullptr).total;
 }
 extern "C" size_t om_encoder_train_workspace_bytes(const OmEncoderConfig* cfg, int64_t B, int64_t L) {
   if (!cfg || B <= 0 || L <= 0) return 0;
-  return carve_ws(dims_of(cfg, B, L), nullptr).total;
+  return carve_ws(sized(cfg, B, L, 0), nullptr).total;
 }
-// Packed rows in training (round 5): the contractions, normalisations and the tape run over `packed_rows` rows -- the tokens up to
-// each sequence's last unmasked one, back to back -- instead of B * L (the reference pads every sequence of a batch to one length,
-// dataset/data_collator.py:13-24, and computes over the padding).  16-bit BERT-family and (round 6) T5 configurations with widths of 256, L <= 256,
-// packed_rows a multiple of 256 that is >= the token count (a bound that is too small turns the representations into NaN).
+// whether the _packed entries take (c, B, L, packed_rows) at the current switches: train_plan.h train_packed_ok
 extern "C" int om_encoder_train_packed_supported(const OmEncoderConfig* c, int64_t B, int64_t L, int64_t packed_rows) {
-  if (!c || B <= 0 || L <= 0 || packed_rows <= 0) return 0;
-  if ((c->arch != OM_ARCH_BERT && c->arch != OM_ARCH_T5) || (c->dtype != OM_BF16 && c->dtype != OM_F16) || c->n_layers <= 0) return 0;      // (T5: round 6)
-  if (packed_rows % 256 || packed_rows < 512 || packed_rows > B * L + 255 || packed_rows >= B * L) return 0;
-  if (c->hidden % 256 || c->ffn % 256 || (c->n_heads * 64 != c->hidden && c->n_heads * 32 != c->hidden)) return 0;
-  if (c->pooling != OM_POOL_FIRST && c->pooling != OM_POOL_MEAN) return 0;
-  if (!om_option(OM_OPT_ATTENTION_FAST) || L > 256) return 0;      // (deliberately stricter than attn_plan.h: float16 packs with the switch on only, and no packed rows beyond 256 tokens)
-  if (c->arch == OM_ARCH_BERT && (size_t)c->ffn < (size_t)2 * c->hidden) return 0;      // (the f32 pooled tail borrows the [M, F] scratch)
-  return 1;
+  return train_packed_ok(c, B, L, packed_rows, train_switches()) ? 1 : 0;
 }
 extern "C" size_t om_encoder_tape_bytes_packed(const OmEncoderConfig* cfg, int64_t B, int64_t L, int64_t packed_rows) {
   if (!om_encoder_train_packed_supported(cfg, B, L, packed_rows)) return 0;
-  return carve_tape(dims_of(cfg, B, L, packed_rows), nullptr).total;
+  return carve_tape(sized(cfg, B, L, packed_rows), nullptr).total;
 }
 extern "C" size_t om_encoder_train_workspace_bytes_packed(const OmEncoderConfig* cfg, int64_t B, int64_t L, int64_t packed_rows) {
   if (!om_encoder_train_packed_supported(cfg, B, L, packed_rows)) return 0;
-  return carve_ws(dims_of(cfg, B, L, packed_rows), nullptr).total;
+  return carve_ws(sized(cfg, B, L, packed_rows), nullptr).total;
 }
 
-#define RUN(expr) do { if (expr) return 1; } while (0)
+// host only: the plan of a training call at the current switches (include/openmatch_hip.h)
+extern "C" int om_debug_train_plan(const OmEncoderConfig* c, int64_t B, int64_t L, int64_t packed_rows, int want_hidden, int has_rel_bias,
+                                   int backward, int tape_flags) {
+  if (!c) {
+    om_set_error("om_debug_train_plan: null argument");
+    return -1;
+  }
+  const TrainPlan p = train_plan(TrainPlanIn{c, B, L, packed_rows, want_hidden != 0, has_rel_bias != 0, backward != 0, tape_flags}, train_switches());
+  if (p.error) {
+    om_set_error(std::string("om_debug_train_plan: ") + p.error);
+    return -1;
+  }
+  if (p.empty) return 0;
+  return p.tail | (int)p.t5 << 2 | (int)p.gated << 3 | (int)p.rel << 4 | (int)p.packed << 5 | (int)p.bert16 << 6 | (int)p.res32 << 7 |
+         (int)p.pre_grad << 8 | (int)p.keep << 9 | (int)p.early_wt << 10 | (int)p.lane << 11 | (int)p.ln_atomics << 12 | p.wbatch << 16;
+}
 
 // out_hidden != NULL: the stack's output [B,L,H] in the compute dtype (T5: after the final RMSNorm and its dropout) is
 // copied out and the pooling / head / normalise tail is skipped (the T5 decoder position consumes it, decoder.hip)
@@ -498,9 +551,8 @@ static int train_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* 
   if (check_train_cfg(c, L)) return 1;
   if (B <= 0) return 0;
   if (((uintptr_t)tape_mem & 255) || ((uintptr_t)workspace & 255)) OM_FAIL("tape/workspace must be 256-byte aligned");
-  if (packed_rows > 0 && (out_hidden || !om_encoder_train_packed_supported(c, B, L, packed_rows)))
-    OM_FAIL("packed rows in training: 16-bit BERT-family or T5 encoder, widths of 256, L <= 256, rows a multiple of 256 in [512, B * L) (om_encoder_train_packed_supported)");
-  const Dims d = dims_of(c, B, L, packed_rows);
+  const TrainPlan d = train_plan_checked(TrainPlanIn{c, B, L, packed_rows, out_hidden != nullptr, w->rel_bias != nullptr, false, -1}, train_switches());
+  if (d.rule == 4) OM_FAIL(d.error);
   const bool packed = d.packed;
   Tape t = carve_tape(d, (char*)tape_mem);
   Ws ws = carve_ws(d, (char*)workspace);
@@ -512,36 +564,18 @@ static int train_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* 
   if (!Ls) OM_FAIL("layers_host is null");
   if (d.t5) {
     char* xf_t5 = nullptr;
-    if (packed) {      // (round 6) the row tables of the BERT branch below; a T5 block has no bias anywhere, so the rows no sequence owns stay exact zeros
-      RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-      RUN(omk_pack_rows(ws.kmax, B, (int)L, M, ws.cu, ws.cls_rows, ws.row_map, s));
-    }
+    RUN(pack_tables(d, attention_mask, ws, s));      // (round 6) a T5 block has no bias anywhere, so the rows no sequence owns stay exact zeros
     if (t5_train_forward(c, w, input_ids, attention_mask, d, t, ws, hidden_dropout, attn_dropout, seed, &xf_t5, s)) return 1;
-    if (out_hidden) {
-      OM_HIP(hipMemcpyAsync(out_hidden, xf_t5, (size_t)M * H * d.es, hipMemcpyDeviceToDevice, s));
-      return 0;
-    }
-    const bool head_t5 = c->head_in > 0 && w->head_w;
-    RUN(omk_pool(dt, xf_t5, attention_mask, t.pooled, B, (int)L, H, c->pooling, s, packed ? ws.cu : nullptr));
-    float* pre_t5 = c->normalize ? t.headout : out_reps;
-    if (head_t5) {
-      if (om_gemm_nt(OM_F32, t.pooled, H, w->head_w, c->head_in, OM_F32, pre_t5, d.D, B, d.D, c->head_in,
-                     nullptr, nullptr, 0, OM_ACT_NONE, s)) return 1;
-    } else {
-      OM_HIP(hipMemcpyAsync(pre_t5, t.pooled, (size_t)B * H * 4, hipMemcpyDeviceToDevice, s));
-    }
-    if (c->normalize) RUN(omk_l2norm(t.headout, out_reps, B, d.D, s));
-    if (packed) RUN(omk_pack_overflow_poison(ws.cu, B, M, out_reps, B * (int64_t)d.D, s));
-    return 0;
+    return train_tail_forward(d, c, w, attention_mask, xf_t5, t, ws, out_reps, out_hidden, s);
   }
   if (L > c->max_pos) OM_FAIL("sequence longer than the position table");
-  if ((w->rel_bias != nullptr) != d.rel) OM_FAIL("relative position bias: rel_bias and rel_buckets must be set together");
+  if (d.error) OM_FAIL(d.error);      // rules 5 and 6 of the plan
   if (w->type_emb && c->type_vocab <= 0) OM_FAIL("token types: a type_emb table needs type_vocab > 0");
   if (d.rel) RUN(rel_bias_setup(c, w, d, ws, s));      // [nh, L, L], added to the scaled scores of every layer's attention
   const float* const posbias = d.rel ? ws.posbias : nullptr;
 
-  tape_flags_set(tape_mem, flags_of(d));
-  if ((om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 2) && d.es == 2 && d.nl > 0) {
+  tape_flags_set(tape_mem, train_tape_flags(d));
+  if (d.early_wt) {
     WgradLane* lane = nullptr;
     RUN(lane_get(d.nl, &lane));
     OM_HIP(hipEventRecord(lane->wt_start, s));                       // everything queued so far (the optimizer's update of the
@@ -551,17 +585,13 @@ static int train_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* 
     OM_HIP(hipEventRecord(lane->wt_done, lane->side));
     lane->wt_ws = ws.wt; lane->wt_w0 = Ls[0].qkv_w; lane->wt_w1 = Ls[d.nl - 1].ffn2_w; lane->wt_nl = d.nl;
   }
-  const int* cu = nullptr;
-  const int* row_map = nullptr;
-  if (packed) {
-    // rows of sequence b: cu[b] .. cu[b + 1] - 1 (up to its last unmasked token); row_map names the token of every row (-1: a zero
-    // row behind the last sequence).  The pad rows stay finite through the forward (a zero embedding row, normalised, projected ...)
-    // except where no kernel writes them -- the attention output -- which is zeroed: the weight gradients sum over all M rows, and
-    // 0 (their dY) x anything finite is 0.
-    RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-    RUN(omk_pack_rows(ws.kmax, B, (int)L, M, ws.cu, ws.cls_rows, ws.row_map, s));
-    cu = ws.cu; row_map = ws.row_map;
-  }
+  // packed rows: rows of sequence b: cu[b] .. cu[b + 1] - 1 (up to its last unmasked token); row_map names the token of every row (-1: a
+  // zero row behind the last sequence).  The pad rows stay finite through the forward (a zero embedding row, normalised, projected ...)
+  // except where no kernel writes them -- the attention output -- which is zeroed: the weight gradients sum over all M rows, and
+  // 0 (their dY) x anything finite is 0.
+  RUN(pack_tables(d, attention_mask, ws, s));
+  const int* const cu = packed ? ws.cu : nullptr;
+  const int* const row_map = packed ? ws.row_map : nullptr;
   RUN(omk_embed(dt, input_ids, token_type_ids, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g,
                 w->emb_ln_b, t.x, M, (int)L, H, c->vocab, c->type_vocab, c->ln_eps, 1, s, row_map));
   // (every hidden-dropout mask is keyed on (token, column): with packed rows the kernels get the row -> token map, so the packed and the
@@ -615,43 +645,7 @@ static int train_forward_impl(const OmEncoderConfig* c, const OmEncoderWeights* 
     if (d.res32) RUN(omk_layernorm_dual(dt, (const float*)y2, H, t.x + t.sx * (l + 1), ws.x32a, H, lw.ln2_g, lw.ln2_b, M, H, c->ln_eps, s));
     else RUN(omk_layernorm(dt, y2, H, t.x + t.sx * (l + 1), H, lw.ln2_g, lw.ln2_b, M, H, c->ln_eps, 0, s));
   }
-  const char* xf = t.x + t.sx * d.nl;
-  if (out_hidden) {
-    OM_HIP(hipMemcpyAsync(out_hidden, xf, (size_t)M * H * d.es, hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  const bool head = c->head_in > 0 && w->head_w;
-  if (d.es == 2 && d.nl > 0 && (c->pooling == OM_POOL_FIRST || d.bert16)) {
-    // 16-bit runs: the pooled rows come from an f32 evaluation of the LAST LayerNorm (its input y2 is on the tape) -- the reference's
-    // autocast runs layer_norm in fp32, so its representations are not rounded to 16 bits on the way to the loss, and the loss of a
-    // contrastive batch lives in the DIFFERENCES between near-equal dot products (tests/golden/train_base.npz: the bf16 rounding
-    // of the final hidden state alone moved the gradients by tens of percent on a random-init model).  The backward is unchanged:
-    // the same function of y2; t.x[n_layers] stays on the tape in the compute format for callers that want the hidden state.
-    const OmLayerWeights& last = Ls[d.nl - 1];
-    const char* y2_last = t.y2 + t.sy * (d.nl - 1);
-    const int ydt_last = d.res32 ? OM_F32 : dt;
-    if (c->pooling == OM_POOL_FIRST) {
-      if (packed) RUN(omk_layernorm_f32out(ydt_last, y2_last, H, t.pooled, H, last.ln2_g, last.ln2_b, B, H, c->ln_eps, 0, s, nullptr, ws.cls_rows));
-      else RUN(omk_layernorm_f32out(ydt_last, y2_last, L * H, t.pooled, H, last.ln2_g, last.ln2_b, B, H, c->ln_eps, 0, s));
-    } else {
-      float* x32 = (float*)ws.df;                        // [M, H] f32 fits the [M, F] 16-bit scratch of the backward (bert16: F >= 2 H)
-      RUN(omk_layernorm_f32out(ydt_last, y2_last, H, x32, H, last.ln2_g, last.ln2_b, M, H, c->ln_eps, 0, s));
-      RUN(omk_pool(OM_F32, x32, attention_mask, t.pooled, B, (int)L, H, c->pooling, s, cu));
-    }
-  } else {
-    if (packed) OM_FAIL("packed rows in training: the 16-bit pooled tail only");
-    RUN(omk_pool(dt, xf, attention_mask, t.pooled, B, (int)L, H, c->pooling, s));
-  }
-  float* pre = c->normalize ? t.headout : out_reps;      // value before F.normalize
-  if (head) {
-    if (om_gemm_nt(OM_F32, t.pooled, H, w->head_w, c->head_in, OM_F32, pre, d.D, B, d.D, c->head_in,
-                   nullptr, nullptr, 0, OM_ACT_NONE, s)) return 1;
-  } else {
-    OM_HIP(hipMemcpyAsync(pre, t.pooled, (size_t)B * H * 4, hipMemcpyDeviceToDevice, s));
-  }
-  if (c->normalize) RUN(omk_l2norm(t.headout, out_reps, B, d.D, s));
-  if (packed) RUN(omk_pack_overflow_poison(ws.cu, B, M, out_reps, B * (int64_t)d.D, s));      // a row bound below the token count: NaN, never a truncated batch
-  return 0;
+  return train_tail_forward(d, c, w, attention_mask, t.x + t.sx * d.nl, t, ws, out_reps, out_hidden, s);
 }
 
 extern "C" int om_encoder_train_forward_packed(const OmEncoderConfig* c, const OmEncoderWeights* w,
@@ -698,31 +692,28 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
   if (!c || !w || !g || !tape_mem || (!d_reps && !d_hidden) || !workspace) OM_FAIL("null argument");
   if (check_train_cfg(c, L)) return 1;
   if (B <= 0) return 0;
-  if (packed_rows > 0 && (d_hidden || !om_encoder_train_packed_supported(c, B, L, packed_rows)))
-    OM_FAIL("packed rows in training: not for this configuration (om_encoder_train_packed_supported)");
-  const Dims d0 = dims_of(c, B, L, packed_rows);
-  const Dims d = dims_with_flags(d0, tape_flags_get(tape_mem, flags_of(d0)));      // the tape as its forward wrote it
+  // (the tape as its forward wrote it; -1, a tape the map does not know: as the switches say now)
+  const TrainPlan d = train_plan_checked(TrainPlanIn{c, B, L, packed_rows, d_hidden != nullptr, w->rel_bias != nullptr, true, tape_flags_get(tape_mem, -1)},
+                                         train_switches());
+  if (d.rule == 4) OM_FAIL(d.error);
   Tape t = carve_tape(d, (char*)tape_mem);
   Ws ws = carve_ws(d, (char*)workspace);
   if (ws.total > workspace_bytes) OM_FAIL("workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int dt = c->dtype, H = d.H, F = d.F;
-  const int64_t M = d.M, Mp = d.Mp;
+  const int64_t M = d.M;
   const OmLayerWeights* Ls = w->layers_host;
   const OmLayerGrads* Gs = g->layers_host;
   if (!Ls || !Gs) OM_FAIL("layers_host is null");
+  if (d.error) OM_FAIL(d.error);      // rules 5 and 6 of the plan
   const float scale = 1.0f / sqrtf((float)c->head_dim);
 
-  const int* cu = nullptr;
-  if (d.packed) {            // the forward's row tables again (the workspace is not the tape: nothing of it survives between the calls)
-    RUN(omk_mask_extent(attention_mask, B, (int)L, ws.kmax, s));
-    RUN(omk_pack_rows(ws.kmax, B, (int)L, M, ws.cu, ws.cls_rows, ws.row_map, s));
-    cu = ws.cu;
-  }
+  RUN(pack_tables(d, attention_mask, ws, s));      // the forward's row tables again
+  const int* const cu = d.packed ? ws.cu : nullptr;
   char* dx = ws.dxa;       // gradient w.r.t. the current layer's OUTPUT
   char* dx_prev = ws.dxb;  // gradient w.r.t. its input (next iteration's dx)
   const float* dpool32 = nullptr;      // the same for the top layer as f32 (16-bit BERT, pooled tail)
-  if (d_hidden) {
+  if (d.tail == TRAIN_TAIL_NONE) {
     OM_HIP(hipMemcpyAsync(dx, d_hidden, (size_t)M * H * d.es, hipMemcpyDeviceToDevice, s));
   } else {
     // ---- tail: normalise -> head -> pooling ----------------------------------------------------
@@ -742,14 +733,13 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
     // GELU' contraction writes it).  That backward projects out most of a contrastive gradient -- the pooled vectors of a batch are
     // nearly parallel -- and what survives is of the size of a bf16 rounding of what went in: rounding here alone moved the
     // step from 2.4 x to 3.9 x (worst tensor 8.9 x) the reference's encoder-only bf16 autocast (tools/emulate_train_dataflow.py).
-    if (d.bert16) {
+    if (d.tail != TRAIN_TAIL_PLAIN) {
       dpool32 = (const float*)ws.df;
       RUN(omk_pool_bwd(OM_F32, dpooled, attention_mask, ws.df, B, (int)L, H, c->pooling, s, cu));
       // packed rows: the rows behind the last sequence carry a ZERO gradient from here down (LayerNorm backward, dropout and the
       // contractions map zero rows to zero rows), so they add nothing to the weight gradients that sum over all M rows
       if (d.packed) RUN(omk_zero_rows_from(ws.df, (int64_t)H * 4, ws.cu + B, M, s));
     } else {
-      if (d.packed && !d.t5) OM_FAIL("packed rows in training: the 16-bit pooled tail only");
       RUN(omk_pool_bwd(dt, dpooled, attention_mask, dx, B, (int)L, H, c->pooling, s, cu));
       if (d.packed) RUN(omk_zero_rows_from(dx, (int64_t)H * d.es, ws.cu + B, M, s));      // zero gradient rows stay zero all the way down (no bias in a T5 block)
     }
@@ -760,51 +750,22 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
 
   // relative-position bias (MPNet): the table is shared by all layers, so every layer's attention backward adds its score gradient,
   // summed over the batch, into ONE per-offset buffer drel [nh, 2L - 1]; omk_t5_bias_bwd folds it into the bucket table at the end
-  if ((w->rel_bias != nullptr) != d.rel) OM_FAIL("relative position bias: rel_bias and rel_buckets must be set together");
   if (d.rel) {
     if (!g->rel_bias) OM_FAIL("relative position bias: the gradients need a rel_bias buffer");
     RUN(rel_bias_setup(c, w, d, ws, s));
     OM_HIP(hipMemsetAsync(ws.drel, 0, (size_t)d.nh * (2 * d.L) * 4, s));
   }
-  // weight gradients on the second stream when every one of them takes the direct kernel (16-bit, widths of 128)
-  WgradLane* lane = nullptr;
-  if (om_option(OM_OPT_TRAIN_WGRAD_STREAM) && omk_gemm_tn_ok(dt, M, H, F, H, F) && omk_gemm_tn_ok(dt, M, F, H, F, H) &&
-      omk_gemm_tn_ok(dt, M, H, H, H, H) && omk_gemm_tn_ok(dt, M, 3 * H, H, 3 * H, H))
-    RUN(lane_get(d.nl, &lane));
-  // Deferred, batched weight gradients (OM_OPT_TRAIN_WGRAD_BATCH = layers per launch): the sites only RECORD their
-  // contraction; the dY they name live in the layer's keep slice (never rewritten inside this backward), and after the
-  // lowest layer of a group one om_gemm_tn_acc_batch launch computes the group's 4 x layers weight gradients -- on the
+  // Weight gradients on the second stream (plan.lane).  Deferred, batched weight gradients (plan.wbatch = layers per launch): the
+  // sites only RECORD their contraction; the dY they name live in the layer's keep slice (never rewritten inside this backward), and
+  // after the lowest layer of a group one om_gemm_tn_acc_batch launch computes the group's 4 x layers weight gradients -- on the
   // side stream when the lane is on (one event per group each way instead of one per site), else in line.
-  int wbatch = om_option(OM_OPT_TRAIN_WGRAD_BATCH);
-  if (wbatch < 0) wbatch = 0;
-  if (wbatch > 12) wbatch = 12;
-  if (wbatch && !(ws.skeep && omk_gemm_tn_batch_ok(dt, M, H, F, H, F) && omk_gemm_tn_batch_ok(dt, M, F, H, F, H) &&
-                  omk_gemm_tn_batch_ok(dt, M, H, H, H, H) && omk_gemm_tn_batch_ok(dt, M, 3 * H, H, 3 * H, H)))
-    wbatch = 0;
-  std::vector<OmTnProblem> pend;
-  const bool ln_atomics = (om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 4) != 0;      // A/B: the LayerNorm parameter sums by atomics, as before round 5
+  WgradLane* lane = nullptr;
+  if (d.lane) RUN(lane_get(d.nl, &lane));
+  WgradSites wg = {d, dt, ws, lane, s, {}};
   std::vector<OmLnSite> ln_pend;                                    // LayerNorm sites whose parameter sums wait for the group's reduce
   int group_top = d.nl - 1;                                         // highest layer of the group being collected
-  const size_t mh_b = (size_t)M * H * d.es, mf_b = (size_t)M * F * d.es;
-#define WGRAD(I_, dY_, N_, X_, K_, dW_, db_)                                                        \
-  do {                                                                                             \
-    if (wbatch) {                                                                                  \
-      OmTnProblem q_;                                                                              \
-      q_.A = dY_; q_.B = X_; q_.C = dW_; q_.bias = db_; q_.lda = N_; q_.ldb = K_; q_.ldc = K_; q_.N = N_; q_.K = K_; \
-      pend.push_back(q_);                                                                          \
-    } else if (lane) {                                                                             \
-      OM_HIP(hipEventRecord(lane->ready[l * 4 + (I_)], s));                                        \
-      OM_HIP(hipStreamWaitEvent(lane->side, lane->ready[l * 4 + (I_)], 0));                        \
-      RUN(wgrad(dt, dY_, N_, X_, K_, dW_, db_, d, ws, lane->side));                                \
-      OM_HIP(hipEventRecord(lane->done[l * 4 + (I_)], lane->side));                                \
-    } else {                                                                                       \
-      RUN(wgrad(dt, dY_, N_, X_, K_, dW_, db_, d, ws, s));                                         \
-    }                                                                                              \
-  } while (0)
-  // before the main stream rewrites a buffer that weight gradient I_ of layer L_ reads
-#define WGRAD_DONE(L_, I_) do { if (lane && !wbatch && (L_) < d.nl) OM_HIP(hipStreamWaitEvent(s, lane->done[(L_) * 4 + (I_)], 0)); } while (0)
   if (g_lane.wt_ws == ws.wt && g_lane.wt_w0 == Ls[0].qkv_w && g_lane.wt_w1 == Ls[d.nl - 1].ffn2_w && g_lane.wt_nl == d.nl &&
-      g_lane.wt_done && (om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 2)) {
+      g_lane.wt_done && d.early_wt) {
     OM_HIP(hipStreamWaitEvent(s, g_lane.wt_done, 0));               // the forward's side-stream transposes of these very weights
   } else {
     // (a forward's transposes of OTHER weights / another shape may still be writing an overlapping part of the workspace)
@@ -825,78 +786,70 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
     const char* gl = t.g + t.sf * l;
     const char* y2 = t.y2 + t.sy * l;
     const WtView wt = wt_of(d, ws, l);
-    // where this layer's dY go: shared scratch, or (deferred weight gradients) the layer's keep slice.  The operand of
-    // the FFN2 / out-proj sites is the dropout-masked gradient when there is dropout, else the LayerNorm backward's output.
-    char* const kp = wbatch ? ws.keep + ws.skeep * l : nullptr;
-    char* const dy2 = (wbatch && hidden_dropout <= 0.f) ? kp : ws.dy;
-    char* const dd2 = (wbatch && hidden_dropout > 0.f) ? kp : ws.dd;
-    char* const dfl = wbatch ? kp + mh_b : ws.df;
-    char* const dy1 = (wbatch && hidden_dropout <= 0.f) ? kp + mh_b + mf_b : ws.dy;
-    char* const dd1 = (wbatch && hidden_dropout > 0.f) ? kp + mh_b + mf_b : ws.dd;
-    char* const dqkvl = wbatch ? kp + 2 * mh_b + mf_b : ws.dqkv;
+    const auto [dy2, dd2, dfl, dy1, dd1, dqkvl] = layer_dy(d, ws, l, hidden_dropout > 0.f);
 
     // LN2 backward: dy2 = d(loss)/d(y2)
     // (+ the FFN output branch's dropout, which sits after the dense and before the residual add, in the same pass)
-    WGRAD_DONE(l + 1, 2);                                           // ws.dy / ws.dd: last read by dWo of the layer above
+    RUN(wg.wait(l + 1, 2));                                           // ws.dy / ws.dd: last read by dWo of the layer above
     {
-      OmLnSite st = {ln_atomics ? nullptr : ws.lnpart + ws.slnpart * (2 * l + 1), lg.ln2_g, lg.ln2_b, 0};
+      OmLnSite st = {d.ln_atomics ? nullptr : ws.lnpart + ws.slnpart * (2 * l + 1), lg.ln2_g, lg.ln2_b, 0};
       RUN(omk_ln_bwd_drop(dt, dx, y2, lw.ln2_g, dy2, dd2, hidden_dropout, site_seed(seed, l, 4), lg.ln2_g, lg.ln2_b, M, H, c->ln_eps, s,
                           l == d.nl - 1 ? dpool32 : nullptr, d.res32 ? (const float*)y2 : nullptr, (float*)st.partial, &st.blocks,
                           d.packed ? ws.row_map : nullptr));
       if (st.partial) ln_pend.push_back(st);
     }
     const char* dO = hidden_dropout > 0.f ? dd2 : dy2;
-    WGRAD(0, dO, H, gl, F, lg.ffn2_w, lg.ffn2_b);                   // dW2 [H,F], db2
+    RUN(wg.site(l, 0, dO, H, gl, F, lg.ffn2_w, lg.ffn2_b));                   // dW2 [H,F], db2
     {
       GemmEpilogue e1 = {};
       // df = (dO W2) * gelu'(f);  W2^T [F,H].  The tape holds gelu'(f) itself in 16-bit runs (see the forward)
       e1.act = d.pre_grad ? OM_ACT_MUL_RESID : OM_ACT_GELU_ERF_GRAD; e1.resid = f; e1.ldr = F;
-      WGRAD_DONE(l + 1, 1);                                         // ws.df: last read by dW1 of the layer above
+      RUN(wg.wait(l + 1, 1));                                         // ws.df: last read by dW1 of the layer above
       RUN(omk_gemm(dt, dO, H, wt.f2, H, dt, dfl, F, M, F, H, e1, s));
     }
-    WGRAD(1, dfl, F, x1, H, lg.ffn1_w, lg.ffn1_b);                  // dW1 [F,H], db1
+    RUN(wg.site(l, 1, dfl, F, x1, H, lg.ffn1_w, lg.ffn1_b));                  // dW1 [F,H], db1
     {
       GemmEpilogue e2 = {};
       e2.resid = dy2; e2.ldr = H;                                   // dx1 = df W1 + dy2 (residual path);  W1^T [H,F]
       RUN(omk_gemm(dt, dfl, F, wt.f1, F, dt, ws.dctx, H, M, H, F, e2, s));
     }
     // LN1 backward (ws.dctx holds d/d(x1) for now)
-    WGRAD_DONE(l, 0);                                               // ws.dy / ws.dd: read by dW2 of this layer
+    RUN(wg.wait(l, 0));                                               // ws.dy / ws.dd: read by dW2 of this layer
     {
-      OmLnSite st = {ln_atomics ? nullptr : ws.lnpart + ws.slnpart * (2 * l), lg.ln1_g, lg.ln1_b, 0};
+      OmLnSite st = {d.ln_atomics ? nullptr : ws.lnpart + ws.slnpart * (2 * l), lg.ln1_g, lg.ln1_b, 0};
       RUN(omk_ln_bwd_drop(dt, ws.dctx, y1, lw.ln1_g, dy1, dd1, hidden_dropout, site_seed(seed, l, 3), lg.ln1_g, lg.ln1_b, M, H, c->ln_eps, s,
                           nullptr, d.res32 ? (const float*)y1 : nullptr, (float*)st.partial, &st.blocks, d.packed ? ws.row_map : nullptr));
       if (st.partial) ln_pend.push_back(st);
     }
     const char* dA = hidden_dropout > 0.f ? dd1 : dy1;
-    WGRAD(2, dA, H, ctx, H, lg.o_w, lg.o_b);                        // dWo [H,H], dbo
+    RUN(wg.site(l, 2, dA, H, ctx, H, lg.o_w, lg.o_b));                        // dWo [H,H], dbo
     {
       GemmEpilogue e3 = {};
       RUN(omk_gemm(dt, dA, H, wt.o, H, dt, ws.dctx, H, M, H, H, e3, s));    // dctx = dA Wo
     }
-    WGRAD_DONE(l + 1, 3);                                           // ws.dqkv: last read by dWqkv of the layer above
+    RUN(wg.wait(l + 1, 3));                                           // ws.dqkv: last read by dWqkv of the layer above
     RUN(omk_attention_bwd(dt, qkv, ctx, ws.dctx, dqkvl, attention_mask, B, (int)L, H, d.nh, scale, attn_dropout, site_seed(seed, l, 2),
                           d.rel ? ws.posbias : nullptr, d.rel ? ws.drel : nullptr, ws.astats, s, cu, d.packed));
     if (d.packed) RUN(omk_zero_rows_from(dqkvl, (int64_t)3 * H * d.es, ws.cu + B, M, s));      // rows the kernel does not own: zero, not stale
-    WGRAD(3, dqkvl, 3 * H, x, H, lg.qkv_w, lg.qkv_b);               // dWqkv [3H,H], dbqkv
+    RUN(wg.site(l, 3, dqkvl, 3 * H, x, H, lg.qkv_w, lg.qkv_b));               // dWqkv [3H,H], dbqkv
     {
       GemmEpilogue e4 = {};
       e4.resid = dy1; e4.ldr = H;                                   // dx = dqkv Wqkv + dy1;  Wqkv^T [H,3H]
       RUN(omk_gemm(dt, dqkvl, 3 * H, wt.qkv, 3 * H, dt, dx_prev, H, M, H, 3 * H, e4, s));
     }
     char* tmp = dx; dx = dx_prev; dx_prev = tmp;
-    if (wbatch) {
+    if (d.wbatch) {
       // the group is complete at its lowest layer: one launch for all of its weight gradients, then the progress events
       // of its layers (their gradients exist once that launch is done)
-      if (l == 0 || group_top - l + 1 >= wbatch) {
+      if (l == 0 || group_top - l + 1 >= d.wbatch) {
         hipStream_t ws_stream = s;
         if (lane) {
           OM_HIP(hipEventRecord(lane->mark[l], s));
           OM_HIP(hipStreamWaitEvent(lane->side, lane->mark[l], 0));
           ws_stream = lane->side;
         }
-        RUN(omk_gemm_tn_batch(dt, pend.data(), (int)pend.size(), M, ws_stream));
-        pend.clear();
+        RUN(omk_gemm_tn_batch(dt, wg.pend.data(), (int)wg.pend.size(), M, ws_stream));
+        wg.pend.clear();
         RUN(omk_ln_param_reduce(ln_pend.data(), (int)ln_pend.size(), H, ws_stream));      // the group's LayerNorm parameter gradients
         ln_pend.clear();
         for (int ll = group_top; ll >= l; --ll) RUN(record_layer_event(ll, ws_stream));
@@ -924,11 +877,7 @@ static int train_backward_impl(const OmEncoderConfig* c, const OmEncoderWeights*
                     w->emb_ln_g, g->word_emb, g->pos_emb, g->type_emb, g->emb_ln_g, g->emb_ln_b, B * L,
                     (int)L, H, c->vocab, c->type_vocab, c->ln_eps, s, cu));
   if (d.rel) RUN(omk_t5_bias_bwd(ws.drel, ws.lut, g->rel_bias, (int)d.L, d.nh, s));
-#undef WGRAD
-#undef WGRAD_DONE
-  RUN(record_layer_event(d.nl, s));
-  g_bwd_events = nullptr; g_bwd_nevents = 0;
-  return 0;
+  return record_layer_event(d.nl, s);
 }
 
 extern "C" int om_encoder_train_backward(const OmEncoderConfig* c, const OmEncoderWeights* w,

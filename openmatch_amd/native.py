@@ -216,6 +216,7 @@ _SIGNATURES = {
                                           c_int, c_int, c_float, c_float, C.c_uint64, c_void_p, c_int, c_void_p]),
     "om_debug_attention_bwd_stats_bytes": (c_size_t, [c_int64, c_int]),
     "om_debug_encoder_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
+    "om_debug_train_plan": (c_int, [C.POINTER(OmEncoderConfig), c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
     "om_debug_encoder_skip_pad": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int]),
     "om_debug_encoder_cls_tail": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "om_debug_encoder_lanes": (c_int, [C.POINTER(OmEncoderConfig), c_int, c_int, c_int64, c_int64, c_int64, c_int, C.POINTER(c_int64)]),
