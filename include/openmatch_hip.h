@@ -424,6 +424,15 @@ int om_debug_wave_sum_check(const float* in, float* out_shuffle, float* out_dpp,
 #define OM_ROW_FWD_X8 2
 #define OM_ROW_LN_BWD 3
 int om_debug_row_kernel_last(void);
+/* Host only (csrc/row_plan.h): the word a normalisation call WOULD note, without a launch or a device -- 0 when there is
+ * nothing to do (M <= 0), -1 with the launcher's own refusal in om_last_error; both set the thread's note word to 0.
+ * om_debug_row_fwd_plan: entry 0 om_debug_layernorm, 1 _f32out, 2 _from_f32, 3 _dual; data_aligned: x, y and x_lo (where given) are
+ * 16-byte aligned; param_aligned: g and b (where given) are; plane: x_lo is given.
+ * om_debug_row_bwd_plan: mode 0 om_debug_norm_bwd / om_debug_ln_bwd_drop (L is not read), 1 om_debug_embed_bwd, at the current
+ * OM_OPT_TRAIN_WGRAD_STREAM; out = {grid, threads per block, dynamic LDS bytes, the value *partial_blocks receives}. */
+int om_debug_row_fwd_plan(int entry, int dtype, int64_t M, int H, int64_t ldx, int64_t ldy, int data_aligned, int param_aligned, int plane,
+                          int lo8);
+int om_debug_row_bwd_plan(int dtype, int mode, int64_t M, int H, int L, int has_x32, int has_dy32, int has_partial, int64_t out[4]);
 int om_debug_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
                        float eps, int rms, const void* x_lo, int lo8, void* stream);
 int om_debug_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b, int64_t M,

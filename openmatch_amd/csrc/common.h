@@ -35,6 +35,9 @@ void om_set_error(const std::string& msg);
     }                                                                       \
   } while (0)
 #define OM_LAUNCH_CHECK() OM_HIP(hipGetLastError())
+// the dtype check of the om_debug_* kernel hooks (a local `dtype`): the three formats, or the two 16-bit ones
+#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+#define OM_DBG_DTYPE16(what) if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_BF16 or OM_F16")
 
 // ---- bf16 <-> f32 ----------------------------------------------------------
 __host__ __device__ inline float bf16_to_f32(bf16_t v) {

@@ -635,7 +635,6 @@ extern "C" int om_linear_f32_backward(const float* dy, const float* x, const flo
 
 // ---- test hooks of this file's kernels (include/openmatch_hip.h, tests/test_decoder_kernels.py): pointers, dtype and ranges
 // checked, then every argument forwarded to the launcher the step and the train pair call ----
-#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
 #define OM_DBG_CROSS(what)                                                                           \
   OM_DBG_DTYPE(what);                                                                                \
   if (L < 1 || L > DEC_MAX_L) OM_FAIL(what ": sequence length must be in [1,1024]");                  \
@@ -688,4 +687,3 @@ extern "C" int om_debug_dec_cast(int dtype, const float* x, void* y, int64_t n, 
 // host only: the per-site dropout seed, so that the tests' Python port of it is pinned to this file
 extern "C" uint64_t om_debug_dec_site(uint64_t seed, int layer, int site) { return dec_site(seed, layer, site); }
 #undef OM_DBG_CROSS
-#undef OM_DBG_DTYPE

@@ -4,10 +4,10 @@
 #include "common.h"
 #include "kernels.h"
 #include "ln_row.h"
+#include "row_plan.h"
 #include <type_traits>
 
-#define ROWS_PER_BLOCK 4
-#define MAX_VEC_LIMIT 8  // 4-element vectors per lane -> H <= 2048 (NV = 4 covers H <= 1024)
+#define ROWS_PER_BLOCK 4      // (4-element vectors per lane: row_max_vec, 4 up to H = 1024 and 8 up to 2048)
 
 // Normalise the row held in x[][] (nv vectors per lane) and write it out.
 // LayerNorm: two-pass mean / biased variance in f32 (torch.nn.LayerNorm);
@@ -407,22 +407,51 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void index_add_f16_kernel(
 static thread_local int g_row_last = 0;     // the OM_ROW_* word of this thread's last normalisation launch (include/openmatch_hip.h)
 void omk_row_note(int word) { g_row_last = word; }
 extern "C" int om_debug_row_kernel_last(void) { return g_row_last; }
-template <typename T> constexpr int row_dt() { return sizeof(T) == 4 ? OM_F32 : (std::is_same<T, bf16_t>::value ? OM_BF16 : OM_F16); }
-static inline int row_fwd_word(int body, int nv, int tin, int tout, bool plane, bool lo8) {
-  return body | nv << 4 | tin << 8 | tout << 12 | (plane ? 1 << 16 : 0) | (plane && lo8 ? 1 << 17 : 0);
+
+// The one forward launch of the four omk_layernorm* entries: what row_fwd_plan (row_plan.h) named, on these arguments.
+struct RowFwdArgs {
+  const void* x; int64_t ldx; void* y; int64_t ldy; const float* g; const float* b; int64_t M; int H; float eps; int rms;
+  const void* x_lo;      // x8 body: the second plane, or NULL
+  const int* rows;       // gather: output row r normalises input row rows[r], or NULL
+  float* y32;            // generic body: the unrounded f32 copy of y (omk_layernorm_dual), or NULL
+};
+static inline bool row_aligned16(const void* a, const void* b, const void* c = nullptr) {      // (a NULL pointer is aligned)
+  return !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15);
 }
 
 template <typename TIn, typename TOut>
-static int launch_ln(const void* x, int64_t ldx, void* y, int64_t ldy, const float* g,
-                     const float* b, int64_t M, int H, float eps, int rms, hipStream_t s, const int* rows = nullptr) {
-  const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-  omk_row_note(row_fwd_word(OM_ROW_FWD_GENERIC, H <= 1024 ? 4 : 8, row_dt<TIn>(), row_dt<TOut>(), false, false));
-  if (H <= 1024)
-    hipLaunchKernelGGL((layernorm_kernel<TIn, TOut, 4>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s,
-                       (const TIn*)x, ldx, (TOut*)y, ldy, g, b, M, H, eps, rms, rows);
-  else
-    hipLaunchKernelGGL((layernorm_kernel<TIn, TOut, 8>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s,
-                       (const TIn*)x, ldx, (TOut*)y, ldy, g, b, M, H, eps, rms, rows);
+static void launch_row_fwd_as(const RowFwdPlan& p, const RowFwdArgs& a, hipStream_t s) {
+  if constexpr (sizeof(TIn) == 2) {
+    if (p.body == OM_ROW_FWD_X8) {
+      auto x8 = [&](auto nv) {
+        hipLaunchKernelGGL((layernorm_bf16x8_kernel<decltype(nv)::value, TOut, TIn>), dim3((unsigned)((a.M + 7) / 8)), dim3(256), 0, s, (const TIn*)a.x,
+                           a.ldx, (TOut*)a.y, a.ldy, a.g, a.b, a.M, a.H, a.eps, a.rms, (const TIn*)a.x_lo, a.rows, (int)p.lo8);
+      };
+      if (p.nv == 1) x8(std::integral_constant<int, 1>());
+      else if (p.nv == 2) x8(std::integral_constant<int, 2>());
+      else if (p.nv == 3) x8(std::integral_constant<int, 3>());
+      else x8(std::integral_constant<int, 4>());
+      return;
+    }
+  }
+  auto generic = [&](auto mv) {
+    hipLaunchKernelGGL((layernorm_kernel<TIn, TOut, decltype(mv)::value>), dim3((unsigned)((a.M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)),
+                       dim3(64 * ROWS_PER_BLOCK), 0, s, (const TIn*)a.x, a.ldx, (TOut*)a.y, a.ldy, a.g, a.b, a.M, a.H, a.eps, a.rms, a.rows, a.y32);
+  };
+  if (p.nv == 4) generic(std::integral_constant<int, 4>());
+  else generic(std::integral_constant<int, 8>());
+}
+
+static int launch_row_fwd(const RowFwdPlan& p, const RowFwdArgs& a, hipStream_t s) {
+  omk_row_note(row_fwd_word(p));
+  const auto is = [&](int tin, int tout) { return p.tin == tin && p.tout == tout; };
+  if (is(OM_BF16, OM_BF16)) launch_row_fwd_as<bf16_t, bf16_t>(p, a, s);
+  else if (is(OM_F16, OM_F16)) launch_row_fwd_as<f16_t, f16_t>(p, a, s);
+  else if (is(OM_BF16, OM_F32)) launch_row_fwd_as<bf16_t, float>(p, a, s);
+  else if (is(OM_F16, OM_F32)) launch_row_fwd_as<f16_t, float>(p, a, s);
+  else if (is(OM_F32, OM_BF16)) launch_row_fwd_as<float, bf16_t>(p, a, s);
+  else if (is(OM_F32, OM_F16)) launch_row_fwd_as<float, f16_t>(p, a, s);
+  else launch_row_fwd_as<float, float>(p, a, s);      // (the plan names these seven pairs and no other)
   OM_LAUNCH_CHECK();
   return 0;
 }
@@ -492,11 +521,10 @@ extern "C" int om_debug_gather_rows(const void* src0, void* dst0, const void* sr
 // x in f32 (a residual stream kept in f32 under a 16-bit compute format: encoder_causal.hip) -> y in the compute format
 int omk_layernorm_from_f32(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
                            float eps, int rms, hipStream_t s) {
-  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-  if (M <= 0) return 0;
-  if (dtype == OM_BF16) return launch_ln<float, bf16_t>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
-  if (dtype == OM_F16) return launch_ln<float, f16_t>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
-  return launch_ln<float, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
+  const RowFwdPlan p = row_fwd_plan(ROW_FWD_FROM_F32, dtype, M, H, ldx, ldy, row_aligned16(x, y), row_aligned16(g, b), false, false);
+  if (p.error) OM_FAIL(p.error);
+  if (p.empty) return 0;
+  return launch_row_fwd(p, RowFwdArgs{x, ldx, y, ldy, g, b, M, H, eps, rms, nullptr, nullptr, nullptr}, s);
 }
 
 // x[f32] += rms(h) * g: the RMSNorm of a sublayer OUTPUT h (compute format) added into a residual stream kept in f32 (Gemma3's
@@ -536,12 +564,12 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void rmsnorm_add_kernel(const 
 template <typename TIn>
 static void launch_rmsnorm_add(const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s) {
   const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-  if (H <= 1024) hipLaunchKernelGGL((rmsnorm_add_kernel<TIn, 4>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, (const TIn*)h, ldh, x, ldx, g, M, H, eps);
+  if (row_max_vec(H) == 4) hipLaunchKernelGGL((rmsnorm_add_kernel<TIn, 4>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, (const TIn*)h, ldh, x, ldx, g, M, H, eps);
   else hipLaunchKernelGGL((rmsnorm_add_kernel<TIn, 8>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, (const TIn*)h, ldh, x, ldx, g, M, H, eps);
 }
 
 int omk_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s) {
-  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
+  if (const char* why = row_width_error(H)) OM_FAIL(why);
   if (ldh % 4 || ldx % 4) OM_FAIL("norm-add: row pitches of whole four-element vectors");
   if (M <= 0) return 0;
   if (dtype == OM_BF16) launch_rmsnorm_add<bf16_t>(h, ldh, x, ldx, g, M, H, eps, s);
@@ -554,27 +582,10 @@ int omk_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx
 // x in the compute format (optionally two planes, bf16) -> y in f32
 int omk_layernorm_f32out(int dtype, const void* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b,
                          int64_t M, int H, float eps, int rms, hipStream_t s, const void* x_lo, const int* rows, int lo8) {
-  if (lo8 && !(x_lo && dtype == OM_F16 && H % 256 == 0 && ldx % H == 0)) OM_FAIL("eight-bit second plane: float16 rows of a whole-tile [M, H] tensor");
-  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-  if (M <= 0) return 0;
-  if ((dtype == OM_BF16 || (dtype == OM_F16 && x_lo)) && H % 8 == 0 && H <= 1024 && ldx % 8 == 0 && ldy % 4 == 0 &&
-      !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)x_lo) & 15) && !(((uintptr_t)g | (uintptr_t)b) & 15)) {
-    const unsigned grid = (unsigned)((M + 7) / 8);
-    const int nv = (H / 8 + 31) / 32;
-#define LN8F_(NV, TI) hipLaunchKernelGGL((layernorm_bf16x8_kernel<NV, float, TI>), dim3(grid), dim3(256), 0, s, (const TI*)x, ldx, \
-                                    y, ldy, g, b, M, H, eps, rms, (const TI*)x_lo, rows, lo8)
-#define LN8F(NV) do { if (dtype == OM_BF16) LN8F_(NV, bf16_t); else LN8F_(NV, f16_t); } while (0)
-    omk_row_note(row_fwd_word(OM_ROW_FWD_X8, nv <= 1 ? 1 : nv, dtype, OM_F32, x_lo != nullptr, lo8 != 0));
-    if (nv <= 1) LN8F(1); else if (nv == 2) LN8F(2); else if (nv == 3) LN8F(3); else LN8F(4);
-#undef LN8F
-#undef LN8F_
-    OM_LAUNCH_CHECK();
-    return 0;
-  }
-  if (x_lo) OM_FAIL("two-plane LayerNorm input: 16-bit rows of whole 16-byte vectors only");
-  if (dtype == OM_BF16) return launch_ln<bf16_t, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s, rows);
-  if (dtype == OM_F16) return launch_ln<f16_t, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s, rows);
-  return launch_ln<float, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s, rows);
+  const RowFwdPlan p = row_fwd_plan(ROW_FWD_F32OUT, dtype, M, H, ldx, ldy, row_aligned16(x, y, x_lo), row_aligned16(g, b), x_lo != nullptr, lo8 != 0);
+  if (p.error) OM_FAIL(p.error);
+  if (p.empty) return 0;
+  return launch_row_fwd(p, RowFwdArgs{x, ldx, y, ldy, g, b, M, H, eps, rms, x_lo, rows, nullptr}, s);
 }
 
 // packed rows: more tokens than the caller's row bound -> every representation becomes NaN (never a silently truncated batch)
@@ -593,64 +604,38 @@ int omk_pack_overflow_poison(const int* cu, int64_t B, int64_t rows, float* out,
 // the LayerNorm of the 16-bit training forward, whose residual stream stays in f32 as the reference's autocast keeps it
 int omk_layernorm_dual(int dtype, const float* x, int64_t ldx, void* y, float* y32, int64_t ldy, const float* g, const float* b,
                        int64_t M, int H, float eps, hipStream_t s) {
-  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-  if (M <= 0) return 0;
-  const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-#define LND(TO, MV) hipLaunchKernelGGL((layernorm_kernel<float, TO, MV>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, x, ldx, (TO*)y, ldy, g, b, M, \
-                                       H, eps, 0, (const int*)nullptr, y32)
-  if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("a 16-bit output format");
-  omk_row_note(row_fwd_word(OM_ROW_FWD_GENERIC, H <= 1024 ? 4 : 8, OM_F32, dtype, false, false));
-  if (dtype == OM_BF16) { if (H <= 1024) LND(bf16_t, 4); else LND(bf16_t, 8); }
-  else { if (H <= 1024) LND(f16_t, 4); else LND(f16_t, 8); }
-#undef LND
-  OM_LAUNCH_CHECK();
-  return 0;
+  const RowFwdPlan p = row_fwd_plan(ROW_FWD_DUAL, dtype, M, H, ldx, ldy, row_aligned16(x, y), row_aligned16(g, b), false, false);
+  if (p.error) OM_FAIL(p.error);
+  if (p.empty) return 0;
+  return launch_row_fwd(p, RowFwdArgs{x, ldx, y, ldy, g, b, M, H, eps, 0, nullptr, nullptr, y32}, s);
 }
 
 int omk_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, const float* g,
                   const float* b, int64_t M, int H, float eps, int rms, hipStream_t s, const void* x_lo, int lo8) {
-  if (lo8 && !(x_lo && dtype == OM_F16 && H % 256 == 0 && ldx % H == 0)) OM_FAIL("eight-bit second plane: float16 rows of a whole-tile [M, H] tensor");
-  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-  if (M <= 0) return 0;
-  if (x_lo && !((dtype == OM_BF16 || dtype == OM_F16) && H % 8 == 0 && H <= 1024 && ldx % 8 == 0 && ldy % 8 == 0 &&
-                !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)x_lo) & 15) && !(((uintptr_t)g | (uintptr_t)b) & 15)))
-    OM_FAIL("two-plane LayerNorm input: 16-bit rows of whole 16-byte vectors only");
-  if ((dtype == OM_BF16 || (dtype == OM_F16 && x_lo)) && H % 8 == 0 && H <= 1024 && ldx % 8 == 0 && ldy % 8 == 0 &&
-      !(((uintptr_t)x | (uintptr_t)y) & 15) && !(((uintptr_t)g | (uintptr_t)b) & 15)) {
-    const unsigned grid = (unsigned)((M + 7) / 8);
-    const int nv = (H / 8 + 31) / 32;
-#define LN8_(NV, TI) hipLaunchKernelGGL((layernorm_bf16x8_kernel<NV, TI, TI>), dim3(grid), dim3(256), 0, s, (const TI*)x, ldx, \
-                                   (TI*)y, ldy, g, b, M, H, eps, rms, (const TI*)x_lo, (const int*)nullptr, lo8)
-#define LN8(NV) do { if (dtype == OM_BF16) LN8_(NV, bf16_t); else LN8_(NV, f16_t); } while (0)
-    omk_row_note(row_fwd_word(OM_ROW_FWD_X8, nv <= 1 ? 1 : nv, dtype, dtype, x_lo != nullptr, lo8 != 0));
-    if (nv <= 1) LN8(1); else if (nv == 2) LN8(2); else if (nv == 3) LN8(3); else LN8(4);
-#undef LN8
-#undef LN8_
-    OM_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == OM_BF16) return launch_ln<bf16_t, bf16_t>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
-  if (dtype == OM_F16) return launch_ln<f16_t, f16_t>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
-  return launch_ln<float, float>(x, ldx, y, ldy, g, b, M, H, eps, rms, s);
+  const RowFwdPlan p = row_fwd_plan(ROW_FWD_LAYERNORM, dtype, M, H, ldx, ldy, row_aligned16(x, y, x_lo), row_aligned16(g, b), x_lo != nullptr, lo8 != 0);
+  if (p.error) OM_FAIL(p.error);
+  if (p.empty) return 0;
+  return launch_row_fwd(p, RowFwdArgs{x, ldx, y, ldy, g, b, M, H, eps, rms, x_lo, nullptr, nullptr}, s);
 }
 
 int omk_embed(int dtype, const int64_t* ids, const int64_t* type_ids, const float* word,
               const float* pos, const float* type, const float* g, const float* b, void* out,
               int64_t M, int L, int H, int vocab, int type_vocab, float eps, int bert,
               hipStream_t s, const int* row_map, float* out32) {
-  if (H % 4 != 0 || H > 64 * 4 * MAX_VEC_LIMIT) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
+  if (const char* why = row_width_error(H)) OM_FAIL(why);
   if (M <= 0) return 0;
   if (out32 && (!bert || row_map)) OM_FAIL("embedding: the f32 copy goes with the BERT LayerNorm on unpacked rows");
   const unsigned grid = (unsigned)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+  const bool narrow = row_max_vec(H) == 4;
 #define EMBED_LAUNCH(TT, NV)                                                                   \
   hipLaunchKernelGGL((embed_kernel<TT, NV>), dim3(grid), dim3(64 * ROWS_PER_BLOCK), 0, s, ids, \
                      type_ids, word, pos, type, g, b, (TT*)out, M, L, H, vocab, type_vocab, eps, bert, row_map, out32)
   if (dtype == OM_BF16) {
-    if (H <= 1024) EMBED_LAUNCH(bf16_t, 4); else EMBED_LAUNCH(bf16_t, 8);
+    if (narrow) EMBED_LAUNCH(bf16_t, 4); else EMBED_LAUNCH(bf16_t, 8);
   } else if (dtype == OM_F16) {
-    if (H <= 1024) EMBED_LAUNCH(f16_t, 4); else EMBED_LAUNCH(f16_t, 8);
+    if (narrow) EMBED_LAUNCH(f16_t, 4); else EMBED_LAUNCH(f16_t, 8);
   } else {
-    if (H <= 1024) EMBED_LAUNCH(float, 4); else EMBED_LAUNCH(float, 8);
+    if (narrow) EMBED_LAUNCH(float, 4); else EMBED_LAUNCH(float, 8);
   }
 #undef EMBED_LAUNCH
   OM_LAUNCH_CHECK();
@@ -728,8 +713,20 @@ extern "C" int om_debug_swiglu_rows(int dtype, const void* in, void* out, int64_
 }
 
 // ---- test hooks of the row kernels (include/openmatch_hip.h): argument checks, then the launcher as it is ----
-#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
-#define OM_DBG_DTYPE16(what) if (dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_BF16 or OM_F16")
+// host only: the note word the entry would store for these arguments (0: nothing to do; -1: refused, the entry's text in om_last_error)
+extern "C" int om_debug_row_fwd_plan(int entry, int dtype, int64_t M, int H, int64_t ldx, int64_t ldy, int data_aligned, int param_aligned, int plane,
+                                     int lo8) {
+  omk_row_note(0);
+  const char* why = nullptr;
+  if (entry < ROW_FWD_LAYERNORM || entry > ROW_FWD_DUAL) why = "entry must be 0 (layernorm), 1 (f32out), 2 (from_f32) or 3 (dual)";
+  else if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) why = "dtype must be OM_F32, OM_BF16 or OM_F16";
+  const RowFwdPlan p = why ? RowFwdPlan{} : row_fwd_plan(entry, dtype, M, H, ldx, ldy, data_aligned != 0, param_aligned != 0, plane != 0, lo8 != 0);
+  if (why || p.error) {
+    om_set_error(std::string("om_debug_row_fwd_plan: ") + (why ? why : p.error));
+    return -1;
+  }
+  return p.empty ? 0 : row_fwd_word(p);
+}
 extern "C" int om_debug_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, const float* g, const float* b, int64_t M, int H,
                                   float eps, int rms, const void* x_lo, int lo8, void* stream) {
   omk_row_note(0);

@@ -4,6 +4,7 @@
 // The dense contractions themselves (dgrad, wgrad) run on the MFMA GEMM of gemm.hip.
 #include "attn_common.h"
 #include "attn_plan.h"
+#include "row_plan.h"
 #include "train_kernels.h"
 
 // ---------------------------------------------------------------------------------------
@@ -99,7 +100,6 @@ int omk_transpose_batch(int dtype, const void* const* in, void* const* out, cons
 }
 
 // ---- test hooks of the transposes (include/openmatch_hip.h): argument checks, then the launcher as it is ----
-#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
 extern "C" int om_debug_transpose(int dtype, const void* in, int64_t ldi, int64_t R, int C, void* out, int64_t ldo, int64_t Rp, int op,
                                   void* stream) {
   if (!in || !out) OM_FAIL("om_debug_transpose: null argument");
@@ -113,7 +113,6 @@ extern "C" int om_debug_transpose_batch(int dtype, const void* const* in, void* 
     if (R[i] > 0 && C[i] > 0 && (!in[i] || !out[i])) OM_FAIL("om_debug_transpose_batch: null argument");
   return omk_transpose_batch(dtype, in, out, R, C, n, (hipStream_t)stream);
 }
-#undef OM_DBG_DTYPE
 
 // out[c] += sum_r x[r][c]      (out is f32 and zero-initialised by the caller)
 template <typename T>
@@ -469,41 +468,45 @@ __global__ __launch_bounds__((NV == 8 || MODE == 1) ? 256 : 512, (NV == 8 || MOD
   }
 }
 
+// What one ln_bwd_kernel launch reads and writes, by name (MODE 0: dy .. partial; MODE 1, the embedding backward: dy, g, dg, db and the tables)
+struct LnBwdArgs {
+  const void* dy = nullptr; const void* x = nullptr; const float* g = nullptr; void* dx = nullptr; float* dg = nullptr; float* db = nullptr;
+  int64_t M = 0; int H = 0; float eps = 0.f;
+  int rms = 0;                               // T5LayerNorm
+  const void* add = nullptr;                 // added to dx
+  void* dx_drop = nullptr; float drop_p = 0.f; uint64_t drop_seed = 0;      // dropout(dx) as well
+  const int* drop_rows = nullptr;            // MODE 0, packed rows: the token of every row (the dropout mask's key)
+  const float* dy32 = nullptr; const float* x32 = nullptr;                  // f32 tensors read instead of dy / x
+  float* partial = nullptr;                  // the blocks' column sums of d_gamma / d_beta, instead of atomics into dg / db
+  const int64_t* ids = nullptr; const int64_t* type_ids = nullptr;          // MODE 1 from here on
+  const float* word = nullptr; const float* pos = nullptr; const float* type = nullptr;
+  float* dword = nullptr; float* dpos = nullptr; float* dtype_ = nullptr;
+  int L = 1, vocab = 1, type_vocab = 1;
+  const int* cu = nullptr;                   // MODE 1, packed rows: dy holds sequence b at rows cu[b] .. cu[b + 1] - 1
+};
+
+// launches what row_bwd_plan (row_plan.h) named; the kernel has ONE pointer for drop_rows (MODE 0) and cu (MODE 1)
 template <typename T, int MODE>
-static int launch_ln_bwd(const void* dy, const void* x, const float* g, void* dx, float* dg, float* db,
-                         int64_t M, int H, float eps, const int64_t* ids, const int64_t* tt,
-                         const float* word, const float* pos, const float* type, float* dword,
-                         float* dpos, float* dtype_, int L, int vocab, int type_vocab, hipStream_t s,
-                         int rms = 0, const void* add = nullptr, void* dx_drop = nullptr, float drop_p = 0.f, uint64_t drop_seed = 0,
-                         const float* dy32 = nullptr, const float* x32 = nullptr, float* partial = nullptr, int* partial_blocks = nullptr,
-                         const int* cu = nullptr) {
-  const int waves = (H <= 1024 && MODE == 0) ? 8 : 4;
-  const int64_t want = (M + waves - 1) / waves;
-  // two blocks per CU: ~12 MB of loads in flight (one row per wave at a time), what ~5 TB/s x ~2 us of latency needs;
-  // more blocks only add same-address atomics on d_gamma / d_beta (1024 blocks: 41 us, 256: 30 us per call)
-  unsigned grid = (unsigned)(want > OM_LNB_MAX_BLOCKS ? OM_LNB_MAX_BLOCKS : want);
-  if (partial_blocks) *partial_blocks = (int)grid;
-  if (MODE == 1) {                     // one position per block, 256 / L blocks per position (kernel comment)
-    if (L < 1 || M % L) OM_FAIL("embedding backward: M must be B * L");
-    const int parts = 256 / L > 0 ? 256 / L : 1;
-    grid = (unsigned)(L * parts);
-  }
-  const size_t lds = (size_t)2 * waves * H * sizeof(float);       // <= 64 KiB for both shapes
+static int launch_ln_bwd(const RowBwdPlan& p, const LnBwdArgs& a, hipStream_t s) {
+  omk_row_note(row_bwd_word(p));
   constexpr bool can_pf = MODE == 0 && sizeof(T) == 2;
-  // the prefetching body: bit 3 of the switch (A/B) takes it out; wider rows spill with it
-  const bool pf = can_pf && x32 && !dy32 && H <= 768 && (om_option(OM_OPT_TRAIN_WGRAD_STREAM) & 8) == 0;
-  const int nv = (H <= 768 && MODE == 0) ? 3 : (H <= 1024 ? 4 : 8);
-  omk_row_note(OM_ROW_LN_BWD | nv << 4 | MODE << 8 | waves << 12 | (pf ? 1 << 16 : 0) | ((MODE == 0 && partial) ? 1 << 17 : 0));
-#define LNB_(NV, PF_) hipLaunchKernelGGL((ln_bwd_kernel<T, NV, MODE, PF_>), dim3(grid), dim3(64 * waves), lds, s, (const T*)dy, (const T*)x, g, (T*)dx, dg, db, M, H, eps, ids, tt, word, pos, type, dword, dpos, dtype_, L, vocab, type_vocab, rms, (const T*)add, (T*)dx_drop, drop_p, drop_seed, dy32, x32, partial, cu)
-#define LNB(NV) LNB_(NV, false)
-  if (pf) LNB_(3, can_pf);
-  else if (H <= 768 && MODE == 0) LNB(3);
-  else if (H <= 1024) LNB(4);
-  else LNB(8);
+#define LNB(NV, PF_) hipLaunchKernelGGL((ln_bwd_kernel<T, NV, MODE, PF_>), dim3((unsigned)p.grid), dim3(64 * p.waves), (size_t)p.lds, s, (const T*)a.dy, \
+                                        (const T*)a.x, a.g, (T*)a.dx, a.dg, a.db, a.M, a.H, a.eps, a.ids, a.type_ids, a.word, a.pos, a.type, a.dword, \
+                                        a.dpos, a.dtype_, a.L, a.vocab, a.type_vocab, a.rms, (const T*)a.add, (T*)a.dx_drop, a.drop_p, a.drop_seed,    \
+                                        a.dy32, a.x32, a.partial, MODE == 1 ? a.cu : a.drop_rows)
+  if (p.prefetch) LNB(3, can_pf);
+  else if (p.nv == 3) LNB(3, false);      // (MODE 1 never plans NV 3: the instantiation stays so that the unit's kernel list does)
+  else if (p.nv == 4) LNB(4, false);
+  else LNB(8, false);
 #undef LNB
-#undef LNB_
   OM_LAUNCH_CHECK();
   return 0;
+}
+template <int MODE>
+static int launch_ln_bwd(int dtype, const RowBwdPlan& p, const LnBwdArgs& a, hipStream_t s) {
+  if (dtype == OM_BF16) return launch_ln_bwd<bf16_t, MODE>(p, a, s);
+  if (dtype == OM_F16) return launch_ln_bwd<f16_t, MODE>(p, a, s);
+  return launch_ln_bwd<float, MODE>(p, a, s);
 }
 
 int omk_ln_bwd(int dtype, const void* dy, const void* x, const float* g, void* dx, float* dg,
@@ -514,14 +517,15 @@ int omk_ln_bwd(int dtype, const void* dy, const void* x, const float* g, void* d
 int omk_ln_bwd_drop(int dtype, const void* dy, const void* x, const float* g, void* dx, void* dx_drop, float drop_p,
                     uint64_t drop_seed, float* dg, float* db, int64_t M, int H, float eps, hipStream_t s, const float* dy32,
                     const float* x32, float* partial, int* partial_blocks, const int* drop_rows) {
-  if (M <= 0) { if (partial_blocks) *partial_blocks = 0; return 0; }
-  if (H % 4 || H > 2048) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-  if (drop_p <= 0.f) dx_drop = nullptr;
-#define OM_LNBD(TT) return launch_ln_bwd<TT, 0>(dy, x, g, dx, dg, db, M, H, eps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, 1, s, 0, nullptr, dx_drop, drop_p, drop_seed, dy32, x32, partial, partial_blocks, drop_rows)
-  if (dtype == OM_BF16) OM_LNBD(bf16_t);
-  if (dtype == OM_F16) OM_LNBD(f16_t);
-  OM_LNBD(float);
-#undef OM_LNBD
+  const RowBwdPlan p = row_bwd_plan(dtype, 0, M, H, 1, x32 != nullptr, dy32 != nullptr, partial != nullptr, row_switches());
+  if (p.error) OM_FAIL(p.error);
+  if (partial_blocks) *partial_blocks = p.partial_blocks;
+  if (p.empty) return 0;
+  LnBwdArgs a;
+  a.dy = dy; a.x = x; a.g = g; a.dx = dx; a.dg = dg; a.db = db; a.M = M; a.H = H; a.eps = eps;
+  a.dx_drop = drop_p > 0.f ? dx_drop : nullptr; a.drop_p = drop_p; a.drop_seed = drop_seed; a.drop_rows = drop_rows;
+  a.dy32 = dy32; a.x32 = x32; a.partial = partial;
+  return launch_ln_bwd<0>(dtype, p, a, s);
 }
 
 // d_gamma[c] += sum over blocks of partial[b][0][c], d_beta likewise, for n LayerNorm sites in one launch (the partial sums that
@@ -560,26 +564,27 @@ int omk_ln_param_reduce(const OmLnSite* sites, int n, int H, hipStream_t s) {
 
 int omk_norm_bwd(int dtype, const void* dy, const void* x, const float* g, void* dx, float* dg,
                  float* db, int64_t M, int H, float eps, int rms, const void* add, hipStream_t s) {
-  if (M <= 0) return 0;
-  if (H % 4 || H > 2048) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-  if (dtype == OM_BF16)
-    return launch_ln_bwd<bf16_t, 0>(dy, x, g, dx, dg, db, M, H, eps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, 1, s, rms, add);
-  if (dtype == OM_F16)
-    return launch_ln_bwd<f16_t, 0>(dy, x, g, dx, dg, db, M, H, eps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, 1, s, rms, add);
-  return launch_ln_bwd<float, 0>(dy, x, g, dx, dg, db, M, H, eps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, 1, s, rms, add);
+  const RowBwdPlan p = row_bwd_plan(dtype, 0, M, H, 1, false, false, false, row_switches());
+  if (p.error) OM_FAIL(p.error);
+  if (p.empty) return 0;
+  LnBwdArgs a;
+  a.dy = dy; a.x = x; a.g = g; a.dx = dx; a.dg = dg; a.db = db; a.M = M; a.H = H; a.eps = eps;
+  a.rms = rms; a.add = add;
+  return launch_ln_bwd<0>(dtype, p, a, s);
 }
 
 int omk_embed_bwd(int dtype, const void* dy, const int64_t* ids, const int64_t* type_ids,
                   const float* word, const float* pos, const float* type, const float* g,
                   float* dword, float* dpos, float* dtype_, float* dg, float* db, int64_t M, int L,
                   int H, int vocab, int type_vocab, float eps, hipStream_t s, const int* cu) {
-  if (M <= 0) return 0;
-  if (H % 4 || H > 2048) OM_FAIL("hidden size must be a multiple of 4 and <= 2048");
-#define OM_EB(TT) return launch_ln_bwd<TT, 1>(dy, nullptr, g, nullptr, dg, db, M, H, eps, ids, type_ids, word, pos, type, dword, dpos, dtype_, L, vocab, type_vocab, s, 0, nullptr, nullptr, 0.f, 0, nullptr, nullptr, nullptr, nullptr, cu)
-  if (dtype == OM_BF16) OM_EB(bf16_t);
-  if (dtype == OM_F16) OM_EB(f16_t);
-  OM_EB(float);
-#undef OM_EB
+  const RowBwdPlan p = row_bwd_plan(dtype, 1, M, H, L, false, false, false, row_switches());
+  if (p.error) OM_FAIL(p.error);
+  if (p.empty) return 0;
+  LnBwdArgs a;
+  a.dy = dy; a.g = g; a.dg = dg; a.db = db; a.M = M; a.H = H; a.eps = eps;
+  a.ids = ids; a.type_ids = type_ids; a.word = word; a.pos = pos; a.type = type; a.dword = dword; a.dpos = dpos; a.dtype_ = dtype_;
+  a.L = L; a.vocab = vocab; a.type_vocab = type_vocab; a.cu = cu;
+  return launch_ln_bwd<1>(dtype, p, a, s);
 }
 
 // rows [*first, M) of a row-major tensor <- 0 (packed rows: the pad rows behind the last sequence; `first` lives on the device)
@@ -682,7 +687,22 @@ int omk_l2norm_bwd(const float* x, const float* dy, float* dx, int64_t M, int D,
 }
 
 // ---- test hooks of the row kernels (include/openmatch_hip.h): argument checks, then the launcher as it is ----
-#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
+// host only: the note word a backward entry would store at the current switches (0: nothing to do; -1: refused, the entry's text in
+// om_last_error), and out = {grid, threads per block, dynamic LDS bytes, what *partial_blocks receives}
+extern "C" int om_debug_row_bwd_plan(int dtype, int mode, int64_t M, int H, int L, int has_x32, int has_dy32, int has_partial, int64_t out[4]) {
+  omk_row_note(0);
+  const char* why = nullptr;
+  if (!out) why = "null argument";
+  else if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) why = "dtype must be OM_F32, OM_BF16 or OM_F16";
+  else if (mode != 0 && mode != 1) why = "mode must be 0 or 1 (the embedding backward)";
+  const RowBwdPlan p = why ? RowBwdPlan{} : row_bwd_plan(dtype, mode, M, H, L, has_x32 != 0, has_dy32 != 0, has_partial != 0, row_switches());
+  if (why || p.error) {
+    om_set_error(std::string("om_debug_row_bwd_plan: ") + (why ? why : p.error));
+    return -1;
+  }
+  out[0] = p.grid; out[1] = 64 * p.waves; out[2] = p.lds; out[3] = p.partial_blocks;
+  return p.empty ? 0 : row_bwd_word(p);
+}
 extern "C" int om_debug_norm_bwd(int dtype, const void* dy, const void* x, const float* g, void* dx, float* dg, float* db, int64_t M, int H,
                                  float eps, int rms, const void* add, void* stream) {
   omk_row_note(0);
@@ -732,7 +752,6 @@ extern "C" int om_debug_dropout(int dtype, const void* x, void* y, int64_t n, fl
   OM_DBG_DTYPE("om_debug_dropout");
   return omk_dropout(dtype, x, y, n, p, seed, (hipStream_t)stream, rows, H);
 }
-#undef OM_DBG_DTYPE
 
 // small f32 contractions (LinearHead backward, [B,768]-sized):
 //   nn: C[i,c] = sum_j A[i,j] * Bm[j,c]      tn: C[j,c] = sum_i A[i,j] * Bm[i,c]
@@ -1451,7 +1470,6 @@ int omk_t5_bias_bwd(const float* drel, const int* lut, float* dtable, int L, int
 }
 
 // ---- test hooks of the T5 kernels (include/openmatch_hip.h): argument checks, then the launcher as it is ----
-#define OM_DBG_DTYPE(what) if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL(what ": dtype must be OM_F32, OM_BF16 or OM_F16")
 extern "C" int om_debug_t5_act_fwd(int dtype, const void* f, const void* f2, void* g, int64_t n, int kind, void* stream) {
   if (!f || !g || (kind && !f2)) OM_FAIL("om_debug_t5_act_fwd: null argument");
   OM_DBG_DTYPE("om_debug_t5_act_fwd");
@@ -1475,4 +1493,3 @@ extern "C" int om_debug_t5_bias_bwd(const float* drel, const int* lut, float* dt
   if (L < 1 || heads < 1) OM_FAIL("om_debug_t5_bias_bwd: L and heads must be at least 1");
   return omk_t5_bias_bwd(drel, lut, dtable, L, heads, (hipStream_t)stream);
 }
-#undef OM_DBG_DTYPE

@@ -16,7 +16,7 @@
 //   - the forward takes the f32 tail for pooling "first" in every 16-bit run with layers, the backward for bert16 alone;
 //   - a backward may reuse the forward's transposes under bit 1 of the lane word alone: the forward's other conditions (16 bits, layers)
 //     are in what the lane remembers of that forward (train.hip WgradLane::wt_*).
-// Bit 3 of OM_OPT_TRAIN_WGRAD_STREAM is not read here: the LayerNorm-backward row kernel's own dispatch reads it (train_kernels.hip).
+// Bit 3 of OM_OPT_TRAIN_WGRAD_STREAM is not read here: the LayerNorm-backward row kernel's own plan reads it (row_plan.h: row_switches).
 #pragma once
 #include <algorithm>
 

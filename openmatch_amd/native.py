@@ -227,6 +227,8 @@ _SIGNATURES = {
     "om_debug_attn_drop_keep": (c_int, [C.c_uint64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float]),
     "om_debug_wave_sum_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "om_debug_row_kernel_last": (c_int, []),
+    "om_debug_row_fwd_plan": (c_int, [c_int, c_int, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "om_debug_row_bwd_plan": (c_int, [c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_int64)]),
     "om_debug_layernorm": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p,
                                    c_int, c_void_p]),
     "om_debug_layernorm_f32out": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int,

@@ -60,6 +60,10 @@ kernel variant -> GPU cases
   dropout_kernel                          test_dropout_*;  ln_fold_kernel: test_ln_fold;  ln_stats_reduce_kernel: test_ln_stats_reduce
 Every expected variant comes from a table of this file (FWD_X8_NV, FWD_GENERIC_MV, BWD_VARIANT, EMBED_VARIANT) that
 test_variant_tables_match_the_launchers_conditions checks against a plain restatement of the launchers' conditions, without a GPU.
+That restatement (launcher_fwd, launcher_bwd) is held to the library's own plan (csrc/row_plan.h) through the host-only hooks
+om_debug_row_fwd_plan / om_debug_row_bwd_plan by test_forward_restatement_matches_the_plan_hook and
+test_backward_restatement_matches_the_plan_hook, also without a GPU; and every GPU case that asserts the noted word asserts that the
+plan hook, asked with the case's own pitches and pointer alignments, answers the same word (PLANNED).
 
 Negative controls (test_bounds_admit_an_emulated_kernel_and_reject_the_controls, CPU, against the reference in float32 in the
 kernel's order, rounded to the storage type); worst error / bound of each at the shape where it is smallest, recorded 2026-10-18:
@@ -136,7 +140,7 @@ def bwd_word(nv, mode, waves, pf, partial):
 
 
 def launcher_fwd(launcher, dtype, H, ldx, ldy, x_al=True, y_al=True, lo_al=True, g_al=True, plane=False, lo8=False):
-    """A plain restatement of the four forward launchers' conditions (csrc/elementwise.hip): the note word, or the refusal's text."""
+    """A plain restatement of the four forward launchers' conditions (row_fwd_plan, csrc/row_plan.h): the note word, or the refusal's text."""
     if lo8 and not (plane and dtype == F16 and H % 256 == 0 and ldx % H == 0):
         return "eight-bit second plane"
     if H % 4 or H > 2048:
@@ -163,7 +167,7 @@ def launcher_fwd(launcher, dtype, H, ldx, ldy, x_al=True, y_al=True, lo_al=True,
 
 
 def launcher_bwd(dtype, H, mode, x32=False, dy32=False, partial=False, pf_off=False):
-    """launch_ln_bwd's conditions (csrc/train_kernels.hip) restated."""
+    """row_bwd_plan's conditions (csrc/row_plan.h) restated."""
     waves = 8 if H <= 1024 and mode == 0 else 4
     pf = mode == 0 and dtype != F32 and x32 and not dy32 and H <= 768 and not pf_off
     nv = 3 if H <= 768 and mode == 0 else 4 if H <= 1024 else 8
@@ -172,6 +176,32 @@ def launcher_bwd(dtype, H, mode, x32=False, dy32=False, partial=False, pf_off=Fa
 
 def last():
     return N.lib().om_debug_row_kernel_last()
+
+
+ENTRY = {"layernorm": 0, "f32out": 1, "from_f32": 2, "dual": 3}      # om_debug_row_fwd_plan's entry
+PLANNED = NS(word=None)      # what the plan hook returned for the arguments of this file's last launcher call (call_fwd, call_norm_bwd, ...)
+
+
+def plan_fwd(launcher, dtype, M, H, ldx, ldy, data_al=True, param_al=True, plane=False, lo8=False):
+    """om_debug_row_fwd_plan (host only): the note word the launcher would store, 0 for nothing to do, or the refusal's text"""
+    lib = N.lib()
+    w = lib.om_debug_row_fwd_plan(ENTRY[launcher], dtype, M, H, ldx, ldy, int(data_al), int(param_al), int(plane), int(lo8))
+    assert w >= -1 and last() == 0
+    return w if w >= 0 else lib.om_last_error().decode()
+
+
+def plan_bwd(dtype, mode, M, H, L=1, x32=False, dy32=False, partial=False):
+    """om_debug_row_bwd_plan (host only, at the current switches): (word, [grid, threads, LDS bytes, partial_blocks]), or the refusal's text"""
+    lib = N.lib()
+    out = (C.c_int64 * 4)(-1, -1, -1, -1)
+    w = lib.om_debug_row_bwd_plan(dtype, mode, M, H, L, int(x32), int(dy32), int(partial), out)
+    assert w >= -1 and last() == 0
+    return (w, list(out)) if w >= 0 else lib.om_last_error().decode()
+
+
+def agrees(want, got):
+    """a restated launcher's answer (a word, or a piece of the refusal's text) against a plan hook's (the word, or the whole text)"""
+    return isinstance(got, str) and want in got if isinstance(want, str) else (not isinstance(got, str) and want == got)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -668,10 +698,124 @@ REFUSALS = [
 FAKE = 0x7000_0000_0000      # made-up 16-byte aligned addresses: the refusals come before any launch and read no pointer
 
 
+def test_forward_restatement_matches_the_plan_hook():
+    """launcher_fwd, to which the variant tables are held, is itself held to csrc/row_plan.h through om_debug_row_fwd_plan, without a
+    device: the whole grid of the GPU cases, the plane and eight-bit cases, every refusal with its text, every alignment input flipped
+    alone, and M = 0"""
+    n = 0
+
+    def check(launcher, dtype, H, ldx, ldy, x_al=True, y_al=True, lo_al=True, g_al=True, plane=False, lo8=False, M=4):
+        nonlocal n
+        want = launcher_fwd(launcher, dtype, H, ldx, ldy, x_al=x_al, y_al=y_al, lo_al=lo_al, g_al=g_al, plane=plane, lo8=lo8)
+        got = plan_fwd(launcher, dtype, M, H, ldx, ldy, data_al=x_al and y_al and (lo_al or not plane), param_al=g_al, plane=plane, lo8=lo8)
+        assert agrees(want, got), (launcher, NAME[dtype], H, ldx, ldy, x_al, y_al, lo_al, g_al, plane, lo8, want, got)
+        n += 1
+        return got
+
+    for launcher in ENTRY:
+        for dtype in DTYPES:
+            for H in FWD_H:
+                for tag, ldx, ldy, x_off, g_off in fwd_cases(launcher, dtype, H):
+                    got = check(launcher, dtype, H, ldx, ldy, x_al=(x_off * (2 if dtype != F32 else 4)) % 16 == 0, g_al=(g_off * 4) % 16 == 0)
+                    if not (launcher == "dual" and dtype == F32):
+                        assert got == fwd_expected(launcher, dtype, H, tag)
+    for dtype in (BF16, F16):
+        for H in FWD_X8_NV:
+            for launcher in ("layernorm", "f32out"):
+                check(launcher, dtype, H, H, H, plane=True)
+                check(launcher, dtype, H, H + 4, H, plane=True)
+        for H in (256, 512):
+            for launcher in ("layernorm", "f32out"):
+                check(launcher, dtype, H, H, H, plane=True, lo8=True)
+                check(launcher, dtype, H, 32 * H, H, plane=True, lo8=True)
+    check("layernorm", F32, 2052, 2052, 2052)
+    check("f32out", F32, 6, 6, 6)
+    for launcher, kw, text in REFUSALS:
+        H = kw["H"]
+        got = check(launcher, kw["dtype"], H, kw.get("ldx", H), H, plane=bool(kw.get("plane")), lo8=bool(kw.get("lo8")))
+        assert isinstance(got, str) and text.decode() in got and got.startswith("om_debug_row_fwd_plan: ")
+    # every alignment input flipped alone: with the x8 body's other conditions met it alone decides (the tables' H = 256 and 1024)
+    for H in (256, 1024):
+        for launcher in ("layernorm", "f32out"):
+            for dtype in DTYPES:
+                for plane in (False, True):
+                    base = check(launcher, dtype, H, H, H, plane=plane)
+                    flips = [dict(x_al=False), dict(y_al=False), dict(g_al=False), dict(ldx=H + 4), dict(ldy=H + 4), dict(ldy=H + 2)]
+                    flips += [dict(lo_al=False)] if plane else []
+                    for flip in flips:
+                        kw = dict(ldx=H, ldy=H, plane=plane)
+                        kw.update(flip)
+                        got = check(launcher, dtype, H, **kw)
+                        x8 = dtype == BF16 or (dtype == F16 and plane)
+                        keeps = flip == dict(ldy=H + 4) and launcher == "f32out"          # f32 output rows: whole vectors of FOUR elements
+                        assert (got == base) == (keeps or not x8), (launcher, NAME[dtype], H, plane, flip)
+    # nothing to do: after the eight-bit and the width refusals, before everything else (dual: before its format check)
+    for launcher in ENTRY:
+        for dtype in DTYPES:
+            assert plan_fwd(launcher, dtype, 0, 256, 256, 256) == 0 == plan_fwd(launcher, dtype, -3, 2048, 2052, 2052, data_al=False, param_al=False)
+            assert "multiple of 4 and <= 2048" in plan_fwd(launcher, dtype, 0, 2052, 2052, 2052)
+    assert plan_fwd("dual", F32, 0, 256, 256, 256) == 0 and "a 16-bit output format" in plan_fwd("dual", F32, 1, 256, 256, 256)
+    assert "eight-bit second plane" in plan_fwd("layernorm", BF16, 0, 256, 256, 256, plane=True, lo8=True)
+    assert "eight-bit second plane" in plan_fwd("f32out", BF16, 0, 2304, 2304, 2304, plane=True, lo8=True)     # (before the width)
+    assert "two-plane LayerNorm input" in plan_fwd("layernorm", F16, 1, 256, 260, 256, plane=True) and plan_fwd("layernorm", F16, 0, 256, 260, 256, plane=True) == 0
+    lib = N.lib()
+    assert lib.om_debug_row_fwd_plan(4, BF16, 1, 8, 8, 8, 1, 1, 0, 0) == -1 and b"entry must be" in lib.om_last_error()
+    assert lib.om_debug_row_fwd_plan(0, 7, 1, 8, 8, 8, 1, 1, 0, 0) == -1 and b"dtype must be" in lib.om_last_error()
+    assert n > 4 * 3 * len(FWD_H) * 5
+
+
+def test_backward_restatement_matches_the_plan_hook():
+    """launcher_bwd against csrc/row_plan.h through om_debug_row_bwd_plan, without a device: the variant at every combination the GPU
+    cases run and with switch bit 3 either way, the grids, the LDS bytes and the refusals"""
+    lib = N.lib()
+    old = lib.om_debug_option_value(N.OPT_TRAIN_WGRAD_STREAM)
+    for pf_off in (False, True):
+        with option(N.OPT_TRAIN_WGRAD_STREAM, (old | 8) if pf_off else (old & ~8)):
+            for dtype in DTYPES:
+                for H in BWD_H:
+                    nv, waves = BWD_VARIANT[H]
+                    for x32 in (False, True):
+                        for dy32 in (False, True):
+                            for partial in (False, True):
+                                word, out = plan_bwd(dtype, 0, 33, H, x32=x32, dy32=dy32, partial=partial)
+                                assert word == launcher_bwd(dtype, H, 0, x32, dy32, partial, pf_off) == bwd_expected(dtype, H, x32, dy32, partial, pf_off)
+                                assert out == [(33 + waves - 1) // waves, 64 * waves, 2 * waves * H * 4, (33 + waves - 1) // waves]
+                for H, (nv, waves) in EMBED_VARIANT.items():
+                    word, out = plan_bwd(dtype, 1, 10, H, L=5, x32=True, partial=True)      # MODE 1 reads neither
+                    assert word == launcher_bwd(dtype, H, 1, x32=True, partial=True, pf_off=pf_off) == bwd_word(nv, 1, waves, False, False)
+                    assert out == [5 * 51, 64 * waves, 2 * waves * H * 4, 3]
+    for M in (1, 7, 8, 9, 33, 4096, 4097):
+        for L in (1, 128, 256, 300):
+            for H in BWD_H:
+                waves = BWD_VARIANT[H][1]
+                out = plan_bwd(F32, 0, M, H, L=L)[1]
+                assert out[0] == out[3] == min((M + waves - 1) // waves, 512) and out[2] == 2 * waves * H * 4
+            for H in EMBED_VARIANT:
+                out = plan_bwd(BF16, 1, M * L, H, L=L)[1]                  # M sequences of L positions
+                assert out[0] == L * max(256 // L, 1) and out[1] == 256 and out[2] == 2 * 4 * H * 4
+                assert out[3] == min((M * L + 3) // 4, 512)              # the MODE 0 figure, though MODE 1 launches out[0] blocks
+            if L > 1:
+                assert "embedding backward: M must be B * L" in plan_bwd(F16, 1, M * L + 1, 768, L=L)
+                assert plan_bwd(F16, 0, M * L + 1, 768, L=L)[0] == bwd_word(3, 0, 8, False, False)      # MODE 0 does not read L
+    assert "M must be B * L" in plan_bwd(F32, 1, 4, 8, L=0) and "M must be B * L" in plan_bwd(F32, 1, 4, 8, L=-2)
+    # nothing to do comes first, then the width
+    for mode in (0, 1):
+        assert plan_bwd(BF16, mode, 0, 768, L=3) == (0, [0, 0, 0, 0]) == plan_bwd(BF16, mode, -1, 2052, L=0)
+        for H in (6, 2052):
+            assert "multiple of 4 and <= 2048" in plan_bwd(BF16, mode, 4, H, L=3)
+    out = (C.c_int64 * 4)()
+    assert lib.om_debug_row_bwd_plan(BF16, 0, 1, 8, 1, 0, 0, 0, None) == -1 and b"null argument" in lib.om_last_error()
+    assert lib.om_debug_row_bwd_plan(7, 0, 1, 8, 1, 0, 0, 0, out) == -1 and b"dtype must be" in lib.om_last_error()
+    assert lib.om_debug_row_bwd_plan(BF16, 2, 1, 8, 1, 0, 0, 0, out) == -1 and b"mode must be" in lib.om_last_error()
+
+
 def call_fwd(launcher, dtype, x, ldx, y, ldy, g, b, M, H, rms=0, x_lo=None, rows=None, lo8=0, y32=None, eps=EPS, stream=None):
     lib = N.lib()
     v = lambda a: a if isinstance(a, C.c_void_p) else N.ptr(a)
     s = stream if stream is not None else N.stream_ptr()
+    al = lambda *ps: all((v(p).value or 0) % 16 == 0 for p in ps)
+    w = lib.om_debug_row_fwd_plan(ENTRY[launcher], dtype, M, H, ldx, ldy, al(x, y, x_lo), al(g, b), x_lo is not None, lo8)
+    PLANNED.word = w if w >= 0 else lib.om_last_error()       # (first: the launcher's own refusal is what om_last_error holds afterwards)
     if launcher == "layernorm":
         return lib.om_debug_layernorm(dtype, v(x), ldx, v(y), ldy, v(g), v(b), M, H, eps, rms, v(x_lo), lo8, s)
     if launcher == "f32out":
@@ -692,13 +836,13 @@ def test_forward_refusals(launcher, kw, text):
     rc = call_fwd(launcher, dtype, p(1), ldx, p(2), H, p(3), p(4), 4, H, x_lo=p(5) if kw.get("plane") else None, lo8=kw.get("lo8", 0), y32=p(6),
                   stream=C.c_void_p(0))
     assert rc != 0 and text in lib.om_last_error(), lib.om_last_error()
-    assert last() == 0
+    assert last() == 0 and isinstance(PLANNED.word, bytes) and text in PLANNED.word
     assert launcher_fwd(launcher, dtype, H, ldx, H, plane=bool(kw.get("plane")), lo8=bool(kw.get("lo8"))).encode() in text + b" "
 
 
 def test_hooks_check_their_arguments():
     lib = N.lib()
-    names = ["om_debug_row_kernel_last", "om_debug_layernorm", "om_debug_layernorm_f32out", "om_debug_layernorm_from_f32", "om_debug_layernorm_dual",
+    names = ["om_debug_row_kernel_last", "om_debug_row_fwd_plan", "om_debug_row_bwd_plan", "om_debug_layernorm", "om_debug_layernorm_f32out", "om_debug_layernorm_from_f32", "om_debug_layernorm_dual",
              "om_debug_norm_bwd", "om_debug_ln_bwd_drop", "om_debug_ln_param_reduce", "om_debug_embed_bwd", "om_debug_pool", "om_debug_pool_bwd",
              "om_debug_l2norm", "om_debug_l2norm_bwd", "om_debug_colsum", "om_debug_dropout", "om_debug_ln_fold", "om_debug_ln_stats_reduce"]
     for name in names:
@@ -788,7 +932,7 @@ def run_forward(launcher, dtype, H, M, ldx, ldy, x_off, g_off, rms, has_b, seed,
     rc = call_fwd(launcher, dtype, xv, ldx, y, ldy, g, b if has_b else None, M, H, rms=rms, y32=y32)
     torch.cuda.synchronize()
     assert rc == 0, N.lib().om_last_error()
-    assert last() == expect, (hex(last()), hex(expect))
+    assert last() == expect == PLANNED.word, (hex(last()), hex(expect), PLANNED.word)
     R = ln_forward(x.double(), g.double(), b.double() if has_b else None, EPS, rms)
     bound = ln_fwd_bound(R, H, out_dt)
     w = worst(y[:M, :H], R.y, bound)
@@ -848,7 +992,7 @@ def test_two_plane(dtype, H):
         y = sentinel_rows(M + GUARD, ld, out_dt)
         assert call_fwd(launcher, dtype, hv, ld, y, ld, g, None if rms else b, M, H, rms=rms, x_lo=lv) == 0, N.lib().om_last_error()
         torch.cuda.synchronize()
-        assert last() == fwd_word("fwd_x8", FWD_X8_NV[H], dtype, out_dt, True)
+        assert last() == fwd_word("fwd_x8", FWD_X8_NV[H], dtype, out_dt, True) == PLANNED.word
         R = ln_forward(x64, g.double(), None if rms else b.double(), EPS, rms)
         assert worst(y[:M, :H], R.y, ln_fwd_bound(R, H, out_dt, xin_err=u * x64.abs())) <= 1.0
         assert is_sentinel(y[M:], out_dt) and is_sentinel(y[:M, H:], out_dt)
@@ -877,7 +1021,7 @@ def test_eight_bit_plane(H):
         y = sentinel_rows(M + GUARD, H, out_dt)
         assert call_fwd(launcher, F16, hi, H, y, H, g, b, M, H, x_lo=blob, lo8=1) == 0, N.lib().om_last_error()
         torch.cuda.synchronize()
-        assert last() == fwd_word("fwd_x8", H // 256, F16, out_dt, True, True)
+        assert last() == fwd_word("fwd_x8", H // 256, F16, out_dt, True, True) == PLANNED.word
         assert worst(y[:M], R.y, ln_fwd_bound(R, H, out_dt, xin_err=u * x64.abs())) <= 1.0 and is_sentinel(y[M:], out_dt)
         if out_dt == F32:      # the plane is read where the port says: without it the f32 output leaves the bound
             assert worst(y[:M], ln_forward(hi.double(), g.double(), b.double(), EPS, 0).y, ln_fwd_bound(R, H, F32, xin_err=u * x64.abs())) > 1.0
@@ -885,7 +1029,7 @@ def test_eight_bit_plane(H):
     y = sentinel_rows(rows.numel() + GUARD, H, F32)
     assert call_fwd("f32out", F16, hi, L * H, y, H, g, b, rows.numel(), H, x_lo=blob, rows=rows, lo8=1) == 0, N.lib().om_last_error()
     torch.cuda.synchronize()
-    assert last() == fwd_word("fwd_x8", H // 256, F16, F32, True, True)
+    assert last() == fwd_word("fwd_x8", H // 256, F16, F32, True, True) == PLANNED.word
     tok = rows.long() * L
     Rg = ln_forward(x64[tok], g.double(), b.double(), EPS, 0)
     assert worst(y[:rows.numel()], Rg.y, ln_fwd_bound(Rg, H, F32, xin_err=u * x64[tok].abs())) <= 1.0 and is_sentinel(y[rows.numel():], F32)
@@ -904,7 +1048,7 @@ def test_row_gather(dtype, H):
     y = sentinel_rows(M + GUARD, H, F32)
     assert call_fwd("f32out", dtype, x, H, y, H, g, b, M, H, rows=rows) == 0, N.lib().om_last_error()
     torch.cuda.synchronize()
-    assert last() == fwd_expected("f32out", dtype, H, "dense")
+    assert last() == fwd_expected("f32out", dtype, H, "dense") == PLANNED.word
     R = ln_forward(x.double()[rows.long()], g.double(), b.double(), EPS, 0)
     assert worst(y[:M], R.y, ln_fwd_bound(R, H, F32)) <= 1.0 and is_sentinel(y[M:], F32)
     if dtype != F32 and H in FWD_X8_NV:
@@ -912,12 +1056,13 @@ def test_row_gather(dtype, H):
         y = sentinel_rows(M + GUARD, H, F32)
         assert call_fwd("f32out", dtype, hi, H, y, H, g, b, M, H, x_lo=lo, rows=rows) == 0, N.lib().om_last_error()
         torch.cuda.synchronize()
-        assert last() == fwd_word("fwd_x8", FWD_X8_NV[H], dtype, F32, True)
+        assert last() == fwd_word("fwd_x8", FWD_X8_NV[H], dtype, F32, True) == PLANNED.word
         R = ln_forward(x64[rows.long()], g.double(), b.double(), EPS, 0)
         assert worst(y[:M], R.y, ln_fwd_bound(R, H, F32, xin_err=u * x64[rows.long()].abs())) <= 1.0 and is_sentinel(y[M:], F32)
 
 
 def call_norm_bwd(dtype, dy, x, g, dx, dg, db, M, H, rms, add):
+    PLANNED.word = plan_bwd(dtype, 0, M, H)[0]
     rc = N.lib().om_debug_norm_bwd(dtype, N.ptr(dy), N.ptr(x), N.ptr(g), N.ptr(dx), N.ptr(dg), N.ptr(db), M, H, EPS, rms, N.ptr(add), N.stream_ptr())
     torch.cuda.synchronize()
     return rc
@@ -938,7 +1083,7 @@ def test_norm_bwd(dtype, H, M):
             dx = sentinel_rows(M + GUARD, H, dtype)
             dg, db = acc_buffer(H), acc_buffer(H) if not (rms and use_add) else None
             assert call_norm_bwd(dtype, dy, x, g, dx, dg, db, M, H, rms, add if use_add else None) == 0, N.lib().om_last_error()
-            assert last() == bwd_word(nv, 0, waves, False, False)
+            assert last() == bwd_word(nv, 0, waves, False, False) == PLANNED.word
             R = ln_backward(x.double(), dy.double(), g.double(), EPS, rms, add.double() if use_add else None)
             e_dx, e_dg, e_db = ln_bwd_bound(R, H, M, dtype)
             ws = (worst(dx[:M], R.dx, e_dx), worst(dg[:H], R.dg + PREFILL, e_dg), worst(db[:H], R.db + PREFILL, e_db) if db is not None else 0.0)
@@ -953,6 +1098,7 @@ def test_norm_bwd(dtype, H, M):
 
 def call_bwd_drop(dtype, dy, x, g, dx, dx_drop, p, seed, dg, db, M, H, dy32, x32, partial, drop_rows):
     blocks = C.c_int(-1)
+    PLANNED.word, PLANNED.out = plan_bwd(dtype, 0, M, H, x32=x32 is not None, dy32=dy32 is not None, partial=partial is not None)
     rc = N.lib().om_debug_ln_bwd_drop(dtype, N.ptr(dy), N.ptr(x), N.ptr(g), N.ptr(dx), N.ptr(dx_drop), p, seed, N.ptr(dg), N.ptr(db), M, H, EPS,
                                       N.ptr(dy32), N.ptr(x32), N.ptr(partial), C.byref(blocks), N.ptr(drop_rows), N.stream_ptr())
     torch.cuda.synchronize()
@@ -1028,6 +1174,7 @@ def _bwd_drop_once(dtype, dy, x, g, p, seed, M, H, dy32, x32, use_partial, rows)
                                partial, rows)
     assert rc == 0, N.lib().om_last_error()
     note = last()
+    assert note == PLANNED.word and blocks == PLANNED.out[3] == PLANNED.out[0]
     if use_partial:
         assert bool((partial[blocks * 2 * H:] == GUARD_F).all())               # exactly `blocks` blocks wrote
         assert reduce_sites([(partial, dg, db, blocks)], H) == 0
@@ -1124,7 +1271,7 @@ def test_embed_bwd(dtype, L, B, H, var):
     torch.cuda.synchronize()
     assert rc == 0, N.lib().om_last_error()
     nv, waves = EMBED_VARIANT[H]
-    assert last() == bwd_word(nv, 1, waves, False, False)
+    assert last() == bwd_word(nv, 1, waves, False, False) == plan_bwd(dtype, 1, M, H, L=L)[0]
     d = lambda t: None if t is None else t.double()
     R = embed_backward(d(dy_pad), ids, tts, d(word), d(pos), d(typ), d(g), EPS, L, vocab, tv, live)
     bw, bp, bt, e_dg, e_db = embed_bwd_bound(R, H, M, d(word), d(pos), d(typ))
