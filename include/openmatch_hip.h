@@ -268,7 +268,7 @@ int om_debug_attention_causal_packed(int dtype, const void* qkv, void* ctx, cons
                                      int n_kv_heads, float scale, void* stream);
 int om_debug_rope_gqa_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling,
                            const int* row_map, void* stream);
-/* The same hooks with a head width (csrc/attention_causal128.hip): head_dim 64 runs the kernels above, head_dim 128 the 128-wide ones
+/* The same hooks with a head width: head_dim 64 runs the kernels above, head_dim 128 the 128-wide ones
  * over qkv [rows, (n_heads + 2 n_kv_heads) * 128] and ctx [rows, n_heads * 128].  om_debug_qknorm_rope: the per-head RMSNorm of the q
  * and k heads (x * rsqrt(mean(x^2) + eps) * g; q_norm_g / k_norm_g device arrays [head_dim] f32, NULL: no norm on that side) and the
  * rotary positions in one pass, in place; inv_freq is a HOST array of head_dim / 2 frequencies.  _packed / _rows as above. */
@@ -280,7 +280,7 @@ int om_debug_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int n_heads, in
                          const float* k_norm_g, float eps, const float* inv_freq, float scaling, void* stream);
 int om_debug_qknorm_rope_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
                               const float* k_norm_g, float eps, const float* inv_freq, float scaling, const int* row_map, void* stream);
-/* Test hooks of the Gemma3 stack.  om_debug_attention_gqa_d256 (csrc/attention_d256.hip): bidirectional grouped-query attention over heads
+/* Test hooks of the Gemma3 stack.  om_debug_attention_gqa_d256 (kernels: csrc/attention_d256.hip): bidirectional grouped-query attention over heads
  * of 256 columns, qkv [rows, (n_heads + 2 n_kv_heads) * 256], ctx [rows, n_heads * 256]; key k visible from query q iff mask[b][k] != 0
  * and, for 0 < w < L - 1, |q - k| <= w (w <= 0 or w >= L - 1: full attention).  om_debug_qknorm_rope_d256: om_debug_qknorm_rope at
  * head_dim 256 in Gemma3's form -- g = 1 + weight from the caller, the normalised value not rounded before the weight multiply;
@@ -321,6 +321,18 @@ int om_debug_attention_last(void);
  * attn_plan_fwd; has_*: whether the optional pointer is given; w: the half window) -- family | key tiles << 8, 0 when nothing would
  * launch (an empty batch), -1 for a refusal with its reason in om_last_error.  Leaves the last-launch words alone. */
 int om_debug_attention_plan(int dtype, int64_t B, int L, int H, int heads, int has_bias, float drop_p, int has_kmax, int has_cu, int w);
+/* Grouped-query attention (csrc/kernels.h omk_attention_gqa, the one entry behind the six om_debug_attention_causal* / _gqa_d256* hooks
+ * above and the Llama / Qwen2, Qwen3 and Gemma3 forwards): the families of its planner (csrc/attn_plan.h attn_plan_gqa; DESIGN.md 4c
+ * lists the rules) and, host only, what it would launch -- causal: the triangle (head_dim 64 or 128, w must be <= 0), else the
+ * bidirectional form (head_dim 256, w the half window); packed: rows packed by sequence; has_ext: whether kmax (padded rows, optional)
+ * or cu (packed rows, required) is given.  out = {family, body (1 float32, 0 16-bit), grid x, grid y, dynamic LDS bytes}.  Returns 0,
+ * every word zero when nothing would launch (an empty batch); -1 for a refusal with its reason in om_last_error. */
+#define OM_ATTN_GQA_FAMILY_CAUSAL64 1   /* attention_causal16 / 32_kernel and their _packed forms                              */
+#define OM_ATTN_GQA_FAMILY_CAUSAL128 2  /* attention_causal16 / 32_d128_kernel                                                 */
+#define OM_ATTN_GQA_FAMILY_FULL256 3    /* attention_d256_16 / 32_kernel<AttnFull>: every unmasked key                         */
+#define OM_ATTN_GQA_FAMILY_BAND256 4    /* attention_d256_16 / 32_kernel<AttnBand>: 0 < w < L - 1 on the padded L              */
+int om_debug_attention_gqa_plan(int dtype, int64_t B, int L, int n_heads, int n_kv_heads, int head_dim, int causal, int w, int packed,
+                                int has_ext, int64_t out[5]);
 /* The same pair for the attention backward of a training step (csrc/train_kernels.h omk_attention_bwd, attn_plan_bwd; packed: the
  * step runs over packed rows).  The last-launch word is the PROCESS's, not the thread's: torch's autograd engine runs a backward on
  * a thread of its own. */

@@ -1,7 +1,9 @@
 // Causal grouped-query attention of the decoder-only backbones (HF:models/llama/modeling_llama.py, HF:models/qwen2/modeling_qwen2.py),
 // and the rotary positions of every backbone that has them (gfx950), head_dim 64, inference.  Here: the two causal kernels -- wrappers of
-// the shared chunked bodies (attn_chunked.h) -- their launch and test hooks, and the ONE rotary kernel with its table cache and both of
-// its entries, omk_rope (ModernBERT and NomicBERT, fused [M, 3H]) and omk_rope_gqa (grouped projection).
+// the shared chunked bodies (attn_chunked.h) -- and their launcher, the ONE rotary kernel with its table cache and both of its entries,
+// omk_rope (ModernBERT and NomicBERT, fused [M, 3H]) and omk_rope_gqa (grouped projection), and, at the end, the one grouped-query
+// attention entry of all three head widths, omk_attention_gqa -- plan (attn_plan.h attn_plan_gqa), switch on the family, launch -- with
+// the test hooks of all three (the 128- and 256-wide kernels and their launchers: attention_causal128.hip, attention_d256.hip).
 //
 //   * Rotary positions applied IN PLACE to the q and k heads of a projection whose rows hold (q heads | k heads | v heads) of 64
 //     columns (apply_rotary_pos_emb with rotate_half: pairs (i, i + 32) of each head, position = row % L as HF's arange(L) whatever
@@ -15,7 +17,7 @@
 //     K / Q loads: K reaches LDS by DMA there, untouched by the vector unit, so a fused rotation would have to rewrite K in LDS once
 //     per (query block, key chunk) -- see DESIGN.md for the measured cost of the pass.
 //
-//   * omk_attention_causal: softmax(Q K^T * scale + mask) V where key k is visible from query q iff k <= q and k is unmasked;
+//   * The causal kernels (omk_attention_causal64; launch only): softmax(Q K^T * scale + mask) V where key k is visible from query q iff k <= q and k is unmasked;
 //     query head h reads K / V head h / (n_heads / n_kv) (HF repeat_kv).  One workgroup owns 128 queries of one (sequence, query
 //     head) and walks the 128-key chunks from key 0 up to its own diagonal chunk (clipped to kmax[b]: keys at or past it are
 //     padding): at 1 024 tokens 4.5 chunks per block on average instead of eight.  The triangle is a select per score in the
@@ -24,7 +26,7 @@
 //     (one workgroup per (sequence, query head, query block)); a form that serves a whole K / V group from one fetch has not been
 //     built or measured.
 //
-//   * Packed rows (om_causal_encoder_forward_packed): omk_attention_causal_packed runs the same two bodies with an AttnRows filled
+//   * Packed rows (om_causal_encoder_forward_packed): the packed kernels run the same two bodies with an AttnRows filled
 //     from cu -- sequence b is rows cu[b] .. cu[b + 1] - 1, the body's L is that row count, the mask keeps its [B, L] pitch -- and
 //     omk_rope_gqa with a row_map takes a row's position from row_map[t] % L (the column omk_pack_rows recorded) instead of row % L.
 //     omk_rope takes the same row_map (NomicBERT under om_encoder_forward_packed).
@@ -34,6 +36,9 @@
 #include <vector>
 
 #include "attn_chunked_wide.h"
+#include "attn_plan.h"
+
+#define RUN(expr) do { if (expr) return 1; } while (0)
 
 namespace {
 
@@ -70,29 +75,14 @@ int omk_rope_table(const float* inv_freq, int n, float scaling, const float2** o
 
 namespace {
 
-template <typename T> struct RopeIO;
-template <> struct RopeIO<float> {
-  __device__ static inline void load4(const float* p, float (&v)[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  __device__ static inline void store4(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <typename T> struct RopeIO16 {
-  __device__ static inline void load4(const T* p, float (&v)[4]) {
-    const uint2 t = *(const uint2*)p;
-    v[0] = Half16<T>::lo(t.x); v[1] = Half16<T>::hi(t.x); v[2] = Half16<T>::lo(t.y); v[3] = Half16<T>::hi(t.y);
-  }
-  __device__ static inline void store4(T* p, const float (&v)[4]) { *(uint2*)p = make_uint2(Half16<T>::pack2(v[0], v[1]), Half16<T>::pack2(v[2], v[3])); }
-};
-template <> struct RopeIO<bf16_t> : RopeIO16<bf16_t> {};
-template <> struct RopeIO<f16_t> : RopeIO16<f16_t> {};
-
 // one thread: four consecutive pairs (i .. i + 3, i + 32 .. i + 35) of one q or k head of one row; the v heads are never touched.
 // q' = q cos + rotate_half(q) sin in f32 (HF: q.float() * cos + rotate_half(q.float()) * sin), rounded once; products and sum kept apart
 // (no fused multiply-add) as torch evaluates them.  p: this thread's first element; t: its position's first (cos, sin).
 template <typename T>
 __device__ __forceinline__ void rope_rotate4(T* p, const float2* t) {
   float a[4], b[4];
-  RopeIO<T>::load4(p, a);
-  RopeIO<T>::load4(p + 32, b);
+  Vec4IO<T>::load4(p, a);
+  Vec4IO<T>::load4(p + 32, b);
   float ra[4], rb[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -100,8 +90,8 @@ __device__ __forceinline__ void rope_rotate4(T* p, const float2* t) {
     ra[e] = __fadd_rn(__fmul_rn(a[e], cs.x), __fmul_rn(-b[e], cs.y));
     rb[e] = __fadd_rn(__fmul_rn(b[e], cs.x), __fmul_rn(a[e], cs.y));
   }
-  RopeIO<T>::store4(p, ra);
-  RopeIO<T>::store4(p + 32, rb);
+  Vec4IO<T>::store4(p, ra);
+  Vec4IO<T>::store4(p + 32, rb);
 }
 
 template <typename T>
@@ -161,35 +151,20 @@ __global__ __launch_bounds__(256) void attention_causal32_packed_kernel(
   attn_grouped_packed<64>(qkv, ctx, mask, Lp, heads, kv_heads, scale, AttnCausal{}, cu);
 }
 
-// ext: kmax [B] (padded rows) or cu [B + 1] (packed rows)
-template <typename T>
-int causal_launch_as(bool packed, dim3 grid, hipStream_t s, const void* qkv, void* ctx, const int64_t* mask, int L, int heads, int kv_heads, float scale,
-                     const int* ext) {
-  if constexpr (std::is_same<T, float>::value) {
-    constexpr int lds = 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4;
-    return attn_launch_form<attention_causal32_kernel, attention_causal32_packed_kernel, float>(packed, grid, lds, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext);
-  } else {
-    constexpr int lds = 2 * 128 * 128 + 128 * 4;
-    return attn_launch_form<attention_causal16_kernel<T>, attention_causal16_packed_kernel<T>, T>(packed, grid, lds, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext);
-  }
-}
-
-// both forms, after the entry's checks: float32, or one of the 16-bit formats (every other dtype code counts as bfloat16)
-int causal_launch(int dtype, bool packed, int64_t B, int L, int heads, int kv_heads, const void* qkv, void* ctx, const int64_t* mask, float scale,
-                  const int* ext, hipStream_t s) {
-  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
-  const int rc = dtype == OM_F32 ? causal_launch_as<float>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext)
-                                 : attn_with_type16(dtype, [&](auto t) { return causal_launch_as<decltype(t)>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext); });
-  if (rc) return 1;
-  OM_LAUNCH_CHECK();
-  return 0;
-}
-
 }  // namespace
 
-static int check_gqa(int heads, int kv_heads) {
-  if (heads < 1 || kv_heads < 1 || heads % kv_heads) OM_FAIL("grouped heads: n_kv_heads must be at least 1 and divide n_heads");
-  return 0;
+// launch only: attn_plan_gqa (attn_plan.h) has checked the arguments and chosen the body, the grid and the LDS bytes; ext: kmax [B]
+// (padded rows) or cu [B + 1] (packed rows)
+int omk_attention_causal64(const AttnGqaPlan& p, int dtype, bool packed, const void* qkv, void* ctx, const int64_t* mask, int L, int heads,
+                           int kv_heads, float scale, const int* ext, hipStream_t s) {
+  static_assert(attn_gqa_lds(64, true) == 128 * AttnGeom<float>::ROWB + 64 * 132 * 4 + 128 * 4 + 128 * 4 && attn_gqa_lds(64, false) == 2 * 128 * 128 + 128 * 4,
+                "the plan's LDS bytes are these kernels'");
+  const dim3 grid(p.grid_x, p.grid_y);
+  if (p.f32) return attn_launch_form<attention_causal32_kernel, attention_causal32_packed_kernel, float>(packed, grid, p.lds, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext);
+  return attn_with_type16(dtype, [&](auto t) {
+    typedef decltype(t) T;
+    return attn_launch_form<attention_causal16_kernel<T>, attention_causal16_packed_kernel<T>, T>(packed, grid, p.lds, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext);
+  });
 }
 
 // rot_heads rotated heads at the start of each row of `pitch` elements
@@ -228,37 +203,43 @@ int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads
                  const int* row_map) {
   if (M <= 0) return 0;
   if (L < 1 || L > kRopeMaxPos) OM_FAIL("rotary positions: sequence length must be in [1,1024]");
-  if (check_gqa(heads, kv_heads)) return 1;
+  if (heads < 1 || kv_heads < 1 || heads % kv_heads) OM_FAIL("grouped heads: n_kv_heads must be at least 1 and divide n_heads");
   if (!inv_freq_host) OM_FAIL("rotary positions: a frequency table of 32 values");
   return rope_launch(dtype, qkv, M, L, heads + kv_heads, (heads + 2 * kv_heads) * 64, inv_freq_host, scaling, s, row_map);
 }
 
-// its own launch: the planner of the bidirectional kernels (attn_plan.h) and omk_attention know nothing of it
-int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                         const int* kmax, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
-  if (check_gqa(heads, kv_heads)) return 1;
-  if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
-  return causal_launch(dtype, false, B, L, heads, kv_heads, qkv, ctx, mask, scale, kmax, s);
+// the one grouped-query attention entry: plan (attn_plan.h), switch on the family, launch
+int omk_attention_gqa(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, int head_dim,
+                      bool causal, float scale, int w, bool packed, const int* ext, hipStream_t s) {
+  const AttnGqaPlan p = attn_plan_gqa(dtype, B, L, heads, kv_heads, head_dim, causal, w, packed, ext != nullptr);
+  if (p.error) OM_FAIL(p.error);
+  switch (p.family) {
+    case 0: return 0;                                   // an empty batch
+    case OM_ATTN_GQA_FAMILY_CAUSAL64: RUN(omk_attention_causal64(p, dtype, packed, qkv, ctx, mask, L, heads, kv_heads, scale, ext, s)); break;
+    case OM_ATTN_GQA_FAMILY_CAUSAL128: RUN(omk_attention_causal128(p, dtype, packed, qkv, ctx, mask, L, heads, kv_heads, scale, ext, s)); break;
+    default: RUN(omk_attention_d256(p, dtype, packed, qkv, ctx, mask, L, heads, kv_heads, scale, w, ext, s));      // FULL256, BAND256
+  }
+  OM_LAUNCH_CHECK();
+  return 0;
 }
 
-// the same two bodies over packed rows: cu [B + 1] from omk_pack_rows (its offsets are clamped to the row bound, so a bound that is too
-// small shortens or empties the last sequences and nothing leaves the buffers); L is the pitch of the mask
-int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                                const int* cu, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
-  if (check_gqa(heads, kv_heads)) return 1;
-  if (!cu) OM_FAIL("causal attention over packed rows: the sequence offsets cu");
-  if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
-  return causal_launch(dtype, true, B, L, heads, kv_heads, qkv, ctx, mask, scale, cu, s);
+// host only: what omk_attention_gqa would launch for these arguments -- out = {family, body (1: float32, 0: 16-bit), grid x, grid y,
+// dynamic LDS bytes}; 0 with every word zero when nothing would launch, -1 for a refusal (its reason in om_last_error)
+extern "C" int om_debug_attention_gqa_plan(int dtype, int64_t B, int L, int n_heads, int n_kv_heads, int head_dim, int causal, int w, int packed,
+                                           int has_ext, int64_t out[5]) {
+  if (!out) OM_FAIL("null argument");
+  const AttnGqaPlan p = attn_plan_gqa(dtype, B, L, n_heads, n_kv_heads, head_dim, causal != 0, w, packed != 0, has_ext != 0);
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (p.error) { om_set_error(std::string(__func__) + ": " + p.error); return -1; }
+  if (p.family) { out[0] = p.family; out[1] = p.f32; out[2] = p.grid_x; out[3] = p.grid_y; out[4] = p.lds; }
+  return 0;
 }
 
-// Test hooks (tests/test_attention_causal.py, tools/causal_lm_bench.py; attention_causal128.hip's share the buffer).  The key extents go into a grow-only device buffer the hook
-// keeps per device (a forward has them in its workspace): like rope_gqa_table_device it allocates on first use only, and launches
-// after that are stream-ordered with no synchronisation -- calls on one device are expected from one stream at a time.
-int omk_causal_debug_kmax(int64_t B, int** out) {
+// Test hooks (tests/test_attention_causal.py, test_qwen3_kernels.py, test_gemma3_kernels.py and their packed twins, tools/causal_lm_bench.py,
+// tools/gemma3_bench.py): the kernels alone.  The key extents of the padded form go into a grow-only device buffer the hooks keep per
+// device (a forward has them in its workspace): like omk_rope_table it allocates on first use only, and launches after that are
+// stream-ordered with no synchronisation -- calls on one device are expected from one stream at a time.
+static int debug_kmax(int64_t B, int** out) {
   static std::mutex mu;
   static std::map<int, std::pair<int*, int64_t>> bufs;
   int dev = 0;
@@ -274,38 +255,77 @@ int omk_causal_debug_kmax(int64_t B, int** out) {
   return 0;
 }
 
+// all six hooks after their null and dtype checks.  cu != NULL: the packed kernels.  Padded: the plan first, so that a refused call
+// leaves nothing on the stream, then the extents (one more small launch), then the entry.
+static int debug_attention_gqa(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L, int heads,
+                               int kv_heads, int head_dim, bool causal, float scale, int w, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (cu) return omk_attention_gqa(dtype, qkv, ctx, mask, B, L, heads, kv_heads, head_dim, causal, scale, w, true, cu, s);
+  const AttnGqaPlan p = attn_plan_gqa(dtype, B, L, heads, kv_heads, head_dim, causal, w, false, true);
+  if (p.error) OM_FAIL(p.error);
+  if (!p.family) return 0;
+  int* kmax = nullptr;
+  RUN(debug_kmax(B, &kmax));
+  RUN(omk_mask_extent(mask, B, L, kmax, s));
+  return omk_attention_gqa(dtype, qkv, ctx, mask, B, L, heads, kv_heads, head_dim, causal, scale, w, false, kmax, s);
+}
+
 extern "C" int om_debug_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads,
                                          int n_kv_heads, float scale, void* stream) {
   if (!qkv || !ctx || !mask) OM_FAIL("null argument");
-  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("causal attention: dtype must be OM_F32, OM_BF16 or OM_F16");
-  if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
-  if (check_gqa(n_heads, n_kv_heads)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  int* kmax = nullptr;
-  if (omk_causal_debug_kmax(B, &kmax)) return 1;
-  if (omk_mask_extent(mask, B, L, kmax, s)) return 1;
-  return omk_attention_causal(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, kmax, s);
+  OM_DBG_DTYPE("causal attention");
+  return debug_attention_gqa(dtype, qkv, ctx, mask, nullptr, B, L, n_heads, n_kv_heads, 64, true, scale, 0, stream);
+}
+
+// the packed kernels alone: cu [B + 1] as om_debug_pack_rows wrote it
+extern "C" int om_debug_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                                int n_heads, int n_kv_heads, float scale, void* stream) {
+  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
+  OM_DBG_DTYPE("causal attention");
+  return debug_attention_gqa(dtype, qkv, ctx, mask, cu, B, L, n_heads, n_kv_heads, 64, true, scale, 0, stream);
+}
+
+// the same two with a head width: 64 runs the kernels above, 128 those of attention_causal128.hip
+extern "C" int om_debug_attention_causal_hd(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads,
+                                            int n_kv_heads, int head_dim, float scale, void* stream) {
+  if (!qkv || !ctx || !mask) OM_FAIL("null argument");
+  RUN(debug_dtype(dtype));
+  return debug_attention_gqa(dtype, qkv, ctx, mask, nullptr, B, L, n_heads, n_kv_heads, head_dim, true, scale, 0, stream);
+}
+
+extern "C" int om_debug_attention_causal_hd_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                                   int n_heads, int n_kv_heads, int head_dim, float scale, void* stream) {
+  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
+  RUN(debug_dtype(dtype));
+  return debug_attention_gqa(dtype, qkv, ctx, mask, cu, B, L, n_heads, n_kv_heads, head_dim, true, scale, 0, stream);
+}
+
+// Gemma3's bidirectional kernels (attention_d256.hip): 0 < w < L - 1 the band, anything else full attention
+extern "C" int om_debug_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads,
+                                           int n_kv_heads, float scale, int w, void* stream) {
+  if (!qkv || !ctx || !mask) OM_FAIL("null argument");
+  RUN(debug_dtype(dtype));
+  return debug_attention_gqa(dtype, qkv, ctx, mask, nullptr, B, L, n_heads, n_kv_heads, 256, false, scale, w, stream);
+}
+
+extern "C" int om_debug_attention_gqa_d256_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
+                                                  int n_heads, int n_kv_heads, float scale, int w, void* stream) {
+  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
+  RUN(debug_dtype(dtype));
+  return debug_attention_gqa(dtype, qkv, ctx, mask, cu, B, L, n_heads, n_kv_heads, 256, false, scale, w, stream);
 }
 
 extern "C" int om_debug_rope_gqa(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling,
                                  void* stream) {
   if (!qkv || !inv_freq) OM_FAIL("null argument");
-  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
+  OM_DBG_DTYPE("rotary positions");
   return omk_rope_gqa(dtype, qkv, M, L, n_heads, n_kv_heads, inv_freq, scaling, (hipStream_t)stream);
 }
 
-// the packed kernels alone: cu [B + 2] and row_map [rows] as om_debug_pack_rows wrote them
-extern "C" int om_debug_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
-                                                int n_heads, int n_kv_heads, float scale, void* stream) {
-  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
-  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("causal attention: dtype must be OM_F32, OM_BF16 or OM_F16");
-  return omk_attention_causal_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, cu, (hipStream_t)stream);
-}
-
+// row_map [rows] as om_debug_pack_rows wrote it
 extern "C" int om_debug_rope_gqa_rows(int dtype, void* qkv, int64_t rows, int L, int n_heads, int n_kv_heads, const float* inv_freq, float scaling,
                                       const int* row_map, void* stream) {
   if (!qkv || !inv_freq || !row_map) OM_FAIL("null argument");
-  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("rotary positions: dtype must be OM_F32, OM_BF16 or OM_F16");
+  OM_DBG_DTYPE("rotary positions");
   return omk_rope_gqa(dtype, qkv, rows, L, n_heads, n_kv_heads, inv_freq, scaling, (hipStream_t)stream, row_map);
 }

@@ -1,8 +1,9 @@
 // What a Qwen3 embedder (HF:models/qwen3/modeling_qwen3.py) adds to the decoder-only stack of attention_causal.hip (gfx950, inference):
 //
-//   * omk_attention_causal_d128 / _packed: causal grouped-query attention over heads of 128 columns.  The projection rows are
+//   * omk_attention_causal128, the launcher of omk_attention_gqa's CAUSAL128 family (attention_causal.hip; launch only): causal
+//     grouped-query attention over heads of 128 columns.  The projection rows are
 //     [M, (heads + 2 kv_heads) * 128] (q heads | k heads | v heads), ctx rows [M, heads * 128].  Grid, policy (AttnCausal), key
-//     extents and the packed form are those of omk_attention_causal: one workgroup of 256 threads per (sequence, query head,
+//     extents and the packed form are those of the 64-wide kernels: one workgroup of 256 threads per (sequence, query head,
 //     128-query block) walking 128-key chunks up to the diagonal chunk, clipped to kmax[b] or the packed extent.  The bodies are
 //     attn_chunked_wide.h at D = 128.
 //
@@ -22,6 +23,7 @@
 //     Gemma3 (gemma = 1, head_dim 256, 32 lanes per head): Gemma3RMSNorm multiplies the f32 normalised value by (1 + weight) and
 //     casts once at the end, so that mode has no rounding between the two multiplies and takes g = 1 + w from the host.
 #include "attn_chunked_wide.h"
+#include "attn_plan.h"
 
 namespace {
 
@@ -53,36 +55,7 @@ __global__ __launch_bounds__(256) void attention_causal32_d128_packed_kernel(
   attn_grouped_packed<128>(qkv, ctx, mask, Lp, heads, kv_heads, scale, AttnCausal{}, cu);
 }
 
-// ext: kmax [B] (padded rows) or cu [B + 1] (packed rows)
-template <typename T>
-int causal_d128_launch_as(bool packed, dim3 grid, hipStream_t s, const void* qkv, void* ctx, const int64_t* mask, int L, int heads, int kv_heads,
-                          float scale, const int* ext) {
-  if constexpr (std::is_same<T, float>::value)
-    return attn_launch_form<attention_causal32_d128_kernel, attention_causal32_d128_packed_kernel, float>(packed, grid, AttnWide<128>::LDS32, s, qkv, ctx, mask, L,
-                                                                                                            heads, kv_heads, scale, ext);
-  else
-    return attn_launch_form<attention_causal16_d128_kernel<T>, attention_causal16_d128_packed_kernel<T>, T>(packed, grid, AttnWide<128>::LDS16, s, qkv, ctx, mask, L,
-                                                                                                              heads, kv_heads, scale, ext);
-}
-
 // ---- q / k RMSNorm + rotary positions ---------------------------------------------------------------------------------------
-template <typename T> struct QkIO;      // four consecutive elements <-> floats; one value rounded to the storage format and back
-template <> struct QkIO<float> {
-  __device__ static inline void load4(const float* p, float (&v)[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  __device__ static inline void store4(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-  __device__ static inline float round(float v) { return v; }
-};
-template <typename T> struct QkIO16 {
-  __device__ static inline void load4(const T* p, float (&v)[4]) {
-    const uint2 t = *(const uint2*)p;
-    v[0] = Half16<T>::lo(t.x); v[1] = Half16<T>::hi(t.x); v[2] = Half16<T>::lo(t.y); v[3] = Half16<T>::hi(t.y);
-  }
-  __device__ static inline void store4(T* p, const float (&v)[4]) { *(uint2*)p = make_uint2(Half16<T>::pack2(v[0], v[1]), Half16<T>::pack2(v[2], v[3])); }
-  __device__ static inline float round(float v) { return Half16<T>::value(Half16<T>::bits(v)); }
-};
-template <> struct QkIO<bf16_t> : QkIO16<bf16_t> {};
-template <> struct QkIO<f16_t> : QkIO16<f16_t> {};
-
 // one thread: the pairs (i0 .. i0 + 3, D/2 + i0 .. D/2 + i0 + 3) of one q or k head of one row; D / 8 consecutive lanes: the head.
 // row_map != NULL (packed rows): the position of row t is row_map[t] % L, rows with row_map[t] < 0 are left as they are.  A group is
 // wholly inside or wholly outside the launch and the row test is the same for all of its lanes, so the shuffles below meet live lanes.
@@ -107,8 +80,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ qkv, c
   }
   T* const p = qkv + row * (int64_t)pitch + (int64_t)seg * D + i0;
   float a[4], b[4];
-  QkIO<T>::load4(p, a);
-  QkIO<T>::load4(p + D / 2, b);
+  Vec4IO<T>::load4(p, a);
+  Vec4IO<T>::load4(p + D / 2, b);
   const float* const g = seg < heads ? qg : kg;
   if (g) {
     float ss = 0.f;
@@ -127,8 +100,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ qkv, c
         a[e] = __fmul_rn(__fmul_rn(a[e], r), wa[e]);
         b[e] = __fmul_rn(__fmul_rn(b[e], r), wb[e]);
       } else {
-        a[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(a[e], r)), wa[e]);
-        b[e] = __fmul_rn(QkIO<T>::round(__fmul_rn(b[e], r)), wb[e]);
+        a[e] = __fmul_rn(Vec4IO<T>::round(__fmul_rn(a[e], r)), wa[e]);
+        b[e] = __fmul_rn(Vec4IO<T>::round(__fmul_rn(b[e], r)), wb[e]);
       }
     }
   }
@@ -140,8 +113,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ qkv, c
     ra[e] = __fadd_rn(__fmul_rn(a[e], cs.x), __fmul_rn(-b[e], cs.y));
     rb[e] = __fadd_rn(__fmul_rn(b[e], cs.x), __fmul_rn(a[e], cs.y));
   }
-  QkIO<T>::store4(p, ra);
-  QkIO<T>::store4(p + D / 2, rb);
+  Vec4IO<T>::store4(p, ra);
+  Vec4IO<T>::store4(p + D / 2, rb);
 }
 
 template <typename T>
@@ -181,65 +154,23 @@ int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_he
   return 0;
 }
 
-// kmax [B] (padded rows, cu NULL) or cu [B + 1] (packed rows): one launch function for both forms
-static int attention_causal_d128_launch(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads,
-                                        float scale, const int* kmax, const int* cu, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
-  if (check_gqa_d(heads, kv_heads, 128)) return 1;
-  if (B * heads > 0x7fffffffLL) OM_FAIL("causal attention: batch too large for one launch");
-  const dim3 grid((unsigned)(heads * B), (unsigned)((L + 127) / 128));
-  // float32, or one of the 16-bit formats (every other dtype code counts as bfloat16)
-  const bool packed = cu != nullptr;
-  const int* const ext = packed ? cu : kmax;
-  const int rc = dtype == OM_F32 ? causal_d128_launch_as<float>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext)
-                                 : attn_with_type16(dtype, [&](auto t) { return causal_d128_launch_as<decltype(t)>(packed, grid, s, qkv, ctx, mask, L, heads, kv_heads, scale, ext); });
-  if (rc) return 1;
-  OM_LAUNCH_CHECK();
-  return 0;
+// launch only: attn_plan_gqa (attn_plan.h) has checked the arguments and chosen the body, the grid and the LDS bytes; ext: kmax [B]
+// (padded rows) or cu [B + 1] (packed rows)
+int omk_attention_causal128(const AttnGqaPlan& p, int dtype, bool packed, const void* qkv, void* ctx, const int64_t* mask, int L, int heads,
+                            int kv_heads, float scale, const int* ext, hipStream_t s) {
+  static_assert(attn_gqa_lds(128, true) == AttnWide<128>::LDS32 && attn_gqa_lds(128, false) == AttnWide<128>::LDS16, "the plan's LDS bytes are these kernels'");
+  const dim3 grid(p.grid_x, p.grid_y);
+  if (p.f32)
+    return attn_launch_form<attention_causal32_d128_kernel, attention_causal32_d128_packed_kernel, float>(packed, grid, p.lds, s, qkv, ctx, mask, L, heads, kv_heads,
+                                                                                                            scale, ext);
+  return attn_with_type16(dtype, [&](auto t) {
+    typedef decltype(t) T;
+    return attn_launch_form<attention_causal16_d128_kernel<T>, attention_causal16_d128_packed_kernel<T>, T>(packed, grid, p.lds, s, qkv, ctx, mask, L, heads, kv_heads,
+                                                                                                              scale, ext);
+  });
 }
 
-int omk_attention_causal_d128(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                              const int* kmax, hipStream_t s) {
-  return attention_causal_d128_launch(dtype, qkv, ctx, mask, B, L, heads, kv_heads, scale, kmax, nullptr, s);
-}
-
-int omk_attention_causal_d128_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                                     const int* cu, hipStream_t s) {
-  if (B > 0 && !cu) OM_FAIL("causal attention over packed rows: the sequence offsets cu");
-  return attention_causal_d128_launch(dtype, qkv, ctx, mask, B, L, heads, kv_heads, scale, nullptr, cu, s);
-}
-
-// Test hooks (tests/test_qwen3_kernels.py, tools/causal_lm_bench.py): the kernels of either head width alone.
-static int debug_dtype(int dtype) {
-  if (dtype != OM_F32 && dtype != OM_BF16 && dtype != OM_F16) OM_FAIL("dtype must be OM_F32, OM_BF16 or OM_F16");
-  return 0;
-}
-
-extern "C" int om_debug_attention_causal_hd(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int n_heads,
-                                            int n_kv_heads, int head_dim, float scale, void* stream) {
-  if (!qkv || !ctx || !mask) OM_FAIL("null argument");
-  if (debug_dtype(dtype)) return 1;
-  if (B <= 0) return 0;
-  if (L < 1 || L > 1024) OM_FAIL("causal attention: sequence length must be in [1,1024]");
-  if (check_gqa_d(n_heads, n_kv_heads, head_dim)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  int* kmax = nullptr;
-  if (omk_causal_debug_kmax(B, &kmax)) return 1;
-  if (omk_mask_extent(mask, B, L, kmax, s)) return 1;
-  if (head_dim == 64) return omk_attention_causal(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, kmax, s);
-  return omk_attention_causal_d128(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, kmax, s);
-}
-
-extern "C" int om_debug_attention_causal_hd_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, const int* cu, int64_t B, int L,
-                                                   int n_heads, int n_kv_heads, int head_dim, float scale, void* stream) {
-  if (!qkv || !ctx || !mask || !cu) OM_FAIL("null argument");
-  if (debug_dtype(dtype)) return 1;
-  if (check_gqa_d(n_heads, n_kv_heads, head_dim)) return 1;
-  if (head_dim == 64) return omk_attention_causal_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, cu, (hipStream_t)stream);
-  return omk_attention_causal_d128_packed(dtype, qkv, ctx, mask, B, L, n_heads, n_kv_heads, scale, cu, (hipStream_t)stream);
-}
-
+// Test hooks (tests/test_qwen3_kernels.py, tests/test_gemma3_kernels.py, tools/causal_lm_bench.py): the norm-and-rotation pass alone.
 extern "C" int om_debug_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int n_heads, int n_kv_heads, int head_dim, const float* q_norm_g,
                                     const float* k_norm_g, float eps, const float* inv_freq, float scaling, void* stream) {
   if (!qkv || !inv_freq) OM_FAIL("null argument");

@@ -1,8 +1,8 @@
-// Which kernel an attention call runs: attn_plan_fwd() and attn_plan_bwd() map (dtype, shape, which optional arguments are present,
-// switches) to an AttnPlan and do nothing else -- no launch, no HIP call, no global written, no pointer dereferenced.  omk_attention
-// (attention.hip) and omk_attention_bwd (train_kernels.hip) launch what they return; om_debug_attention_plan and
-// om_debug_attention_bwd_plan return the plan alone, so both tables are testable on a machine without a GPU.  DESIGN.md 4c lists the
-// rules in the order they are tested here.
+// Which kernel an attention call runs: attn_plan_fwd(), attn_plan_bwd() and attn_plan_gqa() map (dtype, shape, which optional arguments
+// are present, switches) to a plan and do nothing else -- no launch, no HIP call, no global written, no pointer dereferenced.
+// omk_attention (attention.hip), omk_attention_bwd (train_kernels.hip) and omk_attention_gqa (attention_causal.hip) launch what they
+// return; om_debug_attention_plan, om_debug_attention_bwd_plan and om_debug_attention_gqa_plan return the plan alone, so the three
+// tables are testable on a machine without a GPU.  DESIGN.md 4c lists the rules in the order they are tested here.
 #pragma once
 #include "kernels.h"
 
@@ -95,4 +95,45 @@ static AttnPlan attn_plan_bwd(int dtype, int64_t B, int L, int H, int heads, boo
     return refuse(has_cu && !has_bias && !has_drel ? "packed rows: attention backward up to 256 tokens, head_dim 64" : "training supports sequence lengths up to 256");
   if (dtype == OM_F32 && L > 192) return refuse("float32 training supports sequence lengths up to 192 (16-bit formats: 256)");
   return run(OM_ATTN_BWD_FAMILY_GENERIC, attn_kt(L));
+}
+
+// ---- grouped-query attention over the projection [M, (heads + 2 kv_heads) * head_dim]: the causal kernels of the decoder-only stacks
+// (head_dim 64: attention_causal.hip; 128: attention_causal128.hip) and Gemma3's bidirectional ones (256: attention_d256.hip) ----
+// The dynamic LDS of a (head_dim, body) pair; each unit's launcher ties its kernels' own figure to this one with a static_assert.
+constexpr int attn_gqa_lds(int head_dim, bool f32) {
+  return head_dim == 64 ? (f32 ? 67584 : 33280) : head_dim == 128 ? (f32 ? 136192 : 66048) : (f32 ? 136960 : 65792);
+}
+
+// What attn_plan_gqa decided: the family (OM_ATTN_GQA_FAMILY_*; 0: launch nothing -- an empty batch, or a refusal with its reason in
+// `error`), the body (float32, or the 16-bit one of the call's format), the grid and the dynamic LDS bytes.
+struct AttnGqaPlan { int family; bool f32; unsigned grid_x, grid_y; int lds; const char* error; };
+
+// causal: key k visible from query q iff k <= q (else w: the half window, <= 0 none); packed: rows packed by sequence, and then
+// has_ext says whether the offsets cu are given (padded rows: the key extents kmax, which may be absent).  L is the padded length in
+// both forms: a packed launch gets the grid and the body the padded launch of the same batch gets.
+static AttnGqaPlan attn_plan_gqa(int dtype, int64_t B, int L, int heads, int kv_heads, int head_dim, bool causal, int w, bool packed, bool has_ext) {
+  AttnGqaPlan p = {0, dtype == OM_F32, 0, 0, 0, nullptr};
+  auto refuse = [&](const char* why) { p.error = why; return p; };
+  // 1. arguments
+  if (dtype != OM_F32 && !attn_is16(dtype)) return refuse("grouped-query attention: dtype must be OM_F32, OM_BF16 or OM_F16");
+  if (B <= 0) return p;
+  // 2. the kernels that exist: causal at 64 and 128 columns without a window, bidirectional at 256
+  if (causal && head_dim != 64 && head_dim != 128) return refuse("grouped heads: head_dim must be 64 or 128");
+  if (causal && w > 0) return refuse("causal attention: no window");
+  if (!causal && head_dim != 256) return refuse("bidirectional grouped-query attention: head_dim must be 256");
+  if (L < 1 || L > 1024) return refuse(causal ? "causal attention: sequence length must be in [1,1024]" : "attention (head_dim 256): sequence length must be in [1,1024]");
+  if (heads < 1 || kv_heads < 1 || heads % kv_heads) return refuse("grouped heads: n_kv_heads must be at least 1 and divide n_heads");
+  if (packed && !has_ext)
+    return refuse(causal ? "causal attention over packed rows: the sequence offsets cu" : "attention (head_dim 256) over packed rows: the sequence offsets cu");
+  if (B * heads > 0x7fffffffLL) return refuse(causal ? "causal attention: batch too large for one launch" : "attention (head_dim 256): batch too large for one launch");
+  // (the LDS-DMA addresses a sequence's K / V rows with a 32-bit byte offset from its first row)
+  if (head_dim == 256 && (int64_t)L * ((int64_t)heads + 2 * (int64_t)kv_heads) * 512 > 0x7fffffffLL)
+    return refuse("attention (head_dim 256): too many heads for one sequence's 32-bit row offsets");
+  // 3. the family: a window that reaches every key is full attention
+  p.family = head_dim == 64 ? OM_ATTN_GQA_FAMILY_CAUSAL64 : head_dim == 128 ? OM_ATTN_GQA_FAMILY_CAUSAL128
+           : w > 0 && w < L - 1 ? OM_ATTN_GQA_FAMILY_BAND256 : OM_ATTN_GQA_FAMILY_FULL256;
+  p.grid_x = (unsigned)(heads * B);
+  p.grid_y = (unsigned)((L + 127) / 128);
+  p.lds = attn_gqa_lds(head_dim, p.f32);
+  return p;
 }

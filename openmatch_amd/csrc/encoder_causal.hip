@@ -202,13 +202,7 @@ static int causal_forward_impl(const OmCausalConfig* cc, const CausalExtra& ex, 
     } else {
       RUN(omk_rope_gqa(dt, ws.qkv, M, (int)L, nh, nkv, cc->inv_freq, cc->rope_attention_scaling, s, row_map));
     }
-    if (hd == 128) {
-      if (packed) RUN(omk_attention_causal_d128_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
-      else RUN(omk_attention_causal_d128(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
-    } else {
-      if (packed) RUN(omk_attention_causal_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.cu, s));
-      else RUN(omk_attention_causal(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, scale, ws.kmax, s));
-    }
+    RUN(omk_attention_gqa(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, hd, true, scale, 0, packed, packed ? ws.cu : ws.kmax, s));
     // the residual sums: operands in the compute dtype, f32 output and residual (x += A W^T + bias)
     RUN(gemm(ws.ctx, A, lw.o_w, A, OM_F32, ws.x, H, H, A, lw.o_b, ws.x, H));                               // x += o_proj(ctx)
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // post_attention_layernorm

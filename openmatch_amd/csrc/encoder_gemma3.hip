@@ -130,8 +130,8 @@ static int gemma3_forward_impl(const OmGemma3Config* gc, const OmEncoderWeights*
     RUN(gemm(ws.y, H, lw.qkv_w, H, dt, ws.qkv, P, P, H));
     RUN(omk_qknorm_rope(dt, ws.qkv, M, (int)L, nh, nkv, 256, nw.q_norm_g, nw.k_norm_g, c->ln_eps, sliding ? gc->sliding_inv_freq : gc->full_inv_freq,
                         sliding ? gc->sliding_scaling : gc->full_scaling, s, row_map, 1));
-    if (packed) RUN(omk_attention_gqa_d256_packed(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, gc->attn_scale, sliding ? gc->half_window : 0, ws.cu, s));
-    else RUN(omk_attention_gqa_d256(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, gc->attn_scale, sliding ? gc->half_window : 0, ws.kmax, s));
+    RUN(omk_attention_gqa(dt, ws.qkv, ws.ctx, attention_mask, B, (int)L, nh, nkv, 256, false, gc->attn_scale, sliding ? gc->half_window : 0, packed,
+                          packed ? ws.cu : ws.kmax, s));
     RUN(gemm(ws.ctx, A, lw.o_w, A, dt, ws.y, H, H, A));                                                    // h = o_proj(ctx)
     RUN(omk_rmsnorm_add(dt, ws.y, H, (float*)ws.x, H, nw.post_attention_norm_g, M, H, c->ln_eps, s));       // x += post_attention_layernorm(h)
     RUN(omk_layernorm_from_f32(dt, (const float*)ws.x, H, ws.y, H, lw.ln2_g, nullptr, M, H, c->ln_eps, 1, s));   // pre_feedforward_layernorm

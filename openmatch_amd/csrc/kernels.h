@@ -52,41 +52,38 @@ int omk_rope(int dtype, void* qkv, int64_t M, int L, int H, float theta, hipStre
              const int* row_map = nullptr /* packed rows (NomicBERT): the position of row t is row_map[t] % L, rows with row_map[t] < 0 are skipped */);
 int omk_attention_band(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int H, int heads, float scale,
                        int w, const int* kmax, hipStream_t s);
-// Decoder-only backbones (attention_causal.hip, head_dim 64, inference): qkv is the grouped projection [M, (heads + 2 kv_heads) * 64]
-// (q heads | k heads | v heads), ctx [M, heads * 64].  Rotary positions on its q and k heads in place from the host's 32 frequencies
-// (cos, sin times `scaling`), and attention where key k is visible from query q iff k <= q and k is unmasked; query head h reads K / V
-// head h / (heads / kv_heads).  Its own launch: the planner of the bidirectional kernels (attn_plan.h) knows nothing of it.
+// Decoder-only backbones (inference): qkv is the grouped projection [M, (heads + 2 kv_heads) * head_dim] (q heads | k heads | v heads),
+// ctx [M, heads * head_dim]; query head h reads K / V head h / (heads / kv_heads).
+// Rotary positions on the q and k heads in place (attention_causal.hip, head_dim 64) from the host's 32 frequencies (cos, sin times
+// `scaling`); Qwen3 and Gemma3 (attention_causal128.hip): ONE pass for the per-head RMSNorm of q and k (weights [head_dim] f32, NULL: no
+// norm on that side) and the rotary positions, head_dim 64 or 128, from the host's head_dim / 2 frequencies.
 int omk_rope_gqa(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, const float* inv_freq_host, float scaling, hipStream_t s,
                  const int* row_map = nullptr /* packed rows: the position of row t is row_map[t] % L, rows with row_map[t] < 0 are skipped */);
-int omk_attention_causal(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                         const int* kmax, hipStream_t s);
-// packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv / ctx (omk_pack_rows), L stays the pitch of the mask
-int omk_attention_causal_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                                const int* cu, hipStream_t s);
-// Qwen3 (attention_causal128.hip): heads of 128 columns -- qkv [M, (heads + 2 kv_heads) * 128], ctx [M, heads * 128], otherwise the
-// two launches above -- and ONE pass for the per-head RMSNorm of q and k (weights [head_dim] f32, NULL: no norm on that side) and the
-// rotary positions, head_dim 64 or 128, from the host's head_dim / 2 frequencies.
-int omk_attention_causal_d128(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                              const int* kmax, hipStream_t s);
-int omk_attention_causal_d128_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads,
-                                     float scale, const int* cu, hipStream_t s);
 int omk_qknorm_rope(int dtype, void* qkv, int64_t M, int L, int heads, int kv_heads, int head_dim, const float* q_norm_g, const float* k_norm_g,
                     float eps, const float* inv_freq_host, float scaling, hipStream_t s, const int* row_map = nullptr,
                     int gemma = 0 /* 1: Gemma3's form -- head_dim 256, g = 1 + w, the normalised value not rounded before the weight multiply */);
-// Gemma3 (attention_d256.hip): bidirectional grouped-query attention over heads of 256 columns -- qkv [M, (heads + 2 kv_heads) * 256],
-// ctx [M, heads * 256], the caller's score scale; 0 < w < L - 1: key k visible from query q iff |q - k| <= w, else every unmasked key.
-int omk_attention_gqa_d256(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale, int w,
-                           const int* kmax, hipStream_t s);
-// the same over packed rows: sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv and ctx, L the pitch of mask (and what decides band or full)
-int omk_attention_gqa_d256_packed(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, float scale,
-                                  int w, const int* cu, hipStream_t s);
+// The one grouped-query attention entry (attention_causal.hip): it plans (attn_plan.h attn_plan_gqa: arguments, family, body, grid, LDS)
+// and launches.  causal: key k visible from query q iff k <= q and k is unmasked, head_dim 64 (Llama, Qwen2) or 128 (Qwen3), w <= 0 (a
+// window is refused); otherwise Gemma3's bidirectional form, head_dim 256, the caller's score scale: 0 < w < L - 1: key k visible iff |q - k| <= w,
+// else every unmasked key.  Padded rows: ext = kmax [B] (omk_mask_extent; NULL: no key is padding).  Packed rows: ext = cu [B + 1]
+// (omk_pack_rows), required -- sequence b is rows cu[b] .. cu[b + 1] - 1 of qkv and ctx, L stays the pitch of mask and what the grid
+// and band-or-full are decided on.
+int omk_attention_gqa(int dtype, const void* qkv, void* ctx, const int64_t* mask, int64_t B, int L, int heads, int kv_heads, int head_dim,
+                      bool causal, float scale, int w, bool packed, const int* ext, hipStream_t s);
+// its launchers, one per head width (attention_causal.hip, attention_causal128.hip, attention_d256.hip): no argument checks of their own
+struct AttnGqaPlan;
+int omk_attention_causal64(const AttnGqaPlan& p, int dtype, bool packed, const void* qkv, void* ctx, const int64_t* mask, int L, int heads,
+                           int kv_heads, float scale, const int* ext, hipStream_t s);
+int omk_attention_causal128(const AttnGqaPlan& p, int dtype, bool packed, const void* qkv, void* ctx, const int64_t* mask, int L, int heads,
+                            int kv_heads, float scale, const int* ext, hipStream_t s);
+int omk_attention_d256(const AttnGqaPlan& p, int dtype, bool packed, const void* qkv, void* ctx, const int64_t* mask, int L, int heads,
+                       int kv_heads, float scale, int w, const int* ext, hipStream_t s);
 // x[f32] += rms(h) * g over M rows of H columns (elementwise.hip): the norm of a sublayer OUTPUT h (compute dtype) added into the f32
 // residual stream (Gemma3's post_attention_layernorm / post_feedforward_layernorm); g = 1 + w from the host
 int omk_rmsnorm_add(int dtype, const void* h, int64_t ldh, float* x, int64_t ldx, const float* g, int64_t M, int H, float eps, hipStream_t s);
 // attention_causal.hip: the device table [1024 positions][n] of (cos, sin) * scaling for n host frequencies, cached per (device,
-// frequencies, scaling); the grow-only device buffer of key extents the causal test hooks share
+// frequencies, scaling)
 int omk_rope_table(const float* inv_freq, int n, float scaling, const float2** out);
-int omk_causal_debug_kmax(int64_t B, int** out);
 // packed rows (om_encoder_forward_packed): cu[0..B] = offsets of the sequences (kmax[b] rows each) clamped to `rows`, cu[B + 1] = the
 // unclamped token count; cls_rows[b] = min(cu[b], rows - 1); row_map[t] = b * L + position of packed row t, -1 for the pad rows
 int omk_pack_rows(const int* kmax, int64_t B, int L, int64_t rows, int* cu, int* cls_rows, int* row_map, hipStream_t s);

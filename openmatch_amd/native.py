@@ -26,6 +26,8 @@ OPT_GEMM_GROUP_M, OPT_GEMM_VARIANT, OPT_GEMM_SKINNY_M = 6, 12, 19
 GEMM_FAMILY = {"v1": 1, "v2": 2, "v6": 6, "g7": 7, "g7_one_tile": 70, "7c16": 71, "7r16": 72, "skinny": 9}
 # om_debug_attention_last codes (include/openmatch_hip.h: OM_ATTN_FAMILY_*); the call returns family | key tiles << 8
 ATTN_FAMILY = {"generic": 1, "fwd16": 2, "fwd16_kmax4": 3, "fwd16c": 4, "long": 5, "d32": 6, "band16": 7, "band32": 8}
+# om_debug_attention_gqa_plan codes (OM_ATTN_GQA_FAMILY_*): out[0] of the call
+GQA_FAMILY = {"causal64": 1, "causal128": 2, "full256": 3, "band256": 4}
 # om_debug_attention_bwd_last codes (OM_ATTN_BWD_FAMILY_*), packed the same way
 ATTN_BWD_FAMILY = {"bwd16": 1, "generic": 2, "long": 3, "d32": 4}
 # om_debug_encoder_plan codes (OM_ENC_PATH_*); the call returns path | few_rows << 8 | two << 9 | lo8 << 10
@@ -210,6 +212,7 @@ _SIGNATURES = {
     "om_debug_pack_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "om_debug_attention_last": (c_int, []),
     "om_debug_attention_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int]),
+    "om_debug_attention_gqa_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_int64)]),
     "om_debug_attention_bwd_last": (c_int, []),
     "om_debug_attention_bwd_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "om_debug_attention_bwd_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
