@@ -1129,6 +1129,32 @@ int om_sim_topk_filtered_multi(int mode, const float* queries, int64_t n_queries
                                const float* stats, int64_t N, int d, int k, int64_t id_offset, const uint32_t* allow_bits,
                                int64_t words_pitch, int64_t n_filters, const int32_t* filter_of, int64_t n_allowed_min, float* out_scores,
                                int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The search with an EXCLUSION LIST per query (hard-negative mining: every row but the query's few known positives): per query exactly
+ * what om_sim_topk_async of the same mode returns over an index without the excluded rows -- the same scores (the re-score's bits in the
+ * two 16-bit modes), descending, ties by ascending row, ids = id_offset + the ORIGINAL row, (-3.4028235e38, -1) padding when fewer than k
+ * rows remain.  excl: device memory, int32 [n_queries][pitch]; row q holds the rows query q must not return -- ASCENDING, WITHOUT REPEATS,
+ * padded at the end with -1.  pitch is at most */
+#define OM_EXCLUDE_MAX 4096
+/* ids (16 KiB: the drop stages one list in LDS).  An id at or beyond N is legal and matches nothing.  A list that breaks the contract
+ * (unsorted, repeats, a negative other than the padding) may drop the wrong rows or return a short result; it never makes the entry read
+ * outside [excl, excl + n_queries * pitch) or outside the index: every probe of the binary search stays inside the list's own pitch
+ * words, and no value of a list is used as an address.
+ * The chain is om_sim_topk_filtered_multi's with the list in the bitmap's place: in front of EVERY selection a small kernel drops the
+ * excluded keys of every list (one workgroup per query, one binary search per key), so thresholds, certified margins and the re-score
+ * only ever see rows that may be returned; the redo skips the excluded (row, query) pairs and takes its rank, min(k, N - the list's
+ * entries below N), from a count taken on the device.  The schedule is om_debug_search_exclude_schedule's.  Lists that exclude most of
+ * the head of the index act like a clustered bitmap: no threshold exists behind the bootstrap and the queries are redone (status[2]).
+ * Enqueues only; legal on a capturing stream after one eager call.  status: as om_sim_topk_async's, may be NULL.  pitch == 0 is the
+ * unfiltered search, and excl is not read.  Refuses what om_sim_topk_filtered refuses, pitch outside [0, OM_EXCLUDE_MAX], and a NULL excl
+ * with pitch > 0.  workspace: om_sim_topk_excluding_workspace_bytes, 256-byte aligned. */
+size_t om_sim_topk_excluding_workspace_bytes(int64_t n_queries, int d, int k, int64_t pitch);
+int om_sim_topk_excluding(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
+                          const float* stats, int64_t N, int d, int k, int64_t id_offset, const int32_t* excl, int64_t pitch,
+                          float* out_scores, int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The schedule of om_sim_topk_excluding (csrc/search_plan.h search_schedule_excluding: no launch, no HIP call):
+ * om_debug_search_schedule_filtered's for n_allowed = N - pitch, the fewest rows any query of the call may be returned -- a planning
+ * number only.  pitch == 0: om_debug_search_schedule's; N - pitch < 1: every row is scored densely. */
+int om_debug_search_exclude_schedule(int mode, int64_t nq, int64_t N, int k, int64_t pitch, int64_t* chunks, int cap, int* n, int64_t* boot);
 /* The exact top-k of every query over its OWN candidate rows (dense re-ranking of a first-stage run): cand [n_queries][cand_pitch] int32 on
  * the device, cand[q][j] a row number; any value outside [0, N) is a hole -- skipped, never dereferenced.  Rows must be DISTINCT within a
  * query: a repeated row is returned twice (openmatch_amd/index.py removes repeats before the call).  Scores are the re-score's dot product
@@ -1189,6 +1215,13 @@ int om_debug_drop_lists_multi(int64_t n_queries, int m, const float* scores, con
                               const uint32_t* allow, uint32_t nrows, int64_t words_pitch, int64_t n_filters, const int32_t* filter_of,
                               float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes,
                               void* stream);
+/* The drop under the exclusion lists of om_sim_topk_excluding: drop_excluded_kernel launched as that entry launches it, over lists put
+ * and read back as om_debug_select_lists does (the same stale keys, counts and out_* layout).  excl [n_queries][pitch] as that entry's,
+ * pitch in [1, OM_EXCLUDE_MAX], over rows [0, nrows): a key is kept, in its order, when its row is below nrows and not in the query's
+ * list.  A query whose list is empty keeps its list as it is (a count above 8192 is clamped and marked all the same). */
+int om_debug_drop_lists_excluding(int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts, int use_qstat,
+                                  const int32_t* excl, int64_t pitch, uint32_t nrows, float* out_scores, uint32_t* out_rows,
+                                  uint32_t* out_state, void* workspace, size_t workspace_bytes, void* stream);
 /* query_prep_kernel on the grid of the search: queries [n_queries][d] f32 and stats[2] = {max ||p - f16(p)||, max ||f16(p)||} on the
  * device -> out_q16 [round_up(n_queries, 256)][d] float16 (rows beyond n_queries zero) and the certified margins out_margin [n_queries]. */
 int om_debug_query_prep(const float* queries, int64_t n_queries, int d, const float* stats, void* out_q16, float* out_margin, void* stream);

@@ -460,11 +460,38 @@ __global__ __launch_bounds__(256) void count_allowed_kernel(const RowFilters F, 
 // no staging copy is needed.  Position inside a step: wave ballot + the totals of the lower waves.  A list beyond SORT_CAP lost
 // appends: clamped and marked here as the selections do, or the compaction would hide it from them.
 // A query under no filter keeps its list (clamped and marked all the same); one whose filter allows no row ends with an empty list.
+// drop_compact is the compaction itself over the predicate keep(row) -- the bitmaps' here, the exclusion lists' in drop_excluded_kernel:
+// keys [0, n) of `list`, by all 256 threads of the workgroup; wtot: 4 words of LDS.  Returns the number of keys kept.
+template <typename Keep>
+__device__ __forceinline__ unsigned drop_compact(u64* __restrict__ list, unsigned n, unsigned* wtot, Keep keep) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned out = 0;
+  for (unsigned base = 0; base < n; base += 256) {
+    const unsigned i = base + (unsigned)tid;
+    u64 key = 0ull;
+    bool ok = false;
+    if (i < n) {
+      key = list[i];
+      ok = keep(key_payload(key));
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
+    const unsigned below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (lane == 0) wtot[wave] = (unsigned)__builtin_popcountll(m);
+    __syncthreads();                               // the step's keys are read, the wave totals written
+    unsigned off = out;
+    for (int w = 0; w < wave; ++w) off += wtot[w];
+    if (ok) list[off + below] = key;
+    out += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    __syncthreads();                               // the totals are read
+  }
+  return out;
+}
+
 __global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ keys, unsigned* __restrict__ cnt, const RowFilters F,
                                                               uint32_t nrows, unsigned* __restrict__ flag, unsigned* __restrict__ qstat) {
   __shared__ unsigned wtot[4];
   const int64_t q = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t f = filter_index(F, q);              // (workgroup-uniform)
   const uint32_t* __restrict__ allow = F.bits + (f > 0 ? f : 0) * F.pitch;
   unsigned n = cnt[q];
@@ -480,28 +507,75 @@ __global__ __launch_bounds__(256) void drop_disallowed_kernel(u64* __restrict__ 
     if (tid == 0) cnt[q] = f == FILTER_NO_ROW ? 0u : n;
     return;
   }
-  u64* list = keys + q * SORT_CAP;
-  unsigned out = 0;
-  for (unsigned base = 0; base < n; base += 256) {
-    const unsigned i = base + (unsigned)tid;
-    u64 key = 0ull;
-    bool ok = false;
-    if (i < n) {
-      key = list[i];
-      const uint32_t row = key_payload(key);
-      ok = row < nrows && row_allowed(allow, row);
-    }
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (lane == 0) wtot[wave] = (unsigned)__builtin_popcountll(m);
-    __syncthreads();                               // the step's keys are read, the wave totals written
-    unsigned off = out;
-    for (int w = 0; w < wave; ++w) off += wtot[w];
-    if (ok) list[off + below] = key;
-    out += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();                               // the totals are read
-  }
+  const unsigned out = drop_compact(keys + q * SORT_CAP, n, wtot, [&](uint32_t row) { return row < nrows && row_allowed(allow, row); });
   __syncthreads();                                 // (an empty list: every thread has read cnt[q])
+  if (tid == 0) cnt[q] = out;
+}
+
+// ---- the exclusion lists of om_sim_topk_excluding -----------------------------------------------------------------------------------------
+// excl [n_queries][pitch] int32: row q is the rows query q must not return -- ascending, no repeats, padded at the end with -1; pitch is at
+// most EXCLUDE_MAX.  Read as unsigned the whole row is ascending (the padding is the largest word), so one binary search over all `n`
+// words serves every list length.  An id at or beyond N names no row and matches nothing.  A row that breaks the contract (unsorted,
+// repeats, a negative other than the padding) may drop the wrong keys or leave a short result; every probe stays inside [list, list + n),
+// and no value of the list is ever used as an address.
+#define EXCLUDE_MAX SEARCH_EXCLUDE_MAX
+struct RowExclusions {
+  const int32_t* ids;      // nullptr: no exclusion list in the call
+  int64_t pitch;
+};
+__device__ __forceinline__ bool row_excluded(const int32_t* list, int n, uint32_t row) {
+  if (row > 0x7fffffffu) return false;               // an int32 list cannot name it (and the padding must not match it)
+  int lo = 0, hi = n;                                // the first word >= row is in [lo, hi]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((uint32_t)list[mid] < row) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && (uint32_t)list[lo] == row;
+}
+
+// out[q] = N - e_q, the rows list q leaves, e_q its entries in [0, N) (the words below N in the unsigned order): the rank of the redo's
+// select is min(k, this).  One thread and one binary search per query.
+__global__ void count_excluded_kernel(const RowExclusions X, int64_t nq, int64_t N, unsigned* __restrict__ out) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const int32_t* list = X.ids + q * X.pitch;
+  const uint32_t bound = N > 0x7fffffffLL ? 0x80000000u : (uint32_t)N;
+  int lo = 0, hi = (int)X.pitch;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((uint32_t)list[mid] < bound) lo = mid + 1;
+    else hi = mid;
+  }
+  out[q] = (unsigned)(N - lo);
+}
+
+// drop_disallowed_kernel under the list predicate: list q compacted in place to the keys whose row is NOT in the query's exclusion list --
+// the same order, clamp and mark.  The exclusion list is staged in LDS once (at most 16 KiB) and every key costs one binary search there.
+// A query whose list is empty keeps its candidates (clamped and marked all the same), as a query under no bitmap does.
+__global__ __launch_bounds__(256) void drop_excluded_kernel(u64* __restrict__ keys, unsigned* __restrict__ cnt, const RowExclusions X,
+                                                            uint32_t nrows, unsigned* __restrict__ flag, unsigned* __restrict__ qstat) {
+  __shared__ unsigned wtot[4];
+  __shared__ int32_t ex[EXCLUDE_MAX];
+  const int64_t q = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int ne = (int)X.pitch;                       // (the entry refuses a pitch above EXCLUDE_MAX)
+  const int32_t* __restrict__ src = X.ids + q * X.pitch;
+  for (int i = tid; i < ne; i += 256) ex[i] = src[i];
+  unsigned n = cnt[q];
+  if (n > SORT_CAP) {
+    if (tid == 0) {
+      atomicOr(flag, 1u);
+      if (qstat) atomicOr(qstat + q, QSTAT_OVERFLOW);
+    }
+    n = SORT_CAP;
+  }
+  __syncthreads();                                   // the list is staged, every thread has read cnt[q]
+  if (ne == 0 || ex[0] < 0) {                        // (workgroup-uniform) nothing to exclude
+    if (tid == 0) cnt[q] = n;
+    return;
+  }
+  const unsigned out = drop_compact(keys + q * SORT_CAP, n, wtot, [&](uint32_t row) { return row < nrows && !row_excluded(ex, ne, row); });
   if (tid == 0) cnt[q] = out;
 }
 
@@ -546,9 +620,10 @@ __global__ void redo_compact_kernel(const unsigned* __restrict__ qstat, int64_t 
 }
 
 // F, n_allowed: the call's row filters and the device's count of every bitmap's rows (F.bits == nullptr: no filter, neither is read)
+// X: the call's exclusion lists (om_sim_topk_excluding; F has no bitmap then): n_allowed[q] is count_excluded_kernel's count for query q
 __global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restrict__ rs, const unsigned* __restrict__ bad, u64* __restrict__ prefix,
                                                          unsigned* __restrict__ remaining, unsigned* __restrict__ hist, unsigned want,
-                                                         const RowFilters F, const unsigned* __restrict__ n_allowed) {
+                                                         const RowFilters F, const unsigned* __restrict__ n_allowed, const RowExclusions X) {
   const unsigned n_bad = rs[REDO_RS_BAD];
   if (!n_bad) return;
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
@@ -556,13 +631,13 @@ __global__ __launch_bounds__(256) void redo_begin_kernel(const unsigned* __restr
   for (int64_t b = i0; b < n_bad; b += step) {
     // under a row filter the rank is min(k, rows the query's bitmap allows), counted on the device
     const int64_t f = filter_index(F, bad[b]);
-    const unsigned have = f == FILTER_EVERY_ROW ? want : (f == FILTER_NO_ROW ? 0u : n_allowed[f]);
+    const unsigned have = X.ids ? n_allowed[bad[b]] : (f == FILTER_EVERY_ROW ? want : (f == FILTER_NO_ROW ? 0u : n_allowed[f]));
     prefix[b] = 0;
     remaining[b] = have < want ? have : want;
   }
 }
 
-// F: the call's row filters (F.bits == nullptr: every row counts for every query).
+// F: the call's row filters (F.bits == nullptr: every row counts for every query).  X: its exclusion lists (X.ids == nullptr: none).
 // COLLECT = false: hist[b][digit at `shift`] += 1 for every row whose key agrees with prefix[b] above the digit;
 // COLLECT = true: every key >= prefix[b] (= T) appended to list bad[b].  Rows [0, N) of `index`, tiles of R rows (R * d * 4 bytes of LDS).
 // TRow = f16_t (OM_SEARCH_F16_ONLY): the tile is filled from 16-byte loads of eight halves and staged WIDENED to float32, so R, the LDS
@@ -571,7 +646,8 @@ template <bool COLLECT, typename TRow>
 __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict__ q32, const TRow* __restrict__ index, int64_t N, int d, int R,
                                                         const unsigned* __restrict__ rs, const unsigned* __restrict__ bad,
                                                         const u64* __restrict__ prefix, unsigned* __restrict__ hist, int shift, int width,
-                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt, const RowFilters F) {
+                                                        u64* __restrict__ keys, unsigned* __restrict__ cnt, const RowFilters F,
+                                                        const RowExclusions X) {
   const unsigned n_bad = rs[REDO_RS_BAD];
   if (!n_bad) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -602,8 +678,10 @@ __global__ __launch_bounds__(256) void redo_pass_kernel(const float* __restrict_
       const int64_t f = filter_index(F, q);                                  // (workgroup-uniform) the bad query's own bitmap
       if (f == FILTER_NO_ROW) continue;
       const uint32_t* __restrict__ allow = f < 0 ? nullptr : F.bits + f * F.pitch;
+      const int32_t* __restrict__ excl = X.ids ? X.ids + (int64_t)q * X.pitch : nullptr;      // the bad query's own list, served from L2
       for (int r = wave; r < nr; r += 4) {
         if (allow && !row_allowed(allow, (uint32_t)(r0 + r))) continue;      // (wave-uniform) a row the filter drops has no key
+        if (excl && row_excluded(excl, (int)X.pitch, (uint32_t)(r0 + r))) continue;      // (wave-uniform) nor has a row the list excludes
         const float sc = rescore_dot(qv, tile + (int64_t)r * d, d, lane);
         if (lane != 0) continue;
         const u64 key = pack_key(sc, (uint32_t)(r0 + r));
@@ -845,6 +923,8 @@ struct Scan {
   RowFilters filt = {nullptr, 0, 0, nullptr, 0};
   int64_t n_allowed = 0;
   unsigned* fcount = nullptr;
+  // om_sim_topk_excluding only (nullptr: no lists; never together with a bitmap): the exclusion table, fcount one device count per QUERY
+  RowExclusions excl = {nullptr, 0};
   // diagnostics, accumulated over the 16-bit run and the float32 retry (om_sim_topk publishes them, the asynchronous entry's status
   // kernel takes rounds and family): rounds, chunks redone densely or schedules started over, longest list seen by the host,
   // OM_SCAN_FAMILY_* and OM_SCAN_KERNEL_* of the last filtered round (its tail's where the round had no whole tile)
@@ -854,9 +934,13 @@ struct Scan {
   // under a row filter every selection is preceded by the drop of the keys it does not allow
   // (mark: as the selection it precedes -- the last one of the chain, behind the redo, marks no query: nothing reads the marks any more)
   int drop(bool mark = true) {
-    if (!filt.bits) return 0;
-    hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, filt, (uint32_t)N, ws.flag,
-                       mark ? qstat : nullptr);
+    if (!filt.bits && !excl.ids) return 0;
+    if (excl.ids)
+      hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, excl, (uint32_t)N, ws.flag,
+                         mark ? qstat : nullptr);
+    else
+      hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, filt, (uint32_t)N, ws.flag,
+                         mark ? qstat : nullptr);
     OM_LAUNCH_CHECK();
     return 0;
   }
@@ -897,7 +981,7 @@ struct Scan {
   void redo_pass(const AsyncWs& aw, dim3 grid, size_t lds, int R, int shift, int width) {
     with_rows([&](auto* rows) {
       hipLaunchKernelGGL((redo_pass_kernel<COLLECT, RowOf<decltype(rows)>>), grid, dim3(256), lds, s, q32, rows, N, d, R, aw.rs, aw.bad, aw.prefix,
-                         aw.hist, shift, width, ws.keys, ws.cnt, filt);
+                         aw.hist, shift, width, ws.keys, ws.cnt, filt, excl);
     });
   }
   // dense-score rows [r0, r0+n) and merge them into the lists (always exact, HBM heavy)
@@ -969,6 +1053,10 @@ struct Scan {
         hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)blocks, (unsigned)(filt.per_query ? filt.n : 1)), dim3(256), 0, s, filt, N, fcount);
         OM_LAUNCH_CHECK();
       }
+      if (excl.ids && N > 0) {                     // one word of the entry's own counts per query: the rows its list leaves
+        hipLaunchKernelGGL(count_excluded_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, excl, nq, N, fcount);
+        OM_LAUNCH_CHECK();
+      }
     }
     if (bf16 && N > 0) {
       hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
@@ -984,8 +1072,9 @@ struct Scan {
   int fast_rounds(bool bf16, SearchSchedule& sched) {
     int64_t chunks[SEARCH_SCHED_MAX];
     int64_t boot = 1;
-    sched = filt.bits ? search_schedule_filtered(bf16, nq, N, k, n_allowed, sw, chunks, SEARCH_SCHED_MAX, &boot)
-                  : search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
+    sched = excl.ids    ? search_schedule_excluding(bf16, nq, N, k, excl.pitch, sw, chunks, SEARCH_SCHED_MAX, &boot)
+            : filt.bits ? search_schedule_filtered(bf16, nq, N, k, n_allowed, sw, chunks, SEARCH_SCHED_MAX, &boot)
+                        : search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
     if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
     for (int64_t b = 0; b < boot && b * DENSE_CHUNK < N; ++b) {
       if (dense_gemm_append(b * DENSE_CHUNK, (int)std::min<int64_t>(DENSE_CHUNK, N - b * DENSE_CHUNK), bf16)) return 1;
@@ -1139,7 +1228,7 @@ struct Scan {
       // redo: a fixed chain, empty launches when no query is marked
       hipLaunchKernelGGL(redo_compact_kernel, dim3(qblocks), dim3(256), 0, s, qstat, nq, aw.rs, aw.bad);
       hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.bad, aw.prefix, aw.remaining, aw.hist,
-                         (unsigned)std::min<int64_t>(k, N), filt, (const unsigned*)fcount);
+                         (unsigned)std::min<int64_t>(k, N), filt, (const unsigned*)fcount, excl);
       OM_LAUNCH_CHECK();
       const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
       const size_t lds = (size_t)R * d * 4;
@@ -1385,6 +1474,36 @@ extern "C" int om_sim_topk_filtered_multi(int mode, const float* queries, int64_
   return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
 }
 
+// The same chain with an exclusion list per query in the bitmaps' place: the drop (drop_excluded_kernel), the count (one word per query
+// behind the asynchronous workspace) and the redo read list q.  pitch == 0 is om_sim_topk_async's chain itself.
+extern "C" size_t om_sim_topk_excluding_workspace_bytes(int64_t n_queries, int d, int k, int64_t pitch) {
+  (void)k; (void)pitch;
+  if (n_queries <= 0 || d <= 0) return 0;
+  return carve_async(n_queries, d, nullptr).total + align_up((size_t)n_queries * 4, 256);
+}
+
+extern "C" int om_sim_topk_excluding(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
+                                     const float* stats, int64_t N, int d, int k, int64_t id_offset, const int32_t* excl, int64_t pitch,
+                                     float* out_scores, int64_t* out_ids, int64_t* status, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  if (n_queries <= 0) return 0;
+  const SearchArgs a = {mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, workspace_bytes, stream};
+  Scan sc;
+  AsyncWs aw;
+  auto own = [&]() -> const char* {
+    if (pitch < 0 || pitch > EXCLUDE_MAX) return "pitch must be in [0, EXCLUDE_MAX = 4096]: the ids of one query's exclusion list (a RowFilter serves longer ones)";
+    if (!excl && pitch > 0) return "excl is null: the exclusion table of the call (pitch 0 searches all rows)";
+    return nullptr;
+  };
+  if (chain_setup(__func__, sc, aw, a, "", nullptr, own, align_up((size_t)n_queries * 4, 256),
+                  "workspace too small (om_sim_topk_excluding_workspace_bytes)")) return 1;
+  if (pitch > 0) {
+    sc.excl = RowExclusions{excl, pitch};
+    sc.fcount = (unsigned*)((char*)workspace + aw.total);      // the counts: behind the asynchronous workspace
+  }
+  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+}
+
 // ---- om_sim_topk_candidates: the exact top-k of every query over its OWN candidate rows ------------------------------------------------
 // No scan, no margin, no redo: Scan::run_candidates.  A list never holds more than k + CAND_BLOCK <= SORT_CAP keys, and keys of distinct
 // rows never tie, so there is nothing to overflow and nothing to redo.  The chain is fixed by cand_pitch alone; the cost is
@@ -1430,6 +1549,15 @@ extern "C" int om_debug_search_schedule_filtered(int mode, int64_t nq, int64_t N
   if (nq < 1 || N < 0 || k < 1 || k > K_MAX) OM_FAIL("nq >= 1, N >= 0 and k in [1,2048]");
   if (n_allowed < 0 || n_allowed > N) OM_FAIL("n_allowed must be in [0, N]");
   *n = search_schedule_filtered(search_mode_half(mode), nq, N, k, n_allowed, scan_switches(), chunks, cap < 0 ? 0 : cap, boot).n;
+  return 0;
+}
+
+extern "C" int om_debug_search_exclude_schedule(int mode, int64_t nq, int64_t N, int k, int64_t pitch, int64_t* chunks, int cap, int* n,
+                                                int64_t* boot) {
+  if (!n || !boot || (cap > 0 && !chunks)) OM_FAIL("null argument");
+  if (nq < 1 || N < 0 || k < 1 || k > K_MAX) OM_FAIL("nq >= 1, N >= 0 and k in [1,2048]");
+  if (pitch < 0 || pitch > EXCLUDE_MAX) OM_FAIL("pitch must be in [0, EXCLUDE_MAX = 4096]");
+  *n = search_schedule_excluding(search_mode_half(mode), nq, N, k, pitch, scan_switches(), chunks, cap < 0 ? 0 : cap, boot).n;
   return 0;
 }
 
@@ -1499,7 +1627,7 @@ extern "C" int om_debug_rescore_rows(int kernel, int row_dtype, const void* rows
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + R - 1) / R, (int64_t)g7_num_cus() * 4)));
     with_rows(h, r16, r32, [&](auto* r) {
       hipLaunchKernelGGL((redo_pass_kernel<true, RowOf<decltype(r)>>), grid, dim3(256), lds, s, queries, r, N, d, R, aw.rs, aw.bad, aw.prefix, aw.hist,
-                         0, 0, ws.keys, ws.cnt, RowFilters{nullptr, 0, 0, nullptr, 0});
+                         0, 0, ws.keys, ws.cnt, RowFilters{nullptr, 0, 0, nullptr, 0}, RowExclusions{nullptr, 0});
     });
   } else {
     hipLaunchKernelGGL(debug_fill_lists_kernel, dim3(nq), dim3(256), 0, s, cand, m, N, ws.keys, ws.cnt);
@@ -1630,6 +1758,33 @@ extern "C" int om_debug_drop_lists_multi(int64_t n_queries, int m, const float* 
   OM_LAUNCH_CHECK();
   hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowFilters{allow, words_pitch, n_filters, filter_of, 1},
                      nrows, ws.flag, use_qstat ? aw.qstat : (unsigned*)nullptr);
+  OM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
+                     out_rows, out_state);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// The drop under the exclusion lists of om_sim_topk_excluding: drop_excluded_kernel as that entry launches it
+extern "C" int om_debug_drop_lists_excluding(int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts,
+                                             int use_qstat, const int32_t* excl, int64_t pitch, uint32_t nrows, float* out_scores,
+                                             uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!scores || !rows || !counts) OM_FAIL("null argument: scores, rows and counts describe the lists");
+  if (n_queries < 1 || n_queries > 65535) OM_FAIL("1 to 65535 queries");
+  if (m < 1 || m > SORT_CAP) OM_FAIL("m must be in [1, 8192]");
+  if (!excl || nrows < 1) OM_FAIL("the drop needs the exclusion table (excl is null) and nrows >= 1");
+  if (pitch < 1 || pitch > EXCLUDE_MAX) OM_FAIL("pitch must be in [1, EXCLUDE_MAX = 4096]");
+  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
+  const SearchWs ws = carve_search(n_queries, 64, (char*)workspace);
+  const AsyncWs aw = carve_async(n_queries, 64, (char*)workspace);
+  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes(n_queries, 64, 1))");
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned nq = (unsigned)n_queries;
+  hipLaunchKernelGGL(debug_put_lists_kernel, dim3(nq), dim3(256), 0, s, scores, rows, counts, (const float*)nullptr, m, ws.keys, ws.cnt,
+                     ws.cnt_prev, ws.thr, ws.margin, ws.flag, aw.qstat);
+  OM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(drop_excluded_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowExclusions{excl, pitch}, nrows, ws.flag,
+                     use_qstat ? aw.qstat : (unsigned*)nullptr);
   OM_LAUNCH_CHECK();
   hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
                      out_rows, out_state);

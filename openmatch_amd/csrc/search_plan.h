@@ -187,3 +187,16 @@ static SearchSchedule search_schedule_filtered(bool half, int64_t nq, int64_t N,
   return search_schedule_rounds(search_list_estimate(half, k), search_list_estimate(half, search_k_eff(k, N, na)), b * SEARCH_DENSE_CHUNK,
                                 nq, N, sw, chunks, cap);
 }
+
+// ---- the same schedule under an exclusion list per query (om_sim_topk_excluding) ------------------------------------------------------
+// Every query may drop up to `pitch` rows, the width of the call's exclusion table (at most SEARCH_EXCLUDE_MAX ids a query), so at least
+// N - pitch rows may be returned to each: the filtered schedule for that count -- a planning number only, as the bitmaps' count is (the
+// redo's rank comes from a count of every list taken on the device).  pitch == 0 is search_schedule; N - pitch < 1 scores everything
+// densely, as n_allowed < 1 does.  What defeats it is what defeats a clustered bitmap: lists that exclude most of the head of the index
+// leave no threshold behind the bootstrap, the lists overflow and the queries are redone.  Pure.
+#define SEARCH_EXCLUDE_MAX 4096     // ids of one query's exclusion list: 16 KiB, what the drop stages in LDS
+static SearchSchedule search_schedule_excluding(bool half, int64_t nq, int64_t N, int k, int64_t pitch, const ScanSwitches sw, int64_t* chunks,
+                                                int cap, int64_t* boot) {
+  const int64_t left = N - (pitch < 0 ? 0 : pitch);
+  return search_schedule_filtered(half, nq, N, k, left < 0 ? 0 : left, sw, chunks, cap, boot);
+}

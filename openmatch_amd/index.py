@@ -178,6 +178,42 @@ def prepare_candidates(cand: torch.Tensor, ntotal: int):
     return c.to(torch.int32).contiguous(), bad
 
 
+EXCLUDE_MAX = 4096         # include/openmatch_hip.h OM_EXCLUDE_MAX: the ids of one query's exclusion list
+
+
+def prepare_exclusions(excl, ntotal: int, device=None):
+    """The exclusion table of `om_sim_topk_excluding` from a caller's lists: a [Q, E] integer tensor or array padded with -1, or a sequence
+    of per-query id sequences (ragged; a Python loop over the queries pads them, the tensor form has none).  Returns int32 [Q, pitch] on
+    `device` (default: where the ids are): every row ascending, a repeated id kept once, negatives and the padding moved to the end as
+    -1, `pitch` the longest cleaned list (0: nothing is excluded).  An id at or beyond `ntotal` is legal and matches no row; one at or
+    beyond 2^31 cannot be named by the int32 table and is dropped, which is the same thing.  More than EXCLUDE_MAX ids for one query
+    raise ValueError (a `RowFilter(..., invert=True)` serves longer lists).  Torch ops only; reading `pitch` back is the one
+    synchronisation on a device tensor."""
+    if int(ntotal) >= 2 ** 31:
+        raise ValueError("exclusion lists name rows as int32: the index holds 2^31 rows or more")
+    if isinstance(excl, np.ndarray):
+        excl = torch.from_numpy(excl)
+    elif not isinstance(excl, torch.Tensor):
+        rows = [[int(v) for v in (r.tolist() if hasattr(r, "tolist") else r)] for r in excl]
+        width = max([len(r) for r in rows], default=0)
+        excl = torch.tensor([r + [-1] * (width - len(r)) for r in rows], dtype=torch.int64).reshape(len(rows), width)
+    if excl.dim() != 2 or excl.dtype.is_floating_point or excl.dtype == torch.bool:
+        raise ValueError("excl must be [Q, E] integer row ids padded with -1, or a sequence of per-query id sequences")
+    c = excl.to(torch.int64)
+    if device is not None:
+        c = c.to(device)
+    big = 2 ** 31                                      # sorts behind every id an int32 can name
+    c, _ = torch.sort(torch.where((c < 0) | (c >= big), torch.full_like(c, big), c), dim=1)
+    if c.shape[1] > 1:                                 # a repeat becomes padding, and a second sort moves it to the end
+        repeat = c[:, 1:] == c[:, :-1]
+        c, _ = torch.sort(torch.cat([c[:, :1], torch.where(repeat, torch.full_like(c[:, 1:], big), c[:, 1:])], dim=1), dim=1)
+    pitch = int((c < big).sum(1).max().item()) if c.numel() else 0
+    if pitch > EXCLUDE_MAX:
+        raise ValueError(f"{pitch} ids excluded for one query: at most EXCLUDE_MAX = {EXCLUDE_MAX} (RowFilter(..., invert=True) serves longer lists)")
+    c = c[:, :pitch]
+    return torch.where(c >= big, torch.full_like(c, -1), c).to(torch.int32).contiguous()
+
+
 class RowFilter:
     """The rows of one index a filtered search may return: a bitmap over [0, ntotal) shared by all queries of a call.
     allowed: a bool mask [ntotal], or a tensor / array / sequence of row ids (`invert=True`: the ids are an exclusion list).
@@ -551,6 +587,60 @@ class FlatIPIndex:
         """faiss-style, as `search`: numpy in, (D, I) numpy out."""
         q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
         D, I = self.search_device_candidates(q, k, cand)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- exclusion lists: every row but a few that differ per query ----------------------------
+    def _enqueue_excluding(self, q, D, I, mode, k, table, id_offset):
+        """om_sim_topk_excluding over all rows under `table` (int32 [Q, pitch] on the device, as `prepare_exclusions` leaves it), in
+        chunks of at most 32 768 queries.  Returns the (workspace, status) pairs a handle keeps alive."""
+        lib = N.lib()
+        step = 32768
+        chunks = []
+        if table.dtype != torch.int32 or table.device != self.device or table.dim() != 2 or table.shape[0] != q.shape[0]:
+            raise ValueError("the exclusion table must be int32 [Q, pitch] on the index's device")
+        table = table.contiguous()
+        pitch = int(table.shape[1])
+        with torch.cuda.device(self.device):
+            for s in range(0, q.shape[0], step):
+                n = min(step, q.shape[0] - s)
+                nbytes = lib.om_sim_topk_excluding_workspace_bytes(n, self.dpad, k, pitch)
+                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
+                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
+                status = torch.zeros(8, dtype=torch.int64, device=self.device)
+                N.check(lib.om_sim_topk_excluding(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16), N.ptr(self._stats), self.ntotal,
+                                                  self.dpad, k, int(id_offset), N.ptr(table[s:s + n]) if pitch else None, pitch,
+                                                  N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
+                                                  N.stream_ptr(self.device)))
+                chunks.append((buf, status))
+        return chunks
+
+    def search_device_excluding_async(self, queries: torch.Tensor, k: int, excl, id_offset: int = 0):
+        """The exact top-k of query q over every row but those of ITS OWN exclusion list `excl[q]`, stream-ordered: per query what an index
+        of the same precision without those rows returns, with the ORIGINAL row numbers (+ `id_offset`), (-3.4028235e38, -1) padded when
+        fewer than k rows remain.  excl: what `prepare_exclusions` takes -- [Q, E] integer ids padded with -1, or a sequence of per-query
+        id sequences; at most EXCLUDE_MAX ids a query; ids the index does not hold match nothing.  Preparing the table reads its pitch
+        back (one synchronisation); an int32 [Q, pitch] tensor on the index's device is taken as ALREADY prepared and nothing is read,
+        which is the form a graph captures.  Returns a `SearchHandle`; its `info()` adds `route` = 'exclude' and `pitch`."""
+        q, D, I, mode = self._search_args(queries, k)
+        prepared = isinstance(excl, torch.Tensor) and excl.dtype == torch.int32 and excl.device == self.device and excl.dim() == 2
+        table = excl if prepared else prepare_exclusions(excl, self.ntotal, device=self.device)
+        if table.shape[0] != q.shape[0]:
+            raise ValueError(f"{table.shape[0]} exclusion lists for {q.shape[0]} queries")
+        if table.shape[1] > EXCLUDE_MAX:
+            raise ValueError(f"{table.shape[1]} ids excluded for one query: at most EXCLUDE_MAX = {EXCLUDE_MAX}")
+        chunks = self._enqueue_excluding(q, D, I, mode, k, table, id_offset)
+        return SearchHandle(D, I, q, chunks, self.device, {"route": "exclude", "pitch": int(table.shape[1]), "_keep": table})
+
+    def search_device_excluding(self, queries: torch.Tensor, k: int, excl, id_offset: int = 0):
+        """`search_device_excluding_async`, waited for: (D, I) on the GPU, and `last_search_info` with `route`, `pitch` and `redone`."""
+        h = self.search_device_excluding_async(queries, k, excl, id_offset=id_offset)
+        self.last_search_info = h.info()
+        return h.D, h.I
+
+    def search_excluding(self, x, k: int, excl):
+        """faiss-style, as `search`: numpy in, (D, I) numpy out."""
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
+        D, I = self.search_device_excluding(q, k, excl)
         return D.cpu().numpy(), I.cpu().numpy()
 
     # -- a filter per query --------------------------------------------------------------------

@@ -372,6 +372,13 @@ _SIGNATURES = {
     "om_sim_topk_filtered_multi_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int64]),
     "om_sim_topk_filtered_multi": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
                                            c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_sim_topk_excluding_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int64]),
+    "om_sim_topk_excluding": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "om_debug_search_exclude_schedule": (c_int, [c_int, c_int64, c_int64, c_int, c_int64, C.POINTER(c_int64), c_int, C.POINTER(c_int),
+                                                 C.POINTER(c_int64)]),
+    "om_debug_drop_lists_excluding": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, C.c_uint32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "om_sim_topk_candidates_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "om_sim_topk_candidates": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -31,7 +31,7 @@ from ..dataset import DRInferenceCollator
 from ..feed import model_batch
 from ..index import FlatIPIndex, RowFilter, merge_topk, sharded_topk
 from ..modeling import DRModelForInference, DROutput
-from ..utils import merge_retrieval_results_by_score
+from ..utils import merge_retrieval_results_by_score, qrel_positives, sample_hard_negatives
 
 logger = logging.getLogger(__name__)
 
@@ -236,19 +236,33 @@ class Retriever:
         by_qid = {str(qid): docs for qid, docs in doc_filters.items()}
         return [sorted({row_of[str(doc)] for doc in by_qid[str(qid)] if str(doc) in row_of}) if str(qid) in by_qid else None for qid in qids]
 
-    def search(self, topk: int = 100, doc_filter=None, doc_filters=None):
+    def _doc_exclusions(self, exclude, qids):
+        """`exclude` ({query id: collection of doc ids}; a qrel's {docid: grade} works, every doc of it is excluded) -> per query of `qids`
+        the rows of its documents through `doc_lookup` (doc ids the index does not hold are ignored), [] for a query id the mapping does
+        not hold: that query excludes nothing."""
+        row_of = {str(doc): row for row, doc in enumerate(self.doc_lookup)}
+        by_qid = {str(qid): docs for qid, docs in exclude.items()}
+        return [sorted({row_of[str(doc)] for doc in by_qid.get(str(qid), ()) if str(doc) in row_of}) for qid in qids]
+
+    def search(self, topk: int = 100, doc_filter=None, doc_filters=None, exclude=None):
         """doc_filter: None, or a collection of doc ids: only those documents are returned (an exact filtered search:
         `FlatIPIndex.search_filtered`).  Where fewer than `topk` of them are in the index a query gets that many hits and no more:
         the search's padding is dropped, not mapped to a document as the unfiltered path's is (`_hits_to_dict`).
         doc_filters: None, or a mapping from query id to a collection of doc ids -- a first-stage run as `load_from_trec` returns it
         works: every query is scored over ITS OWN documents (`FlatIPIndex.search_candidates`: dense re-ranking, no bitmap anywhere).  A
-        query id the mapping does not hold is searched unfiltered; one with an empty collection gets no hits; padding is dropped."""
+        query id the mapping does not hold is searched unfiltered; one with an empty collection gets no hits; padding is dropped.
+        exclude: None, or a mapping from query id to a collection of doc ids that query must NOT return -- its known positives, when
+        mining hard negatives: an exact search over every other document (`FlatIPIndex.search_excluding`, at most
+        `openmatch_amd.index.EXCLUDE_MAX` documents a query).  Doc ids the index does not hold are ignored, a query id the mapping does not
+        hold excludes nothing; padding is dropped."""
         logger.info("Searching")
         if self.index is None:
             raise ValueError("Index is not initialized")
         if doc_filter is not None and doc_filters is not None:
             raise ValueError("give doc_filter (one set of documents for all queries) or doc_filters (one per query), not both")
-        if (doc_filter is not None or doc_filters is not None) and (self._sharded or self.args.world_size > 1):
+        if exclude is not None and (doc_filter is not None or doc_filters is not None):
+            raise ValueError("give exclude (documents a query must not return) or a doc_filter / doc_filters (documents it may), not both")
+        if (doc_filter is not None or doc_filters is not None or exclude is not None) and (self._sharded or self.args.world_size > 1):
             raise NotImplementedError("doc_filter with an index sharded across ranks: the filtered search serves one local index only")
         if self._sharded:
             return self._search_sharded(topk)
@@ -271,11 +285,23 @@ class Retriever:
             if not own.all():
                 D[~own], I[~own] = self.index.search(encoded[~own], topk)
             drop = own
+        elif exclude is not None:
+            D, I = self.index.search_excluding(encoded, topk, self._doc_exclusions(exclude, self.query_lookup[:len(encoded)]))
+            drop = True
         else:
             D, I = self.index.search(encoded, topk)
         result = self._hits_to_dict(D, I, topk, drop_padding=drop)
         logger.info("End searching with {} queries".format(len(result)))
         return result
+
+    def mine_hard_negatives(self, qrels, depth: int = 200, n_sample: int = 30, seed=None):
+        """Hard negatives for the next training round (the reference's "update the negatives" step, scripts/msmarco/build_hn.py): ONE
+        search of the encoded queries for `depth` hits that excludes every query's positives (`qrels`: {qid: {docid: grade}}, positive
+        above 0, or {qid: collection of positive doc ids}), then `n_sample` of them drawn without replacement by
+        `utils.sample_hard_negatives`.  The positives are dropped inside the search, so a query gets a full `depth` of negatives to draw
+        from where the reference's run of `depth` hits leaves `depth` minus the positives found.  Returns {qid: (positives, negatives)}."""
+        run = self.search(depth, exclude={qid: qrel_positives(judged) for qid, judged in qrels.items()})
+        return sample_hard_negatives(run, qrels, n_sample=n_sample, depth=depth, seed=seed)
 
     def _search_sharded(self, topk):
         """Collective over all ranks: all-gather the queries, search the local shard, then merge BY QUERY RANGE --

@@ -84,6 +84,33 @@ def merge_retrieval_results_by_score(results: List[Dict[str, Dict[str, float]]],
             for qid, hits in merged.items()}
 
 
+def qrel_positives(judged):
+    """The positives of one query: the doc ids with a grade above 0 of a {docid: grade} mapping, or every id of a plain collection
+    (what `SimpleTrainPreProcessor.read_qrel` returns), as strings in their order."""
+    if isinstance(judged, dict):
+        return [str(doc) for doc, grade in judged.items() if grade > 0]
+    return [str(doc) for doc in judged]
+
+
+def sample_hard_negatives(run: Dict[str, Dict[str, float]], qrel, n_sample: int = 30, depth: int = 200, seed=None):
+    """Hard negatives from a run, as `load_ranking` of the reference's scripts/msmarco/build_hn.py takes them from a TREC file: per query of
+    `run` ({qid: {docid: score}}) the hits by descending score (ties keep the run's order) without the query's positives, the first
+    `depth` of those, shuffled, the first `n_sample` of that.  qrel: {qid: {docid: grade}} (positive: grade > 0) or {qid: collection of
+    positive doc ids}; a query without an entry has no positives.  One `random.Random(seed)` serves all queries in the run's order, so a
+    seed fixes the result.  Returns {qid: (positives, negatives)}; a query with fewer than `n_sample` candidates keeps them all."""
+    import random
+    rng = random.Random(seed)
+    out = {}
+    for qid, hits in run.items():
+        positives = qrel_positives(qrel.get(qid, qrel.get(str(qid), ())))
+        known = set(positives)
+        ranked = sorted(hits.items(), key=lambda kv: kv[1], reverse=True)
+        negatives = [str(doc) for doc, _score in ranked if str(doc) not in known][:depth]
+        rng.shuffle(negatives)
+        out[qid] = (positives, negatives[:n_sample])
+    return out
+
+
 def mean_pooling(token_embeddings, attention_mask):
     """Mask-weighted mean over the sequence axis; empty masks divide by 1e-9 (reference :233-235)."""
     mask = attention_mask.unsqueeze(-1).expand(token_embeddings.size()).float()
