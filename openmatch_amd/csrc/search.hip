@@ -913,39 +913,77 @@ static int pinned_words(unsigned*& out) {
 }
 
 namespace {
+// Which rows a query may return: everything the chain knows about the restriction of a call.  Three encodings, at most one in a call: one
+// bitmap for every query (om_sim_topk_filtered), a bitmap per query (om_sim_topk_filtered_multi), an exclusion list per query
+// (om_sim_topk_excluding); the default rule restricts nothing, and not one launch differs under it.  filt and excl are what the kernels
+// take.  drop, count, schedule and place are the only places that ask which kind a rule is.
+struct RowRule {
+  RowFilters filt = {};          // (bits == nullptr: no bitmap)
+  RowExclusions excl = {};       // (ids == nullptr: no lists)
+  int64_t planned = 0;           // what the schedule is planned from: the rows the (sparsest) bitmap allows, or the pitch of the lists
+  unsigned* fcount = nullptr;    // the device's counts of the rows left, set by place: one word, one per bitmap, or one per query (lists)
+  size_t extra_bytes = 0;        // what those counts need behind the asynchronous workspace
+
+  static RowRule bitmap(const uint32_t* bits, int64_t n_allowed) { return {{bits, 0, 1, nullptr, 0}, {}, n_allowed, nullptr, 0}; }
+  static RowRule bitmaps(const uint32_t* bits, int64_t pitch, int64_t n, const int32_t* of, int64_t n_allowed_min) {
+    return {{bits, pitch, n, of, 1}, {}, n_allowed_min, nullptr, align_up((size_t)n * 4, 256)};
+  }
+  // (pitch == 0: no list, the unrestricted chain itself -- the entry's workspace is sized for the counts all the same)
+  static RowRule exclusions(const int32_t* ids, int64_t pitch, int64_t nq) {
+    return {{}, {pitch > 0 ? ids : nullptr, pitch}, pitch, nullptr, align_up((size_t)nq * 4, 256)};
+  }
+
+  // the drop in front of a selection: list q compacted to the keys whose row the rule leaves query q; qstat: the marks, or nullptr
+  int drop(const SearchWs& ws, int64_t nq, uint32_t nrows, unsigned* qstat, hipStream_t s) const {
+    if (!excl.ids && !filt.bits) return 0;
+    if (excl.ids)
+      hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, excl, nrows, ws.flag, qstat);
+    else
+      hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, filt, nrows, ws.flag, qstat);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
+  // fcount = the rows the rule leaves among [0, N), counted on the device behind the kernel that zeroes rs: the ranks of the redo
+  int count(int64_t nq, int64_t N, hipStream_t s) const {
+    if (N <= 0 || (!excl.ids && !filt.bits)) return 0;
+    // bitmaps: one grid row and one word per bitmap, added to -- the words of per-query bitmaps are the entry's own, zeroed here
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(((N + 31) / 32 + 255) / 256, 1024));
+    if (filt.per_query) OM_HIP(hipMemsetAsync(fcount, 0, (size_t)filt.n * 4, s));
+    if (excl.ids)
+      hipLaunchKernelGGL(count_excluded_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, excl, nq, N, fcount);
+    else
+      hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)blocks, (unsigned)(filt.per_query ? filt.n : 1)), dim3(256), 0, s, filt, N, fcount);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
+  // the fast schedule under the rule (search_plan.h): `boot` dense chunks, then the rounds in `chunks` [SEARCH_SCHED_MAX]
+  SearchSchedule schedule(bool bf16, int64_t nq, int64_t N, int k, const ScanSwitches& sw, int64_t* chunks, int64_t* boot) const {
+    return excl.ids    ? search_schedule_excluding(bf16, nq, N, k, planned, sw, chunks, SEARCH_SCHED_MAX, boot)
+           : filt.bits ? search_schedule_filtered(bf16, nq, N, k, planned, sw, chunks, SEARCH_SCHED_MAX, boot)
+                       : search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
+  }
+  // where the counts live: one bitmap's in the redo's own words, per-query bitmaps' and lists' behind the asynchronous workspace
+  void place(void* workspace, const AsyncWs& aw) {
+    fcount = excl.ids || filt.per_query ? (unsigned*)((char*)workspace + aw.total) : filt.bits ? aw.rs + REDO_RS_ALLOWED : nullptr;
+  }
+};
+
 struct Scan {
   int mode; const float* q32; const float* idx32; const f16_t* idx16; int64_t nq, N; int d, k;
   SearchWs ws; hipStream_t s;
   unsigned* qstat = nullptr;      // per-query sticky status: the asynchronous entry only
   ScanSwitches sw;                // the thread's switches, read once by the entry
-  // om_sim_topk_filtered only (nullptr: no filter, and not one launch differs): the bitmap over rows [0, N) and the host's count of its bits
-  // (om_sim_topk_filtered_multi: the bitmaps of the call, n_allowed the count of the sparsest one in use, fcount one device count per bitmap)
-  RowFilters filt = {nullptr, 0, 0, nullptr, 0};
-  int64_t n_allowed = 0;
-  unsigned* fcount = nullptr;
-  // om_sim_topk_excluding only (nullptr: no lists; never together with a bitmap): the exclusion table, fcount one device count per QUERY
-  RowExclusions excl = {nullptr, 0};
+  RowRule rule;                   // which rows a query may return (the default: every row)
   // diagnostics, accumulated over the 16-bit run and the float32 retry (om_sim_topk publishes them, the asynchronous entry's status
   // kernel takes rounds and family): rounds, chunks redone densely or schedules started over, longest list seen by the host,
   // OM_SCAN_FAMILY_* and OM_SCAN_KERNEL_* of the last filtered round (its tail's where the round had no whole tile)
   int64_t rounds = 0, fallbacks = 0, max_list = 0;
   int family = 0, launch = 0;
 
-  // under a row filter every selection is preceded by the drop of the keys it does not allow
-  // (mark: as the selection it precedes -- the last one of the chain, behind the redo, marks no query: nothing reads the marks any more)
-  int drop(bool mark = true) {
-    if (!filt.bits && !excl.ids) return 0;
-    if (excl.ids)
-      hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, excl, (uint32_t)N, ws.flag,
-                         mark ? qstat : nullptr);
-    else
-      hipLaunchKernelGGL(drop_disallowed_kernel, dim3((unsigned)nq), dim3(256), 0, s, ws.keys, ws.cnt, filt, (uint32_t)N, ws.flag,
-                         mark ? qstat : nullptr);
-    OM_LAUNCH_CHECK();
-    return 0;
-  }
+  // under a row rule every selection is preceded by the drop of the keys it does not allow
+  // (mark: the drop as the selection -- the last one of the chain, behind the redo, marks no query: nothing reads the marks any more)
   int select(bool certified, bool mark = true) {
-    if (drop(mark)) return 1;
+    if (rule.drop(ws, nq, (uint32_t)N, mark ? qstat : nullptr, s)) return 1;
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s,
                        ws.keys, ws.cnt, ws.cnt_prev, ws.thr, certified ? ws.margin : nullptr, k,
                        ws.flag, mark ? qstat : nullptr);
@@ -953,7 +991,7 @@ struct Scan {
     return 0;
   }
   int select_radix(bool certified, int cap = SORT_CAP) {
-    if (drop()) return 1;
+    if (rule.drop(ws, nq, (uint32_t)N, qstat, s)) return 1;
     hipLaunchKernelGGL(select_radix_kernel, dim3((unsigned)nq), dim3(256), (size_t)cap * 8 + 1024 + 64, s,
                        ws.keys, ws.cnt, ws.thr, certified ? ws.margin : nullptr, k, ws.flag, cap, qstat);
     OM_LAUNCH_CHECK();
@@ -981,7 +1019,7 @@ struct Scan {
   void redo_pass(const AsyncWs& aw, dim3 grid, size_t lds, int R, int shift, int width) {
     with_rows([&](auto* rows) {
       hipLaunchKernelGGL((redo_pass_kernel<COLLECT, RowOf<decltype(rows)>>), grid, dim3(256), lds, s, q32, rows, N, d, R, aw.rs, aw.bad, aw.prefix,
-                         aw.hist, shift, width, ws.keys, ws.cnt, filt, excl);
+                         aw.hist, shift, width, ws.keys, ws.cnt, rule.filt, rule.excl);
     });
   }
   // dense-score rows [r0, r0+n) and merge them into the lists (always exact, HBM heavy)
@@ -1046,17 +1084,7 @@ struct Scan {
     if (aw) {
       hipLaunchKernelGGL(async_init_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, aw->qstat, aw->rs, status, nq);
       OM_LAUNCH_CHECK();
-      if (filt.bits && N > 0) {                    // behind the kernel that zeroes rs
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(((N + 31) / 32 + 255) / 256, 1024));
-        // one bitmap: counted into rs[REDO_RS_ALLOWED]; a bitmap per query: one grid row and one word of the entry's own counts per bitmap
-        if (filt.per_query) OM_HIP(hipMemsetAsync(fcount, 0, (size_t)filt.n * 4, s));
-        hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)blocks, (unsigned)(filt.per_query ? filt.n : 1)), dim3(256), 0, s, filt, N, fcount);
-        OM_LAUNCH_CHECK();
-      }
-      if (excl.ids && N > 0) {                     // one word of the entry's own counts per query: the rows its list leaves
-        hipLaunchKernelGGL(count_excluded_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, excl, nq, N, fcount);
-        OM_LAUNCH_CHECK();
-      }
+      if (rule.count(nq, N, s)) return 1;
     }
     if (bf16 && N > 0) {
       hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)(((nq + 255) / 256 * 256 + 3) / 4)), dim3(256), 0, s, q32,
@@ -1068,13 +1096,11 @@ struct Scan {
   // The fast schedule's rounds, for both entries (N > DENSE_CHUNK): the dense bootstrap and its selection, then per round the filtered
   // scan and a radix selection, which also flags overflows -- back to back, nothing read by the host.  The list estimate, the growth
   // per round, the selection's LDS copy and the chunks are search_plan.h's search_schedule, returned in `sched`.
-  // Under a row filter the schedule is search_schedule_filtered's: `boot` dense chunks, each with its drop and selection, then the rounds.
+  // Under a row rule the schedule is the rule's: `boot` dense chunks, each with its drop and selection, then the rounds.
   int fast_rounds(bool bf16, SearchSchedule& sched) {
     int64_t chunks[SEARCH_SCHED_MAX];
     int64_t boot = 1;
-    sched = excl.ids    ? search_schedule_excluding(bf16, nq, N, k, excl.pitch, sw, chunks, SEARCH_SCHED_MAX, &boot)
-            : filt.bits ? search_schedule_filtered(bf16, nq, N, k, n_allowed, sw, chunks, SEARCH_SCHED_MAX, &boot)
-                        : search_schedule(bf16, nq, N, k, sw, chunks, SEARCH_SCHED_MAX);
+    sched = rule.schedule(bf16, nq, N, k, sw, chunks, &boot);
     if (sched.n > SEARCH_SCHED_MAX) OM_FAIL("schedule has too many rounds");
     for (int64_t b = 0; b < boot && b * DENSE_CHUNK < N; ++b) {
       if (dense_gemm_append(b * DENSE_CHUNK, (int)std::min<int64_t>(DENSE_CHUNK, N - b * DENSE_CHUNK), bf16)) return 1;
@@ -1228,7 +1254,7 @@ struct Scan {
       // redo: a fixed chain, empty launches when no query is marked
       hipLaunchKernelGGL(redo_compact_kernel, dim3(qblocks), dim3(256), 0, s, qstat, nq, aw.rs, aw.bad);
       hipLaunchKernelGGL(redo_begin_kernel, dim3(256), dim3(256), 0, s, aw.rs, aw.bad, aw.prefix, aw.remaining, aw.hist,
-                         (unsigned)std::min<int64_t>(k, N), filt, (const unsigned*)fcount, excl);
+                         (unsigned)std::min<int64_t>(k, N), rule.filt, (const unsigned*)rule.fcount, rule.excl);
       OM_LAUNCH_CHECK();
       const int R = (int)std::max<int64_t>(1, std::min<int64_t>(32, REDO_TILE_BYTES / ((int64_t)d * 4)));
       const size_t lds = (size_t)R * d * 4;
@@ -1303,7 +1329,7 @@ struct Scan {
 // The arguments every scanning entry takes, as scan_setup and chain_setup read them
 struct SearchArgs {
   int mode; const float* queries; int64_t n_queries; const float* index_f32; const void* index_f16; const float* stats; int64_t N; int d, k;
-  const float* out_scores; const int64_t* out_ids; void* workspace; size_t workspace_bytes; void* stream;
+  float* out_scores; int64_t* out_ids; void* workspace; size_t workspace_bytes; void* stream;
 };
 
 // The argument checks and the set-up the entries share (n_queries > 0).  Returns the refusal, nullptr when there is none: the entry
@@ -1353,10 +1379,10 @@ static int search_attrs() {
 // What the four entries that run the stream-ordered chain (Scan::run_async) do before it, in the order of their refusals: scan_setup; what
 // OM_SEARCH_F16_ONLY refuses; d above the redo's tile and OM_OPT_SCAN_GEN7 = 0, both ending in `tail` (`early`: a refusal the entry has
 // already found, or nullptr -- it is reported between the two); own(), the entry's other argument checks, a refusal or nullptr; the
-// asynchronous workspace with `extra` bytes of the entry's own behind it (`ws_refusal` when it does not fit); qstat; the kernel
-// attributes.  A refusal fails under the entry's name, as OM_FAIL would in its body.
+// asynchronous workspace with what sc.rule needs behind it (`ws_refusal` when it does not fit); qstat and the rule's counts placed; the
+// kernel attributes.  A refusal fails under the entry's name, as OM_FAIL would in its body.
 template <typename Own>
-static int chain_setup(const char* entry, Scan& sc, AsyncWs& aw, const SearchArgs& a, const char* tail, const char* early, Own own, size_t extra,
+static int chain_setup(const char* entry, Scan& sc, AsyncWs& aw, const SearchArgs& a, const char* tail, const char* early, Own own,
                        const char* ws_refusal) {
   auto fail = [&](const std::string& why) { om_set_error(std::string(entry) + ": " + why); return 1; };
   if (const char* why = scan_setup(sc, a)) return fail(why);
@@ -1367,10 +1393,25 @@ static int chain_setup(const char* entry, Scan& sc, AsyncWs& aw, const SearchArg
   if (!sc.sw.gen7) return fail(std::string("OM_OPT_SCAN_GEN7 is 0: the fast schedule this entry runs is switched off") + tail);
   if (const char* why = own()) return fail(why);
   aw = carve_async(a.n_queries, a.d, (char*)a.workspace);
-  if (aw.total + extra > a.workspace_bytes) return fail(ws_refusal);
+  if (aw.total + sc.rule.extra_bytes > a.workspace_bytes) return fail(ws_refusal);
   sc.qstat = aw.qstat;
+  sc.rule.place(a.workspace, aw);
   return search_attrs();
 }
+
+// The stream-ordered search under `rule`, for the entries below (n_queries > 0): chain_setup, then the chain.  The rule adds the count
+// of the rows it leaves behind the init, the drop in front of every selection, its own schedule and the redo's row test.
+template <typename Own>
+static int chain_entry(const char* entry, const SearchArgs& a, int64_t id_offset, int64_t* status, const RowRule& rule, const char* tail,
+                       const char* early, Own own, const char* ws_refusal) {
+  Scan sc;
+  sc.rule = rule;
+  AsyncWs aw;
+  if (chain_setup(entry, sc, aw, a, tail, early, own, ws_refusal)) return 1;
+  return sc.run_async(search_mode_half(a.mode), aw, id_offset, a.out_scores, a.out_ids, status);
+}
+// the workspace of such an entry: the asynchronous one and the rule's counts behind it
+static size_t chain_workspace_bytes(int64_t nq, int d, const RowRule& rule) { return carve_async(nq, d, nullptr).total + rule.extra_bytes; }
 
 extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
                            const float* index_f32, const void* index_f16, const float* stats,
@@ -1382,8 +1423,8 @@ extern "C" int om_sim_topk(int mode, const float* queries, int64_t n_queries,
   Scan sc;
   if (mode == OM_SEARCH_F16_ONLY) {
     AsyncWs aw;
-    if (chain_setup(__func__, sc, aw, a, "", nullptr, no_own_checks, 0,
-                    "workspace too small: OM_SEARCH_F16_ONLY needs om_sim_topk_async_workspace_bytes")) return 1;
+    if (chain_setup(__func__, sc, aw, a, "", nullptr, no_own_checks, "workspace too small: OM_SEARCH_F16_ONLY needs om_sim_topk_async_workspace_bytes"))
+      return 1;
     for (auto& v : g_info) v = 0;
     unsigned redo[3] = {0, 0, 0};
     const int rc = sc.run_sync16(aw, id_offset, out_scores, out_ids, redo);
@@ -1410,43 +1451,33 @@ extern "C" int om_sim_topk_async(int mode, const float* queries, int64_t n_queri
                                  void* stream) {
   if (n_queries <= 0) return 0;
   const SearchArgs a = {mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, workspace_bytes, stream};
-  Scan sc;
-  AsyncWs aw;
-  if (chain_setup(__func__, sc, aw, a, " (use om_sim_topk)",
-                  status ? nullptr : "status is null: the asynchronous entry reports through 8 x int64 of device memory", no_own_checks, 0,
-                  "workspace too small (om_sim_topk_async_workspace_bytes)")) return 1;
-  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+  return chain_entry(__func__, a, id_offset, status, RowRule{}, " (use om_sim_topk)",
+                     status ? nullptr : "status is null: the asynchronous entry reports through 8 x int64 of device memory", no_own_checks,
+                     "workspace too small (om_sim_topk_async_workspace_bytes)");
 }
 
-// The stream-ordered search under a row filter: om_sim_topk_async's chain (Scan::run_async itself) with the bitmap set, which adds the
-// count of the allowed rows behind the init, the drop in front of every selection, the filtered schedule and the redo's row test.
+// The stream-ordered search under a row filter: one bitmap over rows [0, N) for every query, n_allowed the host's count of its bits.
 extern "C" int om_sim_topk_filtered(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
                                     const float* stats, int64_t N, int d, int k, int64_t id_offset, const uint32_t* allow_bits,
                                     int64_t n_allowed, float* out_scores, int64_t* out_ids, int64_t* status, void* workspace,
                                     size_t workspace_bytes, void* stream) {
   if (n_queries <= 0) return 0;
   const SearchArgs a = {mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, workspace_bytes, stream};
-  Scan sc;
-  AsyncWs aw;
   auto own = [&]() -> const char* {
     if (!allow_bits) return "allow_bits is null: the filtered search needs the bitmap of the allowed rows (om_sim_topk_async searches all rows)";
     if (n_allowed < 0 || n_allowed > N) return "n_allowed must be in [0, N]";
     return nullptr;
   };
-  if (chain_setup(__func__, sc, aw, a, "", nullptr, own, 0, "workspace too small (om_sim_topk_filtered_workspace_bytes)")) return 1;
-  sc.filt = RowFilters{allow_bits, 0, 1, nullptr, 0};
-  sc.n_allowed = n_allowed;
-  sc.fcount = aw.rs + REDO_RS_ALLOWED;
-  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+  return chain_entry(__func__, a, id_offset, status, RowRule::bitmap(allow_bits, n_allowed), "", nullptr, own,
+                     "workspace too small (om_sim_topk_filtered_workspace_bytes)");
 }
 
 // The same chain with a bitmap per query: the three kernels that read a bitmap -- the drop, the count, the redo -- take it from
-// filter_of[q]; one count per bitmap lives in n_filters words behind the asynchronous workspace.  The schedule is the single-filter one of
-// the sparsest bitmap in use (search_plan.h).
+// filter_of[q].  The schedule is the single-filter one of the sparsest bitmap in use (search_plan.h).
 extern "C" size_t om_sim_topk_filtered_multi_workspace_bytes(int64_t n_queries, int d, int k, int64_t n_filters) {
   (void)k;
   if (n_queries <= 0 || d <= 0 || n_filters < 1) return 0;
-  return carve_async(n_queries, d, nullptr).total + align_up((size_t)n_filters * 4, 256);
+  return chain_workspace_bytes(n_queries, d, RowRule::bitmaps(nullptr, 0, n_filters, nullptr, 0));
 }
 
 extern "C" int om_sim_topk_filtered_multi(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
@@ -1456,8 +1487,6 @@ extern "C" int om_sim_topk_filtered_multi(int mode, const float* queries, int64_
                                           void* stream) {
   if (n_queries <= 0) return 0;
   const SearchArgs a = {mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, workspace_bytes, stream};
-  Scan sc;
-  AsyncWs aw;
   auto own = [&]() -> const char* {
     if (!allow_bits) return "allow_bits is null: the filtered search needs the bitmaps of the allowed rows (om_sim_topk_async searches all rows)";
     if (n_filters < 1 || n_filters > 65535) return "n_filters must be in [1, 65535]";
@@ -1466,20 +1495,16 @@ extern "C" int om_sim_topk_filtered_multi(int mode, const float* queries, int64_
     if (n_allowed_min < 0 || n_allowed_min > N) return "n_allowed_min must be in [0, N]";
     return nullptr;
   };
-  if (chain_setup(__func__, sc, aw, a, "", nullptr, own, align_up((size_t)n_filters * 4, 256),
-                  "workspace too small (om_sim_topk_filtered_multi_workspace_bytes)")) return 1;
-  sc.filt = RowFilters{allow_bits, words_pitch, n_filters, filter_of, 1};
-  sc.n_allowed = n_allowed_min;
-  sc.fcount = (unsigned*)((char*)workspace + aw.total);      // the counts: behind the asynchronous workspace
-  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+  return chain_entry(__func__, a, id_offset, status, RowRule::bitmaps(allow_bits, words_pitch, n_filters, filter_of, n_allowed_min), "", nullptr,
+                     own, "workspace too small (om_sim_topk_filtered_multi_workspace_bytes)");
 }
 
-// The same chain with an exclusion list per query in the bitmaps' place: the drop (drop_excluded_kernel), the count (one word per query
-// behind the asynchronous workspace) and the redo read list q.  pitch == 0 is om_sim_topk_async's chain itself.
+// The same chain with an exclusion list per query in the bitmaps' place: the drop (drop_excluded_kernel), the count and the redo read
+// list q.  pitch == 0 is om_sim_topk_async's chain itself.
 extern "C" size_t om_sim_topk_excluding_workspace_bytes(int64_t n_queries, int d, int k, int64_t pitch) {
-  (void)k; (void)pitch;
+  (void)k;
   if (n_queries <= 0 || d <= 0) return 0;
-  return carve_async(n_queries, d, nullptr).total + align_up((size_t)n_queries * 4, 256);
+  return chain_workspace_bytes(n_queries, d, RowRule::exclusions(nullptr, pitch, n_queries));
 }
 
 extern "C" int om_sim_topk_excluding(int mode, const float* queries, int64_t n_queries, const float* index_f32, const void* index_f16,
@@ -1488,20 +1513,13 @@ extern "C" int om_sim_topk_excluding(int mode, const float* queries, int64_t n_q
                                      void* stream) {
   if (n_queries <= 0) return 0;
   const SearchArgs a = {mode, queries, n_queries, index_f32, index_f16, stats, N, d, k, out_scores, out_ids, workspace, workspace_bytes, stream};
-  Scan sc;
-  AsyncWs aw;
   auto own = [&]() -> const char* {
     if (pitch < 0 || pitch > EXCLUDE_MAX) return "pitch must be in [0, EXCLUDE_MAX = 4096]: the ids of one query's exclusion list (a RowFilter serves longer ones)";
     if (!excl && pitch > 0) return "excl is null: the exclusion table of the call (pitch 0 searches all rows)";
     return nullptr;
   };
-  if (chain_setup(__func__, sc, aw, a, "", nullptr, own, align_up((size_t)n_queries * 4, 256),
-                  "workspace too small (om_sim_topk_excluding_workspace_bytes)")) return 1;
-  if (pitch > 0) {
-    sc.excl = RowExclusions{excl, pitch};
-    sc.fcount = (unsigned*)((char*)workspace + aw.total);      // the counts: behind the asynchronous workspace
-  }
-  return sc.run_async(search_mode_half(mode), aw, id_offset, out_scores, out_ids, status);
+  return chain_entry(__func__, a, id_offset, status, RowRule::exclusions(excl, pitch, n_queries), "", nullptr, own,
+                     "workspace too small (om_sim_topk_excluding_workspace_bytes)");
 }
 
 // ---- om_sim_topk_candidates: the exact top-k of every query over its OWN candidate rows ------------------------------------------------
@@ -1680,6 +1698,33 @@ __global__ void debug_get_lists_kernel(const u64* __restrict__ keys, const unsig
   if (out_state && q == 0 && threadIdx.x < 4) out_state[nq * 4 + threadIdx.x] = flag[threadIdx.x];
 }
 
+// What the three drop hooks share: the caller's lists put in place, the drop under `rule` as the chain launches it (RowRule::drop), the
+// lists read back.  hook: the name refusals fail under; own: the hook's refusal of its other arguments (nullptr: none), reported
+// between the checks of the lists and those of the workspace.
+static int debug_drop_lists(const char* hook, const RowRule& rule, const char* own, int64_t n_queries, int m, const float* scores,
+                            const uint32_t* rows, const uint32_t* counts, int use_qstat, uint32_t nrows, float* out_scores, uint32_t* out_rows,
+                            uint32_t* out_state, void* workspace, size_t workspace_bytes, void* stream) {
+  auto fail = [&](const char* why) { om_set_error(std::string(hook) + ": " + why); return 1; };
+  if (!scores || !rows || !counts) return fail("null argument: scores, rows and counts describe the lists");
+  if (n_queries < 1 || n_queries > 65535) return fail("1 to 65535 queries");
+  if (m < 1 || m > SORT_CAP) return fail("m must be in [1, 8192]");
+  if (own) return fail(own);
+  if (!workspace || ((uintptr_t)workspace & 255)) return fail("workspace must be 256-byte aligned");
+  const SearchWs ws = carve_search(n_queries, 64, (char*)workspace);
+  const AsyncWs aw = carve_async(n_queries, 64, (char*)workspace);
+  if (aw.total > workspace_bytes) return fail("workspace too small (om_sim_topk_async_workspace_bytes(n_queries, 64, 1))");
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned nq = (unsigned)n_queries;
+  hipLaunchKernelGGL(debug_put_lists_kernel, dim3(nq), dim3(256), 0, s, scores, rows, counts, (const float*)nullptr, m, ws.keys, ws.cnt,
+                     ws.cnt_prev, ws.thr, ws.margin, ws.flag, aw.qstat);
+  OM_LAUNCH_CHECK();
+  if (rule.drop(ws, n_queries, nrows, use_qstat ? aw.qstat : nullptr, s)) return 1;
+  hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
+                     out_rows, out_state);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int om_debug_select_lists(int op, int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts, int k,
                                      const float* margin, int use_qstat, int cap, const uint32_t* allow, uint32_t nrows, const float* S,
                                      int64_t ldS, int n, uint32_t row_base, uint32_t cover, int64_t id_offset, float* emit_scores,
@@ -1687,12 +1732,16 @@ extern "C" int om_debug_select_lists(int op, int64_t n_queries, int m, const flo
                                      size_t workspace_bytes, void* stream) {
   if (op < OM_DEBUG_LISTS_RADIX || op > OM_DEBUG_LISTS_EMIT)
     OM_FAIL("op must be 0 (radix selection), 1 (sorting selection), 2 (drop), 3 (dense append + overflow check) or 4 (emit)");
+  const char* const k_refusal = k < 1 || k > K_MAX ? "k must be in [1, 2048]" : nullptr;
+  if (op == OM_DEBUG_LISTS_DROP)      // the one bitmap of om_sim_topk_filtered
+    return debug_drop_lists(__func__, RowRule::bitmap(allow, 0),
+                            k_refusal ? k_refusal : !allow || nrows < 1 ? "the drop needs the bitmap (null argument) and nrows >= 1" : nullptr,
+                            n_queries, m, scores, rows, counts, use_qstat, nrows, out_scores, out_rows, out_state, workspace, workspace_bytes, stream);
   if (!scores || !rows || !counts) OM_FAIL("null argument: scores, rows and counts describe the lists");
   if (n_queries < 1 || n_queries > 65535) OM_FAIL("1 to 65535 queries");
   if (m < 1 || m > SORT_CAP) OM_FAIL("m must be in [1, 8192]");
-  if (k < 1 || k > K_MAX) OM_FAIL("k must be in [1, 2048]");
+  if (k_refusal) OM_FAIL(k_refusal);
   if (op == OM_DEBUG_LISTS_RADIX && cap != 4096 && cap != SORT_CAP) OM_FAIL("cap must be 4096 or 8192");
-  if (op == OM_DEBUG_LISTS_DROP && (!allow || nrows < 1)) OM_FAIL("the drop needs the bitmap (null argument) and nrows >= 1");
   if (op == OM_DEBUG_LISTS_APPEND && (!S || n < 1 || n > DENSE_CHUNK || ldS < n)) OM_FAIL("the dense append needs S (null argument), n in [1, 4096] and ldS >= n");
   if (op == OM_DEBUG_LISTS_EMIT && (!emit_scores || !emit_ids)) OM_FAIL("null argument: emit writes emit_scores and emit_ids");
   if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
@@ -1716,9 +1765,6 @@ extern "C" int om_debug_select_lists(int op, int64_t n_queries, int m, const flo
       hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(SORT_THREADS), SORT_CAP * 8 + 16, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, mg, k, ws.flag,
                          qstat);
       break;
-    case OM_DEBUG_LISTS_DROP:
-      hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowFilters{allow, 0, 1, nullptr, 0}, nrows, ws.flag, qstat);
-      break;
     case OM_DEBUG_LISTS_APPEND:
       hipLaunchKernelGGL(append_dense_kernel, dim3(nq), dim3(256), 0, s, S, ldS, n, row_base, ws.keys, ws.cnt);
       OM_LAUNCH_CHECK();
@@ -1740,56 +1786,24 @@ extern "C" int om_debug_drop_lists_multi(int64_t n_queries, int m, const float* 
                                          const uint32_t* allow, uint32_t nrows, int64_t words_pitch, int64_t n_filters, const int32_t* filter_of,
                                          float* out_scores, uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-  if (!scores || !rows || !counts) OM_FAIL("null argument: scores, rows and counts describe the lists");
-  if (n_queries < 1 || n_queries > 65535) OM_FAIL("1 to 65535 queries");
-  if (m < 1 || m > SORT_CAP) OM_FAIL("m must be in [1, 8192]");
-  if (!allow || nrows < 1) OM_FAIL("the drop needs the bitmaps (allow is null) and nrows >= 1");
-  if (n_filters < 1) OM_FAIL("n_filters must be at least 1");
-  if (words_pitch < ((int64_t)nrows + 31) / 32) OM_FAIL("words_pitch is below (nrows + 31) / 32, the words of one bitmap");
-  if (!filter_of && n_filters != n_queries) OM_FAIL("filter_of is null: query q is under bitmap q, which needs n_filters == n_queries");
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  const SearchWs ws = carve_search(n_queries, 64, (char*)workspace);
-  const AsyncWs aw = carve_async(n_queries, 64, (char*)workspace);
-  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes(n_queries, 64, 1))");
-  const hipStream_t s = (hipStream_t)stream;
-  const unsigned nq = (unsigned)n_queries;
-  hipLaunchKernelGGL(debug_put_lists_kernel, dim3(nq), dim3(256), 0, s, scores, rows, counts, (const float*)nullptr, m, ws.keys, ws.cnt,
-                     ws.cnt_prev, ws.thr, ws.margin, ws.flag, aw.qstat);
-  OM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(drop_disallowed_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowFilters{allow, words_pitch, n_filters, filter_of, 1},
-                     nrows, ws.flag, use_qstat ? aw.qstat : (unsigned*)nullptr);
-  OM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
-                     out_rows, out_state);
-  OM_LAUNCH_CHECK();
-  return 0;
+  const char* const own = !allow || nrows < 1                           ? "the drop needs the bitmaps (allow is null) and nrows >= 1"
+                          : n_filters < 1                               ? "n_filters must be at least 1"
+                          : words_pitch < ((int64_t)nrows + 31) / 32    ? "words_pitch is below (nrows + 31) / 32, the words of one bitmap"
+                          : !filter_of && n_filters != n_queries        ? "filter_of is null: query q is under bitmap q, which needs n_filters == n_queries"
+                                                                        : nullptr;
+  return debug_drop_lists(__func__, RowRule::bitmaps(allow, words_pitch, n_filters, filter_of, 0), own, n_queries, m, scores, rows, counts,
+                          use_qstat, nrows, out_scores, out_rows, out_state, workspace, workspace_bytes, stream);
 }
 
 // The drop under the exclusion lists of om_sim_topk_excluding: drop_excluded_kernel as that entry launches it
 extern "C" int om_debug_drop_lists_excluding(int64_t n_queries, int m, const float* scores, const uint32_t* rows, const uint32_t* counts,
                                              int use_qstat, const int32_t* excl, int64_t pitch, uint32_t nrows, float* out_scores,
                                              uint32_t* out_rows, uint32_t* out_state, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!scores || !rows || !counts) OM_FAIL("null argument: scores, rows and counts describe the lists");
-  if (n_queries < 1 || n_queries > 65535) OM_FAIL("1 to 65535 queries");
-  if (m < 1 || m > SORT_CAP) OM_FAIL("m must be in [1, 8192]");
-  if (!excl || nrows < 1) OM_FAIL("the drop needs the exclusion table (excl is null) and nrows >= 1");
-  if (pitch < 1 || pitch > EXCLUDE_MAX) OM_FAIL("pitch must be in [1, EXCLUDE_MAX = 4096]");
-  if (!workspace || ((uintptr_t)workspace & 255)) OM_FAIL("workspace must be 256-byte aligned");
-  const SearchWs ws = carve_search(n_queries, 64, (char*)workspace);
-  const AsyncWs aw = carve_async(n_queries, 64, (char*)workspace);
-  if (aw.total > workspace_bytes) OM_FAIL("workspace too small (om_sim_topk_async_workspace_bytes(n_queries, 64, 1))");
-  const hipStream_t s = (hipStream_t)stream;
-  const unsigned nq = (unsigned)n_queries;
-  hipLaunchKernelGGL(debug_put_lists_kernel, dim3(nq), dim3(256), 0, s, scores, rows, counts, (const float*)nullptr, m, ws.keys, ws.cnt,
-                     ws.cnt_prev, ws.thr, ws.margin, ws.flag, aw.qstat);
-  OM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(drop_excluded_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, RowExclusions{excl, pitch}, nrows, ws.flag,
-                     use_qstat ? aw.qstat : (unsigned*)nullptr);
-  OM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(debug_get_lists_kernel, dim3(nq), dim3(256), 0, s, ws.keys, ws.cnt, ws.cnt_prev, ws.thr, ws.flag, aw.qstat, out_scores,
-                     out_rows, out_state);
-  OM_LAUNCH_CHECK();
-  return 0;
+  const char* const own = !excl || nrows < 1                  ? "the drop needs the exclusion table (excl is null) and nrows >= 1"
+                          : pitch < 1 || pitch > EXCLUDE_MAX  ? "pitch must be in [1, EXCLUDE_MAX = 4096]"
+                                                              : nullptr;
+  return debug_drop_lists(__func__, RowRule::exclusions(excl, pitch, n_queries), own, n_queries, m, scores, rows, counts, use_qstat, nrows,
+                          out_scores, out_rows, out_state, workspace, workspace_bytes, stream);
 }
 
 extern "C" int om_debug_query_prep(const float* queries, int64_t n_queries, int d, const float* stats, void* out_q16, float* out_margin,

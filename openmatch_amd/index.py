@@ -214,6 +214,17 @@ def prepare_exclusions(excl, ntotal: int, device=None):
     return torch.where(c >= big, torch.full_like(c, -1), c).to(torch.int32).contiguous()
 
 
+def _as_queries(x):
+    """What the faiss-style methods take: a numpy array becomes a float32 CPU tensor, a tensor stays as it is."""
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
+
+
+def _no_hits(D, I):
+    """The result of a search that can return no row, padded as faiss pads."""
+    D.fill_(torch.finfo(torch.float32).min)
+    I.fill_(-1)
+
+
 class RowFilter:
     """The rows of one index a filtered search may return: a bitmap over [0, ntotal) shared by all queries of a call.
     allowed: a bool mask [ntotal], or a tensor / array / sequence of row ids (`invert=True`: the ids are an exclusion list).
@@ -435,32 +446,43 @@ class FlatIPIndex:
         q, D, I, mode = self._search_args(queries, k)
         return SearchHandle(D, I, q, self._enqueue(q, D, I, mode, k, self._f32, self._f16, self.ntotal, id_offset), self.device)
 
+    def _enqueue_chunks(self, nq, nbytes_of, call, status=True):
+        """The loop of every stream-ordered entry: `nq` queries in chunks of at most 32 768 (an entry takes 65 535), on the index's device.
+        Per chunk: nbytes_of(n) bytes of 256-aligned workspace, 8 zeroed status words for the entries that report through them, and
+        call(rows, n, ws, nbytes, status) -- the native entry over queries `rows` (a slice), its return code checked.  Returns what a
+        handle keeps alive: the (workspace, status) pairs, or the workspaces alone."""
+        keep = []
+        with torch.cuda.device(self.device):
+            for s in range(0, nq, 32768):
+                n = min(32768, nq - s)
+                nbytes = nbytes_of(n)
+                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
+                ws = N.c_void_p(buf.data_ptr() + (-buf.data_ptr()) % 256)
+                st = torch.zeros(8, dtype=torch.int64, device=self.device) if status else None
+                N.check(call(slice(s, s + n), n, ws, nbytes, st))
+                keep.append((buf, st) if status else buf)
+        return keep
+
+    def _waited(self, h):
+        """A search in flight, waited for: `last_search_info` from the handle, (D, I) on the GPU."""
+        self.last_search_info = h.info()
+        return h.D, h.I
+
+    def _planes(self, lo, hi):
+        """Rows [lo, hi) of the float32 and the float16 plane (None where the index has no such plane)."""
+        return tuple(None if plane is None else plane[lo:hi] for plane in (self._f32, self._f16))
+
     def _enqueue(self, q, D, I, mode, k, f32, f16, nrows, id_offset, words=None, n_allowed=0):
         """The stream-ordered chain over rows [0, nrows) of the planes `f32` / `f16`, in chunks of at most 32 768 queries: om_sim_topk_async,
         or with `words` (the bitmap over those rows) om_sim_topk_filtered.  Returns the (workspace, status) pairs a handle keeps alive."""
-        nq = q.shape[0]
         lib = N.lib()
-        step = 32768
-        chunks = []
-        with torch.cuda.device(self.device):
-            for s in range(0, nq, step):
-                n = min(step, nq - s)
-                nbytes = lib.om_sim_topk_async_workspace_bytes(n, self.dpad, k) if words is None else lib.om_sim_topk_filtered_workspace_bytes(n, self.dpad, k)
-                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
-                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
-                status = torch.zeros(8, dtype=torch.int64, device=self.device)
-                if words is None:
-                    N.check(lib.om_sim_topk_async(mode, N.ptr(q[s:s + n]), n, N.ptr(f32), N.ptr(f16),
-                                                  N.ptr(self._stats), nrows, self.dpad, k, int(id_offset),
-                                                  N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
-                                                  N.stream_ptr(self.device)))
-                else:
-                    N.check(lib.om_sim_topk_filtered(mode, N.ptr(q[s:s + n]), n, N.ptr(f32), N.ptr(f16),
-                                                     N.ptr(self._stats), nrows, self.dpad, k, int(id_offset), N.ptr(words), int(n_allowed),
-                                                     N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
-                                                     N.stream_ptr(self.device)))
-                chunks.append((buf, status))
-        return chunks
+        entry, nbytes_of, own = ((lib.om_sim_topk_async, lib.om_sim_topk_async_workspace_bytes, ()) if words is None else
+                                 (lib.om_sim_topk_filtered, lib.om_sim_topk_filtered_workspace_bytes, (N.ptr(words), int(n_allowed))))
+
+        def call(rows, n, ws, nbytes, status):
+            return entry(mode, N.ptr(q[rows]), n, N.ptr(f32), N.ptr(f16), N.ptr(self._stats), nrows, self.dpad, k, int(id_offset), *own,
+                         N.ptr(D[rows]), N.ptr(I[rows]), N.ptr(status), ws, nbytes, N.stream_ptr(self.device))
+        return self._enqueue_chunks(q.shape[0], lambda n: nbytes_of(n, self.dpad, k), call)
 
     # -- filtered search ---------------------------------------------------------------------
     def search_device_filtered_async(self, queries: torch.Tensor, k: int, row_filter: "RowFilter", id_offset: int = 0, route=None):
@@ -479,16 +501,14 @@ class FlatIPIndex:
         way = filter_route(self.precision, k, rf.first, rf.last, rf.n_allowed, route)
         extra = {"route": way, "n_allowed": rf.n_allowed, "_filter": rf}
         if way == "empty" or q.shape[0] == 0:
-            D.fill_(torch.finfo(torch.float32).min)
-            I.fill_(-1)
+            _no_hits(D, I)
             return SearchHandle(D, I, q, [], self.device, extra)
-        cut = lambda plane, lo, hi: None if plane is None else plane[lo:hi]
         if way == "range":                 # a slice of the planes is an index: the unfiltered chain, ids shifted by the slice's first row
             lo, hi = rf.first, rf.last + 1
-            chunks = self._enqueue(q, D, I, mode, k, cut(self._f32, lo, hi), cut(self._f16, lo, hi), hi - lo, int(id_offset) + lo)
+            chunks = self._enqueue(q, D, I, mode, k, *self._planes(lo, hi), hi - lo, int(id_offset) + lo)
         elif way == "scan":                # the bitmap's word of row lo is whole: lo is a multiple of 256
             lo, hi = rf.first // 256 * 256, rf.last + 1
-            chunks = self._enqueue(q, D, I, mode, k, cut(self._f32, lo, hi), cut(self._f16, lo, hi), hi - lo, int(id_offset) + lo,
+            chunks = self._enqueue(q, D, I, mode, k, *self._planes(lo, hi), hi - lo, int(id_offset) + lo,
                                    words=rf.words[lo // 32:], n_allowed=rf.n_allowed)
         else:
             ids, sub = self._gathered(rf)
@@ -514,14 +534,11 @@ class FlatIPIndex:
     def search_device_filtered(self, queries: torch.Tensor, k: int, row_filter: "RowFilter", id_offset: int = 0, route=None):
         """`search_device_filtered_async`, waited for: (D [Q,k] f32, I [Q,k] int64) on the GPU, and `last_search_info` with `route`,
         `n_allowed` and `redone`."""
-        h = self.search_device_filtered_async(queries, k, row_filter, id_offset=id_offset, route=route)
-        self.last_search_info = h.info()
-        return h.D, h.I
+        return self._waited(self.search_device_filtered_async(queries, k, row_filter, id_offset=id_offset, route=route))
 
     def search_filtered(self, x, k: int, row_filter: "RowFilter"):
         """faiss-style, as `search`: numpy in, (D, I) numpy out."""
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
-        D, I = self.search_device_filtered(q, k, row_filter)
+        D, I = self.search_device_filtered(_as_queries(x), k, row_filter)
         return D.cpu().numpy(), I.cpu().numpy()
 
     # -- candidate lists: every query scored over its own rows --------------------------------
@@ -529,26 +546,18 @@ class FlatIPIndex:
         """om_sim_topk_candidates over `cand` (int32 [Q, C] on the device, distinct rows per query, holes -1), in chunks of at most 32 768
         queries.  Returns the workspaces a handle keeps alive."""
         lib = N.lib()
-        step = 32768
         if cand.dtype != torch.int32 or cand.device != self.device or cand.shape[0] != q.shape[0]:
             raise ValueError("candidates must be int32 [Q, C] on the index's device")
         cand = cand.contiguous()
-        keep = [cand]
         if cand.shape[1] == 0 or self.ntotal == 0:
-            D.fill_(torch.finfo(torch.float32).min)
-            I.fill_(-1)
-            return keep
-        with torch.cuda.device(self.device):
-            for s in range(0, q.shape[0], step):
-                n = min(step, q.shape[0] - s)
-                nbytes = lib.om_sim_topk_candidates_workspace_bytes(n, self.dpad, k)
-                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
-                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
-                N.check(lib.om_sim_topk_candidates(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16), self.ntotal, self.dpad, k,
-                                                   int(id_offset), N.ptr(cand[s:s + n]), cand.shape[1], N.ptr(D[s:s + n]), N.ptr(I[s:s + n]),
-                                                   N.c_void_p(ws), nbytes, N.stream_ptr(self.device)))
-                keep.append(buf)
-        return keep
+            _no_hits(D, I)
+            return [cand]
+
+        def call(rows, n, ws, nbytes, _status):
+            return lib.om_sim_topk_candidates(mode, N.ptr(q[rows]), n, N.ptr(self._f32), N.ptr(self._f16), self.ntotal, self.dpad, k,
+                                              int(id_offset), N.ptr(cand[rows]), cand.shape[1], N.ptr(D[rows]), N.ptr(I[rows]), ws, nbytes,
+                                              N.stream_ptr(self.device))
+        return [cand] + self._enqueue_chunks(q.shape[0], lambda n: lib.om_sim_topk_candidates_workspace_bytes(n, self.dpad, k), call, status=False)
 
     def search_device_candidates_async(self, queries: torch.Tensor, k: int, cand, id_offset: int = 0):
         """The exact top-k of query q over ITS OWN candidate rows `cand[q]` (an int tensor or array [Q, C], padded with -1), stream-ordered:
@@ -579,14 +588,11 @@ class FlatIPIndex:
 
     def search_device_candidates(self, queries: torch.Tensor, k: int, cand, id_offset: int = 0):
         """`search_device_candidates_async`, waited for: (D, I) on the GPU, and `last_search_info`."""
-        h = self.search_device_candidates_async(queries, k, cand, id_offset=id_offset)
-        self.last_search_info = h.info()
-        return h.D, h.I
+        return self._waited(self.search_device_candidates_async(queries, k, cand, id_offset=id_offset))
 
     def search_candidates(self, x, k: int, cand):
         """faiss-style, as `search`: numpy in, (D, I) numpy out."""
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
-        D, I = self.search_device_candidates(q, k, cand)
+        D, I = self.search_device_candidates(_as_queries(x), k, cand)
         return D.cpu().numpy(), I.cpu().numpy()
 
     # -- exclusion lists: every row but a few that differ per query ----------------------------
@@ -594,25 +600,16 @@ class FlatIPIndex:
         """om_sim_topk_excluding over all rows under `table` (int32 [Q, pitch] on the device, as `prepare_exclusions` leaves it), in
         chunks of at most 32 768 queries.  Returns the (workspace, status) pairs a handle keeps alive."""
         lib = N.lib()
-        step = 32768
-        chunks = []
         if table.dtype != torch.int32 or table.device != self.device or table.dim() != 2 or table.shape[0] != q.shape[0]:
             raise ValueError("the exclusion table must be int32 [Q, pitch] on the index's device")
         table = table.contiguous()
         pitch = int(table.shape[1])
-        with torch.cuda.device(self.device):
-            for s in range(0, q.shape[0], step):
-                n = min(step, q.shape[0] - s)
-                nbytes = lib.om_sim_topk_excluding_workspace_bytes(n, self.dpad, k, pitch)
-                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
-                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
-                status = torch.zeros(8, dtype=torch.int64, device=self.device)
-                N.check(lib.om_sim_topk_excluding(mode, N.ptr(q[s:s + n]), n, N.ptr(self._f32), N.ptr(self._f16), N.ptr(self._stats), self.ntotal,
-                                                  self.dpad, k, int(id_offset), N.ptr(table[s:s + n]) if pitch else None, pitch,
-                                                  N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws), nbytes,
-                                                  N.stream_ptr(self.device)))
-                chunks.append((buf, status))
-        return chunks
+
+        def call(rows, n, ws, nbytes, status):
+            return lib.om_sim_topk_excluding(mode, N.ptr(q[rows]), n, N.ptr(self._f32), N.ptr(self._f16), N.ptr(self._stats), self.ntotal,
+                                             self.dpad, k, int(id_offset), N.ptr(table[rows]) if pitch else None, pitch, N.ptr(D[rows]),
+                                             N.ptr(I[rows]), N.ptr(status), ws, nbytes, N.stream_ptr(self.device))
+        return self._enqueue_chunks(q.shape[0], lambda n: lib.om_sim_topk_excluding_workspace_bytes(n, self.dpad, k, pitch), call)
 
     def search_device_excluding_async(self, queries: torch.Tensor, k: int, excl, id_offset: int = 0):
         """The exact top-k of query q over every row but those of ITS OWN exclusion list `excl[q]`, stream-ordered: per query what an index
@@ -633,14 +630,11 @@ class FlatIPIndex:
 
     def search_device_excluding(self, queries: torch.Tensor, k: int, excl, id_offset: int = 0):
         """`search_device_excluding_async`, waited for: (D, I) on the GPU, and `last_search_info` with `route`, `pitch` and `redone`."""
-        h = self.search_device_excluding_async(queries, k, excl, id_offset=id_offset)
-        self.last_search_info = h.info()
-        return h.D, h.I
+        return self._waited(self.search_device_excluding_async(queries, k, excl, id_offset=id_offset))
 
     def search_excluding(self, x, k: int, excl):
         """faiss-style, as `search`: numpy in, (D, I) numpy out."""
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
-        D, I = self.search_device_excluding(q, k, excl)
+        D, I = self.search_device_excluding(_as_queries(x), k, excl)
         return D.cpu().numpy(), I.cpu().numpy()
 
     # -- a filter per query --------------------------------------------------------------------
@@ -741,7 +735,6 @@ class FlatIPIndex:
             return h
         if nq == 0:
             return MultiSearchHandle(D, I, q, [], self.device)
-        cut = lambda plane, lo, hi: None if plane is None else plane[lo:hi]
         qp = q if plan["identity"] else q.index_select(0, plan["order"])
         Dp, Ip = (D, I) if plan["identity"] else (torch.empty_like(D), torch.empty_like(I))
         handles = []
@@ -750,8 +743,8 @@ class FlatIPIndex:
             qs, Ds, Is = qp[s:s + n], Dp[s:s + n], Ip[s:s + n]
             if part["route"] == "scan":
                 lo, hi = part["rows"]
-                h = SearchHandle(Ds, Is, qs, self._enqueue_multi(qs, Ds, Is, mode, k, cut(self._f32, lo, hi), cut(self._f16, lo, hi), hi - lo,
-                                                                 int(id_offset) + lo, part["words"], part["filter_of"], part["n_allowed_min"]),
+                h = SearchHandle(Ds, Is, qs, self._enqueue_multi(qs, Ds, Is, mode, k, *self._planes(lo, hi), hi - lo, int(id_offset) + lo,
+                                                                 part["words"], part["filter_of"], part["n_allowed_min"]),
                                  self.device)
                 n_filters = len(part["groups"])
             elif part["route"] == "candidates":
@@ -773,40 +766,27 @@ class FlatIPIndex:
         """om_sim_topk_filtered_multi over rows [0, nrows) of the planes: `words` [F, pitch] int32 bitmaps over those rows, `filter_of`
         int32 [Q] on the device (None: F == Q <= 32 768 and query q is under bitmap q).  Chunks of at most 32 768 queries; returns the (workspace, status) pairs a handle keeps alive."""
         lib = N.lib()
-        step = 32768
-        chunks = []
         n_filters, pitch = words.shape
-        with torch.cuda.device(self.device):
-            for s in range(0, q.shape[0], step):
-                n = min(step, q.shape[0] - s)
-                nbytes = lib.om_sim_topk_filtered_multi_workspace_bytes(n, self.dpad, k, n_filters)
-                buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
-                ws = buf.data_ptr() + (-buf.data_ptr()) % 256
-                status = torch.zeros(8, dtype=torch.int64, device=self.device)
-                N.check(lib.om_sim_topk_filtered_multi(mode, N.ptr(q[s:s + n]), n, N.ptr(f32), N.ptr(f16), N.ptr(self._stats), nrows, self.dpad, k,
-                                                       int(id_offset), N.ptr(words), pitch, n_filters,
-                                                       N.ptr(None if filter_of is None else filter_of[s:s + n]),
-                                                       int(n_allowed_min), N.ptr(D[s:s + n]), N.ptr(I[s:s + n]), N.ptr(status), N.c_void_p(ws),
-                                                       nbytes, N.stream_ptr(self.device)))
-                chunks.append((buf, status))
-        return chunks
+
+        def call(rows, n, ws, nbytes, status):
+            return lib.om_sim_topk_filtered_multi(mode, N.ptr(q[rows]), n, N.ptr(f32), N.ptr(f16), N.ptr(self._stats), nrows, self.dpad, k,
+                                                  int(id_offset), N.ptr(words), pitch, n_filters,
+                                                  N.ptr(None if filter_of is None else filter_of[rows]), int(n_allowed_min), N.ptr(D[rows]),
+                                                  N.ptr(I[rows]), N.ptr(status), ws, nbytes, N.stream_ptr(self.device))
+        return self._enqueue_chunks(q.shape[0], lambda n: lib.om_sim_topk_filtered_multi_workspace_bytes(n, self.dpad, k, n_filters), call)
 
     def search_device_filtered_multi(self, queries: torch.Tensor, k: int, filters, filter_of=None, id_offset: int = 0, route=None):
         """`search_device_filtered_multi_async`, waited for: (D, I) on the GPU, and `last_search_info` with `parts` and `redone`."""
-        h = self.search_device_filtered_multi_async(queries, k, filters, filter_of=filter_of, id_offset=id_offset, route=route)
-        self.last_search_info = h.info()
-        return h.D, h.I
+        return self._waited(self.search_device_filtered_multi_async(queries, k, filters, filter_of=filter_of, id_offset=id_offset, route=route))
 
     def search_filtered_multi(self, x, k: int, filters, filter_of=None):
         """faiss-style, as `search`: numpy in, (D, I) numpy out."""
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
-        D, I = self.search_device_filtered_multi(q, k, filters, filter_of=filter_of)
+        D, I = self.search_device_filtered_multi(_as_queries(x), k, filters, filter_of=filter_of)
         return D.cpu().numpy(), I.cpu().numpy()
 
     def search(self, x, k: int):
         """faiss-style: numpy in, (D, I) numpy out, I = insertion indices, -1 padded."""
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
-        D, I = self.search_device(q, k)
+        D, I = self.search_device(_as_queries(x), k)
         return D.cpu().numpy(), I.cpu().numpy()
 
 
